@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- AMP-Net hot path on MI355X: synthetic ALS windows of 2048 points x 9 features.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode fwd|train] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode fwd|train|fps] [--batch B] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch resident in HBM:
   fwd   (BASELINE.json configs[1]): AMP-Net forward, eval mode, fp32, B=32 samples x W=9 windows x N=2048 points
@@ -10,8 +10,13 @@ One "step" = one pass of the hot path over one batch resident in HBM:
 For N > 1 the driver launches one rank per GPU (torch.distributed, backend nccl = RCCL); every rank processes
 its own batch (data parallel, weak scaling); in train mode gradients are all-reduced.
 Rank 0 prints ONE JSON line.  `value` = points/s over all ranks, inputs resident in HBM before the timed region.
-The roofline object comes from a SECOND pass of the same K steps with HIP events around every kernel launch
-(ampnet_profile_*), so that event recording does not sit inside the throughput number; both times are printed.
+A plain run sets up, warms up, times the K steps and prints the headline line, nothing else.  --full adds what the line
+carried before that split: the self-check against tests/golden/bench_pin.json, the eval-forward ms/window of a train run,
+the other precision modes, the data-parallel legs, the informational legs (loader, inference, FPS, k-means), the CPU
+baseline, and the roofline object, which comes from a SECOND pass of the same K steps with HIP events around every kernel
+launch (ampnet_profile_*), so that event recording does not sit inside the throughput number; both times are printed.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (same inputs on every run with the same
+arguments), so that two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -37,6 +42,46 @@ N_POINTS, N_WIN = 2048, 9
 
 def sub(name=""):
     return importlib.import_module(PKG + ("." + name if name else ""))
+
+
+DUMP_LIMIT_BYTES = 60_000_000     # array data of one --dump-outputs directory: the .npy headers keep the files under 64 MB
+
+
+def step_outputs(out, models=()):
+    """Host copies of what a caller of the timed path receives from one step: every tensor of the returned dict (tuples as
+    <key>_<i>; `targets_pc` only echoes the input), and for each (name, module) in `models` its floating-point state_dict
+    entries, flattened and concatenated in state_dict order (in train mode: the parameters and BatchNorm statistics the step
+    left behind).  Call it before any later step can reuse the step's buffers."""
+    arrays = {}
+    for k, v in out.items():
+        if k == "targets_pc":
+            continue
+        if isinstance(v, torch.Tensor):
+            arrays[k] = v.detach().cpu().numpy()
+        elif isinstance(v, (tuple, list)):
+            arrays.update({f"{k}_{i}": t.detach().cpu().numpy() for i, t in enumerate(v) if isinstance(t, torch.Tensor)})
+    for name, mod in models:
+        arrays[name + "_state"] = torch.cat([t.detach().reshape(-1).float().cpu() for t in mod.state_dict().values()
+                                             if t.is_floating_point()]).numpy()
+    return arrays
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array: float32 stays float32, every other dtype becomes float64 (exact for the integer outputs).
+    When the arrays exceed `limit` bytes in all, the largest ones are cut to a fixed, seeded sample of their flattened elements
+    (sorted indices, the same on every run) so that two builds still compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    left, n_left = limit, len(arrays)
+    for name in sorted(arrays, key=lambda k: (arrays[k].nbytes, k)):
+        a = arrays[name]
+        share = left // n_left
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        n_left -= 1
 
 
 def build_models(device, train):
@@ -211,11 +256,12 @@ def cpu_baseline(mode, budget_s=20.0):
     return out
 
 
-def fps_leg(dev, B, steps, warmup, seed, cpu_baseline_s=0.0):
+def fps_leg(dev, B, steps, warmup, seed, cpu_baseline_s=0.0, knn=True):
     """BASELINE.json configs[4] on one GPU: farthest-point sampling, B clouds x 8192 points -> 4096 samples
-    (data_proc/sample_fps.py:23-31 sizes) and the build-defined k-NN grouping (k = 32) of those centres.
+    (data_proc/sample_fps.py:23-31 sizes) and (knn) the build-defined k-NN grouping (k = 32) of those centres.
     Roofline accounting: 16 B per (candidate, round) = 12 B xyz + 4 B running minimum; the cloud is
-    register-resident, so the true HBM traffic is the floor B*(N*12 + S*4) bytes (PMC: profiles/)."""
+    register-resident, so the true HBM traffic is the floor B*(N*12 + S*4) bytes (PMC: profiles/).
+    Returns (the leg's dict, the indices of the last timed FPS call)."""
     synth = sub("synthetic")
     U = sub("utils.utils")
     N, S, K = 8192, 4096, 32
@@ -230,16 +276,17 @@ def fps_leg(dev, B, steps, warmup, seed, cpu_baseline_s=0.0):
     ev1.record()
     torch.cuda.synchronize(dev)
     fps_ms = ev0.elapsed_time(ev1) / steps                     # the kernel runs on torch's current stream
-    for _ in range(2):
-        U.knn_indices(xyz, idx, K)
-    torch.cuda.synchronize(dev)
-    ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev2.record()
-    for _ in range(steps):
-        U.knn_indices(xyz, idx, K)
-    ev3.record()
-    torch.cuda.synchronize(dev)
-    knn_ms = ev2.elapsed_time(ev3) / steps
+    if knn:
+        for _ in range(2):
+            U.knn_indices(xyz, idx, K)
+        torch.cuda.synchronize(dev)
+        ev2, ev3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev2.record()
+        for _ in range(steps):
+            U.knn_indices(xyz, idx, K)
+        ev3.record()
+        torch.cuda.synchronize(dev)
+        knn_ms = ev2.elapsed_time(ev3) / steps
     ach = float(B) * S * N * 16 / (fps_ms * 1e-3) / 1e9
     # What binds a resident cloud is the DEPENDENT ROUND on the one CU it lives on, not HBM (PMC: ~2 MB of traffic per launch against
     # 8.59 GB "algorithmic"): the roof is the VALU issue floor of a round's update -- 512 threads x 16 points, 8 packed instructions per PAIR
@@ -259,10 +306,11 @@ def fps_leg(dev, B, steps, warmup, seed, cpu_baseline_s=0.0):
                         "hbm_accounting_8d": {"achieved": round(ach, 1), "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": round(ach / PEAK_HBM_GBPS, 4),
                                               "note": "SURVEY 8(d): 16 B per (candidate, round); the cloud is register / LDS resident, so these bytes never "
                                                       "reach HBM (true traffic = B*(N*12+S*4)): kept for continuity, not the binding roof"},
-                        "note": "throughput comes from many clouds at once (fps.many_clouds): 256 clouds fill the chip at the same time per round"},
-           "knn": {"k": K, "ms": round(knn_ms, 4), "centres_per_s": round(B * S / (knn_ms * 1e-3), 1),
-                   "achieved_GBps": round(float(B) * S * N * 12 / (knn_ms * 1e-3) / 1e9, 1), "traffic": pmc_traffic_for("knn_kernel", B * N),
-                   "note": "build-defined exact k-NN (the reference has none); algorithmic 12 B per (candidate, centre), served from LDS"}}
+                        "note": "throughput comes from many clouds at once (fps.many_clouds): 256 clouds fill the chip at the same time per round"}}
+    if knn:
+        out["knn"] = {"k": K, "ms": round(knn_ms, 4), "centres_per_s": round(B * S / (knn_ms * 1e-3), 1),
+                      "achieved_GBps": round(float(B) * S * N * 12 / (knn_ms * 1e-3) / 1e9, 1), "traffic": pmc_traffic_for("knn_kernel", B * N),
+                      "note": "build-defined exact k-NN (the reference has none); algorithmic 12 B per (candidate, centre), served from LDS"}
     if cpu_baseline_s > 0:
         from oracle import fps_oracle
         pc = synth.clouds(seed, 1, N)[0]
@@ -274,7 +322,7 @@ def fps_leg(dev, B, steps, warmup, seed, cpu_baseline_s=0.0):
         dtc = time.perf_counter() - t1
         out["cpu_baseline"] = {"value": round(n * S / dtc, 1), "unit": "selections/s", "cores": 1, "kind": "port",
                                "sample": f"{n} clouds x {N} -> {S}, oracle/fps_oracle.c (scalar C), {dtc:.1f} s"}
-    return out
+    return out, idx
 
 
 def kmeans_leg(dev, steps):
@@ -381,7 +429,10 @@ def bench_fps(args, dev, rank, world, dist):
     if dist is not None:
         dist.barrier()
     t0 = time.perf_counter()
-    leg = fps_leg(dev, B, args.steps, args.warmup, 200 + rank, 10.0 if (world == 1 and not args.no_cpu_baseline) else 0.0)
+    leg, idx = fps_leg(dev, B, args.steps, args.warmup, 200 + rank, 10.0 if (args.full and world == 1 and not args.no_cpu_baseline) else 0.0,
+                       knn=args.full)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"indices": idx.cpu().numpy()})
     if dist is not None:
         dist.barrier()
     ms = leg["ms"]
@@ -394,7 +445,9 @@ def bench_fps(args, dev, rank, world, dist):
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": leg["workload"] + " per GPU", "parallelism": f"replicas{world}"},
-               "us_per_round": leg["us_per_round"], "roofline": leg["roofline"], "knn": leg["knn"]}
+               "us_per_round": leg["us_per_round"]}
+        if args.full:
+            out.update(roofline=leg["roofline"], knn=leg["knn"])
         if "cpu_baseline" in leg:
             out["cpu_baseline"] = leg["cpu_baseline"]
         print(json.dumps(out), flush=True)
@@ -706,18 +759,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=["fwd", "train", "fps", "auto"], default="auto")
     ap.add_argument("--batch", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the informational legs (train_loop_inclusive, fps)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: self-check, roofline / per-kernel pass, eval-forward "
+                                                        "ms/window, the other precision modes, data-parallel and informational legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                                                                        "(train: + the parameters and statistics it left) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full without the informational legs (train_loop_inclusive, fps, ...)")
     ap.add_argument("--sync-bn", action="store_true", help="N > 1: BatchNorm statistics and loss normalisation over the global batch "
                                                            "(36 more latency-bound collectives per step; default: per-rank statistics)")
-    ap.add_argument("--kernels", type=int, default=8, help="how many kernels to list in the JSON line")
+    ap.add_argument("--kernels", type=int, default=8, help="how many kernels to list in the JSON line (--full)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous check only: no GPU work (tests/test_dp_cpu.py)")
     ap.add_argument("--probe", choices=["syncbn"], default=None, help="internal: child-process probes of the default run")
     ap.add_argument("--precision", choices=["fp32", "bf16", "bf16_train", "bf16_store", "f32x3"], default=os.environ.get("AMPNET_PRECISION", "f32x3"),
                     help="matrix-pipe arithmetic: f32x3 (headline since round 4: fp32 results from three-term bf16 split operands on the MFMA-bound "
-                         "layers, every fp32 parity test passes in it with unchanged bars), fp32 = exact fp32 MFMA everywhere (a leg of the default line), "
+                         "layers, every fp32 parity test passes in it with unchanged bars), fp32 = exact fp32 MFMA everywhere (a leg of the --full line), "
                          "bf16 = forward per-point layers, bf16_train = forward + fused backward (fp32 accumulate), bf16_store = + bf16-stored activations")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.probe == "syncbn":
         return syncbn_probe_child(max(args.steps, 3))
@@ -789,13 +848,13 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    # Self-check (never inside the timed region's clock: device tensors are kept, read after the final synchronisation):
+    # Self-check (--full; never inside the timed region's clock: device tensors are kept, read after the final synchronisation):
     #  * the FIRST step of the fresh modules must reproduce the oracle's loss terms on the same inputs (tests/golden/bench_pin.json,
     #    made by tests/golden/make_bench_pin.py and re-derived on the GPU box by tests/test_fullsize_gpu.py) within 1e-4 relative;
     #  * every timed step's ce / reg must be finite.
     # A failed check prints to stderr and exits non-zero WITHOUT a JSON line.
     losses = []
-    if mode == "fwd":
+    if mode == "fwd" and args.full:
         with torch.no_grad():
             first = S.forward_batch(enc, att, x, t, centd, cw, want_loss=True, want_preds=False)
         first_terms = (first["ce"][:1].clone(), None)
@@ -808,20 +867,51 @@ def main():
             losses.append(torch.stack([out["ce"][0], out["reg"].reshape(-1)[0]]))
         return out
 
+    timed_step = checked_step if args.full else step
     for _ in range(args.warmup):
-        checked_step()
+        timed_step()
     n_warm = len(losses)
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        checked_step()
+        last = timed_step()
     sync()
     dt = time.perf_counter() - t0
-    check = self_check(mode, B, args, rank, world, losses, n_warm, first_terms)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(last, (("encoder", enc), ("head", att)) if mode == "train" else ()))
+    check = self_check(mode, B, args, rank, world, losses, n_warm, first_terms) if args.full else None
     if dist is not None:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    pts_step = B * N_WIN * N_POINTS
+    value = world * pts_step * args.steps / dt
+    flop_pt = 413148 if mode == "fwd" else 1239444
+    headline = {
+        "metric": "train points/sec + forward ms/window (N=2048)" if mode == "train" else "forward points/sec + forward ms/window (N=2048)",
+        "value": round(value, 1), "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": {"fp32": "f32", "bf16": "bf16 forward MFMA operands, f32 accumulate / statistics / backward",
+                                      "bf16_train": "bf16 MFMA operands (forward + fused backward), f32 accumulate / statistics / tensors",
+                                      "bf16_store": "bf16 MFMA operands + bf16 stored activations, f32 accumulate / statistics / gradients",
+                                      "f32x3": "f32 via 3xbf16 split operands (six exact bf16 partial products per product on the MFMA-bound layers), f32 accumulate, f32 tensors"}[args.precision], "data": "synthetic",
+        "config": {"workload": ("AMP-Net full train step (fwd+loss+bwd+2xAdam)" if mode == "train" else "AMP-Net forward only (eval, logits+argmax)")
+                   + f", {B} samples x {N_WIN} windows x {N_POINTS} pts x 9 feats per GPU", "batch_per_gpu": B,
+                   "global_batch": B * world, "parallelism": f"dp{world}",
+                   "batchnorm": ("global batch" if (world > 1 and args.sync_bn) else ("per rank" if world > 1 else "single device"))},
+        "ms_per_window": round(dt / args.steps * 1e3 / (B * N_WIN), 5),
+        # a train run's eval-forward figure takes a pass of its own (--full)
+        "forward_ms_per_window": round(dt / args.steps * 1e3 / (B * N_WIN), 5) if mode == "fwd" else None,
+        "model_tflops": round(value * flop_pt / 1e12, 2),
+        "ranks": world, "backend": ("rccl" if backend == "nccl" else backend),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # second pass with HIP events around every instrumented kernel (rank 0 only needs it, all ranks run it)
     L = sub("_lib").lib()
@@ -943,34 +1033,19 @@ def main():
     if mode == "train" and world == 1 and not args.no_extra_legs:
         incl = train_loop_inclusive(enc, att, trainer_mod, B, dev, max(args.steps // 2, 3))
         epoch_leg = train_att_epoch_leg(enc, att, trainer_mod, B, dev, dt / args.steps * 1e3)
-        fps = fps_leg(dev, 16, max(args.steps // 2, 3), 1, 200, 0.0 if args.no_cpu_baseline else 5.0)
+        fps, _ = fps_leg(dev, 16, max(args.steps // 2, 3), 1, 200, 0.0 if args.no_cpu_baseline else 5.0)
         fps["many_clouds"] = fps_many_leg(dev, args.steps, 210)
         infer = inference_leg(enc, att, dev, args.steps)
         kmeans = kmeans_leg(dev, args.steps)
         dp_probe = syncbn_probe(min(args.steps, 8))
 
     if rank == 0:
-        pts_step = B * N_WIN * N_POINTS
-        value = world * pts_step * args.steps / dt
-        flop_pt = 413148 if mode == "fwd" else 1239444
         out = {
-            "metric": "train points/sec + forward ms/window (N=2048)" if mode == "train" else "forward points/sec + forward ms/window (N=2048)",
-            "value": round(value, 1), "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": {"fp32": "f32", "bf16": "bf16 forward MFMA operands, f32 accumulate / statistics / backward",
-                                          "bf16_train": "bf16 MFMA operands (forward + fused backward), f32 accumulate / statistics / tensors",
-                                          "bf16_store": "bf16 MFMA operands + bf16 stored activations, f32 accumulate / statistics / gradients",
-                                          "f32x3": "f32 via 3xbf16 split operands (six exact bf16 partial products per product on the MFMA-bound layers), f32 accumulate, f32 tensors"}[args.precision], "data": "synthetic",
-            "config": {"workload": ("AMP-Net full train step (fwd+loss+bwd+2xAdam)" if mode == "train" else "AMP-Net forward only (eval, logits+argmax)")
-                       + f", {B} samples x {N_WIN} windows x {N_POINTS} pts x 9 feats per GPU", "batch_per_gpu": B,
-                       "global_batch": B * world, "parallelism": f"dp{world}",
-                       "batchnorm": ("global batch" if (world > 1 and args.sync_bn) else ("per rank" if world > 1 else "single device"))},
-            "ms_per_window": round(dt / args.steps * 1e3 / (B * N_WIN), 5),
+            **headline,
             "forward_ms_per_window": round((fwd_ms if fwd_ms is not None else dt / args.steps * 1e3) / (B * N_WIN), 5),
-            "model_tflops": round(value * flop_pt / 1e12, 2),
             "ms_per_step_with_events": round(dt_prof / args.steps * 1e3, 4),
             "fp32_mfma_mode": fp32_leg, "bf16_forward_mode": bf16_leg, "bf16_train_mode": bf16_train_leg, "bf16_store_mode": bf16_store_leg,
-            "ranks": world, "backend": ("rccl" if backend == "nccl" else backend), "allreduce_ms_per_step": None if ar_ms is None else round(ar_ms, 4),
+            "allreduce_ms_per_step": None if ar_ms is None else round(ar_ms, 4),
             "global_batch_batchnorm_mode": sync_bn_leg,
             "train_loop_inclusive": incl, "train_att_epoch": epoch_leg, "fps": fps, "inference": infer, "kmeans": kmeans, "data_parallel_host_cost": dp_probe,
             "check": check,

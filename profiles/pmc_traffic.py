@@ -2,9 +2,9 @@
 """Turns rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs, --kernel-trace only, as MI355X_MICROARCH.md
 prescribes) into HBM bytes per launch for the kernels bench.py names in its `roofline` object.
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc/FETCH_SIZE -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc/WRITE_SIZE -- python3 bench.py ...
-  python profiles/pmc_traffic.py gpurun_out/pmc/train profiles/pmc_traffic.json [rows] [--fps gpurun_out/pmc/fps]   (tools/run_pmc.sh runs the passes)
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <out>/FETCH_SIZE -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d <out>/WRITE_SIZE -- python3 bench.py --full ...
+  python profiles/pmc_traffic.py <out> profiles/pmc_traffic.json [rows] [--fps <fps out>]   (tools/run_pmc.sh runs the passes)
 
 gfx950 corrections: FETCH_SIZE is in KiB and reports HALF of the bytes of wide coalesced reads (x 2); WRITE_SIZE in KiB
 reads exact.  A bench.py event name such as `pw_gemm<128,128>+pool` is a subset of the launches of one kernel symbol

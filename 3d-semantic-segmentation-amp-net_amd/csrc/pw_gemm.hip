@@ -491,6 +491,8 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
                 // lane conditions these are an exec-mask branch around every pair of elements, stores or not
                 const bool cok = X3 || col < a.cout;
                 const float z0 = STATS ? s_z0[t] : 0.f;
+                // pooled layers track z' = sgn(gamma) z (signed weights): the stored Z is z, so the sign comes back off (exact)
+                const float zs = POOL ? sgn[t] : 1.0f;
                 float *zp = a.Z + (size_t)row0 * a.ldz + col;
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
@@ -499,15 +501,15 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
                     const float d0 = acc[t][e], d1 = acc[t][e + 1];
                     if ((X3 ? !POOL : do_store) && cok) {
                         if (BF && ZBF) {
-                            if (ok0) reinterpret_cast<__bf16 *>(a.Z)[((size_t)row0 + rr0) * a.ldz + col] = (__bf16)(d0 + z0);
-                            if (ok1) reinterpret_cast<__bf16 *>(a.Z)[((size_t)row0 + rr0 + 1) * a.ldz + col] = (__bf16)(d1 + z0);
+                            if (ok0) reinterpret_cast<__bf16 *>(a.Z)[((size_t)row0 + rr0) * a.ldz + col] = (__bf16)(zs * (d0 + z0));
+                            if (ok1) reinterpret_cast<__bf16 *>(a.Z)[((size_t)row0 + rr0 + 1) * a.ldz + col] = (__bf16)(zs * (d1 + z0));
                         } else {
                             if (STREAM) {
-                                if (ok0) st_stream(d0 + z0, &zp[(size_t)rr0 * a.ldz]);
-                                if (ok1) st_stream(d1 + z0, &zp[(size_t)(rr0 + 1) * a.ldz]);
+                                if (ok0) st_stream(zs * (d0 + z0), &zp[(size_t)rr0 * a.ldz]);
+                                if (ok1) st_stream(zs * (d1 + z0), &zp[(size_t)(rr0 + 1) * a.ldz]);
                             } else {
-                                if (ok0) zp[(size_t)rr0 * a.ldz] = d0 + z0;
-                                if (ok1) zp[(size_t)(rr0 + 1) * a.ldz] = d1 + z0;
+                                if (ok0) zp[(size_t)rr0 * a.ldz] = zs * (d0 + z0);
+                                if (ok1) zp[(size_t)(rr0 + 1) * a.ldz] = zs * (d1 + z0);
                             }
                         }
                     }
@@ -1103,7 +1105,7 @@ static int launch_pw_x(const PwGemm &a, hipStream_t st)
 {
     if (precision_is_f32()) {
         if constexpr (pw_x3_built<CIN, NT, PRO, POOL>) {
-            if (precision_split() && !a.w_win_stride && a.uniform_rows == 0 && a.cout % (32 * NT) == 0 && (POOL || a.Z) && !a.bias && !a.identity_k &&
+            if (precision_split() && !a.w_win_stride && a.uniform_rows == 0 && a.cout % (32 * NT) == 0 && (POOL ? !a.Z : a.Z != nullptr) && !a.bias && !a.identity_k &&
                 (!a.part_sum || a.part_rows)) {       // the real point layers (not the T-Net FC rows)
                 if constexpr (POOL) {
                     if (!a.part_amax) return launch_pw_y<CIN, NT, PRO, POOL, true, false, false, false, false, true, PW_X3_NW>(a, st);

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 4
+#define AMPNET_ABI_VERSION 5
 
 enum {
     AMPNET_OK = 0,
@@ -435,6 +435,68 @@ int ampnet_adam_step_f32(float *const *params_host, const float *const *grads_ho
  * flops and bytes per kernel name (names: max_rows x 64 chars).  Off by default: no events, no overhead.      */
 int ampnet_profile_enable(int on);
 int ampnet_profile_read(int max_rows, char *names, double *ms, long long *calls, double *flops, double *bytes);
+
+/* ---- test hooks: not used by any product path -----------------------------------------------------------
+ * One launch of a per-point layer kernel on inputs the caller chooses (tests/test_pw_layers_gpu.py holds each one
+ * to a float64 restatement of its contract).  The structs mirror the internal launch records of csrc/kernels.h
+ * (PwGemm, PwBwd + GradSrc / ActSrc): see the comments there for what every field means.  Every pointer comes with
+ * its extent in ELEMENTS (`*_n`); before anything is launched the probe checks on the host that each extent covers
+ * what the kernel will touch (win_off is copied to the host and checked for monotonicity) and returns AMPNET_E_ARG
+ * otherwise.  The current matrix precision picks the kernel family, as it does for the product paths.        */
+typedef struct AmpnetPwGemmProbe {
+    const float *A; int64_t A_n; int32_t lda, cin;
+    const float *W; int64_t W_n; int64_t w_win_stride; int32_t ldw, perwin_slot_major;
+    const float *bias; int64_t bias_n; int64_t bias_win_stride;
+    const float *pro_scale, *pro_shift; int64_t pro_n;        /* [n_slots, cin] each */
+    int32_t n_slots; float drop_p; uint32_t drop_seed; int32_t cout;
+    float *Z; int64_t Z_n; int32_t ldz, stat_lanes;
+    float *part_sum, *part_sq; int64_t part_n;                 /* each */
+    int32_t *part_rows; int64_t part_rows_n;
+    float *part_max; int32_t *part_amax; int64_t pool_n;        /* each */
+    const float *pool_gamma; int64_t pool_gamma_n;
+    const int32_t *win_off; int64_t win_off_n;
+    int32_t Q, chunk_rows, chunks, uniform_rows, identity_k; float fin_eps;
+    const float *fin_gamma, *fin_beta; int64_t fin_in_n;       /* [cout] each */
+    float *fin_scale, *fin_shift, *fin_mean, *fin_invstd, *fin_smean, *fin_suvar; int64_t fin_out_n;   /* [n_slots, cout] each */
+    const float *pfin_sum, *pfin_sq; int64_t pfin_n;           /* [pfin_parts, cin] each */
+    const int32_t *pfin_rows; int64_t pfin_rows_n; int32_t pfin_parts, pad0;
+    const float *pfin_gamma, *pfin_beta; int64_t pfin_in_n;    /* [cin] each */
+    float *pfin_scale, *pfin_shift, *pfin_mean, *pfin_invstd, *pfin_smean, *pfin_suvar; int64_t pfin_out_n;   /* [n_slots, cin] each */
+} AmpnetPwGemmProbe;
+
+/* kind 0 = pw_bwd_fused (which picks the split / bf16 kernels by itself, as in the product).  dbg_row_wrap is always 0. */
+typedef struct AmpnetPwBwdProbe {
+    int32_t kind, CX, CY, act;
+    const float *dy, *gz; int64_t g_n;                         /* [rows, CX] each; gz may be a bf16 tensor (g_z_bf16) */
+    const float *P1, *P2, *P3; int64_t P_n;                    /* [n_slots, CX] each */
+    int32_t g_z_bf16, prev_z_bf16;
+    const float *pz; int64_t pz_n;                             /* [rows, CY] */
+    const float *ps, *pt, *prev_mean, *prev_invstd; int64_t ps_n;   /* [n_slots, CY] each */
+    float drop_p; uint32_t drop_seed;
+    const float *W; int64_t W_n; int64_t w_slot_stride, w_win_stride; int32_t ldw, perwin_slot_major;
+    const float *bias_slot; int64_t bias_slot_n;
+    const float *add; int64_t add_n;
+    float *out; int64_t out_n;
+    float *dWpart, *dbpart, *part_a, *part_b; int64_t dW_n, db_n, pab_n;
+    const int32_t *win_off; int64_t win_off_n;
+    int32_t Q, n_slots, max_rows, blocks_per_slot, items_per_block, fin_parts;
+    const float *fin_part_a, *fin_part_b; int64_t fin_part_n;  /* [fin_parts, CX] each */
+    int32_t fin_rows, pad0;
+    const float *fin_gamma, *fin_mean, *fin_invstd; int64_t fin_in_n;   /* [n_slots, CX] each (gamma: [CX]) */
+    float *fin_P1, *fin_P2, *fin_P3, *fin_slot_ab; int64_t fin_out_n;    /* each >= [n_slots, CX, 2] */
+} AmpnetPwBwdProbe;
+
+/* the geometry the orchestration would choose for a layer of Q windows (max_rows rows at most) in n_slots slots */
+typedef struct AmpnetPwPlan {
+    int32_t stat_lanes, stat_parts, stat_direct, stat_lane_cap;   /* pw_gemm_stat_plan(Q, stat_chunks, n_slots, lane cap of cin x cout) */
+    int32_t chunk_rows, chunks, x_chunk_rows, x_chunks;           /* enc_shape: point layers, point layers on the split kernels */
+    int32_t fc_rows, fc_chunk_rows, fc_chunks;
+    int32_t bwd_blocks, bwd_item_rows, bwd_x3;                    /* pw_bwd_blocks, pw_bwd_item_rows, pw_bwd_x3_supported(bwd) (-1: bwd NULL) */
+} AmpnetPwPlan;
+
+int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream);
+int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream);
+int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, int cout, int stat_chunks, const AmpnetPwBwdProbe *bwd, AmpnetPwPlan *out_host);
 
 #ifdef __cplusplus
 }

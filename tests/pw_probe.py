@@ -1,0 +1,393 @@
+"""Layer-local float64 oracle of the per-point layer kernels (pw_gemm, pw_bwd_fused and the split / bf16 kernels it dispatches to).
+
+The C side is the test hook of include/ampnet_hip.h ("test hooks"): ampnet_probe_pw_gemm_f32 / ampnet_probe_pw_bwd_f32 launch ONE kernel on
+buffers the test chose, after checking every extent on the host.  This module holds
+  * the ctypes mirrors of AmpnetPwGemmProbe / AmpnetPwBwdProbe / AmpnetPwPlan,
+  * a float64 restatement of each kernel's contract, written from the comments in csrc/kernels.h (PwGemm, PwBwd, GradSrc, ActSrc),
+  * the one error bar every comparison uses (`bar`).
+Host side only; the GPU tests are tests/test_pw_layers_gpu.py.
+"""
+import ctypes
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from oracle.ampnet_oracle import keep_mask  # noqa: E402
+
+L = importlib.import_module("3d-semantic-segmentation-amp-net_amd._lib")
+
+AMPNET_E_ARG = -1
+EPS32 = 2.0 ** -24
+EPS16 = 2.0 ** -8     # bf16 operand modes: the same rule with the bf16 unit roundoff
+
+_p, _i64, _i32, _u32, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32, ctypes.c_float
+
+
+class PwGemmProbe(ctypes.Structure):
+    _fields_ = [("A", _p), ("A_n", _i64), ("lda", _i32), ("cin", _i32),
+                ("W", _p), ("W_n", _i64), ("w_win_stride", _i64), ("ldw", _i32), ("perwin_slot_major", _i32),
+                ("bias", _p), ("bias_n", _i64), ("bias_win_stride", _i64),
+                ("pro_scale", _p), ("pro_shift", _p), ("pro_n", _i64),
+                ("n_slots", _i32), ("drop_p", _f32), ("drop_seed", _u32), ("cout", _i32),
+                ("Z", _p), ("Z_n", _i64), ("ldz", _i32), ("stat_lanes", _i32),
+                ("part_sum", _p), ("part_sq", _p), ("part_n", _i64),
+                ("part_rows", _p), ("part_rows_n", _i64),
+                ("part_max", _p), ("part_amax", _p), ("pool_n", _i64),
+                ("pool_gamma", _p), ("pool_gamma_n", _i64),
+                ("win_off", _p), ("win_off_n", _i64),
+                ("Q", _i32), ("chunk_rows", _i32), ("chunks", _i32), ("uniform_rows", _i32), ("identity_k", _i32), ("fin_eps", _f32),
+                ("fin_gamma", _p), ("fin_beta", _p), ("fin_in_n", _i64),
+                ("fin_scale", _p), ("fin_shift", _p), ("fin_mean", _p), ("fin_invstd", _p), ("fin_smean", _p), ("fin_suvar", _p),
+                ("fin_out_n", _i64),
+                ("pfin_sum", _p), ("pfin_sq", _p), ("pfin_n", _i64),
+                ("pfin_rows", _p), ("pfin_rows_n", _i64), ("pfin_parts", _i32), ("pad0", _i32),
+                ("pfin_gamma", _p), ("pfin_beta", _p), ("pfin_in_n", _i64),
+                ("pfin_scale", _p), ("pfin_shift", _p), ("pfin_mean", _p), ("pfin_invstd", _p), ("pfin_smean", _p), ("pfin_suvar", _p),
+                ("pfin_out_n", _i64)]
+
+
+class PwBwdProbe(ctypes.Structure):
+    _fields_ = [("kind", _i32), ("CX", _i32), ("CY", _i32), ("act", _i32),
+                ("dy", _p), ("gz", _p), ("g_n", _i64),
+                ("P1", _p), ("P2", _p), ("P3", _p), ("P_n", _i64),
+                ("g_z_bf16", _i32), ("prev_z_bf16", _i32),
+                ("pz", _p), ("pz_n", _i64),
+                ("ps", _p), ("pt", _p), ("prev_mean", _p), ("prev_invstd", _p), ("ps_n", _i64),
+                ("drop_p", _f32), ("drop_seed", _u32),
+                ("W", _p), ("W_n", _i64), ("w_slot_stride", _i64), ("w_win_stride", _i64), ("ldw", _i32), ("perwin_slot_major", _i32),
+                ("bias_slot", _p), ("bias_slot_n", _i64),
+                ("add", _p), ("add_n", _i64),
+                ("out", _p), ("out_n", _i64),
+                ("dWpart", _p), ("dbpart", _p), ("part_a", _p), ("part_b", _p), ("dW_n", _i64), ("db_n", _i64), ("pab_n", _i64),
+                ("win_off", _p), ("win_off_n", _i64),
+                ("Q", _i32), ("n_slots", _i32), ("max_rows", _i32), ("blocks_per_slot", _i32), ("items_per_block", _i32), ("fin_parts", _i32),
+                ("fin_part_a", _p), ("fin_part_b", _p), ("fin_part_n", _i64),
+                ("fin_rows", _i32), ("pad0", _i32),
+                ("fin_gamma", _p), ("fin_mean", _p), ("fin_invstd", _p), ("fin_in_n", _i64),
+                ("fin_P1", _p), ("fin_P2", _p), ("fin_P3", _p), ("fin_slot_ab", _p), ("fin_out_n", _i64)]
+
+
+class PwPlan(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("stat_lanes", "stat_parts", "stat_direct", "stat_lane_cap", "chunk_rows", "chunks", "x_chunk_rows",
+                                    "x_chunks", "fc_rows", "fc_chunk_rows", "fc_chunks", "bwd_blocks", "bwd_item_rows", "bwd_x3")]
+
+
+def _bind():
+    lib = L.lib()
+    lib.ampnet_probe_pw_gemm_f32.argtypes = [ctypes.POINTER(PwGemmProbe), ctypes.c_void_p]
+    lib.ampnet_probe_pw_bwd_f32.argtypes = [ctypes.POINTER(PwBwdProbe), ctypes.c_void_p]
+    lib.ampnet_probe_pw_plan.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(PwBwdProbe), ctypes.POINTER(PwPlan)]
+    return lib
+
+
+def set_tensors(desc, extents, **tensors):
+    """desc.<name> = device pointer of tensor <name>; the extent field named by `extents[name]` gets the smallest numel of the tensors
+    that share it (None -> NULL and the extent is left alone)."""
+    ext = {}
+    for name, t in tensors.items():
+        if t is None:
+            setattr(desc, name, None)
+            continue
+        assert t.is_cuda and t.is_contiguous(), name
+        setattr(desc, name, t.data_ptr())
+        e = extents.get(name)
+        if e:
+            ext[e] = min(ext.get(e, t.numel()), t.numel())
+    for e, n in ext.items():
+        setattr(desc, e, n)
+
+
+GEMM_EXTENTS = {"A": "A_n", "W": "W_n", "bias": "bias_n", "pro_scale": "pro_n", "pro_shift": "pro_n", "Z": "Z_n", "part_sum": "part_n",
+                "part_sq": "part_n", "part_rows": "part_rows_n", "part_max": "pool_n", "part_amax": "pool_n", "pool_gamma": "pool_gamma_n",
+                "win_off": "win_off_n", "fin_gamma": "fin_in_n", "fin_beta": "fin_in_n",
+                **{f"fin_{k}": "fin_out_n" for k in ("scale", "shift", "mean", "invstd", "smean", "suvar")},
+                "pfin_sum": "pfin_n", "pfin_sq": "pfin_n", "pfin_rows": "pfin_rows_n", "pfin_gamma": "pfin_in_n", "pfin_beta": "pfin_in_n",
+                **{f"pfin_{k}": "pfin_out_n" for k in ("scale", "shift", "mean", "invstd", "smean", "suvar")}}
+BWD_EXTENTS = {"dy": "g_n", "gz": "g_n", "P1": "P_n", "P2": "P_n", "P3": "P_n", "pz": "pz_n", "ps": "ps_n", "pt": "ps_n",
+               "prev_mean": "ps_n", "prev_invstd": "ps_n", "W": "W_n", "bias_slot": "bias_slot_n", "add": "add_n", "out": "out_n",
+               "dWpart": "dW_n", "dbpart": "db_n", "part_a": "pab_n", "part_b": "pab_n", "win_off": "win_off_n",
+               "fin_part_a": "fin_part_n", "fin_part_b": "fin_part_n", "fin_gamma": "fin_in_n", "fin_mean": "fin_in_n", "fin_invstd": "fin_in_n",
+               "fin_P1": "fin_out_n", "fin_P2": "fin_out_n", "fin_P3": "fin_out_n", "fin_slot_ab": "fin_out_n"}
+
+
+def run_gemm(desc):
+    """(return code, kernel names launched) of one probe launch, synchronised."""
+    lib = _bind()
+    lib.ampnet_profile_enable(1)
+    try:
+        rc = lib.ampnet_probe_pw_gemm_f32(ctypes.byref(desc), L.stream_ptr())
+        torch.cuda.synchronize()
+        names = profile_names(lib)
+    finally:
+        lib.ampnet_profile_enable(0)
+    return rc, names
+
+
+def run_bwd(desc):
+    lib = _bind()
+    lib.ampnet_profile_enable(1)
+    try:
+        rc = lib.ampnet_probe_pw_bwd_f32(ctypes.byref(desc), L.stream_ptr())
+        torch.cuda.synchronize()
+        names = profile_names(lib)
+    finally:
+        lib.ampnet_profile_enable(0)
+    return rc, names
+
+
+def profile_names(lib):
+    n_max = 64
+    names = ctypes.create_string_buffer(64 * n_max)
+    ms, fl, by = (ctypes.c_double * n_max)(), (ctypes.c_double * n_max)(), (ctypes.c_double * n_max)()
+    calls = (ctypes.c_longlong * n_max)()
+    n = lib.ampnet_profile_read(n_max, names, ms, calls, fl, by)
+    assert n >= 0
+    return [names.raw[64 * i:64 * (i + 1)].split(b"\0", 1)[0].decode() for i in range(n)]
+
+
+def plan(Q, n_slots, max_rows, cin=64, cout=64, stat_chunks=1, bwd=None):
+    lib = _bind()
+    p = PwPlan()
+    rc = lib.ampnet_probe_pw_plan(Q, n_slots, max_rows, cin, cout, stat_chunks, ctypes.byref(bwd) if bwd is not None else None, ctypes.byref(p))
+    L.check(rc, "ampnet_probe_pw_plan")
+    return p
+
+
+def last_error():
+    msg = L.lib().ampnet_last_error()
+    return msg.decode() if msg else ""
+
+
+# ---- the bar ----------------------------------------------------------------------------------------------------------------------
+def bar(mag, x64, K, eps=EPS32):
+    """|x - x64| <= 8 eps sqrt(K) (|u| |v|) + 2 eps |x64|: mag = (|u| |v|), the float64 product of the absolute operands; K the contraction
+    length.  eps = 2^-24 for exact fp32 and the three-term split, 2^-8 for bf16 operands."""
+    return 8.0 * eps * np.sqrt(np.maximum(K, 1)) * mag + 2.0 * eps * np.abs(x64)
+
+
+def moment_bars(z64, mag, cin, eps=EPS32):
+    """Bars of the per-channel mean and (biased) variance of the rows z64 [K, C] (K = rows) of a layer whose elements carry the operand
+    magnitudes mag [K, C] from a contraction of length cin: the same rule as `bar`, with K = rows for the sums over rows and the
+    elementwise bar of z carried into them.  The variance term covers the kernels' shifted sums (shift = one row of the block)."""
+    K = z64.shape[0]
+    mu = z64.mean(0)
+    dz = z64 - mu
+    var = (dz ** 2).mean(0)
+    bmean = 8 * eps * (np.sqrt(K) + np.sqrt(cin)) * mag.mean(0) + 2 * eps * np.abs(mu)
+    bvar = 8 * eps * (np.sqrt(K) * (var + (dz ** 2).max(0)) + 2 * np.sqrt(cin) * (np.abs(dz) * mag).mean(0)) + 2 * eps * var
+    return mu, var, bmean, bvar
+
+
+def err_ratio(x, want, b):
+    """worst |x - want| / b (finite x required)."""
+    x = np.asarray(x, dtype=np.float64)
+    assert np.all(np.isfinite(x)), "non-finite where the contract writes"
+    return float(np.max(np.abs(x - want) / np.maximum(b, 1e-300))) if x.size else 0.0
+
+
+def ratio(x, x64, mag, K, eps=EPS32):
+    """worst error / bar (finite x required)."""
+    x = np.asarray(x, dtype=np.float64)
+    assert np.all(np.isfinite(x)), "non-finite where the contract writes"
+    b = bar(mag, x64, K, eps)
+    err = np.abs(x - x64)
+    return float(np.max(err / np.maximum(b, 1e-300))) if err.size else 0.0
+
+
+# ---- windows, slots, dropout -----------------------------------------------------------------------------------------------------
+def win_of_rows(win_off):
+    """window index of every row (rows before win_off[0] -> -1)."""
+    win_off = np.asarray(win_off)
+    rows = int(win_off[-1])
+    q = np.full(rows, -1, dtype=np.int64)
+    for i in range(len(win_off) - 1):
+        q[win_off[i]:win_off[i + 1]] = i
+    return q
+
+
+def keep_elems(base, n_rows, C, p):
+    """keep[row, c] of the kernels' dropout hash: mix32((row * C + c) ^ base) >= thr (base = drop_base(seed, stream))."""
+    if p <= 0.0:
+        return np.ones((n_rows, C), dtype=bool)
+    # oracle.keep_mask(seed, stream) hashes with base = mix32(seed + stream * 0x9E3779B9); seed = base - ... is not invertible, so the
+    # base is handed to the kernel as drop_base(seed, stream) and the oracle's own (seed, stream) pair is used here
+    seed, stream = base
+    return keep_mask(seed, stream, n_rows * C, p).reshape(n_rows, C)
+
+
+def drop_base(seed, stream):
+    """the kernels' drop_seed for the oracle's (seed, stream) pair: mix32(seed + stream * 0x9E3779B9) (kernels.h: drop_base)."""
+    from oracle.ampnet_oracle import _mix32
+    return int(_mix32(np.array([(seed + stream * 0x9E3779B9) & 0xFFFFFFFF], dtype=np.uint64))[0])
+
+
+def dscale32(p):
+    """1 / (1 - p) as the kernels form it: in fp32 from the fp32 probability."""
+    return float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
+# ---- forward: Z = pro(A) W^T + bias (+ identity) -------------------------------------------------------------------------------
+def gemm_ref(A, cin, cout, W, win_off, n_slots, pro=None, drop=None, bias=None, bias_win_stride=0, w_win_stride=0, slot_major=0,
+             identity_k=0, rows_window=None):
+    """float64 Z [rows, cout] and the operand magnitudes (|u| |v|) [rows, cout].
+    A [rows, >= cin] fp32; W shared [cout, >= cin] or, w_win_stride != 0, flat [.., cin, cout] k-major at pidx(q) * w_win_stride;
+    pro = (scale [S, cin], shift [S, cin]) -> relu(a s + t); drop = (p, (seed, stream)) on pro(a) at index row * cin + k."""
+    A = np.asarray(A, dtype=np.float64)[:, :cin]
+    rows = A.shape[0]
+    q = win_of_rows(win_off) if rows_window is None else rows_window
+    Q = len(win_off) - 1 if rows_window is None else int(q.max()) + 1
+    slot = np.where(q >= 0, q % n_slots, 0)
+    if pro is not None:
+        s, t = (np.asarray(x, dtype=np.float64)[:, :cin] for x in pro)
+        u = np.maximum(A * s[slot] + t[slot], 0.0)
+        um = np.abs(A * s[slot]) + np.abs(t[slot])
+        if drop is not None and drop[0] > 0.0:
+            k = keep_elems(drop[1], rows, cin, drop[0])
+            ds = dscale32(drop[0])
+            u = np.where(k, u * ds, 0.0)
+            um = np.where(k, um * ds, 0.0)
+    else:
+        u, um = A, np.abs(A)
+    Z = np.zeros((rows, cout))
+    M = np.zeros((rows, cout))
+    if w_win_stride:
+        Wf = np.asarray(W, dtype=np.float64).reshape(-1)
+        for qq in range(Q):
+            r = q == qq
+            pidx = (qq % n_slots) * (Q // n_slots) + qq // n_slots if slot_major else qq
+            Wq = Wf[pidx * w_win_stride:pidx * w_win_stride + cin * cout].reshape(cin, cout)
+            Z[r] = u[r] @ Wq
+            M[r] = um[r] @ np.abs(Wq)
+    else:
+        Wm = np.asarray(W, dtype=np.float64)[:cout, :cin]
+        Z = u @ Wm.T
+        M = um @ np.abs(Wm).T
+    if bias is not None:
+        b = np.asarray(bias, dtype=np.float64).reshape(-1)
+        if bias_win_stride:
+            pid = q
+            bb = np.stack([b[p * bias_win_stride:p * bias_win_stride + cout] for p in pid])
+        else:
+            bb = b[:cout][None, :]
+        Z = Z + bb
+        M = M + np.abs(bb)
+    if identity_k:
+        cols = np.arange(cout)
+        Z[:, cols % (identity_k + 1) == 0] += 1.0
+        M[:, cols % (identity_k + 1) == 0] += 1.0
+    return Z, M
+
+
+def chan_merge(means, m2s, ns):
+    """(n, mean, M2) of a set of (mean, M2, n) partials, float64 (Chan et al.)."""
+    n, mean, m2 = 0.0, np.zeros_like(means[0], dtype=np.float64), np.zeros_like(means[0], dtype=np.float64)
+    for mu, q2, k in zip(means, m2s, ns):
+        k = float(k)
+        if k <= 0:
+            continue
+        mu = np.asarray(mu, dtype=np.float64)
+        d = mu - mean
+        nn = n + k
+        mean = mean + d * (k / nn)
+        m2 = m2 + np.asarray(q2, dtype=np.float64) + d * d * n * k / nn
+        n = nn
+    return n, mean, m2
+
+
+# ---- backward ---------------------------------------------------------------------------------------------------------------------
+def bwd_ref(c):
+    """float64 restatement of pw_bwd_fused (kernels.h: PwBwd) for the dict of numpy inputs `c` (fp32 values, see
+    test_pw_layers_gpu.make_bwd).  Returns per-slot sums {dW [S, CX, CY], db [S, CX], pa [S, CY], pb [S, CY]}, the row outputs out [rows, CY],
+    and the magnitudes of each."""
+    f = lambda k: None if c.get(k) is None else np.asarray(c[k], dtype=np.float64)
+    CX, CY, S = c["CX"], c["CY"], c["n_slots"]
+    q = win_of_rows(c["win_off"])
+    rows = len(q)
+    slot = q % S
+    gz = f("gz")
+    P1, P2, P3 = f("P1"), f("P2"), f("P3")
+    if c["act"]:
+        g = np.maximum(gz * P2[slot] + P3[slot], 0.0)
+        gm = np.abs(gz * P2[slot]) + np.abs(P3[slot])
+    else:
+        dy = f("dy")
+        g = dy * P1[slot] + gz * P2[slot] + P3[slot]
+        gm = np.abs(dy * P1[slot]) + np.abs(gz * P2[slot]) + np.abs(P3[slot])
+    pz = f("pz")
+    yact = c.get("ps") is not None
+    p = c.get("drop_p", 0.0)
+    if yact:
+        s, t = f("ps")[slot], f("pt")[slot]
+        a = np.maximum(pz * s + t, 0.0)
+        am = np.abs(pz * s) + np.abs(t)
+        keep = keep_elems(c["drop_key"], rows, CY, p) if p > 0 else np.ones((rows, CY), dtype=bool)
+        ds = dscale32(p) if p > 0 else 1.0
+        a = np.where(keep, a * ds, 0.0)
+        am = np.where(keep, am * ds, 0.0)
+    else:
+        a, am = pz, np.abs(pz)
+        keep, ds = np.ones((rows, CY), dtype=bool), 1.0
+    # data gradient: v = g W (+ bias_slot + add), masked
+    W = f("W").reshape(-1)
+    v = np.zeros((rows, CY))
+    vm = np.zeros((rows, CY))
+    Q = len(c["win_off"]) - 1
+    if c.get("w_win_stride"):
+        ws = c["w_win_stride"]
+        for qq in range(Q):
+            r = q == qq
+            pidx = (qq % S) * (Q // S) + qq // S if c.get("perwin_slot_major") else qq
+            T = W[pidx * ws:pidx * ws + CY * CX].reshape(CY, CX)        # T[j][k]
+            v[r] = g[r] @ T.T
+            vm[r] = gm[r] @ np.abs(T).T
+    else:
+        ldw, sst = c["ldw"], c.get("w_slot_stride", 0)
+        for sl in range(S):
+            r = slot == sl
+            Wk = W[sl * sst:sl * sst + CX * ldw].reshape(CX, ldw)[:, :CY]     # W[k][j]
+            v[r] = g[r] @ Wk
+            vm[r] = gm[r] @ np.abs(Wk)
+    if c.get("bias_slot") is not None:
+        v += f("bias_slot")[slot]
+        vm += np.abs(f("bias_slot")[slot])
+    if c.get("add") is not None:
+        v += f("add")
+        vm += np.abs(f("add"))
+    if yact:
+        mask = a > 0.0
+        v = np.where(mask, v * ds, 0.0)
+        vm = np.where(keep, vm * ds, 0.0)         # (the mask boundary is inside the bar: a from an fp32 fma)
+    out, outm = v, vm
+    res = {"out": out, "out_m": outm, "dW": np.zeros((S, CX, CY)), "dW_m": np.zeros((S, CX, CY)), "db": np.zeros((S, CX)),
+           "db_m": np.zeros((S, CX)), "pa": np.zeros((S, CY)), "pa_m": np.zeros((S, CY)), "pb": np.zeros((S, CY)), "pb_m": np.zeros((S, CY)),
+           "rows": np.zeros(S)}
+    for sl in range(S):
+        r = slot == sl
+        res["rows"][sl] = r.sum()
+        res["dW"][sl] = g[r].T @ a[r]
+        res["dW_m"][sl] = gm[r].T @ am[r]
+        res["db"][sl] = g[r].sum(0)
+        res["db_m"][sl] = gm[r].sum(0)
+        if yact and c.get("prev_mean") is not None:
+            mean, inv = f("prev_mean")[sl], f("prev_invstd")[sl]
+            zh = (pz[r] - mean) * inv
+            # the kernels form zhat from the activation: (a - beta) / gamma, beta = mean s + t -- the roundings of that path
+            sv, tv = f("ps")[sl], f("pt")[sl]
+            zhm = np.abs(zh) + (np.abs(pz[r] * sv) + np.abs(tv) + np.abs(mean * sv + tv)) * inv / np.maximum(np.abs(sv), 1e-30)
+            res["pa"][sl] = out[r].sum(0)
+            res["pa_m"][sl] = outm[r].sum(0)
+            res["pb"][sl] = (out[r] * zh).sum(0)
+            res["pb_m"][sl] = (outm[r] * zhm).sum(0)
+    return res
+
+
+def slot_sums(part, n_slots, shape):
+    """sum of the partials [grid, *shape] per slot (partial i belongs to slot i % n_slots), float64."""
+    p = np.asarray(part, dtype=np.float64).reshape((-1,) + tuple(shape))
+    return np.stack([p[s::n_slots].sum(0) for s in range(n_slots)])

@@ -1,6 +1,7 @@
 """Edge shapes through the public modules: one cluster, the maximum of 32 clusters, 2 / 8 classes, windows of 4, 33, 257
 points (not multiples of the 32-row MFMA tile, the 256-row work item or the 512-row chunk).  Eval logits against the oracle
-(north_star bar: 1e-3), train step: finite loss and gradients."""
+(north_star bar: 1e-3), train step: finite loss and gradients.  For (3, 2, 33, 2) and (5, 3, 257, 5) the fused backward of one
+layer is also held to float64 at those window shapes (B * W windows of N rows, W BatchNorm slots; tests/test_pw_layers_gpu.py)."""
 import os
 import sys
 
@@ -44,3 +45,12 @@ def test_edge_shapes(synth, params, B, W, N, C):
         o2 = T.forward_backward(enc, att, x, t, cent, torch.ones(C, device="cuda"))
         assert np.isfinite(float(o2["ce"][0])) and np.isfinite(float(o2["reg"]))
         assert all(torch.isfinite(p.grad).all().item() for m in (enc, att) for p in m.parameters())
+
+
+@pytest.mark.parametrize("B,W,N,C", [(3, 2, 33, 2), (5, 3, 257, 5)])
+@pytest.mark.parametrize("layer", ["b128_64", "b64_64add"])
+def test_edge_shapes_layer_backward(matrix_precision_mode, B, W, N, C, layer):
+    """The edge row counts through one fused-backward launch (layer-local float64 check), in the precision the fixture set."""
+    from test_pw_layers_gpu import BWD, run_bwd_case
+    c = dict(BWD[layer], sizes=[N] * (B * W), S=W)
+    assert run_bwd_case(f"edge {layer} {B}x{W}x{N}", c, matrix_precision_mode, 77 + N) <= 1.0

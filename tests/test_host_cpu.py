@@ -13,7 +13,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from conftest import sub                           # noqa: E402
+from conftest import PKG, sub                      # noqa: E402
 
 
 def test_collate_seq_padd_matches_reference(golden, synth):
@@ -116,6 +116,22 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/ampnet_hip.h but not exported"
     assert lib.ampnet_abi_version() == L.ABI_VERSION
+
+
+def test_probe_hooks_stay_out_of_product_code():
+    """The layer probes (include/ampnet_hip.h, "test hooks") serve tests/test_pw_layers_gpu.py only: no module of the package and no
+    orchestration source names them."""
+    pkg = os.path.join(ROOT, PKG)
+    hits = []
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith((".py", ".hip", ".h", ".cpp")) or f == "layer_probe.hip":
+                continue
+            path = os.path.join(dirpath, f)
+            with open(path, errors="replace") as fh:
+                if "ampnet_probe_" in fh.read():
+                    hits.append(os.path.relpath(path, ROOT))
+    assert not hits, f"product code calls the test probes: {hits}"
 
 
 def test_parameter_tables_match_library(params):

@@ -1,11 +1,13 @@
-// layer_probe.hip -- test hooks (include/ampnet_hip.h, "test hooks"): one launch of pw_gemm / pw_bwd_fused on buffers the caller
-// chooses, for the layer-local float64 parity tests (tests/test_pw_layers_gpu.py).  No product path calls these.
+// layer_probe.hip -- test hooks (include/ampnet_hip.h, "test hooks"): one launch of pw_gemm / pw_bwd_fused / pw_dgrad / pw_wgrad, of a
+// kernel of the max-pooled layers' backward or of the input layers' weight gradient on buffers the caller chooses, for the layer-local
+// float64 parity tests (tests/test_pw_layers_gpu.py, tests/test_pooled_bwd_gpu.py).  No product path calls these.
 //
 // The probes exist for shared GPUs: before anything is launched every extent is checked on the host against what the kernel will
 // touch (rows from win_off / uniform_rows, partial slots from the statistics plan, ld x rows), so that a wrong test gets
 // AMPNET_E_ARG instead of an out-of-bounds access.  win_off is copied to the host once per call for that.
 #include <vector>
 #include "kernels.h"
+#include "bwd_misc.h"
 #include "encoder.h"
 
 namespace ampnet {
@@ -129,12 +131,79 @@ PwBwd bwd_record(const AmpnetPwBwdProbe *d)
 }  // namespace
 }  // namespace ampnet
 
+namespace ampnet {
+namespace {
+// kinds 1 (pw_dgrad) and 2 (pw_wgrad): the unfused kernels, fp32 tensors, dense or act gradient source
+int probe_unfused(const AmpnetPwBwdProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE(d->Q >= 1 && d->n_slots >= 1 && d->chunks >= 1 && d->chunk_rows >= 1 && d->CX >= 1 && d->CY >= 1 && d->CX % 4 == 0 &&
+                       d->CY % 4 == 0 && d->CX <= 256 && d->CY <= 256,
+                   "probe_pw_bwd: bad sizes");
+    AMPNET_REQUIRE(!d->g_z_bf16 && !d->prev_z_bf16, "probe_pw_bwd: kinds 1 and 2 read fp32 tensors only");
+    AMPNET_REQUIRE(d->act ? (d->gz && d->P2 && d->P3 && !d->dy && !d->P1) : (d->dy != nullptr), "probe_pw_bwd: gradient source is neither dense nor act");
+    AMPNET_REQUIRE(!d->P1 || (d->P2 && d->P3 && d->gz), "probe_pw_bwd: BatchNorm constants incomplete");
+    AMPNET_REQUIRE((d->ps == nullptr) == (d->pt == nullptr), "probe_pw_bwd: prev scale and shift must come together");
+    AMPNET_REQUIRE((d->prev_mean == nullptr) == (d->prev_invstd == nullptr), "probe_pw_bwd: prev mean and invstd must come together");
+    AMPNET_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f && (d->drop_p == 0.f || d->ps), "probe_pw_bwd: dropout needs the activation");
+    int64_t rows = 0;
+    int max_rows = 0;
+    if (int rc = read_win_off(d->win_off, d->win_off_n, d->Q, st, rows, max_rows); rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE((int64_t)d->chunks * d->chunk_rows >= max_rows, "probe_pw_bwd: %d chunks of %d rows do not cover a window of %d rows", d->chunks,
+                   d->chunk_rows, max_rows);
+    const int64_t CX = d->CX, CY = d->CY, S = d->n_slots, Q = d->Q, parts = Q * d->chunks;
+    AMPNET_REQUIRE((!d->dy || d->g_n >= rows * CX) && (!d->gz || d->g_n >= rows * CX), "probe_pw_bwd: g tensors short");
+    AMPNET_REQUIRE(d->P_n >= S * CX || !(d->P1 || d->P2 || d->P3), "probe_pw_bwd: P1..P3 short");
+    AMPNET_REQUIRE(d->ps_n >= S * CY || !(d->ps || d->prev_mean), "probe_pw_bwd: prev constants short");
+    if (d->kind == 1) {
+        AMPNET_REQUIRE(d->CX == 64 || d->CX == 128 || d->CX == 256, "probe_pw_bwd: pw_dgrad K=%d not in {64, 128, 256}", d->CX);
+        AMPNET_REQUIRE(d->cp == d->CY, "probe_pw_bwd: pw_dgrad writes cp = CY columns (cp %d, CY %d)", d->cp, d->CY);
+        AMPNET_REQUIRE(!d->pz || d->pz_n >= rows * CY, "probe_pw_bwd: prev z short");
+        AMPNET_REQUIRE(!d->ps || d->pz, "probe_pw_bwd: prev constants without prev z");
+        AMPNET_REQUIRE(d->W && d->out && d->out_n >= rows * CY, "probe_pw_bwd: out short");
+        if (d->w_win_stride) {
+            AMPNET_REQUIRE(!d->w_slot_stride && (!d->perwin_slot_major || Q % S == 0) && d->w_win_stride >= CX * CY &&
+                               d->W_n >= (Q - 1) * d->w_win_stride + CX * CY,
+                           "probe_pw_bwd: per-window W short");
+        } else {
+            AMPNET_REQUIRE(d->ldw % 4 == 0 && d->w_slot_stride >= 0 && covers(d->W_n - (S - 1) * d->w_slot_stride, CX, d->ldw, CY), "probe_pw_bwd: W short");
+        }
+        AMPNET_REQUIRE(!d->bias_slot || d->bias_slot_n >= S * CY, "probe_pw_bwd: bias_slot short");
+        AMPNET_REQUIRE(!d->add || d->add_n >= rows * CY, "probe_pw_bwd: add short");
+        const int64_t pc = d->part_chunks ? d->part_chunks : d->chunks;
+        AMPNET_REQUIRE(d->part_chunks == 0 || d->part_chunks >= d->chunks, "probe_pw_bwd: part_chunks %d < chunks %d", d->part_chunks, d->chunks);
+        AMPNET_REQUIRE((d->part_a == nullptr) == (d->part_b == nullptr) && (!d->part_a || (d->pz && d->pab_n >= Q * pc * CY)),
+                       "probe_pw_bwd: part_a / part_b short");
+        PwDgrad g;
+        g.g.dy = d->dy; g.g.z = d->gz; g.g.P1 = d->P1; g.g.P2 = d->P2; g.g.P3 = d->P3; g.g.act = d->act; g.g.C = d->CX;
+        g.W = d->W; g.ldw = d->ldw; g.w_win_stride = d->w_win_stride; g.perwin_slot_major = d->perwin_slot_major; g.w_slot_stride = d->w_slot_stride;
+        g.bias_slot = d->bias_slot; g.add = d->add;
+        g.prev.z = d->pz; g.prev.s = d->ps; g.prev.t = d->pt; g.prev.drop_p = d->drop_p; g.prev.drop_seed = d->drop_seed; g.prev.C = d->CY;
+        g.prev_mean = d->prev_mean; g.prev_invstd = d->prev_invstd;
+        g.out = d->out; g.cp = d->cp; g.part_a = d->part_a; g.part_b = d->part_b; g.part_chunks = d->part_chunks;
+        g.win_off = d->win_off; g.Q = d->Q; g.n_slots = d->n_slots; g.chunk_rows = d->chunk_rows; g.chunks = d->chunks; g.rows_hint = rows;
+        return pw_dgrad(g, st);
+    }
+    AMPNET_REQUIRE(d->chunk_rows % 64 == 0, "probe_pw_bwd: pw_wgrad chunk_rows %d not a multiple of 64", d->chunk_rows);
+    AMPNET_REQUIRE(d->pz && d->pz_n >= rows * CY, "probe_pw_bwd: y z short");
+    AMPNET_REQUIRE(d->ldp >= d->CY && d->dWpart && d->dW_n >= parts * CX * d->ldp, "probe_pw_bwd: dWpart short (%lld partials)", (long long)parts);
+    AMPNET_REQUIRE(!d->dbpart || d->db_n >= parts * CX, "probe_pw_bwd: dbpart short");
+    PwWgrad w;
+    w.x.dy = d->dy; w.x.z = d->gz; w.x.P1 = d->P1; w.x.P2 = d->P2; w.x.P3 = d->P3; w.x.act = d->act; w.x.C = d->CX;
+    w.y.z = d->pz; w.y.s = d->ps; w.y.t = d->pt; w.y.drop_p = d->drop_p; w.y.drop_seed = d->drop_seed; w.y.C = d->CY;
+    w.dWpart = d->dWpart; w.ldp = d->ldp; w.dbpart = d->dbpart;
+    w.win_off = d->win_off; w.Q = d->Q; w.n_slots = d->n_slots; w.chunk_rows = d->chunk_rows; w.chunks = d->chunks; w.rows_hint = rows;
+    return pw_wgrad(w, st);
+}
+}  // namespace
+}  // namespace ampnet
+
 extern "C" int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream)
 {
     using namespace ampnet;
     AMPNET_REQUIRE(d, "probe_pw_bwd: null descriptor");
-    AMPNET_REQUIRE(d->kind == 0, "probe_pw_bwd: kind %d not built (0 = pw_bwd_fused)", d->kind);
+    AMPNET_REQUIRE(d->kind >= 0 && d->kind <= 2, "probe_pw_bwd: kind %d not built (0 = pw_bwd_fused, 1 = pw_dgrad, 2 = pw_wgrad)", d->kind);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d->kind != 0) return probe_unfused(d, st);
     AMPNET_REQUIRE(d->Q >= 1 && d->n_slots >= 1 && d->max_rows >= 1 && pw_bwd_supported(d->CX, d->CY) && d->blocks_per_slot >= 1 &&
                        d->blocks_per_slot <= 4096 && d->items_per_block >= 0,
                    "probe_pw_bwd: bad sizes");
@@ -198,4 +267,187 @@ extern "C" int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, i
     o->bwd_item_rows = pw_bwd_item_rows();
     o->bwd_x3 = bwd ? (pw_bwd_x3_supported(bwd_record(bwd)) ? 1 : 0) : -1;
     return AMPNET_OK;
+}
+
+namespace ampnet {
+namespace {
+template <typename T> int to_host(const T *src, int64_t n, std::vector<T> &h, hipStream_t st, const char *what)
+{
+    h.resize((size_t)n);
+    if (n > 0 && (hipMemcpyAsync(h.data(), src, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+        return fail(AMPNET_E_LAUNCH, "probe: copying %s failed", what);
+    return AMPNET_OK;
+}
+
+// every argmax entry is -1 or a row of its own window (the kernels gather z_prev[arg] and write out[arg])
+int check_arg(const AmpnetPooledBwdProbe *d, const std::vector<int32_t> &wo, hipStream_t st)
+{
+    const int64_t n = (int64_t)d->Q * d->C;
+    AMPNET_REQUIRE(d->arg && d->arg_n >= n, "probe_pooled_bwd: arg [Q, C] short");
+    std::vector<int32_t> h;
+    if (int rc = to_host(d->arg, n, h, st, "arg"); rc != AMPNET_OK) return rc;
+    for (int q = 0; q < d->Q; ++q)
+        for (int c = 0; c < d->C; ++c) {
+            const int r = h[(size_t)q * d->C + c];
+            AMPNET_REQUIRE(r == -1 || (r >= wo[q] && r < wo[q + 1]), "probe_pooled_bwd: arg[%d][%d] = %d outside window [%d, %d)", q, c, r, wo[q], wo[q + 1]);
+        }
+    return AMPNET_OK;
+}
+}  // namespace
+}  // namespace ampnet
+
+extern "C" int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(d, "probe_pooled_bwd: null descriptor");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    AMPNET_REQUIRE(d->op >= 0 && d->op <= 7, "probe_pooled_bwd: op %d not built", d->op);
+    AMPNET_REQUIRE(d->Q >= 1 && d->n_slots >= 1 && d->Q % d->n_slots == 0 && d->C >= 1 && d->C <= 256 && d->cp >= 1 && d->cp <= 128,
+                   "probe_pooled_bwd: bad sizes (Q %d, n_slots %d, C %d, cp %d)", d->Q, d->n_slots, d->C, d->cp);
+    const int64_t Q = d->Q, S = d->n_slots, C = d->C, cp = d->cp;
+    if (d->op == 6 || d->op == 7) {
+        AMPNET_REQUIRE(d->chunks >= 1 && d->red_n0 >= 1 && d->red_part0 && d->red_out0 && d->red_part0_n >= Q * d->chunks * d->red_n0 &&
+                           d->red_out0_n >= S * d->red_n0,
+                       "probe_pooled_bwd: reduce_slots pair 0 short");
+        if (d->op == 6) return reduce_slots(d->red_part0, d->Q, d->chunks, d->n_slots, d->red_n0, d->red_out0, st);
+        AMPNET_REQUIRE(d->red_n1 >= 1 && d->red_part1 && d->red_out1 && d->red_part1_n >= Q * d->chunks * d->red_n1 && d->red_out1_n >= S * d->red_n1,
+                       "probe_pooled_bwd: reduce_slots pair 1 short");
+        return reduce_slots2(d->red_part0, d->red_n0, d->red_out0, d->red_part1, d->red_n1, d->red_out1, d->Q, d->chunks, d->n_slots, st);
+    }
+    if (d->op == 1) {
+        AMPNET_REQUIRE(d->W && d->W_n >= C * cp && d->P2 && d->P3 && d->P_n >= S * C && d->G && d->G_n >= S * cp * cp && d->c0 && d->c0_n >= S * cp,
+                       "probe_pooled_bwd: slot_mats buffers short");
+        return slot_mats(d->W, d->P2, d->P3, d->n_slots, d->C, d->cp, d->G, d->c0, st);
+    }
+    int64_t rows = 0;
+    int max_rows = 0;
+    if (int rc = read_win_off(d->win_off, d->win_off_n, d->Q, st, rows, max_rows); rc != AMPNET_OK) return rc;
+    std::vector<int32_t> wo;
+    if (int rc = to_host(d->win_off, Q + 1, wo, st, "win_off"); rc != AMPNET_OK) return rc;
+    // what the sparse ops read per window: arg, dpm (row prow(q) < Q), P1 [S, C], W [C, cp]
+    const bool zprev_op = d->op == 2 || d->op == 4 || d->op == 5;
+    if (zprev_op) {
+        AMPNET_REQUIRE(d->z_prev && d->z_prev_n >= rows * cp, "probe_pooled_bwd: z_prev [rows, cp] short");
+        AMPNET_REQUIRE(d->s_prev && d->t_prev && d->prev_n >= S * cp, "probe_pooled_bwd: s_prev / t_prev short");
+        AMPNET_REQUIRE(d->op == 5 || (d->mean_prev && d->invstd_prev), "probe_pooled_bwd: mean_prev / invstd_prev missing");
+        AMPNET_REQUIRE(!d->z_bf16 || d->op != 4, "probe_pooled_bwd: sparse_fix reads fp32 z_prev only");
+    }
+    if (d->op == 2 || d->op == 4) {
+        AMPNET_REQUIRE(d->out && d->out_n >= rows * cp, "probe_pooled_bwd: out [rows, cp] short");
+        AMPNET_REQUIRE(d->part_chunks >= 1 && d->slot_idx >= 0 && d->slot_idx < d->part_chunks, "probe_pooled_bwd: slot_idx %d outside part_chunks %d",
+                       d->slot_idx, d->part_chunks);
+        AMPNET_REQUIRE(d->part_a && d->part_b && d->part_n >= Q * d->part_chunks * cp, "probe_pooled_bwd: part_a / part_b short");
+    }
+    if (d->op != 4) {
+        if (int rc = check_arg(d, wo, st); rc != AMPNET_OK) return rc;
+        AMPNET_REQUIRE(d->dpm && d->qc_n >= Q * C, "probe_pooled_bwd: dpm [Q, C] short");
+    }
+    if (d->op == 2 || d->op == 3 || d->op == 5) {
+        AMPNET_REQUIRE(d->P1 && d->P_n >= S * C && d->W && d->W_n >= C * cp, "probe_pooled_bwd: P1 / W short");
+    }
+    switch (d->op) {
+    case 0: {
+        AMPNET_REQUIRE(d->zext && d->d_pooled && d->qc_n >= Q * C, "probe_pooled_bwd: zext / d_pooled short");
+        AMPNET_REQUIRE(d->scale && d->shift && d->mean && d->invstd && d->bn_n >= S * C, "probe_pooled_bwd: BatchNorm constants short");
+        AMPNET_REQUIRE(d->P1 && d->P2 && d->P3 && d->P_n >= S * C && d->slot_ab && d->slot_ab_n >= 2 * S * C, "probe_pooled_bwd: P1..P3 / slot_ab short");
+        PoolBwd p;
+        p.d_pooled = d->d_pooled; p.slot_major = d->slot_major; p.arg = d->arg; p.zext = d->zext;
+        p.scale = d->scale; p.shift = d->shift; p.mean = d->mean; p.invstd = d->invstd;
+        p.win_off = d->win_off; p.Q = d->Q; p.n_slots = d->n_slots; p.C = d->C;
+        p.dpm = d->dpm; p.P1 = d->P1; p.P2 = d->P2; p.P3 = d->P3; p.slot_ab = d->slot_ab;
+        return pool_bwd(p, st);
+    }
+    case 2: {
+        SparseScatter a;
+        a.z_bf16 = d->z_bf16 ? 1 : 0; a.arg = d->arg; a.dpm = d->dpm; a.slot_major = d->slot_major; a.P1 = d->P1; a.W = d->W;
+        a.z_prev = d->z_prev; a.s_prev = d->s_prev; a.t_prev = d->t_prev; a.mean_prev = d->mean_prev; a.invstd_prev = d->invstd_prev;
+        a.Q = d->Q; a.n_slots = d->n_slots; a.C = d->C; a.cp = d->cp; a.out = d->out;
+        a.part_a = d->part_a; a.part_b = d->part_b; a.part_chunks = d->part_chunks; a.slot_idx = d->slot_idx;
+        return sparse_scatter(a, st);
+    }
+    case 3: {
+        AMPNET_REQUIRE(d->cp % 4 == 0 && 256 % (d->cp / 4) == 0, "probe_pooled_bwd: sparse_rows cp %d", d->cp);
+        AMPNET_REQUIRE(d->srows && d->srows_n >= Q * C * cp && d->srow_row && d->srow_row_n >= Q * C && d->srow_cnt && d->srow_cnt_n >= Q,
+                       "probe_pooled_bwd: srows / srow_row / srow_cnt short");
+        SparseRows a;
+        a.arg = d->arg; a.dpm = d->dpm; a.slot_major = d->slot_major; a.P1 = d->P1; a.W = d->W;
+        a.Q = d->Q; a.n_slots = d->n_slots; a.C = d->C; a.cp = d->cp;
+        a.srows = d->srows; a.srow_row = d->srow_row; a.srow_cnt = d->srow_cnt;
+        return sparse_rows(a, st);
+    }
+    case 4: {
+        AMPNET_REQUIRE(d->srows && d->srows_n >= Q * C * cp && d->srow_row && d->srow_row_n >= Q * C && d->srow_cnt && d->srow_cnt_n >= Q,
+                       "probe_pooled_bwd: srows / srow_row / srow_cnt short");
+        // the merged rows name rows of z_prev / out: each of the first srow_cnt[q] must lie in window q
+        std::vector<int32_t> cnt, rr;
+        if (int rc = to_host(d->srow_cnt, Q, cnt, st, "srow_cnt"); rc != AMPNET_OK) return rc;
+        if (int rc = to_host(d->srow_row, Q * C, rr, st, "srow_row"); rc != AMPNET_OK) return rc;
+        for (int q = 0; q < d->Q; ++q) {
+            AMPNET_REQUIRE(cnt[q] >= 0 && cnt[q] <= d->C, "probe_pooled_bwd: srow_cnt[%d] = %d", q, cnt[q]);
+            for (int i = 0; i < cnt[q]; ++i) {
+                const int r = rr[(size_t)q * d->C + i];
+                AMPNET_REQUIRE(r >= wo[q] && r < wo[q + 1], "probe_pooled_bwd: srow_row[%d][%d] = %d outside its window", q, i, r);
+            }
+        }
+        SparseFix a;
+        a.srows = d->srows; a.srow_row = d->srow_row; a.srow_cnt = d->srow_cnt; a.z_prev = d->z_prev;
+        a.s_prev = d->s_prev; a.t_prev = d->t_prev; a.mean_prev = d->mean_prev; a.invstd_prev = d->invstd_prev;
+        a.Q = d->Q; a.n_slots = d->n_slots; a.C = d->C; a.cp = d->cp; a.out = d->out;
+        a.part_a = d->part_a; a.part_b = d->part_b; a.part_chunks = d->part_chunks; a.slot_idx = d->slot_idx;
+        return sparse_fix(a, st);
+    }
+    default: {   // 5
+        AMPNET_REQUIRE(d->P2 && d->P3, "probe_pooled_bwd: P2 / P3 missing");
+        AMPNET_REQUIRE(d->gram && d->gram_n >= S * cp * cp && d->asum && d->asum_n >= S * cp, "probe_pooled_bwd: gram / asum short");
+        AMPNET_REQUIRE(d->dW && d->dW_n >= C * cp, "probe_pooled_bwd: dW short");
+        AMPNET_REQUIRE(((size_t)Q * 2 + (size_t)S * cp * 2) * sizeof(int) <= 60 * 1024, "probe_pooled_bwd: pooled_wgrad needs more than 60 KB of LDS");
+        AMPNET_REQUIRE(!d->wgram || (d->n_slots <= 10 /* SG_MAX_PROBLEMS */ && d->wgram_n >= S * C * cp), "probe_pooled_bwd: wgram short");
+        PooledWgrad a;
+        a.z_bf16 = d->z_bf16 ? 1 : 0; a.W = d->W; a.P1 = d->P1; a.P2 = d->P2; a.P3 = d->P3; a.gram = d->gram; a.asum = d->asum;
+        a.arg = d->arg; a.dpm = d->dpm; a.slot_major = d->slot_major;
+        a.z_prev = d->z_prev; a.s_prev = d->s_prev; a.t_prev = d->t_prev;
+        a.Q = d->Q; a.n_slots = d->n_slots; a.C = d->C; a.cp = d->cp; a.dW = d->dW; a.wgram = d->wgram;
+        return pooled_wgrad(a, st);
+    }
+    }
+}
+
+extern "C" int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void *stream)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(d, "probe_input_wgrad: null descriptor");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    AMPNET_REQUIRE((d->op == 0 || d->op == 1) && (d->mode == 0 || d->mode == 1) && d->Q >= 1 && d->n_slots >= 1 && d->Q % d->n_slots == 0,
+                   "probe_input_wgrad: bad op / mode / sizes");
+    const int64_t Q = d->Q, S = d->n_slots, nw = d->mode ? 12 : 3;
+    AMPNET_REQUIRE(d->W && d->W_n >= 64 * nw, "probe_input_wgrad: W short");
+    AMPNET_REQUIRE(d->mode == 0 || (d->T && d->T_n >= Q * 9), "probe_input_wgrad: T short");
+    AMPNET_REQUIRE(d->dWeff && d->dWeff_n >= Q * 64 * 9, "probe_input_wgrad: dWeff short");
+    if (d->op == 1) {
+        AMPNET_REQUIRE(d->dW && d->dW_n >= 64 * nw && (d->mode == 0 || (d->dT && d->dT_n >= Q * 9)), "probe_input_wgrad: dW / dT short");
+        return input_param_grads(d->dWeff, d->W, d->mode ? d->T : nullptr, d->Q, d->n_slots, d->perwin_slot_major, d->mode, d->dW,
+                                 d->mode ? d->dT : nullptr, st);
+    }
+    int64_t rows = 0;
+    int max_rows = 0;
+    if (int rc = read_win_off(d->win_off, d->win_off_n, d->Q, st, rows, max_rows); rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE(d->x && d->x_n >= rows * 9 && d->dy && d->dy_n >= rows * 64, "probe_input_wgrad: x / dy short");
+    if (d->fin_part_a) {
+        AMPNET_REQUIRE(d->fin_part_b && d->fin_parts >= d->n_slots && d->fin_part_n >= (int64_t)d->fin_parts * 64 && d->fin_rows >= 1 &&
+                           d->fin_gamma && d->fin_gamma_n >= 64 && d->fin_mean && d->fin_invstd && d->fin_in_n >= S * 64 && d->fin_P1 &&
+                           d->fin_P2 && d->fin_P3 && d->fin_slot_ab && d->fin_out_n >= 2 * S * 64,
+                       "probe_input_wgrad: fin_* short");
+    } else {
+        AMPNET_REQUIRE(d->P1 && d->P2 && d->P3 && d->P_n >= S * 64, "probe_input_wgrad: P1..P3 short");
+    }
+    PwInputWgrad a;
+    a.x = d->x; a.dy = d->dy; a.W = d->W; a.T = d->mode ? d->T : nullptr; a.mode = d->mode; a.perwin_slot_major = d->perwin_slot_major;
+    a.fin_part_a = d->fin_part_a; a.fin_part_b = d->fin_part_b; a.fin_parts = d->fin_parts; a.fin_rows = d->fin_rows;
+    a.fin_gamma = d->fin_gamma; a.fin_mean = d->fin_mean; a.fin_invstd = d->fin_invstd;
+    a.fin_P1 = d->fin_P1; a.fin_P2 = d->fin_P2; a.fin_P3 = d->fin_P3; a.fin_slot_ab = d->fin_slot_ab;
+    if (!d->fin_part_a) {
+        a.P1 = d->P1; a.P2 = d->P2; a.P3 = d->P3;
+    }
+    a.dWeff = d->dWeff; a.win_off = d->win_off; a.Q = d->Q; a.n_slots = d->n_slots;
+    return pw_input_wgrad(a, st);
 }

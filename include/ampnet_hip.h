@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 5
+#define AMPNET_ABI_VERSION 6
 
 enum {
     AMPNET_OK = 0,
@@ -464,7 +464,12 @@ typedef struct AmpnetPwGemmProbe {
     float *pfin_scale, *pfin_shift, *pfin_mean, *pfin_invstd, *pfin_smean, *pfin_suvar; int64_t pfin_out_n;   /* [n_slots, cin] each */
 } AmpnetPwGemmProbe;
 
-/* kind 0 = pw_bwd_fused (which picks the split / bf16 kernels by itself, as in the product).  dbg_row_wrap is always 0. */
+/* kind 0 = pw_bwd_fused (which picks the split / bf16 kernels by itself, as in the product).  dbg_row_wrap is always 0.
+ * kind 1 = pw_dgrad (PwDgrad): g = (dy, gz, P1..P3, act, CX), prev = (pz, ps, pt, drop, CY == cp), W / ldw / w_slot_stride /
+ *          w_win_stride / perwin_slot_major, bias_slot, add, out, part_a / part_b [Q * part_chunks, cp], chunk_rows x chunks per window.
+ * kind 2 = pw_wgrad (PwWgrad): x = (dy, gz, P1..P3, act, CX), y = (pz, ps, pt, drop, CY), dWpart [Q * chunks, CX, ldp],
+ *          dbpart [Q * chunks, CX].
+ * Kinds 1 and 2 read fp32 tensors only (no bf16 z) and take the dense / act gradient sources (not the sparse arg / dpool one). */
 typedef struct AmpnetPwBwdProbe {
     int32_t kind, CX, CY, act;
     const float *dy, *gz; int64_t g_n;                         /* [rows, CX] each; gz may be a bf16 tensor (g_z_bf16) */
@@ -484,7 +489,63 @@ typedef struct AmpnetPwBwdProbe {
     int32_t fin_rows, pad0;
     const float *fin_gamma, *fin_mean, *fin_invstd; int64_t fin_in_n;   /* [n_slots, CX] each (gamma: [CX]) */
     float *fin_P1, *fin_P2, *fin_P3, *fin_slot_ab; int64_t fin_out_n;    /* each >= [n_slots, CX, 2] */
+    int32_t cp, part_chunks, chunk_rows, chunks, ldp, pad1;     /* kinds 1 and 2 (ABI 6) */
 } AmpnetPwBwdProbe;
+
+/* One launch of a kernel of the max-pooled layers' backward (kernels.h, "backward of a max-pooled layer"), by `op`:
+ *   0 pool_bwd        (d_pooled, arg, zext, scale .. invstd -> dpm, P1 .. P3, slot_ab)
+ *   1 slot_mats       (W, P2, P3 -> G, c0)
+ *   2 sparse_scatter  (arg, dpm, P1, W, z_prev (bf16 if z_bf16), *_prev -> out +=, part_a / part_b at q * part_chunks + slot_idx)
+ *   3 sparse_rows     (arg, dpm, P1, W -> srows, srow_row, srow_cnt)
+ *   4 sparse_fix      (srows, srow_row, srow_cnt, z_prev, *_prev -> out +=, part_a / part_b)
+ *   5 pooled_wgrad    (W, P1 .. P3, gram, asum, arg, dpm, z_prev, s_prev, t_prev -> dW; wgram optional scratch)
+ *   6 reduce_slots    (red_part0 [Q * chunks, red_n0] -> red_out0 [n_slots, red_n0])
+ *   7 reduce_slots2   (the same for both pairs in one launch)
+ * arg (and, for op 4, srow_cnt / srow_row) are copied to the host and every row they name must lie in its own window;
+ * C <= 256, cp <= 128, Q % n_slots == 0 and pooled_wgrad's LDS bound are checked before the launch.                  */
+typedef struct AmpnetPooledBwdProbe {
+    int32_t op, Q, n_slots, C, cp, slot_major, z_bf16, chunks, part_chunks, slot_idx, red_n0, red_n1;
+    const int32_t *win_off; int64_t win_off_n;
+    const int32_t *arg; int64_t arg_n;                          /* [Q, C] */
+    const float *zext, *d_pooled; float *dpm; int64_t qc_n;     /* [Q, C] each */
+    const float *scale, *shift, *mean, *invstd; int64_t bn_n;   /* [n_slots, C] each */
+    float *P1, *P2, *P3; int64_t P_n;                           /* [n_slots, C] each */
+    float *slot_ab; int64_t slot_ab_n;                          /* [n_slots, C, 2] */
+    const float *W; int64_t W_n;                                /* [C, cp] */
+    float *G, *c0; int64_t G_n, c0_n;                           /* [n_slots, cp, cp], [n_slots, cp] */
+    const float *z_prev; int64_t z_prev_n;                      /* [rows, cp] */
+    const float *s_prev, *t_prev, *mean_prev, *invstd_prev; int64_t prev_n;   /* [n_slots, cp] each */
+    float *out; int64_t out_n;                                  /* [rows, cp] */
+    float *part_a, *part_b; int64_t part_n;                     /* [Q * part_chunks, cp] each */
+    float *srows; int64_t srows_n;                              /* [Q * C, cp] */
+    int32_t *srow_row; int64_t srow_row_n;                      /* [Q * C] */
+    int32_t *srow_cnt; int64_t srow_cnt_n;                      /* [Q] */
+    const float *gram, *asum; int64_t gram_n, asum_n;           /* [n_slots, cp, cp], [n_slots, cp] */
+    float *wgram; int64_t wgram_n;                              /* [n_slots, C, cp] or NULL */
+    float *dW; int64_t dW_n;                                    /* [C, cp] */
+    const float *red_part0, *red_part1; int64_t red_part0_n, red_part1_n;
+    float *red_out0, *red_out1; int64_t red_out0_n, red_out1_n;
+} AmpnetPooledBwdProbe;
+
+/* The input layers' weight gradient: op 0 = pw_input_wgrad (PwInputWgrad, bwd_misc.h; P1 .. P3 given, or formed in the kernel from
+ * fin_part_a / fin_part_b), op 1 = input_param_grads (dWeff -> dW, and dT at the slot-major row in mode 1).  mode 0: W [64, 3];
+ * mode 1: W [64, 12] and T [Q, 3, 3].                                                                                              */
+typedef struct AmpnetInputWgradProbe {
+    int32_t op, mode, perwin_slot_major, Q, n_slots, fin_parts, fin_rows, pad0;
+    const float *x; int64_t x_n;                                /* [rows, 9] */
+    const float *dy; int64_t dy_n;                              /* [rows, 64] */
+    const float *W; int64_t W_n;
+    const float *T; int64_t T_n;                                /* [Q, 9] */
+    const float *P1, *P2, *P3; int64_t P_n;                     /* [n_slots, 64] each */
+    const float *fin_part_a, *fin_part_b; int64_t fin_part_n;   /* [fin_parts, 64] each */
+    const float *fin_gamma; int64_t fin_gamma_n;                /* [64] */
+    const float *fin_mean, *fin_invstd; int64_t fin_in_n;       /* [n_slots, 64] each */
+    float *fin_P1, *fin_P2, *fin_P3, *fin_slot_ab; int64_t fin_out_n;   /* each >= [n_slots, 64, 2] */
+    float *dWeff; int64_t dWeff_n;                              /* [Q, 64, 9] */
+    float *dW; int64_t dW_n;                                    /* [64, 3] or [64, 12] */
+    float *dT; int64_t dT_n;                                    /* [Q, 9] (mode 1) */
+    const int32_t *win_off; int64_t win_off_n;
+} AmpnetInputWgradProbe;
 
 /* the geometry the orchestration would choose for a layer of Q windows (max_rows rows at most) in n_slots slots */
 typedef struct AmpnetPwPlan {
@@ -496,6 +557,8 @@ typedef struct AmpnetPwPlan {
 
 int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream);
 int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream);
+int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream);
+int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void *stream);
 int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, int cout, int stat_chunks, const AmpnetPwBwdProbe *bwd, AmpnetPwPlan *out_host);
 
 #ifdef __cplusplus

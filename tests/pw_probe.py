@@ -70,7 +70,34 @@ class PwBwdProbe(ctypes.Structure):
                 ("fin_part_a", _p), ("fin_part_b", _p), ("fin_part_n", _i64),
                 ("fin_rows", _i32), ("pad0", _i32),
                 ("fin_gamma", _p), ("fin_mean", _p), ("fin_invstd", _p), ("fin_in_n", _i64),
-                ("fin_P1", _p), ("fin_P2", _p), ("fin_P3", _p), ("fin_slot_ab", _p), ("fin_out_n", _i64)]
+                ("fin_P1", _p), ("fin_P2", _p), ("fin_P3", _p), ("fin_slot_ab", _p), ("fin_out_n", _i64),
+                ("cp", _i32), ("part_chunks", _i32), ("chunk_rows", _i32), ("chunks", _i32), ("ldp", _i32), ("pad1", _i32)]
+
+
+class PooledBwdProbe(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("op", "Q", "n_slots", "C", "cp", "slot_major", "z_bf16", "chunks", "part_chunks", "slot_idx",
+                                    "red_n0", "red_n1")] + \
+               [("win_off", _p), ("win_off_n", _i64), ("arg", _p), ("arg_n", _i64),
+                ("zext", _p), ("d_pooled", _p), ("dpm", _p), ("qc_n", _i64),
+                ("scale", _p), ("shift", _p), ("mean", _p), ("invstd", _p), ("bn_n", _i64),
+                ("P1", _p), ("P2", _p), ("P3", _p), ("P_n", _i64), ("slot_ab", _p), ("slot_ab_n", _i64),
+                ("W", _p), ("W_n", _i64), ("G", _p), ("c0", _p), ("G_n", _i64), ("c0_n", _i64),
+                ("z_prev", _p), ("z_prev_n", _i64),
+                ("s_prev", _p), ("t_prev", _p), ("mean_prev", _p), ("invstd_prev", _p), ("prev_n", _i64),
+                ("out", _p), ("out_n", _i64), ("part_a", _p), ("part_b", _p), ("part_n", _i64),
+                ("srows", _p), ("srows_n", _i64), ("srow_row", _p), ("srow_row_n", _i64), ("srow_cnt", _p), ("srow_cnt_n", _i64),
+                ("gram", _p), ("asum", _p), ("gram_n", _i64), ("asum_n", _i64), ("wgram", _p), ("wgram_n", _i64), ("dW", _p), ("dW_n", _i64),
+                ("red_part0", _p), ("red_part1", _p), ("red_part0_n", _i64), ("red_part1_n", _i64),
+                ("red_out0", _p), ("red_out1", _p), ("red_out0_n", _i64), ("red_out1_n", _i64)]
+
+
+class InputWgradProbe(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("op", "mode", "perwin_slot_major", "Q", "n_slots", "fin_parts", "fin_rows", "pad0")] + \
+               [("x", _p), ("x_n", _i64), ("dy", _p), ("dy_n", _i64), ("W", _p), ("W_n", _i64), ("T", _p), ("T_n", _i64),
+                ("P1", _p), ("P2", _p), ("P3", _p), ("P_n", _i64), ("fin_part_a", _p), ("fin_part_b", _p), ("fin_part_n", _i64),
+                ("fin_gamma", _p), ("fin_gamma_n", _i64), ("fin_mean", _p), ("fin_invstd", _p), ("fin_in_n", _i64),
+                ("fin_P1", _p), ("fin_P2", _p), ("fin_P3", _p), ("fin_slot_ab", _p), ("fin_out_n", _i64),
+                ("dWeff", _p), ("dWeff_n", _i64), ("dW", _p), ("dW_n", _i64), ("dT", _p), ("dT_n", _i64), ("win_off", _p), ("win_off_n", _i64)]
 
 
 class PwPlan(ctypes.Structure):
@@ -82,6 +109,8 @@ def _bind():
     lib = L.lib()
     lib.ampnet_probe_pw_gemm_f32.argtypes = [ctypes.POINTER(PwGemmProbe), ctypes.c_void_p]
     lib.ampnet_probe_pw_bwd_f32.argtypes = [ctypes.POINTER(PwBwdProbe), ctypes.c_void_p]
+    lib.ampnet_probe_pooled_bwd_f32.argtypes = [ctypes.POINTER(PooledBwdProbe), ctypes.c_void_p]
+    lib.ampnet_probe_input_wgrad_f32.argtypes = [ctypes.POINTER(InputWgradProbe), ctypes.c_void_p]
     lib.ampnet_probe_pw_plan.argtypes = [ctypes.c_int] * 6 + [ctypes.POINTER(PwBwdProbe), ctypes.POINTER(PwPlan)]
     return lib
 
@@ -114,6 +143,39 @@ BWD_EXTENTS = {"dy": "g_n", "gz": "g_n", "P1": "P_n", "P2": "P_n", "P3": "P_n", 
                "dWpart": "dW_n", "dbpart": "db_n", "part_a": "pab_n", "part_b": "pab_n", "win_off": "win_off_n",
                "fin_part_a": "fin_part_n", "fin_part_b": "fin_part_n", "fin_gamma": "fin_in_n", "fin_mean": "fin_in_n", "fin_invstd": "fin_in_n",
                "fin_P1": "fin_out_n", "fin_P2": "fin_out_n", "fin_P3": "fin_out_n", "fin_slot_ab": "fin_out_n"}
+
+
+POOL_EXTENTS = {"win_off": "win_off_n", "arg": "arg_n", "zext": "qc_n", "d_pooled": "qc_n", "dpm": "qc_n",
+                **{k: "bn_n" for k in ("scale", "shift", "mean", "invstd")}, "P1": "P_n", "P2": "P_n", "P3": "P_n", "slot_ab": "slot_ab_n",
+                "W": "W_n", "G": "G_n", "c0": "c0_n", "z_prev": "z_prev_n", **{k: "prev_n" for k in ("s_prev", "t_prev", "mean_prev", "invstd_prev")},
+                "out": "out_n", "part_a": "part_n", "part_b": "part_n", "srows": "srows_n", "srow_row": "srow_row_n", "srow_cnt": "srow_cnt_n",
+                "gram": "gram_n", "asum": "asum_n", "wgram": "wgram_n", "dW": "dW_n", "red_part0": "red_part0_n", "red_part1": "red_part1_n",
+                "red_out0": "red_out0_n", "red_out1": "red_out1_n"}
+INPUT_EXTENTS = {"x": "x_n", "dy": "dy_n", "W": "W_n", "T": "T_n", "P1": "P_n", "P2": "P_n", "P3": "P_n", "fin_part_a": "fin_part_n",
+                 "fin_part_b": "fin_part_n", "fin_gamma": "fin_gamma_n", "fin_mean": "fin_in_n", "fin_invstd": "fin_in_n",
+                 **{f"fin_{k}": "fin_out_n" for k in ("P1", "P2", "P3", "slot_ab")}, "dWeff": "dWeff_n", "dW": "dW_n", "dT": "dT_n",
+                 "win_off": "win_off_n"}
+
+
+def _run(fn, desc):
+    lib = _bind()
+    lib.ampnet_profile_enable(1)
+    try:
+        rc = getattr(lib, fn)(ctypes.byref(desc), L.stream_ptr())
+        torch.cuda.synchronize()
+        names = profile_names(lib)
+    finally:
+        lib.ampnet_profile_enable(0)
+    return rc, names
+
+
+def run_pooled(desc):
+    """(return code, kernel names launched) of one pooled-backward probe launch, synchronised."""
+    return _run("ampnet_probe_pooled_bwd_f32", desc)
+
+
+def run_input(desc):
+    return _run("ampnet_probe_input_wgrad_f32", desc)
 
 
 def run_gemm(desc):
@@ -315,6 +377,9 @@ def bwd_ref(c):
     if c["act"]:
         g = np.maximum(gz * P2[slot] + P3[slot], 0.0)
         gm = np.abs(gz * P2[slot]) + np.abs(P3[slot])
+    elif P1 is None:                              # no BatchNorm behind the layer: g = dy
+        g = f("dy")
+        gm = np.abs(g)
     else:
         dy = f("dy")
         g = dy * P1[slot] + gz * P2[slot] + P3[slot]

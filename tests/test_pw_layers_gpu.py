@@ -31,7 +31,7 @@ Cases, from the dispatch of pw_gemm / launch_pw / launch_pw_x and pw_bwd_fused /
     b128_128 dense / b128_gram Gram / b128_64 act / b128_64lin / b64_64 act / b64_64add act+add / b64_64lin lin+add / b64_128 /
     b64_128drop dropout / bmm64 per-window weights + items_per_block / slotw Gram with w_slot_stride + bias_slot /
     fin128_64 in-kernel BatchNorm-backward constants (fin_*; fp32 kernels only) / wrap128 Q = 576, 9 slots, 300 rows.
-Not covered here: the unfused pw_dgrad / pw_wgrad and the sparse (pooled-argmax) gradient source -- the probe builds kind 0 only.
+The unfused pw_dgrad / pw_wgrad (probe kinds 1 and 2) and the max-pooled layers' backward are tests/test_pooled_bwd_gpu.py.
 Pool tie rule (pw_gemm.hip: strict compare in ascending rows, lower row on equal merges): the FIRST row of a chunk among equal extremes.
 """
 import os

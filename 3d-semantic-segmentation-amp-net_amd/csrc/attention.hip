@@ -110,7 +110,7 @@ int attention_core(const float *qkv, const uint8_t *key_pad_mask, float *probs, 
 // dropout prologue, z4 [R, ldz4]): transposed logits store [B, C, P], argmax, weighted cross-entropy partials.
 // thread = row; a workgroup's 256 rows are consecutive points of one sample (or straddle two: handled per row).
 // ----------------------------------------------------------------------------------------------------
-constexpr int HL_ROWS = 256;
+constexpr int HL_ROWS = HEAD_LOGITS_ROWS;
 
 __global__ __launch_bounds__(HL_ROWS) void head_logits_kernel(HeadOut a, const float *__restrict__ z4, int ldz4)
 {

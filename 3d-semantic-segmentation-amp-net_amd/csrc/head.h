@@ -98,6 +98,24 @@ int attention_core(const float *qkv, const uint8_t *key_pad_mask, float *probs, 
 // gradients of the above wrt q, k, v given d(ctx): dqkv [Q, 768]
 int attention_core_bwd(const float *qkv, const float *probs, const float *dctx, float *dqkv, int B, int W, float drop_p, uint32_t drop_base,
                        hipStream_t st);
+// conv_4 backward + dropout + bn_3 / ReLU mask (head_bwd.hip): one workgroup per HEAD_OUT_BWD_ROWS rows
+constexpr int HEAD_OUT_BWD_ROWS = 1024;
+struct HeadOutBwd {
+    const float *dlogits;      // [B, C, P]
+    const float *z3;           // [R, 64]
+    int z_bf16;                // z3 is a bf16 tensor (precision mode 3)
+    const float *scale, *shift, *mean, *invstd;   // bn_3 [64]
+    const float *W;            // [C, 64]
+    float drop_p;
+    uint32_t drop_seed;
+    int R, P, C;
+    float *dy3;                // [R, 64] masked gradient wrt bn_3 output
+    float *part_a, *part_b;    // [blocks, 64]
+    float *dWpart;             // [blocks, C * 64 + C]
+};
+int head_out_bwd(const HeadOutBwd &o, hipStream_t st);
+
+constexpr int HEAD_LOGITS_ROWS = 256;      // rows per workgroup of head_logits = one (sum w nll, sum w) partial
 // logits[b, c, p] = conv_4(dropout(relu(bn_3(z3))))[row = b * P + p]; optional weighted CE partials + argmax
 struct HeadOut {
     const float *z3 = nullptr;             // [R, 64]

@@ -12,20 +12,7 @@ namespace ampnet {
 namespace {
 
 constexpr int HB_WAVES = 4, HB_WROWS = 256, HB_ROWS = HB_WAVES * HB_WROWS;   // rows per wave / per workgroup
-
-struct HeadOutBwd {
-    const float *dlogits;      // [B, C, P]
-    const float *z3;           // [R, 64]
-    int z_bf16;                // z3 is a bf16 tensor (precision mode 3)
-    const float *scale, *shift, *mean, *invstd;   // bn_3 [64]
-    const float *W;            // [C, 64]
-    float drop_p;
-    uint32_t drop_seed;
-    int R, P, C;
-    float *dy3;                // [R, 64] masked gradient wrt bn_3 output
-    float *part_a, *part_b;    // [blocks, 64]
-    float *dWpart;             // [blocks, C * 64 + C]
-};
+static_assert(HB_ROWS == HEAD_OUT_BWD_ROWS, "head.h: HEAD_OUT_BWD_ROWS");
 
 // conv_4 backward + dropout + bn_3/ReLU mask, no LDS in the row loop: lane = channel k of the 64, a wave walks its rows.
 // Per row the lane loads z3[row][k] (one 256-byte line per wave), rebuilds a3 = dropout(relu(bn_3(z3))), forms
@@ -251,6 +238,14 @@ void head_bwd_carve(const HeadShape &s, void *base, HeadBwdWs &w)
 }
 
 
+int head_out_bwd(const HeadOutBwd &o, hipStream_t st)
+{
+    const int blocks = cdiv(o.R, HB_ROWS);
+    if (o.z_bf16) hipLaunchKernelGGL(head_out_bwd_kernel<true>, dim3(blocks), dim3(64 * HB_WAVES), 0, st, o);
+    else hipLaunchKernelGGL(head_out_bwd_kernel<false>, dim3(blocks), dim3(64 * HB_WAVES), 0, st, o);
+    return check_launch("head_out_bwd_kernel");
+}
+
 int attention_core_bwd(const float *qkv, const float *probs, const float *dctx, float *dqkv, int B, int W, float drop_p, uint32_t drop_base_,
                        hipStream_t st)
 {
@@ -281,9 +276,7 @@ int head_points_bwd(const HeadShape &s, HeadWs &f, HeadBwdWs &b, const HeadPoint
         o.W = p_.conv4_w; o.drop_p = drop_p; o.drop_seed = drop_base(seed, 2);
         o.R = R; o.P = R / B; o.C = C;
         o.dy3 = b.dy3; o.part_a = b.part_a; o.part_b = b.part_b; o.dWpart = b.w4part;
-        if (o.z_bf16) hipLaunchKernelGGL(head_out_bwd_kernel<true>, dim3(blocks), dim3(64 * HB_WAVES), 0, st, o);
-        else hipLaunchKernelGGL(head_out_bwd_kernel<false>, dim3(blocks), dim3(64 * HB_WAVES), 0, st, o);
-        TRY(check_launch("head_out_bwd_kernel"));
+        TRY(head_out_bwd(o, st));
         red[n_red++] = ReduceItem{b.w4part, blocks, (long)(C * 64 + C), 1, C * 64, C * 64, g.conv4_w, C * 64};
         red[n_red++] = ReduceItem{b.w4part + C * 64, blocks, (long)(C * 64 + C), 1, C, C, g.conv4_b, C};
         if (!fin_in_kernel) {                    // else conv_3's fused backward forms bn_3's constants from these partials itself

@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "bwd_misc.h"
 #include "encoder.h"
+#include "head.h"
 
 namespace ampnet {
 namespace {
@@ -450,4 +451,127 @@ extern "C" int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void
     }
     a.dWeff = d->dWeff; a.win_off = d->win_off; a.Q = d->Q; a.n_slots = d->n_slots;
     return pw_input_wgrad(a, st);
+}
+
+// ---- the head's kernels, the loss tail and the token path's small GEMMs (tests/test_head_layers_gpu.py) ------------------------------------
+namespace ampnet {
+namespace {
+// op 7: y[0][i] = __expf(x[i]) (attention_core), y[1][i] = expf(x[i]), y[2][i] = logf(x[i]) (head_logits, ce_bwd): the functions the softmax bars rest on
+__global__ __launch_bounds__(256) void exp_log_sweep_kernel(const float *__restrict__ x, float *__restrict__ y, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    y[i] = __expf(x[i]);
+    y[(size_t)n + i] = expf(x[i]);
+    y[2 * (size_t)n + i] = logf(x[i]);
+}
+}  // namespace
+}  // namespace ampnet
+
+extern "C" int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(d, "probe_head: null descriptor");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    AMPNET_REQUIRE(d->op >= 0 && d->op <= 7, "probe_head: op %d not built", d->op);
+    AMPNET_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "probe_head: drop_p %f", (double)d->drop_p);
+    if (d->op == 7) {
+        AMPNET_REQUIRE(d->rows >= 1 && d->rows <= (1 << 24) && d->X && d->X_n >= d->rows && d->dX && d->dX_n >= 3 * (int64_t)d->rows, "probe_head: sweep buffers short");
+        ProfScope prof("exp_log_sweep", 0.0, 0.0, st);
+        hipLaunchKernelGGL(exp_log_sweep_kernel, dim3(cdiv(d->rows, 256)), dim3(256), 0, st, d->X, d->dX, d->rows);
+        return check_launch("exp_log_sweep_kernel");
+    }
+    switch (d->op) {
+    case 0: {
+        AMPNET_REQUIRE(d->Q >= 1 && d->Q <= (1 << 20), "probe_head: Q %d", d->Q);
+        const int64_t Q = d->Q;
+        AMPNET_REQUIRE(d->gl && d->gl_n >= Q * HEAD_E && d->cent && d->cent_n >= Q * 2, "probe_head: gl / cent short");
+        AMPNET_REQUIRE(d->w1 && d->w1_n >= 32 && d->b1 && d->b1_n >= 16 && d->w2 && d->w2_n >= HEAD_E * 16 && d->b2 && d->b2_n >= HEAD_E,
+                       "probe_head: positional-encoding parameters short");
+        AMPNET_REQUIRE(d->tok && d->tok_n >= Q * HEAD_E, "probe_head: tok short");
+        AMPNET_REQUIRE((d->hid == nullptr) == (d->slope == nullptr) && (!d->hid || d->hid_n >= Q * 16), "probe_head: hid / slope short");
+        ProfScope prof("posenc_tokens", 0.0, 0.0, st);
+        return posenc_tokens(d->gl, d->cent, d->w1, d->b1, d->w2, d->b2, d->tok, d->Q, st, d->hid, d->slope);
+    }
+    case 1:
+    case 2: {
+        AMPNET_REQUIRE(d->B >= 1 && d->B <= 65535 && d->W >= 1 && d->W <= HEAD_MAX_W, "probe_head: B %d, W %d (1 <= W <= %d)", d->B, d->W, HEAD_MAX_W);
+        const int64_t BW = (int64_t)d->B * d->W, np = (int64_t)d->B * HEAD_HEADS * d->W * d->W;
+        AMPNET_REQUIRE(d->qkv && d->qkv_n >= BW * 3 * HEAD_E, "probe_head: qkv short");
+        if (d->op == 1) {
+            AMPNET_REQUIRE(!d->mask || d->mask_n >= BW, "probe_head: mask short");
+            AMPNET_REQUIRE(!d->probs || d->probs_n >= np, "probe_head: probs short");
+            AMPNET_REQUIRE(d->ctx && d->ctx_n >= BW * HEAD_E, "probe_head: ctx short");
+            ProfScope prof("attention_core", 0.0, 0.0, st);
+            return attention_core(d->qkv, d->mask, d->probs, d->ctx, d->B, d->W, d->drop_p, d->drop_seed, st);
+        }
+        AMPNET_REQUIRE(d->probs && d->probs_n >= np, "probe_head: probs short");
+        AMPNET_REQUIRE(d->dctx && d->dctx_n >= BW * HEAD_E && d->dqkv && d->dqkv_n >= BW * 3 * HEAD_E, "probe_head: dctx / dqkv short");
+        ProfScope prof("attention_core_bwd", 0.0, 0.0, st);
+        return attention_core_bwd(d->qkv, d->probs, d->dctx, d->dqkv, d->B, d->W, d->drop_p, d->drop_seed, st);
+    }
+    case 3:
+    case 4: {
+        AMPNET_REQUIRE(d->C >= 1 && d->C <= HEAD_MAX_CLASSES, "probe_head: %d classes, supported 1..%d", d->C, HEAD_MAX_CLASSES);
+        AMPNET_REQUIRE(d->R >= 1 && d->P >= 1 && d->R % d->P == 0, "probe_head: rows %d not a multiple of points per sample %d", d->R, d->P);
+        const int64_t R = d->R, C = d->C;
+        if (d->op == 3) {
+            const int64_t blocks = cdiv(d->R, HEAD_LOGITS_ROWS);
+            AMPNET_REQUIRE(d->z4 && covers(d->z4_n, R, d->ldz4, C), "probe_head: z4 [%d, %d] short", d->R, d->ldz4);
+            AMPNET_REQUIRE(d->logits && d->logits_n >= R * C, "probe_head: logits short");
+            AMPNET_REQUIRE(!d->targets || d->targets_n >= R, "probe_head: targets short");
+            AMPNET_REQUIRE(!d->class_w || d->class_w_n >= C, "probe_head: class_w short");
+            AMPNET_REQUIRE(!d->preds || d->preds_n >= R, "probe_head: preds short");
+            AMPNET_REQUIRE(!d->loss_part || d->loss_part_n >= blocks * 2, "probe_head: loss_part short");
+            AMPNET_REQUIRE(!d->loss_out || (d->loss_out_n >= 2 && d->loss_part && d->targets), "probe_head: loss_out needs 2 floats, loss_part and targets");
+            HeadOut o;
+            o.R = d->R; o.P = d->P; o.C = d->C;
+            o.logits = d->logits; o.targets = d->targets; o.class_w = d->class_w; o.preds = d->preds;
+            o.loss_part = d->targets ? d->loss_part : nullptr;
+            int nb = 0;
+            {
+                ProfScope prof("head_logits", 0.0, 0.0, st);
+                if (int rc = head_logits(o, d->z4, d->ldz4, &nb, st); rc != AMPNET_OK) return rc;
+            }
+            if (!d->loss_out) return AMPNET_OK;
+            ProfScope prof("loss_finalize", 0.0, 0.0, st);
+            return loss_finalize(d->loss_part, nb, d->loss_out, st);
+        }
+        const int64_t blocks = cdiv(d->R, HEAD_OUT_BWD_ROWS);
+        AMPNET_REQUIRE(d->dlogits && d->dlogits_n >= R * C, "probe_head: dlogits short");
+        AMPNET_REQUIRE(d->z3 && d->z3_n >= R * 64, "probe_head: z3 [%d, 64] short", d->R);
+        AMPNET_REQUIRE(d->scale && d->shift && d->mean && d->invstd && d->bn_n >= 64, "probe_head: bn_3 constants short");
+        AMPNET_REQUIRE(d->w4 && d->w4_n >= C * 64, "probe_head: w4 short");
+        AMPNET_REQUIRE(d->dy3 && d->dy3_n >= R * 64, "probe_head: dy3 short");
+        AMPNET_REQUIRE(d->part_a && d->part_b && d->part_n >= blocks * 64, "probe_head: part_a / part_b short (%lld workgroups)", (long long)blocks);
+        AMPNET_REQUIRE(d->w4part && d->w4part_n >= blocks * (C * 64 + C), "probe_head: w4part short");
+        HeadOutBwd o;
+        o.dlogits = d->dlogits; o.z3 = d->z3; o.z_bf16 = d->z_bf16 ? 1 : 0;
+        o.scale = d->scale; o.shift = d->shift; o.mean = d->mean; o.invstd = d->invstd;
+        o.W = d->w4; o.drop_p = d->drop_p; o.drop_seed = d->drop_seed;
+        o.R = d->R; o.P = d->P; o.C = d->C;
+        o.dy3 = d->dy3; o.part_a = d->part_a; o.part_b = d->part_b; o.dWpart = d->w4part;
+        ProfScope prof(o.z_bf16 ? "head_out_bwd<bf16>" : "head_out_bwd<f32>", 0.0, 0.0, st);
+        return head_out_bwd(o, st);
+    }
+    default: {   // 5, 6
+        AMPNET_REQUIRE(d->rows >= 1 && d->n_out >= 1 && d->n_in >= 1 && d->rows <= (1 << 20) && d->n_out <= 8192 && d->n_in <= 8192,
+                       "probe_head: rows %d, n_out %d, n_in %d", d->rows, d->n_out, d->n_in);
+        const int64_t rows = d->rows, no = d->n_out, ni = d->n_in;
+        AMPNET_REQUIRE(d->G && covers(d->G_n, rows, d->ldg, no) && d->X && covers(d->X_n, rows, d->ldx, ni), "probe_head: G / X short");
+        AMPNET_REQUIRE(d->dW && covers(d->dW_n, no, d->lddw, ni), "probe_head: dW short");
+        AMPNET_REQUIRE(!d->db || d->db_n >= no, "probe_head: db short");
+        if (d->op == 6) {
+            AMPNET_REQUIRE(d->db, "probe_head: sgemm_wgrad_bias writes db");
+            return sgemm_wgrad_bias(d->rows, d->n_out, d->n_in, d->G, d->ldg, d->X, d->ldx, d->dW, d->lddw, d->db, st);
+        }
+        AMPNET_REQUIRE(d->Wl && covers(d->Wl_n, no, d->ldw, ni), "probe_head: W short");
+        AMPNET_REQUIRE(d->dX && covers(d->dX_n, rows, d->lddx, ni), "probe_head: dX short");
+        AMPNET_REQUIRE(!d->dx_mul || covers(d->dx_mul_n, rows, d->lddx, ni), "probe_head: dx_mul short");
+        LinBwdOpt o;
+        o.db = d->db;
+        o.dx_mul = d->dx_mul;
+        return sgemm_linear_bwd(d->rows, d->n_out, d->n_in, d->G, d->ldg, d->X, d->ldx, d->Wl, d->ldw, d->dW, d->lddw, d->dX, d->lddx, st, o);
+    }
+    }
 }

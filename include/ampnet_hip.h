@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 6
+#define AMPNET_ABI_VERSION 7
 
 enum {
     AMPNET_OK = 0,
@@ -555,10 +555,61 @@ typedef struct AmpnetPwPlan {
     int32_t bwd_blocks, bwd_item_rows, bwd_x3;                    /* pw_bwd_blocks, pw_bwd_item_rows, pw_bwd_x3_supported(bwd) (-1: bwd NULL) */
 } AmpnetPwPlan;
 
+/* One launch of a kernel of the segmentation head, the loss tail or the small-GEMM token path (ABI 7), by `op`:
+ *   0 posenc_tokens       (gl [Q, 256], cent [Q, 2], w1 [16, 2], b1 [16], w2 [256, 16], b2 [256] -> tok [Q, 256]; hid / slope [Q, 16] both or neither)
+ *   1 attention_core      (qkv [B * W, 768], mask [B, W] or NULL -> probs [B, 8, W, W] or NULL, ctx [B * W, 256]; drop_p, drop_seed = the hash base)
+ *   2 attention_core_bwd  (qkv, probs, dctx [B * W, 256] -> dqkv [B * W, 768])
+ *   3 head_logits (+ loss_finalize when loss_out is given)
+ *                         (z4 [R, ldz4] -> logits [R / P, C, P]; preds [R], targets [R], class_w [C], loss_part [cdiv(R, 256), 2], loss_out [2]
+ *                          optional; as in the head's forward the kernel gets loss_part only together with targets)
+ *   4 head_out_bwd        (dlogits [R / P, C, P], z3 [R, 64] fp32 or (z_bf16) bf16, scale / shift / mean / invstd [64], w4 [C, 64]
+ *                          -> dy3 [R, 64], part_a / part_b [cdiv(R, 1024), 64], w4part [cdiv(R, 1024), C * 64 + C])
+ *   5 sgemm_linear_bwd    (G [rows, n_out] ldg, X [rows, n_in] ldx, Wl [n_out, n_in] ldw -> dW [n_out, n_in] lddw, dX [rows, n_in] lddx;
+ *                          db [n_out] and dx_mul [rows, n_in] (lddx) optional)
+ *   6 sgemm_wgrad_bias    (G, X -> dW, db)
+ *   7 exp / log sweep     (X [rows] -> dX [3, rows] = __expf(x), expf(x), logf(x): the device functions the softmax bars of the tests rest on)
+ * 1 <= W <= 32, 1 <= C <= 8, R % P == 0 and every extent are checked on the host before the launch.  The launch is recorded under the
+ * kernel's name for ampnet_profile_read ("head_out_bwd<f32>" / "head_out_bwd<bf16>" by z_bf16; the small GEMMs record their own).
+ * z3_n counts elements of z3's own type.                                                                                        */
+typedef struct AmpnetHeadProbe {
+    int32_t op, B, W, Q, R, P, C, ldz4, z_bf16, rows, n_out, n_in, ldg, ldx, ldw, lddw, lddx, pad0;
+    float drop_p; uint32_t drop_seed;
+    const float *gl, *cent, *w1, *b1, *w2, *b2; int64_t gl_n, cent_n, w1_n, b1_n, w2_n, b2_n;
+    float *tok, *hid, *slope; int64_t tok_n, hid_n;              /* hid_n: hid and slope each */
+    const float *qkv; int64_t qkv_n;
+    const uint8_t *mask; int64_t mask_n;
+    float *probs; int64_t probs_n;                               /* written by op 1, read by op 2 */
+    float *ctx; int64_t ctx_n;
+    const float *dctx; int64_t dctx_n;
+    float *dqkv; int64_t dqkv_n;
+    const float *z4; int64_t z4_n;
+    float *logits; int64_t logits_n;
+    const long long *targets; int64_t targets_n;
+    const float *class_w; int64_t class_w_n;
+    long long *preds; int64_t preds_n;
+    float *loss_part; int64_t loss_part_n;
+    float *loss_out; int64_t loss_out_n;
+    const float *dlogits; int64_t dlogits_n;
+    const float *z3; int64_t z3_n;
+    const float *scale, *shift, *mean, *invstd; int64_t bn_n;    /* [64] each */
+    const float *w4; int64_t w4_n;
+    float *dy3; int64_t dy3_n;
+    float *part_a, *part_b; int64_t part_n;                      /* each */
+    float *w4part; int64_t w4part_n;
+    const float *G; int64_t G_n;
+    const float *X; int64_t X_n;
+    const float *Wl; int64_t Wl_n;
+    float *dW; int64_t dW_n;
+    float *dX; int64_t dX_n;
+    float *db; int64_t db_n;
+    const float *dx_mul; int64_t dx_mul_n;
+} AmpnetHeadProbe;
+
 int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream);
 int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream);
 int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream);
 int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void *stream);
+int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream);
 int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, int cout, int stat_chunks, const AmpnetPwBwdProbe *bwd, AmpnetPwPlan *out_host);
 
 #ifdef __cplusplus

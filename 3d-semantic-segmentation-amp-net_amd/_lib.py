@@ -5,6 +5,7 @@ gets an exception.  torch is imported first so that the HIP runtime torch alread
 (its bundled libamdhip64, SONAME libamdhip64.so.7) is the one this library binds to -- two HIP runtimes in
 one process would not share device pointers.
 """
+import contextlib
 import ctypes
 import os
 
@@ -12,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 
@@ -73,8 +74,57 @@ def set_matrix_precision(mode):
     check(lib().ampnet_set_matrix_precision(PRECISIONS[mode]), "ampnet_set_matrix_precision")
 
 
+_MODE_NAMES = {0: "fp32", 1: "bf16", 2: "bf16_train", 3: "bf16_store", 4: "f32x3"}
+PRECISION_NAMES = ("fp32", "f32x3", "bf16", "bf16_train", "bf16_store")   # the canonical names: what --precision offers
+
+
 def get_matrix_precision():
-    return {0: "fp32", 1: "bf16", 2: "bf16_train", 3: "bf16_store", 4: "f32x3"}[lib().ampnet_get_matrix_precision()]
+    """The process-wide default (set_matrix_precision); a precision_scope does not show here."""
+    return _MODE_NAMES[lib().ampnet_get_matrix_precision()]
+
+
+def effective_matrix_precision():
+    """What an entry point called on THIS thread would dispatch on: the innermost precision_scope, else the process-wide default."""
+    return _MODE_NAMES[lib().ampnet_effective_matrix_precision()]
+
+
+def checked_precision(mode):
+    if mode not in PRECISIONS:
+        raise ValueError(f"unknown matrix precision {mode!r}: one of {list(PRECISION_NAMES)}")
+    return mode
+
+
+@contextlib.contextmanager
+def precision_scope(mode):
+    """Runs the body with `mode` as the matrix precision of every C-ABI call made on this thread (include/ampnet_hip.h:
+    ampnet_precision_scope_begin / _end), whatever the process-wide default is; other threads and the default are untouched.
+    mode=None: no scope, the calls follow the default.  The scope is closed when the body raises, too."""
+    if mode is None:
+        yield
+        return
+    L = lib()
+    check(L.ampnet_precision_scope_begin(PRECISIONS[checked_precision(mode)]), "ampnet_precision_scope_begin")
+    try:
+        yield
+    finally:
+        check(L.ampnet_precision_scope_end(), "ampnet_precision_scope_end")
+
+
+def resolve_precision(explicit=None):
+    """The precision a driver runs in: the explicit value (a keyword argument, a --precision flag), else AMPNET_PRECISION from the
+    environment, else None = follow the library's process-wide default (fp32 unless set_matrix_precision changed it)."""
+    mode = explicit if explicit is not None else (os.environ.get("AMPNET_PRECISION") or None)
+    return None if mode is None else checked_precision(mode)
+
+
+def describe_precision(mode):
+    """For the line a driver logs at start: the mode's name, or what None falls back to."""
+    return mode if mode is not None else f"library default ({get_matrix_precision()})"
+
+
+def tape_conflict(a, b):
+    """True when two precisions cannot share a train step: 'bf16_store' keeps the saved activations as bf16, every other mode as fp32."""
+    return a is not None and b is not None and (PRECISIONS[a] == 3) != (PRECISIONS[b] == 3)
 
 
 def check(rc, what):

@@ -5,6 +5,10 @@ logits, loss.backward(), optimizer.step() (train_pointnet-attention.py:396-470) 
 the HIP forward.  These Functions call the C-ABI backward entry points; every forward in grad mode keeps a private
 workspace alive until its backward has run (the reference makes W encoder calls before one backward).
 The package's own train_loop does not go through autograd (trainer.fused_train_step).
+
+Matrix precision: each forward opens _lib.precision_scope(module.precision) and records the mode it actually ran in on ctx; the
+backward opens a scope with THAT mode.  It reads neither the module's attribute (which may have changed since) nor the process-wide
+default, and the scope stack is per thread: autograd runs the backward on a thread of its own.
 """
 import torch
 
@@ -22,7 +26,9 @@ class _EncoderFn(torch.autograd.Function):
     def forward(ctx, meta, x, *params):
         module, pt, bt, off, Q, total, mx, n_slots = meta
         ws = ops.Workspace()
-        local, glob, feat_T, _ = ops.encoder_forward(pt, bt, x, off, Q, total, mx, n_slots, True, ws)
+        with _lib.precision_scope(module.precision):
+            ctx.precision = _lib.effective_matrix_precision()
+            local, glob, feat_T, _ = ops.encoder_forward(pt, bt, x, off, Q, total, mx, n_slots, True, ws)
         # tensors go through save_for_backward: keeping an OUTPUT on ctx directly makes an output -> grad_fn -> ctx -> output cycle
         # the garbage collector cannot break, i.e. the whole activation workspace leaks when the backward never runs
         ctx.save_for_backward(x, local, feat_T)
@@ -36,9 +42,10 @@ class _EncoderFn(torch.autograd.Function):
         named = dict(module.named_parameters())
         grads = {n: torch.empty_like(named[n]) for n in P.ENC_PARAMS}
         gt = ops.PointerTable(P.ENC_PARAMS, grads, "encoder gradients")
-        ops.encoder_backward(pt, gt, x, off, Q, total, mx, n_slots, local, feat_T,
-                             d_local.contiguous().float(), d_glob.contiguous().float(), d_ft.contiguous().float(),
-                             ws, ops.Workspace())
+        with _lib.precision_scope(ctx.precision):
+            ops.encoder_backward(pt, gt, x, off, Q, total, mx, n_slots, local, feat_T,
+                                 d_local.contiguous().float(), d_glob.contiguous().float(), d_ft.contiguous().float(),
+                                 ws, ops.Workspace())
         ctx.meta = None
         return (None, None) + tuple(grads[n] for n in P.ENC_PARAMS)
 
@@ -55,7 +62,9 @@ class _HeadFn(torch.autograd.Function):
     def forward(ctx, meta, gl, lo, *params):
         module, pt, bt, cent, off, mask, B, W, total, mx, n_classes, p_drop, seed = meta
         ws = ops.Workspace()
-        logits, _, _ = ops.head_forward(pt, bt, gl, lo, cent, off, mask, B, W, total, mx, n_classes, True, p_drop, seed, ws)
+        with _lib.precision_scope(module.precision):
+            ctx.precision = _lib.effective_matrix_precision()
+            logits, _, _ = ops.head_forward(pt, bt, gl, lo, cent, off, mask, B, W, total, mx, n_classes, True, p_drop, seed, ws)
         ctx.save_for_backward(lo)
         ctx.meta = (module, pt, cent, off, B, W, total, mx, n_classes, p_drop, seed, ws)
         return logits
@@ -68,8 +77,9 @@ class _HeadFn(torch.autograd.Function):
         named = dict(module.named_parameters())
         grads = {n: torch.empty_like(named[n]) for n in table}
         gt = ops.PointerTable(table, grads, "head gradients")
-        d_lo, d_gl = ops.head_backward(pt, gt, lo, cent, off, B, W, total, mx, n_classes, p_drop, seed,
-                                       dlogits.contiguous().float(), ws, ops.Workspace())
+        with _lib.precision_scope(ctx.precision):
+            d_lo, d_gl = ops.head_backward(pt, gt, lo, cent, off, B, W, total, mx, n_classes, p_drop, seed,
+                                           dlogits.contiguous().float(), ws, ops.Workspace())
         ctx.meta = None
         return (None, d_gl, d_lo) + tuple(grads[n] for n in table)
 
@@ -92,7 +102,9 @@ class _GruHeadFn(torch.autograd.Function):
     def forward(ctx, meta, gl, lo, *params):
         module, pt, bt, off, B, W, total, mx, n_classes, p_drop, seed = meta
         ws = ops.Workspace()
-        logits, _, _ = ops.gru_head_forward(pt, bt, gl, lo, off, B, W, total, mx, n_classes, True, p_drop, seed, ws)
+        with _lib.precision_scope(module.precision):
+            ctx.precision = _lib.effective_matrix_precision()
+            logits, _, _ = ops.gru_head_forward(pt, bt, gl, lo, off, B, W, total, mx, n_classes, True, p_drop, seed, ws)
         ctx.save_for_backward(gl, lo)
         ctx.meta = (module, pt, off, B, W, total, mx, n_classes, p_drop, seed, ws)
         return logits
@@ -105,8 +117,9 @@ class _GruHeadFn(torch.autograd.Function):
         named = dict(module.named_parameters())
         grads = {n: torch.empty_like(named[n]) for n in table}
         gt = ops.PointerTable(table, grads, "GRU head gradients")
-        d_lo, d_gl = ops.gru_head_backward(pt, gt, gl, lo, off, B, W, total, mx, n_classes, p_drop, seed,
-                                           dlogits.contiguous().float(), ws, ops.Workspace())
+        with _lib.precision_scope(ctx.precision):
+            d_lo, d_gl = ops.gru_head_backward(pt, gt, gl, lo, off, B, W, total, mx, n_classes, p_drop, seed,
+                                               dlogits.contiguous().float(), ws, ops.Workspace())
         ctx.meta = None
         return (None, d_gl, d_lo) + tuple(grads[n] for n in table)
 
@@ -127,7 +140,9 @@ class _ClsHeadFn(torch.autograd.Function):
     def forward(ctx, meta, gl, *params):
         module, pt, bt, mask, B, W, n_classes, p_drop, seed = meta
         ws = ops.Workspace()
-        out, aw = ops.cls_head_forward(pt, bt, gl, mask, B, W, n_classes, True, p_drop, seed, ws)
+        with _lib.precision_scope(module.precision):
+            ctx.precision = _lib.effective_matrix_precision()
+            out, aw = ops.cls_head_forward(pt, bt, gl, mask, B, W, n_classes, True, p_drop, seed, ws)
         ctx.save_for_backward(gl)
         ctx.meta = (module, pt, B, W, n_classes, p_drop, seed, ws)
         ctx.mark_non_differentiable(aw)
@@ -141,7 +156,8 @@ class _ClsHeadFn(torch.autograd.Function):
         named = dict(module.named_parameters())
         grads = {n: torch.empty_like(named[n]) for n in table}
         gt = ops.PointerTable(table, grads, "classification head gradients")
-        d_gl = ops.cls_head_backward(pt, gt, gl, B, W, n_classes, p_drop, seed, d_out.contiguous().float(), ws, ops.Workspace())
+        with _lib.precision_scope(ctx.precision):
+            d_gl = ops.cls_head_backward(pt, gt, gl, B, W, n_classes, p_drop, seed, d_out.contiguous().float(), ws, ops.Workspace())
         ctx.meta = None
         return (None, d_gl) + tuple(grads[n] for n in table)
 

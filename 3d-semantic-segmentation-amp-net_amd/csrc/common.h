@@ -35,7 +35,8 @@ struct ProfScope {
     hipStream_t st;
 };
 
-// process-wide MFMA operand precision (ampnet_set_matrix_precision)
+// MFMA operand precision a dispatch on this thread sees: the top of the thread's scope stack (ampnet_precision_scope_begin), else the
+// process-wide default (ampnet_set_matrix_precision)
 int matrix_precision();
 
 // forward-workspace precision tags (core.hip): set by a train-mode forward, checked by its backward

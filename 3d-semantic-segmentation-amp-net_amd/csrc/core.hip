@@ -98,7 +98,21 @@ extern "C" int ampnet_profile_read(int max_rows, char *names, double *ms, long l
 
 namespace ampnet {
 static int g_matrix_precision = AMPNET_PRECISION_F32;
-int matrix_precision() { return g_matrix_precision; }
+// scoped override (ampnet_precision_scope_begin / _end): a per-thread stack whose top, when there is one, every dispatch sees instead of
+// the process-wide default -- autograd runs a backward on a thread of its own, so the scope has to travel with the call, not the process
+namespace {
+struct PrecisionStack {
+    int mode[AMPNET_PRECISION_SCOPE_DEPTH];
+    int depth;
+};
+thread_local PrecisionStack t_precision = {{0}, 0};
+bool valid_precision(int mode)
+{
+    return mode == AMPNET_PRECISION_F32 || mode == AMPNET_PRECISION_BF16 || mode == AMPNET_PRECISION_BF16_TRAIN || mode == AMPNET_PRECISION_BF16_STORE ||
+           mode == AMPNET_PRECISION_F32_SPLIT;
+}
+}  // namespace
+int matrix_precision() { return t_precision.depth > 0 ? t_precision.mode[t_precision.depth - 1] : g_matrix_precision; }
 }  // namespace ampnet
 
 // ---- forward-workspace tags: which precision mode a train-mode forward ran in ------------------------------------------------
@@ -144,7 +158,7 @@ int ws_tag_check(const void *ws, const char *who)
     const int now = matrix_precision();
     if ((have == AMPNET_PRECISION_BF16_STORE) != (now == AMPNET_PRECISION_BF16_STORE))
         return fail(AMPNET_E_ARG, "%s: the forward ran in matrix precision mode %d, the backward is called in mode %d "
-                                  "(ampnet_set_matrix_precision changed in between): the saved activations (%s) would be misread", who, have, now,
+                                  "(ampnet_set_matrix_precision or the precision scope changed in between): the saved activations (%s) would be misread", who, have, now,
                     have == AMPNET_PRECISION_BF16_STORE ? "bf16" : "fp32");
     return AMPNET_OK;
 }
@@ -152,13 +166,30 @@ int ws_tag_check(const void *ws, const char *who)
 
 extern "C" int ampnet_set_matrix_precision(int mode)
 {
-    if (mode != AMPNET_PRECISION_F32 && mode != AMPNET_PRECISION_BF16 && mode != AMPNET_PRECISION_BF16_TRAIN && mode != AMPNET_PRECISION_BF16_STORE &&
-        mode != AMPNET_PRECISION_F32_SPLIT)
+    if (!ampnet::valid_precision(mode))
         return ampnet::fail(AMPNET_E_ARG, "ampnet_set_matrix_precision: mode %d", mode);
     ampnet::g_matrix_precision = mode;
     return AMPNET_OK;
 }
 extern "C" int ampnet_get_matrix_precision(void) { return ampnet::g_matrix_precision; }
+extern "C" int ampnet_effective_matrix_precision(void) { return ampnet::matrix_precision(); }
+
+extern "C" int ampnet_precision_scope_begin(int mode)
+{
+    using namespace ampnet;
+    if (!valid_precision(mode)) return fail(AMPNET_E_ARG, "ampnet_precision_scope_begin: mode %d", mode);
+    if (t_precision.depth >= AMPNET_PRECISION_SCOPE_DEPTH)
+        return fail(AMPNET_E_ARG, "ampnet_precision_scope_begin: more than %d nested scopes on this thread", AMPNET_PRECISION_SCOPE_DEPTH);
+    t_precision.mode[t_precision.depth++] = mode;
+    return AMPNET_OK;
+}
+extern "C" int ampnet_precision_scope_end(void)
+{
+    using namespace ampnet;
+    if (t_precision.depth <= 0) return fail(AMPNET_E_ARG, "ampnet_precision_scope_end: no scope is open on this thread");
+    --t_precision.depth;
+    return AMPNET_OK;
+}
 
 extern "C" int ampnet_abi_version(void) { return AMPNET_ABI_VERSION; }
 extern "C" const char *ampnet_last_error(void) { return ampnet::err_buf(); }

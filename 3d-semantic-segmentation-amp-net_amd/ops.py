@@ -14,12 +14,15 @@ from . import params as P
 class PointerTable:
     """Host array of device pointers in the ABI's fixed order, built from {state_dict key: GPU tensor}."""
 
-    def __init__(self, table, tensors, what):
+    def __init__(self, table, tensors, what, precision=None):
         self.names = list(table.keys())
         missing = [n for n in self.names if n not in tensors]
         if missing:
             raise _lib.AmpnetError(f"{what}: missing tensors {missing[:4]}...")
         self.keep = []
+        # matrix precision of the module the table was built for, None = the default: for callers that launch for a module of which they
+        # hold only the tables (head_forward_files)
+        self.precision = precision
         arr = (ctypes.c_void_p * len(self.names))()
         for i, n in enumerate(self.names):
             t = tensors[n]
@@ -137,7 +140,8 @@ def head_forward(head_params, head_buffers, gl, lo, centroids, win_off, mask, B,
 def head_forward_files(head_params, head_buffers, gl, lo, centroids, win_off, mask, n_files, W, total_rows, max_rows, n_classes, ws):
     """Eval forward of the attention head for several files at once (include/ampnet_hip.h: ampnet_head_fwd_files_f32): gl [n_files*W, 256],
     lo [total_rows, 64], centroids [n_files, W, 2], win_off [n_files*W + 1] (unused slots = zero-row windows), mask [n_files, W] uint8
-    -> (logits [n_classes, total_rows], preds [total_rows] int64)."""
+    -> (logits [n_classes, total_rows], preds [total_rows] int64).  Runs in the matrix precision of the head the parameter table belongs to
+    (head_params.precision), like the head's own forward_rows."""
     for t, name in ((gl, "gl"), (lo, "lo"), (centroids, "centroids"), (mask, "mask")):
         _lib.require_gpu(t, name)
     if tuple(gl.shape) != (n_files * W, P.GLOBAL_DIM) or tuple(lo.shape) != (total_rows, P.LOCAL_DIM) or tuple(centroids.shape) != (n_files, W, 2) \
@@ -147,10 +151,11 @@ def head_forward_files(head_params, head_buffers, gl, lo, centroids, win_off, ma
     dev = gl.device
     L = _lib.lib()
     L.ampnet_head_workspace_bytes.restype = ctypes.c_size_t
-    buf = ws.get(L.ampnet_head_workspace_bytes(n_files, W, total_rows, max_rows, n_classes, 0), dev)
+    with _lib.precision_scope(head_params.precision):
+        buf = ws.get(L.ampnet_head_workspace_bytes(n_files, W, total_rows, max_rows, n_classes, 0), dev)
     logits = torch.empty((n_classes, total_rows), dtype=torch.float32, device=dev)
     preds = torch.empty(total_rows, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), _lib.precision_scope(head_params.precision):
         rc = L.ampnet_head_fwd_files_f32(head_params.arr, head_buffers.arr, _lib.ptr(gl.contiguous().float()), _lib.ptr(lo.contiguous().float()),
                                          _lib.ptr(centroids.contiguous().float()), _lib.ptr(win_off), _lib.ptr(mask.contiguous()), n_files, W,
                                          total_rows, max_rows, n_classes, _lib.ptr(logits), _lib.ptr(preds), _lib.ptr(buf),

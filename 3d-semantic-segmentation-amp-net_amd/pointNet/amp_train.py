@@ -16,6 +16,7 @@ import time
 import numpy as np
 import torch
 
+from .._lib import describe_precision, resolve_precision
 from ..trainer import FusedAdam, shard_indices
 from ..utils.get_metrics import get_accuracy, get_iou_obj
 from ..utils.utils import limit_host_threads, rm_padding, save_checkpoint_segmen_model
@@ -113,14 +114,19 @@ def reduce_epoch_metrics(sums, ious, device=None):
 
 
 def train_att(task, dataset_folder, path_list_files, output_folder, n_points, batch_size, epochs, learning_rate,
-              weighing_method='EFS', beta=0.999, number_of_workers=4, model_checkpoint=None, device='cuda', sync_bn=None):
+              weighing_method='EFS', beta=0.999, number_of_workers=4, model_checkpoint=None, device='cuda', sync_bn=None, precision=None):
     """sync_bn (default: AMPNET_SYNC_BN=1 in the environment): under data parallelism, BatchNorm statistics and the loss normalisation
     over the GLOBAL batch, i.e. the single-device semantics of the reference at batch_size x world (trainer.enable_sync_batchnorm);
-    off, every rank normalises over its own batch_size samples."""
+    off, every rank normalises over its own batch_size samples.
+    precision: the matrix precision both networks run in ('fp32', 'f32x3', 'bf16', 'bf16_train', 'bf16_store'); None: AMPNET_PRECISION from
+    the environment, else the library's process-wide default."""
     if task != 'segmentation':
         raise NotImplementedError("only the segmentation task is on the AMP-Net hot path")
     start = time.time()
     rank, world, local = _dist_setup()
+    precision = resolve_precision(precision)
+    if rank == 0:
+        print("matrix precision:", describe_precision(precision), flush=True)
     limit_host_threads(reserve=number_of_workers)        # the main process's torch pool next to the loader's workers (utils.host_cpu_budget)
     if world > 1 and (sync_bn if sync_bn is not None else os.environ.get("AMPNET_SYNC_BN") == "1"):
         from ..trainer import enable_sync_batchnorm
@@ -156,8 +162,8 @@ def train_att(task, dataset_folder, path_list_files, output_folder, n_points, ba
     if rank == 0:
         print(f'Dataset folder: {dataset_folder}\nSamples for training: {len(train_ds)} (per rank), validation: {len(val_ds)}')
 
-    pointnet = BasePointNet(point_dimension=3, return_local_features=True, global_feat_dim=GLOBAL_FEAT_SIZE, device=device)
-    att_net = SegmentationWithAttention(GLOBAL_FEAT_SIZE, ATT_HEADS, num_classes=5, local_dim=64, device=device)
+    pointnet = BasePointNet(point_dimension=3, return_local_features=True, global_feat_dim=GLOBAL_FEAT_SIZE, device=device, precision=precision)
+    att_net = SegmentationWithAttention(GLOBAL_FEAT_SIZE, ATT_HEADS, num_classes=5, local_dim=64, device=device, precision=precision)
     att_net.seed = (att_net.seed ^ (rank * 0x9E3779B9)) & 0xFFFFFFFF      # data parallel: every rank draws its own dropout masks
     c_weights = torch.FloatTensor([1, 2, 2, 1, 1]).to(device)
     ce_loss = torch.nn.CrossEntropyLoss(weight=c_weights, reduction='mean', ignore_index=-1)

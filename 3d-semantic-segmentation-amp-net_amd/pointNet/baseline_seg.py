@@ -13,6 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .._lib import describe_precision, resolve_precision
 from ..utils.get_metrics import get_accuracy, get_iou_obj
 from ..utils.utils import rotate_point_cloud_z, save_checkpoint
 from .datasets import LidarDatasetExpanded
@@ -47,20 +48,23 @@ def train_loop(data, optimizer, ce_loss, pointnet, w_tensorboard=None, train=Tru
     return metrics, targets.detach().cpu(), preds, last_epoch
 
 
-def _model(model, device):
+def _model(model, device, precision=None):
     if model == 'light':
         from .model.light_pointnet_256 import SegmentationPointNet
-        return SegmentationPointNet(num_classes=NUM_CLASES, point_dimension=2, device=device)
+        return SegmentationPointNet(num_classes=NUM_CLASES, point_dimension=2, device=device, precision=precision)
     from .model.pointnet import SegmentationPointNet
-    return SegmentationPointNet(num_classes=NUM_CLASES, point_dimension=3, device=device)
+    return SegmentationPointNet(num_classes=NUM_CLASES, point_dimension=3, device=device, precision=precision)
 
 
 def train(dataset_folder, path_list_files, output_folder, n_points, batch_size, epochs, learning_rate, number_of_workers=0,
-          model_checkpoint=None, c_sample=False, model='pointnet', device='cuda'):
+          model_checkpoint=None, c_sample=False, model='pointnet', device='cuda', precision=None):
     """Drop-in for train_segmentation.py:33-271: Adam, MultiStepLR [50, 100, 300] gamma 0.5, checkpoint (utils.save_checkpoint keys)
     whenever the mean validation loss improves.  `model`: 'pointnet' (pointNet/model/pointnet.py, the one that runs in the reference,
-    SURVEY F4) or 'light' (light_pointnet_256.py with point_dimension=2).  Returns the per-epoch history."""
+    SURVEY F4) or 'light' (light_pointnet_256.py with point_dimension=2).  `precision`: the matrix precision the network runs in; None:
+    AMPNET_PRECISION from the environment, else the library's default.  Returns the per-epoch history."""
     start = time.time()
+    precision = resolve_precision(precision)
+    print("matrix precision:", describe_precision(precision), flush=True)
     with open(os.path.join(path_list_files, 'train_seg_files.txt')) as f:
         train_files = f.read().splitlines()
     with open(os.path.join(path_list_files, 'val_seg_files.txt')) as f:
@@ -69,7 +73,7 @@ def train(dataset_folder, path_list_files, output_folder, n_points, batch_size, 
         LidarDatasetExpanded(dataset_folder=dataset_folder, task='segmentation', number_of_points=n_points, files=files, fixed_num_points=True),
         batch_size=batch_size, shuffle=True, num_workers=number_of_workers, drop_last=True)
     train_loader, val_loader = mk(train_files), mk(val_files)
-    pointnet = _model(model, torch.device(device))
+    pointnet = _model(model, torch.device(device), precision)
     optimizer = torch.optim.Adam(pointnet.parameters(), lr=learning_rate)
     ce_loss = torch.nn.CrossEntropyLoss(weight=torch.FloatTensor([1, 2, 2, 1, 1]).to(device), reduction='mean', ignore_index=-1)
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[50, 100, 300], gamma=0.5)
@@ -107,15 +111,17 @@ def train(dataset_folder, path_list_files, output_folder, n_points, batch_size, 
 
 
 def test(dataset_folder, n_points, output_folder, number_of_workers, model_checkpoint, path_list_files='pointNet/data/train_test_files/RGBN',
-         model='pointnet', device='cuda'):
+         model='pointnet', device='cuda', precision=None):
     """Drop-in for pointNet/baseline/test_segmentation.py: one file per step (batch 1, all its points), per-class IoU, mean IoU and
-    accuracy over the test list.  Returns the summary dict (the reference prints it and appends a CSV row)."""
+    accuracy over the test list.  Returns the summary dict (the reference prints it and appends a CSV row).  `precision`: as train's."""
+    precision = resolve_precision(precision)
+    print("matrix precision:", describe_precision(precision), flush=True)
     ck = torch.load(model_checkpoint, map_location=device, weights_only=True)
     with open(os.path.join(path_list_files, 'test_seg_files.txt')) as f:
         files = f.read().splitlines()
     ds = LidarDatasetExpanded(dataset_folder=dataset_folder, task='segmentation', number_of_points=n_points, files=files, fixed_num_points=False)
     loader = torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, num_workers=number_of_workers, drop_last=False)
-    net = _model(model, torch.device(device))
+    net = _model(model, torch.device(device), precision)
     net.load_state_dict(ck['model'])
     net.eval()
     names = ['bckg', 'tower', 'cables', 'low_veg', 'high_veg']

@@ -14,6 +14,7 @@ import time
 import numpy as np
 import torch
 
+from .._lib import describe_precision, resolve_precision
 from ..trainer import FusedAdam
 from ..utils.get_metrics import get_accuracy, get_iou_obj
 from ..utils.utils import get_labels, kmeans_clustering, save_checkpoint_segmen_model
@@ -55,10 +56,13 @@ def _epoch(loader, train, pointnet, pred_net, opt_p, opt_g, ce_loss, epoch):
 
 
 def train_gru(task, dataset_folder, path_list_files, output_folder, n_points, n_windows, batch_size, epochs, learning_rate,
-              weighing_method='EFS', beta=0.999, number_of_workers=4, model_checkpoint=None, c_sample=False, use_kmeans=True, device='cuda'):
+              weighing_method='EFS', beta=0.999, number_of_workers=4, model_checkpoint=None, c_sample=False, use_kmeans=True, device='cuda', precision=None):
+    """precision: the matrix precision both networks run in; None: AMPNET_PRECISION from the environment, else the library's default."""
     if task != 'segmentation':
         raise NotImplementedError("the reference's GRU train_loop only reaches a model call for task='segmentation'")
     start = time.time()
+    precision = resolve_precision(precision)
+    print("matrix precision:", describe_precision(precision), flush=True)
     device = torch.device(device)
     with open(os.path.join(path_list_files, 'train_seg_files.txt')) as f:
         train_files = f.read().splitlines()
@@ -75,8 +79,9 @@ def train_gru(task, dataset_folder, path_list_files, output_folder, n_points, n_
     from .amp_train import start_workers
     start_workers(val_loader, train_loader)
     print(f'Dataset folder: {dataset_folder}\nSamples for training: {len(train_ds)}\nSamples for validation: {len(val_ds)}')
-    pointnet = BasePointNet(point_dimension=3, return_local_features=True, global_feat_dim=GLOBAL_FEAT_SIZE, device=device)
-    pred_net = SegmentationWithGRU(num_classes=NUM_CLASSES, global_feat_size=GLOBAL_FEAT_SIZE, hidden_size=HIDDEN_SIZE, device=device)
+    pointnet = BasePointNet(point_dimension=3, return_local_features=True, global_feat_dim=GLOBAL_FEAT_SIZE, device=device, precision=precision)
+    pred_net = SegmentationWithGRU(num_classes=NUM_CLASSES, global_feat_size=GLOBAL_FEAT_SIZE, hidden_size=HIDDEN_SIZE, device=device,
+                                   precision=precision)
     ce_loss = torch.nn.CrossEntropyLoss(reduction='mean', ignore_index=-1)
     opt_p = FusedAdam(pointnet.parameters(), lr=learning_rate)
     opt_g = FusedAdam(pred_net.parameters(), lr=learning_rate)
@@ -115,8 +120,12 @@ def segment_file(base_pointnet, segmen_net, clusters_list, device):
     return preds.reshape(-1).cpu(), targets.reshape(-1)
 
 
-def test(dataset_folder, output_folder, n_points, number_of_workers, model_checkpoint, path_list_files, device='cuda', allow_pickle=None):
+def test(dataset_folder, output_folder, n_points, number_of_workers, model_checkpoint, path_list_files, device='cuda', allow_pickle=None,
+         precision=None):
+    """precision: as train_gru's."""
     start = time.time()
+    precision = resolve_precision(precision)
+    print("matrix precision:", describe_precision(precision), flush=True)
     device = torch.device(device)
     checkpoint = torch.load(model_checkpoint, map_location=device, weights_only=True)
     with open(os.path.join(path_list_files, 'test_seg_files.txt')) as f:
@@ -124,8 +133,8 @@ def test(dataset_folder, output_folder, n_points, number_of_workers, model_check
     ds = LidarDataset4Test(dataset_folder, task='segmentation', number_of_points=n_points, files=test_files, fixed_num_points=False,
                            allow_pickle=allow_pickle)
     loader = torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, num_workers=number_of_workers, drop_last=False)
-    base_pointnet = BasePointNet(point_dimension=3, return_local_features=True, global_feat_dim=GLOBAL_FEAT_SIZE, device=device)
-    segmen_net = SegmentationWithGRU(num_classes=5, global_feat_size=GLOBAL_FEAT_SIZE, hidden_size=HIDDEN_SIZE, device=device)
+    base_pointnet = BasePointNet(point_dimension=3, return_local_features=True, global_feat_dim=GLOBAL_FEAT_SIZE, device=device, precision=precision)
+    segmen_net = SegmentationWithGRU(num_classes=5, global_feat_size=GLOBAL_FEAT_SIZE, hidden_size=HIDDEN_SIZE, device=device, precision=precision)
     base_pointnet.load_state_dict(checkpoint['base_pointnet'])
     segmen_net.load_state_dict(checkpoint['segmen_net'])
     base_pointnet.eval()

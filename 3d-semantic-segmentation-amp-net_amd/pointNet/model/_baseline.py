@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib, ops
-from .pointnetAtt import _BN, _Conv, _Linear
+from .pointnetAtt import _BN, _Conv, _HasPrecision, _Linear
 
 N_LAYERS = 21          # AMPNET_POINTNET_LAYERS
 
@@ -59,8 +59,9 @@ class BaseHolder(nn.Module):
                    (self.conv_4, self.bn_4), (self.conv_5, self.bn_5)])
 
 
-class SegHolder(nn.Module):
-    """Subclasses set VARIANT / T_DIM / widths and build self.base_pointnet + conv_1..4, bn_1..3."""
+class SegHolder(_HasPrecision, nn.Module):
+    """Subclasses set VARIANT / T_DIM / widths and build self.base_pointnet + conv_1..4, bn_1..3; `precision` (keyword-only, after the
+    reference's arguments): pointnetAtt._HasPrecision."""
     VARIANT = None
     T_DIM = None
 
@@ -130,7 +131,7 @@ class SegHolder(nn.Module):
         buf = self._ws.get(need, dev)
         logits = torch.empty((B, self.num_classes, N), dtype=torch.float32, device=dev)
         feat_T = torch.empty((B, 64, 64), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), _lib.precision_scope(self.precision):
             rc = L.ampnet_pointnet_seg_fwd_f32(self._layer_table(), self.VARIANT, _lib.ptr(x), B, N, self.num_classes,
                                                _lib.ptr(logits), _lib.ptr(feat_T), _lib.ptr(buf),
                                                ctypes.c_size_t(buf.numel()), _lib.stream_ptr(dev))
@@ -140,7 +141,8 @@ class SegHolder(nn.Module):
 
 class _BaselineFn(torch.autograd.Function):
     """Train-mode forward (batch statistics, running-statistics update) and backward of SegmentationPointNet through the C ABI.
-    Every forward owns its tape (workspace) until its backward has run."""
+    Every forward owns its tape (workspace) until its backward has run, and records the matrix precision it ran in: the backward runs
+    in that mode (autograd.py, "Matrix precision")."""
 
     @staticmethod
     def forward(ctx, module, slots, x, *params):
@@ -153,7 +155,8 @@ class _BaselineFn(torch.autograd.Function):
         logits = torch.empty((B, module.num_classes, N), dtype=torch.float32, device=dev)
         feat_T = torch.empty((B, 64, 64), dtype=torch.float32, device=dev)
         table = module._layer_table()
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), _lib.precision_scope(module.precision):
+            ctx.precision = _lib.effective_matrix_precision()
             rc = L.ampnet_pointnet_seg_train_fwd_f32(table, module.VARIANT, _lib.ptr(x), B, N, module.num_classes, _lib.ptr(logits),
                                                      _lib.ptr(feat_T), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev))
         _lib.check(rc, "ampnet_pointnet_seg_train_fwd_f32")
@@ -178,7 +181,7 @@ class _BaselineFn(torch.autograd.Function):
                 garr[4 * i + j] = None if k < 0 else grads[k].data_ptr()
         dl = dlogits.contiguous().float()
         dft = None if d_feat_T is None else d_feat_T.contiguous().float()
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), _lib.precision_scope(ctx.precision):
             rc = _lib.lib().ampnet_pointnet_seg_bwd_f32(module._layer_table(), garr, module.VARIANT, _lib.ptr(x), B, N, module.num_classes,
                                                         _lib.ptr(dl), _lib.ptr(dft), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev))
         _lib.check(rc, "ampnet_pointnet_seg_bwd_f32")
@@ -189,7 +192,7 @@ class _BaselineFn(torch.autograd.Function):
 N_CLS_LAYERS = 20      # AMPNET_POINTNET_CLS_LAYERS
 
 
-class ClsHolder(nn.Module):
+class ClsHolder(_HasPrecision, nn.Module):
     """ClassificationPointNet of both baseline files (pointnet.py:100-125, light_pointnet_256.py:100-125): parameter holder with the
     reference's state_dict keys (base_pointnet.*, fc_1..3, bn_1..2; dropout_1 has none); forward -> (log-probabilities [B, num_classes],
     feature_transform [B, 64, 64]) through ampnet_pointnet_cls_fwd_f32, train mode differentiable through ampnet_pointnet_cls_bwd_f32.
@@ -260,7 +263,7 @@ class ClsHolder(nn.Module):
         buf = self._ws.get(L.ampnet_pointnet_cls_workspace_bytes(self.VARIANT, B, N, self.num_classes), dev)
         out = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
         feat_T = torch.empty((B, 64, 64), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), _lib.precision_scope(self.precision):
             rc = L.ampnet_pointnet_cls_fwd_f32(self._layer_table(), self.VARIANT, _lib.ptr(x), B, N, self.num_classes, 0, ctypes.c_float(0.0),
                                                ctypes.c_uint32(0), _lib.ptr(out), _lib.ptr(feat_T), _lib.ptr(buf), ctypes.c_size_t(buf.numel()),
                                                _lib.stream_ptr(dev))
@@ -280,7 +283,8 @@ class _BaselineClsFn(torch.autograd.Function):
         ws = torch.empty(int(L.ampnet_pointnet_cls_workspace_bytes(module.VARIANT, B, N, module.num_classes)), dtype=torch.uint8, device=dev)
         out = torch.empty((B, module.num_classes), dtype=torch.float32, device=dev)
         feat_T = torch.empty((B, 64, 64), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), _lib.precision_scope(module.precision):
+            ctx.precision = _lib.effective_matrix_precision()
             rc = L.ampnet_pointnet_cls_fwd_f32(module._layer_table(), module.VARIANT, _lib.ptr(x), B, N, module.num_classes, 1,
                                                ctypes.c_float(module.p_drop), ctypes.c_uint32(seed), _lib.ptr(out), _lib.ptr(feat_T), _lib.ptr(ws),
                                                ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev))
@@ -305,7 +309,7 @@ class _BaselineClsFn(torch.autograd.Function):
                 garr[4 * i + j] = None if k < 0 else grads[k].data_ptr()
         do = d_out.contiguous().float()
         dft = None if d_feat_T is None else d_feat_T.contiguous().float()
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), _lib.precision_scope(ctx.precision):
             rc = _lib.lib().ampnet_pointnet_cls_bwd_f32(module._layer_table(), garr, module.VARIANT, _lib.ptr(x), B, N, module.num_classes,
                                                         ctypes.c_float(module.p_drop), ctypes.c_uint32(seed), _lib.ptr(do), _lib.ptr(dft), _lib.ptr(ws),
                                                         ctypes.c_size_t(ws.numel()), _lib.stream_ptr(dev))

@@ -23,8 +23,9 @@ class BasePointNet(_B.BaseHolder):
 class SegmentationPointNet(_B.SegHolder):
     VARIANT = 1
 
-    def __init__(self, num_classes, point_dimension=3, device='cuda'):
+    def __init__(self, num_classes, point_dimension=3, device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         self.base_pointnet = BasePointNet(return_local_features=True, point_dimension=point_dimension, device=device)
         self._init_head(num_classes, _G, 256, 128, 64, device)
 
@@ -34,8 +35,9 @@ class ClassificationPointNet(_B.ClsHolder):
     num_classes).  The reference's default point_dimension=3 cannot run (its BasePointNet slices x[:, :, :2], :71): pass point_dimension=2."""
     VARIANT = 1
 
-    def __init__(self, num_classes, dropout=0.3, point_dimension=3, dataset='', device='cuda'):
+    def __init__(self, num_classes, dropout=0.3, point_dimension=3, dataset='', device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         self.dataset = dataset
         self.base_pointnet = BasePointNet(return_local_features=False, point_dimension=point_dimension, device=device)
         self._init_head(num_classes, dropout, _G, 128, 64, False, device)

@@ -23,8 +23,9 @@ class BasePointNet(_B.BaseHolder):
 class SegmentationPointNet(_B.SegHolder):
     VARIANT = 0
 
-    def __init__(self, num_classes, point_dimension=3, device='cuda'):
+    def __init__(self, num_classes, point_dimension=3, device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         self.base_pointnet = BasePointNet(return_local_features=True, point_dimension=point_dimension, device=device)
         self._init_head(num_classes, _G, 512, 256, 128, device)
 
@@ -33,8 +34,9 @@ class ClassificationPointNet(_B.ClsHolder):
     """pointnet.py:100-125: global feature -> fc 1024 -> 512 -> 256 (BatchNorm + ReLU) -> Dropout -> log_softmax(fc 256 -> num_classes)."""
     VARIANT = 0
 
-    def __init__(self, num_classes, dropout=0.3, point_dimension=3, dataset='', device='cuda'):
+    def __init__(self, num_classes, dropout=0.3, point_dimension=3, dataset='', device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         self.dataset = dataset
         self.base_pointnet = BasePointNet(return_local_features=False, point_dimension=point_dimension, dataset=dataset, device=device)
         self._init_head(num_classes, dropout, _G, 512, 256, True, device)

@@ -11,6 +11,10 @@ Beyond the reference signatures, BasePointNet.forward_windows() and Segmentation
 take ALL windows of a step at once (what the reference does with W serial encoder calls and a Python
 repeat/cat loop); the package's train_loop uses those.
 
+Also beyond the reference: the keyword-only constructor argument `precision` (and set_precision()) of the modules that launch
+kernels -- the matrix precision their C-ABI calls run in ('fp32', 'f32x3', 'bf16', 'bf16_train', 'bf16_store'; None = the library's
+process-wide default).  It is a plain attribute: not a parameter, not a buffer, not in the state_dict.
+
 Only the AMP-Net configuration is implemented in HIP: point_dimension=3, global_feat_dim=256, local_dim=64,
 embed_dim=256, num_heads=8, num_classes<=8 (train_pointnet-attention.py:110-118); other values raise.
 """
@@ -70,8 +74,19 @@ def _named_tensors(module):
     return d
 
 
+class _HasPrecision:
+    """Mix-in of the modules that launch kernels: `precision` is the matrix precision every C-ABI call made on the module's behalf runs
+    in (_lib.precision_scope), None = follow the library's process-wide default.  A forward in grad mode records the mode it ran in and
+    its backward runs in that mode (autograd.py), so changing the attribute between the two does not touch a step under way."""
+    precision = None
+
+    def set_precision(self, mode):
+        self.precision = None if mode is None else _lib.checked_precision(mode)
+        return self
+
+
 class _TableCache:
-    """PointerTables rebuilt only when a tensor moved (load_state_dict copies in place, .to() may not)."""
+    """PointerTables rebuilt only when a tensor moved (load_state_dict copies in place, .to() may not) or the module's precision changed."""
 
     def __init__(self):
         self.key = None
@@ -79,9 +94,10 @@ class _TableCache:
 
     def get(self, module, ptable, btable, what):
         t = _named_tensors(module)
-        key = tuple(v.data_ptr() for v in t.values())
+        precision = getattr(module, "precision", None)
+        key = tuple(v.data_ptr() for v in t.values()) + (precision,)
         if key != self.key:
-            self.tables = (ops.PointerTable(ptable, t, what + " parameters"), ops.PointerTable(btable, t, what + " buffers"))
+            self.tables = (ops.PointerTable(ptable, t, what + " parameters", precision), ops.PointerTable(btable, t, what + " buffers", precision))
             self.key = key
         return self.tables
 
@@ -107,10 +123,11 @@ class TransformationNet(nn.Module):
         raise _lib.AmpnetError("TransformationNet runs inside BasePointNet's HIP launch sequence; call BasePointNet")
 
 
-class BasePointNet(nn.Module):
+class BasePointNet(_HasPrecision, nn.Module):
 
-    def __init__(self, point_dimension=2, return_local_features=False, global_feat_dim=256, device='cuda'):
+    def __init__(self, point_dimension=2, return_local_features=False, global_feat_dim=256, device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         if point_dimension != P.POINT_DIM or global_feat_dim != P.GLOBAL_DIM:
             raise NotImplementedError("the HIP encoder is built for point_dimension=3, global_feat_dim=256 "
                                       "(train_pointnet-attention.py:110-113)")
@@ -162,8 +179,9 @@ class BasePointNet(nn.Module):
         if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from ...autograd import encoder_apply
             return encoder_apply(self, pt, bt, rows.float(), off, len(sizes), total, mx, n_slots)
-        local, glob, feat_T, _ = ops.encoder_forward(pt, bt, rows.float(), off, len(sizes), total, mx,
-                                                     n_slots if train else 1, train, self._ws)
+        with _lib.precision_scope(self.precision):
+            local, glob, feat_T, _ = ops.encoder_forward(pt, bt, rows.float(), off, len(sizes), total, mx,
+                                                         n_slots if train else 1, train, self._ws)
         if train:
             self._bump_batches(n_slots)
         return local, glob, feat_T
@@ -180,10 +198,11 @@ class BasePointNet(nn.Module):
         return glob, feat_T
 
 
-class SegmentationWithAttention(nn.Module):
+class SegmentationWithAttention(_HasPrecision, nn.Module):
 
-    def __init__(self, embed_dim, num_heads, num_classes=2, local_dim=128, dropout=0.3, device='cuda'):
+    def __init__(self, embed_dim, num_heads, num_classes=2, local_dim=128, dropout=0.3, device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         if embed_dim != P.GLOBAL_DIM or num_heads != P.HEADS or local_dim != P.LOCAL_DIM or not (1 <= num_classes <= 8):
             raise NotImplementedError("the HIP head is built for embed_dim=256, num_heads=8, local_dim=64, "
                                       "num_classes<=8 (train_pointnet-attention.py:118)")
@@ -229,8 +248,9 @@ class SegmentationWithAttention(nn.Module):
             from ...autograd import head_apply
             return head_apply(self, pt, bt, gl_rows, lo_rows, centroids, off, attn_mask, B, W, total, mx,
                               self.num_classes, self.p_drop, seed, targets, class_w, want_preds)
-        out = ops.head_forward(pt, bt, gl_rows, lo_rows, centroids, off, attn_mask, B, W, total, mx, self.num_classes,
-                               train, self.p_drop, seed, self._ws, targets=targets, class_w=class_w, want_preds=want_preds)
+        with _lib.precision_scope(self.precision):
+            out = ops.head_forward(pt, bt, gl_rows, lo_rows, centroids, off, attn_mask, B, W, total, mx, self.num_classes,
+                                   train, self.p_drop, seed, self._ws, targets=targets, class_w=class_w, want_preds=want_preds)
         if train:
             torch._foreach_add_([self.bn_2.num_batches_tracked, self.bn_3.num_batches_tracked], 1)
         return out
@@ -257,14 +277,15 @@ class _GRU(nn.Module):
         self.bias_hh_l0 = nn.Parameter(torch.empty(3 * hidden, device=device).uniform_(-k, k))
 
 
-class SegmentationWithGRU(nn.Module):
+class SegmentationWithGRU(_HasPrecision, nn.Module):
     """The GRU variant of the sequence model (pointnetAtt.py:212-258): nn.GRU(256 -> 64, batch_first, h0 = 0) over the
     window tokens, hidden state of step w broadcast over the points of window w, then conv_2 / bn_2 / conv_3 / bn_3 / conv_4 with
     Dropout(0.3) twice.  Runs through ampnet_gru_head_fwd_f32 / _bwd_f32 (csrc/gru_head.hip)."""
     head_kind = "gru"
 
-    def __init__(self, num_classes, global_feat_size, hidden_size, device):
+    def __init__(self, num_classes, global_feat_size, hidden_size, device, *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         if global_feat_size != P.GLOBAL_DIM or hidden_size != P.GRU_HIDDEN or not (1 <= num_classes <= 8):
             raise NotImplementedError("the HIP GRU head is built for global_feat_size=256, hidden_size=64, num_classes<=8 "
                                       "(pointNet/rnn/train_pointnetGRU.py:27-28,128)")
@@ -311,8 +332,9 @@ class SegmentationWithGRU(nn.Module):
         if train and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from ...autograd import gru_head_apply
             return gru_head_apply(self, pt, bt, gl_rows, lo_rows, off, B, W, total, mx, self.num_classes, self.p_drop, seed, want_preds)
-        out = ops.gru_head_forward(pt, bt, gl_rows.contiguous().float(), lo_rows.contiguous().float(), off, B, W, total, mx, self.num_classes,
-                                   train, self.p_drop, seed, self._ws, targets=targets, class_w=class_w, want_preds=want_preds)
+        with _lib.precision_scope(self.precision):
+            out = ops.gru_head_forward(pt, bt, gl_rows.contiguous().float(), lo_rows.contiguous().float(), off, B, W, total, mx, self.num_classes,
+                                       train, self.p_drop, seed, self._ws, targets=targets, class_w=class_w, want_preds=want_preds)
         if train:
             torch._foreach_add_([self.bn_2.num_batches_tracked, self.bn_3.num_batches_tracked], 1)
         return out
@@ -345,14 +367,15 @@ class ClassificationFromGRU(nn.Module):
                              "pointnetAtt.py:274; the classification task is not runnable in the reference)")
 
 
-class ClassificationWithAttention(nn.Module):
+class ClassificationWithAttention(_HasPrecision, nn.Module):
     """pointnetAtt.py:115-151 on the HIP path (ampnet_cls_head_fwd_f32 / _bwd_f32, csrc/cls_head.hip): MultiheadAttention over the window
     tokens, conv_1 = Conv1d(num_w -> 1, 1) over the attention output re-viewed as [B, W, E] (a view of the sequence-first tensor, as the
     reference writes it), fc_2 -> bn_2 -> ReLU -> fc_3.  forward(gl_feats [W, B, E], centroids, attn_mask) -> (out [B, C], weights
     [B, W, W]); centroids are unused by the reference (the positional encoding is commented out there)."""
 
-    def __init__(self, embed_dim, num_heads, num_classes=2, dropout=0.3, num_w=9, device='cuda'):
+    def __init__(self, embed_dim, num_heads, num_classes=2, dropout=0.3, num_w=9, device='cuda', *, precision=None):
         super().__init__()
+        self.set_precision(precision)
         if embed_dim != P.GLOBAL_DIM or num_heads != P.HEADS or not (1 <= num_classes <= 16) or not (1 <= num_w <= 32):
             raise NotImplementedError("the HIP classification head is built for embed_dim=256, num_heads=8, num_classes<=16, num_w<=32")
         self.embed_dim = embed_dim
@@ -387,7 +410,8 @@ class ClassificationWithAttention(nn.Module):
         if train and torch.is_grad_enabled() and (gl_feats.requires_grad or any(p.requires_grad for p in self.parameters())):
             from ...autograd import cls_head_apply
             return cls_head_apply(self, pt, bt, gl_rows, attn_mask, B, W, self.num_classes, self.p_drop, seed)
-        out = ops.cls_head_forward(pt, bt, gl_rows.contiguous().float(), attn_mask, B, W, self.num_classes, train, self.p_drop, seed, self._ws)
+        with _lib.precision_scope(self.precision):
+            out = ops.cls_head_forward(pt, bt, gl_rows.contiguous().float(), attn_mask, B, W, self.num_classes, train, self.p_drop, seed, self._ws)
         if train:
             self.bn_2.num_batches_tracked += 1
         return out

@@ -6,6 +6,11 @@ backward -> gradient all-reduce when torch.distributed is initialised (RCCL, one
 optimizer.step() for the two optimisers the caller owns (FusedAdam below, or any torch optimiser: gradients are
 left in p.grad).  The reference does the same work with W serial encoder calls and autograd
 (train_pointnet-attention.py:396-470).
+
+Matrix precision: every C-ABI call of a step runs inside _lib.precision_scope of the module it is made for (module.precision, None =
+the library's process-wide default); Trainer(precision=...) / fused_train_step(precision=...) run the step in one mode for both
+modules instead, without touching the modules' own attribute.  The two
+modules of a step exchange a tape, so 'bf16_store' on one and another mode on the other is refused before anything is launched.
 """
 import ctypes
 
@@ -202,8 +207,23 @@ def _global_loss(loss2, reg):
     return torch.stack([pack[0] / pack[1], pack[1] / world]), pack[2].sqrt().reshape(1), world
 
 
-def forward_backward(pointnet, att_net, x, t, centroids, class_w, reg_weight=0.001, overlap_allreduce=False):
+def step_precision(pointnet, att_net, precision=None):
+    """(encoder precision, head precision) of a step over the two modules: `precision` for both when it is given (checked name), else
+    each module's own, after the check that they can share one: the head's backward
+    hands the encoder's backward gradients for a tape each wrote in its own storage format, so 'bf16_store' (bf16 tape) against any other
+    mode (fp32 tape) raises ValueError -- here, before any launch.  None (= follow the process-wide default) pairs with anything."""
+    if precision is not None:
+        return _lib.checked_precision(precision), precision
+    pe, ph = getattr(pointnet, "precision", None), getattr(att_net, "precision", None)
+    if _lib.tape_conflict(pe, ph):
+        raise ValueError(f"the encoder runs in matrix precision {pe!r} and the head in {ph!r}: 'bf16_store' keeps the saved activations "
+                         "as bf16, every other mode as fp32 -- give both modules of a train step the same storage mode")
+    return pe, ph
+
+
+def forward_backward(pointnet, att_net, x, t, centroids, class_w, reg_weight=0.001, overlap_allreduce=False, precision=None):
     """Forward + loss + backward of one batch; gradients land in p.grad (views of the modules' flat buffers).
+    precision: the matrix precision of this call for both modules; None: each module's own (step_precision).
     x [B, W, N, 9] f32, t [B, W, N] i64 (host or device), centroids [B, W, 2].
     overlap_allreduce (data parallel, opt-in: fused_train_step sets it): the head's flat gradient buffer is complete before the encoder
     backward starts, so its SUM all-reduce is issued there asynchronously and travels under the encoder backward; the work handle is
@@ -214,6 +234,8 @@ def forward_backward(pointnet, att_net, x, t, centroids, class_w, reg_weight=0.0
         raise _lib.AmpnetError("the AMP-Net HIP path needs the model on the GPU")
     if not (pointnet.training and att_net.training):
         raise _lib.AmpnetError("forward_backward needs both modules in train mode")
+    # read once: the backward below runs in the modes the forward ran in, whatever happens to the attributes meanwhile
+    enc_prec, head_prec = step_precision(pointnet, att_net, precision)
     xd = torch.as_tensor(x).to(dev, non_blocking=True).float()
     B, W, N, _ = xd.shape
     targets_pc = torch.as_tensor(t).reshape(B, W * N)
@@ -227,24 +249,28 @@ def forward_backward(pointnet, att_net, x, t, centroids, class_w, reg_weight=0.0
     xr = xd.reshape(rows, 9)
     off, total, mx = ops.window_offsets([N] * Q, dev)
     # ---- forward ----
-    local, glob, feat_T, _ = ops.encoder_forward(ept, ebt, xr, off, Q, total, mx, W, True, pointnet._ws)
+    with _lib.precision_scope(enc_prec):
+        local, glob, feat_T, _ = ops.encoder_forward(ept, ebt, xr, off, Q, total, mx, W, True, pointnet._ws)
     gru = getattr(att_net, "head_kind", "attention") == "gru"      # SegmentationWithGRU: no centroids, no key-padding mask
     seed = (att_net.seed + 0x632BE5AB * att_net._step) & 0xFFFFFFFF
     att_net._step += 1
     if gru:
         if class_w is None:
             class_w = torch.ones(att_net.num_classes, dtype=torch.float32, device=dev)
-        logits, preds, loss2 = ops.gru_head_forward(hpt, hbt, glob, local, off, B, W, total, mx, att_net.num_classes, True, att_net.p_drop,
-                                                    seed, att_net._ws, targets=tgd, class_w=class_w, want_preds=True)
+        with _lib.precision_scope(head_prec):
+            logits, preds, loss2 = ops.gru_head_forward(hpt, hbt, glob, local, off, B, W, total, mx, att_net.num_classes, True, att_net.p_drop,
+                                                        seed, att_net._ws, targets=tgd, class_w=class_w, want_preds=True)
     else:
-        mask = ops.pad_mask(tgd, W)                                 # the reference's literal (targets.view(B, -1, W) == -1).all(dim=1), one launch
-        logits, preds, loss2 = ops.head_forward(hpt, hbt, glob, local, cent, off, mask, B, W, total, mx, att_net.num_classes, True,
-                                                att_net.p_drop, seed, att_net._ws, targets=tgd, class_w=class_w, want_preds=True)
+        with _lib.precision_scope(head_prec):
+            mask = ops.pad_mask(tgd, W)                             # the reference's literal (targets.view(B, -1, W) == -1).all(dim=1), one launch
+            logits, preds, loss2 = ops.head_forward(hpt, hbt, glob, local, cent, off, mask, B, W, total, mx, att_net.num_classes, True,
+                                                    att_net.p_drop, seed, att_net._ws, targets=tgd, class_w=class_w, want_preds=True)
     # num_batches_tracked: + W for the encoder's 16 BatchNorms (W encoder calls in the reference), + 1 for the head's two; one launch
     counters = pointnet._bn_counters() + [att_net.bn_2.num_batches_tracked, att_net.bn_3.num_batches_tracked]
     torch._foreach_add_(counters, [W] * (len(counters) - 2) + [1, 1])
     feat_last = feat_T[-B:]
-    reg, G = ops.reg_loss(feat_last, keep_G=True)
+    with _lib.precision_scope(enc_prec):
+        reg, G = ops.reg_loss(feat_last, keep_G=True)
     # ---- backward ----
     if not hasattr(att_net, "_bws"):
         att_net._bws, pointnet._bws = ops.Workspace(), ops.Workspace()
@@ -253,21 +279,23 @@ def forward_backward(pointnet, att_net, x, t, centroids, class_w, reg_weight=0.0
             raise _SYNC["state"]["error"]
         loss2, reg_b, world = _global_loss(loss2, reg)      # reported ce / reg are the global batch's; seeds scaled by world (see there)
         reg, reg_weight = reg_b, reg_weight * world
-    dlog = ops.ce_backward(logits, tgd, class_w, loss2)
-    if gru:
-        d_lo, d_gl = ops.gru_head_backward(hpt, hg.table, glob, local, off, B, W, total, mx, att_net.num_classes, att_net.p_drop, seed,
+    with _lib.precision_scope(head_prec):
+        dlog = ops.ce_backward(logits, tgd, class_w, loss2)
+        if gru:
+            d_lo, d_gl = ops.gru_head_backward(hpt, hg.table, glob, local, off, B, W, total, mx, att_net.num_classes, att_net.p_drop, seed,
+                                               dlog, att_net._ws, att_net._bws)
+        else:
+            d_lo, d_gl = ops.head_backward(hpt, hg.table, local, cent, off, B, W, total, mx, att_net.num_classes, att_net.p_drop, seed,
                                            dlog, att_net._ws, att_net._bws)
-    else:
-        d_lo, d_gl = ops.head_backward(hpt, hg.table, local, cent, off, B, W, total, mx, att_net.num_classes, att_net.p_drop, seed,
-                                       dlog, att_net._ws, att_net._bws)
     # data parallel: the head's gradient buffer is complete here -- its all-reduce travels while the encoder backward runs
     pending = {}
     if overlap_allreduce:
         dist, world, on = _collectives_on()
         if on:
             pending[hg.flat.data_ptr()] = dist.all_reduce(hg.flat, op=dist.ReduceOp.SUM, async_op=True)
-    d_ft = ops.reg_loss_backward_stack(feat_last, G, reg, reg_weight, feat_T.shape[0])      # zeros + the regulariser's gradient, one launch
-    ops.encoder_backward(ept, eg.table, xr, off, Q, total, mx, W, local, feat_T, d_lo, d_gl, d_ft, pointnet._ws, pointnet._bws)
+    with _lib.precision_scope(enc_prec):
+        d_ft = ops.reg_loss_backward_stack(feat_last, G, reg, reg_weight, feat_T.shape[0])      # zeros + the regulariser's gradient, one launch
+        ops.encoder_backward(ept, eg.table, xr, off, Q, total, mx, W, local, feat_T, d_lo, d_gl, d_ft, pointnet._ws, pointnet._bws)
     eg.attach()
     hg.attach()
     return dict(logits=logits, preds=preds, ce=loss2, reg=reg, targets_pc=targets_pc, B=B, grad_bufs=(eg.flat, hg.flat), pending=pending)
@@ -310,22 +338,31 @@ def shard_indices(n_samples, rank, world, drop_last=True):
     return idx
 
 
-def fused_train_step(pointnet, att_net, optimizer_pointnet, optimizer_att, x, t, centroids, class_w):
-    out = forward_backward(pointnet, att_net, x, t, centroids, class_w, overlap_allreduce=True)
+def fused_train_step(pointnet, att_net, optimizer_pointnet, optimizer_att, x, t, centroids, class_w, precision=None):
+    """precision (not None): the matrix precision of THIS step for both modules; their own `precision` attributes are left alone."""
+    out = forward_backward(pointnet, att_net, x, t, centroids, class_w, overlap_allreduce=True, precision=precision)
     reduce_gradients(out["grad_bufs"], (optimizer_pointnet, optimizer_att), out["pending"])
-    if isinstance(optimizer_pointnet, FusedAdam) and isinstance(optimizer_att, FusedAdam):
-        FusedAdam.step_together((optimizer_pointnet, optimizer_att))          # one multi-tensor launch for both networks
-    else:
-        optimizer_pointnet.step()
-        optimizer_att.step()
+    # the Adam kernel does not depend on the matrix precision; it runs in a scope all the same, so that holds by construction.  One launch
+    # serves both networks, so there is one scope: the step's `precision`, else the ENCODER's (the head's own is not consulted here)
+    with _lib.precision_scope(step_precision(pointnet, att_net, precision)[0]):
+        if isinstance(optimizer_pointnet, FusedAdam) and isinstance(optimizer_att, FusedAdam):
+            FusedAdam.step_together((optimizer_pointnet, optimizer_att))          # one multi-tensor launch for both networks
+        else:
+            optimizer_pointnet.step()
+            optimizer_att.step()
     return out
 
 
 class Trainer:
     """Owns the two FusedAdam optimisers of the reference recipe and runs fused steps (bench.py, smoke())."""
 
-    def __init__(self, pointnet, att_net, lr=1e-3, class_w=None, world_size=1):
+    def __init__(self, pointnet, att_net, lr=1e-3, class_w=None, world_size=1, precision=None):
+        """precision (not None): the matrix precision of every step of this trainer, for both modules (kept on the trainer: the modules'
+        own attributes are not touched); None: each module's own, and a pair that cannot share a step ('bf16_store' on one side only)
+        raises ValueError here."""
         self.pointnet, self.att_net = pointnet, att_net
+        self.precision = None if precision is None else _lib.checked_precision(precision)
+        step_precision(pointnet, att_net, self.precision)
         self.opt_p = FusedAdam(pointnet.parameters(), lr=lr)
         self.opt_a = FusedAdam(att_net.parameters(), lr=lr)
         dev = next(pointnet.parameters()).device
@@ -334,4 +371,4 @@ class Trainer:
         att_net.train()
 
     def step(self, x, t, centroids):
-        return fused_train_step(self.pointnet, self.att_net, self.opt_p, self.opt_a, x, t, centroids, self.class_w)
+        return fused_train_step(self.pointnet, self.att_net, self.opt_p, self.opt_a, x, t, centroids, self.class_w, precision=self.precision)

@@ -12,7 +12,10 @@
  *   - `stream` is a hipStream_t passed as void*; kernels are enqueued on it and never synchronised;
  *   - return value 0 = ok, negative = error (AMPNET_E_*); ampnet_last_error() gives the text
  *     (thread-local).  No exception crosses the ABI;
- *   - the library keeps no state between calls except the thread-local error string.
+ *   - state the library keeps between calls: the thread-local error string; the process-wide default matrix precision
+ *     (ampnet_set_matrix_precision); each thread's stack of scoped precision overrides (ampnet_precision_scope_begin / _end);
+ *     the host-side tags that record which precision a train-mode forward wrote its workspace in; the collective callback
+ *     (ampnet_set_collective) and the event profiler.  Nothing else survives a call.
  *   - float tensors are fp32, row-major, point-major: activations are [rows, channels].
  *
  * Window batching: the reference calls its encoder W times per step, each time on the B windows that
@@ -31,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 7
+#define AMPNET_ABI_VERSION 8
 
 enum {
     AMPNET_OK = 0,
@@ -333,7 +336,7 @@ typedef int (*ampnet_collective_fn)(void *ctx, int op, void *send, void *recv, s
 size_t ampnet_collective_scratch_bytes(int world_size);
 int ampnet_set_collective(ampnet_collective_fn fn, void *ctx, int rank, int world_size, void *scratch, size_t scratch_bytes);
 
-/* ---- matrix-core operand precision (process-wide) -----------------------------------------------------------
+/* ---- matrix-core operand precision (process-wide default, per-thread scoped override) ------------------------
  * AMPNET_PRECISION_F32 (default): v_mfma_f32_32x32x2_f32, exact fp32 products -- the mode every parity figure is quoted in.
  * AMPNET_PRECISION_BF16: the per-point layers of ampnet_encoder_fwd_f32 / ampnet_head_fwd_f32 round their MFMA operands
  * (activations after BatchNorm+ReLU, weights) to bf16 and accumulate in fp32 (v_mfma_f32_32x32x16_bf16); tensors in HBM,
@@ -365,6 +368,17 @@ int ampnet_set_collective(ampnet_collective_fn fn, void *ctx, int rank, int worl
 #define AMPNET_PRECISION_F32_SPLIT 4
 int ampnet_set_matrix_precision(int mode);
 int ampnet_get_matrix_precision(void);
+/* Scoped override: ampnet_precision_scope_begin(mode) pushes `mode` (validated as ampnet_set_matrix_precision validates it) on a stack
+ * that belongs to the CALLING THREAD, ampnet_precision_scope_end() pops it.  While the stack is not empty, every entry point called on
+ * that thread dispatches on its top instead of the process-wide default -- including the workspace tags and their check -- so two
+ * models of one process can run in different modes, and a backward can be run in the mode its forward recorded whatever the default
+ * has become.  Other threads are unaffected.  The stack holds AMPNET_PRECISION_SCOPE_DEPTH entries: one more begin, or an end with
+ * nothing pushed, returns AMPNET_E_ARG and changes nothing.  ampnet_get_matrix_precision() keeps returning the process-wide default;
+ * ampnet_effective_matrix_precision() returns what a dispatch on the calling thread would see.                                   */
+#define AMPNET_PRECISION_SCOPE_DEPTH 8
+int ampnet_precision_scope_begin(int mode);
+int ampnet_precision_scope_end(void);
+int ampnet_effective_matrix_precision(void);
 
 /* ---- a12: baseline single-window PointNet segmentation, eval forward -----------------------------------------
  * replaces SegmentationPointNet.forward (module.eval()) of pointNet/model/pointnet.py:128-154 (variant 0: 1024-d,

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 
@@ -150,3 +150,50 @@ def stream_ptr(device=None):
 def require_gpu(t, name):
     if not t.is_cuda:
         raise AmpnetError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
+
+
+# ---- PointNet++ grouping (include/ampnet_hip.h: ampnet_ball_query_f32, ampnet_sa_forward_f32) ---------------------------------------
+SA_MAX_NSAMPLE, SA_MAX_LAYERS, SA_MAX_CIN, SA_MAX_COUT = 64, 3, 320, 256
+SA_WORKSPACE_BYTES = SA_MAX_LAYERS * 2 * SA_MAX_COUT * 4
+
+
+def ball_query_f32(xyz, centres, radius, nsample, out, count=None):
+    """xyz [B, N, ld] float32, centres [B, S] int32, out [B, S, nsample] int32, count [B, S] int32 or None: contiguous GPU tensors."""
+    B, N, ld = xyz.shape
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_ball_query_f32(ptr(xyz), B, N, ld, ptr(centres), centres.shape[1], ctypes.c_float(radius), int(nsample), ptr(out),
+                                         ptr(count), stream_ptr(xyz.device))
+    check(rc, "ampnet_ball_query_f32")
+
+
+def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
+    """One fused set-abstraction layer.  layers: per layer the six contiguous float32 GPU tensors (weight [cout, cin], conv bias, BatchNorm
+    weight, bias, running_mean, running_var); eps: per layer the BatchNorm eps; feats [B, N, D] or None; out [B, S, cout_last]."""
+    B, N, ld = xyz.shape
+    L = len(layers)
+    cin = 3 + (0 if feats is None else feats.shape[2])
+    for i, layer in enumerate(layers):                         # the kernel trusts these shapes: a short tensor would be read past its end
+        cout = int(layer[0].shape[0])
+        want = [(cout, cin)] + [(cout,)] * 5
+        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                                  for t, w in zip(layer, want)):
+            raise AmpnetError(f"sa_forward: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in layer]}")
+        cin = cout
+    for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
+                        ("feats", feats, torch.float32), ("out", out, torch.float32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt):
+            raise AmpnetError(f"sa_forward: {name} must be a {dt} GPU tensor")
+    S = centres.shape[1]
+    if tuple(centres.shape) != (B, S) or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != (B, S) \
+            or (feats is not None and tuple(feats.shape[:2]) != (B, N)) or (L and tuple(out.shape) != (B, S, int(layers[-1][0].shape[0]))):
+        raise AmpnetError("sa_forward: centres [B, S], group_idx [B, S, nsample], feats [B, N, D], out [B, S, cout] do not agree with xyz [B, N, ld]")
+    tensors = [t for layer in layers for t in layer]
+    table = (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+    couts = (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers])
+    epss = (ctypes.c_float * max(L, 1))(*[float(e) for e in eps])
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_forward_f32(ptr(xyz), B, N, ld, ptr(centres), centres.shape[1], ptr(group_idx), group_idx.shape[2], ptr(feats),
+                                         0 if feats is None else feats.shape[2], table, couts, epss, L, ptr(out), ptr(workspace),
+                                         ctypes.c_size_t(workspace.numel() * workspace.element_size()), stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_forward_f32")

@@ -1,0 +1,103 @@
+"""PointNet++ building blocks on the HIP path: the grouping half of the backbone the reference's `pointnet_2` class needs.
+
+The reference imports `PointNetSetAbstraction` and `PointNetFeaturePropagation` from a package it does not ship (pointnetAtt.py:4,
+used at :285-287).  This module provides the first of them with the constructor and the state_dict keys of the usual PointNet++
+implementation -- `mlp_convs.{i}.{weight [out, in, 1, 1], bias}`, `mlp_bns.{i}.{weight, bias, running_mean, running_var,
+num_batches_tracked}` -- so its checkpoints load.  Inference only: farthest-point sampling (ampnet_fps_f32), ball query
+(ampnet_ball_query_f32) and ONE fused kernel for gather + shared MLP + max (ampnet_sa_forward_f32, exact fp32 whatever the matrix
+precision is).  Not built: `group_all=True`, train-mode BatchNorm statistics, any backward, `PointNetFeaturePropagation`.
+
+Difference from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come from
+the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
+"""
+import torch
+import torch.nn as nn
+
+from ... import _lib
+from ...utils import utils as U
+
+
+class _Conv2d(nn.Module):
+    """Holder with nn.Conv2d(cin, cout, 1)'s parameter names, shapes and initialisation bounds."""
+
+    def __init__(self, cin, cout, device):
+        super().__init__()
+        k = 1.0 / cin ** 0.5
+        self.weight = nn.Parameter(torch.empty(cout, cin, 1, 1, device=device).uniform_(-k, k))
+        self.bias = nn.Parameter(torch.empty(cout, device=device).uniform_(-k, k))
+
+
+class _BN2d(nn.Module):
+    """Holder with nn.BatchNorm2d's parameter and buffer names."""
+
+    def __init__(self, c, device, eps=1e-5):
+        super().__init__()
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(c, device=device))
+        self.bias = nn.Parameter(torch.zeros(c, device=device))
+        self.register_buffer("running_mean", torch.zeros(c, device=device))
+        self.register_buffer("running_var", torch.ones(c, device=device))
+        self.register_buffer("num_batches_tracked", torch.zeros((), dtype=torch.long, device=device))
+
+
+class PointNetSetAbstraction(nn.Module):
+    """One set-abstraction layer: `npoint` centres by farthest-point sampling, per centre the first `nsample` points within `radius`
+    (utils.ball_query), the shared MLP `mlp` (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on [relative xyz, point features], max over the
+    group.  `in_channel` counts the 3 coordinates, as in the usual implementation."""
+
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda'):
+        super().__init__()
+        if group_all:
+            raise NotImplementedError("the HIP set abstraction is built for group_all=False (ball-query groups of <= 64 points); "
+                                      "the single all-points group is not")
+        mlp = [int(c) for c in mlp]
+        if not (1 <= len(mlp) <= _lib.SA_MAX_LAYERS) or any(c % 32 or not 32 <= c <= _lib.SA_MAX_COUT for c in mlp) \
+                or not 3 <= in_channel <= _lib.SA_MAX_CIN or not 1 <= nsample <= _lib.SA_MAX_NSAMPLE:
+            raise NotImplementedError(f"the HIP set abstraction is built for 1..{_lib.SA_MAX_LAYERS} MLP layers of widths that are multiples "
+                                      f"of 32 up to {_lib.SA_MAX_COUT}, 3 <= in_channel <= {_lib.SA_MAX_CIN}, nsample <= {_lib.SA_MAX_NSAMPLE}")
+        self.npoint, self.radius, self.nsample, self.group_all = int(npoint), float(radius), int(nsample), False
+        self.in_channel = int(in_channel)
+        self.mlp_convs, self.mlp_bns = nn.ModuleList(), nn.ModuleList()
+        last = self.in_channel
+        for c in mlp:
+            self.mlp_convs.append(_Conv2d(last, c, device))
+            self.mlp_bns.append(_BN2d(c, device))
+            last = c
+        self._ws = None
+
+    def forward(self, xyz, points, centres=None):
+        """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]).
+        centres: int32 [B, npoint] point indices to use instead of farthest-point sampling from point 0."""
+        if self.training:
+            raise NotImplementedError("the HIP set abstraction is built for eval mode (BatchNorm running statistics, no backward): "
+                                      "call .eval() first")
+        _lib.require_gpu(xyz, "xyz")
+        if xyz.dim() != 3 or xyz.shape[1] != 3:
+            raise _lib.AmpnetError(f"PointNetSetAbstraction: expected xyz [B, 3, N], got {tuple(xyz.shape)}")
+        B, _, N = xyz.shape
+        D = self.in_channel - 3
+        if (points is None) != (D == 0) or (points is not None and (points.dim() != 3 or tuple(points.shape) != (B, D, N))):
+            raise _lib.AmpnetError(f"PointNetSetAbstraction: in_channel={self.in_channel} needs points "
+                                   f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
+        with torch.no_grad():
+            x = xyz.detach().float().transpose(1, 2).contiguous()                     # [B, N, 3]
+            feats = None
+            if points is not None:
+                _lib.require_gpu(points, "points")
+                feats = points.detach().float().transpose(1, 2).contiguous()         # [B, N, D]
+            if centres is None:
+                centres = U.fps_indices(x, self.npoint)
+            elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
+                raise _lib.AmpnetError(f"PointNetSetAbstraction: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
+            group_idx = U.ball_query(x, centres, self.radius, self.nsample)           # validates the centres
+            centres = centres.contiguous()
+            layers = [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
+                       bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(),
+                       bn.running_mean.float().contiguous(), bn.running_var.float().contiguous())
+                      for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
+            if self._ws is None or self._ws.device != x.device:
+                self._ws = torch.empty(_lib.SA_WORKSPACE_BYTES, dtype=torch.uint8, device=x.device)
+            out = torch.empty((B, self.npoint, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
+            _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out, self._ws)
+            new_xyz = U.gather_rows(x, centres)                                       # [B, npoint, 3]
+        return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()

@@ -120,6 +120,34 @@ def knn_indices(xyz, centres, k):
     return out
 
 
+def ball_query(xyz, centres, radius, nsample, return_counts=False):
+    """Ball-query grouping on the GPU (BUILD-DEFINED: the reference has no ball query, include/ampnet_hip.h: ampnet_ball_query_f32).
+    xyz [B, N, D>=3] float32 GPU, centres [B, S] int32 point indices (e.g. fps_indices) -> int32 [B, S, nsample]: per centre the first
+    nsample points j, in ascending index order, with float32 squared distance <= float32(radius * radius); with fewer members the
+    remaining slots repeat the first one.  return_counts=True also returns int32 [B, S] = min(members, nsample)."""
+    _lib.require_gpu(xyz, "xyz")
+    _lib.require_gpu(centres, "centres")
+    if xyz.dim() != 3 or xyz.shape[2] < 3 or centres.dim() != 2 or centres.shape[0] != xyz.shape[0]:
+        raise _lib.AmpnetError(f"ball_query: expected xyz [B, N, D>=3] and centres [B, S], got {tuple(xyz.shape)} {tuple(centres.shape)}")
+    if centres.dtype != torch.int32:
+        raise _lib.AmpnetError("ball_query: centres must be int32")
+    x = xyz.float().contiguous()
+    c = centres.contiguous()
+    B, N, D = x.shape
+    S = c.shape[1]
+    nsample, radius = int(nsample), float(radius)
+    if not (1 <= nsample <= _lib.SA_MAX_NSAMPLE):
+        raise IndexError(f"ball_query: nsample={nsample} out of range [1, {_lib.SA_MAX_NSAMPLE}]")
+    if not radius >= 0.0:
+        raise _lib.AmpnetError(f"ball_query: radius={radius} must be >= 0")
+    if S and (int(c.min()) < 0 or int(c.max()) >= N):
+        raise IndexError("ball_query: centre index out of range")
+    out = torch.empty((B, S, nsample), dtype=torch.int32, device=x.device)
+    count = torch.empty((B, S), dtype=torch.int32, device=x.device) if return_counts else None
+    _lib.ball_query_f32(x, c, radius, nsample, out, count)
+    return (out, count) if return_counts else out
+
+
 def gather_rows(pc, idx):
     """pc [B, N, D] f32 GPU, idx [B, S] int32 -> [B, S, D] (the `pc[sample_inds]` of utils.py:933)."""
     _lib.require_gpu(pc, "pc")

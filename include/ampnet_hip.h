@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 8
+#define AMPNET_ABI_VERSION 9
 
 enum {
     AMPNET_OK = 0,
@@ -302,6 +302,46 @@ int ampnet_collate_augment_f32(const float *pts, const signed char *labels, cons
  *            distance = float32 ((dx*dx + dy*dy) + dz*dz), no fused multiply-add; the centre itself comes first   */
 int ampnet_knn_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, int k, int32_t *out,
                    void *stream);
+
+/* ---- ball-query grouping of FPS centres (BUILD-DEFINED like ampnet_knn_f32: the reference has no ball query) --------
+ * The grouping of a PointNet++ set-abstraction layer (the reference imports it from a package it does not ship, pointnetAtt.py:4); the
+ * spec below is pinned by the build's CPU restatement tests/sa_ref.py:ball_query.
+ *   xyz      [n_clouds, n, ld] float32 (first 3 columns used), n * 12 bytes <= 144 KB (n <= 12288)
+ *   centres  [n_clouds, s] int32 point indices (e.g. the output of ampnet_fps_f32)
+ *   radius   >= 0; r2 = float32 (radius * radius), computed once on the host
+ *   d(j)     = float32 ((dx*dx + dy*dy) + dz*dz), no fused multiply-add (the distance of ampnet_knn_f32);
+ *              point j is a member of the ball when d(j) <= r2 (the boundary is included)
+ *   out      [n_clouds, s, nsample] int32, 1 <= nsample <= AMPNET_SA_MAX_NSAMPLE: the first nsample members in ascending index order;
+ *            with fewer members the remaining slots repeat the first member (the query_ball_point rule)
+ *   count    [n_clouds, s] int32 = min(members, nsample); may be NULL.  A centre is a member of its own ball (finite coordinates),
+ *            so count >= 1.                                                                                                       */
+#define AMPNET_SA_MAX_NSAMPLE 64
+int ampnet_ball_query_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, float radius, int nsample,
+                          int32_t *out, int32_t *count, void *stream);
+
+/* ---- one set-abstraction layer, eval mode, fused (stands in for PointNetSetAbstraction.forward of pointnetAtt.py:4,285-287) ---------
+ *   xyz, centres          as in ampnet_ball_query_f32 (no limit on n here)
+ *   group_idx             [n_clouds, s, nsample] int32 point indices (the output of ampnet_ball_query_f32), 1 <= nsample <= 64
+ *   feats                 [n_clouds, n, D] float32, or NULL with D = 0
+ *   params_host           HOST array of 6 L DEVICE pointers, per layer l < L <= AMPNET_SA_MAX_LAYERS: weight [cout_l, cin_l], conv bias,
+ *                         BatchNorm weight, bias, running_mean, running_var (each [cout_l]); cin_0 = 3 + D, cin_l = cout_{l-1}
+ *   cout_host, eps_host   HOST arrays [L]: the widths and the BatchNorm eps
+ *   out                   [n_clouds, s, cout_{L-1}] float32
+ *   workspace             AMPNET_SA_WORKSPACE_BYTES device bytes (the folded BatchNorm scale and shift)
+ * Row t of centre i's group is [xyz[idx_t] - xyz[centre_i] (3 values), feats[idx_t] (D values)]; every layer computes
+ * relu(bn_eval(W row + b)) with bn_eval folded into fma(W row, scale, shift), scale = gamma / sqrt(var + eps),
+ * shift = (b - mean) * scale + beta; out is the per-channel max over the nsample rows.  Neither the grouped rows nor any intermediate
+ * activation is written to memory.  Limits (anything else is refused with AMPNET_E_ARG, there is no other path):
+ * cin_0 <= AMPNET_SA_MAX_CIN, every cout_l a multiple of 32 and <= AMPNET_SA_MAX_COUT.
+ * Arithmetic: exact fp32 MFMA (v_mfma_f32_32x32x2_f32) whatever the matrix precision is -- neither ampnet_set_matrix_precision nor a
+ * precision scope changes what this entry point computes.                                                                         */
+#define AMPNET_SA_MAX_LAYERS 3
+#define AMPNET_SA_MAX_CIN 320
+#define AMPNET_SA_MAX_COUT 256
+#define AMPNET_SA_WORKSPACE_BYTES (AMPNET_SA_MAX_LAYERS * 2 * AMPNET_SA_MAX_COUT * 4)
+int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                          int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                          const float *eps_host, int L, float *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =

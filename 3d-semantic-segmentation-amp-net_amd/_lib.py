@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 
@@ -197,3 +197,62 @@ def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
                                          0 if feats is None else feats.shape[2], table, couts, epss, L, ptr(out), ptr(workspace),
                                          ctypes.c_size_t(workspace.numel() * workspace.element_size()), stream_ptr(xyz.device))
     check(rc, "ampnet_sa_forward_f32")
+
+
+# ---- PointNet++ feature propagation (include/ampnet_hip.h: ampnet_three_nn_f32, ampnet_fp_forward_f32) ------------------------------
+THREE_NN_MAX_S = 12288
+FP_MAX_LAYERS, FP_MAX_CIN, FP_MAX_COUT = 3, 512, 256
+FP_WORKSPACE_BYTES = FP_MAX_LAYERS * 2 * FP_MAX_COUT * 4
+
+
+def three_nn_f32(fine, coarse, idx, dist2):
+    """fine [B, N, ld1] float32, coarse [B, S, ld2] float32, idx [B, N, k] int32, dist2 [B, N, k] float32, k = min(3, S): contiguous GPU
+    tensors."""
+    B, N, ld1 = fine.shape
+    S, ld2 = coarse.shape[1], coarse.shape[2]
+    k = min(3, S)
+    for name, t, dt in (("fine", fine, torch.float32), ("coarse", coarse, torch.float32), ("idx", idx, torch.int32), ("dist2", dist2, torch.float32)):
+        if not t.is_cuda or t.dtype != dt:
+            raise AmpnetError(f"three_nn: {name} must be a {dt} GPU tensor")
+    if coarse.shape[0] != B or tuple(idx.shape) != (B, N, k) or tuple(dist2.shape) != (B, N, k):
+        raise AmpnetError(f"three_nn: coarse [B, S, ld2], idx and dist2 [B, N, min(3, S)] do not agree with fine {tuple(fine.shape)}")
+    with torch.cuda.device(fine.device):
+        rc = lib().ampnet_three_nn_f32(ptr(fine), B, N, ld1, ptr(coarse), S, ld2, ptr(idx), ptr(dist2), stream_ptr(fine.device))
+    check(rc, "ampnet_three_nn_f32")
+
+
+def fp_forward_f32(points1, points2, idx, dist2, layers, eps, out, workspace):
+    """One fused feature-propagation layer.  points1 [B, N, D1] or None, points2 [B, S, D2], idx int32 / dist2 float32 [B, N, k] (the output
+    of three_nn_f32), layers and eps as in sa_forward_f32 with cin_0 = D1 + D2, out [B, N, cout_last]."""
+    L = len(layers)
+    for name, t, dt in (("points1", points1, torch.float32), ("points2", points2, torch.float32), ("idx", idx, torch.int32),
+                        ("dist2", dist2, torch.float32), ("out", out, torch.float32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or t.dim() != 3):
+            raise AmpnetError(f"fp_forward: {name} must be a 3-d {dt} GPU tensor")
+    B, N, k = idx.shape
+    S, D2 = points2.shape[1], points2.shape[2]
+    D1 = 0 if points1 is None else points1.shape[2]
+    cin = D1 + D2
+    for i, layer in enumerate(layers):                         # the kernel trusts these shapes: a short tensor would be read past its end
+        cout = int(layer[0].shape[0])
+        want = [(cout, cin)] + [(cout,)] * 5
+        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                                  for t, w in zip(layer, want)):
+            raise AmpnetError(f"fp_forward: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in layer]}")
+        cin = cout
+    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)) \
+            or (L and tuple(out.shape) != (B, N, int(layers[-1][0].shape[0]))) or len(eps) != L:
+        raise AmpnetError("fp_forward: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k], out [B, N, cout], eps [L] do not agree with "
+                          f"idx {tuple(idx.shape)}")
+    if workspace.numel() * workspace.element_size() < FP_WORKSPACE_BYTES or not workspace.is_cuda:
+        raise AmpnetError(f"fp_forward: the workspace must hold {FP_WORKSPACE_BYTES} GPU bytes")
+    tensors = [t for layer in layers for t in layer]
+    table = (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+    couts = (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers])
+    epss = (ctypes.c_float * max(L, 1))(*[float(e) for e in eps])
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L, ptr(out),
+                                         ptr(workspace), ctypes.c_size_t(workspace.numel() * workspace.element_size()),
+                                         stream_ptr(points2.device))
+    check(rc, "ampnet_fp_forward_f32")

@@ -13,16 +13,15 @@
 //     writes nothing -- its relu'd accumulators are reduced over their 16 registers and the two lane halves (the row dimension) and
 //     lanes h = 0 store the maxima.
 //   * BatchNorm is folded once per call, ahead of the main kernel, into scale = gamma / sqrt(var + eps) and
-//     shift = (b - mean) * scale + beta (sa_fold_kernel; the parameters live in device memory), applied as fma(acc, scale, shift).
+//     shift = (b - mean) * scale + beta (sa_fold_kernel, declared in sa_fold.h; the parameters live in device memory), applied as fma(acc, scale, shift).
 //   * A layer's weights are staged in LDS (rows padded to the odd stride, once per workgroup) while they fit next to the waves'
 //     tiles, in layer order; the layers that do not fit are read through L2 by the same lane map.
-#include "common.h"
+#include "sa_fold.h"
 
 namespace ampnet {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int SA_MAX_LAYERS = AMPNET_SA_MAX_LAYERS;
 constexpr int SA_LDS_BYTES = 160 * 1024;
 
 struct SaPlan {
@@ -33,12 +32,6 @@ struct SaPlan {
     int w_off[SA_MAX_LAYERS];             // float offset of the layer's staged weights in LDS, -1 = read through L2
     int fold_off[SA_MAX_LAYERS];          // float offset of the layer's scale[cout], shift[cout] in the workspace
     const float *w[SA_MAX_LAYERS];
-};
-
-struct SaFold {
-    int L, cout[SA_MAX_LAYERS], off[SA_MAX_LAYERS];
-    const float *bias[SA_MAX_LAYERS], *gamma[SA_MAX_LAYERS], *beta[SA_MAX_LAYERS], *mean[SA_MAX_LAYERS], *var[SA_MAX_LAYERS];
-    float eps[SA_MAX_LAYERS];
 };
 
 __global__ void sa_fold_kernel(SaFold f, float *__restrict__ fold)
@@ -193,6 +186,12 @@ __global__ __launch_bounds__(256) void sa_forward_kernel(SaPlan p, const float *
     }
 }
 
+int sa_fold_launch(const SaFold &f, float *fold, hipStream_t st)
+{
+    hipLaunchKernelGGL(sa_fold_kernel, dim3(1), dim3(256), 0, st, f, fold);
+    return check_launch("sa_fold_kernel");
+}
+
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 }  // namespace ampnet
@@ -260,8 +259,7 @@ extern "C" int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int 
         attr_set = true;
     }
     float *fold = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(sa_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f, fold);
-    int rc = check_launch("sa_fold_kernel");
+    int rc = sa_fold_launch(f, fold, (hipStream_t)stream);
     if (rc != AMPNET_OK) return rc;
     const int n_groups = n_clouds * s;
     // every workgroup stages the weights once: at most 4 workgroups per CU's worth of them, each wave walking several centres

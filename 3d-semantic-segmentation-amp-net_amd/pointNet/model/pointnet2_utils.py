@@ -1,14 +1,21 @@
-"""PointNet++ building blocks on the HIP path: the grouping half of the backbone the reference's `pointnet_2` class needs.
+"""PointNet++ building blocks on the HIP path: the two layer types the reference's `pointnet_2` class needs.
 
 The reference imports `PointNetSetAbstraction` and `PointNetFeaturePropagation` from a package it does not ship (pointnetAtt.py:4,
-used at :285-287).  This module provides the first of them with the constructor and the state_dict keys of the usual PointNet++
-implementation -- `mlp_convs.{i}.{weight [out, in, 1, 1], bias}`, `mlp_bns.{i}.{weight, bias, running_mean, running_var,
-num_batches_tracked}` -- so its checkpoints load.  Inference only: farthest-point sampling (ampnet_fps_f32), ball query
-(ampnet_ball_query_f32) and ONE fused kernel for gather + shared MLP + max (ampnet_sa_forward_f32, exact fp32 whatever the matrix
-precision is).  Not built: `group_all=True`, train-mode BatchNorm statistics, any backward, `PointNetFeaturePropagation`.
+used at :285-292).  This module provides both with the constructors and the state_dict keys of the usual PointNet++ implementation --
+`mlp_convs.{i}.{weight, bias}` (weight [out, in, 1, 1] in the set abstraction, [out, in, 1] in the feature propagation),
+`mlp_bns.{i}.{weight, bias, running_mean, running_var, num_batches_tracked}` -- so its checkpoints load.  Inference only:
+  * PointNetSetAbstraction: farthest-point sampling (ampnet_fps_f32), ball query (ampnet_ball_query_f32) and ONE fused kernel for
+    gather + shared MLP + max (ampnet_sa_forward_f32);
+  * PointNetFeaturePropagation: the 3 nearest coarse points of every fine point (ampnet_three_nn_f32) and ONE fused kernel for
+    inverse-distance interpolation + concatenation + shared MLP (ampnet_fp_forward_f32).
+Both fused kernels are exact fp32 whatever the matrix precision is.  Not built: `group_all=True`, train-mode BatchNorm statistics, any
+backward.
 
-Difference from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come from
-the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
+Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
+from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
+Its feature propagation finds the 3 neighbours by sorting a `-2 x.y + |x|^2 + |y|^2` matrix, so its choice among NEARLY equal neighbours
+depends on the library; here the distance is float32 ((dx*dx + dy*dy) + dz*dz) and equal distances go to the lower index
+(utils.three_nn).
 """
 import torch
 import torch.nn as nn
@@ -85,19 +92,101 @@ class PointNetSetAbstraction(nn.Module):
             if points is not None:
                 _lib.require_gpu(points, "points")
                 feats = points.detach().float().transpose(1, 2).contiguous()         # [B, N, D]
-            if centres is None:
-                centres = U.fps_indices(x, self.npoint)
-            elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
-                raise _lib.AmpnetError(f"PointNetSetAbstraction: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
-            group_idx = U.ball_query(x, centres, self.radius, self.nsample)           # validates the centres
-            centres = centres.contiguous()
-            layers = [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
-                       bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(),
-                       bn.running_mean.float().contiguous(), bn.running_var.float().contiguous())
-                      for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
-            if self._ws is None or self._ws.device != x.device:
-                self._ws = torch.empty(_lib.SA_WORKSPACE_BYTES, dtype=torch.uint8, device=x.device)
-            out = torch.empty((B, self.npoint, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
-            _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out, self._ws)
-            new_xyz = U.gather_rows(x, centres)                                       # [B, npoint, 3]
+            new_xyz, out = self._forward_rows(x, feats, centres)
         return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
+
+    def _forward_rows(self, x, feats, centres=None):
+        """The layer on point-major tensors (what the kernels take): x [B, N, 3], feats [B, N, D] or None, float32 contiguous GPU
+        -> (new_xyz [B, npoint, 3], new_points [B, npoint, mlp[-1]]).  pointnet_2 chains its blocks through this, without the transpose
+        pair per block that forward() owes to the channel-major interface."""
+        B = x.shape[0]
+        if centres is None:
+            centres = U.fps_indices(x, self.npoint)
+        elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
+            raise _lib.AmpnetError(f"PointNetSetAbstraction: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
+        group_idx = U.ball_query(x, centres, self.radius, self.nsample)           # validates the centres
+        centres = centres.contiguous()
+        layers = _mlp_tensors(self)
+        if self._ws is None or self._ws.device != x.device:
+            self._ws = torch.empty(_lib.SA_WORKSPACE_BYTES, dtype=torch.uint8, device=x.device)
+        out = torch.empty((B, self.npoint, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
+        _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out, self._ws)
+        return U.gather_rows(x, centres), out
+
+
+def _mlp_tensors(mod):
+    """Per layer the six contiguous float32 tensors the fused kernels take: weight [cout, cin], conv bias, BatchNorm weight, bias,
+    running_mean, running_var."""
+    return [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
+             bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(),
+             bn.running_mean.float().contiguous(), bn.running_var.float().contiguous())
+            for conv, bn in zip(mod.mlp_convs, mod.mlp_bns)]
+
+
+class _Conv1d(nn.Module):
+    """Holder with nn.Conv1d(cin, cout, 1)'s parameter names, shapes and initialisation bounds."""
+
+    def __init__(self, cin, cout, device):
+        super().__init__()
+        k = 1.0 / cin ** 0.5
+        self.weight = nn.Parameter(torch.empty(cout, cin, 1, device=device).uniform_(-k, k))
+        self.bias = nn.Parameter(torch.empty(cout, device=device).uniform_(-k, k))
+
+
+class PointNetFeaturePropagation(nn.Module):
+    """One feature-propagation layer: every fine point takes the inverse-squared-distance weighted mean of the features of its 3 nearest
+    coarse points (utils.three_nn; all of them when there are fewer than 3), concatenated behind its own features, through the shared MLP
+    `mlp` (Conv1d 1x1 + BatchNorm1d + ReLU per entry).  `in_channel` = D1 + D2, as in the usual implementation."""
+
+    def __init__(self, in_channel, mlp, device='cuda'):
+        super().__init__()
+        mlp = [int(c) for c in mlp]
+        if not (1 <= len(mlp) <= _lib.FP_MAX_LAYERS) or any(c % 32 or not 32 <= c <= _lib.FP_MAX_COUT for c in mlp) \
+                or not 1 <= in_channel <= _lib.FP_MAX_CIN:
+            raise NotImplementedError(f"the HIP feature propagation is built for 1..{_lib.FP_MAX_LAYERS} MLP layers of widths that are "
+                                      f"multiples of 32 up to {_lib.FP_MAX_COUT} and 1 <= in_channel <= {_lib.FP_MAX_CIN}")
+        self.in_channel = int(in_channel)
+        self.mlp_convs, self.mlp_bns = nn.ModuleList(), nn.ModuleList()
+        last = self.in_channel
+        for c in mlp:
+            self.mlp_convs.append(_Conv1d(last, c, device))
+            self.mlp_bns.append(_BN2d(c, device))                                     # BatchNorm1d has BatchNorm2d's names and shapes
+            last = c
+        self._ws = None
+
+    def forward(self, xyz1, xyz2, points1, points2):
+        """xyz1 [B, 3, N] the fine points, xyz2 [B, 3, S] the coarse ones, points1 [B, D1, N] or None, points2 [B, D2, S]
+        (D1 + D2 = in_channel) -> new_points [B, mlp[-1], N]."""
+        if self.training:
+            raise NotImplementedError("the HIP feature propagation is built for eval mode (BatchNorm running statistics, no backward): "
+                                      "call .eval() first")
+        for name, t in (("xyz1", xyz1), ("xyz2", xyz2), ("points1", points1), ("points2", points2)):
+            if t is not None:
+                _lib.require_gpu(t, name)
+        if xyz1.dim() != 3 or xyz1.shape[1] != 3 or xyz2.dim() != 3 or xyz2.shape[1] != 3 or xyz2.shape[0] != xyz1.shape[0]:
+            raise _lib.AmpnetError(f"PointNetFeaturePropagation: expected xyz1 [B, 3, N] and xyz2 [B, 3, S], got {tuple(xyz1.shape)} "
+                                   f"{tuple(xyz2.shape)}")
+        B, _, N = xyz1.shape
+        S = xyz2.shape[2]
+        if points2 is None or points2.dim() != 3 or points2.shape[0] != B or points2.shape[2] != S:
+            raise _lib.AmpnetError(f"PointNetFeaturePropagation: points2 must be [B, D2, S] = [{B}, D2, {S}], got "
+                                   f"{None if points2 is None else tuple(points2.shape)}")
+        D1 = self.in_channel - points2.shape[1]
+        if D1 < 0 or (points1 is None) != (D1 == 0) or (points1 is not None and tuple(points1.shape) != (B, D1, N)):
+            raise _lib.AmpnetError(f"PointNetFeaturePropagation: in_channel={self.in_channel} with points2 {tuple(points2.shape)} needs "
+                                   f"points1 {'None' if D1 == 0 else [B, D1, N]}, got {None if points1 is None else tuple(points1.shape)}")
+        with torch.no_grad():
+            rows = lambda t: None if t is None else t.detach().float().transpose(1, 2).contiguous()
+            out = self._forward_rows(rows(xyz1), rows(xyz2), rows(points1), rows(points2))
+        return out.transpose(1, 2).contiguous()
+
+    def _forward_rows(self, x1, x2, p1, p2):
+        """The layer on point-major tensors: x1 [B, N, 3], x2 [B, S, 3], p1 [B, N, D1] or None, p2 [B, S, D2], float32 contiguous GPU
+        -> [B, N, mlp[-1]]."""
+        idx, dist2 = U.three_nn(x1, x2)
+        layers = _mlp_tensors(self)
+        if self._ws is None or self._ws.device != x1.device:
+            self._ws = torch.empty(_lib.FP_WORKSPACE_BYTES, dtype=torch.uint8, device=x1.device)
+        out = torch.empty((x1.shape[0], x1.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
+        _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out, self._ws)
+        return out

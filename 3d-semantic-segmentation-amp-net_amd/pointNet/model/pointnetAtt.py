@@ -2,7 +2,7 @@
 
 Same class names, constructor arguments, forward signatures, return values and `state_dict` keys as the
 reference's pointNet/model/pointnetAtt.py (TransformationNet :7-47, BasePointNet :50-112,
-SegmentationWithAttention :154-209, SegmentationWithGRU :212-258), so reference checkpoints load and the reference's train/test scripts
+SegmentationWithAttention :154-209, SegmentationWithGRU :212-258, pointnet_2 :282-322 -- eval mode only), so reference checkpoints load and the reference's train/test scripts
 run unchanged on top of them.  The modules own ordinary nn.Parameters / buffers (as holders: their own
 `forward` is never used); every forward goes through the C ABI (ops.encoder_forward / ops.head_forward).
 There is no CPU or torch fallback: on a CPU tensor the call raises.
@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from ... import _lib, ops
 from ... import params as P
+from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction
 
 
 class _Conv(nn.Module):
@@ -415,3 +416,45 @@ class ClassificationWithAttention(_HasPrecision, nn.Module):
         if train:
             self.bn_2.num_batches_tracked += 1
         return out
+
+
+class pointnet_2(nn.Module):
+    """The PointNet++ backbone of pointnetAtt.py:282-322 in eval mode: three set-abstraction layers (`sa1`..`sa3`), three
+    feature-propagation layers (`fp3`..`fp1`) and `conv1`, with the reference's constructor argument, attribute names, layer sizes and
+    state_dict keys.  forward(xyz [B, 9, N]) -> (global_feature [B, 128], l0_points [B, 128, N]); the nine input channels are the point
+    features of `sa1`, the first three of them the coordinates.  Every block runs its fused HIP kernel (pointnet2_utils.py) and hands the
+    next one its point-major [B, N, C] result as it is; `conv1` and the max over the points are torch operations.  `num_classes` is
+    unused, as in the reference (its classifier layers are commented out there)."""
+
+    def __init__(self, num_classes, device='cuda'):
+        super().__init__()
+        self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device)
+        self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device)
+        self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device)
+        self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device)
+        self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device)
+        self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device)
+        self.conv1 = nn.Conv1d(128, 128, 1, device=device)
+
+    def forward(self, xyz):
+        if self.training:
+            raise NotImplementedError("pointnet_2 on the HIP path is built for eval mode (BatchNorm running statistics, no backward): "
+                                      "call .eval() first")
+        _lib.require_gpu(xyz, "xyz")
+        if xyz.dim() != 3 or xyz.shape[1] != 9:
+            raise _lib.AmpnetError(f"pointnet_2: expected xyz [B, 9, N], got {tuple(xyz.shape)}")
+        for m in (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1):
+            if m.training:
+                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model")
+        with torch.no_grad():
+            l0_points = xyz.detach().float().transpose(1, 2).contiguous()             # [B, N, 9]
+            l0_xyz = l0_points[:, :, :3].contiguous()                                 # [B, N, 3]
+            l1_xyz, l1_points = self.sa1._forward_rows(l0_xyz, l0_points)             # [B, 1024, 3], [B, 1024, 64]
+            l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)             # [B, 256, 3], [B, 256, 128]
+            l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)             # [B, 64, 3], [B, 64, 256]
+            l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)  # [B, 256, 256]
+            l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)  # [B, 1024, 128]
+            l0_points = self.fp1._forward_rows(l0_xyz, l1_xyz, None, l1_points)       # [B, N, 128]
+            l0_points = l0_points.transpose(1, 2).contiguous()                        # [B, 128, N], the reference's layout
+        global_feature = self.conv1(l0_points).amax(2)                                # MaxPool1d(N) + view(-1, 128)
+        return global_feature, l0_points

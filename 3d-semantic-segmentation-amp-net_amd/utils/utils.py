@@ -148,6 +148,33 @@ def ball_query(xyz, centres, radius, nsample, return_counts=False):
     return (out, count) if return_counts else out
 
 
+def three_nn(fine_xyz, coarse_xyz):
+    """The k = min(3, S) nearest coarse points of every fine point on the GPU (BUILD-DEFINED like knn_indices, include/ampnet_hip.h:
+    ampnet_three_nn_f32): the neighbour search of a PointNet++ feature-propagation layer.
+    fine_xyz [B, N, D>=3], coarse_xyz [B, S, D>=3] float32 GPU (the first 3 columns are used; the two widths may differ)
+    -> (idx int32 [B, N, k], dist2 float32 [B, N, k]): per fine point the coarse points with the smallest (float32 squared distance
+    ((dx*dx + dy*dy) + dz*dz), index), ascending, and those distances.  The usual implementation sorts -2 x.y + |x|^2 + |y|^2: among
+    nearly equal neighbours its choice depends on the library; here it does not, and equal distances go to the lower index."""
+    _lib.require_gpu(fine_xyz, "fine_xyz")
+    _lib.require_gpu(coarse_xyz, "coarse_xyz")
+    if fine_xyz.dim() != 3 or fine_xyz.shape[2] < 3 or coarse_xyz.dim() != 3 or coarse_xyz.shape[2] < 3 \
+            or coarse_xyz.shape[0] != fine_xyz.shape[0]:
+        raise _lib.AmpnetError(f"three_nn: expected fine_xyz [B, N, D>=3] and coarse_xyz [B, S, D>=3], got {tuple(fine_xyz.shape)} "
+                               f"{tuple(coarse_xyz.shape)}")
+    x1 = fine_xyz.float().contiguous()
+    x2 = coarse_xyz.float().contiguous()
+    B, N, S = x1.shape[0], x1.shape[1], x2.shape[1]
+    if not (1 <= S <= _lib.THREE_NN_MAX_S):
+        raise IndexError(f"three_nn: S={S} coarse points out of range [1, {_lib.THREE_NN_MAX_S}]")
+    if B < 1 or N < 1:
+        raise IndexError(f"three_nn: nothing to search for in fine_xyz {tuple(fine_xyz.shape)}")
+    k = min(3, S)
+    idx = torch.empty((B, N, k), dtype=torch.int32, device=x1.device)
+    dist2 = torch.empty((B, N, k), dtype=torch.float32, device=x1.device)
+    _lib.three_nn_f32(x1, x2, idx, dist2)
+    return idx, dist2
+
+
 def gather_rows(pc, idx):
     """pc [B, N, D] f32 GPU, idx [B, S] int32 -> [B, S, D] (the `pc[sample_inds]` of utils.py:933)."""
     _lib.require_gpu(pc, "pc")

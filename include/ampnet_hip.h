@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 9
+#define AMPNET_ABI_VERSION 10
 
 enum {
     AMPNET_OK = 0,
@@ -342,6 +342,43 @@ int ampnet_ball_query_f32(const float *xyz, int n_clouds, int n, int ld, const i
 int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
                           int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
                           const float *eps_host, int L, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- 3 nearest coarse points of every fine point (BUILD-DEFINED like ampnet_knn_f32) ---------------------------------------------------
+ * The neighbour search of a PointNet++ feature-propagation layer (the reference imports the layer from a package it does not ship,
+ * pointnetAtt.py:4); the spec below is pinned by the build's CPU restatement tests/fp_ref.py:three_nn.
+ *   fine     [n_clouds, n, ld1] float32 (first 3 columns used), no limit on n
+ *   coarse   [n_clouds, s, ld2] float32 (first 3 columns used), 1 <= s <= AMPNET_THREE_NN_MAX_S (s * 12 bytes <= 144 KB of LDS, the limit
+ *            of ampnet_knn_f32)
+ *   d(i, j)  = float32 ((dx*dx + dy*dy) + dz*dz), one rounding per operation, no fused multiply-add (the distance of ampnet_knn_f32 and
+ *              ampnet_ball_query_f32); coordinates are finite and d does not overflow
+ *   idx      [n_clouds, n, k] int32, k = min(3, s): for fine point i the k coarse points with the smallest (d, index), ascending
+ *   dist2    [n_clouds, n, k] float32: their d values themselves
+ * The usual implementation computes -2 x.y + |x|^2 + |y|^2 as a matrix product and sorts: which of several NEARLY equal neighbours it picks,
+ * and the order of exactly equal ones, depends on the library.  Here equal distances go to the lower index, always.                  */
+#define AMPNET_THREE_NN_MAX_S 12288
+int ampnet_three_nn_f32(const float *fine, int n_clouds, int n, int ld1, const float *coarse, int s, int ld2, int32_t *idx, float *dist2,
+                        void *stream);
+
+/* ---- one feature-propagation layer, eval mode, fused (stands in for PointNetFeaturePropagation.forward of pointnetAtt.py:4,290-292) --
+ *   points1               [n_clouds, n, D1] float32 features of the fine points, or NULL with D1 = 0
+ *   points2               [n_clouds, s, D2] float32 features of the coarse points, D2 >= 1
+ *   idx, dist2            [n_clouds, n, k] the output of ampnet_three_nn_f32, k in {1, 2, 3}, k <= s; indices are clamped into [0, s)
+ *   params_host, cout_host, eps_host, workspace   as in ampnet_sa_forward_f32 with cin_0 = D1 + D2; AMPNET_FP_WORKSPACE_BYTES device bytes
+ *   out                   [n_clouds, n, cout_{L-1}] float32
+ * The input row of fine point i is [points1[i] (D1 values), sum_k w_k points2[idx_k] (D2 values)] -- the column order of the usual
+ * cat([points1, interpolated]) -- with w_k = r_k / sum_k r_k, r_k = 1 / (dist2_k + 1e-8f) computed in the kernel (k = 1: weight 1, the
+ * usual "repeat" branch for s = 1).  Every layer computes relu(bn_eval(W row + b)), bn_eval folded as in ampnet_sa_forward_f32; the last
+ * layer's activations are the output.  Neither the interpolated features, the concatenated rows nor any intermediate activation is
+ * written to memory.  Limits (anything else is refused with AMPNET_E_ARG, there is no other path): 1 <= L <= AMPNET_FP_MAX_LAYERS,
+ * 1 <= D1 + D2 <= AMPNET_FP_MAX_CIN, every cout_l a multiple of 32 in [32, AMPNET_FP_MAX_COUT].
+ * Arithmetic: exact fp32 MFMA (v_mfma_f32_32x32x2_f32) whatever the matrix precision is, as ampnet_sa_forward_f32.                  */
+#define AMPNET_FP_MAX_LAYERS 3
+#define AMPNET_FP_MAX_CIN 512
+#define AMPNET_FP_MAX_COUT 256
+#define AMPNET_FP_WORKSPACE_BYTES (AMPNET_FP_MAX_LAYERS * 2 * AMPNET_FP_MAX_COUT * 4)
+int ampnet_fp_forward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                          const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                          float *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =

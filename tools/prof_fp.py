@@ -1,0 +1,77 @@
+"""3-NN search + fused feature-propagation forward at the reference's fp1 shape (the one that follows from tools/prof_sa.py's sa1 shape:
+B = 16, N = 8192 fine points, S = 1024 coarse points, D1 = 0, D2 = 128, MLP [128, 128, 128]) against what torch-ROCm offers for the same
+layer: cdist + topk, gather, weighted sum, conv1d + BatchNorm1d (eval) + relu.
+python3 tools/prof_fp.py [steps] [warmup]  -- HIP events, warm-up first, each of the three in a timed loop of its own, all in this process;
+prints one JSON line.  Under rocprofv3 (counters in a run of their own) the kernels to look for are three_nn_kernel and fp_forward_kernel."""
+import importlib, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+PKG = "3d-semantic-segmentation-amp-net_amd"
+synth = importlib.import_module(PKG + ".synthetic")
+U = importlib.import_module(PKG + ".utils.utils")
+L = importlib.import_module(PKG + "._lib")
+steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+warmup = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+B, N, S, D1, D2, MLP = 16, 8192, 1024, 0, 128, [128, 128, 128]
+dev = "cuda"
+fine = torch.from_numpy(synth.clouds(210, B, N)).to(dev)
+coarse = U.gather_rows(fine, U.fps_indices(fine, S))                  # the coarse points are FPS centres of the fine ones, as after sa1
+feats = torch.from_numpy(synth.uniform(211, (B, S, D2), -1.0, 1.0)).to(dev)
+g = torch.Generator().manual_seed(0)
+layers, cin = [], D1 + D2
+for cout in MLP:
+    layers.append(tuple(t.to(dev) for t in ((torch.rand(cout, cin, generator=g) - 0.5) * 2 / cin ** 0.5, (torch.rand(cout, generator=g) - 0.5) * 0.2,
+                                            0.5 + torch.rand(cout, generator=g), torch.rand(cout, generator=g) - 0.5,
+                                            (torch.rand(cout, generator=g) - 0.5) * 0.6, 0.5 + torch.rand(cout, generator=g))))
+    cin = cout
+ws = torch.empty(L.FP_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+out = torch.empty((B, N, MLP[-1]), device=dev)
+idx, dist2 = U.three_nn(fine, coarse)
+
+
+def timed(fn):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def torch_layer(neighbours=None):
+    """The same layer in torch, as a user of the usual implementation has it: the [B, N, S] distance matrix, the three smallest per row,
+    the gathered [B, N, 3, D2] features and every activation go through memory.  neighbours = (idx, dist2): skip the search and use these
+    (the comparison of the two outputs: cdist's matrix-product distances pick other neighbours at near-ties and turn a distance of 0
+    into ~1e-7, and an inverse-distance mean over another third neighbour is another number)."""
+    d, i = torch.cdist(fine, coarse).square().topk(3, dim=-1, largest=False) if neighbours is None else (neighbours[1], neighbours[0].long())
+    r = 1.0 / (d + 1e-8)
+    w = r / r.sum(-1, keepdim=True)
+    x = (feats[torch.arange(B, device=dev)[:, None, None], i] * w[..., None]).sum(2).transpose(1, 2)      # [B, D2, N]
+    for wt, b, gamma, beta, mean, var in layers:
+        x = torch.relu(torch.nn.functional.batch_norm(torch.nn.functional.conv1d(x, wt[:, :, None], b), mean, var, gamma, beta, False, 0.0, 1e-5))
+    return x.transpose(1, 2)
+
+
+with torch.no_grad():
+    nn_ms = timed(lambda: U.three_nn(fine, coarse))
+    fp_ms = timed(lambda: L.fp_forward_f32(None, feats, idx, dist2, layers, [1e-5] * len(MLP), out, ws))
+    torch_ms = timed(torch_layer)
+    err_same = float((out - torch_layer((idx, dist2))).abs().max())
+    err_own = float((out - torch_layer()).abs().max())
+    t_idx = torch.cdist(fine, coarse).topk(3, dim=-1, largest=False)[1]
+    other = float((t_idx.sort(-1)[0] != idx.long().sort(-1)[0]).any(-1).float().mean())
+w_bytes = sum(sum(t.numel() for t in layer) for layer in layers) * 4
+# the algorithmic bytes of the fused forward: the coarse features once, the neighbours and distances, the weights, the output
+algo = B * S * D2 * 4 + B * N * 3 * 8 + w_bytes + B * N * MLP[-1] * 4
+flops = 2.0 * B * N * (3 * D2 + sum(a * b for a, b in zip([D1 + D2] + MLP[:-1], MLP)))
+print(json.dumps({"shape": {"B": B, "N": N, "S": S, "D1": D1, "D2": D2, "mlp": MLP}, "three_nn_ms": round(nn_ms, 4),
+                  "fp_forward_ms": round(fp_ms, 4), "torch_cdist_topk_gather_conv1d_ms": round(torch_ms, 4),
+                  "torch_over_three_nn_plus_fused": round(torch_ms / (nn_ms + fp_ms), 2),
+                  "fp_algorithmic_bytes": algo, "fp_GBps_at_algorithmic_bytes": round(algo / (fp_ms * 1e-3) / 1e9, 1),
+                  "fp_useful_TFLOPs": round(flops / (fp_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch_on_the_same_neighbours": err_same,
+                  "max_abs_diff_vs_torch_on_its_own_neighbours": err_own, "rows_where_torch_picks_other_neighbours": other}))

@@ -166,20 +166,34 @@ def ball_query_f32(xyz, centres, radius, nsample, out, count=None):
     check(rc, "ampnet_ball_query_f32")
 
 
+def _mlp_tables(prefix, layers, cin, eps, workspace, workspace_bytes):
+    """What the fused forwards (sa_forward_f32, fp_forward_f32) share: every layer is six contiguous float32 GPU tensors of shapes
+    [(cout, cin)] + [(cout,)] * 5 chained from cin (the kernels trust these shapes: a short tensor would be read past its end), eps has one
+    entry per layer, the workspace holds workspace_bytes GPU bytes -> the (pointer table, couts, epss) ctypes arrays of the C ABI."""
+    L = len(layers)
+    for i, layer in enumerate(layers):
+        cout = int(layer[0].shape[0])
+        want = [(cout, cin)] + [(cout,)] * 5
+        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                                  for t, w in zip(layer, want)):
+            raise AmpnetError(f"{prefix}: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in layer]}")
+        cin = cout
+    if len(eps) != L:
+        raise AmpnetError(f"{prefix}: eps has {len(eps)} entries for {L} layers")
+    if workspace.numel() * workspace.element_size() < workspace_bytes or not workspace.is_cuda:
+        raise AmpnetError(f"{prefix}: the workspace must hold {workspace_bytes} GPU bytes")
+    tensors = [t for layer in layers for t in layer]
+    return ((ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors]),
+            (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers]),
+            (ctypes.c_float * max(L, 1))(*[float(e) for e in eps]))
+
+
 def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
     """One fused set-abstraction layer.  layers: per layer the six contiguous float32 GPU tensors (weight [cout, cin], conv bias, BatchNorm
     weight, bias, running_mean, running_var); eps: per layer the BatchNorm eps; feats [B, N, D] or None; out [B, S, cout_last]."""
     B, N, ld = xyz.shape
     L = len(layers)
-    cin = 3 + (0 if feats is None else feats.shape[2])
-    for i, layer in enumerate(layers):                         # the kernel trusts these shapes: a short tensor would be read past its end
-        cout = int(layer[0].shape[0])
-        want = [(cout, cin)] + [(cout,)] * 5
-        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
-                                  for t, w in zip(layer, want)):
-            raise AmpnetError(f"sa_forward: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
-                              f"got {[tuple(t.shape) for t in layer]}")
-        cin = cout
     for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
                         ("feats", feats, torch.float32), ("out", out, torch.float32)):
         if t is not None and (not t.is_cuda or t.dtype != dt):
@@ -188,10 +202,7 @@ def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
     if tuple(centres.shape) != (B, S) or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != (B, S) \
             or (feats is not None and tuple(feats.shape[:2]) != (B, N)) or (L and tuple(out.shape) != (B, S, int(layers[-1][0].shape[0]))):
         raise AmpnetError("sa_forward: centres [B, S], group_idx [B, S, nsample], feats [B, N, D], out [B, S, cout] do not agree with xyz [B, N, ld]")
-    tensors = [t for layer in layers for t in layer]
-    table = (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
-    couts = (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers])
-    epss = (ctypes.c_float * max(L, 1))(*[float(e) for e in eps])
+    table, couts, epss = _mlp_tables("sa_forward", layers, 3 + (0 if feats is None else feats.shape[2]), eps, workspace, SA_WORKSPACE_BYTES)
     with torch.cuda.device(xyz.device):
         rc = lib().ampnet_sa_forward_f32(ptr(xyz), B, N, ld, ptr(centres), centres.shape[1], ptr(group_idx), group_idx.shape[2], ptr(feats),
                                          0 if feats is None else feats.shape[2], table, couts, epss, L, ptr(out), ptr(workspace),
@@ -232,25 +243,11 @@ def fp_forward_f32(points1, points2, idx, dist2, layers, eps, out, workspace):
     B, N, k = idx.shape
     S, D2 = points2.shape[1], points2.shape[2]
     D1 = 0 if points1 is None else points1.shape[2]
-    cin = D1 + D2
-    for i, layer in enumerate(layers):                         # the kernel trusts these shapes: a short tensor would be read past its end
-        cout = int(layer[0].shape[0])
-        want = [(cout, cin)] + [(cout,)] * 5
-        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
-                                  for t, w in zip(layer, want)):
-            raise AmpnetError(f"fp_forward: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
-                              f"got {[tuple(t.shape) for t in layer]}")
-        cin = cout
     if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)) \
-            or (L and tuple(out.shape) != (B, N, int(layers[-1][0].shape[0]))) or len(eps) != L:
-        raise AmpnetError("fp_forward: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k], out [B, N, cout], eps [L] do not agree with "
+            or (L and tuple(out.shape) != (B, N, int(layers[-1][0].shape[0]))):
+        raise AmpnetError("fp_forward: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k], out [B, N, cout] do not agree with "
                           f"idx {tuple(idx.shape)}")
-    if workspace.numel() * workspace.element_size() < FP_WORKSPACE_BYTES or not workspace.is_cuda:
-        raise AmpnetError(f"fp_forward: the workspace must hold {FP_WORKSPACE_BYTES} GPU bytes")
-    tensors = [t for layer in layers for t in layer]
-    table = (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
-    couts = (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers])
-    epss = (ctypes.c_float * max(L, 1))(*[float(e) for e in eps])
+    table, couts, epss = _mlp_tables("fp_forward", layers, D1 + D2, eps, workspace, FP_WORKSPACE_BYTES)
     with torch.cuda.device(points2.device):
         rc = lib().ampnet_fp_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L, ptr(out),
                                          ptr(workspace), ctypes.c_size_t(workspace.numel() * workspace.element_size()),

@@ -24,13 +24,14 @@ from ... import _lib
 from ...utils import utils as U
 
 
-class _Conv2d(nn.Module):
-    """Holder with nn.Conv2d(cin, cout, 1)'s parameter names, shapes and initialisation bounds."""
+class _Conv(nn.Module):
+    """Holder with the parameter names, shapes and initialisation bounds of nn.Conv2d(cin, cout, 1) (tail = (1, 1)) or nn.Conv1d(cin, cout, 1)
+    (tail = (1,))."""
 
-    def __init__(self, cin, cout, device):
+    def __init__(self, cin, cout, tail, device):
         super().__init__()
         k = 1.0 / cin ** 0.5
-        self.weight = nn.Parameter(torch.empty(cout, cin, 1, 1, device=device).uniform_(-k, k))
+        self.weight = nn.Parameter(torch.empty(cout, cin, *tail, device=device).uniform_(-k, k))
         self.bias = nn.Parameter(torch.empty(cout, device=device).uniform_(-k, k))
 
 
@@ -47,6 +48,31 @@ class _BN2d(nn.Module):
         self.register_buffer("num_batches_tracked", torch.zeros((), dtype=torch.long, device=device))
 
 
+assert (_lib.SA_MAX_LAYERS, _lib.SA_MAX_COUT) == (_lib.FP_MAX_LAYERS, _lib.FP_MAX_COUT)     # _build_mlp checks one pair for both layers
+
+
+def _build_mlp(mod, in_channel, mlp, tail, ok, limits, device):
+    """Sets mod.in_channel, mod.mlp_convs and mod.mlp_bns (BatchNorm1d has BatchNorm2d's names and shapes) for the widths `mlp`; `ok` is the layer's own limit check and `limits` the sentence that names every limit."""
+    mlp = [int(c) for c in mlp]
+    if not (1 <= len(mlp) <= _lib.SA_MAX_LAYERS) or any(c % 32 or not 32 <= c <= _lib.SA_MAX_COUT for c in mlp) or not ok:
+        raise NotImplementedError(limits)
+    mod.in_channel = int(in_channel)
+    mod.mlp_convs, mod.mlp_bns = nn.ModuleList(), nn.ModuleList()
+    last = mod.in_channel
+    for c in mlp:
+        mod.mlp_convs.append(_Conv(last, c, tail, device))
+        mod.mlp_bns.append(_BN2d(c, device))
+        last = c
+    mod._ws = None
+
+
+def _workspace(mod, nbytes, device):
+    """The module's fold workspace, allocated on first use and again when the input moves to another device."""
+    if mod._ws is None or mod._ws.device != device:
+        mod._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return mod._ws
+
+
 class PointNetSetAbstraction(nn.Module):
     """One set-abstraction layer: `npoint` centres by farthest-point sampling, per centre the first `nsample` points within `radius`
     (utils.ball_query), the shared MLP `mlp` (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on [relative xyz, point features], max over the
@@ -57,20 +83,10 @@ class PointNetSetAbstraction(nn.Module):
         if group_all:
             raise NotImplementedError("the HIP set abstraction is built for group_all=False (ball-query groups of <= 64 points); "
                                       "the single all-points group is not")
-        mlp = [int(c) for c in mlp]
-        if not (1 <= len(mlp) <= _lib.SA_MAX_LAYERS) or any(c % 32 or not 32 <= c <= _lib.SA_MAX_COUT for c in mlp) \
-                or not 3 <= in_channel <= _lib.SA_MAX_CIN or not 1 <= nsample <= _lib.SA_MAX_NSAMPLE:
-            raise NotImplementedError(f"the HIP set abstraction is built for 1..{_lib.SA_MAX_LAYERS} MLP layers of widths that are multiples "
-                                      f"of 32 up to {_lib.SA_MAX_COUT}, 3 <= in_channel <= {_lib.SA_MAX_CIN}, nsample <= {_lib.SA_MAX_NSAMPLE}")
+        _build_mlp(self, in_channel, mlp, (1, 1), 3 <= in_channel <= _lib.SA_MAX_CIN and 1 <= nsample <= _lib.SA_MAX_NSAMPLE,
+                   f"the HIP set abstraction is built for 1..{_lib.SA_MAX_LAYERS} MLP layers of widths that are multiples "
+                   f"of 32 up to {_lib.SA_MAX_COUT}, 3 <= in_channel <= {_lib.SA_MAX_CIN}, nsample <= {_lib.SA_MAX_NSAMPLE}", device)
         self.npoint, self.radius, self.nsample, self.group_all = int(npoint), float(radius), int(nsample), False
-        self.in_channel = int(in_channel)
-        self.mlp_convs, self.mlp_bns = nn.ModuleList(), nn.ModuleList()
-        last = self.in_channel
-        for c in mlp:
-            self.mlp_convs.append(_Conv2d(last, c, device))
-            self.mlp_bns.append(_BN2d(c, device))
-            last = c
-        self._ws = None
 
     def forward(self, xyz, points, centres=None):
         """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]).
@@ -107,10 +123,9 @@ class PointNetSetAbstraction(nn.Module):
         group_idx = U.ball_query(x, centres, self.radius, self.nsample)           # validates the centres
         centres = centres.contiguous()
         layers = _mlp_tensors(self)
-        if self._ws is None or self._ws.device != x.device:
-            self._ws = torch.empty(_lib.SA_WORKSPACE_BYTES, dtype=torch.uint8, device=x.device)
         out = torch.empty((B, self.npoint, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
-        _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out, self._ws)
+        _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out,
+                            _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
         return U.gather_rows(x, centres), out
 
 
@@ -123,16 +138,6 @@ def _mlp_tensors(mod):
             for conv, bn in zip(mod.mlp_convs, mod.mlp_bns)]
 
 
-class _Conv1d(nn.Module):
-    """Holder with nn.Conv1d(cin, cout, 1)'s parameter names, shapes and initialisation bounds."""
-
-    def __init__(self, cin, cout, device):
-        super().__init__()
-        k = 1.0 / cin ** 0.5
-        self.weight = nn.Parameter(torch.empty(cout, cin, 1, device=device).uniform_(-k, k))
-        self.bias = nn.Parameter(torch.empty(cout, device=device).uniform_(-k, k))
-
-
 class PointNetFeaturePropagation(nn.Module):
     """One feature-propagation layer: every fine point takes the inverse-squared-distance weighted mean of the features of its 3 nearest
     coarse points (utils.three_nn; all of them when there are fewer than 3), concatenated behind its own features, through the shared MLP
@@ -140,19 +145,9 @@ class PointNetFeaturePropagation(nn.Module):
 
     def __init__(self, in_channel, mlp, device='cuda'):
         super().__init__()
-        mlp = [int(c) for c in mlp]
-        if not (1 <= len(mlp) <= _lib.FP_MAX_LAYERS) or any(c % 32 or not 32 <= c <= _lib.FP_MAX_COUT for c in mlp) \
-                or not 1 <= in_channel <= _lib.FP_MAX_CIN:
-            raise NotImplementedError(f"the HIP feature propagation is built for 1..{_lib.FP_MAX_LAYERS} MLP layers of widths that are "
-                                      f"multiples of 32 up to {_lib.FP_MAX_COUT} and 1 <= in_channel <= {_lib.FP_MAX_CIN}")
-        self.in_channel = int(in_channel)
-        self.mlp_convs, self.mlp_bns = nn.ModuleList(), nn.ModuleList()
-        last = self.in_channel
-        for c in mlp:
-            self.mlp_convs.append(_Conv1d(last, c, device))
-            self.mlp_bns.append(_BN2d(c, device))                                     # BatchNorm1d has BatchNorm2d's names and shapes
-            last = c
-        self._ws = None
+        _build_mlp(self, in_channel, mlp, (1,), 1 <= in_channel <= _lib.FP_MAX_CIN,
+                   f"the HIP feature propagation is built for 1..{_lib.FP_MAX_LAYERS} MLP layers of widths that are "
+                   f"multiples of 32 up to {_lib.FP_MAX_COUT} and 1 <= in_channel <= {_lib.FP_MAX_CIN}", device)
 
     def forward(self, xyz1, xyz2, points1, points2):
         """xyz1 [B, 3, N] the fine points, xyz2 [B, 3, S] the coarse ones, points1 [B, D1, N] or None, points2 [B, D2, S]
@@ -185,8 +180,7 @@ class PointNetFeaturePropagation(nn.Module):
         -> [B, N, mlp[-1]]."""
         idx, dist2 = U.three_nn(x1, x2)
         layers = _mlp_tensors(self)
-        if self._ws is None or self._ws.device != x1.device:
-            self._ws = torch.empty(_lib.FP_WORKSPACE_BYTES, dtype=torch.uint8, device=x1.device)
         out = torch.empty((x1.shape[0], x1.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
-        _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out, self._ws)
+        _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out,
+                            _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
         return out

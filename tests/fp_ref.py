@@ -3,7 +3,7 @@ ampnet_fp_forward_f32): float32 for the neighbour search, float64 for the interp
 library."""
 import numpy as np
 
-from sa_ref import EPS32, make_layers                # noqa: F401  (make_layers: re-exported for the tests)
+from sa_ref import EPS32, make_layers, mlp_chain     # noqa: F401  (make_layers: re-exported for the tests)
 
 # roundings between the float32 inputs and one interpolated feature, see fp_forward
 C_INTERP = 11.0
@@ -43,9 +43,7 @@ def fp_forward(points1, points2, idx, dist2, layers, eps):
         in all 2 + 4 + 1 = 7 on w_k;  then the product w_k f_k and <= 2 additions of the 3-term sum: 3 (a fused multiply-add only
         removes one).  Every term w_k f_k therefore carries <= 10 roundings, a relative error (1 + e)^10 - 1 < 11 e:
             |err| <= C_INTERP e sum_k |w_k f_k|,  C_INTERP = 11;
-      * a layer with input a (bound b_in), product z = W a of length K:  |W| b_in  +  8 e sqrt(K) (|W| |a|)  +  2 e |z|   (pw_probe.bar);
-      * the folded BatchNorm multiplies that by |scale| and adds  6 e (|z scale| + |(b - mean) scale| + |beta|)  (sa_ref.sa_forward);
-      * ReLU is 1-Lipschitz."""
+      * the layers: sa_ref.mlp_chain."""
     d = np.asarray(dist2, dtype=np.float64)
     r = 1.0 / (d + np.float64(np.float32(1e-8)))
     w = r / r.sum(1, keepdims=True)
@@ -56,15 +54,4 @@ def fp_forward(points1, points2, idx, dist2, layers, eps):
         p1 = np.asarray(points1, dtype=np.float64)
         rows = np.concatenate([p1, rows], -1)
         b_in = np.concatenate([np.zeros_like(p1), b_in], -1)
-    a = rows
-    for (wt, b, gamma, beta, mean, var), e in zip(layers, eps):
-        wt, b, gamma, beta, mean, var = (np.asarray(v, dtype=np.float64) for v in (wt, b, gamma, beta, mean, var))
-        K = wt.shape[1]
-        z = a @ wt.T
-        mag = np.abs(a) @ np.abs(wt).T
-        scale = gamma / np.sqrt(var + np.float64(np.float32(e)))
-        y = (z + b - mean) * scale + beta
-        bz = b_in @ np.abs(wt).T + 8.0 * EPS32 * np.sqrt(K) * mag + 2.0 * EPS32 * np.abs(z)
-        b_in = np.abs(scale) * bz + 6.0 * EPS32 * (np.abs(z * scale) + np.abs((b - mean) * scale) + np.abs(beta))
-        a = np.maximum(y, 0.0)
-    return a, b_in
+    return mlp_chain(rows, b_in, layers, eps)

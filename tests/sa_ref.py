@@ -47,29 +47,17 @@ def make_layers(seed, cin, widths, negative_gamma=False):
     return layers
 
 
-def sa_forward(xyz, centres, group_idx, feats, layers, eps):
-    """One cloud.  xyz [n, >=3] float32, centres [s], group_idx [s, nsample], feats [n, D] float32 or None, layers as make_layers, eps per
-    layer -> (out float64 [s, cout_last], bar float64 [s, cout_last]).
+def mlp_chain(a, b_in, layers, eps):
+    """The shared MLP of the fused forwards on rows a [..., cin_0] (float64) that carry the error bound b_in: per layer
+    a <- relu(bn_eval(W a + b)), bn_eval(v) = (v - mean) / sqrt(var + eps) * gamma + beta, in float64 -> (a, b_in) of the last layer.
 
-    out: float64 evaluation of  max_t relu(bn_eval(W row_t + b))  over the layers, row_t = [xyz[idx_t] - xyz[centre], feats[idx_t]] formed
-    exactly from the float32 inputs, bn_eval(v) = (v - mean) / sqrt(var + eps) * gamma + beta.
-
-    bar: the float32 error bound of tests/pw_probe.py::bar pushed through the chain, per output element.  With e = 2^-24:
-      * input: the kernel rounds the three coordinate differences once, |err| <= e |dx|; the features are exact;
+    The float32 error bound of tests/pw_probe.py::bar pushed through the chain, per element.  With e = 2^-24:
       * a layer with input a (bound b_in), product z = W a of length K:  |W| b_in  +  8 e sqrt(K) (|W| |a|)  +  2 e |z|   (pw_probe.bar);
       * the folded BatchNorm y = fma(z, scale, shift), scale = gamma / sqrt(var + eps), shift = (b - mean) scale + beta, multiplies that by
         |scale| and adds its own roundings: scale carries <= 2 e (sum, sqrt, quotient, each half an ulp), b - mean one, the product and
         sum of shift one each, the final fma one -- in all <= 3 e |z scale| + 6 e |(b - mean) scale| + 2 e |beta|, bounded here by
         6 e (|z scale| + |(b - mean) scale| + |beta|);
-      * ReLU and max are 1-Lipschitz: the bound of relu(y) is that of y, the bound of the max is the largest row bound of the group."""
-    p = np.asarray(xyz, dtype=np.float64)[:, :3]
-    rows = p[group_idx] - p[np.asarray(centres)][:, None, :]                             # [s, nsample, 3], exact in float64
-    b_in = EPS32 * np.abs(rows)
-    if feats is not None:
-        f = np.asarray(feats, dtype=np.float64)[group_idx]
-        rows = np.concatenate([rows, f], -1)
-        b_in = np.concatenate([b_in, np.zeros_like(f)], -1)
-    a = rows
+      * ReLU is 1-Lipschitz: the bound of relu(y) is that of y."""
     for (w, b, gamma, beta, mean, var), e in zip(layers, eps):
         w, b, gamma, beta, mean, var = (np.asarray(v, dtype=np.float64) for v in (w, b, gamma, beta, mean, var))
         K = w.shape[1]
@@ -80,4 +68,26 @@ def sa_forward(xyz, centres, group_idx, feats, layers, eps):
         bz = b_in @ np.abs(w).T + 8.0 * EPS32 * np.sqrt(K) * mag + 2.0 * EPS32 * np.abs(z)
         b_in = np.abs(scale) * bz + 6.0 * EPS32 * (np.abs(z * scale) + np.abs((b - mean) * scale) + np.abs(beta))
         a = np.maximum(y, 0.0)
+    return a, b_in
+
+
+def sa_forward(xyz, centres, group_idx, feats, layers, eps):
+    """One cloud.  xyz [n, >=3] float32, centres [s], group_idx [s, nsample], feats [n, D] float32 or None, layers as make_layers, eps per
+    layer -> (out float64 [s, cout_last], bar float64 [s, cout_last]).
+
+    out: float64 evaluation of  max_t relu(bn_eval(W row_t + b))  over the layers, row_t = [xyz[idx_t] - xyz[centre], feats[idx_t]] formed
+    exactly from the float32 inputs, bn_eval(v) = (v - mean) / sqrt(var + eps) * gamma + beta.
+
+    bar: the float32 error bound per output element.  With e = 2^-24:
+      * input: the kernel rounds the three coordinate differences once, |err| <= e |dx|; the features are exact;
+      * the layers: mlp_chain;
+      * max is 1-Lipschitz: the bound of the max is the largest row bound of the group."""
+    p = np.asarray(xyz, dtype=np.float64)[:, :3]
+    rows = p[group_idx] - p[np.asarray(centres)][:, None, :]                             # [s, nsample, 3], exact in float64
+    b_in = EPS32 * np.abs(rows)
+    if feats is not None:
+        f = np.asarray(feats, dtype=np.float64)[group_idx]
+        rows = np.concatenate([rows, f], -1)
+        b_in = np.concatenate([b_in, np.zeros_like(f)], -1)
+    a, b_in = mlp_chain(rows, b_in, layers, eps)
     return a.max(1), b_in.max(1)

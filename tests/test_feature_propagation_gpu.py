@@ -26,7 +26,10 @@ CASES = [("one_layer",      70,  5,  0,   32,  [32],             False),
          ("fp1_form",       33,  4,  0,   128, [128, 128, 128],  False),
          ("one_coarse",     70,  1,  7,   32,  [64, 32],         False),      # k = 1: the "repeat" branch
          ("two_coarse",     70,  2,  0,   32,  [32],             False),      # k = 2
-         ("negative_gamma", 70,  9,  7,   32,  [64, 32],         True)]
+         ("negative_gamma", 70,  9,  7,   32,  [64, 32],         True),
+         # no layer's weights fit beside two waves' 265 + 257 wide tiles: layer 0 (cin = 263) is read dword by dword with column
+         # 263 of its last block of 8 masked (not read), layer 1 (cin = 256) by dwordx4
+         ("odd_wide",       40,  6,  7,   256, [256, 32],        False)]
 
 
 def _inputs(synth, seed, n, s, D1, D2):

@@ -28,6 +28,8 @@ CASES = [("sa1_form",       512, 64, 32,     9,  [32, 32, 64],    0.25,   False)
          ("two_layers",     256, 32, 32,     9,  [64, 96],        0.35,   False),
          ("one_layer",      200, 20, 24,     5,  [160],           0.35,   False),
          ("wide_input",     96,  8,  40,     317, [256, 32],      0.6,    False),
+         # cin_0 = 313 in 320 padded columns, one wave per workgroup, no layer staged: weight columns 313 .. 319 are masked, not read
+         ("wide_odd_input", 96,  8,  40,     310, [256, 32],      0.6,    False),
          ("negative_gamma", 256, 32, 32,     9,  [32, 64, 32],    0.35,   True),
          ("lonely_groups",  256, 32, 32,     9,  [32, 32, 64],    0.02,   False)]
 
@@ -41,12 +43,13 @@ def _inputs(synth, seed, n, s, nsample, D, radius):
     return xyz, feats, cent, np.stack(grp), np.stack(cnt)
 
 
-def _run(L, xyz, feats, cent, grp, layers, prefill=float("nan")):
+def _run(L, xyz, feats, cent, grp, layers, prefill=float("nan"), eps=None, ws_bytes=None):
     dev = "cuda"
     t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     out = torch.full((xyz.shape[0], cent.shape[1], layers[-1][0].shape[0]), prefill, dtype=torch.float32, device=dev)
-    ws = torch.empty(L.SA_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
-    L.sa_forward_f32(t(xyz), t(cent), t(grp), t(feats), [tuple(t(a) for a in layer) for layer in layers], [BN_EPS] * len(layers), out, ws)
+    ws = torch.empty(L.SA_WORKSPACE_BYTES if ws_bytes is None else ws_bytes, dtype=torch.uint8, device=dev)
+    L.sa_forward_f32(t(xyz), t(cent), t(grp), t(feats), [tuple(t(a) for a in layer) for layer in layers],
+                     [BN_EPS] * len(layers) if eps is None else eps, out, ws)
     return out.cpu().numpy()
 
 
@@ -99,3 +102,7 @@ def test_sa_forward_refusals(synth):
         _run(L, xyz, feats, cent, grp, sa_ref.make_layers(1, 12, [32, 32, 32, 32]))
     with pytest.raises(L.AmpnetError):
         _run(L, xyz, feats, cent, grp, sa_ref.make_layers(1, 13, [32]))           # weight [32, 13] against cin_0 = 12
+    with pytest.raises(L.AmpnetError):
+        _run(L, xyz, feats, cent, grp, sa_ref.make_layers(1, 12, [32]), eps=[BN_EPS] * 2)          # one eps per layer
+    with pytest.raises(L.AmpnetError):
+        _run(L, xyz, feats, cent, grp, sa_ref.make_layers(1, 12, [32]), ws_bytes=L.SA_WORKSPACE_BYTES - 1)

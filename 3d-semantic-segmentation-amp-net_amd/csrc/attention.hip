@@ -7,8 +7,6 @@
 
 namespace ampnet {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void posenc_tokens_kernel(const float *__restrict__ gl, const float *__restrict__ cent,
                                                            const float *__restrict__ w1, const float *__restrict__ b1,
                                                            const float *__restrict__ w2, const float *__restrict__ b2,

@@ -6,7 +6,6 @@
 
 namespace ampnet {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ----------------------------------------------------------------------------------------------------
 // bn_bwd_finalize: block = (slot, 64 channels) x 4 groups over the slot's partials, fixed order
@@ -343,17 +342,15 @@ __global__ __launch_bounds__(256 * SG_SK) void sgemm_small_kernel(SgArgs args)
 constexpr int SGM_WAVES = 16;
 constexpr int SGM_PASS = 8;              // chunks of 8 k values a wave has in flight per pass
 
-typedef float sg_f32x16 __attribute__((ext_vector_type(16)));
-typedef float sg_f32x4 __attribute__((ext_vector_type(4)));
 
 // four k values 8 c + 4 h + i of row / column x of an operand; kmaj: k contiguous in memory (element (x, k) at base[x * ld + k])
-__device__ __forceinline__ sg_f32x4 sgm_fetch(const float *__restrict__ base, int ld, bool kmaj, bool vec, int x, int X, int k, int K)
+__device__ __forceinline__ f32x4 sgm_fetch(const float *__restrict__ base, int ld, bool kmaj, bool vec, int x, int X, int k, int K)
 {
-    sg_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (x >= X) return v;
     if (kmaj) {
         const float *p = base + (size_t)x * ld + k;
-        if (vec && k + 3 < K) return *reinterpret_cast<const sg_f32x4 *>(p);
+        if (vec && k + 3 < K) return *reinterpret_cast<const f32x4 *>(p);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (k + i < K) v[i] = p[i];
@@ -382,12 +379,12 @@ __global__ __launch_bounds__(64 * SGM_WAVES) void sgemm_mfma_kernel(SgArgs args)
     const int per_wave = (chunks + SGM_WAVES - 1) / SGM_WAVES;
     const int c_begin = min(wave * per_wave, chunks), c_end = min(c_begin + per_wave, chunks);
     const bool do_rs = g.db != nullptr && blockIdx.x == 0;
-    sg_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
     float rs = 0.f;
     for (int c0 = c_begin; c0 < c_end; c0 += SGM_PASS) {
-        sg_f32x4 av[SGM_PASS], bv[SGM_PASS];
+        f32x4 av[SGM_PASS], bv[SGM_PASS];
 #pragma unroll
         for (int u = 0; u < SGM_PASS; ++u) {
             if (c0 + u < c_end) {                                // wave-uniform
@@ -463,12 +460,7 @@ static int sgemm_launch(const SgProblem *probs, int n, hipStream_t st)
         return check_launch("sgemm_small_kernel");
     }
     constexpr size_t lds = (size_t)(SGM_WAVES * 16 * 64 + SGM_WAVES * 32) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sgemm_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "sgemm_mfma: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (int rc = allow_dynamic_lds<sgemm_mfma_kernel>(lds, "sgemm_mfma")) return rc;
     ProfScope prof("sgemm_mfma", flops, bytes, st);
     hipLaunchKernelGGL(sgemm_mfma_kernel, dim3(gx, gy, n), dim3(64 * SGM_WAVES), lds, st, a);
     return check_launch("sgemm_mfma_kernel");
@@ -689,7 +681,9 @@ __global__ __launch_bounds__(64 * IW_WAVES) void pw_input_wgrad_kernel(PwInputWg
     const int slot = a.n_slots > 1 ? q % a.n_slots : 0;
     float p1, p2, p3;
     if (a.fin_part_a) {
-        // wave w sums the slot's partials w, w + IW_WAVES, ... (all loads of a trip in flight), the waves merge through LDS in wave order
+        // the same arithmetic as the fin_* prologue of the fused backward (pw_bwd_fused.hip), on this kernel's own layout -- lane = channel, one
+        // scalar per thread instead of a channel quad: wave w sums the slot's partials w, w + IW_WAVES, ... (all loads of a trip in flight),
+        // the waves merge through LDS in wave order
         double sa = 0.0, sb = 0.0;
         const int per_slot_parts = (a.fin_parts - slot + a.n_slots - 1) / a.n_slots;
         for (int k0 = wave; k0 < per_slot_parts; k0 += IW_WAVES * 8) {
@@ -777,7 +771,7 @@ __global__ __launch_bounds__(64 * IW_WAVES) void pw_input_wgrad_kernel(PwInputWg
             for (int u = 0; u < IW_U; ++u) {
                 const int i = i0 + IW_WAVES * u;
                 if (i < n) {
-                    const sg_f32x4 x0 = *reinterpret_cast<const sg_f32x4 *>(sx + i * 12), x1 = *reinterpret_cast<const sg_f32x4 *>(sx + i * 12 + 4);
+                    const f32x4 x0 = *reinterpret_cast<const f32x4 *>(sx + i * 12), x1 = *reinterpret_cast<const f32x4 *>(sx + i * 12 + 4);
                     const float xr[9] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3], sx[i * 12 + 8]};
                     float z = 0.f;
                     if (three) {

@@ -21,6 +21,18 @@ inline int check_launch(const char *what)
     return AMPNET_OK;
 }
 
+// Raises the dynamic-LDS limit of kernel KERN above the 64 KB default, once per kernel instantiation; `who` opens the error text.
+template <auto KERN>
+int allow_dynamic_lds(size_t lds, const char *who)
+{
+    static bool done = false;
+    if (done) return AMPNET_OK;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "%s: hipFuncSetAttribute(%zu B LDS): %s", who, lds, hipGetErrorString(e));
+    done = true;
+    return AMPNET_OK;
+}
+
 #define AMPNET_REQUIRE(cond, ...)                                   \
     do {                                                            \
         if (!(cond)) return ::ampnet::fail(AMPNET_E_ARG, __VA_ARGS__); \

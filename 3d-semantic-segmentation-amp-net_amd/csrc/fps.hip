@@ -12,10 +12,10 @@
 // is compiled with -ffp-contract=off and the pragma below repeats it; ties go to the lowest index.
 #include <cstdlib>
 #include "common.h"
+#include "mfma_types.h"
 
 #pragma clang fp contract(off)
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace ampnet {
 

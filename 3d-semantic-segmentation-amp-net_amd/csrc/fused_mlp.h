@@ -18,10 +18,10 @@
 //     until their tiles fit the 160 KB LDS.
 #pragma once
 #include "common.h"
+#include "mfma_types.h"
 
 namespace ampnet {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MLP_MAX_LAYERS = AMPNET_SA_MAX_LAYERS;
 constexpr int MLP_MAX_COUT = AMPNET_SA_MAX_COUT;

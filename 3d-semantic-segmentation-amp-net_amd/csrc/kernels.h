@@ -2,6 +2,7 @@
 // and the kernels.  Not part of the public ABI.
 #pragma once
 #include "common.h"
+#include "mfma_types.h"
 
 namespace ampnet {
 

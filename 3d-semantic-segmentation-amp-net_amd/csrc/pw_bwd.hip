@@ -17,16 +17,7 @@
 
 namespace ampnet {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BW_NW = 4;
-
-__device__ __forceinline__ int pidx_of_b(int q, int n_slots, int Q, int slot_major)
-{
-    return slot_major ? (q % n_slots) * (Q / n_slots) + q / n_slots : q;
-}
 
 // ----------------------------------------------------------------------------------------------------
 // pw_dgrad
@@ -49,7 +40,7 @@ __global__ __launch_bounds__(NW * 64, 2) void pw_dgrad_kernel(PwDgrad a)
     const int row_end = min(a.win_off[q + 1], row_begin + a.chunk_rows);
     const int nrows = max(row_end - row_begin, 0);
     const int slot = (a.n_slots > 1) ? (q % a.n_slots) : 0;
-    const int pidx = pidx_of_b(q, a.n_slots, a.Q, a.perwin_slot_major);
+    const int pidx = pidx_of(q, a.n_slots, a.Q, a.perwin_slot_major);
     const bool act = a.g.act != 0;                       // operand = relu(z * P2 + P3)
     const bool sparse = a.g.dy == nullptr && !act;
     const bool has_bn = a.g.P1 != nullptr || act;        // z is loaded
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(NW * 64, 2) void pw_dgrad_kernel(PwDgrad a)
             sP[K + e] = has_bn ? a.g.P2[(size_t)slot * K + e] : 0.0f;
             sP[2 * K + e] = has_bn ? a.g.P3[(size_t)slot * K + e] : 0.0f;
             if (sparse) {
-                const int prow = pidx_of_b(q, a.n_slots, a.Q, a.g.dpool_slot_major);
+                const int prow = pidx_of(q, a.n_slots, a.Q, a.g.dpool_slot_major);
                 sDp[e] = a.g.dpool[(size_t)prow * K + e];
                 sArg[e] = a.g.arg[(size_t)q * K + e];
             }
@@ -276,14 +267,9 @@ static int launch_dgrad_x(const PwDgrad &a, hipStream_t st)
     constexpr size_t lds_main = (size_t)(CB * (K + 4) + 5 * K) * sizeof(float);
     constexpr size_t lds_red = (size_t)NW * CB * 2 * sizeof(float);
     constexpr size_t lds = lds_main > lds_red ? lds_main : lds_red;
-    static bool attr_set = false;
-    auto kern = pw_dgrad_kernel<K, NT, NW, EXTRA>;
-    if (!attr_set) {
-        if (lds > 65536) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "pw_dgrad: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        }
-        attr_set = true;
+    constexpr auto kern = pw_dgrad_kernel<K, NT, NW, EXTRA>;
+    if (lds > 65536) {
+        if (int rc = allow_dynamic_lds<kern>(lds, "pw_dgrad")) return rc;
     }
     char name[64];
     snprintf(name, sizeof(name), "pw_dgrad<%d,%d>%s", K, CB, a.g.act ? "+act" : (a.g.dy ? "" : "+sparse"));
@@ -368,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(PwWgrad a)
             p3 = *reinterpret_cast<const f32x4 *>(a.x.P3 + (size_t)slot * CX + xc);
         }
         if (sparse) {
-            const int prow = pidx_of_b(q, a.n_slots, a.Q, a.x.dpool_slot_major);
+            const int prow = pidx_of(q, a.n_slots, a.Q, a.x.dpool_slot_major);
             dp = *reinterpret_cast<const f32x4 *>(a.x.dpool + (size_t)prow * CX + xc);
             ar = *reinterpret_cast<const i32x4 *>(a.x.arg + (size_t)q * CX + xc);
         }

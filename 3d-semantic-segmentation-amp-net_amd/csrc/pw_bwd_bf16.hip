@@ -15,44 +15,13 @@
 // read on four disjoint groups of 16 banks.
 // Selected by ampnet_set_matrix_precision(AMPNET_PRECISION_BF16_TRAIN); BASELINE.json config 3 ("bf16 MFMA MLP").
 #include <type_traits>
-#include "kernels.h"
+#include "pw_bwd_common.h"
 
 namespace ampnet {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int FBB_THREADS = 512;
-constexpr int FBB_ITEM_ROWS = 256;      // must equal pw_bwd_item_rows() (the host sizes per-window shares with it)
-
-__device__ __forceinline__ bf16x4 to_bf16x4(const f32x4 &v)
-{
-    bf16x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = (__bf16)v[i];       // v_cvt_pk_bf16_f32, round to nearest even
-    return o;
-}
-
-// MFMA operand whose k runs over the ROWS of a row-major bf16 tile: rows row0 .. row0 + 15, channel col0 + (lane & 31).
-// EXEC must be all ones (the read gathers across lanes): only called from wave-uniform code.
-__device__ __forceinline__ bf16x8 tr_operand(const __bf16 *tile, int ld, int row0, int col0, int lane)
-{
-    const int g4 = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const __bf16 *src = tile + (row0 + 8 * (g4 >> 1) + q) * ld + col0 + 16 * (g4 & 1) + 4 * p;
-    typedef s16x4 __attribute__((address_space(3))) * lds_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(src));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(src + 4 * ld));
-    // whole-vector bit casts + one shuffle: an element-by-element short -> __bf16 copy is miscompiled by this hipcc (ROCm 7.2: it keeps
-    // only the first dword of each read; tools/tr_probe.hip checks the operand map on the hardware)
-    return __builtin_shufflevector(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi), 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 // ZG / ZP: g.z / prev.z are bf16 tensors (activation storage of precision mode 3) -- compile-time, like every other mode of this kernel
 template <int CX, int CY, int ROWS, bool GRAM, bool YACT, bool ADD, bool DROP, bool ZG, bool ZP>
-__global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
+__global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
 {
     constexpr int LDG = CX + 32, LDY = CY + 32;     // bf16 elements per row of the operand tiles (2 C + 64 bytes)
     constexpr int LDZ = CY + 4;                     // fp32 row of the raw z_prev tile
@@ -60,7 +29,7 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
     constexpr int TXN = CX / 32, TYN = CY / 32;
     constexpr int WXN = (TXN == 4 && TYN == 2) ? 4 : 2, WYN = 4 / WXN;
     constexpr int TXW = TXN / WXN, TYW = TYN / WYN;
-    constexpr int STAGE = FBB_THREADS;              // all eight waves stage (two register sets of loads in flight per thread, see the loop): the
+    constexpr int STAGE = PW_BWD_THREADS;              // all eight waves stage (two register sets of loads in flight per thread, see the loop): the
                                                     // D waves' waits are on loads two blocks old, older than any store they still have pending
     constexpr int QX = CX / 4, QY = CY / 4, SX = STAGE / QX, SY = STAGE / QY;
     constexpr int NIX = ROWS / SX, NIY = ROWS / SY;
@@ -79,25 +48,18 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
     const int slot = blockIdx.x % a.n_slots, jb = blockIdx.x / a.n_slots;
     constexpr bool x_act = GRAM, has_bn = !GRAM, y_act = YACT;
 
-    // ---- work split: items = (window of this slot, chunk of FBB_ITEM_ROWS rows), contiguous share per workgroup ----
-    const int per_slot = (a.Q - slot + a.n_slots - 1) / a.n_slots;
-    const int cpw = (a.max_rows + FBB_ITEM_ROWS - 1) / FBB_ITEM_ROWS;
-    const int n_items = per_slot * cpw;
-    const int ipb = a.items_per_block > 0 ? a.items_per_block : (n_items + a.blocks_per_slot - 1) / a.blocks_per_slot;
-    const int item_begin = min(jb * ipb, n_items), item_end = min(item_begin + ipb, n_items);
+    const PwBwdSplit sp = pw_bwd_split(a, slot, jb);
 
     // ---- the transposed weight in bf16 ----
     if (a.w_win_stride != 0) {
-        const int bi = item_begin / cpw;
-        const int pidx = a.perwin_slot_major ? slot * (a.Q / a.n_slots) + bi : bi * a.n_slots + slot;
-        const float *Tq = a.W + (size_t)pidx * a.w_win_stride;               // [cy][cx]: already transposed
-        for (int e = tid; e < CY * (CX / 4); e += FBB_THREADS) {
+        const float *Tq = pw_bwd_window_weight(a, sp, slot);                 // [cy][cx]: already transposed
+        for (int e = tid; e < CY * (CX / 4); e += PW_BWD_THREADS) {
             const int j = e / (CX / 4), k4 = e % (CX / 4);
             *reinterpret_cast<bf16x4 *>(sWt + j * LDW + 4 * k4) = to_bf16x4(*reinterpret_cast<const f32x4 *>(Tq + (size_t)j * CX + 4 * k4));
         }
     } else {
         const float *Wsh = a.W + (size_t)slot * a.w_slot_stride;
-        for (int e = tid; e < CX * (CY / 4); e += FBB_THREADS) {
+        for (int e = tid; e < CX * (CY / 4); e += PW_BWD_THREADS) {
             const int k = e % CX, j4 = e / CX;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(Wsh + (size_t)k * a.ldw + 4 * j4);
 #pragma unroll
@@ -118,31 +80,6 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
     const uint32_t dthr = drop_threshold(a.prev.drop_p);
     const float dscale = DROP ? 1.0f / (1.0f - a.prev.drop_p) : 1.0f;
 
-    struct Pos {
-        int item, row0, row_end;
-    };
-    auto open_item = [&](int item, Pos &p) -> bool {
-        for (; item < item_end; ++item) {
-            const int q = (item / cpw) * a.n_slots + slot, ch = item % cpw;
-            const int rb = a.win_off[q] + ch * FBB_ITEM_ROWS;
-            const int re = min(a.win_off[q + 1], rb + FBB_ITEM_ROWS);
-            if (rb < re) {
-                p.item = item;
-                p.row0 = rb;
-                p.row_end = re;
-                return true;
-            }
-        }
-        return false;
-    };
-    auto advance = [&](Pos &p) -> bool {
-        if (p.row0 + ROWS < p.row_end) {
-            p.row0 += ROWS;
-            return true;
-        }
-        return open_item(p.item + 1, p);
-    };
-
     // the z tensors may be stored as bf16 (precision mode 3): 8-byte loads, kept as they arrive and widened when the tile is written to LDS.
     // Two register sets: the loads of block n + 2 are issued while block n + 1 is still in flight (see the loop) -- with one set a CU has
     // 16 .. 24 KB on the wire, which at the ~1 us of a loaded HBM round trip caps the kernel near 5 TB/s whatever the format (Little's law:
@@ -155,7 +92,7 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
         ZPT yz[NIY];
     };
     auto widen = [](const auto &v) -> f32x4 { return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; };
-    auto load_regs = [&](const Pos &p, Regs &R) {
+    auto load_regs = [&](const PwBwdPos &p, Regs &R) {
 #pragma unroll
         for (int i = 0; i < NIX; ++i) {
             const int row = p.row0 + rsx + SX * i;
@@ -173,7 +110,7 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
         }
     };
     f32x4 dbacc = {0.f, 0.f, 0.f, 0.f};
-    auto write_lds = [&](int buf, const Pos &p, const Regs &R) {
+    auto write_lds = [&](int buf, const PwBwdPos &p, const Regs &R) {
         __bf16 *g = sG + buf * ROWS * LDG;
         __bf16 *y = sY + buf * ROWS * LDY;
         float *z = sZ + buf * ROWS * LDZ;
@@ -241,14 +178,14 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
     // Positions of blocks n (in LDS), n + 1 and n + 2 (in registers, in flight).  A tail position that does not exist repeats the last
     // real one: the loads are issued unconditionally (a conditional load would make every wait in the loop a vmcnt(0), which is the
     // one-deep pipeline again) and their data is simply not written.
-    Pos cur, nxt, nx2;
-    bool live = open_item(item_begin, cur);
+    PwBwdPos cur, nxt, nx2;
+    bool live = open_item(a, sp, slot, sp.item_begin, cur);
     bool more1 = false, more2 = false;
     nxt = cur;
-    if (live) more1 = advance(nxt);
+    if (live) more1 = advance<ROWS>(a, sp, slot, nxt);
     if (!more1) nxt = cur;
     nx2 = nxt;
-    if (more1) more2 = advance(nx2);
+    if (more1) more2 = advance<ROWS>(a, sp, slot, nx2);
     if (!more2) nx2 = nxt;
     Regs S0, S1;
     __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): every constant has landed before the loop (see pw_bwd_fused.hip)
@@ -338,8 +275,8 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
             if (valid >= 32) finish(std::true_type{});
             else finish(std::false_type{});
         }
-        Pos nx3 = nx2;
-        const bool more3 = more2 && advance(nx3);
+        PwBwdPos nx3 = nx2;
+        const bool more3 = more2 && advance<ROWS>(a, sp, slot, nx3);
         if (!more3) nx3 = nx2;
         if (more1) write_lds(buf ^ 1, nxt, A);
         load_regs(nx3, A);
@@ -415,25 +352,20 @@ __global__ __launch_bounds__(FBB_THREADS, 1) void pw_bwd_bf16_kernel(PwBwd a)
 template <int CX, int CY, int ROWS, bool GRAM, bool YACT, bool ADD, bool DROP, bool ZG, bool ZP>
 static int launch_bf16_z(const PwBwd &a, hipStream_t st)
 {
-    constexpr int SX = FBB_THREADS / (CX / 4);
+    constexpr int SX = PW_BWD_THREADS / (CX / 4);
     constexpr size_t red_floats = (size_t)(CX * SX > 8 * CY ? CX * SX : 8 * CY);
     constexpr size_t lds = (size_t)2 * ROWS * (CX + 32) * 2 + (GRAM ? 0 : (size_t)2 * ROWS * (CY + 32) * 2) + (YACT ? (size_t)2 * ROWS * (CY + 4) * 4 : 0) +
                            (size_t)CY * (CX + 8) * 2 + red_floats * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool attr_set = false;
-    auto kern = pw_bwd_bf16_kernel<CX, CY, ROWS, GRAM, YACT, ADD, DROP, ZG, ZP>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "pw_bwd_bf16: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = pw_bwd_bf16_kernel<CX, CY, ROWS, GRAM, YACT, ADD, DROP, ZG, ZP>;
+    if (int rc = allow_dynamic_lds<kern>(lds, "pw_bwd_bf16")) return rc;
     char name[64];
     snprintf(name, sizeof(name), "pw_bwd<%d,%d>%s bf16", CX, CY, a.g.act ? "+gram" : "");
     const double rows = (double)a.rows_hint;
     const bool same = a.g.act && a.g.z == a.prev.z;
     const double zgb = a.g.z_bf16 ? 2.0 : 4.0, zpb = a.prev.z_bf16 ? 2.0 : 4.0;
     ProfScope prof(name, 4.0 * rows * CX * CY, rows * ((a.g.dy ? 4.0 * CX : 0.0) + ((a.g.P1 || a.g.act) ? zgb * CX : 0.0) + (same ? 0.0 : zpb * CY) + 4.0 * CY + (a.add ? 4.0 * CY : 0.0)), st);
-    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(FBB_THREADS), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(PW_BWD_THREADS), lds, st, a);
     return check_launch("pw_bwd_bf16_kernel");
 }
 
@@ -476,7 +408,6 @@ static int launch_bf16(const PwBwd &a, hipStream_t st)
 // same argument contract as pw_bwd_fused (it validates before dispatching here)
 int pw_bwd_fused_bf16(const PwBwd &a, hipStream_t st)
 {
-    static_assert(FBB_ITEM_ROWS == 256, "item size shared with pw_bwd_fused.hip");
     if (a.g.C == 128 && a.prev.C == 128) return launch_bf16<128, 128, 32>(a, st);
     if (a.g.C == 128 && a.prev.C == 64) return launch_bf16<128, 64, 64>(a, st);
     if (a.g.C == 64 && a.prev.C == 64) return launch_bf16<64, 64, 64>(a, st);

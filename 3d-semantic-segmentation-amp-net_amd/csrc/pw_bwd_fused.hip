@@ -14,21 +14,15 @@
 // weights / constants are staged once.  Fixed assignment, no atomics: bitwise reproducible.
 #include <cstdlib>
 #include <type_traits>
-#include "kernels.h"
+#include "pw_bwd_common.h"
 
 namespace ampnet {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int FB_THREADS = 512;
-constexpr int FB_ITEM_ROWS = 256;      // granularity of the work split inside a slot
 
 // GRAM: X operand = relu(z * P2 + P3) of the SAME tensor as z_{l-1} (pooled layers); otherwise dense dy with BatchNorm
 // constants.  YACT: the layer's input is relu(bn(z_{l-1})) (mask + sums), else z_{l-1} itself.  ADD: extra addend.
 // The modes are compile-time so that the prefetch loads sit in one basic block (no conservative vmcnt(0) between them).
 template <int CX, int CY, int ROWS, bool GRAM, bool YACT, bool ADD, bool DROP = false>
-__global__ __launch_bounds__(FB_THREADS, 1) void pw_bwd_kernel(PwBwd a)
+__global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_kernel(PwBwd a)
 {
     constexpr int LDG = CX + 4, LDZ = CY + 4;
     constexpr int TXN = CX / 32, TYN = CY / 32;
@@ -60,9 +54,11 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pw_bwd_kernel(PwBwd a)
     // and keep mask in one, a = a' (1 - p) where it holds.
     constexpr bool SACT = YACT;
 
-    // ---- work split: items = (window of this slot, chunk of FB_ITEM_ROWS rows), contiguous share per workgroup ----
+    // ---- work split: items = (window of this slot, chunk of PW_BWD_ITEM_ROWS rows), contiguous share per workgroup ----
+    // (the same split and walk as pw_bwd_split / open_item / advance of pw_bwd_common.h, which the other fused-backward kernels call; kept as
+    // text here because this kernel's register allocation does not survive the call -- see that header)
     const int per_slot = (a.Q - slot + a.n_slots - 1) / a.n_slots;
-    const int cpw = (a.max_rows + FB_ITEM_ROWS - 1) / FB_ITEM_ROWS;
+    const int cpw = (a.max_rows + PW_BWD_ITEM_ROWS - 1) / PW_BWD_ITEM_ROWS;
     const int n_items = per_slot * cpw;
     const int ipb = a.items_per_block > 0 ? a.items_per_block : (n_items + a.blocks_per_slot - 1) / a.blocks_per_slot;
     const int item_begin = min(jb * ipb, n_items), item_end = min(item_begin + ipb, n_items);
@@ -74,13 +70,13 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pw_bwd_kernel(PwBwd a)
         const int bi = item_begin / cpw;
         const int pidx = a.perwin_slot_major ? slot * (a.Q / a.n_slots) + bi : bi * a.n_slots + slot;
         const float *Tq = a.W + (size_t)pidx * a.w_win_stride;
-        for (int e = tid; e < CY * (CX / 4); e += FB_THREADS) {
+        for (int e = tid; e < CY * (CX / 4); e += PW_BWD_THREADS) {
             const int j = e / (CX / 4), k4 = e % (CX / 4);
             *reinterpret_cast<f32x4 *>(sWt + j * LDG + 4 * k4) = *reinterpret_cast<const f32x4 *>(Tq + (size_t)j * CX + 4 * k4);
         }
     } else {
         const float *Wsh = a.W + (size_t)slot * a.w_slot_stride;
-        for (int e = tid; e < CX * (CY / 4); e += FB_THREADS) {
+        for (int e = tid; e < CX * (CY / 4); e += PW_BWD_THREADS) {
             const int k = e % CX, j4 = e / CX;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(Wsh + (size_t)k * a.ldw + 4 * j4);
 #pragma unroll
@@ -178,8 +174,8 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pw_bwd_kernel(PwBwd a)
     auto open_item = [&](int item, Pos &p) -> bool {       // first block of the next non-empty item at or after `item`
         for (; item < item_end; ++item) {
             const int q = (item / cpw) * a.n_slots + slot, ch = item % cpw;
-            const int rb = a.win_off[q] + ch * FB_ITEM_ROWS;
-            const int re = min(a.win_off[q + 1], rb + FB_ITEM_ROWS);
+            const int rb = a.win_off[q] + ch * PW_BWD_ITEM_ROWS;
+            const int re = min(a.win_off[q + 1], rb + PW_BWD_ITEM_ROWS);
             if (rb < re) {
                 p.item = item;
                 p.row0 = rb;
@@ -563,11 +559,11 @@ int pw_bwd_blocks(int Q, int n_slots, int max_rows)
     int bps = cus / n_slots;
     if (bps < 1) bps = 1;
     const int per_slot = (Q + n_slots - 1) / n_slots;
-    const int items = per_slot * ((max_rows + FB_ITEM_ROWS - 1) / FB_ITEM_ROWS);
+    const int items = per_slot * ((max_rows + PW_BWD_ITEM_ROWS - 1) / PW_BWD_ITEM_ROWS);
     return bps < items ? bps : (items > 0 ? items : 1);
 }
 
-int pw_bwd_item_rows() { return FB_ITEM_ROWS; }
+int pw_bwd_item_rows() { return PW_BWD_ITEM_ROWS; }
 
 bool pw_bwd_supported(int cx, int cy) { return (cx == 128 && (cy == 128 || cy == 64)) || (cx == 64 && (cy == 64 || cy == 128)); }
 
@@ -575,13 +571,8 @@ template <int CX, int CY, int ROWS, bool GRAM, bool YACT, bool ADD, bool DROP = 
 static int launch_fused_x(const PwBwd &a, hipStream_t st)
 {
     constexpr size_t lds = (size_t)(2 * ROWS * (CX + 4) + 2 * ROWS * (CY + 4) + CY * (CX + 4)) * sizeof(float);
-    static bool attr_set = false;
-    auto kern = pw_bwd_kernel<CX, CY, ROWS, GRAM, YACT, ADD, DROP>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "pw_bwd_fused: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = pw_bwd_kernel<CX, CY, ROWS, GRAM, YACT, ADD, DROP>;
+    if (int rc = allow_dynamic_lds<kern>(lds, "pw_bwd_fused")) return rc;
     char name[64];
     // one event name per kernel symbol (the rocprofv3 stats and bench.py's table then name the same thing): +gram, input without activation
     // (lin), with an addend (+add), with dropout (+drop)
@@ -591,7 +582,7 @@ static int launch_fused_x(const PwBwd &a, hipStream_t st)
     // flops the launch executes: the symmetric Gram form multiplies 10 of the 16 tiles
     const double wflops = (GRAM && CX == 128 && CY == 128) ? 2.0 * rows * CX * CY * 10.0 / 16.0 : 2.0 * rows * CX * CY;
     ProfScope prof(name, wflops + 2.0 * rows * CX * CY, rows * 4.0 * ((a.g.dy ? CX : 0) + ((a.g.P1 || a.g.act) ? CX : 0) + (same ? 0 : CY) + CY + (a.add ? CY : 0)), st);
-    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(FB_THREADS), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(PW_BWD_THREADS), lds, st, a);
     return check_launch("pw_bwd_kernel");
 }
 
@@ -629,7 +620,7 @@ int pw_bwd_fused(const PwBwd &a_in, hipStream_t st)
     AMPNET_REQUIRE(a.g.act ? a.g.z == a.prev.z : (a.g.dy && a.g.P1), "pw_bwd_fused: dense gradient with BatchNorm constants, or the Gram form of one tensor");
     AMPNET_REQUIRE(a.g.P2 && a.g.P3 && a.g.z, "pw_bwd_fused: BatchNorm constants incomplete");
     AMPNET_REQUIRE(!a.part_a || (a.part_b && a.prev.s), "pw_bwd_fused: partial sums need the previous layer's BatchNorm");
-    AMPNET_REQUIRE(a.w_win_stride == 0 || (a.items_per_block > 0 && ((a.max_rows + FB_ITEM_ROWS - 1) / FB_ITEM_ROWS) % a.items_per_block == 0 && a.Q % a.n_slots == 0),
+    AMPNET_REQUIRE(a.w_win_stride == 0 || (a.items_per_block > 0 && ((a.max_rows + PW_BWD_ITEM_ROWS - 1) / PW_BWD_ITEM_ROWS) % a.items_per_block == 0 && a.Q % a.n_slots == 0),
                    "pw_bwd_fused: per-window weights need workgroups that stay inside one window");
     AMPNET_REQUIRE(a.ldw % 4 == 0 && a.Q >= 1 && a.n_slots >= 1 && a.max_rows >= 1 && a.blocks_per_slot >= 1, "pw_bwd_fused: bad shape");
     AMPNET_REQUIRE(a.prev.C == 0 || pw_bwd_supported(a.g.C, a.prev.C), "pw_bwd_fused: %d x %d not built", a.g.C, a.prev.C);

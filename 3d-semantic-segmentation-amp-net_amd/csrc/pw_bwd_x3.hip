@@ -14,18 +14,9 @@
 //           which three images of two staged tiles already fill.
 // Built for: Gram form 128 x 128 (the three pooled layers' backward) and the dense 128 x 128 layer (conv_5), activated input, no addend.
 #include <type_traits>
-#include "kernels.h"
+#include "pw_bwd_common.h"
 
 namespace ampnet {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // Development probe (tools/build_stamps.sh, tools/x3_stamps.py bwd): wave 0 (W role) and wave 4 (D role) of workgroup 0 record (label, cycle)
 #ifdef AMPNET_PW_STAMPS
@@ -39,56 +30,9 @@ __device__ unsigned long long g_bx_stamps[2][2048];
 #define BX_STAMP(id) do { } while (0)
 #endif
 
-constexpr int X3B_THREADS = 512;
-constexpr int X3B_ITEM_ROWS = 256;      // must equal pw_bwd_item_rows() (the host sizes per-window shares with it)
-
 namespace {
 
-// the three-term split on pairs (pw_gemm.hip has the same helpers; see there for why the conversion is an instruction)
-__device__ __forceinline__ uint32_t cvt_pk(const f32x2 &v)
-{
-    uint32_t p;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(v[0]), "v"(v[1]));
-    return p;
-}
-__device__ __forceinline__ f32x2 widen_pk(uint32_t p) { return f32x2{__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)}; }
-__device__ __forceinline__ void split_pair(const f32x2 &x, uint32_t &p1, uint32_t &p2, uint32_t &p3)
-{
-    p1 = cvt_pk(x);
-    const f32x2 r = x - widen_pk(p1);
-    p2 = cvt_pk(r);
-    p3 = cvt_pk(r - widen_pk(p2));
-}
-__device__ __forceinline__ void split4(const f32x4 &v, bf16x4 &p1, bf16x4 &p2, bf16x4 &p3)
-{
-    uint32_t q1[2], q2[2], q3[2];
-    split_pair(f32x2{v[0], v[1]}, q1[0], q2[0], q3[0]);
-    split_pair(f32x2{v[2], v[3]}, q1[1], q2[1], q3[1]);
-    p1 = __builtin_bit_cast(bf16x4, u32x2{q1[0], q1[1]});
-    p2 = __builtin_bit_cast(bf16x4, u32x2{q2[0], q2[1]});
-    p3 = __builtin_bit_cast(bf16x4, u32x2{q3[0], q3[1]});
-}
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 &p1, bf16x8 &p2, bf16x8 &p3)
-{
-    uint32_t q1[4], q2[4], q3[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split_pair(f32x2{v[2 * i], v[2 * i + 1]}, q1[i], q2[i], q3[i]);
-    p1 = __builtin_bit_cast(bf16x8, u32x4{q1[0], q1[1], q1[2], q1[3]});
-    p2 = __builtin_bit_cast(bf16x8, u32x4{q2[0], q2[1], q2[2], q2[3]});
-    p3 = __builtin_bit_cast(bf16x8, u32x4{q3[0], q3[1], q3[2], q3[3]});
-}
-
-// MFMA operand whose k runs over the ROWS of a row-major bf16 tile: rows row0 .. row0 + 15, channel col0 + (lane & 31) (pw_bwd_bf16.hip)
-__device__ __forceinline__ bf16x8 tr_operand(const __bf16 *tile, int ld, int row0, int col0, int lane)
-{
-    const int g4 = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const __bf16 *src = tile + (row0 + 8 * (g4 >> 1) + q) * ld + col0 + 16 * (g4 & 1) + 4 * p;
-    typedef s16x4 __attribute__((address_space(3))) * lds_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(src));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(src + 4 * ld));
-    return __builtin_shufflevector(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi), 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
+// (the three-term split split3_bf16 and the plain transposed operand tr_operand: mfma_types.h)
 // ---- the g images are swizzled: the 16-byte granule gi of row `lrow` sits at gi ^ ((lrow >> 2) & 3) ----
 // The row pitch (2 C + 64 bytes) makes the weight-gradient role's transposed reads conflict-free (four rows x 64 bytes per 32 lanes), but rows
 // r, r + 4, r + 8, r + 12 then start in the same bank group, and the data-gradient role's row-major ds_read_b128 (lane = row) replayed four times:
@@ -128,7 +72,7 @@ __device__ __forceinline__ void mfma6(f32x16 &acc, const bf16x8 (&x)[3], const b
 }  // namespace
 
 template <bool GRAM>
-__global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
+__global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
 {
     constexpr int CX = 128, CY = 128, ROWS = 32;
     constexpr int LDG = CX + 32, LDY = CY + 32;     // bf16 elements per row of the operand tiles (2 C + 64 bytes: transposed reads conflict-free)
@@ -138,7 +82,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
     // Gram form: the four W waves stage (their role is the lighter one: no epilogue, no stores), the D waves only multiply, mask and store --
     // with all eight staging, the D wave's products + epilogue (4600 cycles per block) and then its staging (2000) were the block's critical
     // path while the W wave waited at the barrier (in-kernel stamps, tools/x3_stamps.py).  Dense form: everybody stages (three tensors).
-    constexpr int STAGE = GRAM ? X3B_THREADS / 2 : X3B_THREADS;
+    constexpr int STAGE = GRAM ? PW_BWD_THREADS / 2 : PW_BWD_THREADS;
     constexpr int QX = CX / 4, SX = STAGE / QX;     // 32 channel quads, 8 (Gram) or 16 row groups
     constexpr int NIX = ROWS / SX;                  // 4 (Gram) or 2 quads per staging thread and tensor
     constexpr int IMG = ROWS * LDG;                 // elements of one image of one buffer
@@ -153,12 +97,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
     const TrLane trl = tr_lane(LDG, lane);
     const int slot = blockIdx.x % a.n_slots, jb = blockIdx.x / a.n_slots;
 
-    // ---- work split: items = (window of this slot, chunk of X3B_ITEM_ROWS rows), contiguous share per workgroup ----
-    const int per_slot = (a.Q - slot + a.n_slots - 1) / a.n_slots;
-    const int cpw = (a.max_rows + X3B_ITEM_ROWS - 1) / X3B_ITEM_ROWS;
-    const int n_items = per_slot * cpw;
-    const int ipb = a.items_per_block > 0 ? a.items_per_block : (n_items + a.blocks_per_slot - 1) / a.blocks_per_slot;
-    const int item_begin = min(jb * ipb, n_items), item_end = min(item_begin + ipb, n_items);
+    const PwBwdSplit sp = pw_bwd_split(a, slot, jb);
 
     const int cqx = tid % QX, rsx = (tid % STAGE) / QX;
     const bool stager = tid < STAGE;                 // (Gram form: waves 0 .. 3 = the W role)
@@ -232,38 +171,13 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
         yt = *reinterpret_cast<const f32x4 *>(a.prev.t + (size_t)slot * CY + 4 * cqx);
     }
 
-    struct Pos {
-        int item, row0, row_end;
-    };
-    auto open_item = [&](int item, Pos &p) -> bool {
-        for (; item < item_end; ++item) {
-            const int q = (item / cpw) * a.n_slots + slot, ch = item % cpw;
-            const int rb = a.win_off[q] + ch * X3B_ITEM_ROWS;
-            const int re = min(a.win_off[q + 1], rb + X3B_ITEM_ROWS);
-            if (rb < re) {
-                p.item = item;
-                p.row0 = rb;
-                p.row_end = re;
-                return true;
-            }
-        }
-        return false;
-    };
-    auto advance = [&](Pos &p) -> bool {
-        if (p.row0 + ROWS < p.row_end) {
-            p.row0 += ROWS;
-            return true;
-        }
-        return open_item(p.item + 1, p);
-    };
-
     // two register sets of loads in flight (blocks n + 1 and n + 2), issued unconditionally (pw_bwd_bf16.hip explains both)
     struct Regs {
         f32x4 dy[GRAM ? 1 : NIX];
         f32x4 xz[NIX];
         f32x4 yz[GRAM ? 1 : NIX];
     };
-    auto load_regs = [&](const Pos &p, Regs &R) {
+    auto load_regs = [&](const PwBwdPos &p, Regs &R) {
 #pragma unroll
         for (int i = 0; i < NIX; ++i) {
             const int row = p.row0 + rsx + SX * i;
@@ -275,7 +189,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
     };
     f32x4 dbacc = {0.f, 0.f, 0.f, 0.f};
     const bool want_db = a.dbpart != nullptr;
-    auto write_lds = [&](int buf_, const Pos &p, const Regs &R) {
+    auto write_lds = [&](int buf_, const PwBwdPos &p, const Regs &R) {
         int bsel = buf_;
         asm volatile("" : "+s"(bsel));               // (see step(): keeps the addresses of the two buffers from being hoisted apart)
         __bf16 *g = sG + bsel * 3 * IMG;
@@ -297,7 +211,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
                 if (want_db) dbacc += xv;
             }
             bf16x4 t1, t2, t3;
-            split4(xv, t1, t2, t3);
+            split3_bf16(xv, t1, t2, t3);
             const int gofs = lrow * LDG + swz_col(lrow, 4 * cqx);
             *reinterpret_cast<bf16x4 *>(g + gofs) = t1;
             *reinterpret_cast<bf16x4 *>(g + IMG + gofs) = t2;
@@ -310,7 +224,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
                 for (int c = 0; c < 4; ++c) yv[c] = fmaxf(fmaf(R.yz[i][c], ys[c], yt[c]), 0.f);
                 *reinterpret_cast<f32x4 *>(z + lrow * LDZ + 4 * cqx) = yv;           // (finite filler on rows past the end: masked in the epilogue)
                 if (!live_row) yv = f32x4{0.f, 0.f, 0.f, 0.f};                       // rows past the block's end contribute nothing to dW
-                split4(yv, t1, t2, t3);
+                split3_bf16(yv, t1, t2, t3);
                 *reinterpret_cast<bf16x4 *>(y + lrow * LDY + 4 * cqx) = t1;
                 *reinterpret_cast<bf16x4 *>(y + IMG + lrow * LDY + 4 * cqx) = t2;
                 *reinterpret_cast<bf16x4 *>(y + 2 * IMG + lrow * LDY + 4 * cqx) = t3;
@@ -339,7 +253,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = Wsh[(size_t)(16 * s2 + 8 * h + j) * a.ldw + dcol];
-            split8(v, wf[s2][0], wf[s2][1], wf[s2][2]);
+            split3_bf16(v, wf[s2][0], wf[s2][1], wf[s2][2]);
         }
     }
     const float c_b = a.bias_slot ? a.bias_slot[(size_t)slot * CY + dcol] : 0.f;
@@ -358,14 +272,14 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
     // per SIMD here, 3072 cycles, which covers a trip to HBM, and the second set spilled into the loop.  A tail position that does not exist
     // repeats the last real one: the loads are issued unconditionally (a conditional load makes every wait a vmcnt(0)), their data is not written.
     constexpr int NSETS = GRAM ? 2 : 1;
-    Pos cur, nxt, nx2;
-    bool live = open_item(item_begin, cur);
+    PwBwdPos cur, nxt, nx2;
+    bool live = open_item(a, sp, slot, sp.item_begin, cur);
     bool more1 = false, more2 = false;
     nxt = cur;
-    if (live) more1 = advance(nxt);
+    if (live) more1 = advance<ROWS>(a, sp, slot, nxt);
     if (!more1) nxt = cur;
     nx2 = nxt;
-    if (more1) more2 = advance(nx2);
+    if (more1) more2 = advance<ROWS>(a, sp, slot, nx2);
     if (!more2) nx2 = nxt;
     Regs S0, S1;
     __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): every constant has landed before the loop (see pw_bwd_fused.hip)
@@ -386,10 +300,10 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
         // Gram form: the W wave stages block n + 1 FIRST and multiplies block n afterwards, the D wave multiplies first and runs its epilogue
         // afterwards -- so on every SIMD one wave's VALU phase (staging / epilogue) lies under the other's MFMA phase.  With both roles
         // multiplying first the matrix pipe idled for the second half of every block (stamps: products done at 3100 of 5850 cycles).
-        Pos nx3 = nx2;
+        PwBwdPos nx3 = nx2;
         bool more3 = false;
         if constexpr (NSETS == 2) {
-            more3 = more2 && advance(nx3);
+            more3 = more2 && advance<ROWS>(a, sp, slot, nx3);
             if (!more3) nx3 = nx2;
 #ifndef X3B_NO_SKEW                             // (A/B build switch, tools/ab_lib.sh: the W wave stages AFTER its products)
             if (W_ROLE && GRAM) {
@@ -529,7 +443,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
             nxt = nx2;
             live = more1;
             more1 = more2;
-            more2 = more1 && advance(nx2);
+            more2 = more1 && advance<ROWS>(a, sp, slot, nx2);
             if (!more2) nx2 = nxt;
         }
     };
@@ -631,20 +545,15 @@ static int launch_x3(const PwBwd &a, hipStream_t st)
     constexpr size_t img = (size_t)32 * 160 * 2;
     constexpr size_t lds = 2 * 3 * img * (GRAM ? 1 : 2) + (size_t)2 * 32 * 136 * 4;
     static_assert(lds <= 160 * 1024 && lds >= (size_t)16 * 128 * 2 * 8, "LDS budget (tiles; the prologue's double scratch aliases them)");
-    static bool attr_set = false;
-    auto kern = pw_bwd_x3_kernel<GRAM>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "pw_bwd_x3: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = pw_bwd_x3_kernel<GRAM>;
+    if (int rc = allow_dynamic_lds<kern>(lds, "pw_bwd_x3")) return rc;
     char name[64];
     snprintf(name, sizeof(name), "pw_bwd<128,128>%s x3", GRAM ? "+gram" : "");
     const double rows = (double)a.rows_hint;
     // algorithmic flops the launch stands for (each executed as six bf16 partial products): the symmetric Gram form multiplies 10 of its 16 tiles
     const double wflops = GRAM ? 2.0 * rows * 128 * 128 * 10.0 / 16.0 : 2.0 * rows * 128 * 128;
     ProfScope prof(name, wflops + 2.0 * rows * 128 * 128, rows * 4.0 * ((a.g.dy ? 128 : 0) + 128 + (GRAM ? 0 : 128) + 128), st);
-    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(X3B_THREADS), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(PW_BWD_THREADS), lds, st, a);
     return check_launch("pw_bwd_x3_kernel");
 }
 
@@ -658,7 +567,7 @@ static int launch_x3(const PwBwd &a, hipStream_t st)
 //     waves 4, 5       (D): out[row][32 d ..] = mask (g W), weight column block as 8 x 3 bf16 fragments in registers: 48 MFMAs per block
 // A workgroup's waves are dealt to the SIMDs 0, 1, 2, 3, 0, 1, 2, 3: every SIMD holds one MFMA wave and one staging wave.
 template <int CX, int CY, bool YACT, bool DROP, bool ADD>
-__global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
+__global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
 {
     static_assert((CX == 128 && CY == 64) || (CX == 64 && CY == 128) || (CX == 64 && CY == 64), "48 + 48 MFMAs per block (24 + 24 at 64 x 64: HBM-bound)");
     static_assert(!ADD || (CX == 64 && CY == 64), "the addend exists on the 64 x 64 launches");
@@ -671,7 +580,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
     constexpr int QX = CX / 4, QY = CY / 4;         // channel quads per row
     constexpr int SX = NS / QX, SY = NS / QY;       // row groups
     constexpr int NIX = ROWS / SX, NIY = ROWS / SY; // quads per staging thread (4 + 2 at 128 x 64, 2 + 4 at 64 x 128)
-    constexpr int FG = X3B_THREADS / QX;            // prologue: groups of channel quads over the whole workgroup
+    constexpr int FG = PW_BWD_THREADS / QX;            // prologue: groups of channel quads over the whole workgroup
     constexpr int TXW = CX / 64, TYW = CY / 32;     // W role: x blocks per wave, y blocks (all of them): 4 tiles per wave
     constexpr int DB = CY / 64, KS = CX / 16;       // D role: column blocks per wave, k steps: DB * KS * 6 = 48 MFMAs per block
     constexpr size_t BUF = (size_t)3 * IMGG * 2 + (size_t)3 * IMGY * 2 + (size_t)ROWS * LDZ * 4;      // bytes of one staged block
@@ -685,11 +594,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
     const int stid = ((wave < 2 ? wave : wave - 4) << 6) | lane;       // 0 .. 255 over the four staging waves
     const int cqx = stid % QX, rsx = stid / QX, cqy = stid % QY, rsy = stid / QY;
 
-    const int per_slot = (a.Q - slot + a.n_slots - 1) / a.n_slots;
-    const int cpw = (a.max_rows + X3B_ITEM_ROWS - 1) / X3B_ITEM_ROWS;
-    const int n_items = per_slot * cpw;
-    const int ipb = a.items_per_block > 0 ? a.items_per_block : (n_items + a.blocks_per_slot - 1) / a.blocks_per_slot;
-    const int item_begin = min(jb * ipb, n_items), item_end = min(item_begin + ipb, n_items);
+    const PwBwdSplit sp = pw_bwd_split(a, slot, jb);
 
     // ---- BatchNorm-backward constants of the layer g belongs to (formed here from the producer's partial sums, or read) ----
     f32x4 p1 = {1.f, 1.f, 1.f, 1.f}, p2 = {0.f, 0.f, 0.f, 0.f}, p3 = {0.f, 0.f, 0.f, 0.f};
@@ -765,35 +670,10 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
         yt = *reinterpret_cast<const f32x4 *>(a.prev.t + (size_t)slot * CY + 4 * cqy);
     }
 
-    struct Pos {
-        int item, row0, row_end;
-    };
-    auto open_item = [&](int item, Pos &p) -> bool {
-        for (; item < item_end; ++item) {
-            const int q = (item / cpw) * a.n_slots + slot, ch = item % cpw;
-            const int rb = a.win_off[q] + ch * X3B_ITEM_ROWS;
-            const int re = min(a.win_off[q + 1], rb + X3B_ITEM_ROWS);
-            if (rb < re) {
-                p.item = item;
-                p.row0 = rb;
-                p.row_end = re;
-                return true;
-            }
-        }
-        return false;
-    };
-    auto advance = [&](Pos &p) -> bool {
-        if (p.row0 + ROWS < p.row_end) {
-            p.row0 += ROWS;
-            return true;
-        }
-        return open_item(p.item + 1, p);
-    };
-
     struct Regs {
         f32x4 dy[NIX], xz[NIX], yz[NIY];
     };
-    auto load_regs = [&](const Pos &p, Regs &R) {
+    auto load_regs = [&](const PwBwdPos &p, Regs &R) {
 #pragma unroll
         for (int i = 0; i < NIX; ++i) {
             const int row = p.row0 + rsx + SX * i;
@@ -812,7 +692,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
     const bool want_db = a.dbpart != nullptr;
     const uint32_t dthr = drop_threshold(a.prev.drop_p);
     const float dscale = DROP ? 1.0f / (1.0f - a.prev.drop_p) : 1.0f;
-    auto write_lds = [&](int buf_, const Pos &p, const Regs &R) {
+    auto write_lds = [&](int buf_, const PwBwdPos &p, const Regs &R) {
         int bsel = buf_;
         asm volatile("" : "+s"(bsel));               // keeps the addresses of the two buffers from being hoisted apart (see pw_bwd_x3_kernel)
         __bf16 *g = reinterpret_cast<__bf16 *>(smem_raw + bsel * BUF);
@@ -828,7 +708,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
                 if (want_db) dbacc += xv;
             }
             bf16x4 t1, t2, t3;
-            split4(xv, t1, t2, t3);
+            split3_bf16(xv, t1, t2, t3);
             const int gofs = lrow * LDG + swz_col(lrow, 4 * cqx);
             *reinterpret_cast<bf16x4 *>(g + gofs) = t1;
             *reinterpret_cast<bf16x4 *>(g + IMGG + gofs) = t2;
@@ -850,7 +730,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
             }
             if (!(row < p.row_end)) yv = f32x4{0.f, 0.f, 0.f, 0.f};               // rows past the block's end contribute nothing to dW
             bf16x4 t1, t2, t3;
-            split4(yv, t1, t2, t3);
+            split3_bf16(yv, t1, t2, t3);
             *reinterpret_cast<bf16x4 *>(y + lrow * LDY + 4 * cqy) = t1;
             *reinterpret_cast<bf16x4 *>(y + IMGY + lrow * LDY + 4 * cqy) = t2;
             *reinterpret_cast<bf16x4 *>(y + 2 * IMGY + lrow * LDY + 4 * cqy) = t3;
@@ -887,14 +767,14 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
     for (int bq = 0; bq < DB; ++bq) s_a[bq] = s_b[bq] = 0.f;
 
     // blocks n (in LDS), n + 1 and n + 2 (in the stagers' two register sets); a tail position repeats the last real one (unconditional loads)
-    Pos cur, nxt, nx2;
-    bool live = open_item(item_begin, cur);
+    PwBwdPos cur, nxt, nx2;
+    bool live = open_item(a, sp, slot, sp.item_begin, cur);
     bool more1 = false, more2 = false;
     nxt = cur;
-    if (live) more1 = advance(nxt);
+    if (live) more1 = advance<ROWS>(a, sp, slot, nxt);
     if (!more1) nxt = cur;
     nx2 = nxt;
-    if (more1) more2 = advance(nx2);
+    if (more1) more2 = advance<ROWS>(a, sp, slot, nx2);
     if (!more2) nx2 = nxt;
     Regs S0, S1;
     __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): every constant has landed before the loop
@@ -913,8 +793,8 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
         const __bf16 *g = reinterpret_cast<const __bf16 *>(smem_raw + bsel * BUF);
         const __bf16 *y = g + 3 * IMGG;
         const float *z = reinterpret_cast<const float *>(y + 3 * IMGY);
-        Pos nx3 = nx2;
-        const bool more3 = more2 && advance(nx3);
+        PwBwdPos nx3 = nx2;
+        const bool more3 = more2 && advance<ROWS>(a, sp, slot, nx3);
         if (!more3) nx3 = nx2;
         if constexpr (ROLE == 0) {
             if (more1) write_lds(buf ^ 1, nxt, A);
@@ -1038,11 +918,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
         const float *Wsh = a.W + (size_t)slot * a.w_slot_stride;
         const float *Tq = nullptr;
         if (a.w_win_stride != 0) {
-            // per-window matrix T[pidx][cy][cx] (the bmm transform: out[row][cy] = sum_cx g[row][cx] T[cy][cx]); the host keeps every workgroup
-            // inside one window (pw_bwd_fused.hip)
-            const int bi = item_begin / cpw;
-            const int pidx = a.perwin_slot_major ? slot * (a.Q / a.n_slots) + bi : bi * a.n_slots + slot;
-            Tq = a.W + (size_t)pidx * a.w_win_stride;
+            Tq = pw_bwd_window_weight(a, sp, slot);      // [cy][cx]: already transposed
         }
 #pragma unroll
         for (int bq = 0; bq < DB; ++bq)
@@ -1052,7 +928,7 @@ __global__ __launch_bounds__(X3B_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     v[j] = Tq ? Tq[(size_t)dcol[bq] * CX + 16 * s2 + 8 * h + j] : Wsh[(size_t)(16 * s2 + 8 * h + j) * a.ldw + dcol[bq]];
-                split8(v, wf[bq][s2][0], wf[bq][s2][1], wf[bq][s2][2]);
+                split3_bf16(v, wf[bq][s2][0], wf[bq][s2][1], wf[bq][s2][2]);
             }
         while (live) step(S0, std::integral_constant<int, 2>{});
     }
@@ -1106,18 +982,13 @@ static int launch_x3n(const PwBwd &a, hipStream_t st)
     constexpr size_t buf = (size_t)3 * 32 * (CX + 32) * 2 + (size_t)3 * 32 * (CY + 32) * 2 + (size_t)32 * (CY + 8) * 4;
     constexpr size_t lds = 2 * buf;
     static_assert(lds <= 160 * 1024 && lds >= (size_t)16 * 128 * 2 * 8, "LDS budget (tiles; the prologue's double scratch aliases them)");
-    static bool attr_set = false;
-    auto kern = pw_bwd_x3n_kernel<CX, CY, YACT, DROP, ADD>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "pw_bwd_x3n: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = pw_bwd_x3n_kernel<CX, CY, YACT, DROP, ADD>;
+    if (int rc = allow_dynamic_lds<kern>(lds, "pw_bwd_x3n")) return rc;
     char name[64];
     snprintf(name, sizeof(name), "pw_bwd<%d,%d>%s%s%s x3", CX, CY, YACT ? "" : " lin", ADD ? "+add" : "", DROP ? "+drop" : "");
     const double rows = (double)a.rows_hint;
     ProfScope prof(name, 4.0 * rows * CX * CY, rows * 4.0 * (2 * CX + 2 * CY + (ADD ? CY : 0)), st);
-    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(X3B_THREADS), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(a.blocks_per_slot * a.n_slots), dim3(PW_BWD_THREADS), lds, st, a);
     return check_launch("pw_bwd_x3n_kernel");
 }
 
@@ -1142,7 +1013,6 @@ bool pw_bwd_x3_supported(const PwBwd &a)
 // same argument contract as pw_bwd_fused (it validates before dispatching here)
 int pw_bwd_fused_x3(const PwBwd &a, hipStream_t st)
 {
-    static_assert(X3B_ITEM_ROWS == 256, "item size shared with pw_bwd_fused.hip");
     AMPNET_REQUIRE(pw_bwd_x3_supported(a), "pw_bwd_x3: shape not built");
     if (a.g.C == 64 && a.prev.C == 64) {
         if (a.prev.s) return a.add ? launch_x3n<64, 64, true, false, true>(a, st) : launch_x3n<64, 64, true, false, false>(a, st);

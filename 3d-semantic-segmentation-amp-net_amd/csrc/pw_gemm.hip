@@ -23,70 +23,6 @@
 
 namespace ampnet {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bf16x8 pack_bf16(const f32x4 &lo, const f32x4 &hi)
-{
-    bf16x8 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        o[i] = (__bf16)lo[i];          // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-        o[4 + i] = (__bf16)hi[i];
-    }
-    return o;
-}
-
-// Three-term bf16 split (precision mode AMPNET_PRECISION_F32_SPLIT): x = p1 + p2 + p3 exactly -- p1 = bf16(x), p2 = bf16(x - p1),
-// p3 = bf16(x - p1 - p2), round to nearest even each time; the residual of an fp32 number against its 8-bit head has at most 16 significant
-// bits, the second residual at most 8, so both subtractions and the last conversion are exact.  Written on PAIRS so that it compiles to
-// v_cvt_pk_bf16_f32 + (shift, and) + v_pk_add_f32 per step: 9 VALU instructions per two elements.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t cvt_pk_bf16(const f32x2 &v)
-{
-    // as an instruction, not as two conversions: written in C the optimiser re-converts a lone element wherever only one half of the
-    // pair is needed again (the residuals below), 13 conversions per eight elements instead of 12 and scalar subtractions instead of packed
-    uint32_t p;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(v[0]), "v"(v[1]));
-    return p;
-}
-__device__ __forceinline__ f32x2 widen_pk_bf16(uint32_t p)
-{
-    return f32x2{__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)};
-}
-__device__ __forceinline__ void split3_pair(const f32x2 &x, uint32_t &p1, uint32_t &p2, uint32_t &p3)
-{
-    p1 = cvt_pk_bf16(x);
-    const f32x2 r = x - widen_pk_bf16(p1);
-    p2 = cvt_pk_bf16(r);
-    p3 = cvt_pk_bf16(r - widen_pk_bf16(p2));
-}
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3_bf16(const f32x4 &lo, const f32x4 &hi, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3)
-{
-    uint32_t q1[4], q2[4], q3[4];
-    split3_pair(f32x2{lo[0], lo[1]}, q1[0], q2[0], q3[0]);
-    split3_pair(f32x2{lo[2], lo[3]}, q1[1], q2[1], q3[1]);
-    split3_pair(f32x2{hi[0], hi[1]}, q1[2], q2[2], q3[2]);
-    split3_pair(f32x2{hi[2], hi[3]}, q1[3], q2[3], q3[3]);
-    p1 = __builtin_bit_cast(bf16x8, u32x4{q1[0], q1[1], q1[2], q1[3]});
-    p2 = __builtin_bit_cast(bf16x8, u32x4{q2[0], q2[1], q2[2], q2[3]});
-    p3 = __builtin_bit_cast(bf16x8, u32x4{q3[0], q3[1], q3[2], q3[3]});
-}
-__device__ __forceinline__ void split3_bf16(const f32x4 &v, bf16x4 &p1, bf16x4 &p2, bf16x4 &p3)
-{
-    uint32_t q1[2], q2[2], q3[2];
-    split3_pair(f32x2{v[0], v[1]}, q1[0], q2[0], q3[0]);
-    split3_pair(f32x2{v[2], v[3]}, q1[1], q2[1], q3[1]);
-    p1 = __builtin_bit_cast(bf16x4, u32x2{q1[0], q1[1]});
-    p2 = __builtin_bit_cast(bf16x4, u32x2{q2[0], q2[1]});
-    p3 = __builtin_bit_cast(bf16x4, u32x2{q3[0], q3[1]});
-}
-
 constexpr int PW_NW = 4;   // waves per workgroup
 
 // Development probe (tools/x3_stamps.py; built only with -DAMPNET_PW_STAMPS): wave 0 of workgroup 0 of a split kernel records
@@ -109,11 +45,6 @@ __device__ __forceinline__ double rcp_f64(double d)
     x = x * __builtin_fma(-d, x, 2.0);
     x = x * __builtin_fma(-d, x, 2.0);
     return x;
-}
-
-__device__ __forceinline__ int pidx_of(int q, int n_slots, int Q, int slot_major)
-{
-    return slot_major ? (q % n_slots) * (Q / n_slots) + q / n_slots : q;
 }
 
 // PRO: prologue on the A operand -- 0 none, 1 relu(a * scale + shift), 2 the same then dropout.  POOL: track the per-channel
@@ -1066,11 +997,10 @@ static int launch_pw_y(const PwGemm &a, hipStream_t st)
     constexpr size_t lds = lds_main + lds_red;
     static_assert(lds <= 160 * 1024, "LDS budget of a CU");
     static int resident = 0;           // workgroups the device holds at once (CUs x occupancy), measured once per instantiation
-    auto kern = pw_gemm_kernel<CIN, NT, PRO, POOL, BF, ABF, ZBF, PIPE, ARG, X3, NW, XRT>;
+    constexpr auto kern = pw_gemm_kernel<CIN, NT, PRO, POOL, BF, ABF, ZBF, PIPE, ARG, X3, NW, XRT>;
     if (resident == 0) {
         if (lds > 65536) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "pw_gemm: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+            if (int rc = allow_dynamic_lds<kern>(lds, "pw_gemm")) return rc;
         }
         int per_cu = 0, dev = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), NW * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;

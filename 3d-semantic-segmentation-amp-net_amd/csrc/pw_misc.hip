@@ -8,8 +8,6 @@
 
 namespace ampnet {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ----------------------------------------------------------------------------------------------------
 // pw_input: 64 output channels, lane = channel, a wave walks rows.  HBM-bound (36 B in, 256 B out per
 // point), so the layout that matters is the coalesced 256-byte row store; x rows are staged through LDS.

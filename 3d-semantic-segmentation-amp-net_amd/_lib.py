@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 
@@ -253,3 +253,61 @@ def fp_forward_f32(points1, points2, idx, dist2, layers, eps, out, workspace):
                                          ptr(workspace), ctypes.c_size_t(workspace.numel() * workspace.element_size()),
                                          stream_ptr(points2.device))
     check(rc, "ampnet_fp_forward_f32")
+
+
+def fp_backward_workspace_bytes(D1, D2, B, N, couts):
+    """Device bytes fp_backward_f32 needs for points1 [B, N, D1], points2 [B, S, D2] and layers of widths `couts` (include/ampnet_hip.h:
+    ampnet_fp_backward_workspace_bytes); a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    couts = [int(c) for c in couts]
+    fn = lib().ampnet_fp_backward_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    need = fn(int(D1), int(D2), int(B), int(N), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
+    if not need:
+        check(-1, "ampnet_fp_backward_workspace_bytes")
+    return int(need)
+
+
+def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, dpoints2, grads, workspace):
+    """The backward of fp_forward_f32 with the running statistics frozen.  points1 .. eps: the forward's arguments; dout [B, N, cout_last];
+    dpoints1 [B, N, D1] (None exactly when points1 is None) and dpoints2 [B, S, D2]: written; grads: per layer the four contiguous float32
+    GPU tensors (dW [cout, cin], dbias [cout], dgamma [cout], dbeta [cout]), written; workspace: fp_backward_workspace_bytes(...) GPU
+    bytes."""
+    L = len(layers)
+    for name, t, dt in (("points1", points1, torch.float32), ("points2", points2, torch.float32), ("idx", idx, torch.int32),
+                        ("dist2", dist2, torch.float32), ("dout", dout, torch.float32), ("dpoints1", dpoints1, torch.float32),
+                        ("dpoints2", dpoints2, torch.float32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or t.dim() != 3):
+            raise AmpnetError(f"fp_backward: {name} must be a 3-d {dt} GPU tensor")
+    B, N, k = idx.shape
+    S, D2 = points2.shape[1], points2.shape[2]
+    D1 = 0 if points1 is None else points1.shape[2]
+    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)):
+        raise AmpnetError(f"fp_backward: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k] do not agree with idx {tuple(idx.shape)}")
+    if (dpoints1 is None) != (points1 is None):
+        raise AmpnetError(f"fp_backward: dpoints1 must be None exactly when points1 is (D1 = {D1}), got "
+                          f"{None if dpoints1 is None else tuple(dpoints1.shape)}")
+    if dpoints1 is not None and tuple(dpoints1.shape) != tuple(points1.shape):
+        raise AmpnetError(f"fp_backward: dpoints1 {tuple(dpoints1.shape)} must have the shape of points1 {tuple(points1.shape)}")
+    if tuple(dpoints2.shape) != tuple(points2.shape):
+        raise AmpnetError(f"fp_backward: dpoints2 {tuple(dpoints2.shape)} must have the shape of points2 {tuple(points2.shape)}")
+    table, couts, epss = _mlp_tables("fp_backward", layers, D1 + D2, eps, workspace, 0)
+    if L and tuple(dout.shape) != (B, N, int(layers[-1][0].shape[0])):
+        raise AmpnetError(f"fp_backward: dout {tuple(dout.shape)} must be [B, N, cout_last] = {[B, N, int(layers[-1][0].shape[0])]}")
+    if len(grads) != L:
+        raise AmpnetError(f"fp_backward: grads has {len(grads)} entries for {L} layers")
+    for i, (layer, g) in enumerate(zip(layers, grads)):
+        want = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
+        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, want)):
+            raise AmpnetError(f"fp_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in g]}")
+    need = fp_backward_workspace_bytes(D1, D2, B, N, [int(layer[0].shape[0]) for layer in layers])
+    have = workspace.numel() * workspace.element_size()
+    if have < need:
+        raise AmpnetError(f"fp_backward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
+    gtensors = [t for g in grads for t in g]
+    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L,
+                                          ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ptr(workspace), ctypes.c_size_t(have),
+                                          stream_ptr(points2.device))
+    check(rc, "ampnet_fp_backward_f32")

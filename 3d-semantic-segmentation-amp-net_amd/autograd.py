@@ -167,3 +167,52 @@ def cls_head_apply(module, pt, bt, gl_rows, mask, B, W, n_classes, p_drop, seed)
     out, aw = _ClsHeadFn.apply((module, pt, bt, mask, B, W, n_classes, p_drop, seed), gl_rows.contiguous().float(), *params)
     module.bn_2.num_batches_tracked += 1
     return out, aw
+
+
+class _FpFn(torch.autograd.Function):
+    """One fused feature-propagation layer with BatchNorm's running statistics frozen (pointnet2_utils.PointNetFeaturePropagation with
+    grad=True).  tensors: per layer conv weight [out, in, 1], conv bias, BatchNorm weight, bias, running_mean, running_var.  The forward
+    is the eval forward, unchanged, and keeps no activation: the backward kernel recomputes them (csrc/feature_propagation_bwd.hip).
+    Exact fp32 whatever the matrix precision is, so there is no precision scope to carry over."""
+
+    @staticmethod
+    def forward(ctx, eps, fold_ws, p1, p2, idx, dist2, *tensors):
+        layers = _fp_layers(tensors)
+        out = torch.empty((p2.shape[0], idx.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=p2.device)
+        _lib.fp_forward_f32(p1, p2, idx, dist2, layers, eps, out, fold_ws)
+        ctx.save_for_backward(p1, p2, idx, dist2, *tensors)        # (inputs only: see the note in _EncoderFn.forward)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        p1, p2, idx, dist2, *tensors = ctx.saved_tensors
+        layers = _fp_layers(tensors)
+        dp1 = None if p1 is None else torch.empty_like(p1)
+        dp2 = torch.empty_like(p2)
+        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
+        need = _lib.fp_backward_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], p2.shape[0], idx.shape[1],
+                                                [layer[0].shape[0] for layer in layers])
+        _lib.fp_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, dout.contiguous().float(), dp1, dp2, grads,
+                             torch.empty(need, dtype=torch.uint8, device=p2.device))
+        need_grad = ctx.needs_input_grad
+        ret = [None, None, dp1 if need_grad[2] else None, dp2 if need_grad[3] else None, None, None]
+        for l, g in enumerate(grads):
+            w = tensors[6 * l]
+            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3], None, None)):     # the conv weight keeps its [out, in, 1]
+                ret.append(t if t is not None and need_grad[6 + 6 * l + q] else None)
+        return tuple(ret)
+
+
+def _fp_layers(tensors):
+    """The six contiguous float32 tensors per layer that the C ABI takes, from the module's own (weight [out, in, 1] -> [out, in])."""
+    return [tuple(t.detach().reshape(t.shape[0], -1).float().contiguous() if q == 0 else t.detach().float().contiguous()
+                  for q, t in enumerate(tensors[i:i + 6])) for i in range(0, len(tensors), 6)]
+
+
+def fp_apply(module, p1, p2, idx, dist2, fold_ws):
+    """Grad-mode forward of a PointNetFeaturePropagation block on point-major rows: p1 [B, N, D1] or None, p2 [B, S, D2], idx / dist2
+    [B, N, k] from utils.three_nn -> [B, N, mlp[-1]] with a graph to p1, p2 and the block's conv and BatchNorm affine parameters."""
+    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
+               for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+    return _FpFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, p1, p2, idx, dist2, *tensors)

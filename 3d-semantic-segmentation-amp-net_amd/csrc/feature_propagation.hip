@@ -9,7 +9,8 @@
 // kernel's own:
 //
 //   * One row tile per wave.  A tile never spans two clouds; the rows past n of a cloud's last tile are zero-filled in LDS (nothing is
-//     read for them) and never stored.  The row builder's stores walk the column, like the epilogue's: the odd stride serves them too.
+//     read for them) and never stored.  The row builder (fp_rows.h, shared with the backward) stores along the column, like the
+//     epilogue: the odd stride serves both.
 //   * The contraction order inside a block of 8 is K_QUADS (k = k0 + 4 h + i), so unstaged weights with cin a multiple of 8 (every shape of
 //     pointnet_2) are one global_load_dwordx4 per lane and block.
 //   * The last layer stores its relu'd accumulators straight to `out` (for a fixed register the 32 lanes of a half write 128 contiguous
@@ -17,7 +18,7 @@
 //   * A 384-wide input tile plus a 256-wide output tile (fp3 of pointnet_2) is 82 KB per wave and 320 + 256 (fp2) 74 KB: ONE wave per
 //     workgroup for fp3 (B * 256 rows in all: the layer is small), two for fp2, four for fp1.  Layer 0's input is NOT built in K chunks.
 //   * No reduction ties a wave to a group, so the waves of a workgroup (up to 128 rows) share the staged weights.
-#include "fused_mlp.h"
+#include "fp_rows.h"
 
 namespace ampnet {
 
@@ -42,47 +43,11 @@ __global__ __launch_bounds__(256) void fp_forward_kernel(MlpPlan p, const float 
     const MlpLds m = mlp_lds(p, 32, s_mem, wave);
     mlp_stage_weights(p, m.s_w, tid, 64 * p.nw);
     __syncthreads();
-    const int cin0 = p.cin[0], kp0 = p.kp[0], cout_last = p.cout[p.L - 1];
+    const int kp0 = p.kp[0], cout_last = p.cout[p.L - 1];
     for (int tile = blockIdx.x * p.nw + wave; tile < n_tiles; tile += gridDim.x * p.nw) {
         const int cloud_i = tile / tiles_per_cloud, row0 = (tile - cloud_i * tiles_per_cloud) * 32;
         const int rows = min(32, n - row0);
-        const float *p1 = points1 ? points1 + ((size_t)cloud_i * n + row0) * D1 : nullptr;
-        const float *p2 = points2 + (size_t)cloud_i * s * D2;
-        // lane t (and t + 32) holds the neighbours and weights of row t; indices are clamped into the coarse cloud
-        int nb[3] = {0, 0, 0};
-        float wk[3] = {0.0f, 0.0f, 0.0f};
-        if ((lane & 31) < rows) {
-            const size_t o = ((size_t)cloud_i * n + row0 + (lane & 31)) * k;
-            float rk[3] = {0.0f, 0.0f, 0.0f};
-            for (int q = 0; q < k; ++q) {
-                nb[q] = min(max(idx[o + q], 0), s - 1);
-                rk[q] = 1.0f / (dist2[o + q] + 1e-8f);
-            }
-            float sum = rk[0];
-            if (k > 1) sum += rk[1];
-            if (k > 2) sum += rk[2];
-            for (int q = 0; q < k; ++q) wk[q] = rk[q] / sum;
-        }
-        // build the rows into tile A, the columns fastest across the lanes: a row's features load contiguously
-#pragma unroll 2
-        for (int t = 0; t < 32; ++t) {
-            const int j0 = __shfl(nb[0], t), j1 = __shfl(nb[1], t), j2 = __shfl(nb[2], t);
-            const float w0 = __shfl(wk[0], t), w1 = __shfl(wk[1], t), w2 = __shfl(wk[2], t);
-            const float *f0 = p2 + (size_t)j0 * D2, *f1 = p2 + (size_t)j1 * D2, *f2 = p2 + (size_t)j2 * D2;
-            for (int c = lane; c < kp0; c += 64) {
-                float v = 0.0f;
-                if (t < rows) {
-                    if (c < D1) {
-                        v = p1[(size_t)t * D1 + c];
-                    } else if (c < cin0) {
-                        v = w0 * f0[c - D1];
-                        if (k > 1) v = fmaf(w1, f1[c - D1], v);
-                        if (k > 2) v = fmaf(w2, f2[c - D1], v);
-                    }
-                }
-                m.tile_a[t * p.ld_a + c] = v;
-            }
-        }
+        fp_build_rows(m.tile_a, p.ld_a, kp0, points1, D1, points2, D2, n, s, idx, dist2, k, cloud_i, row0, rows, lane);      // fp_rows.h
         wave_lds_sync();
         mlp_run<K_QUADS>(p, 32, m.s_w, m.tile_a, m.tile_b, fold, FpStore{cout_last, rows},
                          out + ((size_t)cloud_i * n + row0) * cout_last, lane);

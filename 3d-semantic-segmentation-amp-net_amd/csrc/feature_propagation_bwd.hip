@@ -1,0 +1,485 @@
+// feature_propagation_bwd.hip -- the backward of one fused feature-propagation layer with BatchNorm's running statistics frozen (C ABI:
+// ampnet_fp_backward_f32, ampnet_fp_backward_workspace_bytes).  Per layer, with a = W x the raw accumulator, scale = gamma / sqrt(var + eps)
+// and y = fma(a, scale, shift) as in the forward:
+//     dy = dx_l [y > 0],  dbeta = sum_rows dy,  G = sum_rows dy a,  dgamma = (G + (b - mean) dbeta) / sqrt(var + eps),
+//     dz = dy scale,  dbias = scale dbeta,  dW = dz^T x_{l-1},  dx_{l-1} = dz W.
+// The forward keeps nothing, so everything is recomputed.  Five kernels on the caller's stream:
+//
+//   fold (sa_fold_kernel)   scale and shift, as in the forward.
+//   fp_backward_kernel      A workgroup is ONE wave and a wave owns 32 consecutive fine points of one cloud, as in the forward.  It rebuilds
+//       their rows with the forward's row builder (fp_rows.h) into tile X_0, runs layers 0 .. L-2 forward with the forward's own code
+//       (mlp_dispatch<K_QUADS>, weights read through L2) into tiles X_1 .. X_{L-1}, and keeps ALL of them: a tile per layer input instead
+//       of the forward's ping-pong.  Then it walks the layers backward.  Layer l: the accumulators a of the layer are computed AGAIN from
+//       X_l in the forward's contraction order (K_QUADS: the same bits, so the same ReLU mask), dx_l -- `dout` from global memory for the
+//       last layer, tile X_{l+1} otherwise -- becomes dz in place in X_{l+1} (the same element, the same lane), and dx_{l-1} = dz W
+//       overwrites X_l, whose activations nobody needs any more.  So L + 1 tiles of widths kp_0, cout_0 .. cout_{L-1}: 115 KB for
+//       fp3 of pointnet_2 (384 -> 256 -> 256).  The one shape family of the forward's limits that this exceeds (cin_0 > 504 with three
+//       layers of 256) builds X_0 in the space of X_2 and X_3 and REBUILDS it there before layer 0's backward.
+//       Why the layer's GEMM is run a second time instead of keeping a: a tile of a per layer would double the LDS, and a cannot be had
+//       back from y when scale = 0.  Why mlp_tiles is not reused for it: its epilogue is handed relu(y) only; its K loop is restated here
+//       (fpb_recompute) with the raw accumulator going to the backward's epilogue, and fused_mlp.h stays as the forward's tests pin it.
+//       dx = dz W is the forward's lane map with cin and cout exchanged: lane (r, h) supplies row r of dz and COLUMN c0 + r of W, read along
+//       W's rows through L2 (128 contiguous bytes per half wave and k); the contraction runs over o ascending in blocks of 8, k-step
+//       i < 4 of lane half h taking o = o0 + 2 i + h, one fmaf chain per output element.
+//       dx_0's columns [0, D1) are stored straight to dpoints1, columns [D1, cin_0) to the workspace for the scatter below.
+//       The wave also stores x_l and dz_l of its rows to the workspace (dW below) and adds its tiles' per-channel sums of dy and dy a
+//       (rows in the accumulator's order, lane half 0 before half 1, tiles in ascending order) into ITS OWN row of a partials array in
+//       global memory: every element is read and written by the same lane only.
+//   fp_wgrad_kernel, fp_wgrad_reduce_kernel   dW_l = dz_l^T x_l as a split-K MFMA GEMM over the rows: a wave takes a 32 x 128 block of dW and
+//       one chunk of rows (ascending, k-step i of half h takes row k0 + 2 i + h), the chunks' partials are added in ascending chunk order.
+//       The project's pw_wgrad / sgemm_wgrad_bias are built around windows and slots of the AMP-Net encoder (per-slot partials, BatchNorm
+//       constants folded in); this layer has neither, so it gets a kernel of its own.
+//   fp_scatter_kernel       dpoints2 as a GATHER: one wave per coarse point j scans its cloud's n k neighbour entries in ascending order, 64
+//       at a time, takes the entries equal to j by ballot and adds w_k dx_0[i, D1:] in ascending (i, k) order, a lane per column.  The
+//       weights are the forward's (fp_interp_weights).  No float atomics; a coarse point nobody picked gets zeros.
+//   fp_bwd_finalize_kernel  adds the workgroups' partials in a fixed order (a wave per channel) and derives dbeta, dgamma and dbias.
+//
+// Every order above is a function of the shape alone: two runs give the same bits.  Exact fp32 MFMA whatever the matrix precision is.
+#include "fp_rows.h"
+
+namespace ampnet {
+
+constexpr int FPB_MAX_GRID = 1024;        // workgroups (= rows of the partials array) of fp_backward_kernel
+constexpr int FPB_MAX_CHUNKS = 256;       // split-K chunks of fp_wgrad_kernel
+constexpr int FPB_MIN_CHUNK_ROWS = 64;
+
+struct FpBwdPlan {
+    int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];   // tile X_l: float offset in LDS, odd row stride
+    int rebuild;                                               // X_0 shares the space of X_2, X_3 and is built twice
+    int ldxs[MLP_MAX_LAYERS];                                  // row stride of x_l in the workspace: cin_l rounded up to 32 (zeros)
+    int sum_c;                                                 // sum of cout_l; layer l's channels start at fold_off[l] / 2
+    float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts;
+};
+
+struct FpBwdFin {
+    float *dbias[MLP_MAX_LAYERS], *dgamma[MLP_MAX_LAYERS], *dbeta[MLP_MAX_LAYERS];
+};
+
+// The accumulators of layer l on the wave's tile x, NT column tiles from n0, in the forward's order (mlp_tiles<NT, K_QUADS, VEC>), and the
+// backward's epilogue: d [32][ldd] holds dx_l on entry (dout != nullptr: the rows come from global memory, row stride cout) and dz on exit.
+template <int NT, bool VEC>
+__device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
+                                              const float *__restrict__ scale, const float *__restrict__ shift, float *d, int ldd,
+                                              const float *__restrict__ dout, int rows, float *__restrict__ dz_ws, float *part_b,
+                                              float *part_g, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    const float *xr = x + r * ldx + 4 * h;
+    for (int k0 = 0; k0 < kp; k0 += 8) {
+        float av[4], bv[NT][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = xr[k0 + i];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float *wr = w + (size_t)(n0 + 32 * t + r) * cin + k0 + 4 * h;
+            if (VEC) {
+                const float4 q = *reinterpret_cast<const float4 *>(wr);
+                bv[t][0] = q.x;
+                bv[t][1] = q.y;
+                bv[t][2] = q.z;
+                bv[t][3] = q.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bv[t][i] = k0 + 4 * h + i < cin ? wr[i] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = n0 + 32 * t + r;
+        const float sc = scale[col], sh = shift[col];
+        float sb = 0.0f, sg = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const float a = acc[t][i];
+            float din;
+            if (dout) din = row < rows ? dout[(size_t)row * cout + col] : 0.0f;
+            else din = d[row * ldd + col];
+            const float dy = fmaf(a, sc, sh) > 0.0f ? din : 0.0f;
+            sb += dy;
+            sg = fmaf(dy, a, sg);
+            const float dzv = dy * sc;
+            d[row * ldd + col] = dzv;
+            if (row < rows) dz_ws[(size_t)row * cout + col] = dzv;
+        }
+        const float ob = __shfl_down(sb, 32), og = __shfl_down(sg, 32);
+        if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
+            part_b[col] += sb + ob;
+            part_g[col] += sg + og;
+        }
+    }
+}
+
+// dx = dz W for NT column tiles of the layer's INPUT from c0: dz [32][ldd] in LDS, w [cout][cin] global.  Results go to tile `xo` (l >= 1)
+// or, xo == nullptr, to dpoints1 / the dx_0 rows of the workspace (layer 0; D1 + D2 = cin).
+template <int NT>
+__device__ __forceinline__ void fpb_dgrad(const float *d, int ldd, const float *__restrict__ w, int cin, int cout, int c0, float *xo, int ldxo,
+                                          float *__restrict__ dp1, int D1, float *__restrict__ dx0, int D2, int rows, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    const float *dr = d + r * ldd + h;
+    for (int o0 = 0; o0 < cout; o0 += 8) {
+        float av[4], bv[NT][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = dr[o0 + 2 * i];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int c = c0 + 32 * t + r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bv[t][i] = c < cin ? w[(size_t)(o0 + 2 * i + h) * cin + c] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int c = c0 + 32 * t + r;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            if (xo) {
+                if (c < cin) xo[row * ldxo + c] = acc[t][i];
+            } else if (row < rows) {
+                if (c < D1) dp1[(size_t)row * D1 + c] = acc[t][i];
+                else if (c < cin) dx0[(size_t)row * D2 + c - D1] = acc[t][i];
+            }
+        }
+    }
+}
+
+// the wave's tile [32][ld] -> rows < rows of a global array with row stride ldg (columns past `valid` as zeros)
+__device__ __forceinline__ void fpb_store_rows(const float *tile, int ld, int valid, float *__restrict__ g, int ldg, int rows, int lane)
+{
+    for (int t = 0; t < rows; ++t)
+        for (int c = lane; c < ldg; c += 64) g[(size_t)t * ldg + c] = c < valid ? tile[t * ld + c] : 0.0f;
+}
+
+__global__ __launch_bounds__(64) void fp_backward_kernel(MlpPlan p, FpBwdPlan b, const float *__restrict__ points1, int D1,
+                                                        const float *__restrict__ points2, int D2, int n, int s,
+                                                        const int32_t *__restrict__ idx, const float *__restrict__ dist2, int k,
+                                                        const float *__restrict__ fold, const float *__restrict__ dout, int tiles_per_cloud,
+                                                        int n_tiles, float *__restrict__ dpoints1)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const int lane = threadIdx.x;
+    const int L = p.L;
+    float *part_b = b.parts + (size_t)blockIdx.x * 2 * b.sum_c, *part_g = part_b + b.sum_c;
+    if (lane < 32)
+        for (int c = lane; c < b.sum_c; c += 32) part_b[c] = part_g[c] = 0.0f;       // channel c belongs to lane c % 32, here and below
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int cloud_i = tile / tiles_per_cloud, row0 = (tile - cloud_i * tiles_per_cloud) * 32;
+        const int rows = min(32, n - row0);
+        const size_t grow = (size_t)cloud_i * n + row0;
+        float *x0 = s_mem + b.off_x[0];
+        fp_build_rows(x0, b.ld_x[0], p.kp[0], points1, D1, points2, D2, n, s, idx, dist2, k, cloud_i, row0, rows, lane);
+        wave_lds_sync();
+        fpb_store_rows(x0, b.ld_x[0], p.kp[0], b.xs[0] + grow * b.ldxs[0], b.ldxs[0], rows, lane);
+        for (int l = 0; l + 1 < L; ++l) {
+            float *y = s_mem + b.off_x[l + 1];
+            mlp_dispatch<K_QUADS>(p, l, 32, s_mem, s_mem + b.off_x[l], b.ld_x[l], fold, MlpToTile{y, b.ld_x[l + 1]}, nullptr, lane);
+            wave_lds_sync();
+            fpb_store_rows(y, b.ld_x[l + 1], p.cout[l], b.xs[l + 1] + grow * b.ldxs[l + 1], b.ldxs[l + 1], rows, lane);
+        }
+        for (int l = L - 1; l >= 0; --l) {
+            float *x = s_mem + b.off_x[l], *d = s_mem + b.off_x[l + 1];
+            const int ldx = b.ld_x[l], ldd = b.ld_x[l + 1], cin = p.cin[l], cout = p.cout[l], ch = p.fold_off[l] / 2;
+            if (l == 0 && b.rebuild) {
+                wave_lds_sync();                  // the reads of X_2 (dx = dz W of layer 1) are done
+                fp_build_rows(x, ldx, p.kp[0], points1, D1, points2, D2, n, s, idx, dist2, k, cloud_i, row0, rows, lane);
+                wave_lds_sync();
+            }
+            const float *scale = fold + p.fold_off[l], *shift = scale + cout;
+            const float *dsrc = l == L - 1 ? dout + grow * cout : nullptr;
+            float *dz_ws = b.dz[l] + grow * cout;
+            int n0 = 0;
+            if (p.w_vec[l]) {
+                for (; n0 + 128 <= cout; n0 += 128)
+                    fpb_recompute<4, true>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, dsrc, rows, dz_ws, part_b + ch, part_g + ch, lane);
+                for (; n0 < cout; n0 += 32)
+                    fpb_recompute<1, true>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, dsrc, rows, dz_ws, part_b + ch, part_g + ch, lane);
+            } else {
+                for (; n0 + 128 <= cout; n0 += 128)
+                    fpb_recompute<4, false>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, dsrc, rows, dz_ws, part_b + ch, part_g + ch, lane);
+                for (; n0 < cout; n0 += 32)
+                    fpb_recompute<1, false>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, dsrc, rows, dz_ws, part_b + ch, part_g + ch, lane);
+            }
+            wave_lds_sync();
+            float *xo = l ? x : nullptr;
+            float *dp1 = dpoints1 ? dpoints1 + grow * D1 : nullptr, *dx0 = b.dx0 + grow * D2;
+            int c0 = 0;
+            for (; c0 + 128 <= cin; c0 += 128) fpb_dgrad<4>(d, ldd, p.w[l], cin, cout, c0, xo, ldx, dp1, D1, dx0, D2, rows, lane);
+            for (; c0 < cin; c0 += 32) fpb_dgrad<1>(d, ldd, p.w[l], cin, cout, c0, xo, ldx, dp1, D1, dx0, D2, rows, lane);
+            wave_lds_sync();
+        }
+    }
+}
+
+// dW partial of one chunk of rows: block (c0 / 128, o0 / 32, chunk), one wave; part [chunks][cout][ldxs]
+__global__ __launch_bounds__(64) void fp_wgrad_kernel(const float *__restrict__ dz, int cout, const float *__restrict__ xs, int ldxs, long long M,
+                                                     int chunk_rows, float *__restrict__ part)
+{
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int c0 = blockIdx.x * 128, o0 = blockIdx.y * 32;
+    const long long k_begin = (long long)blockIdx.z * chunk_rows, k_end = min(M, k_begin + chunk_rows);
+    f32x16 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    for (long long k0 = k_begin; k0 < k_end; k0 += 8) {
+        float av[4], bv[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long row = k0 + 2 * i + h;
+            av[i] = row < k_end ? dz[(size_t)row * cout + o0 + r] : 0.0f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) bv[t][i] = row < k_end && c0 + 32 * t < ldxs ? xs[(size_t)row * ldxs + c0 + 32 * t + r] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+    float *dst = part + (size_t)blockIdx.z * cout * ldxs;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (c0 + 32 * t < ldxs)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) dst[(size_t)(o0 + (i & 3) + 8 * (i >> 2) + 4 * h) * ldxs + c0 + 32 * t + r] = acc[t][i];
+}
+
+__global__ void fp_wgrad_reduce_kernel(const float *__restrict__ part, int chunks, int cout, int cin, int ldxs, float *__restrict__ dW)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= cout * cin) return;
+    const int o = e / cin, c = e - o * cin;
+    float v = 0.0f;
+    for (int q = 0; q < chunks; ++q) v += part[((size_t)q * cout + o) * ldxs + c];
+    dW[e] = v;
+}
+
+__global__ __launch_bounds__(64) void fp_scatter_kernel(const float *__restrict__ dx0, int D2, int n, int s, const int32_t *__restrict__ idx,
+                                                       const float *__restrict__ dist2, int k, float *__restrict__ dpoints2)
+{
+    const int lane = threadIdx.x;
+    const int cloud_i = blockIdx.x / s, j = blockIdx.x - cloud_i * s;
+    const long long total = (long long)n * k;
+    const int32_t *ic = idx + (size_t)cloud_i * total;
+    const float *dc = dist2 + (size_t)cloud_i * total, *gx = dx0 + (size_t)cloud_i * n * D2;
+    float acc[AMPNET_FP_MAX_CIN / 64];
+#pragma unroll
+    for (int u = 0; u < AMPNET_FP_MAX_CIN / 64; ++u) acc[u] = 0.0f;
+    for (long long e0 = 0; e0 < total; e0 += 64) {
+        const long long e = e0 + lane;
+        const bool hit = e < total && min(max(ic[e], 0), s - 1) == j;
+        int i = 0;
+        float w = 0.0f;
+        if (hit) {
+            i = (int)(e / k);
+            const int q = (int)(e - (long long)i * k);
+            float wk[3];
+            fp_interp_weights(dc + (size_t)i * k, k, wk);
+            w = q == 0 ? wk[0] : q == 1 ? wk[1] : wk[2];
+        }
+        unsigned long long mask = __ballot(hit);
+        while (mask) {                            // wave-uniform: every lane walks the hits in ascending entry order
+            const int src = __ffsll(mask) - 1;
+            mask &= mask - 1;
+            const int ib = __shfl(i, src);
+            const float wb = __shfl(w, src);
+            const float *row = gx + (size_t)ib * D2;
+#pragma unroll
+            for (int u = 0; u < AMPNET_FP_MAX_CIN / 64; ++u)
+                if (lane + 64 * u < D2) acc[u] = fmaf(wb, row[lane + 64 * u], acc[u]);
+        }
+    }
+    float *dst = dpoints2 + (size_t)blockIdx.x * D2;
+#pragma unroll
+    for (int u = 0; u < AMPNET_FP_MAX_CIN / 64; ++u)
+        if (lane + 64 * u < D2) dst[lane + 64 * u] = acc[u];
+}
+
+// next to sa_fold_kernel: the same parameters, the other direction.  One wave per channel: lane t adds the partials of workgroups t, t + 64, ..
+// in ascending order, the 64 lane sums go through a fixed halving tree (32, 16, .. 1).
+__global__ __launch_bounds__(256) void fp_bwd_finalize_kernel(MlpPlan p, MlpFold f, FpBwdFin g, const float *__restrict__ fold,
+                                                             const float *__restrict__ parts, int n_parts, int sum_c)
+{
+    const int lane = threadIdx.x & 63, ch = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ch >= sum_c) return;                      // (the whole wave)
+    int l = 0;
+    while (l + 1 < p.L && ch >= p.fold_off[l + 1] / 2) ++l;
+    const int c = ch - p.fold_off[l] / 2;
+    float dbeta = 0.0f, G = 0.0f;
+    for (int q = lane; q < n_parts; q += 64) {
+        dbeta += parts[(size_t)q * 2 * sum_c + ch];
+        G += parts[(size_t)q * 2 * sum_c + sum_c + ch];
+    }
+    for (int off = 32; off; off >>= 1) {
+        dbeta += __shfl_down(dbeta, off);
+        G += __shfl_down(G, off);
+    }
+    if (lane) return;
+    g.dbeta[l][c] = dbeta;
+    g.dgamma[l][c] = fmaf(f.bias[l][c] - f.mean[l][c], dbeta, G) / sqrtf(f.var[l][c] + f.eps[l]);
+    g.dbias[l][c] = fold[p.fold_off[l] + c] * dbeta;
+}
+
+// what both entry points derive from the shape: the launch sizes and the workspace layout (float offsets, each a multiple of 64)
+struct FpBwdShape {
+    long long M;
+    int tiles_per_cloud, n_tiles, grid, chunk_rows, chunks, sum_c;
+    int cin[MLP_MAX_LAYERS], ldxs[MLP_MAX_LAYERS];
+    size_t off_parts, off_xs[MLP_MAX_LAYERS], off_dz[MLP_MAX_LAYERS], off_dx0, off_wpart, floats;
+};
+
+static int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, const int *cout_host, int L, FpBwdShape &sh)
+{
+    AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
+    AMPNET_REQUIRE(n_clouds >= 1 && n >= 1, "%s: bad shape n_clouds=%d n=%d", what, n_clouds, n);
+    AMPNET_REQUIRE(L >= 1 && L <= AMPNET_FP_MAX_LAYERS, "%s: L=%d layers, the kernel is built for 1 .. %d", what, L, AMPNET_FP_MAX_LAYERS);
+    AMPNET_REQUIRE(D1 >= 0 && D2 >= 1 && D1 <= AMPNET_FP_MAX_CIN && D2 <= AMPNET_FP_MAX_CIN && D1 + D2 <= AMPNET_FP_MAX_CIN,
+                   "%s: cin_0 = D1 + D2 = %d + %d must be in [1, %d] with D2 >= 1", what, D1, D2, AMPNET_FP_MAX_CIN);
+    sh = {};
+    sh.tiles_per_cloud = (int)(((long long)n + 31) / 32);
+    AMPNET_REQUIRE((long long)n_clouds * sh.tiles_per_cloud <= 0x7fff0000LL, "%s: n_clouds * ceil(n / 32) = %lld tiles exceed %lld", what,
+                   (long long)n_clouds * sh.tiles_per_cloud, 0x7fff0000LL);
+    sh.M = (long long)n_clouds * n;
+    sh.n_tiles = n_clouds * sh.tiles_per_cloud;
+    sh.grid = sh.n_tiles < FPB_MAX_GRID ? sh.n_tiles : FPB_MAX_GRID;
+    const long long per = (sh.M + FPB_MAX_CHUNKS - 1) / FPB_MAX_CHUNKS;
+    sh.chunk_rows = (int)((per + 7) / 8 * 8);
+    if (sh.chunk_rows < FPB_MIN_CHUNK_ROWS) sh.chunk_rows = FPB_MIN_CHUNK_ROWS;
+    sh.chunks = (int)((sh.M + sh.chunk_rows - 1) / sh.chunk_rows);
+    size_t off = align_up((size_t)AMPNET_FP_WORKSPACE_BYTES / sizeof(float), 64), wmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const int cout = cout_host[l];
+        AMPNET_REQUIRE(cout >= 32 && cout <= AMPNET_FP_MAX_COUT && cout % 32 == 0, "%s: layer %d has cout=%d, must be a multiple of 32 in [32, %d]",
+                       what, l, cout, AMPNET_FP_MAX_COUT);
+        sh.cin[l] = l ? cout_host[l - 1] : D1 + D2;
+        sh.ldxs[l] = (sh.cin[l] + 31) / 32 * 32;
+        sh.sum_c += cout;
+        if ((size_t)cout * sh.ldxs[l] > wmax) wmax = (size_t)cout * sh.ldxs[l];
+    }
+    sh.off_parts = off;
+    off += align_up((size_t)sh.grid * 2 * sh.sum_c, 64);
+    for (int l = 0; l < L; ++l) {
+        sh.off_xs[l] = off;
+        off += align_up((size_t)sh.M * sh.ldxs[l], 64);
+        sh.off_dz[l] = off;
+        off += align_up((size_t)sh.M * cout_host[l], 64);
+    }
+    sh.off_dx0 = off;
+    off += align_up((size_t)sh.M * D2, 64);
+    sh.off_wpart = off;
+    off += align_up((size_t)sh.chunks * wmax, 64);
+    sh.floats = off;
+    return AMPNET_OK;
+}
+
+}  // namespace ampnet
+
+extern "C" size_t ampnet_fp_backward_workspace_bytes(int D1, int D2, int n_clouds, int n, const int *cout_host, int L)
+{
+    using namespace ampnet;
+    FpBwdShape sh;
+    if (fpb_shape("ampnet_fp_backward_workspace_bytes", D1, D2, n_clouds, n, cout_host, L, sh) != AMPNET_OK) return 0;
+    return sh.floats * sizeof(float);
+}
+
+extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                                      const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host,
+                                      int L, const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    using namespace ampnet;
+    const char *what = "ampnet_fp_backward_f32";
+    hipStream_t st = (hipStream_t)stream;
+    AMPNET_REQUIRE(points2 && idx && dist2 && params_host && cout_host && eps_host && dout && dpoints2 && grads_host, "%s: null pointer", what);
+    AMPNET_REQUIRE(s >= 1, "%s: bad shape s=%d", what, s);
+    AMPNET_REQUIRE(k >= 1 && k <= 3 && k <= s, "%s: k=%d must be 1, 2 or 3 and <= s=%d", what, k, s);
+    AMPNET_REQUIRE(D1 >= 0 && (D1 == 0) == (points1 == nullptr), "%s: points1 must be NULL exactly when D1 = 0 (D1=%d)", what, D1);
+    AMPNET_REQUIRE((D1 == 0) == (dpoints1 == nullptr), "%s: dpoints1 must be NULL exactly when D1 = 0 (D1=%d)", what, D1);
+    FpBwdShape sh;
+    int rc = fpb_shape(what, D1, D2, n_clouds, n, cout_host, L, sh);
+    if (rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE((long long)n_clouds * s <= 0x7fffffffLL, "%s: n_clouds * s = %lld coarse points exceed 2^31 - 1", what, (long long)n_clouds * s);
+    for (int q = 0; q < 4 * L; ++q) AMPNET_REQUIRE(grads_host[q], "%s: null gradient pointer %d of layer %d", what, q % 4, q / 4);
+    AMPNET_REQUIRE(workspace && workspace_bytes >= sh.floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
+                   sh.floats * sizeof(float));
+    MlpPlan p;
+    MlpFold f;
+    if (!mlp_plan_build(what, D1 + D2, 32, params_host, cout_host, eps_host, L, p, f)) return AMPNET_E_ARG;
+    p.nw = 1;
+    for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // this kernel stages no weights: every layer is read through L2
+    // the tiles X_0 .. X_L
+    FpBwdPlan b = {};
+    int floats = 0;
+    for (int l = 0; l <= L; ++l) {
+        b.ld_x[l] = (l ? p.cout[l - 1] : p.kp[0]) + 1;
+        b.off_x[l] = floats;
+        floats += 32 * b.ld_x[l];
+    }
+    if ((size_t)floats * sizeof(float) > (size_t)MLP_LDS_BYTES && L == 3 && b.ld_x[0] <= b.ld_x[2] + b.ld_x[3]) {
+        b.rebuild = 1;
+        floats -= 32 * b.ld_x[0];
+        for (int l = 1; l <= L; ++l) b.off_x[l] -= 32 * b.ld_x[0];
+        b.off_x[0] = b.off_x[2];
+    }
+    AMPNET_REQUIRE((size_t)floats * sizeof(float) <= (size_t)MLP_LDS_BYTES, "%s: a wave's tiles (%zu bytes) exceed the LDS", what,
+                   (size_t)floats * sizeof(float));
+    float *ws = static_cast<float *>(workspace);
+    b.sum_c = sh.sum_c;
+    b.parts = ws + sh.off_parts;
+    b.dx0 = ws + sh.off_dx0;
+    FpBwdFin g = {};
+    for (int l = 0; l < L; ++l) {
+        b.ldxs[l] = sh.ldxs[l];
+        b.xs[l] = ws + sh.off_xs[l];
+        b.dz[l] = ws + sh.off_dz[l];
+        g.dbias[l] = grads_host[4 * l + 1];
+        g.dgamma[l] = grads_host[4 * l + 2];
+        g.dbeta[l] = grads_host[4 * l + 3];
+    }
+    static bool attr_set = false;
+    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(fp_backward_kernel), attr_set);
+    if (rc != AMPNET_OK) return rc;
+    rc = mlp_fold_launch(p, f, ws, st);
+    if (rc != AMPNET_OK) return rc;
+    hipLaunchKernelGGL(fp_backward_kernel, dim3(sh.grid), dim3(64), floats * sizeof(float), st, p, b, points1, D1, points2, D2, n, s, idx, dist2,
+                       k, ws, dout, sh.tiles_per_cloud, sh.n_tiles, dpoints1);
+    rc = check_launch("fp_backward_kernel");
+    if (rc != AMPNET_OK) return rc;
+    float *wpart = ws + sh.off_wpart;
+    for (int l = 0; l < L; ++l) {
+        hipLaunchKernelGGL(fp_wgrad_kernel, dim3(cdiv(sh.ldxs[l], 128), p.cout[l] / 32, sh.chunks), dim3(64), 0, st, b.dz[l], p.cout[l], b.xs[l],
+                           sh.ldxs[l], sh.M, sh.chunk_rows, wpart);
+        rc = check_launch("fp_wgrad_kernel");
+        if (rc != AMPNET_OK) return rc;
+        hipLaunchKernelGGL(fp_wgrad_reduce_kernel, dim3(cdiv(p.cout[l] * p.cin[l], 256)), dim3(256), 0, st, wpart, sh.chunks, p.cout[l], p.cin[l],
+                           sh.ldxs[l], grads_host[4 * l]);
+        rc = check_launch("fp_wgrad_reduce_kernel");
+        if (rc != AMPNET_OK) return rc;
+    }
+    hipLaunchKernelGGL(fp_scatter_kernel, dim3(n_clouds * s), dim3(64), 0, st, b.dx0, D2, n, s, idx, dist2, k, dpoints2);
+    rc = check_launch("fp_scatter_kernel");
+    if (rc != AMPNET_OK) return rc;
+    hipLaunchKernelGGL(fp_bwd_finalize_kernel, dim3(cdiv(sh.sum_c, 4)), dim3(256), 0, st, p, f, g, ws, b.parts, sh.grid, sh.sum_c);
+    return check_launch("fp_bwd_finalize_kernel");
+}

@@ -3,13 +3,19 @@
 The reference imports `PointNetSetAbstraction` and `PointNetFeaturePropagation` from a package it does not ship (pointnetAtt.py:4,
 used at :285-292).  This module provides both with the constructors and the state_dict keys of the usual PointNet++ implementation --
 `mlp_convs.{i}.{weight, bias}` (weight [out, in, 1, 1] in the set abstraction, [out, in, 1] in the feature propagation),
-`mlp_bns.{i}.{weight, bias, running_mean, running_var, num_batches_tracked}` -- so its checkpoints load.  Inference only:
+`mlp_bns.{i}.{weight, bias, running_mean, running_var, num_batches_tracked}` -- so its checkpoints load.  Eval mode only:
   * PointNetSetAbstraction: farthest-point sampling (ampnet_fps_f32), ball query (ampnet_ball_query_f32) and ONE fused kernel for
     gather + shared MLP + max (ampnet_sa_forward_f32);
   * PointNetFeaturePropagation: the 3 nearest coarse points of every fine point (ampnet_three_nn_f32) and ONE fused kernel for
     inverse-distance interpolation + concatenation + shared MLP (ampnet_fp_forward_f32).
-Both fused kernels are exact fp32 whatever the matrix precision is.  Not built: `group_all=True`, train-mode BatchNorm statistics, any
-backward.
+Both fused kernels are exact fp32 whatever the matrix precision is.
+
+Gradients are opt-in and cover the decoder half: PointNetFeaturePropagation(..., grad=True) in EVAL mode is differentiable
+(ampnet_fp_backward_f32 through autograd._FpFn) with respect to points1, points2, its conv weights and biases and its BatchNorm weight
+and bias; running_mean and running_var are constants of that backward and are never updated, the coordinates get no gradient.  That is
+what fitting a pretrained decoder to new clouds needs (pointnetAtt.pointnet_2(decoder_grad=True)).  Not built: the set-abstraction
+backward (PointNetSetAbstraction has no gradient at all), train-mode BatchNorm (batch statistics, running-statistics updates: .train()
+still raises), gradients to coordinates, `group_all=True`.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
 from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
@@ -141,10 +147,13 @@ def _mlp_tensors(mod):
 class PointNetFeaturePropagation(nn.Module):
     """One feature-propagation layer: every fine point takes the inverse-squared-distance weighted mean of the features of its 3 nearest
     coarse points (utils.three_nn; all of them when there are fewer than 3), concatenated behind its own features, through the shared MLP
-    `mlp` (Conv1d 1x1 + BatchNorm1d + ReLU per entry).  `in_channel` = D1 + D2, as in the usual implementation."""
+    `mlp` (Conv1d 1x1 + BatchNorm1d + ReLU per entry).  `in_channel` = D1 + D2, as in the usual implementation.
+    grad=True: in eval mode, with grad mode on and an input or a parameter that requires grad, the result carries a graph to points1,
+    points2 and the conv / BatchNorm affine parameters (the running statistics stay frozen).  grad=False (default): no graph, ever."""
 
-    def __init__(self, in_channel, mlp, device='cuda'):
+    def __init__(self, in_channel, mlp, device='cuda', grad=False):
         super().__init__()
+        self.grad = bool(grad)
         _build_mlp(self, in_channel, mlp, (1,), 1 <= in_channel <= _lib.FP_MAX_CIN,
                    f"the HIP feature propagation is built for 1..{_lib.FP_MAX_LAYERS} MLP layers of widths that are "
                    f"multiples of 32 up to {_lib.FP_MAX_COUT} and 1 <= in_channel <= {_lib.FP_MAX_CIN}", device)
@@ -170,15 +179,26 @@ class PointNetFeaturePropagation(nn.Module):
         if D1 < 0 or (points1 is None) != (D1 == 0) or (points1 is not None and tuple(points1.shape) != (B, D1, N)):
             raise _lib.AmpnetError(f"PointNetFeaturePropagation: in_channel={self.in_channel} with points2 {tuple(points2.shape)} needs "
                                    f"points1 {'None' if D1 == 0 else [B, D1, N]}, got {None if points1 is None else tuple(points1.shape)}")
+        if self._wants_grad(points1, points2):                       # differentiable transposes; the coordinates get no gradient
+            rows = lambda t: None if t is None else t.float().transpose(1, 2).contiguous()
+            out = self._forward_rows(rows(xyz1.detach()), rows(xyz2.detach()), rows(points1), rows(points2))
+            return out.transpose(1, 2).contiguous()
         with torch.no_grad():
             rows = lambda t: None if t is None else t.detach().float().transpose(1, 2).contiguous()
             out = self._forward_rows(rows(xyz1), rows(xyz2), rows(points1), rows(points2))
         return out.transpose(1, 2).contiguous()
 
+    def _wants_grad(self, p1, p2):
+        return self.grad and torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in (p1, p2))
+                                                          or any(p.requires_grad for p in self.parameters()))
+
     def _forward_rows(self, x1, x2, p1, p2):
         """The layer on point-major tensors: x1 [B, N, 3], x2 [B, S, 3], p1 [B, N, D1] or None, p2 [B, S, D2], float32 contiguous GPU
         -> [B, N, mlp[-1]]."""
-        idx, dist2 = U.three_nn(x1, x2)
+        idx, dist2 = U.three_nn(x1.detach(), x2.detach())
+        if self._wants_grad(p1, p2):
+            from ... import autograd
+            return autograd.fp_apply(self, p1, p2, idx, dist2, _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
         layers = _mlp_tensors(self)
         out = torch.empty((x1.shape[0], x1.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
         _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out,

@@ -424,16 +424,22 @@ class pointnet_2(nn.Module):
     state_dict keys.  forward(xyz [B, 9, N]) -> (global_feature [B, 128], l0_points [B, 128, N]); the nine input channels are the point
     features of `sa1`, the first three of them the coordinates.  Every block runs its fused HIP kernel (pointnet2_utils.py) and hands the
     next one its point-major [B, N, C] result as it is; `conv1` and the max over the points are torch operations.  `num_classes` is
-    unused, as in the reference (its classifier layers are commented out there)."""
+    unused, as in the reference (its classifier layers are commented out there).
 
-    def __init__(self, num_classes, device='cuda'):
+    decoder_grad=True makes the decoder trainable in eval mode (fine-tuning a pretrained backbone with a torch loss and a torch
+    optimiser): `fp3`, `fp2`, `fp1` run with grad=True and `conv1` is a torch layer, so both outputs carry a graph to the conv weights
+    and biases and the BatchNorm weights and biases of fp1..fp3 and to conv1.  Frozen: `sa1`..`sa3` (the encoder runs under no_grad on
+    detached inputs, its parameters get no gradient) and every running_mean / running_var.  Train mode is still not built: .train() raises."""
+
+    def __init__(self, num_classes, device='cuda', decoder_grad=False):
         super().__init__()
+        self.decoder_grad = bool(decoder_grad)
         self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device)
         self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device)
         self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device)
-        self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device)
-        self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device)
-        self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device)
+        self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device, grad=self.decoder_grad)
+        self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device, grad=self.decoder_grad)
+        self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device, grad=self.decoder_grad)
         self.conv1 = nn.Conv1d(128, 128, 1, device=device)
 
     def forward(self, xyz):
@@ -452,6 +458,7 @@ class pointnet_2(nn.Module):
             l1_xyz, l1_points = self.sa1._forward_rows(l0_xyz, l0_points)             # [B, 1024, 3], [B, 1024, 64]
             l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)             # [B, 256, 3], [B, 256, 128]
             l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)             # [B, 64, 3], [B, 64, 256]
+        with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
             l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)  # [B, 256, 256]
             l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)  # [B, 1024, 128]
             l0_points = self.fp1._forward_rows(l0_xyz, l1_xyz, None, l1_points)       # [B, N, 128]

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 10
+#define AMPNET_ABI_VERSION 11
 
 enum {
     AMPNET_OK = 0,
@@ -379,6 +379,38 @@ int ampnet_three_nn_f32(const float *fine, int n_clouds, int n, int ld1, const f
 int ampnet_fp_forward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
                           const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
                           float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the backward of ampnet_fp_forward_f32 with BatchNorm's running statistics frozen (decoder fine-tuning) --------------------------
+ *   points1 .. eps_host, L   the forward's arguments, unchanged (the forward keeps nothing: the backward recomputes it)
+ *   dout                  [n_clouds, n, cout_{L-1}] float32, the gradient of the forward's `out`
+ *   dpoints1              [n_clouds, n, D1] out, NULL exactly when D1 = 0
+ *   dpoints2              [n_clouds, s, D2] out; the row of a coarse point that is nobody's neighbour is written as zeros
+ *   grads_host            HOST array of 4 L DEVICE pointers, per layer: dW [cout_l, cin_l], dbias, dgamma, dbeta (each [cout_l]), all out
+ *   workspace             ampnet_fp_backward_workspace_bytes(D1, D2, n_clouds, n, cout_host, L) device bytes (0 = the shape is refused,
+ *                         ampnet_last_error says why); contents undefined before and after
+ * Per layer l, over the rows i of all clouds, with x_l the layer's input row (x_0 as in the forward), a = W_l x_l,
+ * scale = gamma / sqrt(var + eps), y = fma(a, scale, shift) exactly as the forward forms them (so the ReLU mask is the forward's):
+ *     dy = dx_{l+1} [y > 0]   (dx_L = dout)          dbeta = sum_i dy          G = sum_i dy a
+ *     dgamma = (G + (b - mean) dbeta) / sqrt(var + eps)          dbias = scale dbeta
+ *     dz = dy scale          dW_l = dz^T x_l          dx_l = dz W_l
+ * dpoints1 = columns [0, D1) of dx_0; dpoints2[j] = sum over the entries (i, q) with idx[i, q] = j (clamped as in the forward) of
+ * w_q(i) dx_0[i, D1:], w the forward's interpolation weights.  running_mean and running_var are constants; xyz, dist2 and the weights w
+ * get no gradient.  gamma = 0 needs no special case.
+ * Summation orders (each a function of the shape alone, so two calls on the same inputs return the same bits; no atomics):
+ *   a, y      the forward's: k ascending in blocks of 8, k-step i < 4 of lane half h takes k = k0 + 4 h + i, one fmaf chain per element
+ *   dx_l      o ascending in blocks of 8, k-step i < 4 of lane half h takes o = o0 + 2 i + h, one fmaf chain per element
+ *   dW_l      the rows in chunks of max(64, ceil(rows / 256) rounded up to 8) rows: inside a chunk one fmaf chain over the rows
+ *             in the order k0 + 2 i + h as above, then the chunks' partial sums ascending
+ *   dbeta, G  per 32-row tile the rows in the accumulator's order (i & 3) + 8 (i >> 2), i < 16, lane half 0 then + half 1; a workgroup adds
+ *             its tiles (tile = workgroup + t * min(tiles, 1024)) ascending; lane t of a wave adds workgroups t, t + 64, .. ascending and
+ *             the 64 lane sums go through a halving tree
+ *   dpoints2  the entries (i, q) ascending, fmaf(w, dx_0, sum)
+ * Limits: the forward's (anything else is refused with AMPNET_E_ARG).  Exact fp32 MFMA whatever the matrix precision is.            */
+size_t ampnet_fp_backward_workspace_bytes(int D1, int D2, int n_clouds, int n, const int *cout_host, int L);
+int ampnet_fp_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                           const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                           const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
+                           size_t workspace_bytes, void *stream);
 
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =

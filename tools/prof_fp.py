@@ -2,7 +2,11 @@
 B = 16, N = 8192 fine points, S = 1024 coarse points, D1 = 0, D2 = 128, MLP [128, 128, 128]) against what torch-ROCm offers for the same
 layer: cdist + topk, gather, weighted sum, conv1d + BatchNorm1d (eval) + relu.
 python3 tools/prof_fp.py [steps] [warmup]  -- HIP events, warm-up first, each of the three in a timed loop of its own, all in this process;
-prints one JSON line.  Under rocprofv3 (counters in a run of their own) the kernels to look for are three_nn_kernel and fp_forward_kernel."""
+prints one JSON line.  Under rocprofv3 (counters in a run of their own) the kernels to look for are three_nn_kernel and fp_forward_kernel.
+The backward leg, same shape, same inputs, same process: the fused backward (ampnet_fp_backward_f32: sa_fold_kernel, fp_backward_kernel,
+fp_wgrad_kernel + fp_wgrad_reduce_kernel per layer, fp_scatter_kernel, fp_bwd_finalize_kernel) against torch.autograd's backward of the
+torch composition below on the SAME neighbours (graph built once and retained, only the backward is timed); the two are timed in
+alternating rounds and every round is reported."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -65,6 +69,30 @@ with torch.no_grad():
     err_own = float((out - torch_layer()).abs().max())
     t_idx = torch.cdist(fine, coarse).topk(3, dim=-1, largest=False)[1]
     other = float((t_idx.sort(-1)[0] != idx.long().sort(-1)[0]).any(-1).float().mean())
+
+# ---- the backward leg -----------------------------------------------------------------------------------------------------------------
+dout = torch.from_numpy(synth.uniform(212, (B, N, MLP[-1]), -1.0, 1.0)).to(dev)
+bws = torch.empty(L.fp_backward_workspace_bytes(D1, D2, B, N, MLP), dtype=torch.uint8, device=dev)
+dfeats = torch.empty_like(feats)
+grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
+fused_bwd = lambda: L.fp_backward_f32(None, feats, idx, dist2, layers, [1e-5] * len(MLP), dout, None, dfeats, grads, bws)
+leaves = [feats.requires_grad_(True)] + [t.requires_grad_(True) for layer in layers for t in layer[:4]]
+t_out = torch_layer((idx, dist2))
+torch_bwd = lambda: torch.autograd.grad(t_out, leaves, dout, retain_graph=True)
+rounds = [(timed(fused_bwd), timed(torch_bwd)) for _ in range(3)]
+t_grads = torch_bwd()
+fused_bwd()
+rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
+bwd_diff = {"dpoints2": rel(dfeats, t_grads[0])}
+for l in range(len(MLP)):
+    for q, name in enumerate(("dW", "dbias", "dgamma", "dbeta")):
+        bwd_diff[f"{name}{l}"] = rel(grads[l][q], t_grads[1 + 4 * l + q])
+for t in leaves:
+    t.requires_grad_(False)
+fb_ms, tb_ms = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
+# useful flops of the backward: the recomputed forward (all layers), dx = dz W and dW = dz^T x per layer, the interpolation and its scatter
+bwd_flops = 2.0 * B * N * (3 * sum(a * b for a, b in zip([D1 + D2] + MLP[:-1], MLP)) + 2 * 3 * D2)
+
 w_bytes = sum(sum(t.numel() for t in layer) for layer in layers) * 4
 # the algorithmic bytes of the fused forward: the coarse features once, the neighbours and distances, the weights, the output
 algo = B * S * D2 * 4 + B * N * 3 * 8 + w_bytes + B * N * MLP[-1] * 4
@@ -74,4 +102,8 @@ print(json.dumps({"shape": {"B": B, "N": N, "S": S, "D1": D1, "D2": D2, "mlp": M
                   "torch_over_three_nn_plus_fused": round(torch_ms / (nn_ms + fp_ms), 2),
                   "fp_algorithmic_bytes": algo, "fp_GBps_at_algorithmic_bytes": round(algo / (fp_ms * 1e-3) / 1e9, 1),
                   "fp_useful_TFLOPs": round(flops / (fp_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch_on_the_same_neighbours": err_same,
-                  "max_abs_diff_vs_torch_on_its_own_neighbours": err_own, "rows_where_torch_picks_other_neighbours": other}))
+                  "max_abs_diff_vs_torch_on_its_own_neighbours": err_own, "rows_where_torch_picks_other_neighbours": other,
+                  "fp_backward_ms": round(fb_ms, 4), "torch_backward_ms": round(tb_ms, 4), "torch_backward_over_fused": round(tb_ms / fb_ms, 2),
+                  "backward_rounds_ms_fused_torch": [[round(a, 4), round(b, 4)] for a, b in rounds],
+                  "fp_backward_useful_TFLOPs": round(bwd_flops / (fb_ms * 1e-3) / 1e12, 2), "fp_backward_workspace_MB": round(bws.numel() / 1e6, 1),
+                  "backward_max_rel_diff_vs_torch": bwd_diff, "backward_hbm_counters": "not measured"}))

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 
@@ -311,3 +311,67 @@ def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, d
                                           ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ptr(workspace), ctypes.c_size_t(have),
                                           stream_ptr(points2.device))
     check(rc, "ampnet_fp_backward_f32")
+
+
+# ---- the set-abstraction backward (include/ampnet_hip.h: ampnet_sa_backward_f32) -------------------------------------------------------
+def sa_backward_workspace_bytes(D, B, S, nsample, couts):
+    """Device bytes sa_backward_f32 needs for feats [B, N, D], S centres per cloud, groups of nsample and layers of widths `couts`
+    (include/ampnet_hip.h: ampnet_sa_backward_workspace_bytes); a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    couts = [int(c) for c in couts]
+    fn = lib().ampnet_sa_backward_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    need = fn(int(D), int(B), int(S), int(nsample), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
+    if not need:
+        check(-1, "ampnet_sa_backward_workspace_bytes")
+    return int(need)
+
+
+def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, grads, workspace, arg_out=None):
+    """The backward of sa_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; dout [B, S, cout_last];
+    dfeats [B, N, D] written, or None when it is not wanted (always None when feats is None); grads: per layer the four contiguous float32
+    GPU tensors (dW [cout, cin], dbias [cout], dgamma [cout], dbeta [cout]), written; workspace: sa_backward_workspace_bytes(...) GPU
+    bytes; arg_out: int32 [B, S, cout_last] or None, the row of each group that the max selected."""
+    L = len(layers)
+    for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
+                        ("feats", feats, torch.float32), ("dout", dout, torch.float32), ("dfeats", dfeats, torch.float32),
+                        ("arg_out", arg_out, torch.int32)):
+        if t is None and name in ("xyz", "centres", "group_idx", "dout"):
+            raise AmpnetError(f"sa_backward: {name} is None, it must be a {dt} GPU tensor")
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt):
+            raise AmpnetError(f"sa_backward: {name} must be a {dt} GPU tensor")
+    if xyz.dim() != 3 or xyz.shape[2] < 3:
+        raise AmpnetError(f"sa_backward: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
+    B, N, ld = xyz.shape
+    if centres.dim() != 2 or centres.shape[0] != B or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != tuple(centres.shape) \
+            or (feats is not None and (feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N))):
+        raise AmpnetError(f"sa_backward: centres [B, S], group_idx [B, S, nsample], feats [B, N, D] do not agree with xyz {tuple(xyz.shape)}")
+    S, nsample = centres.shape[1], group_idx.shape[2]
+    D = 0 if feats is None else feats.shape[2]
+    if feats is None and dfeats is not None:
+        raise AmpnetError(f"sa_backward: dfeats must be None when feats is (D = 0), got {tuple(dfeats.shape)}")
+    if dfeats is not None and tuple(dfeats.shape) != tuple(feats.shape):
+        raise AmpnetError(f"sa_backward: dfeats {tuple(dfeats.shape)} must have the shape of feats {tuple(feats.shape)}")
+    table, couts, epss = _mlp_tables("sa_backward", layers, 3 + D, eps, workspace, 0)
+    want = (B, S, int(layers[-1][0].shape[0])) if L else None
+    if L and tuple(dout.shape) != want:
+        raise AmpnetError(f"sa_backward: dout {tuple(dout.shape)} must be [B, S, cout_last] = {list(want)}")
+    if L and arg_out is not None and tuple(arg_out.shape) != want:
+        raise AmpnetError(f"sa_backward: arg_out {tuple(arg_out.shape)} must be [B, S, cout_last] = {list(want)}")
+    if len(grads) != L:
+        raise AmpnetError(f"sa_backward: grads has {len(grads)} entries for {L} layers")
+    for i, (layer, g) in enumerate(zip(layers, grads)):
+        wantg = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
+        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, wantg)):
+            raise AmpnetError(f"sa_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {wantg}, "
+                              f"got {[tuple(t.shape) for t in g]}")
+    need = sa_backward_workspace_bytes(D, B, S, nsample, [int(layer[0].shape[0]) for layer in layers])
+    have = workspace.numel() * workspace.element_size()
+    if have < need:
+        raise AmpnetError(f"sa_backward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
+    gtensors = [t for g in grads for t in g]
+    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss, L,
+                                          ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ptr(workspace), ctypes.c_size_t(have),
+                                          stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_backward_f32")

@@ -216,3 +216,45 @@ def fp_apply(module, p1, p2, idx, dist2, fold_ws):
     tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
                for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
     return _FpFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, p1, p2, idx, dist2, *tensors)
+
+
+class _SaFn(torch.autograd.Function):
+    """One fused set-abstraction layer with BatchNorm's running statistics frozen (pointnet2_utils.PointNetSetAbstraction with grad=True).
+    tensors: per layer conv weight [out, in, 1, 1], conv bias, BatchNorm weight, bias, running_mean, running_var.  The forward is the eval
+    forward, unchanged, and keeps its inputs only: the backward kernel recomputes the activations and the max's choice
+    (csrc/set_abstraction_bwd.hip).  Exact fp32 whatever the matrix precision is, so there is no precision scope to carry over."""
+
+    @staticmethod
+    def forward(ctx, eps, fold_ws, x, centres, group_idx, feats, *tensors):
+        layers = _fp_layers(tensors)
+        out = torch.empty((x.shape[0], centres.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
+        _lib.sa_forward_f32(x, centres, group_idx, feats, layers, eps, out, fold_ws)
+        ctx.save_for_backward(x, centres, group_idx, feats, *tensors)        # (inputs only: see the note in _EncoderFn.forward)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, centres, group_idx, feats, *tensors = ctx.saved_tensors
+        layers = _fp_layers(tensors)
+        need_grad = ctx.needs_input_grad
+        dfeats = torch.empty_like(feats) if feats is not None and need_grad[5] else None
+        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
+        need = _lib.sa_backward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], centres.shape[1], group_idx.shape[2],
+                                                [layer[0].shape[0] for layer in layers])
+        _lib.sa_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, dout.contiguous().float(), dfeats, grads,
+                             torch.empty(need, dtype=torch.uint8, device=x.device), arg_out=None)
+        ret = [None, None, None, None, None, dfeats]
+        for l, g in enumerate(grads):
+            w = tensors[6 * l]
+            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3], None, None)):     # the conv weight keeps its [out, in, 1, 1]
+                ret.append(t if t is not None and need_grad[6 + 6 * l + q] else None)
+        return tuple(ret)
+
+
+def sa_apply(module, x, centres, group_idx, feats, fold_ws):
+    """Grad-mode forward of a PointNetSetAbstraction block on point-major rows: x [B, N, 3], centres [B, S] and group_idx [B, S, nsample]
+    int32, feats [B, N, D] or None -> [B, S, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters."""
+    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
+               for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+    return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *tensors)

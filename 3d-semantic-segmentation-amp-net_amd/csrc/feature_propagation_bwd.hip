@@ -25,23 +25,21 @@
 //       The wave also stores x_l and dz_l of its rows to the workspace (dW below) and adds its tiles' per-channel sums of dy and dy a
 //       (rows in the accumulator's order, lane half 0 before half 1, tiles in ascending order) into ITS OWN row of a partials array in
 //       global memory: every element is read and written by the same lane only.
-//   fp_wgrad_kernel, fp_wgrad_reduce_kernel   dW_l = dz_l^T x_l as a split-K MFMA GEMM over the rows: a wave takes a 32 x 128 block of dW and
-//       one chunk of rows (ascending, k-step i of half h takes row k0 + 2 i + h), the chunks' partials are added in ascending chunk order.
-//       The project's pw_wgrad / sgemm_wgrad_bias are built around windows and slots of the AMP-Net encoder (per-slot partials, BatchNorm
-//       constants folded in); this layer has neither, so it gets a kernel of its own.
+//   fp_wgrad_kernel, fp_wgrad_reduce_kernel   dW_l = dz_l^T x_l as a split-K MFMA GEMM over the rows (mlp_bwd.hip, shared with the
+//       set-abstraction backward): the chunks' partials are added in ascending chunk order.
 //   fp_scatter_kernel       dpoints2 as a GATHER: one wave per coarse point j scans its cloud's n k neighbour entries in ascending order, 64
 //       at a time, takes the entries equal to j by ballot and adds w_k dx_0[i, D1:] in ascending (i, k) order, a lane per column.  The
 //       weights are the forward's (fp_interp_weights).  No float atomics; a coarse point nobody picked gets zeros.
-//   fp_bwd_finalize_kernel  adds the workgroups' partials in a fixed order (a wave per channel) and derives dbeta, dgamma and dbias.
+//   fp_bwd_finalize_kernel  adds the workgroups' partials in a fixed order (a wave per channel) and derives dbeta, dgamma and dbias
+//       (mlp_bwd.hip).
 //
 // Every order above is a function of the shape alone: two runs give the same bits.  Exact fp32 MFMA whatever the matrix precision is.
 #include "fp_rows.h"
+#include "mlp_bwd.h"
 
 namespace ampnet {
 
 constexpr int FPB_MAX_GRID = 1024;        // workgroups (= rows of the partials array) of fp_backward_kernel
-constexpr int FPB_MAX_CHUNKS = 256;       // split-K chunks of fp_wgrad_kernel
-constexpr int FPB_MIN_CHUNK_ROWS = 64;
 
 struct FpBwdPlan {
     int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];   // tile X_l: float offset in LDS, odd row stride
@@ -49,10 +47,6 @@ struct FpBwdPlan {
     int ldxs[MLP_MAX_LAYERS];                                  // row stride of x_l in the workspace: cin_l rounded up to 32 (zeros)
     int sum_c;                                                 // sum of cout_l; layer l's channels start at fold_off[l] / 2
     float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts;
-};
-
-struct FpBwdFin {
-    float *dbias[MLP_MAX_LAYERS], *dgamma[MLP_MAX_LAYERS], *dbeta[MLP_MAX_LAYERS];
 };
 
 // The accumulators of layer l on the wave's tile x, NT column tiles from n0, in the forward's order (mlp_tiles<NT, K_QUADS, VEC>), and the
@@ -164,13 +158,6 @@ __device__ __forceinline__ void fpb_dgrad(const float *d, int ldd, const float *
     }
 }
 
-// the wave's tile [32][ld] -> rows < rows of a global array with row stride ldg (columns past `valid` as zeros)
-__device__ __forceinline__ void fpb_store_rows(const float *tile, int ld, int valid, float *__restrict__ g, int ldg, int rows, int lane)
-{
-    for (int t = 0; t < rows; ++t)
-        for (int c = lane; c < ldg; c += 64) g[(size_t)t * ldg + c] = c < valid ? tile[t * ld + c] : 0.0f;
-}
-
 __global__ __launch_bounds__(64) void fp_backward_kernel(MlpPlan p, FpBwdPlan b, const float *__restrict__ points1, int D1,
                                                         const float *__restrict__ points2, int D2, int n, int s,
                                                         const int32_t *__restrict__ idx, const float *__restrict__ dist2, int k,
@@ -231,50 +218,6 @@ __global__ __launch_bounds__(64) void fp_backward_kernel(MlpPlan p, FpBwdPlan b,
     }
 }
 
-// dW partial of one chunk of rows: block (c0 / 128, o0 / 32, chunk), one wave; part [chunks][cout][ldxs]
-__global__ __launch_bounds__(64) void fp_wgrad_kernel(const float *__restrict__ dz, int cout, const float *__restrict__ xs, int ldxs, long long M,
-                                                     int chunk_rows, float *__restrict__ part)
-{
-    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-    const int c0 = blockIdx.x * 128, o0 = blockIdx.y * 32;
-    const long long k_begin = (long long)blockIdx.z * chunk_rows, k_end = min(M, k_begin + chunk_rows);
-    f32x16 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    for (long long k0 = k_begin; k0 < k_end; k0 += 8) {
-        float av[4], bv[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const long long row = k0 + 2 * i + h;
-            av[i] = row < k_end ? dz[(size_t)row * cout + o0 + r] : 0.0f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) bv[t][i] = row < k_end && c0 + 32 * t < ldxs ? xs[(size_t)row * ldxs + c0 + 32 * t + r] : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
-    float *dst = part + (size_t)blockIdx.z * cout * ldxs;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-        if (c0 + 32 * t < ldxs)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dst[(size_t)(o0 + (i & 3) + 8 * (i >> 2) + 4 * h) * ldxs + c0 + 32 * t + r] = acc[t][i];
-}
-
-__global__ void fp_wgrad_reduce_kernel(const float *__restrict__ part, int chunks, int cout, int cin, int ldxs, float *__restrict__ dW)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= cout * cin) return;
-    const int o = e / cin, c = e - o * cin;
-    float v = 0.0f;
-    for (int q = 0; q < chunks; ++q) v += part[((size_t)q * cout + o) * ldxs + c];
-    dW[e] = v;
-}
-
 __global__ __launch_bounds__(64) void fp_scatter_kernel(const float *__restrict__ dx0, int D2, int n, int s, const int32_t *__restrict__ idx,
                                                        const float *__restrict__ dist2, int k, float *__restrict__ dpoints2)
 {
@@ -316,31 +259,6 @@ __global__ __launch_bounds__(64) void fp_scatter_kernel(const float *__restrict_
         if (lane + 64 * u < D2) dst[lane + 64 * u] = acc[u];
 }
 
-// next to sa_fold_kernel: the same parameters, the other direction.  One wave per channel: lane t adds the partials of workgroups t, t + 64, ..
-// in ascending order, the 64 lane sums go through a fixed halving tree (32, 16, .. 1).
-__global__ __launch_bounds__(256) void fp_bwd_finalize_kernel(MlpPlan p, MlpFold f, FpBwdFin g, const float *__restrict__ fold,
-                                                             const float *__restrict__ parts, int n_parts, int sum_c)
-{
-    const int lane = threadIdx.x & 63, ch = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (ch >= sum_c) return;                      // (the whole wave)
-    int l = 0;
-    while (l + 1 < p.L && ch >= p.fold_off[l + 1] / 2) ++l;
-    const int c = ch - p.fold_off[l] / 2;
-    float dbeta = 0.0f, G = 0.0f;
-    for (int q = lane; q < n_parts; q += 64) {
-        dbeta += parts[(size_t)q * 2 * sum_c + ch];
-        G += parts[(size_t)q * 2 * sum_c + sum_c + ch];
-    }
-    for (int off = 32; off; off >>= 1) {
-        dbeta += __shfl_down(dbeta, off);
-        G += __shfl_down(G, off);
-    }
-    if (lane) return;
-    g.dbeta[l][c] = dbeta;
-    g.dgamma[l][c] = fmaf(f.bias[l][c] - f.mean[l][c], dbeta, G) / sqrtf(f.var[l][c] + f.eps[l]);
-    g.dbias[l][c] = fold[p.fold_off[l] + c] * dbeta;
-}
-
 // what both entry points derive from the shape: the launch sizes and the workspace layout (float offsets, each a multiple of 64)
 struct FpBwdShape {
     long long M;
@@ -363,10 +281,7 @@ static int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, cons
     sh.M = (long long)n_clouds * n;
     sh.n_tiles = n_clouds * sh.tiles_per_cloud;
     sh.grid = sh.n_tiles < FPB_MAX_GRID ? sh.n_tiles : FPB_MAX_GRID;
-    const long long per = (sh.M + FPB_MAX_CHUNKS - 1) / FPB_MAX_CHUNKS;
-    sh.chunk_rows = (int)((per + 7) / 8 * 8);
-    if (sh.chunk_rows < FPB_MIN_CHUNK_ROWS) sh.chunk_rows = FPB_MIN_CHUNK_ROWS;
-    sh.chunks = (int)((sh.M + sh.chunk_rows - 1) / sh.chunk_rows);
+    fpb_chunk_rule(sh.M, sh.chunk_rows, sh.chunks);
     size_t off = align_up((size_t)AMPNET_FP_WORKSPACE_BYTES / sizeof(float), 64), wmax = 0;
     for (int l = 0; l < L; ++l) {
         const int cout = cout_host[l];
@@ -468,18 +383,11 @@ extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float 
     if (rc != AMPNET_OK) return rc;
     float *wpart = ws + sh.off_wpart;
     for (int l = 0; l < L; ++l) {
-        hipLaunchKernelGGL(fp_wgrad_kernel, dim3(cdiv(sh.ldxs[l], 128), p.cout[l] / 32, sh.chunks), dim3(64), 0, st, b.dz[l], p.cout[l], b.xs[l],
-                           sh.ldxs[l], sh.M, sh.chunk_rows, wpart);
-        rc = check_launch("fp_wgrad_kernel");
-        if (rc != AMPNET_OK) return rc;
-        hipLaunchKernelGGL(fp_wgrad_reduce_kernel, dim3(cdiv(p.cout[l] * p.cin[l], 256)), dim3(256), 0, st, wpart, sh.chunks, p.cout[l], p.cin[l],
-                           sh.ldxs[l], grads_host[4 * l]);
-        rc = check_launch("fp_wgrad_reduce_kernel");
+        rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, wpart, grads_host[4 * l], st);
         if (rc != AMPNET_OK) return rc;
     }
     hipLaunchKernelGGL(fp_scatter_kernel, dim3(n_clouds * s), dim3(64), 0, st, b.dx0, D2, n, s, idx, dist2, k, dpoints2);
     rc = check_launch("fp_scatter_kernel");
     if (rc != AMPNET_OK) return rc;
-    hipLaunchKernelGGL(fp_bwd_finalize_kernel, dim3(cdiv(sh.sum_c, 4)), dim3(256), 0, st, p, f, g, ws, b.parts, sh.grid, sh.sum_c);
-    return check_launch("fp_bwd_finalize_kernel");
+    return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);
 }

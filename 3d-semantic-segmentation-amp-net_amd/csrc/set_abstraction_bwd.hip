@@ -1,0 +1,454 @@
+// set_abstraction_bwd.hip -- the backward of one fused set-abstraction layer with BatchNorm's running statistics frozen (C ABI:
+// ampnet_sa_backward_f32, ampnet_sa_backward_workspace_bytes).  The math per layer is that of feature_propagation_bwd.hip's header
+// (dy, dbeta, G, dgamma, dz, dbias, dW, dx); the rows are the forward's, [xyz[idx_t] - xyz[centre], feats[idx_t]], and dx of the last layer
+// is `dout` routed through the max over the group.  The forward keeps nothing, so everything is recomputed.  Kernels on the caller's stream:
+//
+//   fold (sa_fold_kernel)   scale and shift, as in the forward.
+//   sa_backward_kernel      A workgroup is ONE wave and a wave owns a group, as in the forward.  It gathers the group's rows with the
+//       forward's code into tile X_0 (R = 32 or 64 rows, rows past nsample repeat row 0), runs layers 0 .. L-2 forward with the forward's own
+//       code (mlp_dispatch<K_PAIRS>, weights read through L2) into tiles X_1 .. X_{L-1} and keeps ALL of them, then walks the layers
+//       backward as fp_backward_kernel does: the accumulators a of layer l are computed AGAIN from X_l in the forward's contraction order
+//       (K_PAIRS: k-step i of lane half h takes k = k0 + 2 i + h; the same bits, so the same ReLU mask and the same max), dx_{l+1} becomes
+//       dz in place in X_{l+1}, and dx_l = dz W overwrites X_l.  L + 1 tiles of R rows: at R = 32 every shape of the forward fits the 160 KB
+//       (cin_0 = 320 with three layers of 256: 140 KB); at R = 64 the shapes whose tiles do not fit are refused.
+//       The max.  In the last layer a lane holds, per row tile, column c of 16 rows in its accumulator; it keeps the largest relu(y), the
+//       LOWEST row that attains it and that row's a while it walks the rows in ascending order (strict >), over both row tiles; the two
+//       lane halves are combined with one __shfl_xor(., 32) each, the lower row winning a tie.  Rows past nsample and the slots ball query
+//       filled by repeating its first member are bit-identical to an earlier row and never win.  dz of the last layer is zero except at
+//       (winner, c), where it is dout[g, c] scale if the winner's y > 0: the lane that owns that element writes it.
+//       The wave stores x_l and dz_l of its nsample real rows to the workspace (dW below) and adds its per-channel sums of dy and dy a
+//       (rows in the accumulator's order, row tiles ascending, lane half 0 before half 1, groups ascending) into ITS OWN row of a partials
+//       array: every element is read and written by the same lane only.  dx_0's columns [3, cin_0) go to the workspace for the gather
+//       below; when the caller wants no dfeats, layer 0's dx is not computed at all.
+//   fp_wgrad_kernel, fp_wgrad_reduce_kernel, fp_bwd_finalize_kernel   mlp_bwd.hip, shared with the feature-propagation backward.
+//   sa_dfeats_kernel        dfeats as a GATHER: one wave per point j scans its cloud's s nsample group entries in ascending order, 64 at a
+//       time, takes the entries equal to j (clamped as in the forward) by ballot and adds dx_0[entry, 3:] in ascending entry order, a lane
+//       per column.  No float atomics; a point in no group gets zeros.
+//
+// Every order above is a function of the shape alone: two runs give the same bits.  Exact fp32 MFMA whatever the matrix precision is.
+#include "mlp_bwd.h"
+
+namespace ampnet {
+
+constexpr int SAB_MAX_GRID = 2048;        // workgroups (= rows of the partials array) of sa_backward_kernel
+
+struct SaBwdPlan {
+    int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];   // tile X_l: float offset in LDS, odd row stride
+    int ldxs[MLP_MAX_LAYERS];                                  // row stride of x_l in the workspace: cin_l rounded up to 32 (zeros)
+    int sum_c;                                                 // sum of cout_l; layer l's channels start at fold_off[l] / 2
+    float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts;
+};
+
+// the accumulators of NT column tiles from n0 on the 32 rows whose operand pointer is xr = x + (m0 + r) ldx + h: the forward's
+// mlp_tiles<NT, K_PAIRS, false> on weights read from global memory
+template <int NT>
+__device__ __forceinline__ void sab_accumulate(f32x16 (&acc)[NT], const float *xr, const float *__restrict__ w, int cin, int kp, int n0, int r,
+                                               int h)
+{
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    for (int k0 = 0; k0 < kp; k0 += 8) {
+        float av[4], bv[NT][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = xr[k0 + 2 * i];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float *wr = w + (size_t)(n0 + 32 * t + r) * cin + k0 + h;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bv[t][i] = k0 + h + 2 * i < cin ? wr[2 * i] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+}
+
+// A layer below the last: d [R][ldd] holds dx_{l+1} on entry and dz on exit; dz_ws: the group's rows of the workspace.
+template <int NT>
+__device__ __forceinline__ void sab_hidden(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
+                                           const float *__restrict__ scale, const float *__restrict__ shift, float *d, int ldd, int R,
+                                           int nsample, float *__restrict__ dz_ws, float *part_b, float *part_g, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    float sc[NT], sh[NT], sb[NT], sg[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        sc[t] = scale[n0 + 32 * t + r];
+        sh[t] = shift[n0 + 32 * t + r];
+        sb[t] = sg[t] = 0.0f;
+    }
+    for (int m0 = 0; m0 < R; m0 += 32) {
+        f32x16 acc[NT];
+        sab_accumulate<NT>(acc, x + (m0 + r) * ldx + h, w, cin, kp, n0, r, h);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int col = n0 + 32 * t + r;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const float a = acc[t][i];
+                const float dy = fmaf(a, sc[t], sh[t]) > 0.0f ? d[row * ldd + col] : 0.0f;
+                sb[t] += dy;
+                sg[t] = fmaf(dy, a, sg[t]);
+                const float dzv = dy * sc[t];
+                d[row * ldd + col] = dzv;
+                if (row < nsample) dz_ws[(size_t)row * cout + col] = dzv;
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = n0 + 32 * t + r;
+        const float ob = __shfl_down(sb[t], 32), og = __shfl_down(sg[t], 32);
+        if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
+            part_b[col] += sb[t] + ob;
+            part_g[col] += sg[t] + og;
+        }
+    }
+}
+
+// The last layer: the max over the group's rows, its row, and dz = dout scale at that row alone.  dout_g, arg_g: the group's row of
+// dout / arg_out (arg_g may be null).
+template <int NT>
+__device__ __forceinline__ void sab_last(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
+                                         const float *__restrict__ scale, const float *__restrict__ shift, float *d, int ldd, int R,
+                                         int nsample, const float *__restrict__ dout_g, float *__restrict__ dz_ws, float *part_b,
+                                         float *part_g, int32_t *__restrict__ arg_g, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    float sc[NT], sh[NT], best[NT], ba[NT];
+    int brow[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        sc[t] = scale[n0 + 32 * t + r];
+        sh[t] = shift[n0 + 32 * t + r];
+        best[t] = -INFINITY;
+        ba[t] = 0.0f;
+        brow[t] = 0;
+    }
+    for (int m0 = 0; m0 < R; m0 += 32) {
+        f32x16 acc[NT];
+        sab_accumulate<NT>(acc, x + (m0 + r) * ldx + h, w, cin, kp, n0, r, h);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int col = n0 + 32 * t + r;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;              // ascending in (m0, i): `>` keeps the lowest row
+                const float a = acc[t][i], y = fmaxf(fmaf(a, sc[t], sh[t]), 0.0f);
+                if (y > best[t]) {
+                    best[t] = y;
+                    brow[t] = row;
+                    ba[t] = a;
+                }
+                d[row * ldd + col] = 0.0f;
+                if (row < nsample) dz_ws[(size_t)row * cout + col] = 0.0f;
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = n0 + 32 * t + r;
+        const float ob = __shfl_xor(best[t], 32), oa = __shfl_xor(ba[t], 32);
+        const int orow = __shfl_xor(brow[t], 32);
+        if (ob > best[t] || (ob == best[t] && orow < brow[t])) {
+            best[t] = ob;
+            brow[t] = orow;
+            ba[t] = oa;
+        }
+        // both halves agree now; rows past nsample repeat row 0 and lose the tie to it
+        const float dy = best[t] > 0.0f ? dout_g[col] : 0.0f, dzv = dy * sc[t];
+        if ((((brow[t] & 31) >> 2) & 1) == h) {   // the lane that wrote this element's zero above
+            d[brow[t] * ldd + col] = dzv;
+            if (brow[t] < nsample) dz_ws[(size_t)brow[t] * cout + col] = dzv;
+        }
+        if (h == 0) {
+            part_b[col] += dy;
+            part_g[col] += dy * ba[t];
+            if (arg_g) arg_g[col] = brow[t];
+        }
+    }
+}
+
+// dx = dz W for NT column tiles of the layer's INPUT from c0 on the 32 rows of d [32][ldd] (fpb_dgrad's lane map and order: o ascending
+// in blocks of 8, k-step i of lane half h takes o = o0 + 2 i + h).  Results go to tile `xo` (l >= 1) or, xo == nullptr, columns
+// [3, cin) of the rows < rows to dx0 [.][D] (layer 0).
+template <int NT>
+__device__ __forceinline__ void sab_dgrad(const float *d, int ldd, const float *__restrict__ w, int cin, int cout, int c0, float *xo, int ldxo,
+                                          float *__restrict__ dx0, int D, int rows, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    const float *dr = d + r * ldd + h;
+    for (int o0 = 0; o0 < cout; o0 += 8) {
+        float av[4], bv[NT][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = dr[o0 + 2 * i];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int c = c0 + 32 * t + r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bv[t][i] = c < cin ? w[(size_t)(o0 + 2 * i + h) * cin + c] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int c = c0 + 32 * t + r;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            if (xo) {
+                if (c < cin) xo[row * ldxo + c] = acc[t][i];
+            } else if (row < rows && c >= 3 && c < cin) {
+                dx0[(size_t)row * D + c - 3] = acc[t][i];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void sa_backward_kernel(MlpPlan p, SaBwdPlan b, const float *__restrict__ xyz, int n, int ld,
+                                                        const int32_t *__restrict__ centres, int s, const int32_t *__restrict__ group_idx,
+                                                        int nsample, const float *__restrict__ feats, int D, const float *__restrict__ fold,
+                                                        const float *__restrict__ dout, int n_groups, int want_dx0,
+                                                        int32_t *__restrict__ arg_out)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    const int lane = threadIdx.x;
+    const int L = p.L, R = p.R;
+    const int cin0 = p.cin[0], kp0 = p.kp[0], cout_last = p.cout[L - 1];
+    float *part_b = b.parts + (size_t)blockIdx.x * 2 * b.sum_c, *part_g = part_b + b.sum_c;
+    if (lane < 32)
+        for (int c = lane; c < b.sum_c; c += 32) part_b[c] = part_g[c] = 0.0f;       // channel c belongs to lane c % 32, here and below
+    for (int g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        const int cloud_i = g / s;
+        const float *cloud = xyz + (size_t)cloud_i * n * ld;
+        const float *fcloud = feats ? feats + (size_t)cloud_i * n * D : nullptr;
+        const int cidx = min(max(centres[g], 0), n - 1);
+        const float cx = cloud[(size_t)cidx * ld], cy = cloud[(size_t)cidx * ld + 1], cz = cloud[(size_t)cidx * ld + 2];
+        // the forward's gather: lane t holds the point of row t, rows past nsample repeat row 0
+        const int my_idx = min(max(group_idx[(size_t)g * nsample + (lane < nsample ? lane : 0)], 0), n - 1);
+        float *x0 = s_mem + b.off_x[0];
+        for (int e = lane; e < R * kp0; e += 64) {
+            const int t = e / kp0, c = e - t * kp0;
+            const int j = __shfl(my_idx, t);
+            float v = 0.0f;
+            if (c < 3) v = cloud[(size_t)j * ld + c] - (c == 0 ? cx : c == 1 ? cy : cz);
+            else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
+            x0[t * b.ld_x[0] + c] = v;
+        }
+        wave_lds_sync();
+        const size_t grow = (size_t)g * nsample;
+        fpb_store_rows(x0, b.ld_x[0], kp0, b.xs[0] + grow * b.ldxs[0], b.ldxs[0], nsample, lane);
+        for (int l = 0; l + 1 < L; ++l) {
+            float *y = s_mem + b.off_x[l + 1];
+            mlp_dispatch<K_PAIRS>(p, l, R, s_mem, s_mem + b.off_x[l], b.ld_x[l], fold, MlpToTile{y, b.ld_x[l + 1]}, nullptr, lane);
+            wave_lds_sync();
+            fpb_store_rows(y, b.ld_x[l + 1], p.cout[l], b.xs[l + 1] + grow * b.ldxs[l + 1], b.ldxs[l + 1], nsample, lane);
+        }
+        for (int l = L - 1; l >= 0; --l) {
+            float *x = s_mem + b.off_x[l], *d = s_mem + b.off_x[l + 1];
+            const int ldx = b.ld_x[l], ldd = b.ld_x[l + 1], cin = p.cin[l], cout = p.cout[l], ch = p.fold_off[l] / 2;
+            const float *scale = fold + p.fold_off[l], *shift = scale + cout;
+            float *dz_ws = b.dz[l] + grow * cout;
+            int n0 = 0;
+            if (l == L - 1) {
+                const float *dout_g = dout + (size_t)g * cout_last;
+                int32_t *arg_g = arg_out ? arg_out + (size_t)g * cout_last : nullptr;
+                for (; n0 + 128 <= cout; n0 += 128)
+                    sab_last<4>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, R, nsample, dout_g, dz_ws, part_b + ch, part_g + ch, arg_g, lane);
+                for (; n0 < cout; n0 += 32)
+                    sab_last<1>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, R, nsample, dout_g, dz_ws, part_b + ch, part_g + ch, arg_g, lane);
+            } else {
+                for (; n0 + 128 <= cout; n0 += 128)
+                    sab_hidden<4>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, R, nsample, dz_ws, part_b + ch, part_g + ch, lane);
+                for (; n0 < cout; n0 += 32)
+                    sab_hidden<1>(x, ldx, p.w[l], cin, p.kp[l], cout, n0, scale, shift, d, ldd, R, nsample, dz_ws, part_b + ch, part_g + ch, lane);
+            }
+            wave_lds_sync();
+            if (l == 0 && !want_dx0) break;       // (wave-uniform) nobody asked for dfeats: dx_0 is not needed
+            for (int m0 = 0; m0 < R; m0 += 32) {
+                float *xo = l ? x + m0 * ldx : nullptr;
+                float *dx0 = b.dx0 + (grow + m0) * D;
+                const float *dm = d + m0 * ldd;
+                int c0 = 0;
+                for (; c0 + 128 <= cin; c0 += 128) sab_dgrad<4>(dm, ldd, p.w[l], cin, cout, c0, xo, ldx, dx0, D, nsample - m0, lane);
+                for (; c0 < cin; c0 += 32) sab_dgrad<1>(dm, ldd, p.w[l], cin, cout, c0, xo, ldx, dx0, D, nsample - m0, lane);
+            }
+            wave_lds_sync();
+        }
+        wave_lds_sync();                          // the next group's gather overwrites X_0
+    }
+}
+
+__global__ __launch_bounds__(64) void sa_dfeats_kernel(const float *__restrict__ dx0, int D, int n, int s, int nsample,
+                                                      const int32_t *__restrict__ group_idx, float *__restrict__ dfeats)
+{
+    const int lane = threadIdx.x;
+    const int cloud_i = blockIdx.x / n, j = blockIdx.x - cloud_i * n;
+    const long long total = (long long)s * nsample;
+    const int32_t *ic = group_idx + (size_t)cloud_i * total;
+    const float *gx = dx0 + (size_t)cloud_i * total * D;
+    constexpr int U = (AMPNET_SA_MAX_CIN + 63) / 64;
+    float acc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] = 0.0f;
+    for (long long e0 = 0; e0 < total; e0 += 64) {
+        const long long e = e0 + lane;
+        const bool hit = e < total && min(max(ic[e], 0), n - 1) == j;
+        unsigned long long mask = __ballot(hit);
+        while (mask) {                            // wave-uniform: every lane walks the hits in ascending entry order
+            const int src = __ffsll(mask) - 1;
+            mask &= mask - 1;
+            const float *row = gx + (size_t)(e0 + src) * D;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (lane + 64 * u < D) acc[u] += row[lane + 64 * u];
+        }
+    }
+    float *dst = dfeats + (size_t)blockIdx.x * D;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (lane + 64 * u < D) dst[lane + 64 * u] = acc[u];
+}
+
+// what both entry points derive from the shape: the launch sizes, the LDS tiles and the workspace layout (float offsets, multiples of 64)
+struct SaBwdShape {
+    long long M;
+    int R, n_groups, grid, chunk_rows, chunks, sum_c, lds_floats;
+    int cin[MLP_MAX_LAYERS], ldxs[MLP_MAX_LAYERS], off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];
+    size_t off_parts, off_xs[MLP_MAX_LAYERS], off_dz[MLP_MAX_LAYERS], off_dx0, off_wpart, floats;
+};
+
+static int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SaBwdShape &sh)
+{
+    AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
+    AMPNET_REQUIRE(n_clouds >= 1 && s >= 1, "%s: bad shape n_clouds=%d s=%d", what, n_clouds, s);
+    AMPNET_REQUIRE((long long)n_clouds * s <= 0x7fffffffLL, "%s: n_clouds * s = %lld groups exceed 2^31 - 1", what, (long long)n_clouds * s);
+    AMPNET_REQUIRE(nsample >= 1 && nsample <= AMPNET_SA_MAX_NSAMPLE, "%s: nsample=%d must be in [1, %d]", what, nsample, AMPNET_SA_MAX_NSAMPLE);
+    AMPNET_REQUIRE(L >= 1 && L <= AMPNET_SA_MAX_LAYERS, "%s: L=%d layers, the kernel is built for 1 .. %d", what, L, AMPNET_SA_MAX_LAYERS);
+    AMPNET_REQUIRE(D >= 0 && 3 + D <= AMPNET_SA_MAX_CIN, "%s: cin_0 = 3 + D = %d exceeds %d", what, 3 + D, AMPNET_SA_MAX_CIN);
+    sh = {};
+    sh.R = nsample <= 32 ? 32 : 64;
+    sh.n_groups = n_clouds * s;
+    sh.M = (long long)sh.n_groups * nsample;
+    sh.grid = sh.n_groups < SAB_MAX_GRID ? sh.n_groups : SAB_MAX_GRID;
+    fpb_chunk_rule(sh.M, sh.chunk_rows, sh.chunks);
+    size_t off = align_up((size_t)AMPNET_SA_WORKSPACE_BYTES / sizeof(float), 64), wmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const int cout = cout_host[l];
+        AMPNET_REQUIRE(cout >= 32 && cout <= AMPNET_SA_MAX_COUT && cout % 32 == 0, "%s: layer %d has cout=%d, must be a multiple of 32 in [32, %d]",
+                       what, l, cout, AMPNET_SA_MAX_COUT);
+        sh.cin[l] = l ? cout_host[l - 1] : 3 + D;
+        sh.ldxs[l] = (sh.cin[l] + 31) / 32 * 32;
+        sh.sum_c += cout;
+        if ((size_t)cout * sh.ldxs[l] > wmax) wmax = (size_t)cout * sh.ldxs[l];
+    }
+    // the tiles X_0 .. X_L of R rows
+    for (int l = 0; l <= L; ++l) {
+        sh.ld_x[l] = (l ? cout_host[l - 1] : (3 + D + 7) / 8 * 8) + 1;
+        sh.off_x[l] = sh.lds_floats;
+        sh.lds_floats += sh.R * sh.ld_x[l];
+    }
+    AMPNET_REQUIRE((size_t)sh.lds_floats * sizeof(float) <= (size_t)MLP_LDS_BYTES,
+                   "%s: a wave's %d tiles of %d rows (%zu bytes) exceed the LDS (%d bytes); at nsample <= 32 every shape fits", what, L + 1, sh.R,
+                   (size_t)sh.lds_floats * sizeof(float), MLP_LDS_BYTES);
+    sh.off_parts = off;
+    off += align_up((size_t)sh.grid * 2 * sh.sum_c, 64);
+    for (int l = 0; l < L; ++l) {
+        sh.off_xs[l] = off;
+        off += align_up((size_t)sh.M * sh.ldxs[l], 64);
+        sh.off_dz[l] = off;
+        off += align_up((size_t)sh.M * cout_host[l], 64);
+    }
+    sh.off_dx0 = off;
+    off += align_up((size_t)sh.M * D, 64);
+    sh.off_wpart = off;
+    off += align_up((size_t)sh.chunks * wmax, 64);
+    sh.floats = off;
+    return AMPNET_OK;
+}
+
+}  // namespace ampnet
+
+extern "C" size_t ampnet_sa_backward_workspace_bytes(int D, int n_clouds, int s, int nsample, const int *cout_host, int L)
+{
+    using namespace ampnet;
+    SaBwdShape sh;
+    if (sab_shape("ampnet_sa_backward_workspace_bytes", D, n_clouds, s, nsample, cout_host, L, sh) != AMPNET_OK) return 0;
+    return sh.floats * sizeof(float);
+}
+
+extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                                      int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                                      const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host,
+                                      int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    using namespace ampnet;
+    const char *what = "ampnet_sa_backward_f32";
+    hipStream_t st = (hipStream_t)stream;
+    AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && dout && grads_host, "%s: null pointer", what);
+    AMPNET_REQUIRE(n >= 1 && ld >= 3, "%s: bad shape n=%d ld=%d", what, n, ld);
+    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
+    AMPNET_REQUIRE(D > 0 || dfeats == nullptr, "%s: dfeats must be NULL when D = 0", what);
+    SaBwdShape sh;
+    int rc = sab_shape(what, D, n_clouds, s, nsample, cout_host, L, sh);
+    if (rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE((long long)n_clouds * n <= 0x7fffffffLL, "%s: n_clouds * n = %lld points exceed 2^31 - 1", what, (long long)n_clouds * n);
+    for (int q = 0; q < 4 * L; ++q) AMPNET_REQUIRE(grads_host[q], "%s: null gradient pointer %d of layer %d", what, q % 4, q / 4);
+    AMPNET_REQUIRE(workspace && workspace_bytes >= sh.floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
+                   sh.floats * sizeof(float));
+    MlpPlan p;
+    MlpFold f;
+    if (!mlp_plan_build(what, 3 + D, sh.R, params_host, cout_host, eps_host, L, p, f)) return AMPNET_E_ARG;
+    p.nw = 1;
+    for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // this kernel stages no weights: every layer is read through L2
+    float *ws = static_cast<float *>(workspace);
+    SaBwdPlan b = {};
+    b.sum_c = sh.sum_c;
+    b.parts = ws + sh.off_parts;
+    b.dx0 = ws + sh.off_dx0;
+    for (int l = 0; l <= L; ++l) {
+        b.off_x[l] = sh.off_x[l];
+        b.ld_x[l] = sh.ld_x[l];
+    }
+    FpBwdFin g = {};
+    for (int l = 0; l < L; ++l) {
+        b.ldxs[l] = sh.ldxs[l];
+        b.xs[l] = ws + sh.off_xs[l];
+        b.dz[l] = ws + sh.off_dz[l];
+        g.dbias[l] = grads_host[4 * l + 1];
+        g.dgamma[l] = grads_host[4 * l + 2];
+        g.dbeta[l] = grads_host[4 * l + 3];
+    }
+    static bool attr_set = false;
+    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_backward_kernel), attr_set);
+    if (rc != AMPNET_OK) return rc;
+    rc = mlp_fold_launch(p, f, ws, st);
+    if (rc != AMPNET_OK) return rc;
+    hipLaunchKernelGGL(sa_backward_kernel, dim3(sh.grid), dim3(64), sh.lds_floats * sizeof(float), st, p, b, xyz, n, ld, centres, s, group_idx,
+                       nsample, feats, D, ws, dout, sh.n_groups, dfeats ? 1 : 0, arg_out);
+    rc = check_launch("sa_backward_kernel");
+    if (rc != AMPNET_OK) return rc;
+    for (int l = 0; l < L; ++l) {
+        rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, ws + sh.off_wpart,
+                              grads_host[4 * l], st);
+        if (rc != AMPNET_OK) return rc;
+    }
+    if (dfeats) {
+        hipLaunchKernelGGL(sa_dfeats_kernel, dim3(n_clouds * n), dim3(64), 0, st, b.dx0, D, n, s, nsample, group_idx, dfeats);
+        rc = check_launch("sa_dfeats_kernel");
+        if (rc != AMPNET_OK) return rc;
+    }
+    return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);
+}

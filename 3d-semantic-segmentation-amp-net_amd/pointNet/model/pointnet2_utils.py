@@ -10,12 +10,14 @@ used at :285-292).  This module provides both with the constructors and the stat
     inverse-distance interpolation + concatenation + shared MLP (ampnet_fp_forward_f32).
 Both fused kernels are exact fp32 whatever the matrix precision is.
 
-Gradients are opt-in and cover the decoder half: PointNetFeaturePropagation(..., grad=True) in EVAL mode is differentiable
-(ampnet_fp_backward_f32 through autograd._FpFn) with respect to points1, points2, its conv weights and biases and its BatchNorm weight
-and bias; running_mean and running_var are constants of that backward and are never updated, the coordinates get no gradient.  That is
-what fitting a pretrained decoder to new clouds needs (pointnetAtt.pointnet_2(decoder_grad=True)).  Not built: the set-abstraction
-backward (PointNetSetAbstraction has no gradient at all), train-mode BatchNorm (batch statistics, running-statistics updates: .train()
-still raises), gradients to coordinates, `group_all=True`.
+Gradients are opt-in.  PointNetFeaturePropagation(..., grad=True) in EVAL mode is differentiable (ampnet_fp_backward_f32 through
+autograd._FpFn) with respect to points1, points2, its conv weights and biases and its BatchNorm weight and bias;
+PointNetSetAbstraction(..., grad=True) in EVAL mode is differentiable (ampnet_sa_backward_f32 through autograd._SaFn) with respect to
+`points`, its conv weights and biases and its BatchNorm weight and bias, the max over the group sending each gradient to the lowest row
+that attains it.  running_mean and running_var are constants of both backwards and are never updated, the coordinates get no gradient,
+and farthest-point sampling, ball query and the gather of the centres run under no_grad.  That is what fitting a pretrained backbone to
+new clouds needs (pointnetAtt.pointnet_2(decoder_grad=True, encoder_grad=True)).  Not built: train-mode BatchNorm (batch statistics,
+running-statistics updates: .train() still raises), gradients to coordinates, `group_all=True`.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
 from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
@@ -82,10 +84,14 @@ def _workspace(mod, nbytes, device):
 class PointNetSetAbstraction(nn.Module):
     """One set-abstraction layer: `npoint` centres by farthest-point sampling, per centre the first `nsample` points within `radius`
     (utils.ball_query), the shared MLP `mlp` (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on [relative xyz, point features], max over the
-    group.  `in_channel` counts the 3 coordinates, as in the usual implementation."""
+    group.  `in_channel` counts the 3 coordinates, as in the usual implementation.
+    grad=True: in eval mode, with grad mode on and `points` or a parameter that requires grad, new_points carries a graph to `points` and
+    the conv / BatchNorm affine parameters (the running statistics stay frozen; new_xyz never carries one).  grad=False (default): no
+    graph, ever."""
 
-    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda'):
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda', grad=False):
         super().__init__()
+        self.grad = bool(grad)
         if group_all:
             raise NotImplementedError("the HIP set abstraction is built for group_all=False (ball-query groups of <= 64 points); "
                                       "the single all-points group is not")
@@ -108,31 +114,48 @@ class PointNetSetAbstraction(nn.Module):
         if (points is None) != (D == 0) or (points is not None and (points.dim() != 3 or tuple(points.shape) != (B, D, N))):
             raise _lib.AmpnetError(f"PointNetSetAbstraction: in_channel={self.in_channel} needs points "
                                    f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
+        if points is not None:
+            _lib.require_gpu(points, "points")
+        if self._wants_grad(points):                                 # a differentiable transpose; the coordinates get no gradient
+            x = xyz.detach().float().transpose(1, 2).contiguous()
+            feats = None if points is None else points.float().transpose(1, 2).contiguous()
+            new_xyz, out = self._forward_rows(x, feats, centres)
+            return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
         with torch.no_grad():
             x = xyz.detach().float().transpose(1, 2).contiguous()                     # [B, N, 3]
             feats = None
             if points is not None:
-                _lib.require_gpu(points, "points")
                 feats = points.detach().float().transpose(1, 2).contiguous()         # [B, N, D]
             new_xyz, out = self._forward_rows(x, feats, centres)
         return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
+
+    def _wants_grad(self, feats):
+        return self.grad and torch.is_grad_enabled() and ((feats is not None and feats.requires_grad)
+                                                          or any(p.requires_grad for p in self.parameters()))
 
     def _forward_rows(self, x, feats, centres=None):
         """The layer on point-major tensors (what the kernels take): x [B, N, 3], feats [B, N, D] or None, float32 contiguous GPU
         -> (new_xyz [B, npoint, 3], new_points [B, npoint, mlp[-1]]).  pointnet_2 chains its blocks through this, without the transpose
         pair per block that forward() owes to the channel-major interface."""
         B = x.shape[0]
-        if centres is None:
-            centres = U.fps_indices(x, self.npoint)
-        elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
-            raise _lib.AmpnetError(f"PointNetSetAbstraction: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
-        group_idx = U.ball_query(x, centres, self.radius, self.nsample)           # validates the centres
-        centres = centres.contiguous()
+        with torch.no_grad():
+            x = x.detach()
+            if centres is None:
+                centres = U.fps_indices(x, self.npoint)
+            elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
+                raise _lib.AmpnetError(f"PointNetSetAbstraction: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
+            group_idx = U.ball_query(x, centres, self.radius, self.nsample)       # validates the centres
+            centres = centres.contiguous()
+            new_xyz = U.gather_rows(x, centres)
+        if self._wants_grad(feats):
+            from ... import autograd
+            return new_xyz, autograd.sa_apply(self, x, centres, group_idx, feats, _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
+        feats = None if feats is None else feats.detach()
         layers = _mlp_tensors(self)
         out = torch.empty((B, self.npoint, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
         _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out,
                             _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
-        return U.gather_rows(x, centres), out
+        return new_xyz, out
 
 
 def _mlp_tensors(mod):

@@ -18,6 +18,8 @@ process-wide default).  It is a plain attribute: not a parameter, not a buffer, 
 Only the AMP-Net configuration is implemented in HIP: point_dimension=3, global_feat_dim=256, local_dim=64,
 embed_dim=256, num_heads=8, num_classes<=8 (train_pointnet-attention.py:110-118); other values raise.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -428,15 +430,21 @@ class pointnet_2(nn.Module):
 
     decoder_grad=True makes the decoder trainable in eval mode (fine-tuning a pretrained backbone with a torch loss and a torch
     optimiser): `fp3`, `fp2`, `fp1` run with grad=True and `conv1` is a torch layer, so both outputs carry a graph to the conv weights
-    and biases and the BatchNorm weights and biases of fp1..fp3 and to conv1.  Frozen: `sa1`..`sa3` (the encoder runs under no_grad on
-    detached inputs, its parameters get no gradient) and every running_mean / running_var.  Train mode is still not built: .train() raises."""
+    and biases and the BatchNorm weights and biases of fp1..fp3 and to conv1.  Without encoder_grad, `sa1`..`sa3` are frozen (the encoder
+    runs under no_grad on detached inputs, its parameters get no gradient).  encoder_grad=True (needs decoder_grad=True, else ValueError)
+    runs `sa1`..`sa3` with grad=True as well: the gradient reaches them through l1_points, l2_points and l3_points -- the skip and coarse
+    inputs of fp1..fp3 and the features of sa2 and sa3 -- so the whole backbone can be fine-tuned.  The input and every running_mean /
+    running_var stay frozen either way.  Train mode is still not built: .train() raises."""
 
-    def __init__(self, num_classes, device='cuda', decoder_grad=False):
+    def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False):
         super().__init__()
         self.decoder_grad = bool(decoder_grad)
-        self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device)
-        self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device)
-        self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device)
+        self.encoder_grad = bool(encoder_grad)
+        if self.encoder_grad and not self.decoder_grad:
+            raise ValueError("pointnet_2: encoder_grad=True needs decoder_grad=True (the gradient reaches sa1..sa3 through fp1..fp3)")
+        self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device, grad=self.encoder_grad)
+        self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device, grad=self.encoder_grad)
+        self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device, grad=self.encoder_grad)
         self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device, grad=self.decoder_grad)
         self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device, grad=self.decoder_grad)
         self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device, grad=self.decoder_grad)
@@ -455,6 +463,7 @@ class pointnet_2(nn.Module):
         with torch.no_grad():
             l0_points = xyz.detach().float().transpose(1, 2).contiguous()             # [B, N, 9]
             l0_xyz = l0_points[:, :, :3].contiguous()                                 # [B, N, 3]
+        with contextlib.nullcontext() if self.encoder_grad else torch.no_grad():    # (the caller's grad mode, or none)
             l1_xyz, l1_points = self.sa1._forward_rows(l0_xyz, l0_points)             # [B, 1024, 3], [B, 1024, 64]
             l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)             # [B, 256, 3], [B, 256, 128]
             l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)             # [B, 64, 3], [B, 64, 256]

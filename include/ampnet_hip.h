@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 11
+#define AMPNET_ABI_VERSION 12
 
 enum {
     AMPNET_OK = 0,
@@ -411,6 +411,46 @@ int ampnet_fp_backward_f32(const float *points1, int D1, const float *points2, i
                            const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
                            const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* ---- the backward of ampnet_sa_forward_f32 with BatchNorm's running statistics frozen (encoder fine-tuning) --------------------------
+ *   xyz .. eps_host, L    the forward's arguments, unchanged (the forward keeps nothing: the backward recomputes it)
+ *   dout                  [n_clouds, s, cout_{L-1}] float32, the gradient of the forward's `out`
+ *   dfeats                [n_clouds, n, D] out, or NULL when the caller does not want it (layer 0's dx and the gather are then skipped); must
+ *                         be NULL when D = 0.  The row of a point that is in no group is written as zeros.
+ *   grads_host            HOST array of 4 L DEVICE pointers, per layer: dW [cout_l, cin_l], dbias, dgamma, dbeta (each [cout_l]), all out
+ *   arg_out               [n_clouds, s, cout_{L-1}] int32 out, or NULL: the row of the group that the max selected (below)
+ *   workspace             ampnet_sa_backward_workspace_bytes(D, n_clouds, s, nsample, cout_host, L) device bytes (0 = the shape is refused,
+ *                         ampnet_last_error says why); contents undefined before and after.  It holds x_l and dz_l of all
+ *                         M = n_clouds s nsample rows and dx_0's feature columns: 4 M (sum_l (cin_l rounded up to 32) + sum_l cout_l + D)
+ *                         bytes -- the M D floats of dx_0 are reserved whether or not dfeats is requested -- plus the split-K partials
+ *                         of dW (chunks x the largest cout_l x padded cin_l) and the workgroups' channel sums.
+ * Per layer l, over the M rows (g, t), t < nsample, with x_l the layer's input row (x_0 = [xyz[idx_t] - xyz[centre_g], feats[idx_t]] as in the
+ * forward), a = W_l x_l and y = fma(a, scale, shift) exactly as the forward forms them, the formulas of ampnet_fp_backward_f32:
+ *     dy = dx_{l+1} [y > 0]     dbeta = sum dy     G = sum dy a     dgamma = (G + (b - mean) dbeta) / sqrt(var + eps)     dbias = scale dbeta
+ *     dz = dy scale          dW_l = dz^T x_l          dx_l = dz W_l
+ * The max over the group: dx_L[(g, t), c] = dout[g, c] for ONE row t = arg(g, c), 0 elsewhere.  arg(g, c) is the lowest t in [0, nsample)
+ * whose float32 relu(y) attains the group's maximum (the forward's own bits); the gradient passes only if that y > 0.  Slots that the ball
+ * query filled by repeating its first member are bit-identical to that member's row, so their gradient goes to the first occurrence and
+ * all their dz and dx are exact zeros.  When every row's y <= 0, arg = 0 and no gradient flows.
+ * dfeats[j] = sum over the entries (g, t) with group_idx[g, t] = j (clamped as in the forward) of dx_0[(g, t), 3:]; columns 0 .. 2 of dx_0
+ * (the relative coordinates) are dropped: xyz gets no gradient.  running_mean and running_var are constants.
+ * Summation orders (each a function of the shape alone, so two calls on the same inputs return the same bits; no atomics):
+ *   a, y      the forward's: k ascending in blocks of 8, k-step i < 4 of lane half h takes k = k0 + 2 i + h, one fmaf chain per element
+ *   dx_l      o ascending in blocks of 8, k-step i < 4 of lane half h takes o = o0 + 2 i + h, one fmaf chain per element
+ *   dW_l      as in ampnet_fp_backward_f32 over the M rows in the order (g, t)
+ *   dbeta, G  per group the rows of each 32-row tile in the accumulator's order (i & 3) + 8 (i >> 2), i < 16, tiles ascending, lane half 0
+ *             then + half 1 (the last layer: its one term); a workgroup adds its groups (group = workgroup + t * min(groups, 2048))
+ *             ascending; lane t of a wave adds workgroups t, t + 64, .. ascending and the 64 lane sums go through a halving tree
+ *   dfeats    the entries (g, t) ascending, plain sums
+ * Limits: the forward's (nsample <= 64, L <= 3, cin_0 = 3 + D <= 320, widths multiples of 32 up to 256), and a wave's L + 1 tiles of
+ * R = 32 (nsample <= 32) or 64 rows -- 4 R (((cin_0 + 7) / 8 * 8 + 1) + sum_l (cout_l + 1)) bytes -- must fit the 160 KB LDS: at R = 32 every
+ * such shape does (cin_0 = 320 with three layers of 256: 140 KB), at R = 64 wide stacks do not (the same shape: 280 KB) and are refused
+ * by both entry points with AMPNET_E_ARG.  Exact fp32 MFMA whatever the matrix precision is.                                      */
+size_t ampnet_sa_backward_workspace_bytes(int D, int n_clouds, int s, int nsample, const int *cout_host, int L);
+int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                           int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                           const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =

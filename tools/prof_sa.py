@@ -1,7 +1,14 @@
 """Ball query + fused set-abstraction forward at the reference's sa1 shape (B = 16, N = 8192, npoint = 1024, nsample = 32, D = 9,
 MLP [32, 32, 64]) against what torch-ROCm offers for the same layer: gather + conv2d + BatchNorm2d (eval) + relu + max.
 python3 tools/prof_sa.py [steps] [warmup]  -- HIP events, warm-up first, both sides in this process; prints one JSON line.
-Under rocprofv3 (counters in a run of their own) the kernels to look for are ball_query_kernel and sa_forward_kernel."""
+Under rocprofv3 (counters in a run of their own) the kernels to look for are ball_query_kernel and sa_forward_kernel.
+The backward leg, at the sa1, sa2 and sa3 shapes of pointnet_2 at B = 16 (sa2's cloud is sa1's centres, sa3's is sa2's): the fused backward
+(ampnet_sa_backward_f32: sa_fold_kernel, sa_backward_kernel, fp_wgrad_kernel + fp_wgrad_reduce_kernel per layer, sa_dfeats_kernel,
+fp_bwd_finalize_kernel) against torch.autograd's backward of the torch composition below on the SAME groups (graph built once and retained,
+only the backward is timed); the two are timed in alternating rounds and every round is reported.  sa1's features are the input data, so
+its dfeats is not requested, as in the model; sa2 and sa3 are also timed without dfeats, which prices layer 0's dx plus the gather.
+python3 tools/prof_sa.py [steps] [warmup] trace  -- runs nothing but the fused backward, `steps` times per shape, for a
+`rocprofv3 --kernel-trace --stats` run that splits it by kernel (sa2 and sa3 with dfeats: sa_dfeats_kernel's own time is in that split)."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -12,6 +19,7 @@ U = importlib.import_module(PKG + ".utils.utils")
 L = importlib.import_module(PKG + "._lib")
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 warmup = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+trace_only = len(sys.argv) > 3 and sys.argv[3] == "trace"
 B, N, S, K, D, MLP, RADIUS = 16, 8192, 1024, 32, 9, [32, 32, 64], 0.1
 dev = "cuda"
 xyz = torch.from_numpy(synth.clouds(200, B, N)).to(dev)
@@ -53,6 +61,90 @@ def torch_layer():
     return x.max(-1)[0].transpose(1, 2)
 
 
+def make_layers(cin, mlp, seed):
+    gen, res = torch.Generator().manual_seed(seed), []
+    for cout in mlp:
+        res.append(tuple(t.to(dev) for t in ((torch.rand(cout, cin, generator=gen) - 0.5) * 2 / cin ** 0.5, (torch.rand(cout, generator=gen) - 0.5) * 0.2,
+                                             0.5 + torch.rand(cout, generator=gen), torch.rand(cout, generator=gen) - 0.5,
+                                             (torch.rand(cout, generator=gen) - 0.5) * 0.6, 0.5 + torch.rand(cout, generator=gen))))
+        cin = cout
+    return res
+
+
+def torch_sa(pts, f, c, gi, lay):
+    """torch_layer() on any cloud: gather, 1x1 conv, eval BatchNorm, ReLU, max."""
+    b = pts.shape[0]
+    bi = torch.arange(b, device=dev)[:, None, None]
+    g_xyz = pts[bi, gi.long()] - pts[torch.arange(b, device=dev)[:, None], c.long()][:, :, None, :]
+    x = torch.cat([g_xyz, f[bi, gi.long()]], -1).permute(0, 3, 1, 2)
+    for w, bias, gamma, beta, mean, var in lay:
+        x = torch.relu(torch.nn.functional.batch_norm(torch.nn.functional.conv2d(x, w[:, :, None, None], bias), mean, var, gamma, beta, False, 0.0, 1e-5))
+    return x.max(-1)[0].transpose(1, 2)
+
+
+def backward_leg():
+    """-> {block: figures} for sa1, sa2, sa3 of pointnet_2 at B = 16."""
+    res, pts = {}, xyz
+    for block, (s_, k_, d_, mlp, radius, want_df) in {"sa1": (1024, 32, 9, [32, 32, 64], 0.1, False), "sa2": (256, 32, 64, [64, 64, 128], 0.2, True),
+                                                      "sa3": (64, 32, 128, [128, 128, 256], 0.4, True)}.items():
+        n_ = pts.shape[1]
+        f = torch.from_numpy(synth.uniform(220 + d_, (B, n_, d_), -1.0, 1.0)).to(dev)
+        c = U.fps_indices(pts, s_)
+        gi = U.ball_query(pts, c, radius, k_)
+        lay = make_layers(3 + d_, mlp, d_)
+        dout = torch.from_numpy(synth.uniform(230 + d_, (B, s_, mlp[-1]), -1.0, 1.0)).to(dev)
+        bws = torch.empty(L.sa_backward_workspace_bytes(d_, B, s_, k_, mlp), dtype=torch.uint8, device=dev)
+        df = torch.empty_like(f)
+        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in lay]
+        eps = [1e-5] * len(mlp)
+        fused = lambda with_df: L.sa_backward_f32(pts, c, gi, f, lay, eps, dout, df if with_df else None, grads, bws)
+        if trace_only:
+            for _ in range(steps):
+                fused(want_df)
+            torch.cuda.synchronize()
+            pts = U.gather_rows(pts, c)
+            continue
+        leaves = ([f.requires_grad_(True)] if want_df else []) + [t.requires_grad_(True) for layer in lay for t in layer[:4]]
+        t_out = torch_sa(pts, f, c, gi, lay)
+        torch_bwd = lambda: torch.autograd.grad(t_out, leaves, dout, retain_graph=True)
+        rounds = [(timed(lambda: fused(want_df)), timed(torch_bwd)) for _ in range(3)]
+        no_df_ms = timed(lambda: fused(False)) if want_df else None
+        t_grads = torch_bwd()
+        fused(want_df)
+        rel = lambda a, b_: float((a - b_).abs().max() / b_.abs().max())
+        diff = {"dfeats": rel(df, t_grads[0])} if want_df else {}
+        for l in range(len(mlp)):
+            for q, name in enumerate(("dW", "dbias", "dgamma", "dbeta")):
+                diff[f"{name}{l}"] = rel(grads[l][q], t_grads[int(want_df) + 4 * l + q])
+        for t in leaves:
+            t.requires_grad_(False)
+        fb, tb = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
+        M = B * s_ * k_
+        cins = [3 + d_] + mlp[:-1]
+        # the workspace traffic by construction: x_l and dz_l of every row written once by sa_backward_kernel and read by fp_wgrad_kernel
+        # once per 32-row block of dW (x_l) / per 128-column block of dW (dz_l); dx_0 written once and read by the gather
+        ldxs = [(ci + 31) // 32 * 32 for ci in cins]
+        written = 4 * M * (sum(ldxs) + sum(mlp) + (d_ if want_df else 0))
+        wgrad_reads = 4 * M * sum(lx * (co // 32) + co * ((lx + 127) // 128) for lx, co in zip(ldxs, mlp))
+        flops = 2.0 * M * (3 * sum(a * b_ for a, b_ in zip(cins, mlp)) - (0 if want_df else cins[0] * mlp[0]))
+        res[block] = {"shape": {"B": B, "N": n_, "npoint": s_, "nsample": k_, "D": d_, "mlp": mlp, "radius": radius, "dfeats": want_df},
+                      "sa_backward_ms": round(fb, 4), "torch_backward_ms": round(tb, 4), "torch_backward_over_fused": round(tb / fb, 2),
+                      "rounds_ms_fused_torch": [[round(a, 4), round(b_, 4)] for a, b_ in rounds],
+                      "sa_backward_without_dfeats_ms": None if no_df_ms is None else round(no_df_ms, 4),
+                      "layer0_dx_plus_gather_ms": None if no_df_ms is None else round(fb - no_df_ms, 4),
+                      "useful_TFLOPs": round(flops / (fb * 1e-3) / 1e12, 2), "workspace_MB": round(bws.numel() / 1e6, 1),
+                      "workspace_bytes_written_by_construction_MB": round(written / 1e6, 1),
+                      "workspace_bytes_read_by_wgrad_by_construction_MB": round(wgrad_reads / 1e6, 1),
+                      "max_rel_diff_vs_torch": diff, "hbm_counters": "not measured"}
+        pts = U.gather_rows(pts, c)
+    return res
+
+
+if trace_only:
+    backward_leg()
+    print(json.dumps({"trace_only": True, "fused_backward_calls_per_shape": steps}))
+    sys.exit(0)
+
 with torch.no_grad():
     bq_ms = timed(lambda: U.ball_query(xyz, cent, RADIUS, K))
     sa_ms = timed(lambda: L.sa_forward_f32(xyz, cent, grp, feats, layers, [1e-5] * len(MLP), out, ws))
@@ -67,4 +159,4 @@ print(json.dumps({"shape": {"B": B, "N": N, "npoint": S, "nsample": K, "D": D, "
                   "mean_members": round(float(cnt.float().mean()), 2), "ball_query_ms": round(bq_ms, 4), "sa_forward_ms": round(sa_ms, 4),
                   "torch_gather_conv2d_max_ms": round(torch_ms, 4), "torch_over_fused": round(torch_ms / sa_ms, 2),
                   "sa_algorithmic_bytes": algo, "sa_GBps_at_algorithmic_bytes": round(algo / (sa_ms * 1e-3) / 1e9, 1),
-                  "sa_useful_TFLOPs": round(flops / (sa_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch": err}))
+                  "sa_useful_TFLOPs": round(flops / (sa_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch": err, "backward": backward_leg()}))

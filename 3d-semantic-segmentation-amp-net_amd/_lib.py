@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lib = None
 
@@ -311,6 +311,114 @@ def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, d
                                           ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ptr(workspace), ctypes.c_size_t(have),
                                           stream_ptr(points2.device))
     check(rc, "ampnet_fp_backward_f32")
+
+
+# ---- train-mode feature propagation (include/ampnet_hip.h: ampnet_fp_train_forward_f32, ampnet_fp_train_backward_f32) ----------------
+def _fp_train_workspace_bytes(which, D1, D2, B, N, couts):
+    couts = [int(c) for c in couts]
+    name = f"ampnet_fp_train_{which}_workspace_bytes"
+    fn = getattr(lib(), name)
+    fn.restype = ctypes.c_size_t
+    need = fn(int(D1), int(D2), int(B), int(N), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
+    if not need:
+        check(-1, name)
+    return int(need)
+
+
+def fp_train_forward_workspace_bytes(D1, D2, B, N, couts):
+    """Device bytes fp_train_forward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    return _fp_train_workspace_bytes("forward", D1, D2, B, N, couts)
+
+
+def fp_train_backward_workspace_bytes(D1, D2, B, N, couts):
+    """Device bytes fp_train_backward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    return _fp_train_workspace_bytes("backward", D1, D2, B, N, couts)
+
+
+def _fp_train_shapes(prefix, points1, points2, idx, dist2, extra):
+    for name, t, dt in (("points1", points1, torch.float32), ("points2", points2, torch.float32), ("idx", idx, torch.int32),
+                        ("dist2", dist2, torch.float32)) + tuple(extra):
+        if t is not None and (not t.is_cuda or t.dtype != dt or t.dim() != 3):
+            raise AmpnetError(f"{prefix}: {name} must be a 3-d {dt} GPU tensor")
+    B, N, k = idx.shape
+    S, D2 = points2.shape[1], points2.shape[2]
+    D1 = 0 if points1 is None else points1.shape[2]
+    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)):
+        raise AmpnetError(f"{prefix}: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k] do not agree with idx {tuple(idx.shape)}")
+    return B, N, k, S, D1, D2
+
+
+def _fp_saved(prefix, name, t, sum_c, null_ok=False):
+    if t is None and null_ok:                                   # (NULL: the C ABI refuses it by name)
+        return
+    if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (sum_c,):
+        raise AmpnetError(f"{prefix}: {name} must be a contiguous float32 GPU tensor of sum(cout) = {sum_c} elements, got "
+                          f"{None if t is None else tuple(t.shape)}")
+
+
+def fp_train_forward_f32(points1, points2, idx, dist2, layers, eps, momentum, out, save_mean, save_invstd, workspace):
+    """One fused feature-propagation layer with batch-statistics BatchNorm.  The arguments of fp_forward_f32; running_mean and running_var
+    (entries 4 and 5 of every layer) are UPDATED IN PLACE with `momentum` (a float in [0, 1]); save_mean / save_invstd [sum of couts]:
+    written, layer l at the offset of the layers before it; workspace: fp_train_forward_workspace_bytes(...) GPU bytes."""
+    L = len(layers)
+    B, N, k, S, D1, D2 = _fp_train_shapes("fp_train_forward", points1, points2, idx, dist2, (("out", out, torch.float32),))
+    if L and tuple(out.shape) != (B, N, int(layers[-1][0].shape[0])):
+        raise AmpnetError(f"fp_train_forward: out {tuple(out.shape)} must be [B, N, cout_last] = {[B, N, int(layers[-1][0].shape[0])]}")
+    if momentum is None:
+        raise AmpnetError("fp_train_forward: momentum=None (the cumulative average) is not built; give a float in [0, 1]")
+    table, couts, epss = _mlp_tables("fp_train_forward", layers, D1 + D2, eps, workspace, 0)
+    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
+    _fp_saved("fp_train_forward", "save_mean", save_mean, sum_c, null_ok=True)
+    _fp_saved("fp_train_forward", "save_invstd", save_invstd, sum_c, null_ok=True)
+    have = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_train_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L,
+                                               ctypes.c_float(float(momentum)), ptr(out), ptr(save_mean), ptr(save_invstd), ptr(workspace),
+                                               ctypes.c_size_t(have), stream_ptr(points2.device))
+    check(rc, "ampnet_fp_train_forward_f32")
+
+
+def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, save_invstd, dout, dpoints1, dpoints2, grads, workspace):
+    """The backward of fp_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
+    further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dpoints1, dpoints2, grads as in
+    fp_backward_f32 (dbias is written as zeros); workspace: fp_train_backward_workspace_bytes(...) GPU bytes."""
+    L = len(layers)
+    B, N, k, S, D1, D2 = _fp_train_shapes("fp_train_backward", points1, points2, idx, dist2,
+                                          (("dout", dout, torch.float32), ("dpoints1", dpoints1, torch.float32),
+                                           ("dpoints2", dpoints2, torch.float32)))
+    if (dpoints1 is None) != (points1 is None):
+        raise AmpnetError(f"fp_train_backward: dpoints1 must be None exactly when points1 is (D1 = {D1}), got "
+                          f"{None if dpoints1 is None else tuple(dpoints1.shape)}")
+    if dpoints1 is not None and tuple(dpoints1.shape) != tuple(points1.shape):
+        raise AmpnetError(f"fp_train_backward: dpoints1 {tuple(dpoints1.shape)} must have the shape of points1 {tuple(points1.shape)}")
+    if tuple(dpoints2.shape) != tuple(points2.shape):
+        raise AmpnetError(f"fp_train_backward: dpoints2 {tuple(dpoints2.shape)} must have the shape of points2 {tuple(points2.shape)}")
+    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
+    _fp_saved("fp_train_backward", "save_mean", save_mean, sum_c)
+    _fp_saved("fp_train_backward", "save_invstd", save_invstd, sum_c)
+    slotted, off = [], 0
+    for layer in layers:                                        # slots 4 and 5 of the C ABI: the layer's saved statistics
+        c = int(layer[0].shape[0])
+        slotted.append(tuple(layer[:4]) + (save_mean[off:off + c], save_invstd[off:off + c]))
+        off += c
+    table, couts, epss = _mlp_tables("fp_train_backward", slotted, D1 + D2, eps, workspace, 0)
+    if L and tuple(dout.shape) != (B, N, int(layers[-1][0].shape[0])):
+        raise AmpnetError(f"fp_train_backward: dout {tuple(dout.shape)} must be [B, N, cout_last] = {[B, N, int(layers[-1][0].shape[0])]}")
+    if len(grads) != L:
+        raise AmpnetError(f"fp_train_backward: grads has {len(grads)} entries for {L} layers")
+    for i, (layer, g) in enumerate(zip(layers, grads)):
+        want = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
+        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, want)):
+            raise AmpnetError(f"fp_train_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in g]}")
+    gtensors = [t for g in grads for t in g]
+    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
+    have = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_train_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L,
+                                                ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ptr(workspace), ctypes.c_size_t(have),
+                                                stream_ptr(points2.device))
+    check(rc, "ampnet_fp_train_backward_f32")
 
 
 # ---- the set-abstraction backward (include/ampnet_hip.h: ampnet_sa_backward_f32) -------------------------------------------------------

@@ -218,6 +218,67 @@ def fp_apply(module, p1, p2, idx, dist2, fold_ws):
     return _FpFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, p1, p2, idx, dist2, *tensors)
 
 
+class _FpTrainFn(torch.autograd.Function):
+    """One fused feature-propagation layer with TRAIN-mode BatchNorm (pointnet2_utils.PointNetFeaturePropagation with grad=True and
+    batch_stats=True, in train mode).  tensors: per layer conv weight [out, in, 1], conv bias, BatchNorm weight, bias; stats: per layer the
+    module's (running_mean, running_var) buffers, updated in place by the forward and NOT saved -- the backward takes the batch statistics
+    the forward wrote (save_mean, save_invstd), so a later forward cannot change an earlier one's gradient.  Exact fp32 whatever the matrix
+    precision is (csrc/feature_propagation_train.hip)."""
+
+    @staticmethod
+    def forward(ctx, eps, momentum, stats, p1, p2, idx, dist2, *tensors):
+        layers = [layer + tuple(st) for layer, st in zip(_fp_train_layers(tensors), stats)]
+        out, save_mean, save_invstd = fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum)
+        ctx.save_for_backward(p1, p2, idx, dist2, save_mean, save_invstd, *tensors)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        p1, p2, idx, dist2, save_mean, save_invstd, *tensors = ctx.saved_tensors
+        layers = _fp_train_layers(tensors)
+        dp1 = None if p1 is None else torch.empty_like(p1)
+        dp2 = torch.empty_like(p2)
+        grads = [tuple(torch.empty_like(t) for t in layer) for layer in layers]
+        need = _lib.fp_train_backward_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], p2.shape[0], idx.shape[1],
+                                                      [layer[0].shape[0] for layer in layers])
+        _lib.fp_train_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, save_mean, save_invstd, dout.contiguous().float(), dp1, dp2, grads,
+                                   torch.empty(need, dtype=torch.uint8, device=p2.device))
+        need_grad = ctx.needs_input_grad
+        ret = [None, None, None, dp1 if need_grad[3] else None, dp2 if need_grad[4] else None, None, None]
+        for l, g in enumerate(grads):
+            w = tensors[4 * l]
+            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3])):     # the conv weight keeps its [out, in, 1]; dbias is zeros
+                ret.append(t if need_grad[7 + 4 * l + q] else None)
+        return tuple(ret)
+
+
+def _fp_train_layers(tensors):
+    """The four contiguous float32 parameter tensors per layer, from the module's own (weight [out, in, 1] -> [out, in])."""
+    return [tuple(t.detach().reshape(t.shape[0], -1).float().contiguous() if q == 0 else t.detach().float().contiguous()
+                  for q, t in enumerate(tensors[i:i + 4])) for i in range(0, len(tensors), 4)]
+
+
+def fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum):
+    """ampnet_fp_train_forward_f32 on layers of six tensors (the running statistics are updated in place) -> (out, save_mean, save_invstd)."""
+    couts = [int(layer[0].shape[0]) for layer in layers]
+    out = torch.empty((p2.shape[0], idx.shape[1], couts[-1]), dtype=torch.float32, device=p2.device)
+    save_mean, save_invstd = (torch.empty(sum(couts), dtype=torch.float32, device=p2.device) for _ in range(2))
+    need = _lib.fp_train_forward_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], p2.shape[0], idx.shape[1], couts)
+    _lib.fp_train_forward_f32(p1, p2, idx, dist2, layers, eps, momentum, out, save_mean, save_invstd,
+                              torch.empty(need, dtype=torch.uint8, device=p2.device))
+    return out, save_mean, save_invstd
+
+
+def fp_train_apply(module, p1, p2, idx, dist2, momentum):
+    """Grad-mode, train-mode forward of a PointNetFeaturePropagation block on point-major rows (as fp_apply): batch statistics, the
+    module's running statistics updated in place, a graph to p1, p2 and the block's conv and BatchNorm affine parameters (the conv bias
+    gets zeros: it has no effect on a batch-normalised output)."""
+    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns) for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
+    stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
+    return _FpTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, p1, p2, idx, dist2, *tensors)
+
+
 class _SaFn(torch.autograd.Function):
     """One fused set-abstraction layer with BatchNorm's running statistics frozen (pointnet2_utils.PointNetSetAbstraction with grad=True).
     tensors: per layer conv weight [out, in, 1, 1], conv bias, BatchNorm weight, bias, running_mean, running_var.  The forward is the eval

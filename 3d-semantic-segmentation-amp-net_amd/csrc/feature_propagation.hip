@@ -57,6 +57,20 @@ __global__ __launch_bounds__(256) void fp_forward_kernel(MlpPlan p, const float 
     }
 }
 
+// fp_forward_kernel on `st` with the plan and LDS bytes of mlp_plan_build and a fold that is already (being) written on `st`: the eval entry
+// point below folds the running statistics, the train-mode forward (feature_propagation_train.hip) the batch's.
+int fp_forward_launch(const char *what, const MlpPlan &p, int lds, const float *points1, int D1, const float *points2, int D2, int n_clouds, int n,
+                      int s, const int32_t *idx, const float *dist2, int k, const float *fold, float *out, hipStream_t st)
+{
+    static bool attr_set = false;
+    int rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(fp_forward_kernel), attr_set);
+    if (rc != AMPNET_OK) return rc;
+    const int tiles_per_cloud = (int)(((long long)n + 31) / 32), n_tiles = n_clouds * tiles_per_cloud;
+    hipLaunchKernelGGL(fp_forward_kernel, dim3(mlp_grid(n_tiles, p.nw)), dim3(64 * p.nw), lds, st, p, points1, D1, points2, D2, n, s, idx, dist2, k,
+                       fold, tiles_per_cloud, n_tiles, out);
+    return check_launch("fp_forward_kernel");
+}
+
 }  // namespace ampnet
 
 extern "C" int ampnet_fp_forward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
@@ -81,14 +95,8 @@ extern "C" int ampnet_fp_forward_f32(const float *points1, int D1, const float *
     MlpFold f;
     const int lds = mlp_plan_build("ampnet_fp_forward_f32", D1 + D2, 32, params_host, cout_host, eps_host, L, p, f);
     if (!lds) return AMPNET_E_ARG;
-    static bool attr_set = false;
-    int rc = mlp_allow_full_lds("ampnet_fp_forward_f32", reinterpret_cast<const void *>(fp_forward_kernel), attr_set);
+    int rc = mlp_fold_launch(p, f, static_cast<float *>(workspace), (hipStream_t)stream);
     if (rc != AMPNET_OK) return rc;
-    float *fold = static_cast<float *>(workspace);
-    rc = mlp_fold_launch(p, f, fold, (hipStream_t)stream);
-    if (rc != AMPNET_OK) return rc;
-    const int n_tiles = n_clouds * tiles_per_cloud;
-    hipLaunchKernelGGL(fp_forward_kernel, dim3(mlp_grid(n_tiles, p.nw)), dim3(64 * p.nw), lds, (hipStream_t)stream, p, points1, D1, points2, D2, n, s,
-                       idx, dist2, k, fold, tiles_per_cloud, n_tiles, out);
-    return check_launch("fp_forward_kernel");
+    return fp_forward_launch("ampnet_fp_forward_f32", p, lds, points1, D1, points2, D2, n_clouds, n, s, idx, dist2, k, static_cast<float *>(workspace),
+                             out, (hipStream_t)stream);
 }

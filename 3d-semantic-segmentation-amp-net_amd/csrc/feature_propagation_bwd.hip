@@ -34,12 +34,9 @@
 //       (mlp_bwd.hip).
 //
 // Every order above is a function of the shape alone: two runs give the same bits.  Exact fp32 MFMA whatever the matrix precision is.
-#include "fp_rows.h"
-#include "mlp_bwd.h"
+#include "fp_bwd_tiles.h"
 
 namespace ampnet {
-
-constexpr int FPB_MAX_GRID = 1024;        // workgroups (= rows of the partials array) of fp_backward_kernel
 
 struct FpBwdPlan {
     int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];   // tile X_l: float offset in LDS, odd row stride
@@ -59,34 +56,7 @@ __device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const flo
 {
     const int r = lane & 31, h = lane >> 5;
     f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    const float *xr = x + r * ldx + 4 * h;
-    for (int k0 = 0; k0 < kp; k0 += 8) {
-        float av[4], bv[NT][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = xr[k0 + i];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const float *wr = w + (size_t)(n0 + 32 * t + r) * cin + k0 + 4 * h;
-            if (VEC) {
-                const float4 q = *reinterpret_cast<const float4 *>(wr);
-                bv[t][0] = q.x;
-                bv[t][1] = q.y;
-                bv[t][2] = q.z;
-                bv[t][3] = q.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) bv[t][i] = k0 + 4 * h + i < cin ? wr[i] : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
+    fpb_accumulate<NT, VEC>(x, ldx, w, cin, kp, n0, acc, lane);              // fp_bwd_tiles.h
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int col = n0 + 32 * t + r;
@@ -110,50 +80,6 @@ __device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const flo
         if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
             part_b[col] += sb + ob;
             part_g[col] += sg + og;
-        }
-    }
-}
-
-// dx = dz W for NT column tiles of the layer's INPUT from c0: dz [32][ldd] in LDS, w [cout][cin] global.  Results go to tile `xo` (l >= 1)
-// or, xo == nullptr, to dpoints1 / the dx_0 rows of the workspace (layer 0; D1 + D2 = cin).
-template <int NT>
-__device__ __forceinline__ void fpb_dgrad(const float *d, int ldd, const float *__restrict__ w, int cin, int cout, int c0, float *xo, int ldxo,
-                                          float *__restrict__ dp1, int D1, float *__restrict__ dx0, int D2, int rows, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    const float *dr = d + r * ldd + h;
-    for (int o0 = 0; o0 < cout; o0 += 8) {
-        float av[4], bv[NT][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = dr[o0 + 2 * i];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int c = c0 + 32 * t + r;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[t][i] = c < cin ? w[(size_t)(o0 + 2 * i + h) * cin + c] : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = c0 + 32 * t + r;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (xo) {
-                if (c < cin) xo[row * ldxo + c] = acc[t][i];
-            } else if (row < rows) {
-                if (c < D1) dp1[(size_t)row * D1 + c] = acc[t][i];
-                else if (c < cin) dx0[(size_t)row * D2 + c - D1] = acc[t][i];
-            }
         }
     }
 }
@@ -259,15 +185,14 @@ __global__ __launch_bounds__(64) void fp_scatter_kernel(const float *__restrict_
         if (lane + 64 * u < D2) dst[lane + 64 * u] = acc[u];
 }
 
-// what both entry points derive from the shape: the launch sizes and the workspace layout (float offsets, each a multiple of 64)
-struct FpBwdShape {
-    long long M;
-    int tiles_per_cloud, n_tiles, grid, chunk_rows, chunks, sum_c;
-    int cin[MLP_MAX_LAYERS], ldxs[MLP_MAX_LAYERS];
-    size_t off_parts, off_xs[MLP_MAX_LAYERS], off_dz[MLP_MAX_LAYERS], off_dx0, off_wpart, floats;
-};
+int fp_scatter_launch(const float *dx0, int D2, int n_clouds, int n, int s, const int32_t *idx, const float *dist2, int k, float *dpoints2,
+                      hipStream_t st)
+{
+    hipLaunchKernelGGL(fp_scatter_kernel, dim3(n_clouds * s), dim3(64), 0, st, dx0, D2, n, s, idx, dist2, k, dpoints2);
+    return check_launch("fp_scatter_kernel");
+}
 
-static int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, const int *cout_host, int L, FpBwdShape &sh)
+int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, const int *cout_host, int L, FpBwdShape &sh)
 {
     AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
     AMPNET_REQUIRE(n_clouds >= 1 && n >= 1, "%s: bad shape n_clouds=%d n=%d", what, n_clouds, n);
@@ -386,8 +311,7 @@ extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float 
         rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, wpart, grads_host[4 * l], st);
         if (rc != AMPNET_OK) return rc;
     }
-    hipLaunchKernelGGL(fp_scatter_kernel, dim3(n_clouds * s), dim3(64), 0, st, b.dx0, D2, n, s, idx, dist2, k, dpoints2);
-    rc = check_launch("fp_scatter_kernel");
+    rc = fp_scatter_launch(b.dx0, D2, n_clouds, n, s, idx, dist2, k, dpoints2, st);
     if (rc != AMPNET_OK) return rc;
     return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);
 }

@@ -1,6 +1,7 @@
 // fp_rows.h -- the input rows of a feature-propagation layer, built into a wave's LDS tile: ONE copy of the interpolation arithmetic for the
-// forward (feature_propagation.hip) and the backward (feature_propagation_bwd.hip), which rebuilds the rows instead of reading stored ones
-// and has to get the forward's bits to find the forward's ReLU masks.
+// forward (feature_propagation.hip), the eval backward (feature_propagation_bwd.hip) and the train-mode passes
+// (feature_propagation_train.hip), which rebuild the rows instead of reading stored ones and have to get the forward's bits to find the
+// forward's ReLU masks.  Also the launcher of the forward's kernel, which the eval and the train-mode forward share.
 #pragma once
 #include "fused_mlp.h"
 
@@ -56,5 +57,9 @@ __device__ __forceinline__ void fp_build_rows(float *tile, int ld, int kp0, cons
         }
     }
 }
+
+// fp_forward_kernel (feature_propagation.hip) on `st`, reading scale and shift of every layer from `fold` (plan.fold_off)
+int fp_forward_launch(const char *what, const MlpPlan &p, int lds, const float *points1, int D1, const float *points2, int D2, int n_clouds, int n,
+                      int s, const int32_t *idx, const float *dist2, int k, const float *fold, float *out, hipStream_t st);
 
 }  // namespace ampnet

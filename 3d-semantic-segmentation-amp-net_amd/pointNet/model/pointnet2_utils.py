@@ -16,8 +16,14 @@ PointNetSetAbstraction(..., grad=True) in EVAL mode is differentiable (ampnet_sa
 `points`, its conv weights and biases and its BatchNorm weight and bias, the max over the group sending each gradient to the lowest row
 that attains it.  running_mean and running_var are constants of both backwards and are never updated, the coordinates get no gradient,
 and farthest-point sampling, ball query and the gather of the centres run under no_grad.  That is what fitting a pretrained backbone to
-new clouds needs (pointnetAtt.pointnet_2(decoder_grad=True, encoder_grad=True)).  Not built: train-mode BatchNorm (batch statistics,
-running-statistics updates: .train() still raises), gradients to coordinates, `group_all=True`.
+new clouds needs (pointnetAtt.pointnet_2(decoder_grad=True, encoder_grad=True)).
+
+Train-mode BatchNorm is opt-in too, and built for the feature propagation only: PointNetFeaturePropagation(..., batch_stats=True) in
+TRAIN mode normalises with the statistics of the batch (all B * N rows of the call), updates running_mean / running_var in place with
+each BatchNorm's `momentum` and counts num_batches_tracked (ampnet_fp_train_forward_f32); with grad=True its backward goes through the
+statistics (ampnet_fp_train_backward_f32 through autograd._FpTrainFn), as torch's does.  In eval mode the flag changes nothing.
+Not built: train-mode BatchNorm in the set abstraction (its .train() still raises), momentum=None, gradients to coordinates,
+`group_all=True`.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
 from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
@@ -49,6 +55,7 @@ class _BN2d(nn.Module):
     def __init__(self, c, device, eps=1e-5):
         super().__init__()
         self.eps = eps
+        self.momentum = 0.1                       # (an attribute, not a state_dict key; used by train-mode feature propagation only)
         self.weight = nn.Parameter(torch.ones(c, device=device))
         self.bias = nn.Parameter(torch.zeros(c, device=device))
         self.register_buffer("running_mean", torch.zeros(c, device=device))
@@ -167,16 +174,24 @@ def _mlp_tensors(mod):
             for conv, bn in zip(mod.mlp_convs, mod.mlp_bns)]
 
 
+_FP_EVAL_ONLY = ("the HIP feature propagation is built for eval mode (BatchNorm running statistics, no backward): call .eval() first, "
+                 "or build the block with batch_stats=True")
+
+
 class PointNetFeaturePropagation(nn.Module):
     """One feature-propagation layer: every fine point takes the inverse-squared-distance weighted mean of the features of its 3 nearest
     coarse points (utils.three_nn; all of them when there are fewer than 3), concatenated behind its own features, through the shared MLP
     `mlp` (Conv1d 1x1 + BatchNorm1d + ReLU per entry).  `in_channel` = D1 + D2, as in the usual implementation.
-    grad=True: in eval mode, with grad mode on and an input or a parameter that requires grad, the result carries a graph to points1,
-    points2 and the conv / BatchNorm affine parameters (the running statistics stay frozen).  grad=False (default): no graph, ever."""
+    grad=True: with grad mode on and an input or a parameter that requires grad, the result carries a graph to points1, points2 and the
+    conv / BatchNorm affine parameters.  grad=False (default): no graph, ever.
+    batch_stats=False (default): eval mode only, the running statistics frozen; train mode raises.  batch_stats=True: train mode is
+    accepted and runs BatchNorm on the batch's statistics, updating running_mean / running_var (momentum: the `momentum` attribute of the
+    block's mlp_bns, one value for the block) and num_batches_tracked once per forward, graph or not; eval mode is unchanged."""
 
-    def __init__(self, in_channel, mlp, device='cuda', grad=False):
+    def __init__(self, in_channel, mlp, device='cuda', grad=False, batch_stats=False):
         super().__init__()
         self.grad = bool(grad)
+        self.batch_stats = bool(batch_stats)
         _build_mlp(self, in_channel, mlp, (1,), 1 <= in_channel <= _lib.FP_MAX_CIN,
                    f"the HIP feature propagation is built for 1..{_lib.FP_MAX_LAYERS} MLP layers of widths that are "
                    f"multiples of 32 up to {_lib.FP_MAX_COUT} and 1 <= in_channel <= {_lib.FP_MAX_CIN}", device)
@@ -184,9 +199,8 @@ class PointNetFeaturePropagation(nn.Module):
     def forward(self, xyz1, xyz2, points1, points2):
         """xyz1 [B, 3, N] the fine points, xyz2 [B, 3, S] the coarse ones, points1 [B, D1, N] or None, points2 [B, D2, S]
         (D1 + D2 = in_channel) -> new_points [B, mlp[-1], N]."""
-        if self.training:
-            raise NotImplementedError("the HIP feature propagation is built for eval mode (BatchNorm running statistics, no backward): "
-                                      "call .eval() first")
+        if self.training and not self.batch_stats:
+            raise NotImplementedError(_FP_EVAL_ONLY)
         for name, t in (("xyz1", xyz1), ("xyz2", xyz2), ("points1", points1), ("points2", points2)):
             if t is not None:
                 _lib.require_gpu(t, name)
@@ -219,6 +233,8 @@ class PointNetFeaturePropagation(nn.Module):
         """The layer on point-major tensors: x1 [B, N, 3], x2 [B, S, 3], p1 [B, N, D1] or None, p2 [B, S, D2], float32 contiguous GPU
         -> [B, N, mlp[-1]]."""
         idx, dist2 = U.three_nn(x1.detach(), x2.detach())
+        if self.training:
+            return self._train_rows(p1, p2, idx, dist2)
         if self._wants_grad(p1, p2):
             from ... import autograd
             return autograd.fp_apply(self, p1, p2, idx, dist2, _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
@@ -226,4 +242,27 @@ class PointNetFeaturePropagation(nn.Module):
         out = torch.empty((x1.shape[0], x1.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
         _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out,
                             _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
+        return out
+
+    def _train_rows(self, p1, p2, idx, dist2):
+        """_forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when one is wanted."""
+        if not self.batch_stats:
+            raise NotImplementedError(_FP_EVAL_ONLY)
+        momenta = {bn.momentum for bn in self.mlp_bns}
+        if None in momenta or len(momenta) != 1:
+            raise NotImplementedError("train-mode feature propagation takes one float momentum for the block's BatchNorms, got "
+                                      f"{[bn.momentum for bn in self.mlp_bns]} (momentum=None, the cumulative average, is not built)")
+        momentum = float(momenta.pop())
+        from ... import autograd
+        if self._wants_grad(p1, p2):
+            out = autograd.fp_train_apply(self, p1, p2, idx, dist2, momentum)
+        else:
+            with torch.no_grad():
+                layers = [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
+                           bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(), bn.running_mean, bn.running_var)
+                          for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
+                out, _, _ = autograd.fp_train_forward(None if p1 is None else p1.detach(), p2.detach(), idx, dist2, layers,
+                                                      [bn.eps for bn in self.mlp_bns], momentum)
+        with torch.no_grad():
+            torch._foreach_add_([bn.num_batches_tracked for bn in self.mlp_bns], 1)
         return out

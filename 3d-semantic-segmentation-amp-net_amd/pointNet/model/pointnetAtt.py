@@ -434,32 +434,51 @@ class pointnet_2(nn.Module):
     runs under no_grad on detached inputs, its parameters get no gradient).  encoder_grad=True (needs decoder_grad=True, else ValueError)
     runs `sa1`..`sa3` with grad=True as well: the gradient reaches them through l1_points, l2_points and l3_points -- the skip and coarse
     inputs of fp1..fp3 and the features of sa2 and sa3 -- so the whole backbone can be fine-tuned.  The input and every running_mean /
-    running_var stay frozen either way.  Train mode is still not built: .train() raises."""
+    running_var stay frozen either way, and without decoder_batch_stats train mode is not built: .train() raises.
 
-    def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False):
+    decoder_batch_stats=True (needs decoder_grad=True, else ValueError) lets the decoder TRAIN as torch trains it: `fp3`, `fp2`, `fp1` are
+    built with batch_stats=True, and .train(mode) puts the model, fp1..fp3 and conv1 in `mode` while `sa1`..`sa3` stay in eval mode
+    whatever encoder_grad is -- the encoder remains a frozen-statistics feature extractor (train-mode set abstraction is not built).  In
+    train mode fp1..fp3 normalise with batch statistics, update their running statistics and back-propagate through them."""
+
+    def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False):
         super().__init__()
         self.decoder_grad = bool(decoder_grad)
         self.encoder_grad = bool(encoder_grad)
+        self.decoder_batch_stats = bool(decoder_batch_stats)
+        if self.decoder_batch_stats and not self.decoder_grad:
+            raise ValueError("pointnet_2: decoder_batch_stats=True needs decoder_grad=True (train mode is for training the decoder)")
         if self.encoder_grad and not self.decoder_grad:
             raise ValueError("pointnet_2: encoder_grad=True needs decoder_grad=True (the gradient reaches sa1..sa3 through fp1..fp3)")
         self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device, grad=self.encoder_grad)
         self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device, grad=self.encoder_grad)
         self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device, grad=self.encoder_grad)
-        self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device, grad=self.decoder_grad)
-        self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device, grad=self.decoder_grad)
-        self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device, grad=self.decoder_grad)
+        self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
+        self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
+        self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
         self.conv1 = nn.Conv1d(128, 128, 1, device=device)
 
+    def train(self, mode=True):
+        super().train(mode)
+        if self.decoder_batch_stats:                                                  # the encoder keeps its frozen statistics
+            for m in (self.sa1, self.sa2, self.sa3):
+                m.train(False)
+        return self
+
     def forward(self, xyz):
-        if self.training:
+        if self.training and not self.decoder_batch_stats:
             raise NotImplementedError("pointnet_2 on the HIP path is built for eval mode (BatchNorm running statistics, no backward): "
                                       "call .eval() first")
         _lib.require_gpu(xyz, "xyz")
         if xyz.dim() != 3 or xyz.shape[1] != 9:
             raise _lib.AmpnetError(f"pointnet_2: expected xyz [B, 9, N], got {tuple(xyz.shape)}")
-        for m in (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1):
+        for m in (self.sa1, self.sa2, self.sa3):
             if m.training:
                 raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model")
+        for m in (self.fp3, self.fp2, self.fp1):
+            if m.training != self.training:
+                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
+                                          "pointnet_2: fp1..fp3 follow the model's mode; call .train() on the model, not on its blocks")
         with torch.no_grad():
             l0_points = xyz.detach().float().transpose(1, 2).contiguous()             # [B, N, 9]
             l0_xyz = l0_points[:, :, :3].contiguous()                                 # [B, N, 3]

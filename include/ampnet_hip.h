@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 12
+#define AMPNET_ABI_VERSION 13
 
 enum {
     AMPNET_OK = 0,
@@ -411,6 +411,43 @@ int ampnet_fp_backward_f32(const float *points1, int D1, const float *points2, i
                            const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
                            const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* ---- ampnet_fp_forward_f32 and its backward with TRAIN-mode BatchNorm: batch statistics (decoder training; new in ABI 13) -------------
+ * Forward.  The arguments of ampnet_fp_forward_f32, and:
+ *   params_host           per layer W, b, gamma, beta, running_mean, running_var as before; running_mean and running_var are READ AND WRITTEN
+ *   momentum              a float in [0, 1] (anything else, NaN included, is refused)
+ *   save_mean, save_invstd   [sum_l cout_l] float32 out each, layer l at offset sum_{j<l} cout_j: the batch mean of the raw accumulator
+ *                         (WITHOUT the conv bias) and 1 / sqrt(var + eps).  The backward takes them; it never recomputes statistics.
+ *   workspace             ampnet_fp_train_forward_workspace_bytes(D1, D2, n_clouds, n, cout_host, L) device bytes (0 = the shape is refused)
+ * Per layer l over the M = n_clouds n rows of the call, with a = W x the raw accumulator in the eval forward's contraction order:
+ *     mu = mean_rows a      var = mean_rows (a - mu)^2 (biased)      invstd = 1 / sqrt(var + eps)      scale = gamma invstd
+ *     shift = fma(-mu, scale, beta)   (the conv bias cancels)      y = fma(a, scale, shift)      x_{l+1} = relu(y)
+ *     running_mean <- fma(m, mu + b, (1 - m) running_mean)      running_var <- fma(m, var M / (M - 1), (1 - m) running_var)
+ * The variance is CENTRED: per column and 32-row tile the count, the mean and sum (a - tile mean)^2 of the tile's valid rows (rows in
+ * the accumulator's order (i & 3) + 8 (i >> 2), i < 16, lane half 0 + half 1); tiles are merged with Chan's formula
+ *     n = nA + nB,  d = meanB - meanA,  mean = fma(d, nB / n, meanA),  M2 = fma(d d, nA nB / n, M2A + M2B)
+ * first into P = min(tiles, 1024) partial rows (row r: the tiles r, r + P, .. ascending), then over the rows: lane t of a wave merges
+ * rows t, t + 64, .. ascending and the 64 lane results go through a halving tree (lane t takes lane t + 32, 16, .. 1).  The last
+ * launch is the eval forward's own kernel on the fold (scale, shift) so formed.
+ * Backward.  The arguments of ampnet_fp_backward_f32 with, per layer, save_mean_l and save_invstd_l (pointers into the forward's two
+ * arrays) in slots 4 and 5 of params_host in place of running_mean and running_var; b (slot 1) is not read.  From dx_L = dout:
+ *     dy = dx_{l+1} [y > 0]      dbeta = sum_rows dy      G = sum_rows dy a      dgamma = invstd fma(-mu, dbeta, G)      dbias = 0 (exact zeros)
+ *     dz = scale fma(-(a - mu), dgamma invstd / M, dy - dbeta / M)      dW_l = dz^T x_l      dx_l = dz W_l
+ * dpoints1, dpoints2, the summation orders of a, dx_l, dW_l, dbeta, G and dpoints2: as in ampnet_fp_backward_f32.
+ * Limits and refusals: those of the eval entry points, plus M < 2, M > AMPNET_FP_TRAIN_MAX_ROWS (the statistics carry row counts as
+ * floats, exact up to there) and the momentum range (AMPNET_E_ARG).  No float atomics: two calls
+ * return the same bits.  Exact fp32 MFMA whatever the matrix precision is.  Caller's stream, no host synchronisation.               */
+#define AMPNET_FP_TRAIN_MAX_ROWS (1 << 24)
+size_t ampnet_fp_train_forward_workspace_bytes(int D1, int D2, int n_clouds, int n, const int *cout_host, int L);
+int ampnet_fp_train_forward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                                const float *dist2, int k, float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                                float momentum, float *out, float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
+                                void *stream);
+size_t ampnet_fp_train_backward_workspace_bytes(int D1, int D2, int n_clouds, int n, const int *cout_host, int L);
+int ampnet_fp_train_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                                 const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host,
+                                 int L, const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
+                                 size_t workspace_bytes, void *stream);
 
 /* ---- the backward of ampnet_sa_forward_f32 with BatchNorm's running statistics frozen (encoder fine-tuning) --------------------------
  *   xyz .. eps_host, L    the forward's arguments, unchanged (the forward keeps nothing: the backward recomputes it)

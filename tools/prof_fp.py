@@ -6,7 +6,14 @@ prints one JSON line.  Under rocprofv3 (counters in a run of their own) the kern
 The backward leg, same shape, same inputs, same process: the fused backward (ampnet_fp_backward_f32: sa_fold_kernel, fp_backward_kernel,
 fp_wgrad_kernel + fp_wgrad_reduce_kernel per layer, fp_scatter_kernel, fp_bwd_finalize_kernel) against torch.autograd's backward of the
 torch composition below on the SAME neighbours (graph built once and retained, only the backward is timed); the two are timed in
-alternating rounds and every round is reported."""
+alternating rounds and every round is reported.
+The train-mode leg, same shape, same process ("train" in the JSON line): the fused batch-statistics forward (ampnet_fp_train_forward_f32:
+per layer fpt_stats_kernel + fpt_stats_finalize_kernel, then fp_forward_kernel) and backward (ampnet_fp_train_backward_f32:
+fpt_fold_kernel, L + 1 fpt_bwd_phase_kernel with fpt_bwd_finalize_kernel between them, fp_wgrad_kernel + fp_wgrad_reduce_kernel per layer,
+fp_scatter_kernel) against torch's train-mode composition -- conv1d + batch_norm(training=True) + relu per layer -- on the SAME interpolated
+rows, which torch is handed ready-made (the fused side interpolates in its forward and gathers dpoints2 in its backward).  Same protocol:
+HIP events, `steps` calls after `warmup`, three alternating rounds, the median round reported.  Per-kernel times: a kernel-trace run of
+this tool, on its own, never together with counters."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -93,6 +100,65 @@ fb_ms, tb_ms = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
 # useful flops of the backward: the recomputed forward (all layers), dx = dz W and dW = dz^T x per layer, the interpolation and its scatter
 bwd_flops = 2.0 * B * N * (3 * sum(a * b for a, b in zip([D1 + D2] + MLP[:-1], MLP)) + 2 * 3 * D2)
 
+# ---- the train-mode leg ---------------------------------------------------------------------------------------------------------------
+A = importlib.import_module(PKG + ".autograd")
+t_layers = [tuple(t.detach().clone() for t in layer) for layer in layers]                # the fused side's own running statistics
+sum_c = sum(MLP)
+save_mean, save_invstd = torch.empty(sum_c, device=dev), torch.empty(sum_c, device=dev)
+fws = torch.empty(L.fp_train_forward_workspace_bytes(D1, D2, B, N, MLP), dtype=torch.uint8, device=dev)
+tbws = torch.empty(L.fp_train_backward_workspace_bytes(D1, D2, B, N, MLP), dtype=torch.uint8, device=dev)
+t_out_f = torch.empty((B, N, MLP[-1]), device=dev)
+feats_d = feats.detach()
+fused_tf = lambda: L.fp_train_forward_f32(None, feats_d, idx, dist2, t_layers, [1e-5] * len(MLP), 0.1, t_out_f, save_mean, save_invstd, fws)
+fused_tb = lambda: L.fp_train_backward_f32(None, feats_d, idx, dist2, t_layers, [1e-5] * len(MLP), save_mean, save_invstd, dout, None, dfeats,
+                                           grads, tbws)
+with torch.no_grad():
+    r = 1.0 / (dist2 + 1e-8)
+    w = r / r.sum(-1, keepdim=True)
+    x0 = (feats_d[torch.arange(B, device=dev)[:, None, None], idx.long()] * w[..., None]).sum(2).transpose(1, 2).contiguous()   # [B, D2, N]
+x0.requires_grad_(True)
+p_layers = [tuple(t.detach().clone() for t in layer) for layer in layers]                # torch's own running statistics
+t_leaves = [x0] + [t.requires_grad_(True) for layer in p_layers for t in layer[:4]]
+
+
+def torch_train():
+    x = x0
+    for wt, b, gamma, beta, mean, var in p_layers:
+        x = torch.relu(torch.nn.functional.batch_norm(torch.nn.functional.conv1d(x, wt[:, :, None], b), mean, var, gamma, beta, True, 0.1, 1e-5))
+    return x.transpose(1, 2)
+
+
+def torch_train_fwd():
+    with torch.no_grad():
+        torch_train()
+
+
+tt_out = torch_train()
+torch_tb = lambda: torch.autograd.grad(tt_out, t_leaves, dout, retain_graph=True)
+t_rounds = [(timed(fused_tf), timed(torch_train_fwd), timed(fused_tb), timed(torch_tb)) for _ in range(3)]
+fused_tf()
+fused_tb()
+tt_grads = torch_tb()
+train_diff = {"out": rel(t_out_f, tt_out.detach())}
+for l in range(len(MLP)):
+    for q, name in enumerate(("dW", "dbias", "dgamma", "dbeta")):
+        if name != "dbias":                                                              # (zeros on one side, roundings of zero on the other)
+            train_diff[f"{name}{l}"] = rel(grads[l][q], tt_grads[1 + 4 * l + q])
+# torch's statistics differ from the fused ones in the last bits, so a few of the 16.8 M ReLU inputs per layer change sign between the two and each
+# moves a gradient by a whole term; the fused dbeta of the last layer against a float64 sum over the fused output's OWN mask tells the two apart
+mask = t_out_f > 0
+train_diff["last_layer_relu_sign_mismatches_vs_torch"] = int((mask != (tt_out.detach() > 0)).sum())
+own = (dout.double() * mask).sum((0, 1))
+train_diff["dbeta_last_vs_float64_sum_over_own_mask"] = float((grads[-1][3].double() - own).abs().max() / own.abs().max())
+med = lambda q: sorted(r[q] for r in t_rounds)[1]
+train = {"fp_train_forward_ms": round(med(0), 4), "torch_train_forward_ms": round(med(1), 4), "fp_train_backward_ms": round(med(2), 4),
+         "torch_train_backward_ms": round(med(3), 4), "torch_forward_over_fused": round(med(1) / med(0), 2),
+         "torch_backward_over_fused": round(med(3) / med(2), 2), "train_forward_over_eval_forward": round(med(0) / fp_ms, 2),
+         "train_backward_over_eval_backward": round(med(2) / fb_ms, 2),
+         "rounds_ms_fused_fwd_torch_fwd_fused_bwd_torch_bwd": [[round(v, 4) for v in r] for r in t_rounds],
+         "train_forward_workspace_MB": round(fws.numel() / 1e6, 2), "train_backward_workspace_MB": round(tbws.numel() / 1e6, 1),
+         "max_rel_diff_vs_torch": train_diff}
+
 w_bytes = sum(sum(t.numel() for t in layer) for layer in layers) * 4
 # the algorithmic bytes of the fused forward: the coarse features once, the neighbours and distances, the weights, the output
 algo = B * S * D2 * 4 + B * N * 3 * 8 + w_bytes + B * N * MLP[-1] * 4
@@ -106,4 +172,4 @@ print(json.dumps({"shape": {"B": B, "N": N, "S": S, "D1": D1, "D2": D2, "mlp": M
                   "fp_backward_ms": round(fb_ms, 4), "torch_backward_ms": round(tb_ms, 4), "torch_backward_over_fused": round(tb_ms / fb_ms, 2),
                   "backward_rounds_ms_fused_torch": [[round(a, 4), round(b, 4)] for a, b in rounds],
                   "fp_backward_useful_TFLOPs": round(bwd_flops / (fb_ms * 1e-3) / 1e12, 2), "fp_backward_workspace_MB": round(bws.numel() / 1e6, 1),
-                  "backward_max_rel_diff_vs_torch": bwd_diff, "backward_hbm_counters": "not measured"}))
+                  "backward_max_rel_diff_vs_torch": bwd_diff, "backward_hbm_counters": "not measured", "train": train}))

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lib = None
 
@@ -483,3 +483,122 @@ def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, g
                                           ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ptr(workspace), ctypes.c_size_t(have),
                                           stream_ptr(xyz.device))
     check(rc, "ampnet_sa_backward_f32")
+
+
+# ---- train-mode set abstraction (include/ampnet_hip.h: ampnet_sa_train_forward_f32, ampnet_sa_train_backward_f32) --------------------
+SA_TRAIN_MAX_ROWS = 1 << 24
+
+
+def _sa_train_workspace_bytes(which, D, B, S, nsample, couts):
+    couts = [int(c) for c in couts]
+    name = f"ampnet_sa_train_{which}_workspace_bytes"
+    fn = getattr(lib(), name)
+    fn.restype = ctypes.c_size_t
+    need = fn(int(D), int(B), int(S), int(nsample), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
+    if not need:
+        check(-1, name)
+    return int(need)
+
+
+def sa_train_forward_workspace_bytes(D, B, S, nsample, couts):
+    """Device bytes sa_train_forward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    return _sa_train_workspace_bytes("forward", D, B, S, nsample, couts)
+
+
+def sa_train_backward_workspace_bytes(D, B, S, nsample, couts):
+    """Device bytes sa_train_backward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    return _sa_train_workspace_bytes("backward", D, B, S, nsample, couts)
+
+
+def sa_train_backward_tape(D, B, S, nsample, couts, l):
+    """Test hook (ampnet_sa_train_backward_tape): where layer l's input rows x_l and its dz_l lie in the workspace that
+    sa_train_backward_f32 has run on -> (x byte offset, x row stride in floats, dz byte offset, dz row stride in floats)."""
+    couts = [int(c) for c in couts]
+    xo, dzo = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    xs, dzs = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib().ampnet_sa_train_backward_tape(int(D), int(B), int(S), int(nsample), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts), int(l),
+                                             ctypes.byref(xo), ctypes.byref(xs), ctypes.byref(dzo), ctypes.byref(dzs))
+    check(rc, "ampnet_sa_train_backward_tape")
+    return int(xo.value), int(xs.value), int(dzo.value), int(dzs.value)
+
+
+def _sa_train_shapes(prefix, xyz, centres, group_idx, feats, extra):
+    for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
+                        ("feats", feats, torch.float32)) + tuple(extra):
+        if t is None and name in ("xyz", "centres", "group_idx", "out", "dout"):
+            raise AmpnetError(f"{prefix}: {name} is None, it must be a {dt} GPU tensor")
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+            raise AmpnetError(f"{prefix}: {name} must be a contiguous {dt} GPU tensor")
+    if xyz.dim() != 3 or xyz.shape[2] < 3:
+        raise AmpnetError(f"{prefix}: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
+    B, N, ld = xyz.shape
+    if centres.dim() != 2 or centres.shape[0] != B or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != tuple(centres.shape) \
+            or (feats is not None and (feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N))):
+        raise AmpnetError(f"{prefix}: centres [B, S], group_idx [B, S, nsample], feats [B, N, D] do not agree with xyz {tuple(xyz.shape)}")
+    return B, N, ld, centres.shape[1], group_idx.shape[2], 0 if feats is None else feats.shape[2]
+
+
+def sa_train_forward_f32(xyz, centres, group_idx, feats, layers, eps, momentum, out, save_mean, save_invstd, workspace):
+    """One fused set-abstraction layer with batch-statistics BatchNorm over all B * S * nsample rows.  The arguments of sa_forward_f32;
+    running_mean and running_var (entries 4 and 5 of every layer) are UPDATED IN PLACE with `momentum` (a float in [0, 1]); save_mean /
+    save_invstd [sum of couts]: written, layer l at the offset of the layers before it; workspace: sa_train_forward_workspace_bytes(...)
+    GPU bytes."""
+    L = len(layers)
+    B, N, ld, S, nsample, D = _sa_train_shapes("sa_train_forward", xyz, centres, group_idx, feats, (("out", out, torch.float32),))
+    if L and tuple(out.shape) != (B, S, int(layers[-1][0].shape[0])):
+        raise AmpnetError(f"sa_train_forward: out {tuple(out.shape)} must be [B, S, cout_last] = {[B, S, int(layers[-1][0].shape[0])]}")
+    if momentum is None:
+        raise AmpnetError("sa_train_forward: momentum=None (the cumulative average) is not built; give a float in [0, 1]")
+    table, couts, epss = _mlp_tables("sa_train_forward", layers, 3 + D, eps, workspace, 0)
+    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
+    _fp_saved("sa_train_forward", "save_mean", save_mean, sum_c, null_ok=True)
+    _fp_saved("sa_train_forward", "save_invstd", save_invstd, sum_c, null_ok=True)
+    have = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_train_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss, L,
+                                               ctypes.c_float(float(momentum)), ptr(out), ptr(save_mean), ptr(save_invstd), ptr(workspace),
+                                               ctypes.c_size_t(have), stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_train_forward_f32")
+
+
+def sa_train_backward_f32(xyz, centres, group_idx, feats, layers, eps, save_mean, save_invstd, dout, dfeats, grads, workspace, arg_out=None):
+    """The backward of sa_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
+    further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dfeats, grads, arg_out as in
+    sa_backward_f32 (dbias is written as zeros); workspace: sa_train_backward_workspace_bytes(...) GPU bytes."""
+    L = len(layers)
+    B, N, ld, S, nsample, D = _sa_train_shapes("sa_train_backward", xyz, centres, group_idx, feats,
+                                               (("dout", dout, torch.float32), ("dfeats", dfeats, torch.float32),
+                                                ("arg_out", arg_out, torch.int32)))
+    if feats is None and dfeats is not None:
+        raise AmpnetError(f"sa_train_backward: dfeats must be None when feats is (D = 0), got {tuple(dfeats.shape)}")
+    if dfeats is not None and tuple(dfeats.shape) != tuple(feats.shape):
+        raise AmpnetError(f"sa_train_backward: dfeats {tuple(dfeats.shape)} must have the shape of feats {tuple(feats.shape)}")
+    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
+    _fp_saved("sa_train_backward", "save_mean", save_mean, sum_c)
+    _fp_saved("sa_train_backward", "save_invstd", save_invstd, sum_c)
+    slotted, off = [], 0
+    for layer in layers:                                        # slots 4 and 5 of the C ABI: the layer's saved statistics
+        c = int(layer[0].shape[0])
+        slotted.append(tuple(layer[:4]) + (save_mean[off:off + c], save_invstd[off:off + c]))
+        off += c
+    table, couts, epss = _mlp_tables("sa_train_backward", slotted, 3 + D, eps, workspace, 0)
+    want = (B, S, int(layers[-1][0].shape[0])) if L else None
+    if L and tuple(dout.shape) != want:
+        raise AmpnetError(f"sa_train_backward: dout {tuple(dout.shape)} must be [B, S, cout_last] = {list(want)}")
+    if L and arg_out is not None and tuple(arg_out.shape) != want:
+        raise AmpnetError(f"sa_train_backward: arg_out {tuple(arg_out.shape)} must be [B, S, cout_last] = {list(want)}")
+    if len(grads) != L:
+        raise AmpnetError(f"sa_train_backward: grads has {len(grads)} entries for {L} layers")
+    for i, (layer, g) in enumerate(zip(layers, grads)):
+        wantg = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
+        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, wantg)):
+            raise AmpnetError(f"sa_train_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {wantg}, "
+                              f"got {[tuple(t.shape) for t in g]}")
+    gtensors = [t for g in grads for t in g]
+    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
+    have = workspace.numel() * workspace.element_size()
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_train_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
+                                                L, ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ptr(workspace), ctypes.c_size_t(have),
+                                                stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_train_backward_f32")

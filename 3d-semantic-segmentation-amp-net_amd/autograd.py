@@ -319,3 +319,57 @@ def sa_apply(module, x, centres, group_idx, feats, fold_ws):
     tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
                for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
     return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *tensors)
+
+
+class _SaTrainFn(torch.autograd.Function):
+    """One fused set-abstraction layer with TRAIN-mode BatchNorm (pointnet2_utils.PointNetSetAbstraction with grad=True and
+    batch_stats=True, in train mode).  tensors: per layer conv weight [out, in, 1, 1], conv bias, BatchNorm weight, bias; stats: per layer
+    the module's (running_mean, running_var) buffers, updated in place by the forward and NOT saved -- the backward takes the batch
+    statistics the forward wrote (save_mean, save_invstd), so a later forward cannot change an earlier one's gradient.  Exact fp32 whatever
+    the matrix precision is (csrc/set_abstraction_train.hip)."""
+
+    @staticmethod
+    def forward(ctx, eps, momentum, stats, x, centres, group_idx, feats, *tensors):
+        layers = [layer + tuple(st) for layer, st in zip(_fp_train_layers(tensors), stats)]
+        out, save_mean, save_invstd = sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum)
+        ctx.save_for_backward(x, centres, group_idx, feats, save_mean, save_invstd, *tensors)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, centres, group_idx, feats, save_mean, save_invstd, *tensors = ctx.saved_tensors
+        layers = _fp_train_layers(tensors)
+        need_grad = ctx.needs_input_grad
+        dfeats = torch.empty_like(feats) if feats is not None and need_grad[6] else None
+        grads = [tuple(torch.empty_like(t) for t in layer) for layer in layers]
+        need = _lib.sa_train_backward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], centres.shape[1], group_idx.shape[2],
+                                                      [layer[0].shape[0] for layer in layers])
+        _lib.sa_train_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, save_mean, save_invstd, dout.contiguous().float(), dfeats,
+                                   grads, torch.empty(need, dtype=torch.uint8, device=x.device), arg_out=None)
+        ret = [None, None, None, None, None, None, dfeats]
+        for l, g in enumerate(grads):
+            w = tensors[4 * l]
+            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3])):     # the conv weight keeps its [out, in, 1, 1]; dbias is zeros
+                ret.append(t if need_grad[7 + 4 * l + q] else None)
+        return tuple(ret)
+
+
+def sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum):
+    """ampnet_sa_train_forward_f32 on layers of six tensors (the running statistics are updated in place) -> (out, save_mean, save_invstd)."""
+    couts = [int(layer[0].shape[0]) for layer in layers]
+    out = torch.empty((x.shape[0], centres.shape[1], couts[-1]), dtype=torch.float32, device=x.device)
+    save_mean, save_invstd = (torch.empty(sum(couts), dtype=torch.float32, device=x.device) for _ in range(2))
+    need = _lib.sa_train_forward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], centres.shape[1], group_idx.shape[2], couts)
+    _lib.sa_train_forward_f32(x, centres, group_idx, feats, layers, eps, momentum, out, save_mean, save_invstd,
+                              torch.empty(need, dtype=torch.uint8, device=x.device))
+    return out, save_mean, save_invstd
+
+
+def sa_train_apply(module, x, centres, group_idx, feats, momentum):
+    """Grad-mode, train-mode forward of a PointNetSetAbstraction block on point-major rows (as sa_apply): batch statistics over all
+    B * npoint * nsample rows, the module's running statistics updated in place, a graph to feats and the block's conv and BatchNorm affine
+    parameters (the conv bias gets zeros: it has no effect on a batch-normalised output)."""
+    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns) for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
+    stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
+    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats, *tensors)

@@ -35,33 +35,12 @@
 //       dbeta, dgamma = invstd (G - mu dbeta), dbias = 0 and the two coefficients dbeta / M and dgamma invstd / M of the next phase.
 //   fpb_wgrad_launch, fp_scatter_launch   dW_l = dz_l^T x_l and dpoints2, exactly the eval backward's.
 //   A phase holds two tiles of the widest layer input (at most 131 KB), so the eval backward's shared-space special case is not needed.
+#include "bn_train.h"
 #include "fp_bwd_tiles.h"
 
 namespace ampnet {
 
 constexpr long long FPT_MAX_ROWS = AMPNET_FP_TRAIN_MAX_ROWS;    // the merges carry row counts as floats: exact up to here, larger M is refused
-
-// Chan's merge of (nA, meanA, M2A) and (nB, meanB, M2B) into A; nA = 0 takes B as it is
-__device__ __forceinline__ void fpt_chan(float &nA, float &meanA, float &m2A, float nB, float meanB, float m2B)
-{
-    if (nA == 0.0f) {
-        nA = nB;
-        meanA = meanB;
-        m2A = m2B;
-        return;
-    }
-    const float n = nA + nB, delta = meanB - meanA;
-    meanA = fmaf(delta, nB / n, meanA);
-    m2A = fmaf(delta * delta, nA * nB / n, m2A + m2B);
-    nA = n;
-}
-
-struct FptStats {                         // what the finalize of pass l reads and writes
-    const float *bias, *gamma, *beta;
-    float *running_mean, *running_var, *save_mean, *save_invstd;
-    float eps, momentum;
-    int cout, fold_off;
-};
 
 // the statistics of NT column tiles of layer l from n0 over the valid rows of the wave's tile, merged into the workgroup's partial row
 template <int NT, bool VEC>
@@ -551,3 +530,28 @@ extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const 
     }
     return fp_scatter_launch(b.dx0, D2, n_clouds, n, s, idx, dist2, k, dpoints2, st);
 }
+
+namespace ampnet {
+
+// bn_train.h: the kernels above that the train-mode set abstraction launches too
+int fpt_stats_finalize_launch(const FptStats &q, const float *parts, int n_parts, long long M, float *fold, hipStream_t st)
+{
+    hipLaunchKernelGGL(fpt_stats_finalize_kernel, dim3(cdiv(q.cout, 4)), dim3(256), 0, st, q, parts, n_parts, (float)M, fold);
+    return check_launch("fpt_stats_finalize_kernel");
+}
+
+int fpt_fold_launch(const MlpPlan &p, const MlpFold &f, float *fold, hipStream_t st)
+{
+    hipLaunchKernelGGL(fpt_fold_kernel, dim3(1), dim3(256), 0, st, p, f, fold);
+    return check_launch("fpt_fold_kernel");
+}
+
+int fpt_bwd_finalize_launch(int cout, const float *parts, int n_parts, long long M, const float *mean, const float *invstd, float *dbias,
+                            float *dgamma, float *dbeta, float *coef, hipStream_t st)
+{
+    hipLaunchKernelGGL(fpt_bwd_finalize_kernel, dim3(cdiv(cout, 4)), dim3(256), 0, st, cout, parts, n_parts, (float)M, mean, invstd, dbias, dgamma,
+                       dbeta, coef);
+    return check_launch("fpt_bwd_finalize_kernel");
+}
+
+}  // namespace ampnet

@@ -10,7 +10,7 @@
 //   * The contraction order inside a block of 8 is K_PAIRS (k = k0 + 2 i + h); weights that are not staged are read dword by dword.
 //   * The last layer writes nothing to LDS: its relu'd accumulators are reduced over their 16 registers and the two lane halves (the
 //     row dimension) and lanes h = 0 store the maxima.
-#include "fused_mlp.h"
+#include "sa_tiles.h"
 
 namespace ampnet {
 
@@ -61,6 +61,18 @@ __global__ __launch_bounds__(256) void sa_forward_kernel(MlpPlan p, const float 
     }
 }
 
+int sa_forward_launch(const char *what, const MlpPlan &p, int lds, const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s,
+                      const int32_t *group_idx, int nsample, const float *feats, int D, const float *fold, float *out, hipStream_t st)
+{
+    static bool attr_set = false;
+    int rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_forward_kernel), attr_set);
+    if (rc != AMPNET_OK) return rc;
+    const int n_groups = n_clouds * s;
+    hipLaunchKernelGGL(sa_forward_kernel, dim3(mlp_grid(n_groups, p.nw)), dim3(64 * p.nw), lds, st, p, xyz, n, ld, centres, s, group_idx, nsample,
+                       feats, D, fold, n_groups, out);
+    return check_launch("sa_forward_kernel");
+}
+
 }  // namespace ampnet
 
 extern "C" int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
@@ -81,14 +93,9 @@ extern "C" int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int 
     MlpFold f;
     const int lds = mlp_plan_build("ampnet_sa_forward_f32", 3 + D, nsample <= 32 ? 32 : 64, params_host, cout_host, eps_host, L, p, f);
     if (!lds) return AMPNET_E_ARG;
-    static bool attr_set = false;
-    int rc = mlp_allow_full_lds("ampnet_sa_forward_f32", reinterpret_cast<const void *>(sa_forward_kernel), attr_set);
-    if (rc != AMPNET_OK) return rc;
     float *fold = static_cast<float *>(workspace);
-    rc = mlp_fold_launch(p, f, fold, (hipStream_t)stream);
+    int rc = mlp_fold_launch(p, f, fold, (hipStream_t)stream);
     if (rc != AMPNET_OK) return rc;
-    const int n_groups = n_clouds * s;
-    hipLaunchKernelGGL(sa_forward_kernel, dim3(mlp_grid(n_groups, p.nw)), dim3(64 * p.nw), lds, (hipStream_t)stream, p, xyz, n, ld, centres, s,
-                       group_idx, nsample, feats, D, fold, n_groups, out);
-    return check_launch("sa_forward_kernel");
+    return sa_forward_launch("ampnet_sa_forward_f32", p, lds, xyz, n_clouds, n, ld, centres, s, group_idx, nsample, feats, D, fold, out,
+                             (hipStream_t)stream);
 }

@@ -26,11 +26,9 @@
 //       per column.  No float atomics; a point in no group gets zeros.
 //
 // Every order above is a function of the shape alone: two runs give the same bits.  Exact fp32 MFMA whatever the matrix precision is.
-#include "mlp_bwd.h"
+#include "sa_tiles.h"
 
 namespace ampnet {
-
-constexpr int SAB_MAX_GRID = 2048;        // workgroups (= rows of the partials array) of sa_backward_kernel
 
 struct SaBwdPlan {
     int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];   // tile X_l: float offset in LDS, odd row stride
@@ -38,33 +36,6 @@ struct SaBwdPlan {
     int sum_c;                                                 // sum of cout_l; layer l's channels start at fold_off[l] / 2
     float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts;
 };
-
-// the accumulators of NT column tiles from n0 on the 32 rows whose operand pointer is xr = x + (m0 + r) ldx + h: the forward's
-// mlp_tiles<NT, K_PAIRS, false> on weights read from global memory
-template <int NT>
-__device__ __forceinline__ void sab_accumulate(f32x16 (&acc)[NT], const float *xr, const float *__restrict__ w, int cin, int kp, int n0, int r,
-                                               int h)
-{
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    for (int k0 = 0; k0 < kp; k0 += 8) {
-        float av[4], bv[NT][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = xr[k0 + 2 * i];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const float *wr = w + (size_t)(n0 + 32 * t + r) * cin + k0 + h;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[t][i] = k0 + h + 2 * i < cin ? wr[2 * i] : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
-}
 
 // A layer below the last: d [R][ldd] holds dx_{l+1} on entry and dz on exit; dz_ws: the group's rows of the workspace.
 template <int NT>
@@ -169,50 +140,6 @@ __device__ __forceinline__ void sab_last(const float *x, int ldx, const float *_
             part_b[col] += dy;
             part_g[col] += dy * ba[t];
             if (arg_g) arg_g[col] = brow[t];
-        }
-    }
-}
-
-// dx = dz W for NT column tiles of the layer's INPUT from c0 on the 32 rows of d [32][ldd] (fpb_dgrad's lane map and order: o ascending
-// in blocks of 8, k-step i of lane half h takes o = o0 + 2 i + h).  Results go to tile `xo` (l >= 1) or, xo == nullptr, columns
-// [3, cin) of the rows < rows to dx0 [.][D] (layer 0).
-template <int NT>
-__device__ __forceinline__ void sab_dgrad(const float *d, int ldd, const float *__restrict__ w, int cin, int cout, int c0, float *xo, int ldxo,
-                                          float *__restrict__ dx0, int D, int rows, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    const float *dr = d + r * ldd + h;
-    for (int o0 = 0; o0 < cout; o0 += 8) {
-        float av[4], bv[NT][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = dr[o0 + 2 * i];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int c = c0 + 32 * t + r;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[t][i] = c < cin ? w[(size_t)(o0 + 2 * i + h) * cin + c] : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = c0 + 32 * t + r;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (xo) {
-                if (c < cin) xo[row * ldxo + c] = acc[t][i];
-            } else if (row < rows && c >= 3 && c < cin) {
-                dx0[(size_t)row * D + c - 3] = acc[t][i];
-            }
         }
     }
 }
@@ -322,15 +249,7 @@ __global__ __launch_bounds__(64) void sa_dfeats_kernel(const float *__restrict__
         if (lane + 64 * u < D) dst[lane + 64 * u] = acc[u];
 }
 
-// what both entry points derive from the shape: the launch sizes, the LDS tiles and the workspace layout (float offsets, multiples of 64)
-struct SaBwdShape {
-    long long M;
-    int R, n_groups, grid, chunk_rows, chunks, sum_c, lds_floats;
-    int cin[MLP_MAX_LAYERS], ldxs[MLP_MAX_LAYERS], off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];
-    size_t off_parts, off_xs[MLP_MAX_LAYERS], off_dz[MLP_MAX_LAYERS], off_dx0, off_wpart, floats;
-};
-
-static int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SaBwdShape &sh)
+int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SaBwdShape &sh)
 {
     AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
     AMPNET_REQUIRE(n_clouds >= 1 && s >= 1, "%s: bad shape n_clouds=%d s=%d", what, n_clouds, s);
@@ -377,6 +296,12 @@ static int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, 
     off += align_up((size_t)sh.chunks * wmax, 64);
     sh.floats = off;
     return AMPNET_OK;
+}
+
+int sa_dfeats_launch(const float *dx0, int D, int n_clouds, int n, int s, int nsample, const int32_t *group_idx, float *dfeats, hipStream_t st)
+{
+    hipLaunchKernelGGL(sa_dfeats_kernel, dim3(n_clouds * n), dim3(64), 0, st, dx0, D, n, s, nsample, group_idx, dfeats);
+    return check_launch("sa_dfeats_kernel");
 }
 
 }  // namespace ampnet
@@ -446,8 +371,7 @@ extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int
         if (rc != AMPNET_OK) return rc;
     }
     if (dfeats) {
-        hipLaunchKernelGGL(sa_dfeats_kernel, dim3(n_clouds * n), dim3(64), 0, st, b.dx0, D, n, s, nsample, group_idx, dfeats);
-        rc = check_launch("sa_dfeats_kernel");
+        rc = sa_dfeats_launch(b.dx0, D, n_clouds, n, s, nsample, group_idx, dfeats, st);
         if (rc != AMPNET_OK) return rc;
     }
     return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);

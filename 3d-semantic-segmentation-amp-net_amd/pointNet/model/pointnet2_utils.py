@@ -18,12 +18,14 @@ that attains it.  running_mean and running_var are constants of both backwards a
 and farthest-point sampling, ball query and the gather of the centres run under no_grad.  That is what fitting a pretrained backbone to
 new clouds needs (pointnetAtt.pointnet_2(decoder_grad=True, encoder_grad=True)).
 
-Train-mode BatchNorm is opt-in too, and built for the feature propagation only: PointNetFeaturePropagation(..., batch_stats=True) in
-TRAIN mode normalises with the statistics of the batch (all B * N rows of the call), updates running_mean / running_var in place with
-each BatchNorm's `momentum` and counts num_batches_tracked (ampnet_fp_train_forward_f32); with grad=True its backward goes through the
-statistics (ampnet_fp_train_backward_f32 through autograd._FpTrainFn), as torch's does.  In eval mode the flag changes nothing.
-Not built: train-mode BatchNorm in the set abstraction (its .train() still raises), momentum=None, gradients to coordinates,
-`group_all=True`.
+Train-mode BatchNorm is opt-in too: PointNetFeaturePropagation(..., batch_stats=True) in TRAIN mode normalises with the statistics of
+the batch (all B * N rows of the call), updates running_mean / running_var in place with each BatchNorm's `momentum` and counts
+num_batches_tracked (ampnet_fp_train_forward_f32); with grad=True its backward goes through the statistics
+(ampnet_fp_train_backward_f32 through autograd._FpTrainFn), as torch's does.  PointNetSetAbstraction(..., batch_stats=True) does the same
+over all B * npoint * nsample rows of its groups -- the slots that ball query filled by repeating a group's first member are rows like any
+other, as they are for BatchNorm2d over [B, C, nsample, npoint] (ampnet_sa_train_forward_f32, ampnet_sa_train_backward_f32 through
+autograd._SaTrainFn).  In eval mode the flag changes nothing, and without it .train() still raises.
+Not built: momentum=None, gradients to coordinates, `group_all=True`.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
 from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
@@ -55,7 +57,7 @@ class _BN2d(nn.Module):
     def __init__(self, c, device, eps=1e-5):
         super().__init__()
         self.eps = eps
-        self.momentum = 0.1                       # (an attribute, not a state_dict key; used by train-mode feature propagation only)
+        self.momentum = 0.1                       # (an attribute, not a state_dict key; used by the batch_stats=True blocks in train mode)
         self.weight = nn.Parameter(torch.ones(c, device=device))
         self.bias = nn.Parameter(torch.zeros(c, device=device))
         self.register_buffer("running_mean", torch.zeros(c, device=device))
@@ -88,17 +90,25 @@ def _workspace(mod, nbytes, device):
     return mod._ws
 
 
+_SA_EVAL_ONLY = "the HIP set abstraction is built for eval mode (BatchNorm running statistics, no backward): call .eval() first"
+
+
 class PointNetSetAbstraction(nn.Module):
     """One set-abstraction layer: `npoint` centres by farthest-point sampling, per centre the first `nsample` points within `radius`
     (utils.ball_query), the shared MLP `mlp` (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on [relative xyz, point features], max over the
     group.  `in_channel` counts the 3 coordinates, as in the usual implementation.
     grad=True: in eval mode, with grad mode on and `points` or a parameter that requires grad, new_points carries a graph to `points` and
     the conv / BatchNorm affine parameters (the running statistics stay frozen; new_xyz never carries one).  grad=False (default): no
-    graph, ever."""
+    graph, ever.
+    batch_stats=False (default): eval mode only, the running statistics frozen; train mode raises.  batch_stats=True: train mode is
+    accepted and runs BatchNorm on the statistics of all B * npoint * nsample rows, updating running_mean / running_var (momentum: the
+    `momentum` attribute of the block's mlp_bns, one value for the block) and num_batches_tracked once per forward, graph or not; with
+    grad=True the backward goes through the statistics; eval mode is unchanged."""
 
-    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda', grad=False):
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda', grad=False, batch_stats=False):
         super().__init__()
         self.grad = bool(grad)
+        self.batch_stats = bool(batch_stats)
         if group_all:
             raise NotImplementedError("the HIP set abstraction is built for group_all=False (ball-query groups of <= 64 points); "
                                       "the single all-points group is not")
@@ -110,9 +120,8 @@ class PointNetSetAbstraction(nn.Module):
     def forward(self, xyz, points, centres=None):
         """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]).
         centres: int32 [B, npoint] point indices to use instead of farthest-point sampling from point 0."""
-        if self.training:
-            raise NotImplementedError("the HIP set abstraction is built for eval mode (BatchNorm running statistics, no backward): "
-                                      "call .eval() first")
+        if self.training and not self.batch_stats:
+            raise NotImplementedError(_SA_EVAL_ONLY)
         _lib.require_gpu(xyz, "xyz")
         if xyz.dim() != 3 or xyz.shape[1] != 3:
             raise _lib.AmpnetError(f"PointNetSetAbstraction: expected xyz [B, 3, N], got {tuple(xyz.shape)}")
@@ -154,6 +163,8 @@ class PointNetSetAbstraction(nn.Module):
             group_idx = U.ball_query(x, centres, self.radius, self.nsample)       # validates the centres
             centres = centres.contiguous()
             new_xyz = U.gather_rows(x, centres)
+        if self.training:
+            return new_xyz, self._train_rows(x, centres, group_idx, feats)
         if self._wants_grad(feats):
             from ... import autograd
             return new_xyz, autograd.sa_apply(self, x, centres, group_idx, feats, _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
@@ -163,6 +174,31 @@ class PointNetSetAbstraction(nn.Module):
         _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out,
                             _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
         return new_xyz, out
+
+
+    def _train_rows(self, x, centres, group_idx, feats):
+        """The fused layer of _forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when
+        one is wanted."""
+        if not self.batch_stats:
+            raise NotImplementedError(_SA_EVAL_ONLY)
+        momenta = {bn.momentum for bn in self.mlp_bns}
+        if None in momenta or len(momenta) != 1:
+            raise NotImplementedError("train-mode set abstraction takes one float momentum for the block's BatchNorms, got "
+                                      f"{[bn.momentum for bn in self.mlp_bns]} (momentum=None, the cumulative average, is not built)")
+        momentum = float(momenta.pop())
+        from ... import autograd
+        if self._wants_grad(feats):
+            out = autograd.sa_train_apply(self, x, centres, group_idx, feats, momentum)
+        else:
+            with torch.no_grad():
+                layers = [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
+                           bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(), bn.running_mean, bn.running_var)
+                          for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
+                out, _, _ = autograd.sa_train_forward(x, centres, group_idx, None if feats is None else feats.detach(), layers,
+                                                      [bn.eps for bn in self.mlp_bns], momentum)
+        with torch.no_grad():
+            torch._foreach_add_([bn.num_batches_tracked for bn in self.mlp_bns], 1)
+        return out
 
 
 def _mlp_tensors(mod):

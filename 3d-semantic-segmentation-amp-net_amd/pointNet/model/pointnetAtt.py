@@ -438,21 +438,34 @@ class pointnet_2(nn.Module):
 
     decoder_batch_stats=True (needs decoder_grad=True, else ValueError) lets the decoder TRAIN as torch trains it: `fp3`, `fp2`, `fp1` are
     built with batch_stats=True, and .train(mode) puts the model, fp1..fp3 and conv1 in `mode` while `sa1`..`sa3` stay in eval mode
-    whatever encoder_grad is -- the encoder remains a frozen-statistics feature extractor (train-mode set abstraction is not built).  In
-    train mode fp1..fp3 normalise with batch statistics, update their running statistics and back-propagate through them."""
+    whatever encoder_grad is -- without encoder_batch_stats the encoder remains a frozen-statistics feature extractor.  In
+    train mode fp1..fp3 normalise with batch statistics, update their running statistics and back-propagate through them.
 
-    def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False):
+    encoder_batch_stats=True (needs encoder_grad=True and decoder_batch_stats=True, else ValueError) trains the model from scratch as
+    torch trains it: `sa1`..`sa3` are built with batch_stats=True and .train(mode) puts the WHOLE model in `mode`.  In train mode every
+    block normalises with the statistics of its batch (the set abstraction over all B * npoint * nsample rows), updates its running
+    statistics and num_batches_tracked, and back-propagates through the statistics."""
+
+    def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False,
+                 encoder_batch_stats=False):
         super().__init__()
         self.decoder_grad = bool(decoder_grad)
         self.encoder_grad = bool(encoder_grad)
         self.decoder_batch_stats = bool(decoder_batch_stats)
+        self.encoder_batch_stats = bool(encoder_batch_stats)
+        if self.encoder_batch_stats and not (self.encoder_grad and self.decoder_batch_stats):
+            raise ValueError("pointnet_2: encoder_batch_stats=True needs encoder_grad=True and decoder_batch_stats=True (train mode is for "
+                             "training the whole backbone)")
         if self.decoder_batch_stats and not self.decoder_grad:
             raise ValueError("pointnet_2: decoder_batch_stats=True needs decoder_grad=True (train mode is for training the decoder)")
         if self.encoder_grad and not self.decoder_grad:
             raise ValueError("pointnet_2: encoder_grad=True needs decoder_grad=True (the gradient reaches sa1..sa3 through fp1..fp3)")
-        self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device, grad=self.encoder_grad)
-        self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device, grad=self.encoder_grad)
-        self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device, grad=self.encoder_grad)
+        self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, 9 + 3, [32, 32, 64], False, device=device, grad=self.encoder_grad,
+                                          batch_stats=self.encoder_batch_stats)
+        self.sa2 = PointNetSetAbstraction(256, 0.2, 32, 64 + 3, [64, 64, 128], False, device=device, grad=self.encoder_grad,
+                                          batch_stats=self.encoder_batch_stats)
+        self.sa3 = PointNetSetAbstraction(64, 0.4, 32, 128 + 3, [128, 128, 256], False, device=device, grad=self.encoder_grad,
+                                          batch_stats=self.encoder_batch_stats)
         self.fp3 = PointNetFeaturePropagation(384, [256, 256], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
         self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
         self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
@@ -460,7 +473,7 @@ class pointnet_2(nn.Module):
 
     def train(self, mode=True):
         super().train(mode)
-        if self.decoder_batch_stats:                                                  # the encoder keeps its frozen statistics
+        if self.decoder_batch_stats and not self.encoder_batch_stats:                 # the encoder keeps its frozen statistics
             for m in (self.sa1, self.sa2, self.sa3):
                 m.train(False)
         return self
@@ -473,8 +486,9 @@ class pointnet_2(nn.Module):
         if xyz.dim() != 3 or xyz.shape[1] != 9:
             raise _lib.AmpnetError(f"pointnet_2: expected xyz [B, 9, N], got {tuple(xyz.shape)}")
         for m in (self.sa1, self.sa2, self.sa3):
-            if m.training:
-                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model")
+            if m.training != (self.training and self.encoder_batch_stats):
+                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
+                                          "pointnet_2: sa1..sa3 follow the model's mode; call .train() on the model, not on its blocks")
         for m in (self.fp3, self.fp2, self.fp1):
             if m.training != self.training:
                 raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else

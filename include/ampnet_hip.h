@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 13
+#define AMPNET_ABI_VERSION 14
 
 enum {
     AMPNET_OK = 0,
@@ -489,6 +489,62 @@ int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int ld, const 
                            const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- ampnet_sa_forward_f32 and its backward with TRAIN-mode BatchNorm: batch statistics (encoder training; new in ABI 14) -------------
+ * Forward.  The arguments of ampnet_sa_forward_f32, and (as in ampnet_fp_train_forward_f32):
+ *   params_host           per layer W, b, gamma, beta, running_mean, running_var as before; running_mean and running_var are READ AND WRITTEN
+ *   momentum              a float in [0, 1] (anything else, NaN included, is refused)
+ *   save_mean, save_invstd   [sum_l cout_l] float32 out each, layer l at offset sum_{j<l} cout_j: the batch mean of the raw accumulator
+ *                         (WITHOUT the conv bias) and 1 / sqrt(var + eps).  The backward takes them; it never recomputes statistics.
+ *   workspace             ampnet_sa_train_forward_workspace_bytes(D, n_clouds, s, nsample, cout_host, L) device bytes (0 = the shape is
+ *                         refused): the fold and min(n_clouds s, 1024) partial rows of 3 max_l cout_l floats, whatever M is
+ * Rows.  M = n_clouds s nsample; the rows (g, t), t < nsample, are those of the eval forward.  A slot that ball query filled by repeating
+ * its first member is a row like any other: it enters the statistics, it gets a (generally nonzero) dz from the correction terms below and
+ * it contributes to dW and dfeats -- what BatchNorm2d over [B, C, nsample, npoint] does.  The rows t >= nsample that pad a group to 32 or 64
+ * enter nothing.
+ * Per layer l over the M rows, with a = W x the raw accumulator in the eval forward's contraction order (k ascending in blocks of 8, k-step
+ * i < 4 of lane half h takes k = k0 + 2 i + h, one fmaf chain per element), the formulas of ampnet_fp_train_forward_f32:
+ *     mu = mean_rows a      var = mean_rows (a - mu)^2 (biased)      invstd = 1 / sqrt(var + eps)      scale = gamma invstd
+ *     shift = fma(-mu, scale, beta)   (the conv bias cancels)      y = fma(a, scale, shift)      x_{l+1} = relu(y)
+ *     running_mean <- fma(m, mu + b, (1 - m) running_mean)      running_var <- fma(m, var M / (M - 1), (1 - m) running_var)
+ * The variance is CENTRED: per column, group and 32-row tile of the group the count, the mean and sum (a - tile mean)^2 of the tile's rows
+ * t < nsample (rows in the accumulator's order (i & 3) + 8 (i >> 2), i < 16, lane half 0 + half 1); they are merged with Chan's formula
+ * (ampnet_fp_train_forward_f32) first into P = min(groups, 1024) partial rows (row r: the groups r, r + P, .. ascending, a group's tiles
+ * ascending), then over the rows: lane t of a wave merges rows t, t + 64, .. ascending and the 64 lane results go through a halving tree
+ * (lane t takes lane t + 32, 16, .. 1).  Pass l recomputes layers < l from the inputs; no activation is written to memory.  The last
+ * launch is the eval forward's own kernel on the fold (scale, shift) so formed: `out` is the max of what the statistics were taken from.
+ * Backward.  The arguments of ampnet_sa_backward_f32 with, per layer, save_mean_l and save_invstd_l (pointers into the forward's two
+ * arrays) in slots 4 and 5 of params_host in place of running_mean and running_var; b (slot 1) is not read.  scale and shift are rebuilt
+ * from them by the forward's two operations (the same bits).
+ *   arg(g, c)  the lowest t in [0, nsample) whose float32 relu(y) attains the group's maximum, y = fma(a, scale, shift); written to arg_out
+ *              (may be NULL).  dx_L[(g, t), c] = dout[g, c] at t = arg(g, c), 0 elsewhere.
+ *     dy = dx_{l+1} [y > 0]      dbeta = sum_rows dy      G = sum_rows dy a      dgamma = invstd fma(-mu, dbeta, G)      dbias = 0 (exact zeros)
+ *     dz = scale fma(-(a - mu), dgamma invstd / M, dy - dbeta / M)   for EVERY row t < nsample      dW_l = dz^T x_l      dx_l = dz W_l
+ * dfeats is the ordered gather of dx_0[:, 3:] as in ampnet_sa_backward_f32; xyz gets no gradient.  dz_l needs the sums over all rows, so
+ * the backward is L + 1 phases with a finalize between them; the last layer's dy is kept as arg plus dout, never as a dense array.
+ * Summation orders: a, y, dx_l, dW_l and dfeats as in ampnet_sa_backward_f32;
+ *   dbeta, G  the last layer: one term dout[g, c] (times a at arg) per group; the other layers: per 32-row tile (g, m) the rows in the
+ *             accumulator's order, lane half 0 then + half 1.  A workgroup adds its groups (the last layer) or tiles (tile = 2 g + m at
+ *             nsample > 32, else g) w, w + P, .. ascending, P = min(groups, 2048); lane t of a wave adds workgroups t, t + 64, ..
+ *             ascending and the 64 lane sums go through a halving tree
+ * Workspace of the backward: ampnet_sa_train_backward_workspace_bytes(...) device bytes -- the layout of ampnet_sa_backward_f32 (x_l and dz_l
+ * of all M rows, dx_0's feature columns, the split-K partials, the channel sums), then 2 sum_l cout_l coefficients and the n_clouds s
+ * cout_{L-1} int32 of arg.
+ * Limits and refusals (all four entry points, AMPNET_E_ARG with a sentence): those of ampnet_sa_forward_f32 and of ampnet_sa_backward_f32,
+ * its 64-row LDS limit included (a shape that trains has a backward), plus M < 2, M > AMPNET_SA_TRAIN_MAX_ROWS (the statistics carry row
+ * counts as floats, exact up to there), the momentum range and a short workspace.  No float atomics: two calls return the same bits.  Exact
+ * fp32 MFMA whatever the matrix precision is.  Caller's stream, no host synchronisation.                                              */
+#define AMPNET_SA_TRAIN_MAX_ROWS (1 << 24)
+size_t ampnet_sa_train_forward_workspace_bytes(int D, int n_clouds, int s, int nsample, const int *cout_host, int L);
+int ampnet_sa_train_forward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                                int nsample, const float *feats, int D, float *const *params_host, const int *cout_host,
+                                const float *eps_host, int L, float momentum, float *out, float *save_mean, float *save_invstd,
+                                void *workspace, size_t workspace_bytes, void *stream);
+size_t ampnet_sa_train_backward_workspace_bytes(int D, int n_clouds, int s, int nsample, const int *cout_host, int L);
+int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                                 int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                                 const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =
  * n_points, n_init 5, max_iter 10, tol 1e-2, features x, y, NDVI) and utils/utils.py:500-505 (size_min only).  That package is not part
@@ -811,6 +867,14 @@ int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream);
 int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void *stream);
 int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream);
 int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, int cout, int stat_chunks, const AmpnetPwBwdProbe *bwd, AmpnetPwPlan *out_host);
+
+/* The tape of ampnet_sa_train_backward_f32 (csrc/set_abstraction_train.hip; tests/test_sa_train_gpu.py checks every layer alone on it).
+ * For layer l < L of the shape (D, n_clouds, s, nsample, cout_host, L): the byte offsets inside the backward's workspace, and the row
+ * strides in floats, of x_l (the layer's input rows, stride = cin_l rounded up to 32, the padded columns zero) and dz_l (stride cout_l).
+ * Both hold the M = n_clouds s nsample rows (g, t), t < nsample, in that order, and are valid after ampnet_sa_train_backward_f32 has
+ * returned (and its stream has run) until the workspace is written again.  Launches nothing; the shape's refusals are the backward's. */
+int ampnet_sa_train_backward_tape(int D, int n_clouds, int s, int nsample, const int *cout_host, int L, int l, size_t *x_offset_bytes,
+                                  int *x_stride, size_t *dz_offset_bytes, int *dz_stride);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,14 @@ fp_bwd_finalize_kernel) against torch.autograd's backward of the torch compositi
 only the backward is timed); the two are timed in alternating rounds and every round is reported.  sa1's features are the input data, so
 its dfeats is not requested, as in the model; sa2 and sa3 are also timed without dfeats, which prices layer 0's dx plus the gather.
 python3 tools/prof_sa.py [steps] [warmup] trace  -- runs nothing but the fused backward, `steps` times per shape, for a
-`rocprofv3 --kernel-trace --stats` run that splits it by kernel (sa2 and sa3 with dfeats: sa_dfeats_kernel's own time is in that split)."""
+`rocprofv3 --kernel-trace --stats` run that splits it by kernel (sa2 and sa3 with dfeats: sa_dfeats_kernel's own time is in that split).
+The train-mode leg, at the same three shapes: the fused train forward and backward (ampnet_sa_train_forward_f32: sat_stats_kernel +
+fpt_stats_finalize_kernel per layer, sa_forward_kernel; ampnet_sa_train_backward_f32: fpt_fold_kernel, sat_bwd_last_kernel,
+sat_bwd_phase_kernel per remaining phase, fpt_bwd_finalize_kernel per layer, fp_wgrad_kernel + fp_wgrad_reduce_kernel per layer,
+sa_dfeats_kernel) against torch's train-mode composition (batch_norm(training=True), forward under no_grad and the backward of a retained
+graph) and against this project's eval forward and eval backward, in alternating rounds, every round reported.
+python3 tools/prof_sa.py [steps] [warmup] train        -- the train-mode leg alone; prints one JSON line.
+python3 tools/prof_sa.py [steps] [warmup] train-trace  -- nothing but the fused train forward and backward, for a kernel trace."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,7 +26,8 @@ U = importlib.import_module(PKG + ".utils.utils")
 L = importlib.import_module(PKG + "._lib")
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 warmup = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-trace_only = len(sys.argv) > 3 and sys.argv[3] == "trace"
+mode = sys.argv[3] if len(sys.argv) > 3 else ""
+trace_only = mode == "trace"
 B, N, S, K, D, MLP, RADIUS = 16, 8192, 1024, 32, 9, [32, 32, 64], 0.1
 dev = "cuda"
 xyz = torch.from_numpy(synth.clouds(200, B, N)).to(dev)
@@ -140,6 +148,88 @@ def backward_leg():
     return res
 
 
+def train_leg(trace):
+    """-> {block: figures} for sa1, sa2, sa3 of pointnet_2 at B = 16 in train mode (batch statistics over all B npoint nsample rows)."""
+    res, pts = {}, xyz
+    for block, (s_, k_, d_, mlp, radius, want_df) in {"sa1": (1024, 32, 9, [32, 32, 64], 0.1, False), "sa2": (256, 32, 64, [64, 64, 128], 0.2, True),
+                                                      "sa3": (64, 32, 128, [128, 128, 256], 0.4, True)}.items():
+        n_ = pts.shape[1]
+        f = torch.from_numpy(synth.uniform(220 + d_, (B, n_, d_), -1.0, 1.0)).to(dev)
+        c = U.fps_indices(pts, s_)
+        gi = U.ball_query(pts, c, radius, k_)
+        lay = make_layers(3 + d_, mlp, d_)                                    # the fused side's own running statistics
+        dout = torch.from_numpy(synth.uniform(230 + d_, (B, s_, mlp[-1]), -1.0, 1.0)).to(dev)
+        eps, sum_c = [1e-5] * len(mlp), sum(mlp)
+        fws = torch.empty(L.sa_train_forward_workspace_bytes(d_, B, s_, k_, mlp), dtype=torch.uint8, device=dev)
+        bws = torch.empty(L.sa_train_backward_workspace_bytes(d_, B, s_, k_, mlp), dtype=torch.uint8, device=dev)
+        ews = torch.empty(L.sa_backward_workspace_bytes(d_, B, s_, k_, mlp), dtype=torch.uint8, device=dev)
+        sm, si = torch.empty(sum_c, device=dev), torch.empty(sum_c, device=dev)
+        o, df = torch.empty((B, s_, mlp[-1]), device=dev), torch.empty_like(f)
+        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in lay]
+        fused_f = lambda: L.sa_train_forward_f32(pts, c, gi, f, lay, eps, 0.1, o, sm, si, fws)
+        fused_b = lambda: L.sa_train_backward_f32(pts, c, gi, f, lay, eps, sm, si, dout, df if want_df else None, grads, bws)
+        if trace:
+            for _ in range(steps):
+                fused_f()
+                fused_b()
+            torch.cuda.synchronize()
+            pts = U.gather_rows(pts, c)
+            continue
+        e_lay = make_layers(3 + d_, mlp, d_)
+        eval_f = lambda: L.sa_forward_f32(pts, c, gi, f, e_lay, eps, o, ws)
+        eval_b = lambda: L.sa_backward_f32(pts, c, gi, f, e_lay, eps, dout, df if want_df else None, grads, ews)
+        p_lay = make_layers(3 + d_, mlp, d_)                                  # torch's own running statistics
+        bi = torch.arange(B, device=dev)[:, None, None]
+        fg = f.detach().clone().requires_grad_(want_df)
+        leaves = ([fg] if want_df else []) + [t.requires_grad_(True) for layer in p_lay for t in layer[:4]]
+
+        def torch_train():
+            g_xyz = pts[bi, gi.long()] - pts[torch.arange(B, device=dev)[:, None], c.long()][:, :, None, :]
+            x = torch.cat([g_xyz, fg[bi, gi.long()]], -1).permute(0, 3, 1, 2)
+            for w, bias, gamma, beta, mean, var in p_lay:
+                x = torch.relu(torch.nn.functional.batch_norm(torch.nn.functional.conv2d(x, w[:, :, None, None], bias), mean, var, gamma, beta, True,
+                                                              0.1, 1e-5))
+            return x.max(-1)[0].transpose(1, 2)
+
+        def torch_f():
+            with torch.no_grad():
+                torch_train()
+
+        t_out = torch_train()
+        torch_b = lambda: torch.autograd.grad(t_out, leaves, dout, retain_graph=True)
+        rounds = [(timed(fused_f), timed(torch_f), timed(fused_b), timed(torch_b), timed(eval_f), timed(eval_b)) for _ in range(3)]
+        fused_f()
+        fused_b()
+        t_grads = torch_b()
+        rel = lambda a, b_: float((a - b_).abs().max() / b_.abs().max())
+        diff = {"out": rel(o, t_out.detach())}
+        if want_df:
+            diff["dfeats"] = rel(df, t_grads[0])
+        for l in range(len(mlp)):
+            for q, name in enumerate(("dW", "dbias", "dgamma", "dbeta")):
+                if name != "dbias":                                          # (zeros on one side, roundings of zero on the other)
+                    diff[f"{name}{l}"] = rel(grads[l][q], t_grads[int(want_df) + 4 * l + q])
+        for t in leaves:
+            t.requires_grad_(False)
+        med = lambda q: sorted(r[q] for r in rounds)[1]
+        res[block] = {"shape": {"B": B, "N": n_, "npoint": s_, "nsample": k_, "D": d_, "mlp": mlp, "radius": radius, "dfeats": want_df},
+                      "sa_train_forward_ms": round(med(0), 4), "torch_train_forward_ms": round(med(1), 4),
+                      "sa_train_backward_ms": round(med(2), 4), "torch_train_backward_ms": round(med(3), 4),
+                      "sa_eval_forward_ms": round(med(4), 4), "sa_eval_backward_ms": round(med(5), 4),
+                      "torch_forward_over_fused": round(med(1) / med(0), 2), "torch_backward_over_fused": round(med(3) / med(2), 2),
+                      "train_forward_over_eval_forward": round(med(0) / med(4), 2), "train_backward_over_eval_backward": round(med(2) / med(5), 2),
+                      "rounds_ms_fused_fwd_torch_fwd_fused_bwd_torch_bwd_eval_fwd_eval_bwd": [[round(v, 4) for v in r] for r in rounds],
+                      "train_forward_workspace_MB": round(fws.numel() / 1e6, 2), "train_backward_workspace_MB": round(bws.numel() / 1e6, 1),
+                      "max_rel_diff_vs_torch": diff}
+        pts = U.gather_rows(pts, c)
+    return res
+
+
+if mode in ("train", "train-trace"):
+    r = train_leg(mode == "train-trace")
+    print(json.dumps({"trace_only": True, "fused_train_calls_per_shape": steps} if mode == "train-trace" else {"train": r}))
+    sys.exit(0)
+
 if trace_only:
     backward_leg()
     print(json.dumps({"trace_only": True, "fused_backward_calls_per_shape": steps}))
@@ -159,4 +249,4 @@ print(json.dumps({"shape": {"B": B, "N": N, "npoint": S, "nsample": K, "D": D, "
                   "mean_members": round(float(cnt.float().mean()), 2), "ball_query_ms": round(bq_ms, 4), "sa_forward_ms": round(sa_ms, 4),
                   "torch_gather_conv2d_max_ms": round(torch_ms, 4), "torch_over_fused": round(torch_ms / sa_ms, 2),
                   "sa_algorithmic_bytes": algo, "sa_GBps_at_algorithmic_bytes": round(algo / (sa_ms * 1e-3) / 1e9, 1),
-                  "sa_useful_TFLOPs": round(flops / (sa_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch": err, "backward": backward_leg()}))
+                  "sa_useful_TFLOPs": round(flops / (sa_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch": err, "backward": backward_leg(), "train": train_leg(False)}))

@@ -68,10 +68,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(BnBwdFinalize a)
         const size_t o = (size_t)slot * a.C + c;
         const double invstd = a.invstd[o], mean = a.mean[o];
         const double s = (double)a.gamma[c] * invstd;
-        const double p2 = -s * invstd * Bs / n;
+        const double p2 = n > 0.0 ? -s * invstd * Bs / n : 0.0;     // a slot with no row: P2 = P3 = 0 (as bn_finalize guards N > 0)
         a.P1[o] = (float)s;
         a.P2[o] = (float)p2;
-        a.P3[o] = (float)(-s * A / n - p2 * mean);
+        a.P3[o] = (float)(n > 0.0 ? -s * A / n - p2 * mean : 0.0);
         a.slot_ab[o * 2 + 0] = (float)A;
         a.slot_ab[o * 2 + 1] = (float)Bs;
     }

@@ -187,6 +187,9 @@ int sync_bn_fc_apply(const float *da, const float *z, const float *scale, const 
                      const float *slot_ab, int n_slots, int per, int C, float *g, hipStream_t st);
 inline size_t bn_finalize_merge_floats(int n_slots, int C) { return (size_t)n_slots * 16 * (2 * (size_t)C + 1); }
 int bn_finalize(const BnFinalize &a, hipStream_t st);
+// the finalize launch of the global-batch form on its own: `all` holds `ranks` gathered segments of `seg` floats (see gather_ranks above);
+// the part_* / win_off / uniform_rows / Q / chunks fields of `a` are not read.  bn_finalize's collective branch ends in this call.
+int bn_finalize_gathered(const BnFinalize &a, const float *all, int ranks, size_t seg, hipStream_t st);
 
 // eval mode: scale/shift from running statistics for a list of layers, one launch
 struct BnFoldItem {
@@ -206,7 +209,9 @@ int bn_running_update(const BnRunItem *items_host, int n_items, float momentum, 
 
 // MaxPool1d over each window after BatchNorm + ReLU:
 //   pooled[orow(q), c] = relu(scale * extreme + shift), extreme = max for scale >= 0 else min (pw_gemm tracked the one
-//   sign(gamma) = sign(scale) asks for), arg[q, c] = row index of that extreme
+//   sign(gamma) = sign(scale) asks for), arg[q, c] = row index of that extreme; equal extremes: the earliest chunk's row.
+//   A window whose chunks are all empty (part_amax < 0, or +-inf without part_amax) has no extreme: arg = -1, zext = 0 and
+//   pooled = relu(shift) (the extreme taken as 0).
 struct PoolFinalize {
     const float *part_max = nullptr;
     const int *part_amax = nullptr;
@@ -387,6 +392,9 @@ int reduce_windows_multi(const ReduceItem *items, int n, hipStream_t st);
 // BatchNorm backward constants of one layer from the partial sums of pw_dgrad / head_out_bwd / pool_bwd:
 //   per slot: A = sum dy, Bs = sum dy * zhat  ->  P1 = s, P2 = -s * invstd * Bs / n, P3 = -s * A / n - P2 * mean,
 //   slot_ab[slot][c] = (A, Bs) for the parameter gradients (dbeta = sum_slots A, dgamma = sum_slots Bs)
+//   A slot with no row (n = 0): P2 = P3 = 0 (P1 = s and slot_ab as above) -- no row reads them, and they stay finite.
+//   Two instantiations, same sums in a different grouping: 16 channels x 64 groups per block when
+//   n_slots * cdiv(C, 64) < 8 and cdiv(part_Q > 0 ? part_Q : Q, n_slots) * chunks >= 512 (the head), else 64 x 16.
 struct BnBwdFinalize {
     const float *part_a = nullptr, *part_b = nullptr;   // [Q * chunks, C]
     const int *win_off = nullptr;                       // rows per slot are counted from it

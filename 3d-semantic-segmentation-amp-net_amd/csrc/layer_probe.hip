@@ -1,6 +1,7 @@
 // layer_probe.hip -- test hooks (include/ampnet_hip.h, "test hooks"): one launch of pw_gemm / pw_bwd_fused / pw_dgrad / pw_wgrad, of a
 // kernel of the max-pooled layers' backward or of the input layers' weight gradient on buffers the caller chooses, for the layer-local
-// float64 parity tests (tests/test_pw_layers_gpu.py, tests/test_pooled_bwd_gpu.py).  No product path calls these.
+// float64 parity tests (tests/test_pw_layers_gpu.py, tests/test_pooled_bwd_gpu.py), of the head's kernels (tests/test_head_layers_gpu.py) and of
+// the BatchNorm / pooling glue kernels (tests/test_bn_glue_gpu.py).  No product path calls these.
 //
 // The probes exist for shared GPUs: before anything is launched every extent is checked on the host against what the kernel will
 // touch (rows from win_off / uniform_rows, partial slots from the statistics plan, ld x rows), so that a wrong test gets
@@ -574,4 +575,332 @@ extern "C" int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream)
         return sgemm_linear_bwd(d->rows, d->n_out, d->n_in, d->G, d->ldg, d->X, d->ldx, d->Wl, d->ldw, d->dW, d->lddw, d->dX, d->lddx, st, o);
     }
     }
+}
+
+// ---- the BatchNorm / pooling glue kernels (tests/test_bn_glue_gpu.py) ---------------------------------------------------------------------
+// One launch of a kernel of pw_misc.hip, of a small kernel of bwd_misc.hip or of reduce_windows (pw_bwd.hip), or of its host entry point.  The
+// host entry points branch on an installed collective (sync_bn_on()); the probe is about the single-process forms and refuses to run then.
+namespace ampnet {
+namespace {
+
+constexpr int64_t BIG = 1 << 26;       // no probe buffer is larger than this many elements: index arithmetic in int stays exact
+
+template <typename T> int bn_to_host(const T *src, int64_t n, std::vector<T> &h, hipStream_t st, const char *what)
+{
+    h.resize((size_t)n);
+    if (n > 0 && (hipMemcpyAsync(h.data(), src, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+        return fail(AMPNET_E_LAUNCH, "probe_bn: copying %s failed", what);
+    return AMPNET_OK;
+}
+
+// win_off on the host: Q + 1 ascending values from 0 up
+int bn_win_off(const AmpnetBnProbe *d, hipStream_t st, std::vector<int32_t> &wo, int64_t &rows, int &max_rows)
+{
+    AMPNET_REQUIRE(d->win_off && d->win_off_n >= (int64_t)d->Q + 1, "probe_bn: win_off needs Q + 1 = %d entries (has %lld)", d->Q + 1, (long long)d->win_off_n);
+    if (int rc = bn_to_host(d->win_off, (int64_t)d->Q + 1, wo, st, "win_off"); rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE(wo[0] == 0, "probe_bn: win_off[0] = %d != 0", wo[0]);
+    max_rows = 0;
+    for (int q = 0; q < d->Q; ++q) {
+        AMPNET_REQUIRE(wo[q + 1] >= wo[q], "probe_bn: win_off not ascending at %d", q);
+        if (wo[q + 1] - wo[q] > max_rows) max_rows = wo[q + 1] - wo[q];
+    }
+    rows = wo[d->Q];
+    AMPNET_REQUIRE(rows <= BIG, "probe_bn: %lld rows", (long long)rows);
+    return AMPNET_OK;
+}
+
+bool covers2(int64_t n, int64_t rows, int64_t ld, int64_t cols) { return rows <= 0 || (ld >= cols && n >= (rows - 1) * ld + cols); }
+
+// the item offsets of ops 3, 4, 7: item i starts at sum_{j<i} it_C[j]; returns the total, -1 if an item is out of range
+int64_t item_total(const AmpnetBnProbe *d, int n)
+{
+    int64_t t = 0;
+    for (int i = 0; i < n; ++i) {
+        if (d->it_C[i] < 1 || d->it_C[i] > 4096) return -1;
+        t += d->it_C[i];
+    }
+    return t;
+}
+
+int probe_pw_input(const AmpnetBnProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE((d->mode == 0 || d->mode == 1) && d->Q >= 1 && d->Q <= (1 << 16) && d->n_slots >= 1 && d->chunks >= 1 && d->chunks <= 64 && d->chunk_rows >= 1,
+                   "probe_bn: pw_input sizes");
+    AMPNET_REQUIRE(!(d->mode == 1 && d->perwin_slot_major) || d->Q % d->n_slots == 0, "probe_bn: pw_input slot-major T needs Q %% n_slots == 0");
+    std::vector<int32_t> wo;
+    int64_t rows = 0;
+    int max_rows = 0;
+    if (int rc = bn_win_off(d, st, wo, rows, max_rows); rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE((int64_t)d->chunks * d->chunk_rows >= max_rows, "probe_bn: pw_input %d chunks of %d rows do not cover a window of %d rows", d->chunks,
+                   d->chunk_rows, max_rows);
+    const int64_t Q = d->Q, S = d->n_slots;
+    AMPNET_REQUIRE(d->x && d->x_n >= rows * 9, "probe_bn: x [rows, 9] short");
+    AMPNET_REQUIRE(d->W && d->W_n >= (d->mode ? 64 * 12 : 64 * 3), "probe_bn: pw_input W short");
+    AMPNET_REQUIRE(d->mode == 0 || (d->T && d->T_n >= Q * 9), "probe_bn: T [Q, 9] short");
+    AMPNET_REQUIRE(d->Z && d->Z_n >= rows * 64, "probe_bn: Z [rows, 64] short");
+    AMPNET_REQUIRE((d->part_sum == nullptr) == (d->part_sq == nullptr), "probe_bn: part_sum and part_sq come together");
+    if (d->part_rows) {
+        AMPNET_REQUIRE(d->part_sum && d->stat_lanes >= d->n_slots && d->stat_lanes <= 2048, "probe_bn: pw_input stat_lanes %d", d->stat_lanes);
+        const int64_t parts = (int64_t)cdiv(d->stat_lanes, d->n_slots) * S;
+        AMPNET_REQUIRE(d->part_sum_n >= parts * 64 && d->part_sq_n >= parts * 64 && d->part_rows_n >= parts, "probe_bn: pw_input per-workgroup partials short");
+    } else if (d->part_sum) {
+        AMPNET_REQUIRE(d->part_sum_n >= Q * d->chunks * 64 && d->part_sq_n >= Q * d->chunks * 64, "probe_bn: pw_input per-chunk partials short");
+    }
+    PwInput a;
+    a.x = d->x; a.W = d->W; a.T = d->mode ? d->T : nullptr; a.mode = d->mode; a.perwin_slot_major = d->perwin_slot_major; a.n_slots = d->n_slots;
+    a.Z = d->Z; a.z_bf16 = d->z_bf16 ? 1 : 0; a.part_sum = d->part_sum; a.part_sq = d->part_sq; a.part_rows = d->part_rows;
+    a.stat_lanes = d->stat_lanes; a.win_off = d->win_off; a.Q = d->Q; a.chunk_rows = d->chunk_rows; a.chunks = d->chunks;
+    return pw_input(a, st);
+}
+
+int probe_bn_finalize(const AmpnetBnProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE(d->n_slots >= 1 && d->n_slots <= 4096 && d->C >= 1 && d->C <= 4096, "probe_bn: bn_finalize sizes");
+    const int64_t S = d->n_slots, C = d->C;
+    AMPNET_REQUIRE(d->gamma && d->gamma_n >= C && d->beta && d->beta_n >= C, "probe_bn: gamma / beta [C] short");
+    AMPNET_REQUIRE(d->scale && d->scale_n >= S * C && d->shift && d->shift_n >= S * C, "probe_bn: scale / shift [n_slots, C] short");
+    AMPNET_REQUIRE((!d->mean || d->mean_n >= S * C) && (!d->invstd || d->invstd_n >= S * C), "probe_bn: mean / invstd short");
+    AMPNET_REQUIRE((d->stat_mean == nullptr) == (d->stat_uvar == nullptr) && (!d->stat_mean || (d->stat_mean_n >= S * C && d->stat_uvar_n >= S * C)),
+                   "probe_bn: stat_mean / stat_uvar short");
+    BnFinalize a;
+    a.n_slots = d->n_slots; a.C = d->C; a.gamma = d->gamma; a.beta = d->beta; a.eps = d->eps;
+    a.scale = d->scale; a.shift = d->shift; a.mean = d->mean; a.invstd = d->invstd; a.stat_mean = d->stat_mean; a.stat_uvar = d->stat_uvar;
+    if (d->op == 2) {
+        const int64_t body = S * (2 * C + 1);
+        AMPNET_REQUIRE(d->gather_ranks >= 1 && d->gather_ranks <= 64 && d->gather_seg >= body, "probe_bn: gather_ranks %d, gather_seg %lld", d->gather_ranks,
+                       (long long)d->gather_seg);
+        AMPNET_REQUIRE(d->part_sum && d->part_sum_n >= (d->gather_ranks - 1) * d->gather_seg + body, "probe_bn: gathered segments short");
+        return bn_finalize_gathered(a, d->part_sum, d->gather_ranks, (size_t)d->gather_seg, st);
+    }
+    AMPNET_REQUIRE(d->Q >= 1 && d->Q <= (1 << 20) && d->chunks >= 1 && d->chunks <= 64 && d->chunk_rows >= 1 && d->uniform_rows >= 0, "probe_bn: bn_finalize sizes");
+    const int64_t parts = (int64_t)d->Q * d->chunks;
+    AMPNET_REQUIRE(parts * C <= BIG, "probe_bn: bn_finalize partials too large");
+    AMPNET_REQUIRE(d->part_sum && d->part_sum_n >= parts * C && d->part_sq && d->part_sq_n >= parts * C, "probe_bn: part_sum / part_sq [Q * chunks, C] short");
+    if (d->part_rows) {
+        AMPNET_REQUIRE(d->part_rows_n >= parts, "probe_bn: part_rows [Q * chunks] short");
+    } else if (d->uniform_rows > 0) {
+        AMPNET_REQUIRE((int64_t)d->chunks * d->chunk_rows >= d->uniform_rows, "probe_bn: chunks do not cover uniform_rows");
+    } else {
+        std::vector<int32_t> wo;
+        int64_t rows = 0;
+        int max_rows = 0;
+        if (int rc = bn_win_off(d, st, wo, rows, max_rows); rc != AMPNET_OK) return rc;
+        AMPNET_REQUIRE((int64_t)d->chunks * d->chunk_rows >= max_rows, "probe_bn: chunks do not cover a window of %d rows", max_rows);
+    }
+    AMPNET_REQUIRE(!d->merge_ws || d->merge_ws_n >= (int64_t)bn_finalize_merge_floats(d->n_slots, d->C), "probe_bn: merge_ws short");
+    a.part_sum = d->part_sum; a.part_sq = d->part_sq; a.part_rows = d->part_rows; a.chunk_rows = d->chunk_rows;
+    a.uniform_rows = d->part_rows ? 0 : d->uniform_rows; a.win_off = (d->part_rows || d->uniform_rows > 0) ? nullptr : d->win_off;
+    a.Q = d->Q; a.chunks = d->chunks; a.merge_ws = d->merge_ws;
+    return bn_finalize(a, st);
+}
+
+int probe_items(const AmpnetBnProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE(d->n_items >= 1 && d->n_items <= AMPNET_BN_PROBE_ITEMS && d->n_slots >= 1 && d->n_slots <= 64, "probe_bn: %d items, %d slots", d->n_items, d->n_slots);
+    const int n = d->n_items;
+    const int64_t tot = item_total(d, n), S = d->n_slots;
+    AMPNET_REQUIRE(tot > 0, "probe_bn: it_C out of range");
+    if (d->op == 3) {
+        AMPNET_REQUIRE(d->gamma && d->gamma_n >= tot && d->beta && d->beta_n >= tot && d->rmean && d->rmean_n >= tot && d->rvar && d->rvar_n >= tot &&
+                           d->scale && d->scale_n >= tot && d->shift && d->shift_n >= tot,
+                       "probe_bn: bn_fold arrays short (%lld channels)", (long long)tot);
+        BnFoldItem it[AMPNET_BN_PROBE_ITEMS];
+        int64_t o = 0;
+        for (int i = 0; i < n; o += d->it_C[i], ++i) it[i] = {d->gamma + o, d->beta + o, d->rmean + o, d->rvar + o, d->scale + o, d->shift + o, d->it_C[i]};
+        return bn_fold(it, n, d->eps, st);
+    }
+    if (d->op == 4) {
+        AMPNET_REQUIRE(d->stat_mean && d->stat_mean_n >= S * tot && d->stat_uvar && d->stat_uvar_n >= S * tot && d->rmean && d->rmean_n >= tot && d->rvar &&
+                           d->rvar_n >= tot,
+                       "probe_bn: bn_running_update arrays short");
+        BnRunItem it[AMPNET_BN_PROBE_ITEMS];
+        int64_t o = 0;
+        for (int i = 0; i < n; o += d->it_C[i], ++i) it[i] = {d->stat_mean + S * o, d->stat_uvar + S * o, d->rmean + o, d->rvar + o, d->it_C[i], d->n_slots};
+        return bn_running_update(it, n, d->momentum, st);
+    }
+    AMPNET_REQUIRE(d->slot_ab && d->slot_ab_n >= 2 * S * tot && d->dgamma && d->dgamma_n >= tot && d->dbeta && d->dbeta_n >= tot, "probe_bn: bn_param_grads arrays short");
+    BnGradItem it[AMPNET_BN_PROBE_ITEMS];
+    int64_t o = 0;
+    for (int i = 0; i < n; o += d->it_C[i], ++i) it[i] = {d->slot_ab + 2 * S * o, d->dgamma + o, d->dbeta + o, d->it_C[i], d->n_slots};
+    return bn_param_grads(it, n, st);
+}
+
+int probe_pool_finalize(const AmpnetBnProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE((d->mode == 0 || d->mode == 1) && d->Q >= 1 && d->Q <= (1 << 16) && d->n_slots >= 1 && d->n_slots <= d->Q && d->C >= 1 && d->C <= 4096 &&
+                       d->chunks >= 1 && d->chunks <= 64,
+                   "probe_bn: pool_finalize sizes");
+    AMPNET_REQUIRE(!d->out_slot_major || d->Q % d->n_slots == 0, "probe_bn: pool_finalize slot-major output needs Q %% n_slots == 0");
+    const int64_t Q = d->Q, S = d->n_slots, C = d->C, parts = Q * d->chunks;
+    AMPNET_REQUIRE(d->part_max && d->part_max_n >= parts * C, "probe_bn: part_max [Q * chunks, C] short");
+    AMPNET_REQUIRE(d->pooled && d->pooled_n >= Q * C && (!d->arg || d->arg_n >= Q * C) && (!d->zext || d->zext_n >= Q * C), "probe_bn: pooled / arg / zext [Q, C] short");
+    AMPNET_REQUIRE(d->scale && d->scale_n >= S * C && d->shift && d->shift_n >= S * C, "probe_bn: scale / shift [n_slots, C] short");
+    AMPNET_REQUIRE(d->part_amax || !d->arg, "probe_bn: arg without part_amax");
+    if (d->part_amax) {
+        AMPNET_REQUIRE(d->part_amax_n >= parts * C, "probe_bn: part_amax short");
+        std::vector<int32_t> wo, am;
+        int64_t rows = 0;
+        int max_rows = 0;
+        if (int rc = bn_win_off(d, st, wo, rows, max_rows); rc != AMPNET_OK) return rc;
+        if (int rc = bn_to_host(d->part_amax, parts * C, am, st, "part_amax"); rc != AMPNET_OK) return rc;
+        for (int64_t p = 0; p < parts; ++p)
+            for (int64_t c = 0; c < C; ++c) {
+                const int r = am[(size_t)(p * C + c)], q = (int)(p / d->chunks);
+                AMPNET_REQUIRE(r == -1 || (r >= wo[q] && r < wo[q + 1]), "probe_bn: part_amax[%lld][%lld] = %d outside window %d", (long long)p, (long long)c, r, q);
+            }
+    }
+    PoolFinalize a;
+    a.part_max = d->part_max; a.part_amax = d->part_amax; a.Q = d->Q; a.chunks = d->chunks; a.n_slots = d->n_slots; a.C = d->C;
+    a.out_slot_major = d->out_slot_major; a.pooled = d->pooled; a.arg = d->arg; a.zext = d->zext;
+    if (d->mode == 0) {
+        a.scale = d->scale; a.shift = d->shift;
+        return pool_finalize(a, st);
+    }
+    AMPNET_REQUIRE(d->C == 256 && d->part_amax, "probe_bn: the in-kernel BatchNorm form needs 256 channels and part_amax");
+    AMPNET_REQUIRE(d->pfin_parts >= d->n_slots && d->pfin_parts % d->n_slots == 0 && d->pfin_parts <= (1 << 16), "probe_bn: pfin_parts %d", d->pfin_parts);
+    const int64_t pp = d->pfin_parts;
+    AMPNET_REQUIRE(d->part_sum && d->part_sum_n >= pp * 256 && d->part_sq && d->part_sq_n >= pp * 256 && d->part_rows && d->part_rows_n >= pp,
+                   "probe_bn: the producer's partials [pfin_parts, 256] short");
+    std::vector<int32_t> pr;
+    if (int rc = bn_to_host((const int32_t *)d->part_rows, pp, pr, st, "part_rows"); rc != AMPNET_OK) return rc;
+    for (int64_t p = 0; p < pp; ++p) AMPNET_REQUIRE(pr[(size_t)p] >= 0, "probe_bn: part_rows[%lld] = %d", (long long)p, pr[(size_t)p]);
+    AMPNET_REQUIRE(d->gamma && d->gamma_n >= 256 && d->beta && d->beta_n >= 256, "probe_bn: gamma / beta short");
+    AMPNET_REQUIRE(d->mean && d->mean_n >= S * C && d->invstd && d->invstd_n >= S * C && d->stat_mean && d->stat_mean_n >= S * C && d->stat_uvar && d->stat_uvar_n >= S * C,
+                   "probe_bn: the BatchNorm outputs [n_slots, 256] short");
+    a.pfin_sum = d->part_sum; a.pfin_sq = d->part_sq; a.pfin_rows = d->part_rows; a.pfin_parts = d->pfin_parts;
+    a.pfin_gamma = d->gamma; a.pfin_beta = d->beta; a.pfin_eps = d->eps;
+    a.pfin_scale = d->scale; a.pfin_shift = d->shift; a.pfin_mean = d->mean; a.pfin_invstd = d->invstd; a.pfin_smean = d->stat_mean; a.pfin_suvar = d->stat_uvar;
+    return pool_finalize(a, st);
+}
+
+int probe_bn_bwd_finalize(const AmpnetBnProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE(d->Q >= 1 && d->Q <= (1 << 20) && d->n_slots >= 1 && d->n_slots <= 4096 && d->C >= 1 && d->C <= 4096 && d->chunks >= 1 && d->chunks <= 64 &&
+                       d->part_Q >= 0 && d->part_Q <= (1 << 20) && d->uniform_rows >= 0,
+                   "probe_bn: bn_bwd_finalize sizes");
+    const int64_t S = d->n_slots, C = d->C, parts = (int64_t)(d->part_Q > 0 ? d->part_Q : d->Q) * d->chunks;
+    AMPNET_REQUIRE(parts * C <= BIG, "probe_bn: bn_bwd_finalize partials too large");
+    AMPNET_REQUIRE(d->part_a && d->part_a_n >= parts * C && d->part_b && d->part_b_n >= parts * C, "probe_bn: part_a / part_b short");
+    if (d->uniform_rows <= 0) {
+        std::vector<int32_t> wo;
+        int64_t rows = 0;
+        int max_rows = 0;
+        if (int rc = bn_win_off(d, st, wo, rows, max_rows); rc != AMPNET_OK) return rc;
+    } else {
+        AMPNET_REQUIRE((int64_t)cdiv(d->Q, d->n_slots) * d->uniform_rows <= BIG, "probe_bn: rows per slot");
+    }
+    AMPNET_REQUIRE(d->gamma && d->gamma_n >= C && d->mean && d->mean_n >= S * C && d->invstd && d->invstd_n >= S * C, "probe_bn: gamma / mean / invstd short");
+    AMPNET_REQUIRE(d->P1 && d->P1_n >= S * C && d->P2 && d->P2_n >= S * C && d->P3 && d->P3_n >= S * C && d->slot_ab && d->slot_ab_n >= 2 * S * C, "probe_bn: P1..P3 / slot_ab short");
+    BnBwdFinalize a;
+    a.part_a = d->part_a; a.part_b = d->part_b; a.win_off = d->uniform_rows > 0 ? nullptr : d->win_off; a.uniform_rows = d->uniform_rows;
+    a.Q = d->Q; a.chunks = d->chunks; a.n_slots = d->n_slots; a.C = d->C; a.part_Q = d->part_Q;
+    a.gamma = d->gamma; a.mean = d->mean; a.invstd = d->invstd; a.P1 = d->P1; a.P2 = d->P2; a.P3 = d->P3; a.slot_ab = d->slot_ab;
+    return bn_bwd_finalize(a, st);
+}
+
+int probe_fc(const AmpnetBnProbe *d, hipStream_t st)
+{
+    AMPNET_REQUIRE(d->C >= 1 && d->C <= 4096 && d->per >= 1 && d->per <= (1 << 20), "probe_bn: fc sizes");
+    const int64_t C = d->C;
+    if (d->op == 10) {
+        AMPNET_REQUIRE(d->n_slots >= 1 && d->n_slots <= 4096, "probe_bn: fc_bn_bwd n_slots %d", d->n_slots);
+        const int64_t S = d->n_slots, rows = S * d->per;
+        AMPNET_REQUIRE(rows * C <= BIG, "probe_bn: fc_bn_bwd too large");
+        AMPNET_REQUIRE(d->da && d->da_n >= rows * C && d->z && d->z_n >= rows * C && d->g && d->g_n >= rows * C, "probe_bn: da / z / g [n_slots * per, C] short");
+        AMPNET_REQUIRE(d->scale && d->scale_n >= S * C && d->shift && d->shift_n >= S * C && d->mean && d->mean_n >= S * C && d->invstd && d->invstd_n >= S * C,
+                       "probe_bn: fc_bn_bwd constants [n_slots, C] short");
+        AMPNET_REQUIRE(d->slot_ab && d->slot_ab_n >= 2 * S * C, "probe_bn: slot_ab short");
+        return fc_bn_bwd(d->da, d->z, d->scale, d->shift, d->mean, d->invstd, d->n_slots, d->per, d->C, d->g, d->slot_ab, st);
+    }
+    AMPNET_REQUIRE(d->rows >= 1 && d->rows <= (1 << 20), "probe_bn: fc_act rows %d", d->rows);
+    const int64_t rows = d->rows, groups = cdiv(d->rows, d->per);
+    AMPNET_REQUIRE(rows * C <= BIG, "probe_bn: fc_act too large");
+    AMPNET_REQUIRE(d->z && d->z_n >= rows * C && d->act && d->act_n >= rows * C && d->scale && d->scale_n >= groups * C && d->shift && d->shift_n >= groups * C,
+                   "probe_bn: fc_act buffers short");
+    if (d->op == 8) return fc_act(d->z, d->scale, d->shift, d->rows, d->C, d->per, d->act, st);
+    const int64_t C1 = d->C1;
+    AMPNET_REQUIRE(d->C1 >= 1 && d->C1 <= 4096 && rows * C1 <= BIG, "probe_bn: fc_act_pair C1 %d", d->C1);
+    AMPNET_REQUIRE(d->z1 && d->z1_n >= rows * C1 && d->act1 && d->act1_n >= rows * C1 && d->s1 && d->s1_n >= groups * C1 && d->t1 && d->t1_n >= groups * C1,
+                   "probe_bn: fc_act_pair second buffers short");
+    return fc_act_pair(d->z, d->scale, d->shift, d->C, d->act, d->z1, d->s1, d->t1, d->C1, d->act1, d->rows, d->per, st);
+}
+
+// partials `stride` apart of [rows, cols] on ld_part, Q of them, from element `off` of a buffer of n elements
+bool reduce_src_ok(int64_t n, int64_t off, int64_t Q, int64_t stride, int64_t rows, int64_t cols, int64_t ld)
+{
+    return Q >= 1 && Q <= (1 << 16) && rows >= 1 && cols >= 1 && rows * cols <= (1 << 22) && ld >= cols && stride >= 0 && off >= 0 &&
+           off + (Q - 1) * stride + (rows - 1) * ld + cols <= n && n <= BIG;
+}
+
+int probe_reduce(const AmpnetBnProbe *d, hipStream_t st)
+{
+    if (d->op == 12) {
+        AMPNET_REQUIRE(d->src && reduce_src_ok(d->src_n, 0, d->Q, d->stride, d->rows, d->cols, d->ld_part), "probe_bn: reduce_windows partials short");
+        AMPNET_REQUIRE(d->dst && covers2(d->dst_n, d->rows, d->ld_dst, d->cols), "probe_bn: reduce_windows dst short");
+        return reduce_windows(d->src, d->Q, (long)d->stride, d->rows, d->cols, d->ld_part, d->dst, d->ld_dst, d->accumulate ? 1 : 0, st);
+    }
+    AMPNET_REQUIRE(d->n_items >= 1 && d->n_items <= AMPNET_BN_PROBE_REDUCE && d->src && d->dst, "probe_bn: reduce_windows_multi %d items", d->n_items);
+    ReduceItem it[AMPNET_BN_PROBE_REDUCE];
+    for (int i = 0; i < d->n_items; ++i) {
+        AMPNET_REQUIRE(reduce_src_ok(d->src_n, d->it_part_off[i], d->it_Q[i], d->it_stride[i], d->it_rows[i], d->it_cols[i], d->it_ld_part[i]),
+                       "probe_bn: reduce_windows_multi item %d partials short", i);
+        AMPNET_REQUIRE(d->it_dst_off[i] >= 0 && covers2(d->dst_n - d->it_dst_off[i], d->it_rows[i], d->it_ld_dst[i], d->it_cols[i]),
+                       "probe_bn: reduce_windows_multi item %d dst short", i);
+        it[i] = {d->src + d->it_part_off[i], d->it_Q[i], (long)d->it_stride[i], d->it_rows[i], d->it_cols[i], d->it_ld_part[i], d->dst + d->it_dst_off[i], d->it_ld_dst[i]};
+    }
+    return reduce_windows_multi(it, d->n_items, st);
+}
+
+}  // namespace
+}  // namespace ampnet
+
+extern "C" int ampnet_probe_bn_f32(const AmpnetBnProbe *d, void *stream)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(d, "probe_bn: null descriptor");
+    AMPNET_REQUIRE(d->op >= 0 && d->op <= 16, "probe_bn: op %d not built", d->op);
+    AMPNET_REQUIRE(!sync_bn_on(), "probe_bn: a collective is installed; the probe launches the single-process forms only");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    switch (d->op) {
+    case 0: return probe_pw_input(d, st);
+    case 1:
+    case 2: return probe_bn_finalize(d, st);
+    case 3:
+    case 4:
+    case 7: return probe_items(d, st);
+    case 5: return probe_pool_finalize(d, st);
+    case 6: return probe_bn_bwd_finalize(d, st);
+    case 8:
+    case 9:
+    case 10: return probe_fc(d, st);
+    case 11:
+        AMPNET_REQUIRE(d->rows >= 1 && d->C >= 1 && d->C <= 4096 && (int64_t)d->rows * d->C <= BIG, "probe_bn: colsum sizes");
+        AMPNET_REQUIRE(d->src && d->src_n >= (int64_t)d->rows * d->C && d->dst && d->dst_n >= d->C, "probe_bn: colsum buffers short");
+        return colsum(d->src, d->rows, d->C, d->dst, st);
+    case 12:
+    case 13: return probe_reduce(d, st);
+    case 14: {
+        AMPNET_REQUIRE(d->Q >= 1 && d->Q <= 4096 && d->n_slots >= 1 && d->Q % d->n_slots == 0 && d->chunks >= 1 && d->chunks <= 64, "probe_bn: transpose64 sizes");
+        const int64_t Q = d->Q;
+        AMPNET_REQUIRE(d->src && d->src_n >= Q * d->chunks * 4096 && d->dst && d->dst_n >= Q * 4096 && (!d->add || d->add_n >= Q * 4096), "probe_bn: transpose64 buffers short");
+        return transpose64_slot_major(d->src, d->dst, d->Q, d->n_slots, d->chunks, d->by_workgroup ? 1 : 0, d->add, st);
+    }
+    case 15:
+        AMPNET_REQUIRE(d->Q >= 1 && d->Q <= (1 << 16) && d->k >= 1 && d->k <= 64, "probe_bn: add_identity sizes");
+        AMPNET_REQUIRE(d->dst && d->dst_n >= (int64_t)d->Q * d->k * d->k, "probe_bn: add_identity T [Q, k, k] short");
+        return add_identity(d->dst, d->Q, d->k, st);
+    default:
+        AMPNET_REQUIRE(d->rows >= 1 && d->rows <= BIG && d->idst && d->idst_n >= d->rows, "probe_bn: fill_i32_ramp dst short");
+        return fill_i32_ramp(d->idst, d->rows, d->step, st);
+    }
+}
+
+extern "C" int ampnet_probe_bn_plan(int Q, int chunks, int n_slots, int C, AmpnetBnPlan *o)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(o && Q >= 1 && chunks >= 1 && n_slots >= 1 && C >= 1, "probe_bn_plan: bad arguments");
+    o->input_stat_lanes = pw_input_stat_lanes(Q, chunks, n_slots);
+    o->input_stat_parts = cdiv(o->input_stat_lanes, n_slots) * n_slots;
+    o->merge_floats = (int64_t)bn_finalize_merge_floats(n_slots, C);
+    return AMPNET_OK;
 }

@@ -271,6 +271,17 @@ __global__ __launch_bounds__(64 * FIN_G) void bn_finalize_kernel(BnFinalize a, f
     }
 }
 
+// the second launch of the global-batch form: finalize from `ranks` gathered segments of `seg` floats (BnFinalize.gather_*)
+int bn_finalize_gathered(const BnFinalize &a, const float *all, int ranks, size_t seg, hipStream_t st)
+{
+    BnFinalize s2 = a;
+    s2.part_sum = all; s2.part_sq = all + (size_t)a.n_slots * a.C;
+    s2.gather_ranks = ranks; s2.gather_seg = (long)seg;
+    s2.Q = ranks * a.n_slots; s2.chunks = 1; s2.uniform_rows = 0; s2.part_rows = nullptr;
+    hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3(a.n_slots, cdiv(a.C, 64)), dim3(64 * FIN_G), 0, st, s2, nullptr, nullptr, nullptr);
+    return check_launch("bn_finalize_kernel (global batch)");
+}
+
 int bn_finalize(const BnFinalize &a, hipStream_t st)
 {
     AMPNET_REQUIRE(a.part_sum && a.part_sq && (a.win_off || a.part_rows || a.uniform_rows > 0) && a.gamma && a.beta && a.scale && a.shift, "bn_finalize: null pointer");
@@ -287,12 +298,7 @@ int bn_finalize(const BnFinalize &a, hipStream_t st)
         if (rc != AMPNET_OK) return rc;
         rc = sync_bn_exchange(AMPNET_COLLECTIVE_ALLGATHER, loc, all, seg, st);
         if (rc != AMPNET_OK) return rc;
-        BnFinalize s2 = a;
-        s2.part_sum = all; s2.part_sq = all + (size_t)a.n_slots * a.C;
-        s2.gather_ranks = sync_bn_world(); s2.gather_seg = (long)seg;
-        s2.Q = sync_bn_world() * a.n_slots; s2.chunks = 1; s2.uniform_rows = 0; s2.part_rows = nullptr;
-        hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3(a.n_slots, cdiv(a.C, 64)), dim3(64 * FIN_G), 0, st, s2, nullptr, nullptr, nullptr);
-        return check_launch("bn_finalize_kernel (global batch)");
+        return bn_finalize_gathered(a, all, sync_bn_world(), seg, st);
     }
     const long per_slot_parts = (long)((a.Q + a.n_slots - 1) / a.n_slots) * a.chunks;
     if (a.merge_ws && per_slot_parts > 192 && a.n_slots * FIN_V <= a.Q) {

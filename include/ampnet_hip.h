@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 14
+#define AMPNET_ABI_VERSION 15
 
 enum {
     AMPNET_OK = 0,
@@ -861,11 +861,108 @@ typedef struct AmpnetHeadProbe {
     const float *dx_mul; int64_t dx_mul_n;
 } AmpnetHeadProbe;
 
+/* One launch of a BatchNorm / pooling glue kernel (csrc/pw_misc.hip, bwd_misc.hip, pw_bwd.hip: reduce_windows) or of its host entry
+ * point (ABI 15; csrc/layer_probe.hip, tests/test_bn_glue_gpu.py), by `op`.  Field names are those of the launch records in csrc/kernels.h.
+ *   0  pw_input            (x [rows, 9], W [64, 3 | 12], T [Q, 9] in mode 1 -> Z [rows, 64] fp32 or (z_bf16) bf16; part_sum / part_sq
+ *                           [Q * chunks, 64], or with part_rows [parts] the per-workgroup form [parts, 64], parts = stat_lanes rounded up to
+ *                           a multiple of n_slots, stat_lanes from ampnet_probe_bn_plan)
+ *   1  bn_finalize         (part_sum / part_sq [Q * chunks, C]; rows per partial from part_rows [Q * chunks], uniform_rows or win_off;
+ *                           gamma / beta [C] -> scale / shift [n_slots, C]; mean / invstd and stat_mean / stat_uvar optional;
+ *                           merge_ws [bn_finalize_merge_floats] optional: the two-stage form where the host entry point picks it)
+ *   2  bn_finalize_gathered (part_sum = gather_ranks segments of gather_seg floats {mean [n_slots, C], M2 [n_slots, C], rows [n_slots] int})
+ *   3  bn_fold             (n_items layers of it_C[i] channels, item i at offset sum_{j<i} it_C[j] of gamma / beta / rmean / rvar / scale /
+ *                           shift; eps)
+ *   4  bn_running_update   (item i at offset n_slots * sum_{j<i} it_C[j] of stat_mean / stat_uvar [n_slots, it_C[i]] and sum it_C[j] of
+ *                           rmean / rvar; momentum)
+ *   5  pool_finalize       (part_max [Q * chunks, C], part_amax or NULL, scale / shift [n_slots, C] -> pooled, arg, zext [Q, C]; mode 1:
+ *                           the in-kernel BatchNorm form, C == 256, part_sum / part_sq [pfin_parts, 256] and part_rows [pfin_parts] are the
+ *                           producer's partials, gamma / beta in, scale / shift / mean / invstd / stat_mean / stat_uvar out; win_off is
+ *                           needed with part_amax: every entry must be -1 or a row of its window)
+ *   6  bn_bwd_finalize     (part_a / part_b [(part_Q > 0 ? part_Q : Q) * chunks, C], win_off or uniform_rows, gamma, mean, invstd
+ *                           -> P1 .. P3 [n_slots, C], slot_ab [n_slots, C, 2])
+ *   7  bn_param_grads      (items as op 4: slot_ab [n_slots, it_C[i], 2] -> dgamma / dbeta [it_C[i]])
+ *   8  fc_act              (z [rows, C], scale / shift [cdiv(rows, per), C] -> act)
+ *   9  fc_act_pair         (op 8 for (z, scale, shift, act, C) and (z1, s1, t1, act1, C1) in one launch)
+ *   10 fc_bn_bwd           (da, z [n_slots * per, C], scale .. invstd [n_slots, C] -> g, slot_ab)
+ *   11 colsum              (src [rows, C] -> dst [C])
+ *   12 reduce_windows      (src: Q partials `stride` apart of [rows, cols] on ld_part -> dst [rows, cols] on ld_dst, = or +=)
+ *   13 reduce_windows_multi (n_items of op 12's overwrite form: it_* and the element offsets it_part_off / it_dst_off into src / dst)
+ *   14 transpose64_slot_major (src [Q * chunks, 64, 64], add [Q, 64, 64] or NULL -> dst [Q, 64, 64])
+ *   15 add_identity        (dst [Q, k, k] += I)
+ *   16 fill_i32_ramp       (idst [rows] = i * step)
+ * Every extent is checked on the host first (win_off, part_amax and, for op 5 mode 1, part_rows are copied to the host for that); the
+ * probe refuses to run while a collective is installed (the host entry points then take their global-batch branches).                  */
+#define AMPNET_BN_PROBE_ITEMS 25       /* one more than bn_fold / bn_running_update / bn_param_grads take: the refusal can be reached */
+#define AMPNET_BN_PROBE_REDUCE 13      /* one more than reduce_windows_multi takes */
+typedef struct AmpnetBnProbe {
+    int32_t op, mode, Q, n_slots, C, C1, chunks, chunk_rows, uniform_rows, stat_lanes, perwin_slot_major, z_bf16, out_slot_major, part_Q,
+            pfin_parts, gather_ranks, n_items, rows, cols, ld_part, ld_dst, accumulate, by_workgroup, per, k, step;
+    float eps, momentum;
+    int64_t stride, gather_seg;
+    int32_t it_C[AMPNET_BN_PROBE_ITEMS], pad0;
+    int32_t it_Q[AMPNET_BN_PROBE_REDUCE], it_rows[AMPNET_BN_PROBE_REDUCE], it_cols[AMPNET_BN_PROBE_REDUCE],
+            it_ld_part[AMPNET_BN_PROBE_REDUCE], it_ld_dst[AMPNET_BN_PROBE_REDUCE], pad1;
+    int64_t it_stride[AMPNET_BN_PROBE_REDUCE], it_part_off[AMPNET_BN_PROBE_REDUCE], it_dst_off[AMPNET_BN_PROBE_REDUCE];
+    const float *x; int64_t x_n;
+    const float *W; int64_t W_n;
+    const float *T; int64_t T_n;
+    float *Z; int64_t Z_n;                                      /* elements of Z's own type */
+    float *part_sum; int64_t part_sum_n;
+    float *part_sq; int64_t part_sq_n;
+    int32_t *part_rows; int64_t part_rows_n;
+    const int32_t *win_off; int64_t win_off_n;
+    const float *gamma; int64_t gamma_n;
+    const float *beta; int64_t beta_n;
+    float *scale; int64_t scale_n;
+    float *shift; int64_t shift_n;
+    float *mean; int64_t mean_n;
+    float *invstd; int64_t invstd_n;
+    float *stat_mean; int64_t stat_mean_n;
+    float *stat_uvar; int64_t stat_uvar_n;
+    float *merge_ws; int64_t merge_ws_n;
+    float *rmean; int64_t rmean_n;
+    float *rvar; int64_t rvar_n;
+    const float *part_max; int64_t part_max_n;
+    const int32_t *part_amax; int64_t part_amax_n;
+    float *pooled; int64_t pooled_n;
+    int32_t *arg; int64_t arg_n;
+    float *zext; int64_t zext_n;
+    const float *part_a; int64_t part_a_n;
+    const float *part_b; int64_t part_b_n;
+    float *P1; int64_t P1_n;
+    float *P2; int64_t P2_n;
+    float *P3; int64_t P3_n;
+    float *slot_ab; int64_t slot_ab_n;
+    float *dgamma; int64_t dgamma_n;
+    float *dbeta; int64_t dbeta_n;
+    const float *z; int64_t z_n;
+    const float *da; int64_t da_n;
+    float *g; int64_t g_n;
+    float *act; int64_t act_n;
+    const float *z1; int64_t z1_n;
+    const float *s1; int64_t s1_n;
+    const float *t1; int64_t t1_n;
+    float *act1; int64_t act1_n;
+    const float *src; int64_t src_n;
+    float *dst; int64_t dst_n;
+    const float *add; int64_t add_n;
+    int32_t *idst; int64_t idst_n;
+} AmpnetBnProbe;
+
+/* what the orchestration would size for the input layers' per-workgroup statistics and the two-stage bn_finalize */
+typedef struct AmpnetBnPlan {
+    int32_t input_stat_lanes;      /* pw_input_stat_lanes(Q, chunks, n_slots) */
+    int32_t input_stat_parts;      /* the partial slots those lanes write: lanes rounded up to a multiple of n_slots */
+    int64_t merge_floats;          /* bn_finalize_merge_floats(n_slots, C) */
+} AmpnetBnPlan;
+
 int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream);
 int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream);
 int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream);
 int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void *stream);
 int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream);
+int ampnet_probe_bn_f32(const AmpnetBnProbe *d, void *stream);
+int ampnet_probe_bn_plan(int Q, int chunks, int n_slots, int C, AmpnetBnPlan *out_host);
 int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, int cout, int stat_chunks, const AmpnetPwBwdProbe *bwd, AmpnetPwPlan *out_host);
 
 /* The tape of ampnet_sa_train_backward_f32 (csrc/set_abstraction_train.hip; tests/test_sa_train_gpu.py checks every layer alone on it).

@@ -18,7 +18,6 @@ namespace {
 // ORDER = params.CLS_HEAD_PARAMS of the Python package = state_dict order of the reference module
 enum ClsParam { CP_INPROJ_W = 0, CP_INPROJ_B, CP_OUTPROJ_W, CP_OUTPROJ_B, CP_CONV1_W, CP_CONV1_B, CP_FC2_W, CP_FC2_B, CP_FC3_W, CP_FC3_B,
                 CP_BN2_W, CP_BN2_B, CP_COUNT };
-constexpr int CLS_HID = 128, CLS_MAX_CLASSES = 16;
 
 struct ClsWs {
     float *qkv, *probs, *ctx, *o;      // [Q,768] [B,8,W,W] [Q,256] [Q,256]
@@ -181,6 +180,40 @@ __global__ __launch_bounds__(256) void cls_mix_bwd_kernel(const float *__restric
 }
 
 }  // namespace
+
+// the launches of the head's own kernels: geometry lives here (head.h)
+int cls_mix(const float *o, const float *cw, const float *cb, int B, int W, float *x, hipStream_t st)
+{
+    hipLaunchKernelGGL(cls_mix_kernel, dim3(B), dim3(256), 0, st, o, cw, cb, B, W, x);
+    return check_launch("cls_mix_kernel");
+}
+
+int cls_weights(const float *probs, int B, int W, float drop_p, uint32_t drop_base, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(cls_weights_kernel, dim3(cdiv(B * W * W, 256)), dim3(256), 0, st, probs, B, W, drop_p, drop_base, out);
+    return check_launch("cls_weights_kernel");
+}
+
+int cls_bn_act(float *z, const float *b2, const float *gamma, const float *beta, float *rmean, float *rvar, int B, int train, float *scale,
+               float *shift, float *mean, float *invstd, float *act, hipStream_t st)
+{
+    hipLaunchKernelGGL(cls_bn_act_kernel, dim3(CLS_HID / 64), dim3(64), 0, st, z, b2, gamma, beta, rmean, rvar, B, train, scale, shift, mean, invstd,
+                       act);
+    return check_launch("cls_bn_act_kernel");
+}
+
+int cls_out(const float *act, const float *W3, const float *b3, int B, int C, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(cls_out_kernel, dim3(B), dim3(64), 0, st, act, W3, b3, C, out);
+    return check_launch("cls_out_kernel");
+}
+
+int cls_mix_bwd(const float *dx, const float *x, const float *o, const float *cw, int B, int W, float *d_o, float *cwpart, hipStream_t st)
+{
+    hipLaunchKernelGGL(cls_mix_bwd_kernel, dim3(B), dim3(256), 0, st, dx, x, o, cw, B, W, d_o, cwpart);
+    return check_launch("cls_mix_bwd_kernel");
+}
+
 }  // namespace ampnet
 
 using namespace ampnet;
@@ -227,17 +260,13 @@ extern "C" int ampnet_cls_head_fwd_f32(const float *const *params_host, float *c
     TRY(attention_core(ws.qkv, key_pad_mask, ws.probs, ws.ctx, B, W, dp, drop_base(seed, 0), st));
     TRY(tok_gemm(ws.ctx, P[CP_OUTPROJ_W], P[CP_OUTPROJ_B], 256, ws.o));
     if (attn_weights) {
-        hipLaunchKernelGGL(cls_weights_kernel, dim3(cdiv(B * W * W, 256)), dim3(256), 0, st, ws.probs, B, W, dp, drop_base(seed, 0), attn_weights);
-        TRY(check_launch("cls_weights_kernel"));
+        TRY(cls_weights(ws.probs, B, W, dp, drop_base(seed, 0), attn_weights, st));
     }
-    hipLaunchKernelGGL(cls_mix_kernel, dim3(B), dim3(256), 0, st, ws.o, P[CP_CONV1_W], P[CP_CONV1_B], B, W, ws.x);
-    TRY(check_launch("cls_mix_kernel"));
+    TRY(cls_mix(ws.o, P[CP_CONV1_W], P[CP_CONV1_B], B, W, ws.x, st));
     TRY(sgemm_small(0, 1, B, CLS_HID, 256, ws.x, 256, P[CP_FC2_W], 256, ws.z, CLS_HID, 0, st));
-    hipLaunchKernelGGL(cls_bn_act_kernel, dim3(CLS_HID / 64), dim3(64), 0, st, ws.z, P[CP_FC2_B], P[CP_BN2_W], P[CP_BN2_B], buffers_host[0],
-                       buffers_host[1], B, train, ws.scale, ws.shift, ws.mean, ws.invstd, ws.act);
-    TRY(check_launch("cls_bn_act_kernel"));
-    hipLaunchKernelGGL(cls_out_kernel, dim3(B), dim3(64), 0, st, ws.act, P[CP_FC3_W], P[CP_FC3_B], n_classes, out);
-    return check_launch("cls_out_kernel");
+    TRY(cls_bn_act(ws.z, P[CP_FC2_B], P[CP_BN2_W], P[CP_BN2_B], buffers_host[0], buffers_host[1], B, train, ws.scale, ws.shift, ws.mean, ws.invstd,
+                   ws.act, st));
+    return cls_out(ws.act, P[CP_FC3_W], P[CP_FC3_B], B, n_classes, out, st);
 }
 
 extern "C" size_t ampnet_cls_head_bwd_workspace_bytes(int B, int W)
@@ -276,8 +305,7 @@ extern "C" int ampnet_cls_head_bwd_f32(const float *const *params_host, float *c
     TRY(sgemm_linear_bwd(B, CLS_HID, 256, b.dy, CLS_HID, f.x, 256, P[CP_FC2_W], 256, G[CP_FC2_W], 256, b.dx, 256, st));
     TRY(colsum(b.dy, B, CLS_HID, G[CP_FC2_B], st));
     // conv_1 over the re-viewed attention output
-    hipLaunchKernelGGL(cls_mix_bwd_kernel, dim3(B), dim3(256), 0, st, b.dx, f.x, f.o, P[CP_CONV1_W], B, W, b.d_o, b.cwpart);
-    TRY(check_launch("cls_mix_bwd_kernel"));
+    TRY(cls_mix_bwd(b.dx, f.x, f.o, P[CP_CONV1_W], B, W, b.d_o, b.cwpart, st));
     TRY(colsum(b.cwpart, B, W + 1, b.dx, st));                          // dx is free now: [0 .. W) = d conv_1.weight, [W] = d conv_1.bias
     if (hipMemcpyAsync(G[CP_CONV1_W], b.dx, (size_t)W * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipMemcpyAsync(G[CP_CONV1_B], b.dx + W, sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)

@@ -113,7 +113,37 @@ HeadPointParams point_params(const float *const *P, float *const *bufs)
     return pp;
 }
 
+// test hook (layer_probe.hip): y[0][i] = tanhf(x[i]), y[1][i] = sigmoidf_(x[i]), the two device functions of the cell above
+__global__ __launch_bounds__(256) void gru_act_sweep_kernel(const float *__restrict__ x, float *__restrict__ y, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    y[i] = tanhf(x[i]);
+    y[(size_t)n + i] = sigmoidf_(x[i]);
+}
+
 }  // namespace
+
+// the launches of the two recurrence kernels: geometry and LDS size live here (head.h)
+int gru_seq(const float *gi, const float *Whh, const float *bhh, float *h_out, float *gates, int B, int W, hipStream_t st)
+{
+    hipLaunchKernelGGL(gru_seq_kernel, dim3(B), dim3(64), (size_t)GRU_H * (G3 + 1) * sizeof(float), st, gi, Whh, bhh, h_out, gates, W);
+    return check_launch("gru_seq_kernel");
+}
+
+int gru_seq_bwd(const float *dH, const float *gates, const float *h_all, const float *Whh, float *dgi, float *dgh, float *hprev_out, int B, int W,
+                hipStream_t st)
+{
+    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(B), dim3(64), (size_t)G3 * GRU_H * sizeof(float), st, dH, gates, h_all, Whh, dgi, dgh, hprev_out, W);
+    return check_launch("gru_seq_bwd_kernel");
+}
+
+int gru_act_sweep(const float *x, float *y, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(gru_act_sweep_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, x, y, n);
+    return check_launch("gru_act_sweep_kernel");
+}
+
 }  // namespace ampnet
 
 using namespace ampnet;
@@ -162,9 +192,7 @@ extern "C" int ampnet_gru_head_fwd_f32(const float *const *params_host, float *c
         return pw_gemm(g, st);
     };
     TRY(tok_gemm(gl, 256, P[GP_WIH], 256, P[GP_BIH], G3, ws.qkv));                              // gi = W_ih x + b_ih, all steps at once
-    hipLaunchKernelGGL(gru_seq_kernel, dim3(B), dim3(64), (size_t)GRU_H * (G3 + 1) * sizeof(float), st, ws.qkv, P[GP_WHH], P[GP_BHH], ws.g2,
-                       tr ? ws.ctx : nullptr, W);
-    TRY(check_launch("gru_seq_kernel"));
+    TRY(gru_seq(ws.qkv, P[GP_WHH], P[GP_BHH], ws.g2, tr ? ws.ctx : nullptr, B, W, st));
     TRY(tok_gemm(ws.g2, GRU_H, P[GP_CONV2_W] + 64, 64 + GRU_H, P[GP_CONV2_B], 128, ws.gbias));   // hidden-state half of conv_2 + its bias
 
     HeadLossArgs o;
@@ -209,9 +237,7 @@ extern "C" int ampnet_gru_head_bwd_f32(const float *const *params_host, float *c
     TRY(head_points_bwd(s, f, b, point_params(P, nullptr), pg, lo, win_off, drop_p, seed, dlogits, d_lo, st));
     // gbias = h W2[:, 64:]^T + b2: weight gradient of the hidden-state half and dL/dh of every step
     TRY(sgemm_linear_bwd(Q, 128, GRU_H, b.dgb, 128, f.g2, GRU_H, P[GP_CONV2_W] + 64, 64 + GRU_H, G[GP_CONV2_W] + 64, 64 + GRU_H, b.d_g2, GRU_H, st));
-    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(B), dim3(64), (size_t)G3 * GRU_H * sizeof(float), st, b.d_g2, f.ctx, f.g2, P[GP_WHH], b.d_qkv,
-                       b.d_ctx, b.hid, W);
-    TRY(check_launch("gru_seq_bwd_kernel"));
+    TRY(gru_seq_bwd(b.d_g2, f.ctx, f.g2, P[GP_WHH], b.d_qkv, b.d_ctx, b.hid, B, W, st));
     // gi = x W_ih^T + b_ih: dW_ih = d(gi)^T x, dx = d(gi) W_ih;  gh = h_{t-1} W_hh^T + b_hh: dW_hh = d(gh)^T h_{t-1}
     TRY(sgemm_linear_bwd(Q, G3, 256, b.d_qkv, G3, gl, 256, P[GP_WIH], 256, G[GP_WIH], 256, d_gl, 256, st));
     TRY(colsum(b.d_qkv, Q, G3, G[GP_BIH], st));

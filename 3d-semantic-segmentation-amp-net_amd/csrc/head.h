@@ -98,6 +98,29 @@ int attention_core(const float *qkv, const uint8_t *key_pad_mask, float *probs, 
 // gradients of the above wrt q, k, v given d(ctx): dqkv [Q, 768]
 int attention_core_bwd(const float *qkv, const float *probs, const float *dctx, float *dqkv, int B, int W, float drop_p, uint32_t drop_base,
                        hipStream_t st);
+// the GRU recurrence (gru_head.hip), one wave per sample: gi [B * W, 192] = W_ih x + b_ih -> h_out [B * W, 64]; gates [B * W, 4, 64] =
+// (r, z, n, W_hn h + b_hn) for the backward, or nullptr
+int gru_seq(const float *gi, const float *Whh, const float *bhh, float *h_out, float *gates, int B, int W, hipStream_t st);
+// back-propagation through time: dH [B * W, 64] -> d(gi), d(gh) [B * W, 192] and h_{t-1} [B * W, 64] (zeros at t = 0 of every sample)
+int gru_seq_bwd(const float *dH, const float *gates, const float *h_all, const float *Whh, float *dgi, float *dgh, float *hprev_out, int B, int W,
+                hipStream_t st);
+// test hook: y [2, n] = tanhf(x), the recurrence's sigmoid(x)
+int gru_act_sweep(const float *x, float *y, int n, hipStream_t st);
+
+// the classification head's own kernels (cls_head.hip)
+constexpr int CLS_HID = 128, CLS_MAX_CLASSES = 16;
+// x [B, 256] = relu(conv_1 over the .view(-1, W, 256) of the sequence-first attention output; o [B * W, 256] holds token (b, w) at row b W + w)
+int cls_mix(const float *o, const float *cw, const float *cb, int B, int W, float *x, hipStream_t st);
+// out [B, W, W] = mean over the heads of the (dropped) probabilities probs [B, 8, W, W]
+int cls_weights(const float *probs, int B, int W, float drop_p, uint32_t drop_base, float *out, hipStream_t st);
+// z [B, 128] += b2 in place; bn_2 over the B rows (train: batch statistics and the running update, else the running statistics) + ReLU -> act
+int cls_bn_act(float *z, const float *b2, const float *gamma, const float *beta, float *rmean, float *rvar, int B, int train, float *scale,
+               float *shift, float *mean, float *invstd, float *act, hipStream_t st);
+// out [B, C] = act W3^T + b3, C <= CLS_MAX_CLASSES
+int cls_out(const float *act, const float *W3, const float *b3, int B, int C, float *out, hipStream_t st);
+// conv_1 backward: d_o [B * W, 256] and the per-sample partials cwpart [B, W + 1] of d conv_1.weight (columns 0 .. W - 1) and d conv_1.bias (column W)
+int cls_mix_bwd(const float *dx, const float *x, const float *o, const float *cw, int B, int W, float *d_o, float *cwpart, hipStream_t st);
+
 // conv_4 backward + dropout + bn_3 / ReLU mask (head_bwd.hip): one workgroup per HEAD_OUT_BWD_ROWS rows
 constexpr int HEAD_OUT_BWD_ROWS = 1024;
 struct HeadOutBwd {

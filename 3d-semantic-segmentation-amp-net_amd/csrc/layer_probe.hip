@@ -1,7 +1,8 @@
 // layer_probe.hip -- test hooks (include/ampnet_hip.h, "test hooks"): one launch of pw_gemm / pw_bwd_fused / pw_dgrad / pw_wgrad, of a
 // kernel of the max-pooled layers' backward or of the input layers' weight gradient on buffers the caller chooses, for the layer-local
 // float64 parity tests (tests/test_pw_layers_gpu.py, tests/test_pooled_bwd_gpu.py), of the head's kernels (tests/test_head_layers_gpu.py) and of
-// the BatchNorm / pooling glue kernels (tests/test_bn_glue_gpu.py).  No product path calls these.
+// the BatchNorm / pooling glue kernels (tests/test_bn_glue_gpu.py), and of the GRU recurrence and the classification head's kernels
+// (tests/test_gru_cls_layers_gpu.py).  No product path calls these.
 //
 // The probes exist for shared GPUs: before anything is launched every extent is checked on the host against what the kernel will
 // touch (rows from win_off / uniform_rows, partial slots from the statistics plan, ld x rows), so that a wrong test gets
@@ -903,4 +904,79 @@ extern "C" int ampnet_probe_bn_plan(int Q, int chunks, int n_slots, int C, Ampne
     o->input_stat_parts = cdiv(o->input_stat_lanes, n_slots) * n_slots;
     o->merge_floats = (int64_t)bn_finalize_merge_floats(n_slots, C);
     return AMPNET_OK;
+}
+
+// ---- the GRU recurrence and the classification head's kernels (tests/test_gru_cls_layers_gpu.py) ------------------------------------------
+// One launch through the wrappers of head.h that ampnet_gru_head_* / ampnet_cls_head_* call themselves.
+extern "C" int ampnet_probe_seq_f32(const AmpnetSeqProbe *d, void *stream)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(d, "probe_seq: null descriptor");
+    AMPNET_REQUIRE(d->op >= 0 && d->op <= 7, "probe_seq: op %d not built", d->op);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d->op == 7) {
+        AMPNET_REQUIRE(d->rows >= 1 && d->rows <= (1 << 24) && d->X && d->X_n >= d->rows && d->Y && d->Y_n >= 2 * (int64_t)d->rows, "probe_seq: sweep buffers short");
+        ProfScope prof("gru_act_sweep", 0.0, 0.0, st);
+        return gru_act_sweep(d->X, d->Y, d->rows, st);
+    }
+    AMPNET_REQUIRE(d->B >= 1 && d->B <= 65535, "probe_seq: B %d", d->B);
+    const int64_t B = d->B, W = d->W, Q = B * W;
+    switch (d->op) {
+    case 0:
+    case 1: {
+        AMPNET_REQUIRE(d->W >= 1 && d->W <= 4096, "probe_seq: W %d (1 <= W <= 4096)", d->W);
+        AMPNET_REQUIRE(d->Whh && d->Whh_n >= 3 * GRU_H * GRU_H, "probe_seq: Whh [192, 64] short");
+        if (d->op == 0) {
+            AMPNET_REQUIRE(d->gi && d->gi_n >= Q * 3 * GRU_H && d->bhh && d->bhh_n >= 3 * GRU_H, "probe_seq: gi / bhh short");
+            AMPNET_REQUIRE(d->h_out && d->h_out_n >= Q * GRU_H && (!d->gates || d->gates_n >= Q * 4 * GRU_H), "probe_seq: h_out / gates short");
+            ProfScope prof("gru_seq_kernel", 0.0, 0.0, st);
+            return gru_seq(d->gi, d->Whh, d->bhh, d->h_out, d->gates, d->B, d->W, st);
+        }
+        AMPNET_REQUIRE(d->dH && d->dH_n >= Q * GRU_H && d->gates && d->gates_n >= Q * 4 * GRU_H && d->h_all && d->h_all_n >= Q * GRU_H,
+                       "probe_seq: dH / gates / h_all short");
+        AMPNET_REQUIRE(d->dgi && d->dgi_n >= Q * 3 * GRU_H && d->dgh && d->dgh_n >= Q * 3 * GRU_H && d->hprev_out && d->hprev_out_n >= Q * GRU_H,
+                       "probe_seq: dgi / dgh / hprev_out short");
+        ProfScope prof("gru_seq_bwd_kernel", 0.0, 0.0, st);
+        return gru_seq_bwd(d->dH, d->gates, d->h_all, d->Whh, d->dgi, d->dgh, d->hprev_out, d->B, d->W, st);
+    }
+    case 2:
+    case 3:
+    case 6: {
+        AMPNET_REQUIRE(d->W >= 1 && d->W <= HEAD_MAX_W, "probe_seq: W %d (1 <= W <= %d)", d->W, HEAD_MAX_W);
+        if (d->op == 3) {
+            AMPNET_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "probe_seq: drop_p %f", (double)d->drop_p);
+            AMPNET_REQUIRE(d->probs && d->probs_n >= B * HEAD_HEADS * W * W && d->wout && d->wout_n >= B * W * W, "probe_seq: probs / wout short");
+            ProfScope prof("cls_weights_kernel", 0.0, 0.0, st);
+            return cls_weights(d->probs, d->B, d->W, d->drop_p, d->drop_seed, d->wout, st);
+        }
+        AMPNET_REQUIRE(d->o && d->o_n >= Q * 256 && d->cw && d->cw_n >= W && d->x && d->x_n >= B * 256, "probe_seq: o / cw / x short");
+        if (d->op == 2) {
+            AMPNET_REQUIRE(d->cb && d->cb_n >= 1, "probe_seq: cb short");
+            ProfScope prof("cls_mix_kernel", 0.0, 0.0, st);
+            return cls_mix(d->o, d->cw, d->cb, d->B, d->W, d->x, st);
+        }
+        AMPNET_REQUIRE(d->dx && d->dx_n >= B * 256 && d->d_o && d->d_o_n >= Q * 256 && d->cwpart && d->cwpart_n >= B * (W + 1), "probe_seq: dx / d_o / cwpart short");
+        ProfScope prof("cls_mix_bwd_kernel", 0.0, 0.0, st);
+        return cls_mix_bwd(d->dx, d->x, d->o, d->cw, d->B, d->W, d->d_o, d->cwpart, st);
+    }
+    case 4: {
+        AMPNET_REQUIRE(d->z && d->z_n >= B * CLS_HID && d->act && d->act_n >= B * CLS_HID, "probe_seq: z / act [B, 128] short");
+        AMPNET_REQUIRE(d->b2 && d->b2_n >= CLS_HID && d->gamma && d->gamma_n >= CLS_HID && d->beta && d->beta_n >= CLS_HID && d->rmean &&
+                           d->rmean_n >= CLS_HID && d->rvar && d->rvar_n >= CLS_HID,
+                       "probe_seq: b2 / gamma / beta / rmean / rvar [128] short");
+        AMPNET_REQUIRE(d->scale && d->scale_n >= CLS_HID && d->shift && d->shift_n >= CLS_HID && d->mean && d->mean_n >= CLS_HID && d->invstd &&
+                           d->invstd_n >= CLS_HID,
+                       "probe_seq: scale / shift / mean / invstd [128] short");
+        ProfScope prof("cls_bn_act_kernel", 0.0, 0.0, st);
+        return cls_bn_act(d->z, d->b2, d->gamma, d->beta, d->rmean, d->rvar, d->B, d->train ? 1 : 0, d->scale, d->shift, d->mean, d->invstd, d->act, st);
+    }
+    default: {   // 5
+        AMPNET_REQUIRE(d->C >= 1 && d->C <= CLS_MAX_CLASSES, "probe_seq: %d classes, supported 1..%d", d->C, CLS_MAX_CLASSES);
+        AMPNET_REQUIRE(d->act && d->act_n >= B * CLS_HID && d->W3 && d->W3_n >= (int64_t)d->C * CLS_HID && d->b3 && d->b3_n >= d->C && d->out &&
+                           d->out_n >= B * d->C,
+                       "probe_seq: act / W3 / b3 / out short");
+        ProfScope prof("cls_out_kernel", 0.0, 0.0, st);
+        return cls_out(d->act, d->W3, d->b3, d->B, d->C, d->out, st);
+    }
+    }
 }

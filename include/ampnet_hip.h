@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 15
+#define AMPNET_ABI_VERSION 16
 
 enum {
     AMPNET_OK = 0,
@@ -956,6 +956,59 @@ typedef struct AmpnetBnPlan {
     int64_t merge_floats;          /* bn_finalize_merge_floats(n_slots, C) */
 } AmpnetBnPlan;
 
+/* One launch of a kernel of the GRU recurrence (csrc/gru_head.hip) or of the classification head (csrc/cls_head.hip) through the launch
+ * wrappers the product entry points call (csrc/head.h), by `op` (ABI 16; csrc/layer_probe.hip, tests/test_gru_cls_layers_gpu.py):
+ *   0 gru_seq_kernel      (gi [B * W, 192] = W_ih x + b_ih, Whh [192, 64], bhh [192] -> h_out [B * W, 64]; gates [B * W, 256] =
+ *                          (r, z, n, W_hn h + b_hn) per step, or NULL)
+ *   1 gru_seq_bwd_kernel  (dH [B * W, 64], gates, h_all [B * W, 64], Whh -> dgi, dgh [B * W, 192], hprev_out [B * W, 64])
+ *   2 cls_mix_kernel      (o [B * W, 256] (token (b, w) at row b W + w), cw [W], cb [1] -> x [B, 256])
+ *   3 cls_weights_kernel  (probs [B, 8, W, W], drop_p, drop_seed = the hash base -> wout [B, W, W])
+ *   4 cls_bn_act_kernel   (z [B, 128] in place, b2, gamma, beta [128], rmean, rvar [128] in place when train -> scale, shift, mean,
+ *                          invstd [128], act [B, 128])
+ *   5 cls_out_kernel      (act [B, 128], W3 [C, 128], b3 [C] -> out [B, C])
+ *   6 cls_mix_bwd_kernel  (dx, x [B, 256], o, cw -> d_o [B * W, 256], cwpart [B, W + 1])
+ *   7 tanhf / sigmoid sweep (X [rows] -> Y [2, rows] = tanhf(x), the recurrence's 1 / (1 + __expf(-x)))
+ * 1 <= B <= 65535; 1 <= W <= 4096 for ops 0 and 1, 1 <= W <= 32 for ops 2, 3, 6; 1 <= C <= 16 for op 5; 0 <= drop_p < 1; every extent is
+ * checked on the host before the launch, which is recorded under the kernel's name for ampnet_profile_read ("gru_act_sweep" for op 7). */
+typedef struct AmpnetSeqProbe {
+    int32_t op, B, W, C, train, rows; float drop_p; uint32_t drop_seed;
+    const float *gi; int64_t gi_n;
+    const float *Whh; int64_t Whh_n;
+    const float *bhh; int64_t bhh_n;
+    float *h_out; int64_t h_out_n;
+    float *gates; int64_t gates_n;                               /* written by op 0, read by op 1 */
+    const float *dH; int64_t dH_n;
+    const float *h_all; int64_t h_all_n;
+    float *dgi; int64_t dgi_n;
+    float *dgh; int64_t dgh_n;
+    float *hprev_out; int64_t hprev_out_n;
+    const float *o; int64_t o_n;
+    const float *cw; int64_t cw_n;
+    const float *cb; int64_t cb_n;
+    float *x; int64_t x_n;                                       /* written by op 2, read by op 6 */
+    const float *probs; int64_t probs_n;
+    float *wout; int64_t wout_n;
+    float *z; int64_t z_n;
+    const float *b2; int64_t b2_n;
+    const float *gamma; int64_t gamma_n;
+    const float *beta; int64_t beta_n;
+    float *rmean; int64_t rmean_n;
+    float *rvar; int64_t rvar_n;
+    float *scale; int64_t scale_n;
+    float *shift; int64_t shift_n;
+    float *mean; int64_t mean_n;
+    float *invstd; int64_t invstd_n;
+    float *act; int64_t act_n;                                   /* written by op 4, read by op 5 */
+    const float *W3; int64_t W3_n;
+    const float *b3; int64_t b3_n;
+    float *out; int64_t out_n;
+    const float *dx; int64_t dx_n;
+    float *d_o; int64_t d_o_n;
+    float *cwpart; int64_t cwpart_n;
+    const float *X; int64_t X_n;
+    float *Y; int64_t Y_n;
+} AmpnetSeqProbe;
+
 int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream);
 int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream);
 int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream);
@@ -963,6 +1016,7 @@ int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void *stream);
 int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream);
 int ampnet_probe_bn_f32(const AmpnetBnProbe *d, void *stream);
 int ampnet_probe_bn_plan(int Q, int chunks, int n_slots, int C, AmpnetBnPlan *out_host);
+int ampnet_probe_seq_f32(const AmpnetSeqProbe *d, void *stream);
 int ampnet_probe_pw_plan(int Q, int n_slots, int max_rows, int cin, int cout, int stat_chunks, const AmpnetPwBwdProbe *bwd, AmpnetPwPlan *out_host);
 
 /* The tape of ampnet_sa_train_backward_f32 (csrc/set_abstraction_train.hip; tests/test_sa_train_gpu.py checks every layer alone on it).

@@ -16,8 +16,8 @@
 //       fp3 of pointnet_2 (384 -> 256 -> 256).  The one shape family of the forward's limits that this exceeds (cin_0 > 504 with three
 //       layers of 256) builds X_0 in the space of X_2 and X_3 and REBUILDS it there before layer 0's backward.
 //       Why the layer's GEMM is run a second time instead of keeping a: a tile of a per layer would double the LDS, and a cannot be had
-//       back from y when scale = 0.  Why mlp_tiles is not reused for it: its epilogue is handed relu(y) only; its K loop is restated here
-//       (fpb_recompute) with the raw accumulator going to the backward's epilogue, and fused_mlp.h stays as the forward's tests pin it.
+//       back from y when scale = 0.  Why mlp_tiles is not reused for it: its epilogue is handed relu(y) only; its K loop is fused_mlp.h's
+//       mlp_accumulate, whose raw accumulator goes to the backward's epilogue (fpb_recompute).
 //       dx = dz W is the forward's lane map with cin and cout exchanged: lane (r, h) supplies row r of dz and COLUMN c0 + r of W, read along
 //       W's rows through L2 (128 contiguous bytes per half wave and k); the contraction runs over o ascending in blocks of 8, k-step
 //       i < 4 of lane half h taking o = o0 + 2 i + h, one fmaf chain per output element.
@@ -46,7 +46,7 @@ struct FpBwdPlan {
     float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts;
 };
 
-// The accumulators of layer l on the wave's tile x, NT column tiles from n0, in the forward's order (mlp_tiles<NT, K_QUADS, VEC>), and the
+// The accumulators of layer l on the wave's tile x, NT column tiles from n0, in the forward's order (mlp_accumulate<NT, K_QUADS, VEC>), and the
 // backward's epilogue: d [32][ldd] holds dx_l on entry (dout != nullptr: the rows come from global memory, row stride cout) and dz on exit.
 template <int NT, bool VEC>
 __device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
@@ -56,7 +56,7 @@ __device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const flo
 {
     const int r = lane & 31, h = lane >> 5;
     f32x16 acc[NT];
-    fpb_accumulate<NT, VEC>(x, ldx, w, cin, kp, n0, acc, lane);              // fp_bwd_tiles.h
+    mlp_accumulate<NT, K_QUADS, VEC>(acc, mlp_operand<K_QUADS>(x, ldx, r, h), w, cin, cin, kp, n0, r, h);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int col = n0 + 32 * t + r;
@@ -137,8 +137,8 @@ __global__ __launch_bounds__(64) void fp_backward_kernel(MlpPlan p, FpBwdPlan b,
             float *xo = l ? x : nullptr;
             float *dp1 = dpoints1 ? dpoints1 + grow * D1 : nullptr, *dx0 = b.dx0 + grow * D2;
             int c0 = 0;
-            for (; c0 + 128 <= cin; c0 += 128) fpb_dgrad<4>(d, ldd, p.w[l], cin, cout, c0, xo, ldx, dp1, D1, dx0, D2, rows, lane);
-            for (; c0 < cin; c0 += 32) fpb_dgrad<1>(d, ldd, p.w[l], cin, cout, c0, xo, ldx, dp1, D1, dx0, D2, rows, lane);
+            for (; c0 + 128 <= cin; c0 += 128) mlp_dgrad<4>(d, ldd, p.w[l], cin, cout, c0, xo, ldx, dp1, D1, dx0, D2, rows, lane);
+            for (; c0 < cin; c0 += 32) mlp_dgrad<1>(d, ldd, p.w[l], cin, cout, c0, xo, ldx, dp1, D1, dx0, D2, rows, lane);
             wave_lds_sync();
         }
     }
@@ -207,30 +207,8 @@ int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, const int *
     sh.n_tiles = n_clouds * sh.tiles_per_cloud;
     sh.grid = sh.n_tiles < FPB_MAX_GRID ? sh.n_tiles : FPB_MAX_GRID;
     fpb_chunk_rule(sh.M, sh.chunk_rows, sh.chunks);
-    size_t off = align_up((size_t)AMPNET_FP_WORKSPACE_BYTES / sizeof(float), 64), wmax = 0;
-    for (int l = 0; l < L; ++l) {
-        const int cout = cout_host[l];
-        AMPNET_REQUIRE(cout >= 32 && cout <= AMPNET_FP_MAX_COUT && cout % 32 == 0, "%s: layer %d has cout=%d, must be a multiple of 32 in [32, %d]",
-                       what, l, cout, AMPNET_FP_MAX_COUT);
-        sh.cin[l] = l ? cout_host[l - 1] : D1 + D2;
-        sh.ldxs[l] = (sh.cin[l] + 31) / 32 * 32;
-        sh.sum_c += cout;
-        if ((size_t)cout * sh.ldxs[l] > wmax) wmax = (size_t)cout * sh.ldxs[l];
-    }
-    sh.off_parts = off;
-    off += align_up((size_t)sh.grid * 2 * sh.sum_c, 64);
-    for (int l = 0; l < L; ++l) {
-        sh.off_xs[l] = off;
-        off += align_up((size_t)sh.M * sh.ldxs[l], 64);
-        sh.off_dz[l] = off;
-        off += align_up((size_t)sh.M * cout_host[l], 64);
-    }
-    sh.off_dx0 = off;
-    off += align_up((size_t)sh.M * D2, 64);
-    sh.off_wpart = off;
-    off += align_up((size_t)sh.chunks * wmax, 64);
-    sh.floats = off;
-    return AMPNET_OK;
+    return mlp_bwd_layout(what, align_up((size_t)AMPNET_FP_WORKSPACE_BYTES / sizeof(float), 64), D1 + D2, D2, sh.M, sh.grid, sh.chunks, cout_host, L,
+                          sh);
 }
 
 }  // namespace ampnet

@@ -7,13 +7,12 @@
 //   fpt_stats_kernel (pass l)   The forward's workgroup (its plan: up to four waves that share the staged weights of layers < l); a wave
 //       owns 32 consecutive fine points of one cloud at a time.  It rebuilds the tile's rows (fp_rows.h), runs layers < l with the
 //       forward's own code (mlp_dispatch<K_QUADS>, reading the scale and shift that the earlier passes' finalizes wrote), forms layer l's
-//       raw accumulators a = W x in the forward's contraction order (fpb_accumulate) and, per column, the tile's count, mean and
+//       raw accumulators a = W x in the forward's contraction order (mlp_accumulate) and, per column, the tile's count, mean and
 //       sum (a - mean)^2 over its VALID rows (the rows past n of a cloud's last tile enter none of the three).  The tiles r, r + P, ..
 //       (P = min(tiles, 1024)) are merged in ascending order into row r of a partials array with Chan's pairwise formula; a row belongs to
 //       one wave, so every word of it is read and written by the same lane only, and the order does not depend on the plan.
-//   fpt_stats_finalize_kernel   a wave per channel merges the rows with the same formula (lane t the rows t, t + 64, .. ascending, then a
-//       halving tree over the lanes: 16 + 6 dependent merges instead of 1024) and writes scale_l, shift_l into the
-//       fold, save_mean, save_invstd, and the running-statistics update.
+//   fpt_stats_finalize_kernel   (bn_train.hip) a wave per channel merges the rows with the same formula and writes scale_l, shift_l into
+//       the fold, save_mean, save_invstd, and the running-statistics update.
 //   fp_forward_kernel           the eval forward's kernel on that fold (fp_forward_launch): eval and train share the hot kernel, and the
 //       accumulators the statistics were taken from are the ones it normalises, bit for bit.
 //   Why recompute layers < l in every pass instead of spilling a_l: the eval forward keeps no activation in memory and neither does this;
@@ -26,56 +25,23 @@
 //                 later phases: the rows are never built again);  then part B below with dx = dout.
 //       l < L-1:  part A for layer l+1: x_{l+1} from the workspace into T0, a_{l+1} recomputed, dy_{l+1} back from the workspace,
 //                 dz_{l+1} = scale (dy - dbeta / M - (a - mu) invstd dgamma / M) with the sums final (zero for the rows past n) into T1 and
-//                 over dy in the workspace;  dx_l = dz_{l+1} W_{l+1} (fpb_dgrad) over T0;  l = -1 ends here, dx_0 going to dpoints1 and the
+//                 over dy in the workspace;  dx_l = dz_{l+1} W_{l+1} (mlp_dgrad) over T0;  l = -1 ends here, dx_0 going to dpoints1 and the
 //                 gather's rows.
 //       part B for layer l:  x_l from the workspace into T1, a_l recomputed, dy_l = dx_l [fma(a, scale, shift) > 0] stored to the workspace,
 //                 sum dy and sum dy a added into the workgroup's own partial row (rows in the accumulator's order, lane half 0 before
 //                 half 1, tiles ascending).
-//   fpt_bwd_finalize_kernel     a wave per channel adds the partial rows (lane t rows t, t + 64, .. ascending, then a halving tree), writes
-//       dbeta, dgamma = invstd (G - mu dbeta), dbias = 0 and the two coefficients dbeta / M and dgamma invstd / M of the next phase.
+//   fpt_bwd_finalize_kernel     (bn_train.hip) a wave per channel adds the partial rows and writes dbeta, dgamma = invstd (G - mu dbeta),
+//       dbias = 0 and the two coefficients dbeta / M and dgamma invstd / M of the next phase.
 //   fpb_wgrad_launch, fp_scatter_launch   dW_l = dz_l^T x_l and dpoints2, exactly the eval backward's.
 //   A phase holds two tiles of the widest layer input (at most 131 KB), so the eval backward's shared-space special case is not needed.
+//   The statistics, part A and part B of a tile are bn_train.h's (bnt_tile_stats, bnt_form_dz, bnt_form_dy), shared with the set
+//   abstraction; this file keeps what is feature propagation's own: the row builder, the tiling and the entry points.
 #include "bn_train.h"
 #include "fp_bwd_tiles.h"
 
 namespace ampnet {
 
 constexpr long long FPT_MAX_ROWS = AMPNET_FP_TRAIN_MAX_ROWS;    // the merges carry row counts as floats: exact up to here, larger M is refused
-
-// the statistics of NT column tiles of layer l from n0 over the valid rows of the wave's tile, merged into the workgroup's partial row
-template <int NT, bool VEC>
-__device__ __forceinline__ void fpt_tile_stats(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int n0, int rows,
-                                               float *part_n, float *part_mean, float *part_m2, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-    fpb_accumulate<NT, VEC>(x, ldx, w, cin, kp, n0, acc, lane);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = n0 + 32 * t + r;
-        float sum = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if ((i & 3) + 8 * (i >> 2) + 4 * h < rows) sum += acc[t][i];
-        sum += __shfl_xor(sum, 32);
-        const float mean = sum / (float)rows;
-        float q = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if ((i & 3) + 8 * (i >> 2) + 4 * h < rows) {
-                const float d = acc[t][i] - mean;
-                q = fmaf(d, d, q);
-            }
-        q += __shfl_xor(q, 32);
-        if (h == 0) {                             // (this lane alone ever touches these three words of the workgroup's partials)
-            float nA = part_n[col], meanA = part_mean[col], m2A = part_m2[col];
-            fpt_chan(nA, meanA, m2A, (float)rows, mean, q);
-            part_n[col] = nA;
-            part_mean[col] = meanA;
-            part_m2[col] = m2A;
-        }
-    }
-}
 
 // parts [n_parts][3 cout_l]: per partial row the count, mean and sum of squared deviations of every channel of layer l.  Row r takes the
 // tiles r, r + n_parts, .. in ascending order and belongs to ONE wave, whatever the plan's waves per workgroup are.
@@ -110,133 +76,18 @@ __global__ __launch_bounds__(256) void fpt_stats_kernel(MlpPlan p, int l, const 
             const int ldx = ld[l & 1];
             int n0 = 0;
             if (p.w_vec[l]) {
-                for (; n0 + 128 <= cout; n0 += 128) fpt_tile_stats<4, true>(x, ldx, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
-                for (; n0 < cout; n0 += 32) fpt_tile_stats<1, true>(x, ldx, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
+                for (; n0 + 128 <= cout; n0 += 128) bnt_tile_stats<4, K_QUADS, true>(x, ldx, 0, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
+                for (; n0 < cout; n0 += 32) bnt_tile_stats<1, K_QUADS, true>(x, ldx, 0, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
             } else {
-                for (; n0 + 128 <= cout; n0 += 128) fpt_tile_stats<4, false>(x, ldx, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
-                for (; n0 < cout; n0 += 32) fpt_tile_stats<1, false>(x, ldx, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
+                for (; n0 + 128 <= cout; n0 += 128) bnt_tile_stats<4, K_QUADS, false>(x, ldx, 0, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
+                for (; n0 < cout; n0 += 32) bnt_tile_stats<1, K_QUADS, false>(x, ldx, 0, p.w[l], cin, kp, n0, rows, part_n, part_mean, part_m2, lane);
             }
             wave_lds_sync();                      // the next tile's rows overwrite tile A
         }
     }
 }
 
-// One wave per channel, as fp_bwd_finalize_kernel: lane t merges the partial rows t, t + 64, .. in ascending order, then the 64 lane results
-// go through a fixed halving tree (lane t takes lane t + 32, 16, .. 1).  A lane without rows carries n = 0, which fpt_chan passes through.
-__global__ __launch_bounds__(256) void fpt_stats_finalize_kernel(FptStats q, const float *__restrict__ parts, int n_parts, float M,
-                                                                float *__restrict__ fold)
-{
-    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= q.cout) return;                      // (the whole wave)
-    float n = 0.0f, mean = 0.0f, m2 = 0.0f;
-    for (int g = lane; g < n_parts; g += 64) {
-        const float *row = parts + (size_t)g * 3 * q.cout;
-        fpt_chan(n, mean, m2, row[c], row[q.cout + c], row[2 * q.cout + c]);
-    }
-    for (int off = 32; off; off >>= 1) {
-        const float nB = __shfl_down(n, off), meanB = __shfl_down(mean, off), m2B = __shfl_down(m2, off);
-        if (nB > 0.0f) fpt_chan(n, mean, m2, nB, meanB, m2B);
-    }
-    if (lane) return;
-    const float var = m2 / M, invstd = 1.0f / sqrtf(var + q.eps);
-    const float scale = q.gamma[c] * invstd;
-    fold[q.fold_off + c] = scale;
-    fold[q.fold_off + q.cout + c] = fmaf(-mean, scale, q.beta[c]);
-    q.save_mean[c] = mean;
-    q.save_invstd[c] = invstd;
-    const float keep = 1.0f - q.momentum;
-    q.running_mean[c] = fmaf(q.momentum, mean + q.bias[c], keep * q.running_mean[c]);
-    q.running_var[c] = fmaf(q.momentum, m2 / (M - 1.0f), keep * q.running_var[c]);
-}
-
-// scale and shift of every layer from the saved statistics, as the forward's finalize formed them (the same two operations: the same bits)
-__global__ void fpt_fold_kernel(MlpPlan p, MlpFold f, float *__restrict__ fold)
-{
-    for (int l = 0; l < p.L; ++l)
-        for (int c = threadIdx.x; c < p.cout[l]; c += blockDim.x) {
-            const float scale = f.gamma[l][c] * f.var[l][c];                      // (slot 5 of a layer holds save_invstd, slot 4 save_mean)
-            fold[p.fold_off[l] + c] = scale;
-            fold[p.fold_off[l] + p.cout[l] + c] = fmaf(-f.mean[l][c], scale, f.beta[l][c]);
-        }
-}
-
-struct FptBwd {
-    int ld;                                                    // odd row stride of both LDS tiles
-    int ldxs[MLP_MAX_LAYERS];                                  // row stride of x_l in the workspace: cin_l rounded up to 32 (zeros)
-    float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts, *coef;     // coef: per layer (fold_off) dbeta / M, then dgamma invstd / M
-    const float *mean[MLP_MAX_LAYERS];
-};
-
-// rows < rows of a global array with row stride ldg -> the wave's tile, `width` columns (a multiple of 8, <= ldg); the rows past `rows` zero
-__device__ __forceinline__ void fpt_load_rows(float *tile, int ld, int width, const float *__restrict__ g, int ldg, int rows, int lane)
-{
-    for (int t = 0; t < 32; ++t)
-        for (int c = lane; c < width; c += 64) tile[t * ld + c] = t < rows ? g[(size_t)t * ldg + c] : 0.0f;
-}
-
-// part A: a of layer j recomputed on tile x; dy of the wave's rows from dz_ws; dz into tile d and over dy in dz_ws
-template <int NT, bool VEC>
-__device__ __forceinline__ void fpt_form_dz(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
-                                            const float *__restrict__ scale, const float *__restrict__ mean, const float *__restrict__ c1,
-                                            const float *__restrict__ c2, float *d, int ldd, int rows, float *dz_ws, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-    fpb_accumulate<NT, VEC>(x, ldx, w, cin, kp, n0, acc, lane);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = n0 + 32 * t + r;
-        const float sc = scale[col], mu = mean[col], k1 = c1[col], k2 = c2[col];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            float dzv = 0.0f;
-            if (row < rows) {
-                const float dy = dz_ws[(size_t)row * cout + col];
-                dzv = sc * fmaf(-(acc[t][i] - mu), k2, dy - k1);
-                dz_ws[(size_t)row * cout + col] = dzv;
-            }
-            d[row * ldd + col] = dzv;
-        }
-    }
-}
-
-// part B: a of layer j recomputed on tile x; dy = dx [y > 0] (dx from `dout`, global with row stride cout, or tile d) to dz_ws and the sums
-template <int NT, bool VEC>
-__device__ __forceinline__ void fpt_form_dy(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
-                                            const float *__restrict__ scale, const float *__restrict__ shift, const float *d, int ldd,
-                                            const float *__restrict__ dout, int rows, float *dz_ws, float *part_b, float *part_g, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-    fpb_accumulate<NT, VEC>(x, ldx, w, cin, kp, n0, acc, lane);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = n0 + 32 * t + r;
-        const float sc = scale[col], sh = shift[col];
-        float sb = 0.0f, sg = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            const float a = acc[t][i];
-            float dy = 0.0f;
-            if (row < rows) {
-                const float din = dout ? dout[(size_t)row * cout + col] : d[row * ldd + col];
-                dy = fmaf(a, sc, sh) > 0.0f ? din : 0.0f;
-                dz_ws[(size_t)row * cout + col] = dy;
-            }
-            sb += dy;
-            sg = fmaf(dy, a, sg);
-        }
-        const float ob = __shfl_down(sb, 32), og = __shfl_down(sg, 32);
-        if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
-            part_b[col] += sb + ob;
-            part_g[col] += sg + og;
-        }
-    }
-}
-
-__global__ __launch_bounds__(64) void fpt_bwd_phase_kernel(MlpPlan p, FptBwd b, int l, const float *__restrict__ points1, int D1,
+__global__ __launch_bounds__(64) void fpt_bwd_phase_kernel(MlpPlan p, BntBwd b, int l, const float *__restrict__ points1, int D1,
                                                           const float *__restrict__ points2, int D2, int n, int s,
                                                           const int32_t *__restrict__ idx, const float *__restrict__ dist2, int k,
                                                           const float *__restrict__ fold, const float *__restrict__ dout, int tiles_per_cloud,
@@ -271,32 +122,32 @@ __global__ __launch_bounds__(64) void fpt_bwd_phase_kernel(MlpPlan p, FptBwd b, 
             x_l = T[(L - 1) & 1];
         } else {
             const int j = l + 1, cin = p.cin[j], cout = p.cout[j], kp = p.kp[j];
-            fpt_load_rows(T[0], ld, kp, b.xs[j] + grow * b.ldxs[j], b.ldxs[j], rows, lane);
+            fpb_load_rows(T[0], ld, kp, b.xs[j] + grow * b.ldxs[j], b.ldxs[j], rows, lane);
             wave_lds_sync();
-            const float *scale = fold + p.fold_off[j], *c1 = b.coef + p.fold_off[j], *c2 = c1 + cout;
+            const float *scale = fold + p.fold_off[j], *shift = scale + cout, *c1 = b.coef + p.fold_off[j], *c2 = c1 + cout;
             float *dz_ws = b.dz[j] + grow * cout;
             int n0 = 0;
             if (p.w_vec[j]) {
                 for (; n0 + 128 <= cout; n0 += 128)
-                    fpt_form_dz<4, true>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, b.mean[j], c1, c2, T[1], ld, rows, dz_ws, lane);
+                    bnt_form_dz<4, K_QUADS, true>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, 0, nullptr, nullptr, dz_ws, lane);
                 for (; n0 < cout; n0 += 32)
-                    fpt_form_dz<1, true>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, b.mean[j], c1, c2, T[1], ld, rows, dz_ws, lane);
+                    bnt_form_dz<1, K_QUADS, true>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, 0, nullptr, nullptr, dz_ws, lane);
             } else {
                 for (; n0 + 128 <= cout; n0 += 128)
-                    fpt_form_dz<4, false>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, b.mean[j], c1, c2, T[1], ld, rows, dz_ws, lane);
+                    bnt_form_dz<4, K_QUADS, false>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, 0, nullptr, nullptr, dz_ws, lane);
                 for (; n0 < cout; n0 += 32)
-                    fpt_form_dz<1, false>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, b.mean[j], c1, c2, T[1], ld, rows, dz_ws, lane);
+                    bnt_form_dz<1, K_QUADS, false>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, 0, nullptr, nullptr, dz_ws, lane);
             }
             wave_lds_sync();
             // dx_l = dz_j W_j over T0 (x_j has been used), or to dpoints1 and the gather's rows
             float *xo = j ? T[0] : nullptr;
             float *dp1 = dpoints1 ? dpoints1 + grow * D1 : nullptr, *dx0 = b.dx0 + grow * D2;
             int c0 = 0;
-            for (; c0 + 128 <= cin; c0 += 128) fpb_dgrad<4>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, dp1, D1, dx0, D2, rows, lane);
-            for (; c0 < cin; c0 += 32) fpb_dgrad<1>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, dp1, D1, dx0, D2, rows, lane);
+            for (; c0 + 128 <= cin; c0 += 128) mlp_dgrad<4>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, dp1, D1, dx0, D2, rows, lane);
+            for (; c0 < cin; c0 += 32) mlp_dgrad<1>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, dp1, D1, dx0, D2, rows, lane);
             wave_lds_sync();
             if (l >= 0) {
-                fpt_load_rows(T[1], ld, p.kp[l], b.xs[l] + grow * b.ldxs[l], b.ldxs[l], rows, lane);
+                fpb_load_rows(T[1], ld, p.kp[l], b.xs[l] + grow * b.ldxs[l], b.ldxs[l], rows, lane);
                 wave_lds_sync();
                 x_l = T[1];
             }
@@ -309,53 +160,18 @@ __global__ __launch_bounds__(64) void fpt_bwd_phase_kernel(MlpPlan p, FptBwd b, 
             int n0 = 0;
             if (p.w_vec[l]) {
                 for (; n0 + 128 <= cout; n0 += 128)
-                    fpt_form_dy<4, true>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
+                    bnt_form_dy<4, K_QUADS, true, true>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
                 for (; n0 < cout; n0 += 32)
-                    fpt_form_dy<1, true>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
+                    bnt_form_dy<1, K_QUADS, true, true>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
             } else {
                 for (; n0 + 128 <= cout; n0 += 128)
-                    fpt_form_dy<4, false>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
+                    bnt_form_dy<4, K_QUADS, false, true>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
                 for (; n0 < cout; n0 += 32)
-                    fpt_form_dy<1, false>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
+                    bnt_form_dy<1, K_QUADS, false, true>(x_l, ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, dsrc, rows, dz_ws, part_b, part_g, lane);
             }
         }
         wave_lds_sync();                          // the next tile overwrites both tiles
     }
-}
-
-// parts [n_parts][2 cout]: a row per workgroup, sum dy then sum dy a.  One wave per channel, as fp_bwd_finalize_kernel.
-__global__ __launch_bounds__(256) void fpt_bwd_finalize_kernel(int cout, const float *__restrict__ parts, int n_parts, float M,
-                                                              const float *__restrict__ mean, const float *__restrict__ invstd,
-                                                              float *__restrict__ dbias, float *__restrict__ dgamma, float *__restrict__ dbeta,
-                                                              float *__restrict__ coef)
-{
-    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= cout) return;                        // (the whole wave)
-    float sb = 0.0f, G = 0.0f;
-    for (int q = lane; q < n_parts; q += 64) {
-        sb += parts[(size_t)q * 2 * cout + c];
-        G += parts[(size_t)q * 2 * cout + cout + c];
-    }
-    for (int off = 32; off; off >>= 1) {
-        sb += __shfl_down(sb, off);
-        G += __shfl_down(G, off);
-    }
-    if (lane) return;
-    const float dg = invstd[c] * fmaf(-mean[c], sb, G);
-    dbeta[c] = sb;
-    dgamma[c] = dg;
-    dbias[c] = 0.0f;
-    coef[c] = sb / M;
-    coef[cout + c] = dg * invstd[c] / M;
-}
-
-// the two limits of the batch statistics on top of the eval entry points' (`what` opens the message)
-static int fpt_rows_ok(const char *what, long long M)
-{
-    AMPNET_REQUIRE(M >= 2, "%s: batch statistics need M = n_clouds * n >= 2 rows, got %lld", what, M);
-    AMPNET_REQUIRE(M <= FPT_MAX_ROWS, "%s: M = n_clouds * n = %lld rows exceed %lld (the row counts of the statistics are exact floats)", what, M,
-                   FPT_MAX_ROWS);
-    return AMPNET_OK;
 }
 
 // what the forward's two entry points derive from the shape
@@ -370,7 +186,7 @@ static int fpt_fwd_shape(const char *what, int D1, int D2, int n_clouds, int n, 
     FpBwdShape b;                                 // (the limits are the backward's, which are the eval forward's)
     int rc = fpb_shape(what, D1, D2, n_clouds, n, cout_host, L, b);
     if (rc != AMPNET_OK) return rc;
-    rc = fpt_rows_ok(what, b.M);
+    rc = bnt_rows_ok(what, b.M, FPT_MAX_ROWS, "n_clouds * n");
     if (rc != AMPNET_OK) return rc;
     sh = {};
     sh.M = b.M;
@@ -432,8 +248,7 @@ extern "C" int ampnet_fp_train_forward_f32(const float *points1, int D1, const f
         if (rc != AMPNET_OK) return rc;
         FptStats q = {f.bias[l], f.gamma[l], f.beta[l], params_host[6 * l + 4], params_host[6 * l + 5], save_mean + ch, save_invstd + ch,
                       f.eps[l],  momentum,   p.cout[l], p.fold_off[l]};
-        hipLaunchKernelGGL(fpt_stats_finalize_kernel, dim3(cdiv(p.cout[l], 4)), dim3(256), 0, st, q, parts, sh.grid, (float)sh.M, ws);
-        rc = check_launch("fpt_stats_finalize_kernel");
+        rc = fpt_stats_finalize_launch(q, parts, sh.grid, sh.M, ws, st);
         if (rc != AMPNET_OK) return rc;
         ch += p.cout[l];
     }
@@ -447,7 +262,7 @@ static int fpt_bwd_shape(const char *what, int D1, int D2, int n_clouds, int n, 
 {
     int rc = fpb_shape(what, D1, D2, n_clouds, n, cout_host, L, sh);
     if (rc != AMPNET_OK) return rc;
-    rc = fpt_rows_ok(what, sh.M);
+    rc = bnt_rows_ok(what, sh.M, FPT_MAX_ROWS, "n_clouds * n");
     if (rc != AMPNET_OK) return rc;
     off_coef = sh.floats;                         // behind the eval backward's layout: two coefficients per channel
     floats = off_coef + align_up((size_t)2 * sh.sum_c, 64);
@@ -492,25 +307,12 @@ extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const 
     p.nw = 1;
     for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // these kernels stage no weights: every layer is read through L2
     float *ws = static_cast<float *>(workspace);
-    FptBwd b = {};
-    int widest = p.kp[0];
-    for (int l = 0; l < L; ++l) widest = p.cout[l] > widest ? p.cout[l] : widest;
-    b.ld = widest + 1;
-    b.parts = ws + sh.off_parts;
-    b.dx0 = ws + sh.off_dx0;
-    b.coef = ws + off_coef;
-    for (int l = 0; l < L; ++l) {
-        b.ldxs[l] = sh.ldxs[l];
-        b.xs[l] = ws + sh.off_xs[l];
-        b.dz[l] = ws + sh.off_dz[l];
-        b.mean[l] = f.mean[l];
-    }
-    const size_t lds = (size_t)2 * 32 * b.ld * sizeof(float);
+    BntBwd b;
+    const size_t lds = bnt_bwd_plan(p, f, sh, ws, off_coef, b);
     static bool attr_set = false;
     rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(fpt_bwd_phase_kernel), attr_set);
     if (rc != AMPNET_OK) return rc;
-    hipLaunchKernelGGL(fpt_fold_kernel, dim3(1), dim3(256), 0, st, p, f, ws);
-    rc = check_launch("fpt_fold_kernel");
+    rc = fpt_fold_launch(p, f, ws, st);
     if (rc != AMPNET_OK) return rc;
     for (int l = L - 1; l >= -1; --l) {
         hipLaunchKernelGGL(fpt_bwd_phase_kernel, dim3(sh.grid), dim3(64), lds, st, p, b, l, points1, D1, points2, D2, n, s, idx, dist2, k, ws, dout,
@@ -518,9 +320,8 @@ extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const 
         rc = check_launch("fpt_bwd_phase_kernel");
         if (rc != AMPNET_OK) return rc;
         if (l < 0) break;
-        hipLaunchKernelGGL(fpt_bwd_finalize_kernel, dim3(cdiv(p.cout[l], 4)), dim3(256), 0, st, p.cout[l], b.parts, sh.grid, (float)sh.M, f.mean[l],
-                           f.var[l], grads_host[4 * l + 1], grads_host[4 * l + 2], grads_host[4 * l + 3], b.coef + p.fold_off[l]);
-        rc = check_launch("fpt_bwd_finalize_kernel");
+        rc = fpt_bwd_finalize_launch(p.cout[l], b.parts, sh.grid, sh.M, f.mean[l], f.var[l], grads_host[4 * l + 1], grads_host[4 * l + 2],
+                                     grads_host[4 * l + 3], b.coef + p.fold_off[l], st);
         if (rc != AMPNET_OK) return rc;
     }
     float *wpart = ws + sh.off_wpart;
@@ -530,28 +331,3 @@ extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const 
     }
     return fp_scatter_launch(b.dx0, D2, n_clouds, n, s, idx, dist2, k, dpoints2, st);
 }
-
-namespace ampnet {
-
-// bn_train.h: the kernels above that the train-mode set abstraction launches too
-int fpt_stats_finalize_launch(const FptStats &q, const float *parts, int n_parts, long long M, float *fold, hipStream_t st)
-{
-    hipLaunchKernelGGL(fpt_stats_finalize_kernel, dim3(cdiv(q.cout, 4)), dim3(256), 0, st, q, parts, n_parts, (float)M, fold);
-    return check_launch("fpt_stats_finalize_kernel");
-}
-
-int fpt_fold_launch(const MlpPlan &p, const MlpFold &f, float *fold, hipStream_t st)
-{
-    hipLaunchKernelGGL(fpt_fold_kernel, dim3(1), dim3(256), 0, st, p, f, fold);
-    return check_launch("fpt_fold_kernel");
-}
-
-int fpt_bwd_finalize_launch(int cout, const float *parts, int n_parts, long long M, const float *mean, const float *invstd, float *dbias,
-                            float *dgamma, float *dbeta, float *coef, hipStream_t st)
-{
-    hipLaunchKernelGGL(fpt_bwd_finalize_kernel, dim3(cdiv(cout, 4)), dim3(256), 0, st, cout, parts, n_parts, (float)M, mean, invstd, dbias, dgamma,
-                       dbeta, coef);
-    return check_launch("fpt_bwd_finalize_kernel");
-}
-
-}  // namespace ampnet

@@ -105,6 +105,54 @@ struct MlpToTile {
     __device__ static void done(float, float *, int, int) {}
 };
 
+// what mlp_accumulate takes as xr: the operand pointer of the lane of half h that supplies row `row` of x [.][ldx]
+template <int KORDER>
+__device__ __forceinline__ const float *mlp_operand(const float *x, int ldx, int row, int h)
+{
+    return x + row * ldx + (KORDER == K_PAIRS ? 1 : 4) * h;
+}
+
+// The raw accumulator outside the forward: acc = W x for NT column tiles from n0 on the 32 rows whose operand pointer is xr, k ascending in
+// blocks of 8 in the order KORDER names.  Every backward and train-mode kernel that has to find the forward's bits again (its ReLU mask, its
+// max, its statistics) runs this one loop; it is mlp_tiles' loop below, statement for statement, and the two must stay so.  (mlp_tiles does
+// not call it: hipcc lays the forward kernels' blocks out differently when the loop arrives through a call, and the forward stays as it
+// was tuned.)  w: weights [cout][ldw], k_valid = columns of w that exist (the rest of kp counts as zero); VEC: 16-byte aligned rows,
+// k_valid == kp.  Lane (r, h) ends with column n0 + 32 t + r of rows (i & 3) + 8 (i >> 2) + 4 h in acc[t][i].
+template <int NT, int KORDER, bool VEC>
+__device__ __forceinline__ void mlp_accumulate(f32x16 (&acc)[NT], const float *xr, const float *__restrict__ w, int ldw, int k_valid, int kp, int n0,
+                                               int r, int h)
+{
+    static_assert(!VEC || KORDER == K_QUADS, "only K_QUADS gives a lane four contiguous weights");
+    constexpr int KH = KORDER == K_PAIRS ? 1 : 4, KI = KORDER == K_PAIRS ? 2 : 1;      // k-step i of lane half h takes k = k0 + KH h + KI i
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    for (int k0 = 0; k0 < kp; k0 += 8) {
+        float av[4], bv[NT][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = xr[k0 + KI * i];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float *wr = w + (size_t)(n0 + 32 * t + r) * ldw + k0 + KH * h;
+            if (VEC) {
+                const float4 q = *reinterpret_cast<const float4 *>(wr);
+                bv[t][0] = q.x;
+                bv[t][1] = q.y;
+                bv[t][2] = q.z;
+                bv[t][3] = q.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bv[t][i] = k0 + KH * h + KI * i < k_valid ? wr[KI * i] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+}
+
 // NT column tiles of one layer over the R / 32 row tiles of the wave.  x: the wave's input tile [R][ldx]; w: weights [cout][ldw] (LDS or
 // global), k_valid = columns of w that exist (the rest of kp counts as zero); VEC: w is global, 16-byte aligned rows, k_valid == kp.
 template <int NT, int KORDER, bool VEC, class EPILOGUE>

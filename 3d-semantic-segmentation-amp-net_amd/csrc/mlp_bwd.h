@@ -1,6 +1,9 @@
 // mlp_bwd.h -- what the backwards of the two fused PointNet++ layers share (feature_propagation_bwd.hip, set_abstraction_bwd.hip; the
 // kernels and their launchers: mlp_bwd.hip): the split-K GEMM dW_l = dz_l^T x_l over rows kept in the workspace, its ordered reduce,
-// the finalize kernel that turns the workgroups' per-channel partial sums into dbeta, dgamma and dbias, and the chunk rule.
+// the finalize kernel that turns the workgroups' per-channel partial sums into dbeta, dgamma and dbias, the chunk rule, the common part of
+// the workspace layout, and the device code all four backwards (eval and train-mode) run on a wave's 32-row tile: the row stores and loads
+// between LDS and the workspace and dx = dz W (mlp_dgrad).  The raw accumulator they recompute is the forward's, fused_mlp.h's
+// mlp_accumulate, where the lane map and the two contraction orders are defined.
 #pragma once
 #include "fused_mlp.h"
 
@@ -31,11 +34,91 @@ int fpb_wgrad_launch(const float *dz, int cout, const float *xs, int cin, int ld
 int fpb_finalize_launch(const MlpPlan &p, const MlpFold &f, const FpBwdFin &g, const float *fold, const float *parts, int n_parts, int sum_c,
                         hipStream_t st);
 
+// The part of the workspace every backward lays out the same way (float offsets, each a multiple of 64): the workgroups' partial rows, per
+// layer its input rows x_l [M][ldxs_l] and dz_l [M][cout_l], the dx_0 rows the gather reads, and the split-K partials of dW.
+struct MlpBwdLayout {
+    int sum_c;                                                 // sum of cout_l
+    int cin[MLP_MAX_LAYERS], ldxs[MLP_MAX_LAYERS];             // ldxs: cin_l rounded up to 32 (zeros)
+    size_t off_parts, off_xs[MLP_MAX_LAYERS], off_dz[MLP_MAX_LAYERS], off_dx0, off_wpart, floats;
+};
+
+// Checks every cout (`what` opens the message) and fills lay from float offset `off` on: grid partial rows of 2 sum_c floats, M rows per
+// layer, dx0_cols columns of dx_0, `chunks` partials of the largest dW.
+int mlp_bwd_layout(const char *what, size_t off, int cin0, int dx0_cols, long long M, int grid, int chunks, const int *cout_host, int L,
+                   MlpBwdLayout &lay);
+
 // the wave's tile [.][ld] -> rows < rows of a global array with row stride ldg (columns past `valid` as zeros)
 __device__ __forceinline__ void fpb_store_rows(const float *tile, int ld, int valid, float *__restrict__ g, int ldg, int rows, int lane)
 {
     for (int t = 0; t < rows; ++t)
         for (int c = lane; c < ldg; c += 64) g[(size_t)t * ldg + c] = c < valid ? tile[t * ld + c] : 0.0f;
+}
+
+// rows < rows of a global array with row stride ldg -> the wave's tile, `width` columns (a multiple of 8, <= ldg); the rows past `rows` zero.
+// A lane reads the words fpb_store_rows made it write (column c belongs to lane c % 64 in both), so a wave may load what it stored itself
+// without a fence.
+__device__ __forceinline__ void fpb_load_rows(float *tile, int ld, int width, const float *g, int ldg, int rows, int lane)
+{
+    for (int t = 0; t < 32; ++t)
+        for (int c = lane; c < width; c += 64) tile[t * ld + c] = t < rows ? g[(size_t)t * ldg + c] : 0.0f;
+}
+
+// fpb_load_rows for rows another KERNEL stored: the elements spread over all 64 lanes (32 width is a multiple of 64)
+__device__ __forceinline__ void fpb_load_rows_flat(float *tile, int ld, int width, const float *__restrict__ g, int ldg, int rows, int lane)
+{
+    for (int e = lane; e < 32 * width; e += 64) {
+        const int t = e / width, c = e - t * width;
+        tile[t * ld + c] = t < rows ? g[(size_t)t * ldg + c] : 0.0f;
+    }
+}
+
+// dx = dz W for NT column tiles of the layer's INPUT from c0: dz [32][ldd] in LDS, w [cout][cin] global.  The forward's lane map with cin
+// and cout exchanged: lane (r, h) supplies row r of dz and column c0 + 32 t + r of W; o ascending in blocks of 8, k-step i < 4 of lane half
+// h takes o = o0 + 2 i + h.  Results go to tile `xo` (l >= 1) or, xo == nullptr (layer 0), the rows < rows leave the kernel: columns < D1
+// to dp1 [.][D1], columns [D1, cin) to dx0 [.][D2].  DROP_D1: nobody wants the first D1 columns and dp1 is null (set abstraction's three
+// coordinates); a flag and not a test of dp1, so that each caller keeps one condition per element, as its kernel was tuned.
+template <int NT, bool DROP_D1 = false>
+__device__ __forceinline__ void mlp_dgrad(const float *d, int ldd, const float *__restrict__ w, int cin, int cout, int c0, float *xo, int ldxo,
+                                          float *__restrict__ dp1, int D1, float *__restrict__ dx0, int D2, int rows, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    const float *dr = d + r * ldd + h;
+    for (int o0 = 0; o0 < cout; o0 += 8) {
+        float av[4], bv[NT][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = dr[o0 + 2 * i];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int c = c0 + 32 * t + r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bv[t][i] = c < cin ? w[(size_t)(o0 + 2 * i + h) * cin + c] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int c = c0 + 32 * t + r;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            if (xo) {
+                if (c < cin) xo[row * ldxo + c] = acc[t][i];
+            } else if (DROP_D1) {
+                if (row < rows && c >= D1 && c < cin) dx0[(size_t)row * D2 + c - D1] = acc[t][i];
+            } else if (row < rows) {
+                if (c < D1) dp1[(size_t)row * D1 + c] = acc[t][i];
+                else if (c < cin) dx0[(size_t)row * D2 + c - D1] = acc[t][i];
+            }
+        }
+    }
 }
 
 }  // namespace ampnet

@@ -78,6 +78,36 @@ __global__ __launch_bounds__(256) void fp_bwd_finalize_kernel(MlpPlan p, MlpFold
     g.dbias[l][c] = fold[p.fold_off[l] + c] * dbeta;
 }
 
+int mlp_bwd_layout(const char *what, size_t off, int cin0, int dx0_cols, long long M, int grid, int chunks, const int *cout_host, int L,
+                   MlpBwdLayout &lay)
+{
+    lay = {};
+    size_t wmax = 0;
+    for (int l = 0; l < L; ++l) {
+        const int cout = cout_host[l];
+        AMPNET_REQUIRE(cout >= 32 && cout <= MLP_MAX_COUT && cout % 32 == 0, "%s: layer %d has cout=%d, must be a multiple of 32 in [32, %d]", what,
+                       l, cout, MLP_MAX_COUT);
+        lay.cin[l] = l ? cout_host[l - 1] : cin0;
+        lay.ldxs[l] = (lay.cin[l] + 31) / 32 * 32;
+        lay.sum_c += cout;
+        if ((size_t)cout * lay.ldxs[l] > wmax) wmax = (size_t)cout * lay.ldxs[l];
+    }
+    lay.off_parts = off;
+    off += align_up((size_t)grid * 2 * lay.sum_c, 64);
+    for (int l = 0; l < L; ++l) {
+        lay.off_xs[l] = off;
+        off += align_up((size_t)M * lay.ldxs[l], 64);
+        lay.off_dz[l] = off;
+        off += align_up((size_t)M * cout_host[l], 64);
+    }
+    lay.off_dx0 = off;
+    off += align_up((size_t)M * dx0_cols, 64);
+    lay.off_wpart = off;
+    off += align_up((size_t)chunks * wmax, 64);
+    lay.floats = off;
+    return AMPNET_OK;
+}
+
 int fpb_wgrad_launch(const float *dz, int cout, const float *xs, int cin, int ldxs, long long M, int chunk_rows, int chunks, float *wpart,
                      float *dW, hipStream_t st)
 {

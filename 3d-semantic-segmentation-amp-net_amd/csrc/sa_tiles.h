@@ -1,6 +1,7 @@
-// sa_tiles.h -- what the two set-abstraction backwards share (set_abstraction_bwd.hip: running statistics frozen;
-// set_abstraction_train.hip: batch statistics): the raw accumulators of a layer in the forward's contraction order, dx = dz W in its lane
-// map, the workspace layout, and the launchers of the forward's kernel and of the dfeats gather.
+// sa_tiles.h -- what the set-abstraction kernels share (set_abstraction.hip: the eval forward; set_abstraction_bwd.hip: the backward with the
+// running statistics frozen; set_abstraction_train.hip: batch statistics): the gather of a group's rows into a wave's LDS tile, the
+// backwards' launch sizes and workspace layout, and the launchers of the forward's kernel and of the dfeats gather.  The device code of a
+// tile (the raw accumulator, dx = dz W, the row stores and loads) is fused_mlp.h's and mlp_bwd.h's.
 #pragma once
 #include "mlp_bwd.h"
 
@@ -8,83 +9,53 @@ namespace ampnet {
 
 constexpr int SAB_MAX_GRID = 2048;        // workgroups (= rows of the partials array) of the one-wave-per-group kernels
 
-// the accumulators of NT column tiles from n0 on the 32 rows whose operand pointer is xr = x + (m0 + r) ldx + h: the forward's
-// mlp_tiles<NT, K_PAIRS, false> on weights read from global memory
-template <int NT>
-__device__ __forceinline__ void sab_accumulate(f32x16 (&acc)[NT], const float *xr, const float *__restrict__ w, int cin, int kp, int n0, int r,
-                                               int h)
+// The forward's gather of a WHOLE group g: the R rows [xyz[idx_t] - xyz[centre] (3), feats[idx_t] (D)] of group_idx[g][:] into `tile`
+// [R][ldt], kp0 columns each (zeros past cin0).  Lane t holds the point of row t; the rows past nsample REPEAT row 0, which changes no max.
+// Element e = (row, column) with the columns fastest, so a row's features load contiguously.
+__device__ __forceinline__ void sa_gather_group(float *tile, int ldt, int R, int kp0, int cin0, const float *__restrict__ xyz, int n, int ld,
+                                                const int32_t *__restrict__ centres, int s, const int32_t *__restrict__ group_idx, int nsample,
+                                                const float *__restrict__ feats, int D, int g, int lane)
 {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    for (int k0 = 0; k0 < kp; k0 += 8) {
-        float av[4], bv[NT][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = xr[k0 + 2 * i];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const float *wr = w + (size_t)(n0 + 32 * t + r) * cin + k0 + h;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[t][i] = k0 + h + 2 * i < cin ? wr[2 * i] : 0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
+    const int cloud_i = g / s;
+    const float *cloud = xyz + (size_t)cloud_i * n * ld;
+    const float *fcloud = feats ? feats + (size_t)cloud_i * n * D : nullptr;
+    const int cidx = min(max(centres[g], 0), n - 1);
+    const float cx = cloud[(size_t)cidx * ld], cy = cloud[(size_t)cidx * ld + 1], cz = cloud[(size_t)cidx * ld + 2];
+    const int my_idx = min(max(group_idx[(size_t)g * nsample + (lane < nsample ? lane : 0)], 0), n - 1);
+    for (int e = lane; e < R * kp0; e += 64) {
+        const int t = e / kp0, c = e - t * kp0;
+        const int j = __shfl(my_idx, t);
+        float v = 0.0f;
+        if (c < 3) v = cloud[(size_t)j * ld + c] - (c == 0 ? cx : c == 1 ? cy : cz);
+        else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
+        tile[t * ldt + c] = v;
     }
 }
 
-// dx = dz W for NT column tiles of the layer's INPUT from c0 on the 32 rows of d [32][ldd] (fpb_dgrad's lane map and order: o ascending
-// in blocks of 8, k-step i of lane half h takes o = o0 + 2 i + h).  Results go to tile `xo` (l >= 1) or, xo == nullptr, columns
-// [3, cin) of the rows < rows to dx0 [.][D] (layer 0).
-template <int NT>
-__device__ __forceinline__ void sab_dgrad(const float *d, int ldd, const float *__restrict__ w, int cin, int cout, int c0, float *xo, int ldxo,
-                                          float *__restrict__ dx0, int D, int rows, int lane)
+// The 32-row-tile variant: rows m0 .. m0 + 31 of a group (group_g: its nsample indices; cx, cy, cz: its centre) into `tile` [32][ld].
+// Unlike sa_gather_group it ZEROES the rows past `rows` instead of repeating row 0: its callers sum over the rows they store.
+__device__ __forceinline__ void sat_gather_rows(float *tile, int ld, int kp0, int cin0, const float *__restrict__ cloud, int ldc,
+                                                const float *__restrict__ fcloud, int D, int n, const int32_t *__restrict__ group_g, float cx,
+                                                float cy, float cz, int m0, int rows, int lane)
 {
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    const float *dr = d + r * ldd + h;
-    for (int o0 = 0; o0 < cout; o0 += 8) {
-        float av[4], bv[NT][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = dr[o0 + 2 * i];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int c = c0 + 32 * t + r;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[t][i] = c < cin ? w[(size_t)(o0 + 2 * i + h) * cin + c] : 0.0f;
+    const int my_idx = min(max(group_g[(lane & 31) < rows ? m0 + (lane & 31) : 0], 0), n - 1);
+    for (int e = lane; e < 32 * kp0; e += 64) {                // (32 kp0 is a multiple of 64: every lane makes the same trips)
+        const int t = e / kp0, c = e - t * kp0;
+        const int j = __shfl(my_idx, t);
+        float v = 0.0f;
+        if (t < rows) {
+            if (c < 3) v = cloud[(size_t)j * ldc + c] - (c == 0 ? cx : c == 1 ? cy : cz);
+            else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[t][i], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = c0 + 32 * t + r;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (xo) {
-                if (c < cin) xo[row * ldxo + c] = acc[t][i];
-            } else if (row < rows && c >= 3 && c < cin) {
-                dx0[(size_t)row * D + c - 3] = acc[t][i];
-            }
-        }
+        tile[t * ld + c] = v;
     }
 }
 
-// what both entry points derive from the shape: the launch sizes, the LDS tiles and the workspace layout (float offsets, multiples of 64)
-struct SaBwdShape {
+// what both entry points derive from the shape: the launch sizes, the LDS tiles and the workspace layout
+struct SaBwdShape : MlpBwdLayout {
     long long M;
-    int R, n_groups, grid, chunk_rows, chunks, sum_c, lds_floats;
-    int cin[MLP_MAX_LAYERS], ldxs[MLP_MAX_LAYERS], off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];
-    size_t off_parts, off_xs[MLP_MAX_LAYERS], off_dz[MLP_MAX_LAYERS], off_dx0, off_wpart, floats;
+    int R, n_groups, grid, chunk_rows, chunks, lds_floats;
+    int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];
 };
 
 // checks the shape against the forward's limits and the LDS limit of sa_backward_kernel (`what` opens every message) and fills sh

@@ -37,22 +37,7 @@ __global__ __launch_bounds__(256) void sa_forward_kernel(MlpPlan p, const float 
     __syncthreads();
     const int cin0 = p.cin[0], kp0 = p.kp[0], cout_last = p.cout[p.L - 1];
     for (int g = blockIdx.x * p.nw + wave; g < n_groups; g += gridDim.x * p.nw) {
-        const int cloud_i = g / s;
-        const float *cloud = xyz + (size_t)cloud_i * n * ld;
-        const float *fcloud = feats ? feats + (size_t)cloud_i * n * D : nullptr;
-        const int cidx = min(max(centres[g], 0), n - 1);
-        const float cx = cloud[(size_t)cidx * ld], cy = cloud[(size_t)cidx * ld + 1], cz = cloud[(size_t)cidx * ld + 2];
-        // lane t holds the point of row t; rows past nsample repeat row 0
-        const int my_idx = min(max(group_idx[(size_t)g * nsample + (lane < nsample ? lane : 0)], 0), n - 1);
-        // gather the rows into tile A: element e = (row, column) with the columns fastest, so a row's features load contiguously
-        for (int e = lane; e < p.R * kp0; e += 64) {
-            const int t = e / kp0, c = e - t * kp0;
-            const int j = __shfl(my_idx, t);
-            float v = 0.0f;
-            if (c < 3) v = cloud[(size_t)j * ld + c] - (c == 0 ? cx : c == 1 ? cy : cz);
-            else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
-            m.tile_a[t * p.ld_a + c] = v;
-        }
+        sa_gather_group(m.tile_a, p.ld_a, p.R, kp0, cin0, xyz, n, ld, centres, s, group_idx, nsample, feats, D, g, lane);
         wave_lds_sync();
         mlp_run<K_PAIRS>(p, p.R, m.s_w, m.tile_a, m.tile_b, fold, SaMax{}, out + (size_t)g * cout_last, lane);
         // the next centre's gather overwrites tile A: every read of this centre is done (the last layer's results are in registers)

@@ -53,7 +53,7 @@ __device__ __forceinline__ void sab_hidden(const float *x, int ldx, const float 
     }
     for (int m0 = 0; m0 < R; m0 += 32) {
         f32x16 acc[NT];
-        sab_accumulate<NT>(acc, x + (m0 + r) * ldx + h, w, cin, kp, n0, r, h);
+        mlp_accumulate<NT, K_PAIRS, false>(acc, mlp_operand<K_PAIRS>(x, ldx, m0 + r, h), w, cin, cin, kp, n0, r, h);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int col = n0 + 32 * t + r;
@@ -102,7 +102,7 @@ __device__ __forceinline__ void sab_last(const float *x, int ldx, const float *_
     }
     for (int m0 = 0; m0 < R; m0 += 32) {
         f32x16 acc[NT];
-        sab_accumulate<NT>(acc, x + (m0 + r) * ldx + h, w, cin, kp, n0, r, h);
+        mlp_accumulate<NT, K_PAIRS, false>(acc, mlp_operand<K_PAIRS>(x, ldx, m0 + r, h), w, cin, cin, kp, n0, r, h);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int col = n0 + 32 * t + r;
@@ -158,22 +158,8 @@ __global__ __launch_bounds__(64) void sa_backward_kernel(MlpPlan p, SaBwdPlan b,
     if (lane < 32)
         for (int c = lane; c < b.sum_c; c += 32) part_b[c] = part_g[c] = 0.0f;       // channel c belongs to lane c % 32, here and below
     for (int g = blockIdx.x; g < n_groups; g += gridDim.x) {
-        const int cloud_i = g / s;
-        const float *cloud = xyz + (size_t)cloud_i * n * ld;
-        const float *fcloud = feats ? feats + (size_t)cloud_i * n * D : nullptr;
-        const int cidx = min(max(centres[g], 0), n - 1);
-        const float cx = cloud[(size_t)cidx * ld], cy = cloud[(size_t)cidx * ld + 1], cz = cloud[(size_t)cidx * ld + 2];
-        // the forward's gather: lane t holds the point of row t, rows past nsample repeat row 0
-        const int my_idx = min(max(group_idx[(size_t)g * nsample + (lane < nsample ? lane : 0)], 0), n - 1);
         float *x0 = s_mem + b.off_x[0];
-        for (int e = lane; e < R * kp0; e += 64) {
-            const int t = e / kp0, c = e - t * kp0;
-            const int j = __shfl(my_idx, t);
-            float v = 0.0f;
-            if (c < 3) v = cloud[(size_t)j * ld + c] - (c == 0 ? cx : c == 1 ? cy : cz);
-            else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
-            x0[t * b.ld_x[0] + c] = v;
-        }
+        sa_gather_group(x0, b.ld_x[0], R, kp0, cin0, xyz, n, ld, centres, s, group_idx, nsample, feats, D, g, lane);
         wave_lds_sync();
         const size_t grow = (size_t)g * nsample;
         fpb_store_rows(x0, b.ld_x[0], kp0, b.xs[0] + grow * b.ldxs[0], b.ldxs[0], nsample, lane);
@@ -209,8 +195,8 @@ __global__ __launch_bounds__(64) void sa_backward_kernel(MlpPlan p, SaBwdPlan b,
                 float *dx0 = b.dx0 + (grow + m0) * D;
                 const float *dm = d + m0 * ldd;
                 int c0 = 0;
-                for (; c0 + 128 <= cin; c0 += 128) sab_dgrad<4>(dm, ldd, p.w[l], cin, cout, c0, xo, ldx, dx0, D, nsample - m0, lane);
-                for (; c0 < cin; c0 += 32) sab_dgrad<1>(dm, ldd, p.w[l], cin, cout, c0, xo, ldx, dx0, D, nsample - m0, lane);
+                for (; c0 + 128 <= cin; c0 += 128) mlp_dgrad<4, true>(dm, ldd, p.w[l], cin, cout, c0, xo, ldx, nullptr, 3, dx0, D, nsample - m0, lane);
+                for (; c0 < cin; c0 += 32) mlp_dgrad<1, true>(dm, ldd, p.w[l], cin, cout, c0, xo, ldx, nullptr, 3, dx0, D, nsample - m0, lane);
             }
             wave_lds_sync();
         }
@@ -263,16 +249,9 @@ int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const i
     sh.M = (long long)sh.n_groups * nsample;
     sh.grid = sh.n_groups < SAB_MAX_GRID ? sh.n_groups : SAB_MAX_GRID;
     fpb_chunk_rule(sh.M, sh.chunk_rows, sh.chunks);
-    size_t off = align_up((size_t)AMPNET_SA_WORKSPACE_BYTES / sizeof(float), 64), wmax = 0;
-    for (int l = 0; l < L; ++l) {
-        const int cout = cout_host[l];
-        AMPNET_REQUIRE(cout >= 32 && cout <= AMPNET_SA_MAX_COUT && cout % 32 == 0, "%s: layer %d has cout=%d, must be a multiple of 32 in [32, %d]",
-                       what, l, cout, AMPNET_SA_MAX_COUT);
-        sh.cin[l] = l ? cout_host[l - 1] : 3 + D;
-        sh.ldxs[l] = (sh.cin[l] + 31) / 32 * 32;
-        sh.sum_c += cout;
-        if ((size_t)cout * sh.ldxs[l] > wmax) wmax = (size_t)cout * sh.ldxs[l];
-    }
+    const int rc = mlp_bwd_layout(what, align_up((size_t)AMPNET_SA_WORKSPACE_BYTES / sizeof(float), 64), 3 + D, D, sh.M, sh.grid, sh.chunks, cout_host,
+                                  L, sh);
+    if (rc != AMPNET_OK) return rc;
     // the tiles X_0 .. X_L of R rows
     for (int l = 0; l <= L; ++l) {
         sh.ld_x[l] = (l ? cout_host[l - 1] : (3 + D + 7) / 8 * 8) + 1;
@@ -282,19 +261,6 @@ int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const i
     AMPNET_REQUIRE((size_t)sh.lds_floats * sizeof(float) <= (size_t)MLP_LDS_BYTES,
                    "%s: a wave's %d tiles of %d rows (%zu bytes) exceed the LDS (%d bytes); at nsample <= 32 every shape fits", what, L + 1, sh.R,
                    (size_t)sh.lds_floats * sizeof(float), MLP_LDS_BYTES);
-    sh.off_parts = off;
-    off += align_up((size_t)sh.grid * 2 * sh.sum_c, 64);
-    for (int l = 0; l < L; ++l) {
-        sh.off_xs[l] = off;
-        off += align_up((size_t)sh.M * sh.ldxs[l], 64);
-        sh.off_dz[l] = off;
-        off += align_up((size_t)sh.M * cout_host[l], 64);
-    }
-    sh.off_dx0 = off;
-    off += align_up((size_t)sh.M * D, 64);
-    sh.off_wpart = off;
-    off += align_up((size_t)sh.chunks * wmax, 64);
-    sh.floats = off;
     return AMPNET_OK;
 }
 

@@ -9,11 +9,11 @@
 //   sat_stats_kernel (pass l)   The forward's workgroup (its plan: up to four waves that share the staged weights of layers < l); a wave owns
 //       a group at a time.  It gathers the group's R rows as the forward does, runs layers < l with the forward's own code
 //       (mlp_dispatch<K_PAIRS>, reading the scale and shift that the earlier passes' finalizes wrote), forms layer l's raw accumulators
-//       a = W x in the forward's contraction order (sab_accumulate) and, per column and 32-row tile, the count, mean and sum (a - mean)^2
+//       a = W x in the forward's contraction order (mlp_accumulate) and, per column and 32-row tile, the count, mean and sum (a - mean)^2
 //       over the rows t < nsample.  The groups r, r + P, .. (P = min(groups, 1024)) are merged in ascending order, a group's tiles
 //       ascending, into row r of a partials array with Chan's formula; a row belongs to one wave, so every word of it is read and written
 //       by the same lane only, and the order does not depend on the plan.
-//   fpt_stats_finalize_kernel   (feature_propagation_train.hip) merges the rows and writes the fold, save_mean, save_invstd and the
+//   fpt_stats_finalize_kernel   (bn_train.hip) merges the rows and writes the fold, save_mean, save_invstd and the
 //       running-statistics update.
 //   sa_forward_kernel           the eval forward's kernel on that fold (sa_forward_launch): eval and train share the hot kernel, and `out`
 //       is the max of what the statistics were taken from, bit for bit.
@@ -30,13 +30,15 @@
 //   sat_bwd_phase_kernel (phase l = L-2 .. -1), one wave per workgroup, a 32-row tile (g, m) at a time:
 //       part A for layer j = l+1: x_j from the workspace into T0, a_j recomputed, dy_j from the workspace (j = L-1: dout at the row arg
 //       names when its y > 0), dz_j = scale fma(-(a - mu), dgamma invstd / M, dy - dbeta / M) for EVERY row t < nsample (zero for the padding
-//       rows) into T1 and the workspace;  dx_l = dz_j W_j (sab_dgrad) over T0;  l = -1 ends here, dx_0's feature columns going to the
+//       rows) into T1 and the workspace;  dx_l = dz_j W_j (mlp_dgrad) over T0;  l = -1 ends here, dx_0's feature columns going to the
 //       gather's rows (skipped when nobody wants dfeats).
 //       part B for layer l:  x_l from the workspace into T1, a_l recomputed, dy_l = dx_l [fma(a, scale, shift) > 0] stored to the workspace,
 //       sum dy and sum dy a added into the workgroup's own partial row.
-//   fpt_bwd_finalize_kernel     (feature_propagation_train.hip) after every phase l >= 0.
+//   fpt_bwd_finalize_kernel     (bn_train.hip) after every phase l >= 0.
 //   fpb_wgrad_launch, sa_dfeats_launch   dW_l = dz_l^T x_l and dfeats, exactly the eval backward's, on the eval backward's workspace layout.
 //   A phase holds two 32-row tiles of the widest layer input (at most 82 KB) whatever nsample is.
+//   The statistics, part A and part B of a tile are bn_train.h's (bnt_tile_stats, bnt_form_dz, bnt_form_dy), shared with feature propagation;
+//   this file keeps what is set abstraction's own: the gathers, the tiling, the max of the last layer (sat_last).
 #include "bn_train.h"
 #include "sa_tiles.h"
 
@@ -45,77 +47,13 @@ namespace ampnet {
 constexpr long long SAT_MAX_ROWS = AMPNET_SA_TRAIN_MAX_ROWS;    // the merges carry row counts as floats: exact up to here, larger M is refused
 constexpr int SAT_MAX_PARTS = 1024;                            // partial rows of the statistics passes
 
-// rows m0 .. m0 + 31 of group g into `tile` [32][ld], kp0 columns each (zeros past cin0): the forward's gather; the rows past `rows` are zero
-__device__ __forceinline__ void sat_gather_rows(float *tile, int ld, int kp0, int cin0, const float *__restrict__ cloud, int ldc,
-                                                const float *__restrict__ fcloud, int D, int n, const int32_t *__restrict__ group_g, float cx,
-                                                float cy, float cz, int m0, int rows, int lane)
-{
-    const int my_idx = min(max(group_g[(lane & 31) < rows ? m0 + (lane & 31) : 0], 0), n - 1);
-    for (int e = lane; e < 32 * kp0; e += 64) {                // (32 kp0 is a multiple of 64: every lane makes the same trips)
-        const int t = e / kp0, c = e - t * kp0;
-        const int j = __shfl(my_idx, t);
-        float v = 0.0f;
-        if (t < rows) {
-            if (c < 3) v = cloud[(size_t)j * ldc + c] - (c == 0 ? cx : c == 1 ? cy : cz);
-            else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
-        }
-        tile[t * ld + c] = v;
-    }
-}
-
-// rows < rows of a global array with row stride ldg -> the wave's tile, `width` columns (a multiple of 8, <= ldg); the rows past `rows` zero.
-// A lane reads the words fpb_store_rows made it write, so a wave may load what it stored itself.
-__device__ __forceinline__ void sat_load_rows(float *tile, int ld, int width, const float *g, int ldg, int rows, int lane)
-{
-    for (int t = 0; t < 32; ++t)
-        for (int c = lane; c < width; c += 64) tile[t * ld + c] = t < rows ? g[(size_t)t * ldg + c] : 0.0f;
-}
-
-// sat_load_rows for rows another KERNEL stored: the elements spread over all 64 lanes (32 width is a multiple of 64)
-__device__ __forceinline__ void sat_load_rows_flat(float *tile, int ld, int width, const float *__restrict__ g, int ldg, int rows, int lane)
-{
-    for (int e = lane; e < 32 * width; e += 64) {
-        const int t = e / width, c = e - t * width;
-        tile[t * ld + c] = t < rows ? g[(size_t)t * ldg + c] : 0.0f;
-    }
-}
-
-// the statistics of NT column tiles of layer l from n0 over the rows t < nsample of the wave's group, merged into the wave's partial row
+// the statistics of NT column tiles of layer l from n0 over the rows t < nsample of the wave's group, a 32-row tile at a time
 template <int NT>
-__device__ __forceinline__ void sat_tile_stats(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int n0, int R, int nsample,
-                                               float *part_n, float *part_mean, float *part_m2, int lane)
+__device__ __forceinline__ void sat_group_stats(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int n0, int R, int nsample,
+                                                float *part_n, float *part_mean, float *part_m2, int lane)
 {
-    const int r = lane & 31, h = lane >> 5;
-    for (int m0 = 0; m0 < R; m0 += 32) {
-        const int rows = min(32, nsample - m0);   // >= 1: R = 64 only when nsample > 32
-        f32x16 acc[NT];
-        sab_accumulate<NT>(acc, x + (m0 + r) * ldx + h, w, cin, kp, n0, r, h);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int col = n0 + 32 * t + r;
-            float sum = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if ((i & 3) + 8 * (i >> 2) + 4 * h < rows) sum += acc[t][i];
-            sum += __shfl_xor(sum, 32);
-            const float mean = sum / (float)rows;
-            float q = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if ((i & 3) + 8 * (i >> 2) + 4 * h < rows) {
-                    const float d = acc[t][i] - mean;
-                    q = fmaf(d, d, q);
-                }
-            q += __shfl_xor(q, 32);
-            if (h == 0) {                         // (this lane alone ever touches these three words of the wave's partial row)
-                float nA = part_n[col], meanA = part_mean[col], m2A = part_m2[col];
-                fpt_chan(nA, meanA, m2A, (float)rows, mean, q);
-                part_n[col] = nA;
-                part_mean[col] = meanA;
-                part_m2[col] = m2A;
-            }
-        }
-    }
+    for (int m0 = 0; m0 < R; m0 += 32)            // (rows >= 1: R = 64 only when nsample > 32)
+        bnt_tile_stats<NT, K_PAIRS, false>(x, ldx, m0, w, cin, kp, n0, min(32, nsample - m0), part_n, part_mean, part_m2, lane);
 }
 
 // parts [n_parts][3 cout_l]: per partial row the count, mean and sum of squared deviations of every channel of layer l.  Row r takes the
@@ -138,21 +76,8 @@ __global__ __launch_bounds__(256) void sat_stats_kernel(MlpPlan p, int l, const 
         if (lane < 32)
             for (int c = lane; c < cout; c += 32) part_n[c] = part_mean[c] = part_m2[c] = 0.0f;  // channel c belongs to lane c % 32
         for (int g = row; g < n_groups; g += n_parts) {
-            const int cloud_i = g / s;
-            const float *cloud = xyz + (size_t)cloud_i * n * ld;
-            const float *fcloud = feats ? feats + (size_t)cloud_i * n * D : nullptr;
-            const int cidx = min(max(centres[g], 0), n - 1);
-            const float cx = cloud[(size_t)cidx * ld], cy = cloud[(size_t)cidx * ld + 1], cz = cloud[(size_t)cidx * ld + 2];
-            // the forward's gather: lane t holds the point of row t, rows past nsample repeat row 0 (and enter no statistic)
-            const int my_idx = min(max(group_idx[(size_t)g * nsample + (lane < nsample ? lane : 0)], 0), n - 1);
-            for (int e = lane; e < p.R * kp0; e += 64) {
-                const int t = e / kp0, c = e - t * kp0;
-                const int j = __shfl(my_idx, t);
-                float v = 0.0f;
-                if (c < 3) v = cloud[(size_t)j * ld + c] - (c == 0 ? cx : c == 1 ? cy : cz);
-                else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
-                m.tile_a[t * p.ld_a + c] = v;
-            }
+            sa_gather_group(m.tile_a, p.ld_a, p.R, kp0, cin0, xyz, n, ld, centres, s, group_idx, nsample, feats, D, g, lane);
+            // (the rows past nsample repeat row 0 and enter no statistic)
             wave_lds_sync();
             for (int j = 0; j < l; ++j) {
                 mlp_dispatch<K_PAIRS>(p, j, p.R, m.s_w, tile[j & 1], ldt[j & 1], fold, MlpToTile{tile[(j + 1) & 1], ldt[(j + 1) & 1]}, nullptr, lane);
@@ -161,20 +86,12 @@ __global__ __launch_bounds__(256) void sat_stats_kernel(MlpPlan p, int l, const 
             const float *x = tile[l & 1];
             const int ldx = ldt[l & 1];
             int n0 = 0;
-            for (; n0 + 128 <= cout; n0 += 128) sat_tile_stats<4>(x, ldx, p.w[l], cin, kp, n0, p.R, nsample, part_n, part_mean, part_m2, lane);
-            for (; n0 < cout; n0 += 32) sat_tile_stats<1>(x, ldx, p.w[l], cin, kp, n0, p.R, nsample, part_n, part_mean, part_m2, lane);
+            for (; n0 + 128 <= cout; n0 += 128) sat_group_stats<4>(x, ldx, p.w[l], cin, kp, n0, p.R, nsample, part_n, part_mean, part_m2, lane);
+            for (; n0 < cout; n0 += 32) sat_group_stats<1>(x, ldx, p.w[l], cin, kp, n0, p.R, nsample, part_n, part_mean, part_m2, lane);
             wave_lds_sync();                      // the next group's gather overwrites tile A
         }
     }
 }
-
-struct SatBwd {
-    int ld;                                                    // odd row stride of both LDS tiles
-    int ldxs[MLP_MAX_LAYERS];                                  // row stride of x_l in the workspace: cin_l rounded up to 32 (zeros)
-    float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts, *coef;     // coef: per layer (fold_off) dbeta / M, then dgamma invstd / M
-    const float *mean[MLP_MAX_LAYERS];
-    int32_t *arg;                                              // [n_groups][cout_{L-1}]: the row the max selected
-};
 
 // The last layer of one group: x_{L-1} of its row tiles in T0 (rows 0 .. 31) and T1 (32 .. 63).  Per column the largest relu(y), the lowest
 // row t < nsample that attains it and its a; the group's one term of sum dy and sum dy a; arg to the workspace and to arg_out.
@@ -198,7 +115,7 @@ __device__ __forceinline__ void sat_last(const float *t0, const float *t1, int l
     for (int m0 = 0; m0 < R; m0 += 32) {
         const float *x = m0 ? t1 : t0;
         f32x16 acc[NT];
-        sab_accumulate<NT>(acc, x + r * ldx + h, w, cin, kp, n0, r, h);
+        mlp_accumulate<NT, K_PAIRS, false>(acc, mlp_operand<K_PAIRS>(x, ldx, r, h), w, cin, cin, kp, n0, r, h);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -232,7 +149,7 @@ __device__ __forceinline__ void sat_last(const float *t0, const float *t1, int l
     }
 }
 
-__global__ __launch_bounds__(64) void sat_bwd_last_kernel(MlpPlan p, SatBwd b, const float *__restrict__ xyz, int n, int ldc,
+__global__ __launch_bounds__(64) void sat_bwd_last_kernel(MlpPlan p, BntBwd b, const float *__restrict__ xyz, int n, int ldc,
                                                          const int32_t *__restrict__ centres, int s, const int32_t *__restrict__ group_idx,
                                                          int nsample, const float *__restrict__ feats, int D, const float *__restrict__ fold,
                                                          const float *__restrict__ dout, int n_groups, int32_t *__restrict__ arg_out)
@@ -267,7 +184,7 @@ __global__ __launch_bounds__(64) void sat_bwd_last_kernel(MlpPlan p, SatBwd b, c
             wave_lds_sync();                      // the next tile's gather overwrites T0
         }
         for (int m0 = 0; m0 < R; m0 += 32)
-            sat_load_rows(T[m0 >> 5], ld, p.kp[l], b.xs[l] + (grow + m0) * b.ldxs[l], b.ldxs[l], min(32, nsample - m0), lane);
+            fpb_load_rows(T[m0 >> 5], ld, p.kp[l], b.xs[l] + (grow + m0) * b.ldxs[l], b.ldxs[l], min(32, nsample - m0), lane);
         wave_lds_sync();
         const float *dout_g = dout + (size_t)g * cout;
         int32_t *arg_ws = b.arg + (size_t)g * cout, *arg_g = arg_out ? arg_out + (size_t)g * cout : nullptr;
@@ -280,77 +197,9 @@ __global__ __launch_bounds__(64) void sat_bwd_last_kernel(MlpPlan p, SatBwd b, c
     }
 }
 
-// part A: a of layer j recomputed on tile x; dy of the wave's rows from dz_ws, or (arg_g != nullptr, the last layer) dout_g at the row arg_g
-// names when its y > 0; dz into tile d and into dz_ws.  row0: the tile's first row inside its group.
-template <int NT>
-__device__ __forceinline__ void sat_form_dz(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
-                                            const float *__restrict__ scale, const float *__restrict__ shift, const float *__restrict__ mean,
-                                            const float *__restrict__ c1, const float *__restrict__ c2, float *d, int ldd, int rows, int row0,
-                                            const int32_t *__restrict__ arg_g, const float *__restrict__ dout_g, float *dz_ws, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-    sab_accumulate<NT>(acc, x + r * ldx + h, w, cin, kp, n0, r, h);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = n0 + 32 * t + r;
-        const float sc = scale[col], sh = shift[col], mu = mean[col], k1 = c1[col], k2 = c2[col];
-        const int arow = arg_g ? arg_g[col] - row0 : -1;
-        const float dsel = arg_g ? dout_g[col] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            float dzv = 0.0f;
-            if (row < rows) {
-                const float a = acc[t][i];
-                float dy;
-                if (arg_g) dy = row == arow && fmaf(a, sc, sh) > 0.0f ? dsel : 0.0f;
-                else dy = dz_ws[(size_t)row * cout + col];
-                dzv = sc * fmaf(-(a - mu), k2, dy - k1);
-                dz_ws[(size_t)row * cout + col] = dzv;
-            }
-            d[row * ldd + col] = dzv;
-        }
-    }
-}
-
-// part B: a of layer l recomputed on tile x; dy = dx [y > 0] (dx in tile d) to dz_ws and the sums
-template <int NT>
-__device__ __forceinline__ void sat_form_dy(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
-                                            const float *__restrict__ scale, const float *__restrict__ shift, const float *d, int ldd, int rows,
-                                            float *dz_ws, float *part_b, float *part_g, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-    sab_accumulate<NT>(acc, x + r * ldx + h, w, cin, kp, n0, r, h);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = n0 + 32 * t + r;
-        const float sc = scale[col], sh = shift[col];
-        float sb = 0.0f, sg = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            const float a = acc[t][i];
-            float dy = 0.0f;
-            if (row < rows) {
-                dy = fmaf(a, sc, sh) > 0.0f ? d[row * ldd + col] : 0.0f;
-                dz_ws[(size_t)row * cout + col] = dy;
-            }
-            sb += dy;
-            sg = fmaf(dy, a, sg);
-        }
-        const float ob = __shfl_down(sb, 32), og = __shfl_down(sg, 32);
-        if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
-            part_b[col] += sb + ob;
-            part_g[col] += sg + og;
-        }
-    }
-}
-
 // Two column tiles per step, not four, and two waves per SIMD asked of the compiler (256 registers, two of them spilled): the phases wait on
 // the workspace, not on the MFMAs, and at sa1's shape a second wave per SIMD takes the backward from 3.18 ms to 2.12 ms.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sat_bwd_phase_kernel(MlpPlan p, SatBwd b, int l, int nsample, int D, const float *__restrict__ fold,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sat_bwd_phase_kernel(MlpPlan p, BntBwd b, int l, int nsample, int D, const float *__restrict__ fold,
                                                           const float *__restrict__ dout, int n_tiles, int want_dx0)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -370,7 +219,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sa
         const size_t grow = (size_t)g * nsample + m0;
         {
             const int j = l + 1, cin = p.cin[j], cout = p.cout[j], kp = p.kp[j];
-            sat_load_rows_flat(T[0], ld, kp, b.xs[j] + grow * b.ldxs[j], b.ldxs[j], rows, lane);
+            fpb_load_rows_flat(T[0], ld, kp, b.xs[j] + grow * b.ldxs[j], b.ldxs[j], rows, lane);
             wave_lds_sync();
             const float *scale = fold + p.fold_off[j], *shift = scale + cout, *c1 = b.coef + p.fold_off[j], *c2 = c1 + cout;
             const int32_t *arg_g = j == L - 1 ? b.arg + (size_t)g * cout : nullptr;
@@ -378,42 +227,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sa
             float *dz_ws = b.dz[j] + grow * cout;
             int n0 = 0;
             for (; n0 + 64 <= cout; n0 += 64)
-                sat_form_dz<2>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, m0, arg_g, dout_g, dz_ws, lane);
+                bnt_form_dz<2, K_PAIRS, false>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, m0, arg_g, dout_g, dz_ws, lane);
             for (; n0 < cout; n0 += 32)
-                sat_form_dz<1>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, m0, arg_g, dout_g, dz_ws, lane);
+                bnt_form_dz<1, K_PAIRS, false>(T[0], ld, p.w[j], cin, kp, cout, n0, scale, shift, b.mean[j], c1, c2, T[1], ld, rows, m0, arg_g, dout_g, dz_ws, lane);
             wave_lds_sync();
             if (j == 0 && !want_dx0) continue;    // (wave-uniform) nobody asked for dfeats: dx_0 is not needed
             // dx_l = dz_j W_j over T0 (x_j has been used), or its feature columns to the gather's rows
             float *xo = j ? T[0] : nullptr;
             float *dx0 = b.dx0 + grow * D;
             int c0 = 0;
-            for (; c0 + 64 <= cin; c0 += 64) sab_dgrad<2>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, dx0, D, rows, lane);
-            for (; c0 < cin; c0 += 32) sab_dgrad<1>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, dx0, D, rows, lane);
+            for (; c0 + 64 <= cin; c0 += 64) mlp_dgrad<2, true>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, nullptr, 3, dx0, D, rows, lane);
+            for (; c0 < cin; c0 += 32) mlp_dgrad<1, true>(T[1], ld, p.w[j], cin, cout, c0, xo, ld, nullptr, 3, dx0, D, rows, lane);
             wave_lds_sync();
         }
         if (l >= 0) {
             const int cin = p.cin[l], cout = p.cout[l], kp = p.kp[l];
-            sat_load_rows_flat(T[1], ld, kp, b.xs[l] + grow * b.ldxs[l], b.ldxs[l], rows, lane);
+            fpb_load_rows_flat(T[1], ld, kp, b.xs[l] + grow * b.ldxs[l], b.ldxs[l], rows, lane);
             wave_lds_sync();
             const float *scale = fold + p.fold_off[l], *shift = scale + cout;
             float *dz_ws = b.dz[l] + grow * cout;
             int n0 = 0;
             for (; n0 + 64 <= cout; n0 += 64)
-                sat_form_dy<2>(T[1], ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, rows, dz_ws, part_b, part_g, lane);
+                bnt_form_dy<2, K_PAIRS, false, false>(T[1], ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, nullptr, rows, dz_ws, part_b, part_g, lane);
             for (; n0 < cout; n0 += 32)
-                sat_form_dy<1>(T[1], ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, rows, dz_ws, part_b, part_g, lane);
+                bnt_form_dy<1, K_PAIRS, false, false>(T[1], ld, p.w[l], cin, kp, cout, n0, scale, shift, T[0], ld, nullptr, rows, dz_ws, part_b, part_g, lane);
         }
         wave_lds_sync();                          // the next tile overwrites both tiles
     }
-}
-
-// the two limits of the batch statistics on top of the eval entry points' (`what` opens the message)
-static int sat_rows_ok(const char *what, long long M)
-{
-    AMPNET_REQUIRE(M >= 2, "%s: batch statistics need M = n_clouds * s * nsample >= 2 rows, got %lld", what, M);
-    AMPNET_REQUIRE(M <= SAT_MAX_ROWS, "%s: M = n_clouds * s * nsample = %lld rows exceed %lld (the row counts of the statistics are exact floats)",
-                   what, M, SAT_MAX_ROWS);
-    return AMPNET_OK;
 }
 
 // what the forward's two entry points derive from the shape (the limits are the backward's: what trains has a backward)
@@ -428,7 +268,7 @@ static int sat_fwd_shape(const char *what, int D, int n_clouds, int s, int nsamp
     SaBwdShape b;
     int rc = sab_shape(what, D, n_clouds, s, nsample, cout_host, L, b);
     if (rc != AMPNET_OK) return rc;
-    rc = sat_rows_ok(what, b.M);
+    rc = bnt_rows_ok(what, b.M, SAT_MAX_ROWS, "n_clouds * s * nsample");
     if (rc != AMPNET_OK) return rc;
     sh = {};
     sh.M = b.M;
@@ -448,7 +288,7 @@ static int sat_bwd_shape(const char *what, int D, int n_clouds, int s, int nsamp
 {
     int rc = sab_shape(what, D, n_clouds, s, nsample, cout_host, L, sh);
     if (rc != AMPNET_OK) return rc;
-    rc = sat_rows_ok(what, sh.M);
+    rc = bnt_rows_ok(what, sh.M, SAT_MAX_ROWS, "n_clouds * s * nsample");
     if (rc != AMPNET_OK) return rc;
     off_coef = sh.floats;
     off_arg = off_coef + align_up((size_t)2 * sh.sum_c, 64);
@@ -563,21 +403,9 @@ extern "C" int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int 
     p.nw = 1;
     for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // these kernels stage no weights: every layer is read through L2
     float *ws = static_cast<float *>(workspace);
-    SatBwd b = {};
-    int widest = p.kp[0];
-    for (int l = 0; l < L; ++l) widest = p.cout[l] > widest ? p.cout[l] : widest;
-    b.ld = widest + 1;
-    b.parts = ws + sh.off_parts;
-    b.dx0 = ws + sh.off_dx0;
-    b.coef = ws + off_coef;
+    BntBwd b;
+    const size_t lds = bnt_bwd_plan(p, f, sh, ws, off_coef, b);
     b.arg = reinterpret_cast<int32_t *>(ws + off_arg);
-    for (int l = 0; l < L; ++l) {
-        b.ldxs[l] = sh.ldxs[l];
-        b.xs[l] = ws + sh.off_xs[l];
-        b.dz[l] = ws + sh.off_dz[l];
-        b.mean[l] = f.mean[l];
-    }
-    const size_t lds = (size_t)2 * 32 * b.ld * sizeof(float);
     static bool attr_last = false, attr_phase = false;
     rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_bwd_last_kernel), attr_last);
     if (rc != AMPNET_OK) return rc;

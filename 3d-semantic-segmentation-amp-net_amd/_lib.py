@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMPNET_LIB_PATH") or os.path.join(_HERE, "libampnet_hip.so")   # the override is for A/B runs of two builds
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _lib = None
 
@@ -483,6 +483,103 @@ def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, g
                                           ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ptr(workspace), ctypes.c_size_t(have),
                                           stream_ptr(xyz.device))
     check(rc, "ampnet_sa_backward_f32")
+
+
+# ---- set abstraction over one group of all points (include/ampnet_hip.h: ampnet_sa_all_forward_f32, ampnet_sa_all_backward_f32) -------
+def _sa_all_workspace_bytes(which, D, B, N, couts):
+    couts = [int(c) for c in couts]
+    name = f"ampnet_sa_all_{which}_workspace_bytes"
+    fn = getattr(lib(), name)
+    fn.restype = ctypes.c_size_t
+    need = fn(int(D), int(B), int(N), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
+    if not need:
+        check(-1, name)
+    return int(need)
+
+
+def sa_all_forward_workspace_bytes(D, B, N, couts):
+    """Device bytes sa_all_forward_f32 needs for B clouds of N points with D features and layers of widths `couts`; a shape outside the
+    kernel's limits is an AmpnetError that names the limit."""
+    return _sa_all_workspace_bytes("forward", D, B, N, couts)
+
+
+def sa_all_backward_workspace_bytes(D, B, N, couts):
+    """Device bytes sa_all_backward_f32 needs (as sa_all_forward_workspace_bytes)."""
+    return _sa_all_workspace_bytes("backward", D, B, N, couts)
+
+
+def _sa_all_shapes(prefix, xyz, feats, extra):
+    """The checks sa_all_forward_f32 and sa_all_backward_f32 share -> (B, N, ld, D).  extra: (name, tensor, dtype, required) of the rest."""
+    for name, t, dt, required in (("xyz", xyz, torch.float32, True), ("feats", feats, torch.float32, False)) + tuple(extra):
+        if t is None and required:
+            raise AmpnetError(f"{prefix}: {name} is None, it must be a {dt} GPU tensor")
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt):
+            raise AmpnetError(f"{prefix}: {name} must be a {dt} GPU tensor")
+    if xyz.dim() != 3 or xyz.shape[2] < 3:
+        raise AmpnetError(f"{prefix}: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
+    B, N, ld = xyz.shape
+    if feats is not None and (feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N)):
+        raise AmpnetError(f"{prefix}: feats {tuple(feats.shape)} must be [B, N, D] with xyz {tuple(xyz.shape)}")
+    return B, N, ld, 0 if feats is None else feats.shape[2]
+
+
+def sa_all_forward_f32(xyz, feats, layers, eps, out, workspace, arg_out=None):
+    """One fused set-abstraction layer over ONE group of all N points per cloud (group_all=True).  xyz [B, N, ld], feats [B, N, D] or None,
+    layers / eps as in sa_forward_f32 with cin_0 = 3 + D; out [B, cout_last]; arg_out: int32 [B, cout_last] or None, the lowest row that
+    attains each maximum; workspace: sa_all_forward_workspace_bytes(...) GPU bytes."""
+    L = len(layers)
+    B, N, ld, D = _sa_all_shapes("sa_all_forward", xyz, feats, (("out", out, torch.float32, True), ("arg_out", arg_out, torch.int32, False)))
+    table, couts, epss = _mlp_tables("sa_all_forward", layers, 3 + D, eps, workspace, 0)
+    want = (B, int(layers[-1][0].shape[0])) if L else None
+    if L and tuple(out.shape) != want:
+        raise AmpnetError(f"sa_all_forward: out {tuple(out.shape)} must be [B, cout_last] = {list(want)}")
+    if L and arg_out is not None and tuple(arg_out.shape) != want:
+        raise AmpnetError(f"sa_all_forward: arg_out {tuple(arg_out.shape)} must be [B, cout_last] = {list(want)}")
+    need = sa_all_forward_workspace_bytes(D, B, N, [int(layer[0].shape[0]) for layer in layers])
+    have = workspace.numel() * workspace.element_size()
+    if have < need:
+        raise AmpnetError(f"sa_all_forward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_all_forward_f32(ptr(xyz), B, N, ld, ptr(feats), D, table, couts, epss, L, ptr(out), ptr(arg_out), ptr(workspace),
+                                             ctypes.c_size_t(have), stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_all_forward_f32")
+
+
+def sa_all_backward_f32(xyz, feats, layers, eps, arg, dout, dfeats, grads, workspace):
+    """The backward of sa_all_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; arg: int32
+    [B, cout_last], the forward's arg_out (an input); dout [B, cout_last]; dfeats [B, N, D] written (zeros outside the rows in arg), or None
+    when it is not wanted (always None when feats is None); grads as in sa_backward_f32; workspace: sa_all_backward_workspace_bytes(...)
+    GPU bytes."""
+    L = len(layers)
+    B, N, ld, D = _sa_all_shapes("sa_all_backward", xyz, feats, (("arg", arg, torch.int32, True), ("dout", dout, torch.float32, True),
+                                                                 ("dfeats", dfeats, torch.float32, False)))
+    if feats is None and dfeats is not None:
+        raise AmpnetError(f"sa_all_backward: dfeats must be None when feats is (D = 0), got {tuple(dfeats.shape)}")
+    if dfeats is not None and tuple(dfeats.shape) != tuple(feats.shape):
+        raise AmpnetError(f"sa_all_backward: dfeats {tuple(dfeats.shape)} must have the shape of feats {tuple(feats.shape)}")
+    table, couts, epss = _mlp_tables("sa_all_backward", layers, 3 + D, eps, workspace, 0)
+    want = (B, int(layers[-1][0].shape[0])) if L else None
+    if L and tuple(dout.shape) != want:
+        raise AmpnetError(f"sa_all_backward: dout {tuple(dout.shape)} must be [B, cout_last] = {list(want)}")
+    if L and tuple(arg.shape) != want:
+        raise AmpnetError(f"sa_all_backward: arg {tuple(arg.shape)} must be [B, cout_last] = {list(want)}")
+    if len(grads) != L:
+        raise AmpnetError(f"sa_all_backward: grads has {len(grads)} entries for {L} layers")
+    for i, (layer, g) in enumerate(zip(layers, grads)):
+        wantg = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
+        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, wantg)):
+            raise AmpnetError(f"sa_all_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {wantg}, "
+                              f"got {[tuple(t.shape) for t in g]}")
+    need = sa_all_backward_workspace_bytes(D, B, N, [int(layer[0].shape[0]) for layer in layers])
+    have = workspace.numel() * workspace.element_size()
+    if have < need:
+        raise AmpnetError(f"sa_all_backward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
+    gtensors = [t for g in grads for t in g]
+    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_all_backward_f32(ptr(xyz), B, N, ld, ptr(feats), D, table, couts, epss, L, ptr(arg), ptr(dout), ptr(dfeats), gtable,
+                                              ptr(workspace), ctypes.c_size_t(have), stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_all_backward_f32")
 
 
 # ---- train-mode set abstraction (include/ampnet_hip.h: ampnet_sa_train_forward_f32, ampnet_sa_train_backward_f32) --------------------

@@ -321,6 +321,56 @@ def sa_apply(module, x, centres, group_idx, feats, fold_ws):
     return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *tensors)
 
 
+class _SaAllFn(torch.autograd.Function):
+    """One fused set-abstraction layer over ONE group of all points per cloud (pointnet2_utils.PointNetSetAbstraction with group_all=True
+    and grad=True), BatchNorm's running statistics frozen.  tensors as in _SaFn.  The forward is the eval forward and also asks for the row
+    each maximum came from: [B, cout_last] int32, tiny, and it spares the backward a second pass over all N rows -- the backward runs on
+    those rows alone (csrc/set_abstraction_all.hip).  Exact fp32 whatever the matrix precision is."""
+
+    @staticmethod
+    def forward(ctx, eps, x, feats, *tensors):
+        out, arg = sa_all_forward(x, feats, _fp_layers(tensors), eps, want_arg=True)
+        ctx.save_for_backward(x, feats, arg, *tensors)               # (inputs and arg only: see the note in _EncoderFn.forward)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, feats, arg, *tensors = ctx.saved_tensors
+        layers = _fp_layers(tensors)
+        need_grad = ctx.needs_input_grad
+        dfeats = torch.empty_like(feats) if feats is not None and need_grad[2] else None
+        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
+        need = _lib.sa_all_backward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], x.shape[1],
+                                                    [layer[0].shape[0] for layer in layers])
+        _lib.sa_all_backward_f32(x, feats, layers, ctx.eps, arg, dout.contiguous().float(), dfeats, grads,
+                                 torch.empty(need, dtype=torch.uint8, device=x.device))
+        ret = [None, None, dfeats]
+        for l, g in enumerate(grads):
+            w = tensors[6 * l]
+            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3], None, None)):     # the conv weight keeps its [out, in, 1, 1]
+                ret.append(t if t is not None and need_grad[3 + 6 * l + q] else None)
+        return tuple(ret)
+
+
+def sa_all_forward(x, feats, layers, eps, want_arg=False):
+    """ampnet_sa_all_forward_f32 on layers of six tensors -> (out [B, cout_last], arg int32 [B, cout_last] or None)."""
+    couts = [int(layer[0].shape[0]) for layer in layers]
+    out = torch.empty((x.shape[0], couts[-1]), dtype=torch.float32, device=x.device)
+    arg = torch.empty((x.shape[0], couts[-1]), dtype=torch.int32, device=x.device) if want_arg else None
+    need = _lib.sa_all_forward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], x.shape[1], couts)
+    _lib.sa_all_forward_f32(x, feats, layers, eps, out, torch.empty(need, dtype=torch.uint8, device=x.device), arg_out=arg)
+    return out, arg
+
+
+def sa_all_apply(module, x, feats):
+    """Grad-mode forward of a group_all PointNetSetAbstraction block on point-major rows: x [B, N, 3], feats [B, N, D] or None ->
+    [B, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters."""
+    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
+               for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+    return _SaAllFn.apply([bn.eps for bn in module.mlp_bns], x, feats, *tensors)
+
+
 class _SaTrainFn(torch.autograd.Function):
     """One fused set-abstraction layer with TRAIN-mode BatchNorm (pointnet2_utils.PointNetSetAbstraction with grad=True and
     batch_stats=True, in train mode).  tensors: per layer conv weight [out, in, 1, 1], conv bias, BatchNorm weight, bias; stats: per layer

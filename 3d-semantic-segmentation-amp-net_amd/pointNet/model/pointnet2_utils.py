@@ -25,7 +25,12 @@ num_batches_tracked (ampnet_fp_train_forward_f32); with grad=True its backward g
 over all B * npoint * nsample rows of its groups -- the slots that ball query filled by repeating a group's first member are rows like any
 other, as they are for BatchNorm2d over [B, C, nsample, npoint] (ampnet_sa_train_forward_f32, ampnet_sa_train_backward_f32 through
 autograd._SaTrainFn).  In eval mode the flag changes nothing, and without it .train() still raises.
-Not built: momentum=None, gradients to coordinates, `group_all=True`.
+
+PointNetSetAbstraction(..., group_all=True) forms ONE group of all N points of a cloud, runs the shared MLP on [xyz, features] (the
+coordinates as they are) and takes the max over the points: the global descriptor of a cloud (ampnet_sa_all_forward_f32).  Eval mode,
+with grad=True the frozen-statistics backward (ampnet_sa_all_backward_f32 through autograd._SaAllFn), which runs on the rows that won a
+channel and on nothing else.
+Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
 from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
@@ -103,23 +108,34 @@ class PointNetSetAbstraction(nn.Module):
     batch_stats=False (default): eval mode only, the running statistics frozen; train mode raises.  batch_stats=True: train mode is
     accepted and runs BatchNorm on the statistics of all B * npoint * nsample rows, updating running_mean / running_var (momentum: the
     `momentum` attribute of the block's mlp_bns, one value for the block) and num_batches_tracked once per forward, graph or not; with
-    grad=True the backward goes through the statistics; eval mode is unchanged."""
+    grad=True the backward goes through the statistics; eval mode is unchanged.
+    group_all=True: ONE group of all N points per cloud, the coordinates as they are (the usual sample_and_group_all): npoint, radius and
+    nsample are ignored and may be None, new_xyz is zeros [B, 3, 1] and new_points [B, mlp[-1], 1] (ampnet_sa_all_forward_f32); grad=True
+    works as above (ampnet_sa_all_backward_f32 through autograd._SaAllFn: only the rows that won a channel carry a gradient);
+    `centres=` raises and batch_stats=True is refused at construction."""
 
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda', grad=False, batch_stats=False):
         super().__init__()
         self.grad = bool(grad)
         self.batch_stats = bool(batch_stats)
         if group_all:
-            raise NotImplementedError("the HIP set abstraction is built for group_all=False (ball-query groups of <= 64 points); "
-                                      "the single all-points group is not")
+            if self.batch_stats:
+                raise NotImplementedError("group_all=True is built for eval mode (with grad=True: the running statistics frozen); train mode "
+                                          "-- batch_stats=True, BatchNorm over the B * N rows of the whole-cloud group -- is not")
+            _build_mlp(self, in_channel, mlp, (1, 1), 3 <= in_channel <= _lib.SA_MAX_CIN,
+                       f"the HIP set abstraction with group_all=True is built for 1..{_lib.SA_MAX_LAYERS} MLP layers of widths that are "
+                       f"multiples of 32 up to {_lib.SA_MAX_COUT} and 3 <= in_channel <= {_lib.SA_MAX_CIN}", device)
+            self.npoint, self.radius, self.nsample, self.group_all = npoint, radius, nsample, True      # (ignored; they may be None)
+            return
         _build_mlp(self, in_channel, mlp, (1, 1), 3 <= in_channel <= _lib.SA_MAX_CIN and 1 <= nsample <= _lib.SA_MAX_NSAMPLE,
                    f"the HIP set abstraction is built for 1..{_lib.SA_MAX_LAYERS} MLP layers of widths that are multiples "
                    f"of 32 up to {_lib.SA_MAX_COUT}, 3 <= in_channel <= {_lib.SA_MAX_CIN}, nsample <= {_lib.SA_MAX_NSAMPLE}", device)
         self.npoint, self.radius, self.nsample, self.group_all = int(npoint), float(radius), int(nsample), False
 
     def forward(self, xyz, points, centres=None):
-        """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]).
-        centres: int32 [B, npoint] point indices to use instead of farthest-point sampling from point 0."""
+        """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]);
+        npoint counts as 1 in a group_all block.  centres: int32 [B, npoint] point indices to use instead of farthest-point sampling
+        from point 0."""
         if self.training and not self.batch_stats:
             raise NotImplementedError(_SA_EVAL_ONLY)
         _lib.require_gpu(xyz, "xyz")
@@ -153,6 +169,8 @@ class PointNetSetAbstraction(nn.Module):
         """The layer on point-major tensors (what the kernels take): x [B, N, 3], feats [B, N, D] or None, float32 contiguous GPU
         -> (new_xyz [B, npoint, 3], new_points [B, npoint, mlp[-1]]).  pointnet_2 chains its blocks through this, without the transpose
         pair per block that forward() owes to the channel-major interface."""
+        if self.group_all:
+            return self._all_rows(x, feats, centres)
         B = x.shape[0]
         with torch.no_grad():
             x = x.detach()
@@ -175,6 +193,21 @@ class PointNetSetAbstraction(nn.Module):
                             _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
         return new_xyz, out
 
+    def _all_rows(self, x, feats, centres):
+        """_forward_rows of a group_all block: ONE group of all N points per cloud, the coordinates as they are (no centre)
+        -> (zeros [B, 1, 3], [B, 1, mlp[-1]])."""
+        if centres is not None:
+            raise _lib.AmpnetError("PointNetSetAbstraction: group_all=True has no centres (one group of all points, new_xyz is the origin)")
+        if self.training:
+            raise NotImplementedError(_SA_EVAL_ONLY)
+        from ... import autograd
+        x = x.detach()
+        new_xyz = torch.zeros((x.shape[0], 1, 3), dtype=torch.float32, device=x.device)
+        if self._wants_grad(feats):
+            return new_xyz, autograd.sa_all_apply(self, x, feats).unsqueeze(1)
+        with torch.no_grad():
+            out, _ = autograd.sa_all_forward(x, None if feats is None else feats.detach(), _mlp_tensors(self), [bn.eps for bn in self.mlp_bns])
+        return new_xyz, out.unsqueeze(1)
 
     def _train_rows(self, x, centres, group_idx, feats):
         """The fused layer of _forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 16
+#define AMPNET_ABI_VERSION 17
 
 enum {
     AMPNET_OK = 0,
@@ -488,6 +488,46 @@ int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int ld, const 
                            int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
                            const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- set abstraction with ONE group of all n points per cloud (group_all=True of the usual implementation; new in ABI 17) -----------
+ * Forward, eval mode.  Row j of cloud b is [xyz[b, j, 0:3], feats[b, j, :]]: the coordinates as they are, no centre (a centre at the origin).
+ *   xyz                   [n_clouds, n, ld] float32 (first 3 columns used), n >= 1, n_clouds * n <= 2^31 - 1
+ *   feats                 [n_clouds, n, D] float32, or NULL with D = 0
+ *   params_host, cout_host, eps_host, L   as in ampnet_sa_forward_f32, cin_0 = 3 + D
+ *   out                   [n_clouds, cout_{L-1}] float32: out[b, c] = max_j relu(bn_eval(...)) over the layers
+ *   arg_out               [n_clouds, cout_{L-1}] int32 out, or NULL: the LOWEST row j of cloud b whose float32 value attains out[b, c]
+ *                         (row 0 when every row's y <= 0), the rule of ampnet_sa_backward_f32's arg_out
+ *   workspace             ampnet_sa_all_forward_workspace_bytes(D, n_clouds, n, cout_host, L) device bytes (0 = the shape is refused,
+ *                         ampnet_last_error says why); contents undefined before and after.  It holds the BatchNorm fold and, per cloud,
+ *                         min(ceil(n / 32), 256) partial rows of cout_{L-1} (max, row) pairs.
+ * A wave owns a tile of 32 consecutive rows (rows past n repeat the tile's first row), a cloud's tiles are dealt to at most 256 runs of
+ * consecutive tiles, and an ordered reduce combines the runs: ascending rows with a strict > everywhere, no atomics, so two calls return
+ * the same bits.  The value of a row is formed exactly as ampnet_sa_forward_f32 forms it (k ascending in blocks of 8, k-step i < 4 of lane
+ * half h takes k = k0 + 2 i + h): on the same rows, with a centre at the origin, the two entry points agree bit for bit.
+ * Limits (AMPNET_E_ARG otherwise): L <= AMPNET_SA_MAX_LAYERS, cin_0 <= AMPNET_SA_MAX_CIN, every cout_l a multiple of 32 and
+ * <= AMPNET_SA_MAX_COUT; every such shape is accepted for every n.  Exact fp32 MFMA whatever the matrix precision is.
+ *
+ * Backward, BatchNorm's running statistics frozen.
+ *   xyz .. eps_host, L    the forward's arguments
+ *   arg                   [n_clouds, cout_{L-1}] int32, an INPUT: the forward's arg_out (values are clamped to [0, n))
+ *   dout                  [n_clouds, cout_{L-1}] float32
+ *   dfeats                [n_clouds, n, D] out, or NULL when it is not wanted; must be NULL when D = 0.  Zero outside the rows in `arg`.
+ *   grads_host            as in ampnet_sa_backward_f32: per layer dW, dbias, dgamma, dbeta, all out
+ *   workspace             ampnet_sa_all_backward_workspace_bytes(D, n_clouds, n, cout_host, L) device bytes (0 = refused)
+ * Only the rows in `arg` carry a gradient (eval BatchNorm is a per-row map): at most cout_{L-1} distinct rows per cloud.  They are sorted
+ * into ascending order and compacted into cout_{L-1} / 32 chunks of 32 rows (a chunk is padded by repeating its first member, an empty
+ * chunk repeats the cloud's first winner), chunk k gets dout where arg's row lies in chunk k and 0 elsewhere, and the chunks go through
+ * ampnet_sa_backward_f32 as groups of nsample = 32 around an all-zero centre: its formulas, summation orders and bits over
+ * M = n_clouds * cout_{L-1} rows.  Inside a chunk the recomputed max selects the cloud's winner again (same value, ascending order, the
+ * padding repeats an earlier row).  The work after one pass over `arg` does not depend on n, the zero fill of dfeats apart.        */
+size_t ampnet_sa_all_forward_workspace_bytes(int D, int n_clouds, int n, const int *cout_host, int L);
+int ampnet_sa_all_forward_f32(const float *xyz, int n_clouds, int n, int ld, const float *feats, int D, const float *const *params_host,
+                              const int *cout_host, const float *eps_host, int L, float *out, int32_t *arg_out, void *workspace,
+                              size_t workspace_bytes, void *stream);
+size_t ampnet_sa_all_backward_workspace_bytes(int D, int n_clouds, int n, const int *cout_host, int L);
+int ampnet_sa_all_backward_f32(const float *xyz, int n_clouds, int n, int ld, const float *feats, int D, const float *const *params_host,
+                               const int *cout_host, const float *eps_host, int L, const int32_t *arg, const float *dout, float *dfeats,
+                               float *const *grads_host, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- ampnet_sa_forward_f32 and its backward with TRAIN-mode BatchNorm: batch statistics (encoder training; new in ABI 14) -------------
  * Forward.  The arguments of ampnet_sa_forward_f32, and (as in ampnet_fp_train_forward_f32):

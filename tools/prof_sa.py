@@ -15,7 +15,14 @@ sat_bwd_phase_kernel per remaining phase, fpt_bwd_finalize_kernel per layer, fp_
 sa_dfeats_kernel) against torch's train-mode composition (batch_norm(training=True), forward under no_grad and the backward of a retained
 graph) and against this project's eval forward and eval backward, in alternating rounds, every round reported.
 python3 tools/prof_sa.py [steps] [warmup] train        -- the train-mode leg alone; prints one JSON line.
-python3 tools/prof_sa.py [steps] [warmup] train-trace  -- nothing but the fused train forward and backward, for a kernel trace."""
+python3 tools/prof_sa.py [steps] [warmup] train-trace  -- nothing but the fused train forward and backward, for a kernel trace.
+The group_all leg: one group of all N points per cloud at B = 16, D = 256, MLP [256, 256, 256], N = 64 and N = 1024 side by side -- the fused
+forward (ampnet_sa_all_forward_f32: sa_fold_kernel, sa_all_forward_kernel, sa_all_reduce_kernel) and backward (ampnet_sa_all_backward_f32:
+sa_all_compact_kernel, the kernels of ampnet_sa_backward_f32 on the compacted winners, a memset of dfeats, sa_all_scatter_kernel) against
+torch's composition conv2d 1x1 + eval batch_norm + relu on [B, C, N, 1], then max (forward under no_grad, the backward of a retained graph),
+in alternating rounds, every round reported.  The backward works on the winners alone: its time should not grow with N.
+python3 tools/prof_sa.py [steps] [warmup] group_all        -- the group_all leg alone; prints one JSON line.
+python3 tools/prof_sa.py [steps] [warmup] group_all-trace  -- nothing but the fused group_all forward and backward, for a kernel trace."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -224,6 +231,75 @@ def train_leg(trace):
         pts = U.gather_rows(pts, c)
     return res
 
+
+def group_all_leg(trace):
+    """-> {"n64": figures, "n1024": figures}: one group of all points, B = 16, D = 256, [256, 256, 256]."""
+    res, d_, mlp = {}, 256, [256, 256, 256]
+    for n_ in (64, 1024):
+        pts = torch.from_numpy(synth.clouds(240, B, n_)).to(dev)
+        f = torch.from_numpy(synth.uniform(241, (B, n_, d_), -1.0, 1.0)).to(dev)
+        lay = make_layers(3 + d_, mlp, 7)
+        dout = torch.from_numpy(synth.uniform(242, (B, mlp[-1]), -1.0, 1.0)).to(dev)
+        eps = [1e-5] * len(mlp)
+        fws = torch.empty(L.sa_all_forward_workspace_bytes(d_, B, n_, mlp), dtype=torch.uint8, device=dev)
+        bws = torch.empty(L.sa_all_backward_workspace_bytes(d_, B, n_, mlp), dtype=torch.uint8, device=dev)
+        o, arg = torch.empty((B, mlp[-1]), device=dev), torch.empty((B, mlp[-1]), dtype=torch.int32, device=dev)
+        df = torch.empty_like(f)
+        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in lay]
+        fused_f = lambda: L.sa_all_forward_f32(pts, f, lay, eps, o, fws, arg_out=arg)
+        fused_b = lambda: L.sa_all_backward_f32(pts, f, lay, eps, arg, dout, df, grads, bws)
+        fused_f()                                                             # (the backward takes the forward's arg)
+        if trace:
+            for _ in range(steps):
+                fused_f()
+                fused_b()
+            torch.cuda.synchronize()
+            continue
+        fg = f.detach().clone().requires_grad_(True)
+        leaves = [fg] + [t.requires_grad_(True) for layer in lay for t in layer[:4]]
+
+        def torch_all():
+            x = torch.cat([pts, fg], -1).permute(0, 2, 1)[..., None]          # [B, C, N, 1]
+            for w, bias, gamma, beta, mean, var in lay:
+                x = torch.relu(torch.nn.functional.batch_norm(torch.nn.functional.conv2d(x, w[:, :, None, None], bias), mean, var, gamma, beta, False,
+                                                              0.0, 1e-5))
+            return x.max(2)[0].squeeze(-1)
+
+        def torch_f():
+            with torch.no_grad():
+                torch_all()
+
+        t_out = torch_all()
+        torch_b = lambda: torch.autograd.grad(t_out, leaves, dout, retain_graph=True)
+        rounds = [(timed(fused_f), timed(torch_f), timed(fused_b), timed(torch_b)) for _ in range(3)]
+        fused_f()
+        fused_b()
+        t_grads = torch_b()
+        rel = lambda a, b_: float((a - b_).abs().max() / b_.abs().max())
+        diff = {"out": rel(o, t_out.detach()), "dfeats": rel(df, t_grads[0])}
+        for l in range(len(mlp)):
+            for q, name in enumerate(("dW", "dbias", "dgamma", "dbeta")):
+                diff[f"{name}{l}"] = rel(grads[l][q], t_grads[1 + 4 * l + q])
+        for t in leaves:
+            t.requires_grad_(False)
+        med = lambda q: sorted(r[q] for r in rounds)[1]
+        flops = 2.0 * B * n_ * sum(a * b_ for a, b_ in zip([3 + d_] + mlp[:-1], mlp))
+        res[f"n{n_}"] = {"shape": {"B": B, "N": n_, "D": d_, "mlp": mlp},
+                         "sa_all_forward_ms": round(med(0), 4), "torch_forward_ms": round(med(1), 4),
+                         "sa_all_backward_ms": round(med(2), 4), "torch_backward_ms": round(med(3), 4),
+                         "torch_forward_over_fused": round(med(1) / med(0), 2), "torch_backward_over_fused": round(med(3) / med(2), 2),
+                         "rounds_ms_fused_fwd_torch_fwd_fused_bwd_torch_bwd": [[round(v, 4) for v in r] for r in rounds],
+                         "forward_useful_TFLOPs": round(flops / (med(0) * 1e-3) / 1e12, 2),
+                         "distinct_winners_per_cloud_mean": round(float(sum(len(torch.unique(a)) for a in arg) / B), 1),
+                         "forward_workspace_MB": round(fws.numel() / 1e6, 2), "backward_workspace_MB": round(bws.numel() / 1e6, 2),
+                         "max_rel_diff_vs_torch": diff}
+    return res
+
+
+if mode in ("group_all", "group_all-trace"):
+    r = group_all_leg(mode == "group_all-trace")
+    print(json.dumps({"trace_only": True, "fused_group_all_calls_per_shape": steps} if mode == "group_all-trace" else {"group_all": r}))
+    sys.exit(0)
 
 if mode in ("train", "train-trace"):
     r = train_leg(mode == "train-trace")

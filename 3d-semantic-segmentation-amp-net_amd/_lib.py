@@ -152,9 +152,14 @@ def require_gpu(t, name):
         raise AmpnetError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
 
 
-# ---- PointNet++ grouping (include/ampnet_hip.h: ampnet_ball_query_f32, ampnet_sa_forward_f32) ---------------------------------------
+# ---- PointNet++ (include/ampnet_hip.h: ampnet_ball_query_f32, ampnet_three_nn_f32 and the ampnet_sa_*, ampnet_fp_* entry points) -----
 SA_MAX_NSAMPLE, SA_MAX_LAYERS, SA_MAX_CIN, SA_MAX_COUT = 64, 3, 320, 256
 SA_WORKSPACE_BYTES = SA_MAX_LAYERS * 2 * SA_MAX_COUT * 4
+SA_TRAIN_MAX_ROWS = 1 << 24
+THREE_NN_MAX_S = 12288
+FP_MAX_LAYERS, FP_MAX_CIN, FP_MAX_COUT = 3, 512, 256
+FP_WORKSPACE_BYTES = FP_MAX_LAYERS * 2 * FP_MAX_COUT * 4
+_F32, _I32 = torch.float32, torch.int32
 
 
 def ball_query_f32(xyz, centres, radius, nsample, out, count=None):
@@ -164,56 +169,6 @@ def ball_query_f32(xyz, centres, radius, nsample, out, count=None):
         rc = lib().ampnet_ball_query_f32(ptr(xyz), B, N, ld, ptr(centres), centres.shape[1], ctypes.c_float(radius), int(nsample), ptr(out),
                                          ptr(count), stream_ptr(xyz.device))
     check(rc, "ampnet_ball_query_f32")
-
-
-def _mlp_tables(prefix, layers, cin, eps, workspace, workspace_bytes):
-    """What the fused forwards (sa_forward_f32, fp_forward_f32) share: every layer is six contiguous float32 GPU tensors of shapes
-    [(cout, cin)] + [(cout,)] * 5 chained from cin (the kernels trust these shapes: a short tensor would be read past its end), eps has one
-    entry per layer, the workspace holds workspace_bytes GPU bytes -> the (pointer table, couts, epss) ctypes arrays of the C ABI."""
-    L = len(layers)
-    for i, layer in enumerate(layers):
-        cout = int(layer[0].shape[0])
-        want = [(cout, cin)] + [(cout,)] * 5
-        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
-                                  for t, w in zip(layer, want)):
-            raise AmpnetError(f"{prefix}: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
-                              f"got {[tuple(t.shape) for t in layer]}")
-        cin = cout
-    if len(eps) != L:
-        raise AmpnetError(f"{prefix}: eps has {len(eps)} entries for {L} layers")
-    if workspace.numel() * workspace.element_size() < workspace_bytes or not workspace.is_cuda:
-        raise AmpnetError(f"{prefix}: the workspace must hold {workspace_bytes} GPU bytes")
-    tensors = [t for layer in layers for t in layer]
-    return ((ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors]),
-            (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers]),
-            (ctypes.c_float * max(L, 1))(*[float(e) for e in eps]))
-
-
-def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
-    """One fused set-abstraction layer.  layers: per layer the six contiguous float32 GPU tensors (weight [cout, cin], conv bias, BatchNorm
-    weight, bias, running_mean, running_var); eps: per layer the BatchNorm eps; feats [B, N, D] or None; out [B, S, cout_last]."""
-    B, N, ld = xyz.shape
-    L = len(layers)
-    for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
-                        ("feats", feats, torch.float32), ("out", out, torch.float32)):
-        if t is not None and (not t.is_cuda or t.dtype != dt):
-            raise AmpnetError(f"sa_forward: {name} must be a {dt} GPU tensor")
-    S = centres.shape[1]
-    if tuple(centres.shape) != (B, S) or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != (B, S) \
-            or (feats is not None and tuple(feats.shape[:2]) != (B, N)) or (L and tuple(out.shape) != (B, S, int(layers[-1][0].shape[0]))):
-        raise AmpnetError("sa_forward: centres [B, S], group_idx [B, S, nsample], feats [B, N, D], out [B, S, cout] do not agree with xyz [B, N, ld]")
-    table, couts, epss = _mlp_tables("sa_forward", layers, 3 + (0 if feats is None else feats.shape[2]), eps, workspace, SA_WORKSPACE_BYTES)
-    with torch.cuda.device(xyz.device):
-        rc = lib().ampnet_sa_forward_f32(ptr(xyz), B, N, ld, ptr(centres), centres.shape[1], ptr(group_idx), group_idx.shape[2], ptr(feats),
-                                         0 if feats is None else feats.shape[2], table, couts, epss, L, ptr(out), ptr(workspace),
-                                         ctypes.c_size_t(workspace.numel() * workspace.element_size()), stream_ptr(xyz.device))
-    check(rc, "ampnet_sa_forward_f32")
-
-
-# ---- PointNet++ feature propagation (include/ampnet_hip.h: ampnet_three_nn_f32, ampnet_fp_forward_f32) ------------------------------
-THREE_NN_MAX_S = 12288
-FP_MAX_LAYERS, FP_MAX_CIN, FP_MAX_COUT = 3, 512, 256
-FP_WORKSPACE_BYTES = FP_MAX_LAYERS * 2 * FP_MAX_COUT * 4
 
 
 def three_nn_f32(fine, coarse, idx, dist2):
@@ -232,379 +187,200 @@ def three_nn_f32(fine, coarse, idx, dist2):
     check(rc, "ampnet_three_nn_f32")
 
 
-def fp_forward_f32(points1, points2, idx, dist2, layers, eps, out, workspace):
-    """One fused feature-propagation layer.  points1 [B, N, D1] or None, points2 [B, S, D2], idx int32 / dist2 float32 [B, N, k] (the output
-    of three_nn_f32), layers and eps as in sa_forward_f32 with cin_0 = D1 + D2, out [B, N, cout_last]."""
-    L = len(layers)
-    for name, t, dt in (("points1", points1, torch.float32), ("points2", points2, torch.float32), ("idx", idx, torch.int32),
-                        ("dist2", dist2, torch.float32), ("out", out, torch.float32)):
-        if t is not None and (not t.is_cuda or t.dtype != dt or t.dim() != 3):
-            raise AmpnetError(f"fp_forward: {name} must be a 3-d {dt} GPU tensor")
+# The rules the fused set-abstraction (sa_*) and feature-propagation (fp_*) wrappers share, each written once.  The kernels take bare
+# pointers and no strides: what a wrapper lets through is read wrongly without any error.  `prefix` is the wrapper's name, the start of
+# every message.
+def _workspace_bytes(symbol, ints, couts):
+    """Device bytes the entry point sized by the C symbol `symbol` needs for the shape `ints` and layers of widths `couts`; a shape
+    outside the kernel's limits is an AmpnetError that names the limit."""
+    couts = [int(c) for c in couts]
+    fn = getattr(lib(), symbol)
+    fn.restype = ctypes.c_size_t
+    need = fn(*[int(v) for v in ints], (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
+    if not need:
+        check(-1, symbol)
+    return int(need)
+
+
+def _check_tensors(prefix, rows):
+    """rows: (name, tensor, dtype, ndim, required).  A missing required tensor is named first; every tensor that is given must be a
+    contiguous GPU tensor of that dtype and rank."""
+    for name, t, dt, nd, required in rows:
+        if t is None and required:
+            raise AmpnetError(f"{prefix}: {name} is None, it must be a contiguous {nd}-d {dt} GPU tensor")
+    for name, t, dt, nd, _ in rows:
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or t.dim() != nd or not t.is_contiguous()):
+            got = f"{tuple(t.shape)} {t.dtype} on {t.device}, strides {t.stride()}" if torch.is_tensor(t) else type(t).__name__
+            raise AmpnetError(f"{prefix}: {name} must be a contiguous {nd}-d {dt} GPU tensor, got {got}")
+
+
+def _sa_geometry(prefix, xyz, centres, group_idx, feats, extra):
+    """xyz [B, N, ld >= 3], centres [B, S], group_idx [B, S, nsample], feats [B, N, D] or None -> (B, N, ld, S, nsample, D).  extra: the
+    _check_tensors rows of the wrapper's other tensors."""
+    _check_tensors(prefix, [("xyz", xyz, _F32, 3, True), ("centres", centres, _I32, 2, True), ("group_idx", group_idx, _I32, 3, True),
+                            ("feats", feats, _F32, 3, False)] + extra)
+    B, N, ld = xyz.shape
+    if ld < 3:
+        raise AmpnetError(f"{prefix}: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
+    if centres.shape[0] != B or tuple(group_idx.shape[:2]) != tuple(centres.shape) or (feats is not None and tuple(feats.shape[:2]) != (B, N)):
+        raise AmpnetError(f"{prefix}: centres [B, S], group_idx [B, S, nsample], feats [B, N, D] do not agree with xyz {tuple(xyz.shape)}")
+    return B, N, ld, centres.shape[1], group_idx.shape[2], 0 if feats is None else feats.shape[2]
+
+
+def _sa_all_geometry(prefix, xyz, feats, extra):
+    """xyz [B, N, ld >= 3], feats [B, N, D] or None -> (B, N, ld, D).  extra as in _sa_geometry."""
+    _check_tensors(prefix, [("xyz", xyz, _F32, 3, True), ("feats", feats, _F32, 3, False)] + extra)
+    B, N, ld = xyz.shape
+    if ld < 3:
+        raise AmpnetError(f"{prefix}: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
+    if feats is not None and tuple(feats.shape[:2]) != (B, N):
+        raise AmpnetError(f"{prefix}: feats {tuple(feats.shape)} must be [B, N, D] with xyz {tuple(xyz.shape)}")
+    return B, N, ld, 0 if feats is None else feats.shape[2]
+
+
+def _fp_geometry(prefix, points1, points2, idx, dist2, extra):
+    """points1 [B, N, D1] or None, points2 [B, S, D2], idx and dist2 [B, N, k] -> (B, N, k, S, D1, D2).  extra as in _sa_geometry."""
+    _check_tensors(prefix, [("points1", points1, _F32, 3, False), ("points2", points2, _F32, 3, True), ("idx", idx, _I32, 3, True),
+                            ("dist2", dist2, _F32, 3, True)] + extra)
     B, N, k = idx.shape
-    S, D2 = points2.shape[1], points2.shape[2]
-    D1 = 0 if points1 is None else points1.shape[2]
-    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)) \
-            or (L and tuple(out.shape) != (B, N, int(layers[-1][0].shape[0]))):
-        raise AmpnetError("fp_forward: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k], out [B, N, cout] do not agree with "
-                          f"idx {tuple(idx.shape)}")
-    table, couts, epss = _mlp_tables("fp_forward", layers, D1 + D2, eps, workspace, FP_WORKSPACE_BYTES)
-    with torch.cuda.device(points2.device):
-        rc = lib().ampnet_fp_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L, ptr(out),
-                                         ptr(workspace), ctypes.c_size_t(workspace.numel() * workspace.element_size()),
-                                         stream_ptr(points2.device))
-    check(rc, "ampnet_fp_forward_f32")
+    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)):
+        raise AmpnetError(f"{prefix}: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k] do not agree with idx {tuple(idx.shape)}")
+    return B, N, k, points2.shape[1], 0 if points1 is None else points1.shape[2], points2.shape[2]
+
+
+def _mlp_tables(prefix, layers, cin, eps):
+    """Every layer is six contiguous float32 GPU tensors of shapes [(cout, cin)] + [(cout,)] * 5 chained from cin (the kernels trust these
+    shapes: a short tensor would be read past its end) and eps has one entry per layer -> the (pointer table, couts, epss) ctypes arrays
+    of the C ABI."""
+    L = len(layers)
+    for i, layer in enumerate(layers):
+        cout = int(layer[0].shape[0])
+        want = [(cout, cin)] + [(cout,)] * 5
+        if len(layer) != 6 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                                  for t, w in zip(layer, want)):
+            raise AmpnetError(f"{prefix}: layer {i} needs six contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in layer]}")
+        cin = cout
+    if len(eps) != L:
+        raise AmpnetError(f"{prefix}: eps has {len(eps)} entries for {L} layers")
+    tensors = [t for layer in layers for t in layer]
+    return ((ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors]),
+            (ctypes.c_int * max(L, 1))(*[int(layer[0].shape[0]) for layer in layers]),
+            (ctypes.c_float * max(L, 1))(*[float(e) for e in eps]))
+
+
+def _check_cout_last(prefix, layers, lead, label, **tensors):
+    """Each tensor that is given must be `lead` + (cout_last,); `label` is how the message writes `lead`."""
+    if layers:
+        want = tuple(lead) + (int(layers[-1][0].shape[0]),)
+        for name, t in tensors.items():
+            if t is not None and tuple(t.shape) != want:
+                raise AmpnetError(f"{prefix}: {name} {tuple(t.shape)} must be [{label}, cout_last] = {list(want)}")
+
+
+def _check_grad_of(prefix, dname, d, name, t, optional=False):
+    """d, the gradient written for the input t: None exactly when t is (optional: also wherever it is not wanted), else of t's shape."""
+    if d is None and (t is None or optional):
+        return
+    if d is None or t is None:
+        raise AmpnetError(f"{prefix}: {dname} must be None {'when' if optional else 'exactly when'} {name} is, got "
+                          f"{None if d is None else tuple(d.shape)}")
+    if tuple(d.shape) != tuple(t.shape):
+        raise AmpnetError(f"{prefix}: {dname} {tuple(d.shape)} must have the shape of {name} {tuple(t.shape)}")
+
+
+def _grad_table(prefix, layers, grads):
+    """grads: per layer (dW, dbias, dgamma, dbeta) of the shapes of the layer's weight and bias -> the pointer table of the C ABI."""
+    if len(grads) != len(layers):
+        raise AmpnetError(f"{prefix}: grads has {len(grads)} entries for {len(layers)} layers")
+    for i, (layer, g) in enumerate(zip(layers, grads)):
+        want = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
+        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, want)):
+            raise AmpnetError(f"{prefix}: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {want}, "
+                              f"got {[tuple(t.shape) for t in g]}")
+    tensors = [t for g in grads for t in g]
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+
+
+def _saved_rows(save_mean, save_invstd):
+    return [("save_mean", save_mean, _F32, 1, True), ("save_invstd", save_invstd, _F32, 1, True)]
+
+
+def _check_saved(prefix, layers, save_mean, save_invstd):
+    """The batch statistics of a train entry point: sum(cout) elements each, layer l at the offset of the layers before it."""
+    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
+    for name, t in (("save_mean", save_mean), ("save_invstd", save_invstd)):
+        if t.numel() != sum_c:
+            raise AmpnetError(f"{prefix}: {name} must hold sum(cout) = {sum_c} elements, got {tuple(t.shape)}")
+
+
+def _saved_slots(prefix, layers, save_mean, save_invstd):
+    """The layers a train backward hands to _mlp_tables: (weight, conv bias, BatchNorm weight, bias) of each layer -- further entries are
+    ignored -- and, in slots 4 and 5 of the C ABI, the layer's saved statistics."""
+    _check_saved(prefix, layers, save_mean, save_invstd)
+    slotted, off = [], 0
+    for layer in layers:
+        c = int(layer[0].shape[0])
+        slotted.append(tuple(layer[:4]) + (save_mean[off:off + c], save_invstd[off:off + c]))
+        off += c
+    return slotted
+
+
+def _momentum(prefix, momentum):
+    if momentum is None:
+        raise AmpnetError(f"{prefix}: momentum=None (the cumulative average) is not built; give a float in [0, 1]")
+    return ctypes.c_float(float(momentum))
+
+
+def _workspace_args(prefix, workspace):
+    """(pointer, size in bytes) of the workspace.  Its size is checked against the shape by every ampnet_*_f32 entry point itself -- the
+    copy of that rule that cannot go stale -- so only what the C ABI cannot see is checked here."""
+    if not torch.is_tensor(workspace) or not workspace.is_cuda or not workspace.is_contiguous():
+        raise AmpnetError(f"{prefix}: the workspace must be a contiguous GPU tensor")
+    return ptr(workspace), ctypes.c_size_t(workspace.numel() * workspace.element_size())
 
 
 def fp_backward_workspace_bytes(D1, D2, B, N, couts):
     """Device bytes fp_backward_f32 needs for points1 [B, N, D1], points2 [B, S, D2] and layers of widths `couts` (include/ampnet_hip.h:
     ampnet_fp_backward_workspace_bytes); a shape outside the kernel's limits is an AmpnetError that names the limit."""
-    couts = [int(c) for c in couts]
-    fn = lib().ampnet_fp_backward_workspace_bytes
-    fn.restype = ctypes.c_size_t
-    need = fn(int(D1), int(D2), int(B), int(N), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
-    if not need:
-        check(-1, "ampnet_fp_backward_workspace_bytes")
-    return int(need)
-
-
-def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, dpoints2, grads, workspace):
-    """The backward of fp_forward_f32 with the running statistics frozen.  points1 .. eps: the forward's arguments; dout [B, N, cout_last];
-    dpoints1 [B, N, D1] (None exactly when points1 is None) and dpoints2 [B, S, D2]: written; grads: per layer the four contiguous float32
-    GPU tensors (dW [cout, cin], dbias [cout], dgamma [cout], dbeta [cout]), written; workspace: fp_backward_workspace_bytes(...) GPU
-    bytes."""
-    L = len(layers)
-    for name, t, dt in (("points1", points1, torch.float32), ("points2", points2, torch.float32), ("idx", idx, torch.int32),
-                        ("dist2", dist2, torch.float32), ("dout", dout, torch.float32), ("dpoints1", dpoints1, torch.float32),
-                        ("dpoints2", dpoints2, torch.float32)):
-        if t is not None and (not t.is_cuda or t.dtype != dt or t.dim() != 3):
-            raise AmpnetError(f"fp_backward: {name} must be a 3-d {dt} GPU tensor")
-    B, N, k = idx.shape
-    S, D2 = points2.shape[1], points2.shape[2]
-    D1 = 0 if points1 is None else points1.shape[2]
-    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)):
-        raise AmpnetError(f"fp_backward: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k] do not agree with idx {tuple(idx.shape)}")
-    if (dpoints1 is None) != (points1 is None):
-        raise AmpnetError(f"fp_backward: dpoints1 must be None exactly when points1 is (D1 = {D1}), got "
-                          f"{None if dpoints1 is None else tuple(dpoints1.shape)}")
-    if dpoints1 is not None and tuple(dpoints1.shape) != tuple(points1.shape):
-        raise AmpnetError(f"fp_backward: dpoints1 {tuple(dpoints1.shape)} must have the shape of points1 {tuple(points1.shape)}")
-    if tuple(dpoints2.shape) != tuple(points2.shape):
-        raise AmpnetError(f"fp_backward: dpoints2 {tuple(dpoints2.shape)} must have the shape of points2 {tuple(points2.shape)}")
-    table, couts, epss = _mlp_tables("fp_backward", layers, D1 + D2, eps, workspace, 0)
-    if L and tuple(dout.shape) != (B, N, int(layers[-1][0].shape[0])):
-        raise AmpnetError(f"fp_backward: dout {tuple(dout.shape)} must be [B, N, cout_last] = {[B, N, int(layers[-1][0].shape[0])]}")
-    if len(grads) != L:
-        raise AmpnetError(f"fp_backward: grads has {len(grads)} entries for {L} layers")
-    for i, (layer, g) in enumerate(zip(layers, grads)):
-        want = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
-        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, want)):
-            raise AmpnetError(f"fp_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {want}, "
-                              f"got {[tuple(t.shape) for t in g]}")
-    need = fp_backward_workspace_bytes(D1, D2, B, N, [int(layer[0].shape[0]) for layer in layers])
-    have = workspace.numel() * workspace.element_size()
-    if have < need:
-        raise AmpnetError(f"fp_backward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
-    gtensors = [t for g in grads for t in g]
-    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
-    with torch.cuda.device(points2.device):
-        rc = lib().ampnet_fp_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L,
-                                          ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ptr(workspace), ctypes.c_size_t(have),
-                                          stream_ptr(points2.device))
-    check(rc, "ampnet_fp_backward_f32")
-
-
-# ---- train-mode feature propagation (include/ampnet_hip.h: ampnet_fp_train_forward_f32, ampnet_fp_train_backward_f32) ----------------
-def _fp_train_workspace_bytes(which, D1, D2, B, N, couts):
-    couts = [int(c) for c in couts]
-    name = f"ampnet_fp_train_{which}_workspace_bytes"
-    fn = getattr(lib(), name)
-    fn.restype = ctypes.c_size_t
-    need = fn(int(D1), int(D2), int(B), int(N), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
-    if not need:
-        check(-1, name)
-    return int(need)
+    return _workspace_bytes("ampnet_fp_backward_workspace_bytes", (D1, D2, B, N), couts)
 
 
 def fp_train_forward_workspace_bytes(D1, D2, B, N, couts):
     """Device bytes fp_train_forward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
-    return _fp_train_workspace_bytes("forward", D1, D2, B, N, couts)
+    return _workspace_bytes("ampnet_fp_train_forward_workspace_bytes", (D1, D2, B, N), couts)
 
 
 def fp_train_backward_workspace_bytes(D1, D2, B, N, couts):
     """Device bytes fp_train_backward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
-    return _fp_train_workspace_bytes("backward", D1, D2, B, N, couts)
+    return _workspace_bytes("ampnet_fp_train_backward_workspace_bytes", (D1, D2, B, N), couts)
 
 
-def _fp_train_shapes(prefix, points1, points2, idx, dist2, extra):
-    for name, t, dt in (("points1", points1, torch.float32), ("points2", points2, torch.float32), ("idx", idx, torch.int32),
-                        ("dist2", dist2, torch.float32)) + tuple(extra):
-        if t is not None and (not t.is_cuda or t.dtype != dt or t.dim() != 3):
-            raise AmpnetError(f"{prefix}: {name} must be a 3-d {dt} GPU tensor")
-    B, N, k = idx.shape
-    S, D2 = points2.shape[1], points2.shape[2]
-    D1 = 0 if points1 is None else points1.shape[2]
-    if points2.shape[0] != B or tuple(dist2.shape) != (B, N, k) or (points1 is not None and tuple(points1.shape[:2]) != (B, N)):
-        raise AmpnetError(f"{prefix}: points1 [B, N, D1], points2 [B, S, D2], dist2 [B, N, k] do not agree with idx {tuple(idx.shape)}")
-    return B, N, k, S, D1, D2
-
-
-def _fp_saved(prefix, name, t, sum_c, null_ok=False):
-    if t is None and null_ok:                                   # (NULL: the C ABI refuses it by name)
-        return
-    if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (sum_c,):
-        raise AmpnetError(f"{prefix}: {name} must be a contiguous float32 GPU tensor of sum(cout) = {sum_c} elements, got "
-                          f"{None if t is None else tuple(t.shape)}")
-
-
-def fp_train_forward_f32(points1, points2, idx, dist2, layers, eps, momentum, out, save_mean, save_invstd, workspace):
-    """One fused feature-propagation layer with batch-statistics BatchNorm.  The arguments of fp_forward_f32; running_mean and running_var
-    (entries 4 and 5 of every layer) are UPDATED IN PLACE with `momentum` (a float in [0, 1]); save_mean / save_invstd [sum of couts]:
-    written, layer l at the offset of the layers before it; workspace: fp_train_forward_workspace_bytes(...) GPU bytes."""
-    L = len(layers)
-    B, N, k, S, D1, D2 = _fp_train_shapes("fp_train_forward", points1, points2, idx, dist2, (("out", out, torch.float32),))
-    if L and tuple(out.shape) != (B, N, int(layers[-1][0].shape[0])):
-        raise AmpnetError(f"fp_train_forward: out {tuple(out.shape)} must be [B, N, cout_last] = {[B, N, int(layers[-1][0].shape[0])]}")
-    if momentum is None:
-        raise AmpnetError("fp_train_forward: momentum=None (the cumulative average) is not built; give a float in [0, 1]")
-    table, couts, epss = _mlp_tables("fp_train_forward", layers, D1 + D2, eps, workspace, 0)
-    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
-    _fp_saved("fp_train_forward", "save_mean", save_mean, sum_c, null_ok=True)
-    _fp_saved("fp_train_forward", "save_invstd", save_invstd, sum_c, null_ok=True)
-    have = workspace.numel() * workspace.element_size()
-    with torch.cuda.device(points2.device):
-        rc = lib().ampnet_fp_train_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L,
-                                               ctypes.c_float(float(momentum)), ptr(out), ptr(save_mean), ptr(save_invstd), ptr(workspace),
-                                               ctypes.c_size_t(have), stream_ptr(points2.device))
-    check(rc, "ampnet_fp_train_forward_f32")
-
-
-def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, save_invstd, dout, dpoints1, dpoints2, grads, workspace):
-    """The backward of fp_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
-    further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dpoints1, dpoints2, grads as in
-    fp_backward_f32 (dbias is written as zeros); workspace: fp_train_backward_workspace_bytes(...) GPU bytes."""
-    L = len(layers)
-    B, N, k, S, D1, D2 = _fp_train_shapes("fp_train_backward", points1, points2, idx, dist2,
-                                          (("dout", dout, torch.float32), ("dpoints1", dpoints1, torch.float32),
-                                           ("dpoints2", dpoints2, torch.float32)))
-    if (dpoints1 is None) != (points1 is None):
-        raise AmpnetError(f"fp_train_backward: dpoints1 must be None exactly when points1 is (D1 = {D1}), got "
-                          f"{None if dpoints1 is None else tuple(dpoints1.shape)}")
-    if dpoints1 is not None and tuple(dpoints1.shape) != tuple(points1.shape):
-        raise AmpnetError(f"fp_train_backward: dpoints1 {tuple(dpoints1.shape)} must have the shape of points1 {tuple(points1.shape)}")
-    if tuple(dpoints2.shape) != tuple(points2.shape):
-        raise AmpnetError(f"fp_train_backward: dpoints2 {tuple(dpoints2.shape)} must have the shape of points2 {tuple(points2.shape)}")
-    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
-    _fp_saved("fp_train_backward", "save_mean", save_mean, sum_c)
-    _fp_saved("fp_train_backward", "save_invstd", save_invstd, sum_c)
-    slotted, off = [], 0
-    for layer in layers:                                        # slots 4 and 5 of the C ABI: the layer's saved statistics
-        c = int(layer[0].shape[0])
-        slotted.append(tuple(layer[:4]) + (save_mean[off:off + c], save_invstd[off:off + c]))
-        off += c
-    table, couts, epss = _mlp_tables("fp_train_backward", slotted, D1 + D2, eps, workspace, 0)
-    if L and tuple(dout.shape) != (B, N, int(layers[-1][0].shape[0])):
-        raise AmpnetError(f"fp_train_backward: dout {tuple(dout.shape)} must be [B, N, cout_last] = {[B, N, int(layers[-1][0].shape[0])]}")
-    if len(grads) != L:
-        raise AmpnetError(f"fp_train_backward: grads has {len(grads)} entries for {L} layers")
-    for i, (layer, g) in enumerate(zip(layers, grads)):
-        want = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
-        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, want)):
-            raise AmpnetError(f"fp_train_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {want}, "
-                              f"got {[tuple(t.shape) for t in g]}")
-    gtensors = [t for g in grads for t in g]
-    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
-    have = workspace.numel() * workspace.element_size()
-    with torch.cuda.device(points2.device):
-        rc = lib().ampnet_fp_train_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, L,
-                                                ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ptr(workspace), ctypes.c_size_t(have),
-                                                stream_ptr(points2.device))
-    check(rc, "ampnet_fp_train_backward_f32")
-
-
-# ---- the set-abstraction backward (include/ampnet_hip.h: ampnet_sa_backward_f32) -------------------------------------------------------
 def sa_backward_workspace_bytes(D, B, S, nsample, couts):
     """Device bytes sa_backward_f32 needs for feats [B, N, D], S centres per cloud, groups of nsample and layers of widths `couts`
     (include/ampnet_hip.h: ampnet_sa_backward_workspace_bytes); a shape outside the kernel's limits is an AmpnetError that names the limit."""
-    couts = [int(c) for c in couts]
-    fn = lib().ampnet_sa_backward_workspace_bytes
-    fn.restype = ctypes.c_size_t
-    need = fn(int(D), int(B), int(S), int(nsample), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
-    if not need:
-        check(-1, "ampnet_sa_backward_workspace_bytes")
-    return int(need)
+    return _workspace_bytes("ampnet_sa_backward_workspace_bytes", (D, B, S, nsample), couts)
 
 
-def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, grads, workspace, arg_out=None):
-    """The backward of sa_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; dout [B, S, cout_last];
-    dfeats [B, N, D] written, or None when it is not wanted (always None when feats is None); grads: per layer the four contiguous float32
-    GPU tensors (dW [cout, cin], dbias [cout], dgamma [cout], dbeta [cout]), written; workspace: sa_backward_workspace_bytes(...) GPU
-    bytes; arg_out: int32 [B, S, cout_last] or None, the row of each group that the max selected."""
-    L = len(layers)
-    for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
-                        ("feats", feats, torch.float32), ("dout", dout, torch.float32), ("dfeats", dfeats, torch.float32),
-                        ("arg_out", arg_out, torch.int32)):
-        if t is None and name in ("xyz", "centres", "group_idx", "dout"):
-            raise AmpnetError(f"sa_backward: {name} is None, it must be a {dt} GPU tensor")
-        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt):
-            raise AmpnetError(f"sa_backward: {name} must be a {dt} GPU tensor")
-    if xyz.dim() != 3 or xyz.shape[2] < 3:
-        raise AmpnetError(f"sa_backward: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
-    B, N, ld = xyz.shape
-    if centres.dim() != 2 or centres.shape[0] != B or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != tuple(centres.shape) \
-            or (feats is not None and (feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N))):
-        raise AmpnetError(f"sa_backward: centres [B, S], group_idx [B, S, nsample], feats [B, N, D] do not agree with xyz {tuple(xyz.shape)}")
-    S, nsample = centres.shape[1], group_idx.shape[2]
-    D = 0 if feats is None else feats.shape[2]
-    if feats is None and dfeats is not None:
-        raise AmpnetError(f"sa_backward: dfeats must be None when feats is (D = 0), got {tuple(dfeats.shape)}")
-    if dfeats is not None and tuple(dfeats.shape) != tuple(feats.shape):
-        raise AmpnetError(f"sa_backward: dfeats {tuple(dfeats.shape)} must have the shape of feats {tuple(feats.shape)}")
-    table, couts, epss = _mlp_tables("sa_backward", layers, 3 + D, eps, workspace, 0)
-    want = (B, S, int(layers[-1][0].shape[0])) if L else None
-    if L and tuple(dout.shape) != want:
-        raise AmpnetError(f"sa_backward: dout {tuple(dout.shape)} must be [B, S, cout_last] = {list(want)}")
-    if L and arg_out is not None and tuple(arg_out.shape) != want:
-        raise AmpnetError(f"sa_backward: arg_out {tuple(arg_out.shape)} must be [B, S, cout_last] = {list(want)}")
-    if len(grads) != L:
-        raise AmpnetError(f"sa_backward: grads has {len(grads)} entries for {L} layers")
-    for i, (layer, g) in enumerate(zip(layers, grads)):
-        wantg = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
-        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, wantg)):
-            raise AmpnetError(f"sa_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {wantg}, "
-                              f"got {[tuple(t.shape) for t in g]}")
-    need = sa_backward_workspace_bytes(D, B, S, nsample, [int(layer[0].shape[0]) for layer in layers])
-    have = workspace.numel() * workspace.element_size()
-    if have < need:
-        raise AmpnetError(f"sa_backward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
-    gtensors = [t for g in grads for t in g]
-    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
-    with torch.cuda.device(xyz.device):
-        rc = lib().ampnet_sa_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss, L,
-                                          ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ptr(workspace), ctypes.c_size_t(have),
-                                          stream_ptr(xyz.device))
-    check(rc, "ampnet_sa_backward_f32")
+def sa_train_forward_workspace_bytes(D, B, S, nsample, couts):
+    """Device bytes sa_train_forward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    return _workspace_bytes("ampnet_sa_train_forward_workspace_bytes", (D, B, S, nsample), couts)
 
 
-# ---- set abstraction over one group of all points (include/ampnet_hip.h: ampnet_sa_all_forward_f32, ampnet_sa_all_backward_f32) -------
-def _sa_all_workspace_bytes(which, D, B, N, couts):
-    couts = [int(c) for c in couts]
-    name = f"ampnet_sa_all_{which}_workspace_bytes"
-    fn = getattr(lib(), name)
-    fn.restype = ctypes.c_size_t
-    need = fn(int(D), int(B), int(N), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
-    if not need:
-        check(-1, name)
-    return int(need)
+def sa_train_backward_workspace_bytes(D, B, S, nsample, couts):
+    """Device bytes sa_train_backward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
+    return _workspace_bytes("ampnet_sa_train_backward_workspace_bytes", (D, B, S, nsample), couts)
 
 
 def sa_all_forward_workspace_bytes(D, B, N, couts):
     """Device bytes sa_all_forward_f32 needs for B clouds of N points with D features and layers of widths `couts`; a shape outside the
     kernel's limits is an AmpnetError that names the limit."""
-    return _sa_all_workspace_bytes("forward", D, B, N, couts)
+    return _workspace_bytes("ampnet_sa_all_forward_workspace_bytes", (D, B, N), couts)
 
 
 def sa_all_backward_workspace_bytes(D, B, N, couts):
     """Device bytes sa_all_backward_f32 needs (as sa_all_forward_workspace_bytes)."""
-    return _sa_all_workspace_bytes("backward", D, B, N, couts)
-
-
-def _sa_all_shapes(prefix, xyz, feats, extra):
-    """The checks sa_all_forward_f32 and sa_all_backward_f32 share -> (B, N, ld, D).  extra: (name, tensor, dtype, required) of the rest."""
-    for name, t, dt, required in (("xyz", xyz, torch.float32, True), ("feats", feats, torch.float32, False)) + tuple(extra):
-        if t is None and required:
-            raise AmpnetError(f"{prefix}: {name} is None, it must be a {dt} GPU tensor")
-        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt):
-            raise AmpnetError(f"{prefix}: {name} must be a {dt} GPU tensor")
-    if xyz.dim() != 3 or xyz.shape[2] < 3:
-        raise AmpnetError(f"{prefix}: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
-    B, N, ld = xyz.shape
-    if feats is not None and (feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N)):
-        raise AmpnetError(f"{prefix}: feats {tuple(feats.shape)} must be [B, N, D] with xyz {tuple(xyz.shape)}")
-    return B, N, ld, 0 if feats is None else feats.shape[2]
-
-
-def sa_all_forward_f32(xyz, feats, layers, eps, out, workspace, arg_out=None):
-    """One fused set-abstraction layer over ONE group of all N points per cloud (group_all=True).  xyz [B, N, ld], feats [B, N, D] or None,
-    layers / eps as in sa_forward_f32 with cin_0 = 3 + D; out [B, cout_last]; arg_out: int32 [B, cout_last] or None, the lowest row that
-    attains each maximum; workspace: sa_all_forward_workspace_bytes(...) GPU bytes."""
-    L = len(layers)
-    B, N, ld, D = _sa_all_shapes("sa_all_forward", xyz, feats, (("out", out, torch.float32, True), ("arg_out", arg_out, torch.int32, False)))
-    table, couts, epss = _mlp_tables("sa_all_forward", layers, 3 + D, eps, workspace, 0)
-    want = (B, int(layers[-1][0].shape[0])) if L else None
-    if L and tuple(out.shape) != want:
-        raise AmpnetError(f"sa_all_forward: out {tuple(out.shape)} must be [B, cout_last] = {list(want)}")
-    if L and arg_out is not None and tuple(arg_out.shape) != want:
-        raise AmpnetError(f"sa_all_forward: arg_out {tuple(arg_out.shape)} must be [B, cout_last] = {list(want)}")
-    need = sa_all_forward_workspace_bytes(D, B, N, [int(layer[0].shape[0]) for layer in layers])
-    have = workspace.numel() * workspace.element_size()
-    if have < need:
-        raise AmpnetError(f"sa_all_forward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
-    with torch.cuda.device(xyz.device):
-        rc = lib().ampnet_sa_all_forward_f32(ptr(xyz), B, N, ld, ptr(feats), D, table, couts, epss, L, ptr(out), ptr(arg_out), ptr(workspace),
-                                             ctypes.c_size_t(have), stream_ptr(xyz.device))
-    check(rc, "ampnet_sa_all_forward_f32")
-
-
-def sa_all_backward_f32(xyz, feats, layers, eps, arg, dout, dfeats, grads, workspace):
-    """The backward of sa_all_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; arg: int32
-    [B, cout_last], the forward's arg_out (an input); dout [B, cout_last]; dfeats [B, N, D] written (zeros outside the rows in arg), or None
-    when it is not wanted (always None when feats is None); grads as in sa_backward_f32; workspace: sa_all_backward_workspace_bytes(...)
-    GPU bytes."""
-    L = len(layers)
-    B, N, ld, D = _sa_all_shapes("sa_all_backward", xyz, feats, (("arg", arg, torch.int32, True), ("dout", dout, torch.float32, True),
-                                                                 ("dfeats", dfeats, torch.float32, False)))
-    if feats is None and dfeats is not None:
-        raise AmpnetError(f"sa_all_backward: dfeats must be None when feats is (D = 0), got {tuple(dfeats.shape)}")
-    if dfeats is not None and tuple(dfeats.shape) != tuple(feats.shape):
-        raise AmpnetError(f"sa_all_backward: dfeats {tuple(dfeats.shape)} must have the shape of feats {tuple(feats.shape)}")
-    table, couts, epss = _mlp_tables("sa_all_backward", layers, 3 + D, eps, workspace, 0)
-    want = (B, int(layers[-1][0].shape[0])) if L else None
-    if L and tuple(dout.shape) != want:
-        raise AmpnetError(f"sa_all_backward: dout {tuple(dout.shape)} must be [B, cout_last] = {list(want)}")
-    if L and tuple(arg.shape) != want:
-        raise AmpnetError(f"sa_all_backward: arg {tuple(arg.shape)} must be [B, cout_last] = {list(want)}")
-    if len(grads) != L:
-        raise AmpnetError(f"sa_all_backward: grads has {len(grads)} entries for {L} layers")
-    for i, (layer, g) in enumerate(zip(layers, grads)):
-        wantg = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
-        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, wantg)):
-            raise AmpnetError(f"sa_all_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {wantg}, "
-                              f"got {[tuple(t.shape) for t in g]}")
-    need = sa_all_backward_workspace_bytes(D, B, N, [int(layer[0].shape[0]) for layer in layers])
-    have = workspace.numel() * workspace.element_size()
-    if have < need:
-        raise AmpnetError(f"sa_all_backward: the workspace holds {have} bytes, the shape needs {need} GPU bytes")
-    gtensors = [t for g in grads for t in g]
-    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
-    with torch.cuda.device(xyz.device):
-        rc = lib().ampnet_sa_all_backward_f32(ptr(xyz), B, N, ld, ptr(feats), D, table, couts, epss, L, ptr(arg), ptr(dout), ptr(dfeats), gtable,
-                                              ptr(workspace), ctypes.c_size_t(have), stream_ptr(xyz.device))
-    check(rc, "ampnet_sa_all_backward_f32")
-
-
-# ---- train-mode set abstraction (include/ampnet_hip.h: ampnet_sa_train_forward_f32, ampnet_sa_train_backward_f32) --------------------
-SA_TRAIN_MAX_ROWS = 1 << 24
-
-
-def _sa_train_workspace_bytes(which, D, B, S, nsample, couts):
-    couts = [int(c) for c in couts]
-    name = f"ampnet_sa_train_{which}_workspace_bytes"
-    fn = getattr(lib(), name)
-    fn.restype = ctypes.c_size_t
-    need = fn(int(D), int(B), int(S), int(nsample), (ctypes.c_int * max(len(couts), 1))(*couts), len(couts))
-    if not need:
-        check(-1, name)
-    return int(need)
-
-
-def sa_train_forward_workspace_bytes(D, B, S, nsample, couts):
-    """Device bytes sa_train_forward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
-    return _sa_train_workspace_bytes("forward", D, B, S, nsample, couts)
-
-
-def sa_train_backward_workspace_bytes(D, B, S, nsample, couts):
-    """Device bytes sa_train_backward_f32 needs; a shape outside the kernel's limits is an AmpnetError that names the limit."""
-    return _sa_train_workspace_bytes("backward", D, B, S, nsample, couts)
+    return _workspace_bytes("ampnet_sa_all_backward_workspace_bytes", (D, B, N), couts)
 
 
 def sa_train_backward_tape(D, B, S, nsample, couts, l):
@@ -619,42 +395,88 @@ def sa_train_backward_tape(D, B, S, nsample, couts, l):
     return int(xo.value), int(xs.value), int(dzo.value), int(dzs.value)
 
 
-def _sa_train_shapes(prefix, xyz, centres, group_idx, feats, extra):
-    for name, t, dt in (("xyz", xyz, torch.float32), ("centres", centres, torch.int32), ("group_idx", group_idx, torch.int32),
-                        ("feats", feats, torch.float32)) + tuple(extra):
-        if t is None and name in ("xyz", "centres", "group_idx", "out", "dout"):
-            raise AmpnetError(f"{prefix}: {name} is None, it must be a {dt} GPU tensor")
-        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-            raise AmpnetError(f"{prefix}: {name} must be a contiguous {dt} GPU tensor")
-    if xyz.dim() != 3 or xyz.shape[2] < 3:
-        raise AmpnetError(f"{prefix}: xyz must be [B, N, ld >= 3], got {tuple(xyz.shape)}")
-    B, N, ld = xyz.shape
-    if centres.dim() != 2 or centres.shape[0] != B or group_idx.dim() != 3 or tuple(group_idx.shape[:2]) != tuple(centres.shape) \
-            or (feats is not None and (feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N))):
-        raise AmpnetError(f"{prefix}: centres [B, S], group_idx [B, S, nsample], feats [B, N, D] do not agree with xyz {tuple(xyz.shape)}")
-    return B, N, ld, centres.shape[1], group_idx.shape[2], 0 if feats is None else feats.shape[2]
+# ---- set abstraction: eval forward and frozen-statistics backward ------------------------------------------------------------------------
+def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
+    """One fused set-abstraction layer.  layers: per layer the six contiguous float32 GPU tensors (weight [cout, cin], conv bias, BatchNorm
+    weight, bias, running_mean, running_var); eps: per layer the BatchNorm eps; feats [B, N, D] or None; out [B, S, cout_last]; workspace:
+    SA_WORKSPACE_BYTES GPU bytes."""
+    B, N, ld, S, nsample, D = _sa_geometry("sa_forward", xyz, centres, group_idx, feats, [("out", out, _F32, 3, True)])
+    table, couts, epss = _mlp_tables("sa_forward", layers, 3 + D, eps)
+    _check_cout_last("sa_forward", layers, (B, S), "B, S", out=out)
+    ws, ws_bytes = _workspace_args("sa_forward", workspace)
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
+                                         len(layers), ptr(out), ws, ws_bytes, stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_forward_f32")
 
 
+def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, grads, workspace, arg_out=None):
+    """The backward of sa_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; dout [B, S, cout_last];
+    dfeats [B, N, D] written, or None when it is not wanted (always None when feats is None); grads: per layer (dW [cout, cin],
+    dbias [cout], dgamma [cout], dbeta [cout]), written (_grad_table); workspace: sa_backward_workspace_bytes(...) GPU bytes; arg_out: int32 [B, S, cout_last] or None, the row of each group that the max selected."""
+    B, N, ld, S, nsample, D = _sa_geometry("sa_backward", xyz, centres, group_idx, feats,
+                                           [("dout", dout, _F32, 3, True), ("dfeats", dfeats, _F32, 3, False), ("arg_out", arg_out, _I32, 3, False)])
+    _check_grad_of("sa_backward", "dfeats", dfeats, "feats", feats, optional=True)
+    table, couts, epss = _mlp_tables("sa_backward", layers, 3 + D, eps)
+    _check_cout_last("sa_backward", layers, (B, S), "B, S", dout=dout, arg_out=arg_out)
+    gtable = _grad_table("sa_backward", layers, grads)
+    ws, ws_bytes = _workspace_args("sa_backward", workspace)
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
+                                          len(layers), ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ws, ws_bytes, stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_backward_f32")
+
+
+# ---- set abstraction over one group of all points ---------------------------------------------------------------------------------------
+def sa_all_forward_f32(xyz, feats, layers, eps, out, workspace, arg_out=None):
+    """One fused set-abstraction layer over ONE group of all N points per cloud (group_all=True).  xyz [B, N, ld], feats [B, N, D] or None,
+    layers / eps as in sa_forward_f32 with cin_0 = 3 + D; out [B, cout_last]; arg_out: int32 [B, cout_last] or None, the lowest row that
+    attains each maximum; workspace: sa_all_forward_workspace_bytes(...) GPU bytes."""
+    B, N, ld, D = _sa_all_geometry("sa_all_forward", xyz, feats, [("out", out, _F32, 2, True), ("arg_out", arg_out, _I32, 2, False)])
+    table, couts, epss = _mlp_tables("sa_all_forward", layers, 3 + D, eps)
+    _check_cout_last("sa_all_forward", layers, (B,), "B", out=out, arg_out=arg_out)
+    ws, ws_bytes = _workspace_args("sa_all_forward", workspace)
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_all_forward_f32(ptr(xyz), B, N, ld, ptr(feats), D, table, couts, epss, len(layers), ptr(out), ptr(arg_out), ws,
+                                             ws_bytes, stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_all_forward_f32")
+
+
+def sa_all_backward_f32(xyz, feats, layers, eps, arg, dout, dfeats, grads, workspace):
+    """The backward of sa_all_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; arg: int32
+    [B, cout_last], the forward's arg_out (an input); dout [B, cout_last]; dfeats [B, N, D] written (zeros outside the rows in arg), or None
+    when it is not wanted (always None when feats is None); grads as in sa_backward_f32; workspace: sa_all_backward_workspace_bytes(...)
+    GPU bytes."""
+    B, N, ld, D = _sa_all_geometry("sa_all_backward", xyz, feats,
+                                   [("arg", arg, _I32, 2, True), ("dout", dout, _F32, 2, True), ("dfeats", dfeats, _F32, 3, False)])
+    _check_grad_of("sa_all_backward", "dfeats", dfeats, "feats", feats, optional=True)
+    table, couts, epss = _mlp_tables("sa_all_backward", layers, 3 + D, eps)
+    _check_cout_last("sa_all_backward", layers, (B,), "B", dout=dout, arg=arg)
+    gtable = _grad_table("sa_all_backward", layers, grads)
+    ws, ws_bytes = _workspace_args("sa_all_backward", workspace)
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_all_backward_f32(ptr(xyz), B, N, ld, ptr(feats), D, table, couts, epss, len(layers), ptr(arg), ptr(dout),
+                                              ptr(dfeats), gtable, ws, ws_bytes, stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_all_backward_f32")
+
+
+# ---- train-mode set abstraction ----------------------------------------------------------------------------------------------------------
 def sa_train_forward_f32(xyz, centres, group_idx, feats, layers, eps, momentum, out, save_mean, save_invstd, workspace):
     """One fused set-abstraction layer with batch-statistics BatchNorm over all B * S * nsample rows.  The arguments of sa_forward_f32;
     running_mean and running_var (entries 4 and 5 of every layer) are UPDATED IN PLACE with `momentum` (a float in [0, 1]); save_mean /
     save_invstd [sum of couts]: written, layer l at the offset of the layers before it; workspace: sa_train_forward_workspace_bytes(...)
     GPU bytes."""
-    L = len(layers)
-    B, N, ld, S, nsample, D = _sa_train_shapes("sa_train_forward", xyz, centres, group_idx, feats, (("out", out, torch.float32),))
-    if L and tuple(out.shape) != (B, S, int(layers[-1][0].shape[0])):
-        raise AmpnetError(f"sa_train_forward: out {tuple(out.shape)} must be [B, S, cout_last] = {[B, S, int(layers[-1][0].shape[0])]}")
-    if momentum is None:
-        raise AmpnetError("sa_train_forward: momentum=None (the cumulative average) is not built; give a float in [0, 1]")
-    table, couts, epss = _mlp_tables("sa_train_forward", layers, 3 + D, eps, workspace, 0)
-    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
-    _fp_saved("sa_train_forward", "save_mean", save_mean, sum_c, null_ok=True)
-    _fp_saved("sa_train_forward", "save_invstd", save_invstd, sum_c, null_ok=True)
-    have = workspace.numel() * workspace.element_size()
+    B, N, ld, S, nsample, D = _sa_geometry("sa_train_forward", xyz, centres, group_idx, feats,
+                                           [("out", out, _F32, 3, True)] + _saved_rows(save_mean, save_invstd))
+    mom = _momentum("sa_train_forward", momentum)
+    table, couts, epss = _mlp_tables("sa_train_forward", layers, 3 + D, eps)
+    _check_cout_last("sa_train_forward", layers, (B, S), "B, S", out=out)
+    _check_saved("sa_train_forward", layers, save_mean, save_invstd)
+    ws, ws_bytes = _workspace_args("sa_train_forward", workspace)
     with torch.cuda.device(xyz.device):
-        rc = lib().ampnet_sa_train_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss, L,
-                                               ctypes.c_float(float(momentum)), ptr(out), ptr(save_mean), ptr(save_invstd), ptr(workspace),
-                                               ctypes.c_size_t(have), stream_ptr(xyz.device))
+        rc = lib().ampnet_sa_train_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
+                                               len(layers), mom, ptr(out), ptr(save_mean), ptr(save_invstd), ws, ws_bytes,
+                                               stream_ptr(xyz.device))
     check(rc, "ampnet_sa_train_forward_f32")
 
 
@@ -662,40 +484,89 @@ def sa_train_backward_f32(xyz, centres, group_idx, feats, layers, eps, save_mean
     """The backward of sa_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
     further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dfeats, grads, arg_out as in
     sa_backward_f32 (dbias is written as zeros); workspace: sa_train_backward_workspace_bytes(...) GPU bytes."""
-    L = len(layers)
-    B, N, ld, S, nsample, D = _sa_train_shapes("sa_train_backward", xyz, centres, group_idx, feats,
-                                               (("dout", dout, torch.float32), ("dfeats", dfeats, torch.float32),
-                                                ("arg_out", arg_out, torch.int32)))
-    if feats is None and dfeats is not None:
-        raise AmpnetError(f"sa_train_backward: dfeats must be None when feats is (D = 0), got {tuple(dfeats.shape)}")
-    if dfeats is not None and tuple(dfeats.shape) != tuple(feats.shape):
-        raise AmpnetError(f"sa_train_backward: dfeats {tuple(dfeats.shape)} must have the shape of feats {tuple(feats.shape)}")
-    sum_c = sum(int(layer[0].shape[0]) for layer in layers)
-    _fp_saved("sa_train_backward", "save_mean", save_mean, sum_c)
-    _fp_saved("sa_train_backward", "save_invstd", save_invstd, sum_c)
-    slotted, off = [], 0
-    for layer in layers:                                        # slots 4 and 5 of the C ABI: the layer's saved statistics
-        c = int(layer[0].shape[0])
-        slotted.append(tuple(layer[:4]) + (save_mean[off:off + c], save_invstd[off:off + c]))
-        off += c
-    table, couts, epss = _mlp_tables("sa_train_backward", slotted, 3 + D, eps, workspace, 0)
-    want = (B, S, int(layers[-1][0].shape[0])) if L else None
-    if L and tuple(dout.shape) != want:
-        raise AmpnetError(f"sa_train_backward: dout {tuple(dout.shape)} must be [B, S, cout_last] = {list(want)}")
-    if L and arg_out is not None and tuple(arg_out.shape) != want:
-        raise AmpnetError(f"sa_train_backward: arg_out {tuple(arg_out.shape)} must be [B, S, cout_last] = {list(want)}")
-    if len(grads) != L:
-        raise AmpnetError(f"sa_train_backward: grads has {len(grads)} entries for {L} layers")
-    for i, (layer, g) in enumerate(zip(layers, grads)):
-        wantg = [tuple(layer[0].shape)] + [tuple(layer[1].shape)] * 3
-        if len(g) != 4 or any(tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() for t, w in zip(g, wantg)):
-            raise AmpnetError(f"sa_train_backward: the gradients of layer {i} must be four contiguous float32 GPU tensors of shapes {wantg}, "
-                              f"got {[tuple(t.shape) for t in g]}")
-    gtensors = [t for g in grads for t in g]
-    gtable = (ctypes.c_void_p * max(len(gtensors), 1))(*[t.data_ptr() for t in gtensors])
-    have = workspace.numel() * workspace.element_size()
+    B, N, ld, S, nsample, D = _sa_geometry("sa_train_backward", xyz, centres, group_idx, feats,
+                                           _saved_rows(save_mean, save_invstd) + [("dout", dout, _F32, 3, True), ("dfeats", dfeats, _F32, 3, False),
+                                                                                  ("arg_out", arg_out, _I32, 3, False)])
+    _check_grad_of("sa_train_backward", "dfeats", dfeats, "feats", feats, optional=True)
+    table, couts, epss = _mlp_tables("sa_train_backward", _saved_slots("sa_train_backward", layers, save_mean, save_invstd), 3 + D, eps)
+    _check_cout_last("sa_train_backward", layers, (B, S), "B, S", dout=dout, arg_out=arg_out)
+    gtable = _grad_table("sa_train_backward", layers, grads)
+    ws, ws_bytes = _workspace_args("sa_train_backward", workspace)
     with torch.cuda.device(xyz.device):
         rc = lib().ampnet_sa_train_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
-                                                L, ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ptr(workspace), ctypes.c_size_t(have),
-                                                stream_ptr(xyz.device))
+                                                len(layers), ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ws, ws_bytes, stream_ptr(xyz.device))
     check(rc, "ampnet_sa_train_backward_f32")
+
+
+# ---- feature propagation: eval forward and frozen-statistics backward --------------------------------------------------------------------
+def fp_forward_f32(points1, points2, idx, dist2, layers, eps, out, workspace):
+    """One fused feature-propagation layer.  points1 [B, N, D1] or None, points2 [B, S, D2], idx int32 / dist2 float32 [B, N, k] (the output
+    of three_nn_f32), layers and eps as in sa_forward_f32 with cin_0 = D1 + D2, out [B, N, cout_last]; workspace: FP_WORKSPACE_BYTES GPU
+    bytes."""
+    B, N, k, S, D1, D2 = _fp_geometry("fp_forward", points1, points2, idx, dist2, [("out", out, _F32, 3, True)])
+    table, couts, epss = _mlp_tables("fp_forward", layers, D1 + D2, eps)
+    _check_cout_last("fp_forward", layers, (B, N), "B, N", out=out)
+    ws, ws_bytes = _workspace_args("fp_forward", workspace)
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, len(layers),
+                                         ptr(out), ws, ws_bytes, stream_ptr(points2.device))
+    check(rc, "ampnet_fp_forward_f32")
+
+
+def _fp_backward_rows(dout, dpoints1, dpoints2):
+    return [("dout", dout, _F32, 3, True), ("dpoints1", dpoints1, _F32, 3, False), ("dpoints2", dpoints2, _F32, 3, True)]
+
+
+def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, dpoints2, grads, workspace):
+    """The backward of fp_forward_f32 with the running statistics frozen.  points1 .. eps: the forward's arguments; dout [B, N, cout_last];
+    dpoints1 [B, N, D1] (None exactly when points1 is None) and dpoints2 [B, S, D2]: written; grads as in sa_backward_f32; workspace:
+    fp_backward_workspace_bytes(...) GPU bytes."""
+    B, N, k, S, D1, D2 = _fp_geometry("fp_backward", points1, points2, idx, dist2, _fp_backward_rows(dout, dpoints1, dpoints2))
+    _check_grad_of("fp_backward", "dpoints1", dpoints1, "points1", points1)
+    _check_grad_of("fp_backward", "dpoints2", dpoints2, "points2", points2)
+    table, couts, epss = _mlp_tables("fp_backward", layers, D1 + D2, eps)
+    _check_cout_last("fp_backward", layers, (B, N), "B, N", dout=dout)
+    gtable = _grad_table("fp_backward", layers, grads)
+    ws, ws_bytes = _workspace_args("fp_backward", workspace)
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, len(layers),
+                                          ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws, ws_bytes, stream_ptr(points2.device))
+    check(rc, "ampnet_fp_backward_f32")
+
+
+# ---- train-mode feature propagation ------------------------------------------------------------------------------------------------------
+def fp_train_forward_f32(points1, points2, idx, dist2, layers, eps, momentum, out, save_mean, save_invstd, workspace):
+    """One fused feature-propagation layer with batch-statistics BatchNorm.  The arguments of fp_forward_f32; running_mean and running_var
+    (entries 4 and 5 of every layer) are UPDATED IN PLACE with `momentum` (a float in [0, 1]); save_mean / save_invstd [sum of couts]:
+    written, layer l at the offset of the layers before it; workspace: fp_train_forward_workspace_bytes(...) GPU bytes."""
+    B, N, k, S, D1, D2 = _fp_geometry("fp_train_forward", points1, points2, idx, dist2,
+                                      [("out", out, _F32, 3, True)] + _saved_rows(save_mean, save_invstd))
+    mom = _momentum("fp_train_forward", momentum)
+    table, couts, epss = _mlp_tables("fp_train_forward", layers, D1 + D2, eps)
+    _check_cout_last("fp_train_forward", layers, (B, N), "B, N", out=out)
+    _check_saved("fp_train_forward", layers, save_mean, save_invstd)
+    ws, ws_bytes = _workspace_args("fp_train_forward", workspace)
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_train_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss,
+                                               len(layers), mom, ptr(out), ptr(save_mean), ptr(save_invstd), ws, ws_bytes,
+                                               stream_ptr(points2.device))
+    check(rc, "ampnet_fp_train_forward_f32")
+
+
+def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, save_invstd, dout, dpoints1, dpoints2, grads, workspace):
+    """The backward of fp_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
+    further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dpoints1, dpoints2, grads as in
+    fp_backward_f32 (dbias is written as zeros); workspace: fp_train_backward_workspace_bytes(...) GPU bytes."""
+    B, N, k, S, D1, D2 = _fp_geometry("fp_train_backward", points1, points2, idx, dist2,
+                                      _saved_rows(save_mean, save_invstd) + _fp_backward_rows(dout, dpoints1, dpoints2))
+    _check_grad_of("fp_train_backward", "dpoints1", dpoints1, "points1", points1)
+    _check_grad_of("fp_train_backward", "dpoints2", dpoints2, "points2", points2)
+    table, couts, epss = _mlp_tables("fp_train_backward", _saved_slots("fp_train_backward", layers, save_mean, save_invstd), D1 + D2, eps)
+    _check_cout_last("fp_train_backward", layers, (B, N), "B, N", dout=dout)
+    gtable = _grad_table("fp_train_backward", layers, grads)
+    ws, ws_bytes = _workspace_args("fp_train_backward", workspace)
+    with torch.cuda.device(points2.device):
+        rc = lib().ampnet_fp_train_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss,
+                                                len(layers), ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws, ws_bytes,
+                                                stream_ptr(points2.device))
+    check(rc, "ampnet_fp_train_backward_f32")

@@ -169,6 +169,48 @@ def cls_head_apply(module, pt, bt, gl_rows, mask, B, W, n_classes, p_drop, seed)
     return out, aw
 
 
+# ---- what the five PointNet++ Functions below share ------------------------------------------------------------------------------------
+def _block_tensors(module, stats=True):
+    """The conv and BatchNorm tensors of a PointNetSetAbstraction / PointNetFeaturePropagation block, the module's own, layer after layer:
+    conv weight, conv bias, BatchNorm weight, bias and, with `stats`, running_mean, running_var."""
+    return [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
+            for t in (conv.weight, conv.bias, bn.weight, bn.bias) + ((bn.running_mean, bn.running_var) if stats else ())]
+
+
+def _mlp_layers(tensors, per):
+    """The `per` contiguous float32 tensors per layer that the C ABI takes, from the module's own (weight [out, in, 1(, 1)] -> [out, in])."""
+    return [tuple(t.detach().reshape(t.shape[0], -1).float().contiguous() if q == 0 else t.detach().float().contiguous()
+                  for q, t in enumerate(tensors[i:i + per])) for i in range(0, len(tensors), per)]
+
+
+def _couts(layers):
+    return [int(layer[0].shape[0]) for layer in layers]
+
+
+def _width(t):
+    return 0 if t is None else t.shape[2]
+
+
+def _ws(nbytes, device):
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _alloc_grads(layers):
+    return [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
+
+
+def _param_grads(tensors, grads, per, need_grad, first):
+    """The parameter tail of a backward's return tuple.  tensors: the forward's *tensors, `per` of them per layer, tensors[0] being the
+    forward's argument number `first`; grads: per layer (dW, dbias, dgamma, dbeta).  dW takes the conv weight's own shape (its trailing
+    singleton dimensions), the running statistics (per = 6) get None, and so does every tensor that did not ask for a gradient."""
+    ret = []
+    for l, g in enumerate(grads):
+        for q in range(per):
+            wanted = q < 4 and need_grad[first + per * l + q]
+            ret.append(None if not wanted else g[q] if q else g[0].reshape(tensors[per * l].shape))
+    return tuple(ret)
+
+
 class _FpFn(torch.autograd.Function):
     """One fused feature-propagation layer with BatchNorm's running statistics frozen (pointnet2_utils.PointNetFeaturePropagation with
     grad=True).  tensors: per layer conv weight [out, in, 1], conv bias, BatchNorm weight, bias, running_mean, running_var.  The forward
@@ -177,7 +219,7 @@ class _FpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eps, fold_ws, p1, p2, idx, dist2, *tensors):
-        layers = _fp_layers(tensors)
+        layers = _mlp_layers(tensors, 6)
         out = torch.empty((p2.shape[0], idx.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=p2.device)
         _lib.fp_forward_f32(p1, p2, idx, dist2, layers, eps, out, fold_ws)
         ctx.save_for_backward(p1, p2, idx, dist2, *tensors)        # (inputs only: see the note in _EncoderFn.forward)
@@ -187,35 +229,21 @@ class _FpFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         p1, p2, idx, dist2, *tensors = ctx.saved_tensors
-        layers = _fp_layers(tensors)
+        layers = _mlp_layers(tensors, 6)
         dp1 = None if p1 is None else torch.empty_like(p1)
         dp2 = torch.empty_like(p2)
-        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
-        need = _lib.fp_backward_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], p2.shape[0], idx.shape[1],
-                                                [layer[0].shape[0] for layer in layers])
-        _lib.fp_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, dout.contiguous().float(), dp1, dp2, grads,
-                             torch.empty(need, dtype=torch.uint8, device=p2.device))
+        grads = _alloc_grads(layers)
+        need = _lib.fp_backward_workspace_bytes(_width(p1), p2.shape[2], p2.shape[0], idx.shape[1], _couts(layers))
+        _lib.fp_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, dout.contiguous().float(), dp1, dp2, grads, _ws(need, p2.device))
         need_grad = ctx.needs_input_grad
-        ret = [None, None, dp1 if need_grad[2] else None, dp2 if need_grad[3] else None, None, None]
-        for l, g in enumerate(grads):
-            w = tensors[6 * l]
-            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3], None, None)):     # the conv weight keeps its [out, in, 1]
-                ret.append(t if t is not None and need_grad[6 + 6 * l + q] else None)
-        return tuple(ret)
-
-
-def _fp_layers(tensors):
-    """The six contiguous float32 tensors per layer that the C ABI takes, from the module's own (weight [out, in, 1] -> [out, in])."""
-    return [tuple(t.detach().reshape(t.shape[0], -1).float().contiguous() if q == 0 else t.detach().float().contiguous()
-                  for q, t in enumerate(tensors[i:i + 6])) for i in range(0, len(tensors), 6)]
+        return (None, None, dp1 if need_grad[2] else None, dp2 if need_grad[3] else None, None, None) \
+            + _param_grads(tensors, grads, 6, need_grad, 6)
 
 
 def fp_apply(module, p1, p2, idx, dist2, fold_ws):
     """Grad-mode forward of a PointNetFeaturePropagation block on point-major rows: p1 [B, N, D1] or None, p2 [B, S, D2], idx / dist2
     [B, N, k] from utils.three_nn -> [B, N, mlp[-1]] with a graph to p1, p2 and the block's conv and BatchNorm affine parameters."""
-    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
-               for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-    return _FpFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, p1, p2, idx, dist2, *tensors)
+    return _FpFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, p1, p2, idx, dist2, *_block_tensors(module))
 
 
 class _FpTrainFn(torch.autograd.Function):
@@ -227,7 +255,7 @@ class _FpTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eps, momentum, stats, p1, p2, idx, dist2, *tensors):
-        layers = [layer + tuple(st) for layer, st in zip(_fp_train_layers(tensors), stats)]
+        layers = [layer + tuple(st) for layer, st in zip(_mlp_layers(tensors, 4), stats)]
         out, save_mean, save_invstd = fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum)
         ctx.save_for_backward(p1, p2, idx, dist2, save_mean, save_invstd, *tensors)
         ctx.eps = eps
@@ -236,37 +264,25 @@ class _FpTrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         p1, p2, idx, dist2, save_mean, save_invstd, *tensors = ctx.saved_tensors
-        layers = _fp_train_layers(tensors)
+        layers = _mlp_layers(tensors, 4)
         dp1 = None if p1 is None else torch.empty_like(p1)
         dp2 = torch.empty_like(p2)
-        grads = [tuple(torch.empty_like(t) for t in layer) for layer in layers]
-        need = _lib.fp_train_backward_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], p2.shape[0], idx.shape[1],
-                                                      [layer[0].shape[0] for layer in layers])
+        grads = _alloc_grads(layers)
+        need = _lib.fp_train_backward_workspace_bytes(_width(p1), p2.shape[2], p2.shape[0], idx.shape[1], _couts(layers))
         _lib.fp_train_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, save_mean, save_invstd, dout.contiguous().float(), dp1, dp2, grads,
-                                   torch.empty(need, dtype=torch.uint8, device=p2.device))
+                                   _ws(need, p2.device))
         need_grad = ctx.needs_input_grad
-        ret = [None, None, None, dp1 if need_grad[3] else None, dp2 if need_grad[4] else None, None, None]
-        for l, g in enumerate(grads):
-            w = tensors[4 * l]
-            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3])):     # the conv weight keeps its [out, in, 1]; dbias is zeros
-                ret.append(t if need_grad[7 + 4 * l + q] else None)
-        return tuple(ret)
-
-
-def _fp_train_layers(tensors):
-    """The four contiguous float32 parameter tensors per layer, from the module's own (weight [out, in, 1] -> [out, in])."""
-    return [tuple(t.detach().reshape(t.shape[0], -1).float().contiguous() if q == 0 else t.detach().float().contiguous()
-                  for q, t in enumerate(tensors[i:i + 4])) for i in range(0, len(tensors), 4)]
+        return (None, None, None, dp1 if need_grad[3] else None, dp2 if need_grad[4] else None, None, None) \
+            + _param_grads(tensors, grads, 4, need_grad, 7)                         # (dbias is zeros)
 
 
 def fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum):
     """ampnet_fp_train_forward_f32 on layers of six tensors (the running statistics are updated in place) -> (out, save_mean, save_invstd)."""
-    couts = [int(layer[0].shape[0]) for layer in layers]
+    couts = _couts(layers)
     out = torch.empty((p2.shape[0], idx.shape[1], couts[-1]), dtype=torch.float32, device=p2.device)
     save_mean, save_invstd = (torch.empty(sum(couts), dtype=torch.float32, device=p2.device) for _ in range(2))
-    need = _lib.fp_train_forward_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], p2.shape[0], idx.shape[1], couts)
-    _lib.fp_train_forward_f32(p1, p2, idx, dist2, layers, eps, momentum, out, save_mean, save_invstd,
-                              torch.empty(need, dtype=torch.uint8, device=p2.device))
+    need = _lib.fp_train_forward_workspace_bytes(_width(p1), p2.shape[2], p2.shape[0], idx.shape[1], couts)
+    _lib.fp_train_forward_f32(p1, p2, idx, dist2, layers, eps, momentum, out, save_mean, save_invstd, _ws(need, p2.device))
     return out, save_mean, save_invstd
 
 
@@ -274,9 +290,8 @@ def fp_train_apply(module, p1, p2, idx, dist2, momentum):
     """Grad-mode, train-mode forward of a PointNetFeaturePropagation block on point-major rows (as fp_apply): batch statistics, the
     module's running statistics updated in place, a graph to p1, p2 and the block's conv and BatchNorm affine parameters (the conv bias
     gets zeros: it has no effect on a batch-normalised output)."""
-    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns) for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
     stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
-    return _FpTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, p1, p2, idx, dist2, *tensors)
+    return _FpTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, p1, p2, idx, dist2, *_block_tensors(module, stats=False))
 
 
 class _SaFn(torch.autograd.Function):
@@ -287,7 +302,7 @@ class _SaFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eps, fold_ws, x, centres, group_idx, feats, *tensors):
-        layers = _fp_layers(tensors)
+        layers = _mlp_layers(tensors, 6)
         out = torch.empty((x.shape[0], centres.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
         _lib.sa_forward_f32(x, centres, group_idx, feats, layers, eps, out, fold_ws)
         ctx.save_for_backward(x, centres, group_idx, feats, *tensors)        # (inputs only: see the note in _EncoderFn.forward)
@@ -297,28 +312,20 @@ class _SaFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, centres, group_idx, feats, *tensors = ctx.saved_tensors
-        layers = _fp_layers(tensors)
+        layers = _mlp_layers(tensors, 6)
         need_grad = ctx.needs_input_grad
         dfeats = torch.empty_like(feats) if feats is not None and need_grad[5] else None
-        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
-        need = _lib.sa_backward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], centres.shape[1], group_idx.shape[2],
-                                                [layer[0].shape[0] for layer in layers])
-        _lib.sa_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, dout.contiguous().float(), dfeats, grads,
-                             torch.empty(need, dtype=torch.uint8, device=x.device), arg_out=None)
-        ret = [None, None, None, None, None, dfeats]
-        for l, g in enumerate(grads):
-            w = tensors[6 * l]
-            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3], None, None)):     # the conv weight keeps its [out, in, 1, 1]
-                ret.append(t if t is not None and need_grad[6 + 6 * l + q] else None)
-        return tuple(ret)
+        grads = _alloc_grads(layers)
+        need = _lib.sa_backward_workspace_bytes(_width(feats), x.shape[0], centres.shape[1], group_idx.shape[2], _couts(layers))
+        _lib.sa_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, dout.contiguous().float(), dfeats, grads, _ws(need, x.device),
+                             arg_out=None)
+        return (None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 6, need_grad, 6)
 
 
 def sa_apply(module, x, centres, group_idx, feats, fold_ws):
     """Grad-mode forward of a PointNetSetAbstraction block on point-major rows: x [B, N, 3], centres [B, S] and group_idx [B, S, nsample]
     int32, feats [B, N, D] or None -> [B, S, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters."""
-    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
-               for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-    return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *tensors)
+    return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *_block_tensors(module))
 
 
 class _SaAllFn(torch.autograd.Function):
@@ -329,7 +336,7 @@ class _SaAllFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eps, x, feats, *tensors):
-        out, arg = sa_all_forward(x, feats, _fp_layers(tensors), eps, want_arg=True)
+        out, arg = sa_all_forward(x, feats, _mlp_layers(tensors, 6), eps, want_arg=True)
         ctx.save_for_backward(x, feats, arg, *tensors)               # (inputs and arg only: see the note in _EncoderFn.forward)
         ctx.eps = eps
         return out
@@ -337,38 +344,29 @@ class _SaAllFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, feats, arg, *tensors = ctx.saved_tensors
-        layers = _fp_layers(tensors)
+        layers = _mlp_layers(tensors, 6)
         need_grad = ctx.needs_input_grad
         dfeats = torch.empty_like(feats) if feats is not None and need_grad[2] else None
-        grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in layers]
-        need = _lib.sa_all_backward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], x.shape[1],
-                                                    [layer[0].shape[0] for layer in layers])
-        _lib.sa_all_backward_f32(x, feats, layers, ctx.eps, arg, dout.contiguous().float(), dfeats, grads,
-                                 torch.empty(need, dtype=torch.uint8, device=x.device))
-        ret = [None, None, dfeats]
-        for l, g in enumerate(grads):
-            w = tensors[6 * l]
-            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3], None, None)):     # the conv weight keeps its [out, in, 1, 1]
-                ret.append(t if t is not None and need_grad[3 + 6 * l + q] else None)
-        return tuple(ret)
+        grads = _alloc_grads(layers)
+        need = _lib.sa_all_backward_workspace_bytes(_width(feats), x.shape[0], x.shape[1], _couts(layers))
+        _lib.sa_all_backward_f32(x, feats, layers, ctx.eps, arg, dout.contiguous().float(), dfeats, grads, _ws(need, x.device))
+        return (None, None, dfeats) + _param_grads(tensors, grads, 6, need_grad, 3)
 
 
 def sa_all_forward(x, feats, layers, eps, want_arg=False):
     """ampnet_sa_all_forward_f32 on layers of six tensors -> (out [B, cout_last], arg int32 [B, cout_last] or None)."""
-    couts = [int(layer[0].shape[0]) for layer in layers]
+    couts = _couts(layers)
     out = torch.empty((x.shape[0], couts[-1]), dtype=torch.float32, device=x.device)
     arg = torch.empty((x.shape[0], couts[-1]), dtype=torch.int32, device=x.device) if want_arg else None
-    need = _lib.sa_all_forward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], x.shape[1], couts)
-    _lib.sa_all_forward_f32(x, feats, layers, eps, out, torch.empty(need, dtype=torch.uint8, device=x.device), arg_out=arg)
+    need = _lib.sa_all_forward_workspace_bytes(_width(feats), x.shape[0], x.shape[1], couts)
+    _lib.sa_all_forward_f32(x, feats, layers, eps, out, _ws(need, x.device), arg_out=arg)
     return out, arg
 
 
 def sa_all_apply(module, x, feats):
     """Grad-mode forward of a group_all PointNetSetAbstraction block on point-major rows: x [B, N, 3], feats [B, N, D] or None ->
     [B, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters."""
-    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
-               for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-    return _SaAllFn.apply([bn.eps for bn in module.mlp_bns], x, feats, *tensors)
+    return _SaAllFn.apply([bn.eps for bn in module.mlp_bns], x, feats, *_block_tensors(module))
 
 
 class _SaTrainFn(torch.autograd.Function):
@@ -380,7 +378,7 @@ class _SaTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eps, momentum, stats, x, centres, group_idx, feats, *tensors):
-        layers = [layer + tuple(st) for layer, st in zip(_fp_train_layers(tensors), stats)]
+        layers = [layer + tuple(st) for layer, st in zip(_mlp_layers(tensors, 4), stats)]
         out, save_mean, save_invstd = sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum)
         ctx.save_for_backward(x, centres, group_idx, feats, save_mean, save_invstd, *tensors)
         ctx.eps = eps
@@ -389,30 +387,23 @@ class _SaTrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, centres, group_idx, feats, save_mean, save_invstd, *tensors = ctx.saved_tensors
-        layers = _fp_train_layers(tensors)
+        layers = _mlp_layers(tensors, 4)
         need_grad = ctx.needs_input_grad
         dfeats = torch.empty_like(feats) if feats is not None and need_grad[6] else None
-        grads = [tuple(torch.empty_like(t) for t in layer) for layer in layers]
-        need = _lib.sa_train_backward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], centres.shape[1], group_idx.shape[2],
-                                                      [layer[0].shape[0] for layer in layers])
+        grads = _alloc_grads(layers)
+        need = _lib.sa_train_backward_workspace_bytes(_width(feats), x.shape[0], centres.shape[1], group_idx.shape[2], _couts(layers))
         _lib.sa_train_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, save_mean, save_invstd, dout.contiguous().float(), dfeats,
-                                   grads, torch.empty(need, dtype=torch.uint8, device=x.device), arg_out=None)
-        ret = [None, None, None, None, None, None, dfeats]
-        for l, g in enumerate(grads):
-            w = tensors[4 * l]
-            for q, t in enumerate((g[0].reshape(w.shape), g[1], g[2], g[3])):     # the conv weight keeps its [out, in, 1, 1]; dbias is zeros
-                ret.append(t if need_grad[7 + 4 * l + q] else None)
-        return tuple(ret)
+                                   grads, _ws(need, x.device), arg_out=None)
+        return (None, None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 4, need_grad, 7)      # (dbias is zeros)
 
 
 def sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum):
     """ampnet_sa_train_forward_f32 on layers of six tensors (the running statistics are updated in place) -> (out, save_mean, save_invstd)."""
-    couts = [int(layer[0].shape[0]) for layer in layers]
+    couts = _couts(layers)
     out = torch.empty((x.shape[0], centres.shape[1], couts[-1]), dtype=torch.float32, device=x.device)
     save_mean, save_invstd = (torch.empty(sum(couts), dtype=torch.float32, device=x.device) for _ in range(2))
-    need = _lib.sa_train_forward_workspace_bytes(0 if feats is None else feats.shape[2], x.shape[0], centres.shape[1], group_idx.shape[2], couts)
-    _lib.sa_train_forward_f32(x, centres, group_idx, feats, layers, eps, momentum, out, save_mean, save_invstd,
-                              torch.empty(need, dtype=torch.uint8, device=x.device))
+    need = _lib.sa_train_forward_workspace_bytes(_width(feats), x.shape[0], centres.shape[1], group_idx.shape[2], couts)
+    _lib.sa_train_forward_f32(x, centres, group_idx, feats, layers, eps, momentum, out, save_mean, save_invstd, _ws(need, x.device))
     return out, save_mean, save_invstd
 
 
@@ -420,6 +411,5 @@ def sa_train_apply(module, x, centres, group_idx, feats, momentum):
     """Grad-mode, train-mode forward of a PointNetSetAbstraction block on point-major rows (as sa_apply): batch statistics over all
     B * npoint * nsample rows, the module's running statistics updated in place, a graph to feats and the block's conv and BatchNorm affine
     parameters (the conv bias gets zeros: it has no effect on a batch-normalised output)."""
-    tensors = [t for conv, bn in zip(module.mlp_convs, module.mlp_bns) for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
     stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
-    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats, *tensors)
+    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats, *_block_tensors(module, stats=False))

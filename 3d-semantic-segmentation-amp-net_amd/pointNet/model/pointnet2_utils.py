@@ -95,6 +95,30 @@ def _workspace(mod, nbytes, device):
     return mod._ws
 
 
+def _mlp_tensors(mod, live_stats=False):
+    """Per layer the six contiguous float32 tensors the fused kernels take: weight [cout, cin], conv bias, BatchNorm weight, bias,
+    running_mean, running_var -- the statistics as float32 copies (eval: they are read) or, with live_stats, the module's buffers
+    themselves (train: the forward updates them in place)."""
+    from ... import autograd as A
+    if not live_stats:
+        return A._mlp_layers(A._block_tensors(mod), 6)
+    return [layer + (bn.running_mean, bn.running_var) for layer, bn in zip(A._mlp_layers(A._block_tensors(mod, stats=False), 4), mod.mlp_bns)]
+
+
+def _momentum(mod, what):
+    """The one float momentum of the block's BatchNorms (train mode)."""
+    momenta = {bn.momentum for bn in mod.mlp_bns}
+    if None in momenta or len(momenta) != 1:
+        raise NotImplementedError(f"train-mode {what} takes one float momentum for the block's BatchNorms, got "
+                                  f"{[bn.momentum for bn in mod.mlp_bns]} (momentum=None, the cumulative average, is not built)")
+    return float(momenta.pop())
+
+
+def _count_batch(mod):
+    with torch.no_grad():
+        torch._foreach_add_([bn.num_batches_tracked for bn in mod.mlp_bns], 1)
+
+
 _SA_EVAL_ONLY = "the HIP set abstraction is built for eval mode (BatchNorm running statistics, no backward): call .eval() first"
 
 
@@ -148,17 +172,12 @@ class PointNetSetAbstraction(nn.Module):
                                    f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
         if points is not None:
             _lib.require_gpu(points, "points")
+        rows = lambda t: None if t is None else t.float().transpose(1, 2).contiguous()       # [B, N, 3], [B, N, D]
         if self._wants_grad(points):                                 # a differentiable transpose; the coordinates get no gradient
-            x = xyz.detach().float().transpose(1, 2).contiguous()
-            feats = None if points is None else points.float().transpose(1, 2).contiguous()
-            new_xyz, out = self._forward_rows(x, feats, centres)
-            return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
-        with torch.no_grad():
-            x = xyz.detach().float().transpose(1, 2).contiguous()                     # [B, N, 3]
-            feats = None
-            if points is not None:
-                feats = points.detach().float().transpose(1, 2).contiguous()         # [B, N, D]
-            new_xyz, out = self._forward_rows(x, feats, centres)
+            new_xyz, out = self._forward_rows(rows(xyz.detach()), rows(points), centres)
+        else:
+            with torch.no_grad():
+                new_xyz, out = self._forward_rows(rows(xyz), rows(points), centres)
         return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
 
     def _wants_grad(self, feats):
@@ -214,33 +233,16 @@ class PointNetSetAbstraction(nn.Module):
         one is wanted."""
         if not self.batch_stats:
             raise NotImplementedError(_SA_EVAL_ONLY)
-        momenta = {bn.momentum for bn in self.mlp_bns}
-        if None in momenta or len(momenta) != 1:
-            raise NotImplementedError("train-mode set abstraction takes one float momentum for the block's BatchNorms, got "
-                                      f"{[bn.momentum for bn in self.mlp_bns]} (momentum=None, the cumulative average, is not built)")
-        momentum = float(momenta.pop())
+        momentum = _momentum(self, "set abstraction")
         from ... import autograd
         if self._wants_grad(feats):
             out = autograd.sa_train_apply(self, x, centres, group_idx, feats, momentum)
         else:
             with torch.no_grad():
-                layers = [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
-                           bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(), bn.running_mean, bn.running_var)
-                          for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
-                out, _, _ = autograd.sa_train_forward(x, centres, group_idx, None if feats is None else feats.detach(), layers,
-                                                      [bn.eps for bn in self.mlp_bns], momentum)
-        with torch.no_grad():
-            torch._foreach_add_([bn.num_batches_tracked for bn in self.mlp_bns], 1)
+                out, _, _ = autograd.sa_train_forward(x, centres, group_idx, None if feats is None else feats.detach(),
+                                                      _mlp_tensors(self, live_stats=True), [bn.eps for bn in self.mlp_bns], momentum)
+        _count_batch(self)
         return out
-
-
-def _mlp_tensors(mod):
-    """Per layer the six contiguous float32 tensors the fused kernels take: weight [cout, cin], conv bias, BatchNorm weight, bias,
-    running_mean, running_var."""
-    return [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
-             bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(),
-             bn.running_mean.float().contiguous(), bn.running_var.float().contiguous())
-            for conv, bn in zip(mod.mlp_convs, mod.mlp_bns)]
 
 
 _FP_EVAL_ONLY = ("the HIP feature propagation is built for eval mode (BatchNorm running statistics, no backward): call .eval() first, "
@@ -317,21 +319,13 @@ class PointNetFeaturePropagation(nn.Module):
         """_forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when one is wanted."""
         if not self.batch_stats:
             raise NotImplementedError(_FP_EVAL_ONLY)
-        momenta = {bn.momentum for bn in self.mlp_bns}
-        if None in momenta or len(momenta) != 1:
-            raise NotImplementedError("train-mode feature propagation takes one float momentum for the block's BatchNorms, got "
-                                      f"{[bn.momentum for bn in self.mlp_bns]} (momentum=None, the cumulative average, is not built)")
-        momentum = float(momenta.pop())
+        momentum = _momentum(self, "feature propagation")
         from ... import autograd
         if self._wants_grad(p1, p2):
             out = autograd.fp_train_apply(self, p1, p2, idx, dist2, momentum)
         else:
             with torch.no_grad():
-                layers = [(conv.weight.detach().reshape(conv.weight.shape[0], -1).float().contiguous(), conv.bias.detach().float().contiguous(),
-                           bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous(), bn.running_mean, bn.running_var)
-                          for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
-                out, _, _ = autograd.fp_train_forward(None if p1 is None else p1.detach(), p2.detach(), idx, dist2, layers,
-                                                      [bn.eps for bn in self.mlp_bns], momentum)
-        with torch.no_grad():
-            torch._foreach_add_([bn.num_batches_tracked for bn in self.mlp_bns], 1)
+                out, _, _ = autograd.fp_train_forward(None if p1 is None else p1.detach(), p2.detach(), idx, dist2,
+                                                      _mlp_tensors(self, live_stats=True), [bn.eps for bn in self.mlp_bns], momentum)
+        _count_batch(self)
         return out

@@ -155,6 +155,7 @@ def require_gpu(t, name):
 # ---- PointNet++ (include/ampnet_hip.h: ampnet_ball_query_f32, ampnet_three_nn_f32 and the ampnet_sa_*, ampnet_fp_* entry points) -----
 SA_MAX_NSAMPLE, SA_MAX_LAYERS, SA_MAX_CIN, SA_MAX_COUT = 64, 3, 320, 256
 SA_WORKSPACE_BYTES = SA_MAX_LAYERS * 2 * SA_MAX_COUT * 4
+SA_MSG_MAX_SCALES = 4
 SA_TRAIN_MAX_ROWS = 1 << 24
 THREE_NN_MAX_S = 12288
 FP_MAX_LAYERS, FP_MAX_CIN, FP_MAX_COUT = 3, 512, 256
@@ -408,6 +409,76 @@ def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
         rc = lib().ampnet_sa_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
                                          len(layers), ptr(out), ws, ws_bytes, stream_ptr(xyz.device))
     check(rc, "ampnet_sa_forward_f32")
+
+
+# ---- multi-scale grouping: K radii, K branches around the same centres ------------------------------------------------------------------
+def ball_query_msg_f32(xyz, centres, radii, nsamples, outs, counts=None):
+    """ball_query_f32 at K radii in one launch.  xyz [B, N, ld] float32, centres [B, S] int32; radii, nsamples: K host numbers each;
+    outs: K int32 tensors, outs[k] [B, S, nsamples[k]]; counts: None, or K entries each an int32 [B, S] tensor or None."""
+    K = len(outs)
+    if len(radii) != K or len(nsamples) != K or (counts is not None and len(counts) != K):
+        raise AmpnetError(f"ball_query_msg: radii, nsamples, outs and counts must have one entry per scale, got {len(radii)}, "
+                          f"{len(nsamples)}, {K}, {None if counts is None else len(counts)}")
+    rows = [("xyz", xyz, _F32, 3, True), ("centres", centres, _I32, 2, True)]
+    rows += [(f"outs[{k}]", t, _I32, 3, True) for k, t in enumerate(outs)]
+    rows += [(f"counts[{k}]", t, _I32, 2, False) for k, t in enumerate(counts or ())]
+    _check_tensors("ball_query_msg", rows)
+    B, N, ld = xyz.shape
+    S = centres.shape[1]
+    if centres.shape[0] != B or any(tuple(t.shape) != (B, S, int(ns)) for t, ns in zip(outs, nsamples)) \
+            or any(t is not None and tuple(t.shape) != (B, S) for t in counts or ()):
+        raise AmpnetError(f"ball_query_msg: centres [B, S], outs[k] [B, S, nsamples[k]], counts[k] [B, S] do not agree with xyz "
+                          f"{tuple(xyz.shape)}, nsamples {list(nsamples)}")
+    n = max(K, 1)
+    out_table = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
+    count_table = None if counts is None else (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in counts])
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_ball_query_msg_f32(ptr(xyz), B, N, ld, ptr(centres), S, (ctypes.c_float * n)(*[float(r) for r in radii]),
+                                             (ctypes.c_int * n)(*[int(ns) for ns in nsamples]), K, out_table, count_table,
+                                             stream_ptr(xyz.device))
+    check(rc, "ampnet_ball_query_msg_f32")
+
+
+def sa_msg_forward_workspace_bytes(K):
+    """Device bytes sa_msg_forward_f32 needs for K branches: K * SA_WORKSPACE_BYTES, answered on the host; K outside
+    [1, SA_MSG_MAX_SCALES] is an AmpnetError."""
+    fn = lib().ampnet_sa_msg_forward_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    need = fn(int(K))
+    if not need:
+        check(-1, "ampnet_sa_msg_forward_workspace_bytes")
+    return int(need)
+
+
+def sa_msg_forward_f32(xyz, centres, group_idxs, feats, branches, eps, out, workspace):
+    """K fused set-abstraction branches around the same centres in one launch.  group_idxs: K int32 tensors [B, S, nsample_k]; branches:
+    per branch the `layers` of sa_forward_f32 (cin_0 = 3 + D in every branch); eps: per branch the per-layer BatchNorm eps; out
+    [B, S, sum of the branches' cout_last], branch k in its column slice; workspace: sa_msg_forward_workspace_bytes(K) GPU bytes."""
+    K = len(branches)
+    if len(group_idxs) != K or len(eps) != K:
+        raise AmpnetError(f"sa_msg_forward: group_idxs, branches and eps must have one entry per branch, got {len(group_idxs)}, {K}, {len(eps)}")
+    _check_tensors("sa_msg_forward", [("xyz", xyz, _F32, 3, True), ("centres", centres, _I32, 2, True), ("out", out, _F32, 3, True)])
+    (B, N, ld), S, D = xyz.shape, centres.shape[1], 0 if feats is None else feats.shape[-1]
+    params, couts, epss, C = [], [], [], 0
+    for k, layers in enumerate(branches):
+        prefix = f"sa_msg_forward: branch {k}"
+        _, _, _, _, _, D = _sa_geometry(prefix, xyz, centres, group_idxs[k], feats, [])
+        table, cout, e = _mlp_tables(prefix, layers, 3 + D, eps[k])
+        params += table[:6 * len(layers)]
+        couts += cout[:len(layers)]
+        epss += e[:len(layers)]
+        C += couts[-1] if layers else 0
+    if K and tuple(out.shape) != (B, S, C):
+        raise AmpnetError(f"sa_msg_forward: out {tuple(out.shape)} must be [B, S, sum of the branches' cout_last] = {[B, S, C]}")
+    ws, ws_bytes = _workspace_args("sa_msg_forward", workspace)
+    n = max(K, 1)
+    cat = lambda ctype, values: (ctype * max(len(values), 1))(*values)
+    with torch.cuda.device(xyz.device):
+        rc = lib().ampnet_sa_msg_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, (ctypes.c_void_p * n)(*[g.data_ptr() for g in group_idxs]),
+                                             (ctypes.c_int * n)(*[int(g.shape[2]) for g in group_idxs]), ptr(feats), D,
+                                             cat(ctypes.c_void_p, params), cat(ctypes.c_int, couts), cat(ctypes.c_float, epss),
+                                             (ctypes.c_int * n)(*[len(b) for b in branches]), K, ptr(out), ws, ws_bytes, stream_ptr(xyz.device))
+    check(rc, "ampnet_sa_msg_forward_f32")
 
 
 def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, grads, workspace, arg_out=None):

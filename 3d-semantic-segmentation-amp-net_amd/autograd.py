@@ -170,11 +170,13 @@ def cls_head_apply(module, pt, bt, gl_rows, mask, B, W, n_classes, p_drop, seed)
 
 
 # ---- what the five PointNet++ Functions below share ------------------------------------------------------------------------------------
-def _block_tensors(module, stats=True):
+def _block_tensors(module, stats=True, w0=None):
     """The conv and BatchNorm tensors of a PointNetSetAbstraction / PointNetFeaturePropagation block, the module's own, layer after layer:
-    conv weight, conv bias, BatchNorm weight, bias and, with `stats`, running_mean, running_var."""
-    return [t for conv, bn in zip(module.mlp_convs, module.mlp_bns)
-            for t in (conv.weight, conv.bias, bn.weight, bn.bias) + ((bn.running_mean, bn.running_var) if stats else ())]
+    conv weight, conv bias, BatchNorm weight, bias and, with `stats`, running_mean, running_var.  w0: what stands in for layer 0's conv
+    weight (a branch of PointNetSetAbstractionMsg hands it with its columns rotated, by a differentiable op when a graph is wanted)."""
+    return [t for l, (conv, bn) in enumerate(zip(module.mlp_convs, module.mlp_bns))
+            for t in (w0 if l == 0 and w0 is not None else conv.weight, conv.bias, bn.weight, bn.bias)
+            + ((bn.running_mean, bn.running_var) if stats else ())]
 
 
 def _mlp_layers(tensors, per):
@@ -322,10 +324,11 @@ class _SaFn(torch.autograd.Function):
         return (None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 6, need_grad, 6)
 
 
-def sa_apply(module, x, centres, group_idx, feats, fold_ws):
+def sa_apply(module, x, centres, group_idx, feats, fold_ws, w0=None):
     """Grad-mode forward of a PointNetSetAbstraction block on point-major rows: x [B, N, 3], centres [B, S] and group_idx [B, S, nsample]
-    int32, feats [B, N, D] or None -> [B, S, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters."""
-    return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *_block_tensors(module))
+    int32, feats [B, N, D] or None -> [B, S, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters.
+    w0: as in _block_tensors."""
+    return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *_block_tensors(module, w0=w0))
 
 
 class _SaAllFn(torch.autograd.Function):
@@ -407,9 +410,10 @@ def sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum):
     return out, save_mean, save_invstd
 
 
-def sa_train_apply(module, x, centres, group_idx, feats, momentum):
+def sa_train_apply(module, x, centres, group_idx, feats, momentum, w0=None):
     """Grad-mode, train-mode forward of a PointNetSetAbstraction block on point-major rows (as sa_apply): batch statistics over all
     B * npoint * nsample rows, the module's running statistics updated in place, a graph to feats and the block's conv and BatchNorm affine
-    parameters (the conv bias gets zeros: it has no effect on a batch-normalised output)."""
+    parameters (the conv bias gets zeros: it has no effect on a batch-normalised output).  w0: as in _block_tensors."""
     stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
-    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats, *_block_tensors(module, stats=False))
+    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats,
+                            *_block_tensors(module, stats=False, w0=w0))

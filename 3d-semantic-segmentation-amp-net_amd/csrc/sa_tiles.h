@@ -32,6 +32,18 @@ __device__ __forceinline__ void sa_gather_group(float *tile, int ldt, int R, int
     }
 }
 
+// the eval forwards' last-layer epilogue (set_abstraction.hip, set_abstraction_msg.hip): the per-column max over the group's rows, stored to
+// this centre's output row
+struct SaMax {
+    __device__ static float init() { return -INFINITY; }
+    __device__ static void put(float &mx, float *, int, int, float v) { mx = fmaxf(mx, v); }
+    __device__ static void done(float mx, float *dst, int col, int h)
+    {
+        const float o = fmaxf(mx, __shfl_xor(mx, 32));
+        if (h == 0) dst[col] = o;
+    }
+};
+
 // The 32-row-tile variant: rows m0 .. m0 + 31 of a group (group_g: its nsample indices; cx, cy, cz: its centre) into `tile` [32][ld].
 // Unlike sa_gather_group it ZEROES the rows past `rows` instead of repeating row 0: its callers sum over the rows they store.
 __device__ __forceinline__ void sat_gather_rows(float *tile, int ld, int kp0, int cin0, const float *__restrict__ cloud, int ldc,

@@ -14,17 +14,6 @@
 
 namespace ampnet {
 
-// the last layer's epilogue: the per-column max over the group's rows, stored to this centre's output row
-struct SaMax {
-    __device__ static float init() { return -INFINITY; }
-    __device__ static void put(float &mx, float *, int, int, float v) { mx = fmaxf(mx, v); }
-    __device__ static void done(float mx, float *dst, int col, int h)
-    {
-        const float o = fmaxf(mx, __shfl_xor(mx, 32));
-        if (h == 0) dst[col] = o;
-    }
-};
-
 __global__ __launch_bounds__(256) void sa_forward_kernel(MlpPlan p, const float *__restrict__ xyz, int n, int ld, const int32_t *__restrict__ centres,
                                                         int s, const int32_t *__restrict__ group_idx, int nsample,
                                                         const float *__restrict__ feats, int D, const float *__restrict__ fold,

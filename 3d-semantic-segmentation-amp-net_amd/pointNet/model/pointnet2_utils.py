@@ -30,6 +30,11 @@ PointNetSetAbstraction(..., group_all=True) forms ONE group of all N points of a
 coordinates as they are) and takes the max over the points: the global descriptor of a cloud (ampnet_sa_all_forward_f32).  Eval mode,
 with grad=True the frozen-statistics backward (ampnet_sa_all_backward_f32 through autograd._SaAllFn), which runs on the rows that won a
 channel and on nothing else.
+
+PointNetSetAbstractionMsg is the multi-scale-grouping layer of the usual implementation (conv_blocks / bn_blocks): several (radius, nsample,
+mlp) branches around the same centres, concatenated.  Farthest-point sampling runs once, one ball query fills all index lists
+(ampnet_ball_query_msg_f32) and in eval mode one launch runs all branches (ampnet_sa_msg_forward_f32); grad=True and batch_stats=True go
+branch by branch through the kernels above.  It serves models defined inside the set-abstraction limits (its docstring).
 Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
@@ -95,14 +100,15 @@ def _workspace(mod, nbytes, device):
     return mod._ws
 
 
-def _mlp_tensors(mod, live_stats=False):
+def _mlp_tensors(mod, live_stats=False, w0=None):
     """Per layer the six contiguous float32 tensors the fused kernels take: weight [cout, cin], conv bias, BatchNorm weight, bias,
     running_mean, running_var -- the statistics as float32 copies (eval: they are read) or, with live_stats, the module's buffers
-    themselves (train: the forward updates them in place)."""
+    themselves (train: the forward updates them in place).  w0: what stands in for layer 0's conv weight (autograd._block_tensors)."""
     from ... import autograd as A
     if not live_stats:
-        return A._mlp_layers(A._block_tensors(mod), 6)
-    return [layer + (bn.running_mean, bn.running_var) for layer, bn in zip(A._mlp_layers(A._block_tensors(mod, stats=False), 4), mod.mlp_bns)]
+        return A._mlp_layers(A._block_tensors(mod, w0=w0), 6)
+    return [layer + (bn.running_mean, bn.running_var)
+            for layer, bn in zip(A._mlp_layers(A._block_tensors(mod, stats=False, w0=w0), 4), mod.mlp_bns)]
 
 
 def _momentum(mod, what):
@@ -243,6 +249,152 @@ class PointNetSetAbstraction(nn.Module):
                                                       _mlp_tensors(self, live_stats=True), [bn.eps for bn in self.mlp_bns], momentum)
         _count_batch(self)
         return out
+
+
+class _Branch:
+    """One branch of a PointNetSetAbstractionMsg as _build_mlp lays a block out (mlp_convs, mlp_bns): what the helpers of the single-scale
+    blocks take.  Not a Module and never kept: the owner registers the two lists under the usual implementation's names (conv_blocks[i],
+    bn_blocks[i]) and makes a view of them per call."""
+
+    def __init__(self, mlp_convs=None, mlp_bns=None):
+        self.mlp_convs, self.mlp_bns = mlp_convs, mlp_bns
+
+
+class _Bns:
+    """All BatchNorms of a PointNetSetAbstractionMsg as one block's mlp_bns, for the rules that cover the module (_momentum, _count_batch)."""
+
+    def __init__(self, branches):
+        self.mlp_bns = [bn for b in branches for bn in b.mlp_bns]
+
+
+class PointNetSetAbstractionMsg(nn.Module):
+    """One multi-scale-grouping set-abstraction layer: `npoint` centres by farthest-point sampling, and for every (radius, nsample, mlp) of
+    radius_list, nsample_list and mlp_list a branch that groups the first `nsample` points within `radius` of each centre
+    (utils.ball_query_msg: all radii in one pass), runs its shared MLP (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on the group and takes
+    the max; new_points is the branches' outputs concatenated in list order.  Constructor, attribute names and state_dict keys are the usual
+    implementation's -- conv_blocks.{i}.{j}.{weight [out, in, 1, 1], bias}, bn_blocks.{i}.{j}.{weight, bias, running_mean, running_var,
+    num_batches_tracked} -- so checkpoints are exchanged with a torch model.
+    `in_channel` does NOT count the 3 coordinates here (layer 0 of every branch has in = in_channel + 3); PointNetSetAbstraction's does.
+    That difference is the usual implementation's own.
+    Row order: the usual MSG row is [point features (D), relative xyz (3)], features FIRST ([relative xyz] alone when points is None);
+    the kernels take [relative xyz, features].  The module hands them layer 0's weight with its columns rotated
+    (cat(W[:, D:], W[:, :D])): the checkpoint keeps the usual order, and with grad=True the rotation is a differentiable op, so layer 0's
+    weight gradient arrives in the checkpoint's column order.
+    Eval mode without a graph: ONE launch for all branches (ampnet_sa_msg_forward_f32), each branch writing its column slice.
+    grad=True (eval mode): branch by branch through autograd._SaFn on the shared centres, concatenated; the value equals the fused
+    forward's bit for bit, and the gradient to `points` is the sum over the branches.  batch_stats=True (train mode): branch by branch
+    through ampnet_sa_train_forward_f32 / autograd._SaTrainFn, each branch with its own statistics over its B * npoint * nsample_k rows
+    and its running statistics updated in place; num_batches_tracked goes up once per forward; one float momentum covers the module.
+    Without the flag .train() raises.  grad and batch_stats otherwise as in PointNetSetAbstraction.
+    Limits: 1..SA_MSG_MAX_SCALES branches, each within the set-abstraction limits (1..3 layers, widths multiples of 32 up to 256,
+    in_channel + 3 <= 320, nsample <= 64).  This block serves models DEFINED inside those limits: the stock MSG segmentation model's
+    widths 16, 196, 384 and 512 are outside them and are refused, not approximated.  Not built: group_all or k-NN grouping inside this
+    block, a fused multi-branch backward or train path."""
+
+    def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list, device='cuda', grad=False, batch_stats=False):
+        super().__init__()
+        self.grad = bool(grad)
+        self.batch_stats = bool(batch_stats)
+        radius_list, nsample_list, mlp_list = list(radius_list), list(nsample_list), list(mlp_list)
+        K = len(radius_list)
+        limits = (f"the HIP multi-scale set abstraction is built for radius_list, nsample_list and mlp_list of one length in "
+                  f"1..{_lib.SA_MSG_MAX_SCALES}, every branch with 1..{_lib.SA_MAX_LAYERS} MLP layers of widths that are multiples of 32 up to "
+                  f"{_lib.SA_MAX_COUT}, 0 <= in_channel and in_channel + 3 <= {_lib.SA_MAX_CIN}, nsample <= {_lib.SA_MAX_NSAMPLE}")
+        if len(nsample_list) != K or len(mlp_list) != K or not 1 <= K <= _lib.SA_MSG_MAX_SCALES:
+            raise NotImplementedError(limits)
+        self.npoint, self.in_channel = int(npoint), int(in_channel)
+        self.radius_list, self.nsample_list = [float(r) for r in radius_list], [int(ns) for ns in nsample_list]
+        self.conv_blocks, self.bn_blocks = nn.ModuleList(), nn.ModuleList()
+        for nsample, mlp in zip(self.nsample_list, mlp_list):
+            b = _Branch()
+            _build_mlp(b, self.in_channel + 3, mlp, (1, 1), 3 <= self.in_channel + 3 <= _lib.SA_MAX_CIN and 1 <= nsample <= _lib.SA_MAX_NSAMPLE,
+                       limits, device)
+            self.conv_blocks.append(b.mlp_convs)
+            self.bn_blocks.append(b.mlp_bns)
+        self._ws = None
+
+    @property
+    def _branches(self):
+        return [_Branch(convs, bns) for convs, bns in zip(self.conv_blocks, self.bn_blocks)]
+
+    def forward(self, xyz, points, centres=None):
+        """xyz [B, 3, N], points [B, D, N] or None (D = in_channel) -> (new_xyz [B, 3, npoint], new_points [B, sum of the branches' last
+        widths, npoint]).  centres: int32 [B, npoint] point indices to use instead of farthest-point sampling from point 0."""
+        if self.training and not self.batch_stats:
+            raise NotImplementedError(_SA_EVAL_ONLY)
+        _lib.require_gpu(xyz, "xyz")
+        if xyz.dim() != 3 or xyz.shape[1] != 3:
+            raise _lib.AmpnetError(f"PointNetSetAbstractionMsg: expected xyz [B, 3, N], got {tuple(xyz.shape)}")
+        B, _, N = xyz.shape
+        D = self.in_channel
+        if (points is None) != (D == 0) or (points is not None and (points.dim() != 3 or tuple(points.shape) != (B, D, N))):
+            raise _lib.AmpnetError(f"PointNetSetAbstractionMsg: in_channel={self.in_channel} needs points "
+                                   f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
+        if points is not None:
+            _lib.require_gpu(points, "points")
+        rows = lambda t: None if t is None else t.float().transpose(1, 2).contiguous()       # [B, N, 3], [B, N, D]
+        if self._wants_grad(points):                                 # a differentiable transpose; the coordinates get no gradient
+            new_xyz, out = self._forward_rows(rows(xyz.detach()), rows(points), centres)
+        else:
+            with torch.no_grad():
+                new_xyz, out = self._forward_rows(rows(xyz), rows(points), centres)
+        return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
+
+    _wants_grad = PointNetSetAbstraction._wants_grad
+
+    def _w0(self, b):
+        """Layer 0's weight of branch b as the kernels take it: the checkpoint's columns [features (D), xyz (3)] rotated to [xyz, features]."""
+        D, w = self.in_channel, b.mlp_convs[0].weight
+        return None if D == 0 else torch.cat((w[:, D:], w[:, :D]), dim=1)
+
+    def _forward_rows(self, x, feats, centres=None):
+        """The layer on point-major tensors (what the kernels take): x [B, N, 3], feats [B, N, D] or None, float32 contiguous GPU
+        -> (new_xyz [B, npoint, 3], new_points [B, npoint, sum of the branches' last widths]).  Farthest-point sampling and the ball
+        query at all radii run once."""
+        B, K = x.shape[0], len(self._branches)
+        with torch.no_grad():
+            x = x.detach()
+            if centres is None:
+                centres = U.fps_indices(x, self.npoint)
+            elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
+                raise _lib.AmpnetError(f"PointNetSetAbstractionMsg: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
+            group_idxs = U.ball_query_msg(x, centres, self.radius_list, self.nsample_list)       # validates the centres
+            centres = centres.contiguous()
+            new_xyz = U.gather_rows(x, centres)
+        wants_grad = self._wants_grad(feats)
+        if self.training:
+            return new_xyz, self._train_rows(x, centres, group_idxs, feats, wants_grad)
+        ws = _workspace(self, _lib.sa_msg_forward_workspace_bytes(K), x.device)
+        if wants_grad:                                               # K launches of the single-branch kernel, each with its own fold region
+            from ... import autograd
+            step = _lib.SA_WORKSPACE_BYTES
+            return new_xyz, torch.cat([autograd.sa_apply(b, x, centres, g, feats, ws[k * step:(k + 1) * step], w0=self._w0(b))
+                                       for k, (b, g) in enumerate(zip(self._branches, group_idxs))], dim=2)
+        feats = None if feats is None else feats.detach()
+        branches = [_mlp_tensors(b, w0=self._w0(b)) for b in self._branches]
+        out = torch.empty((B, self.npoint, sum(layers[-1][0].shape[0] for layers in branches)), dtype=torch.float32, device=x.device)
+        _lib.sa_msg_forward_f32(x, centres, group_idxs, feats, branches, [[bn.eps for bn in b.mlp_bns] for b in self._branches], out, ws)
+        return new_xyz, out
+
+    def _train_rows(self, x, centres, group_idxs, feats, wants_grad):
+        """_forward_rows in train mode (batch_stats=True): every branch on its own batch statistics, its buffers updated in place, a graph
+        when one is wanted; the launches are those of K PointNetSetAbstraction blocks in train mode."""
+        if not self.batch_stats:
+            raise NotImplementedError(_SA_EVAL_ONLY)
+        every = _Bns(self._branches)
+        momentum = _momentum(every, "multi-scale set abstraction")
+        from ... import autograd
+        outs = []
+        for b, g in zip(self._branches, group_idxs):
+            if wants_grad:
+                outs.append(autograd.sa_train_apply(b, x, centres, g, feats, momentum, w0=self._w0(b)))
+            else:
+                with torch.no_grad():
+                    outs.append(autograd.sa_train_forward(x, centres, g, None if feats is None else feats.detach(),
+                                                          _mlp_tensors(b, live_stats=True, w0=self._w0(b)), [bn.eps for bn in b.mlp_bns],
+                                                          momentum)[0])
+        _count_batch(every)
+        return torch.cat(outs, dim=2)
 
 
 _FP_EVAL_ONLY = ("the HIP feature propagation is built for eval mode (BatchNorm running statistics, no backward): call .eval() first, "

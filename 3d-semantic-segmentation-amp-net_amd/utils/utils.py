@@ -125,27 +125,55 @@ def ball_query(xyz, centres, radius, nsample, return_counts=False):
     xyz [B, N, D>=3] float32 GPU, centres [B, S] int32 point indices (e.g. fps_indices) -> int32 [B, S, nsample]: per centre the first
     nsample points j, in ascending index order, with float32 squared distance <= float32(radius * radius); with fewer members the
     remaining slots repeat the first one.  return_counts=True also returns int32 [B, S] = min(members, nsample)."""
-    _lib.require_gpu(xyz, "xyz")
-    _lib.require_gpu(centres, "centres")
-    if xyz.dim() != 3 or xyz.shape[2] < 3 or centres.dim() != 2 or centres.shape[0] != xyz.shape[0]:
-        raise _lib.AmpnetError(f"ball_query: expected xyz [B, N, D>=3] and centres [B, S], got {tuple(xyz.shape)} {tuple(centres.shape)}")
-    if centres.dtype != torch.int32:
-        raise _lib.AmpnetError("ball_query: centres must be int32")
-    x = xyz.float().contiguous()
-    c = centres.contiguous()
-    B, N, D = x.shape
-    S = c.shape[1]
-    nsample, radius = int(nsample), float(radius)
-    if not (1 <= nsample <= _lib.SA_MAX_NSAMPLE):
-        raise IndexError(f"ball_query: nsample={nsample} out of range [1, {_lib.SA_MAX_NSAMPLE}]")
-    if not radius >= 0.0:
-        raise _lib.AmpnetError(f"ball_query: radius={radius} must be >= 0")
-    if S and (int(c.min()) < 0 or int(c.max()) >= N):
-        raise IndexError("ball_query: centre index out of range")
+    x, c, (radius,), (nsample,) = _ball_query_args("ball_query", xyz, centres, [radius], [nsample], [""])
+    B, S = c.shape
     out = torch.empty((B, S, nsample), dtype=torch.int32, device=x.device)
     count = torch.empty((B, S), dtype=torch.int32, device=x.device) if return_counts else None
     _lib.ball_query_f32(x, c, radius, nsample, out, count)
     return (out, count) if return_counts else out
+
+
+def _ball_query_args(what, xyz, centres, radii, nsamples, tags):
+    """The argument rules of ball_query and ball_query_msg, written once -> (xyz float32 contiguous, centres contiguous, radii as floats,
+    nsamples as ints).  tags[k] closes a message about scale k.  The centres are validated ONCE, whatever the number of scales: the
+    read-back of their min and max is the call's only wait for the device."""
+    _lib.require_gpu(xyz, "xyz")
+    _lib.require_gpu(centres, "centres")
+    if xyz.dim() != 3 or xyz.shape[2] < 3 or centres.dim() != 2 or centres.shape[0] != xyz.shape[0]:
+        raise _lib.AmpnetError(f"{what}: expected xyz [B, N, D>=3] and centres [B, S], got {tuple(xyz.shape)} {tuple(centres.shape)}")
+    if centres.dtype != torch.int32:
+        raise _lib.AmpnetError(f"{what}: centres must be int32")
+    x = xyz.float().contiguous()
+    c = centres.contiguous()
+    N, S = x.shape[1], c.shape[1]
+    radii, nsamples = [float(r) for r in radii], [int(ns) for ns in nsamples]
+    for radius, nsample, tag in zip(radii, nsamples, tags):
+        if not (1 <= nsample <= _lib.SA_MAX_NSAMPLE):
+            raise IndexError(f"{what}: nsample={nsample} out of range [1, {_lib.SA_MAX_NSAMPLE}]{tag}")
+        if not radius >= 0.0:
+            raise _lib.AmpnetError(f"{what}: radius={radius} must be >= 0{tag}")
+    if S and (int(c.min()) < 0 or int(c.max()) >= N):
+        raise IndexError(f"{what}: centre index out of range")
+    return x, c, radii, nsamples
+
+
+def ball_query_msg(xyz, centres, radii, nsamples, return_counts=False):
+    """ball_query at K radii around the same centres in ONE launch (include/ampnet_hip.h: ampnet_ball_query_msg_f32): the grouping of a
+    multi-scale set-abstraction layer.  radii, nsamples: K values each, 1 <= K <= _lib.SA_MSG_MAX_SCALES, the radii in any order
+    -> a list of K int32 tensors [B, S, nsamples[k]], each bit for bit ball_query(xyz, centres, radii[k], nsamples[k]);
+    return_counts=True also returns the list of K int32 [B, S] counts.  The cloud is staged and walked once and the centres are validated
+    once (one read-back of their range where K ball_query calls make K); the argument rules and error types are ball_query's."""
+    radii, nsamples = list(radii), list(nsamples)
+    K = len(radii)
+    if len(nsamples) != K or not (1 <= K <= _lib.SA_MSG_MAX_SCALES):
+        raise _lib.AmpnetError(f"ball_query_msg: {K} radii and {len(nsamples)} nsamples, expected one of each for 1 .. "
+                               f"{_lib.SA_MSG_MAX_SCALES} scales")
+    x, c, radii, nsamples = _ball_query_args("ball_query_msg", xyz, centres, radii, nsamples, [f" (scale {k})" for k in range(K)])
+    B, S = c.shape
+    outs = [torch.empty((B, S, ns), dtype=torch.int32, device=x.device) for ns in nsamples]
+    counts = [torch.empty((B, S), dtype=torch.int32, device=x.device) for _ in nsamples] if return_counts else None
+    _lib.ball_query_msg_f32(x, c, radii, nsamples, outs, counts)
+    return (outs, counts) if return_counts else outs
 
 
 def three_nn(fine_xyz, coarse_xyz):

@@ -319,6 +319,20 @@ int ampnet_knn_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t 
 int ampnet_ball_query_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, float radius, int nsample,
                           int32_t *out, int32_t *count, void *stream);
 
+/* ---- ball query at K radii around the same centres (multi-scale grouping; added within ABI 17: a new symbol, nothing else moved) -----
+ *   xyz, n_clouds, n, ld, centres, s   as in ampnet_ball_query_f32
+ *   radii_host, nsample_host           HOST arrays [K], 1 <= K <= AMPNET_SA_MSG_MAX_SCALES; the radii in any order, equal ones allowed
+ *   out_host                           HOST array of K DEVICE pointers, out_host[k] is [n_clouds, s, nsample_host[k]] int32
+ *   count_host                         NULL, or a HOST array of K DEVICE pointers [n_clouds, s] int32 of which any may be NULL
+ * For every k, out_host[k] and count_host[k] are bit for bit what ampnet_ball_query_f32 (.., radii_host[k], nsample_host[k], ..) writes:
+ * the same d(j), r2_k = float32 (radius_k * radius_k) computed once per scale on the host, the boundary included, ascending index order,
+ * the padding repeating the list's own first member.  One launch stages the cloud once and walks it once per centre: d(j) is formed
+ * once per candidate and compared with every r2_k, and the walk ends with the step after which EVERY list is full.
+ * Limits per scale are those of ampnet_ball_query_f32; a message names the offending scale.                                        */
+#define AMPNET_SA_MSG_MAX_SCALES 4
+int ampnet_ball_query_msg_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const float *radii_host,
+                              const int *nsample_host, int K, int32_t *const *out_host, int32_t *const *count_host, void *stream);
+
 /* ---- one set-abstraction layer, eval mode, fused (stands in for PointNetSetAbstraction.forward of pointnetAtt.py:4,285-287) ---------
  *   xyz, centres          as in ampnet_ball_query_f32 (no limit on n here)
  *   group_idx             [n_clouds, s, nsample] int32 point indices (the output of ampnet_ball_query_f32), 1 <= nsample <= 64
@@ -342,6 +356,28 @@ int ampnet_ball_query_f32(const float *xyz, int n_clouds, int n, int ld, const i
 int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
                           int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
                           const float *eps_host, int L, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- K set-abstraction branches around the same centres in ONE launch (multi-scale grouping; added within ABI 17: new symbols) -------
+ *   xyz .. s, feats, D    as in ampnet_sa_forward_f32; every branch has cin_0 = 3 + D and that entry point's row [relative xyz, feats]
+ *   group_idx_host        HOST array of K DEVICE pointers, group_idx_host[k] is [n_clouds, s, nsample_host[k]] int32
+ *   nsample_host, L_host  HOST arrays [K]: branch k's group size and its number of layers; 1 <= K <= AMPNET_SA_MSG_MAX_SCALES
+ *   params_host (6 device pointers per layer), cout_host, eps_host   the branches' tables of ampnet_sa_forward_f32 laid end to end in
+ *                         branch order: sum_k L_host[k] layers
+ *   out                   [n_clouds, s, C] float32, C = sum_k cout_last_k; branch k owns the columns [off_k, off_k + cout_last_k),
+ *                         off_k = sum_{j<k} cout_last_j
+ *   workspace             ampnet_sa_msg_forward_workspace_bytes(K) = K * AMPNET_SA_WORKSPACE_BYTES device bytes (0 = K is refused):
+ *                         branch k's BatchNorm fold lies in the k-th region
+ * Branch k's column slice is bit for bit the `out` of ampnet_sa_forward_f32 on group_idx_host[k] with that branch's layers: the same
+ * plan, gather and layer code, only the destination row differs (out + g C + off_k).  After the K fold launches ONE kernel runs every
+ * branch: a workgroup belongs to one branch (taken from its index, so wave-uniform), stages that branch's weights once and walks that
+ * branch's groups; the dynamic LDS is the largest of the branches' needs.  No atomics; nothing grouped and no activation reaches memory;
+ * exact fp32 MFMA whatever the matrix precision is.  Limits per branch are those of ampnet_sa_forward_f32 (AMPNET_E_ARG otherwise); a
+ * message names the offending branch.                                                                                              */
+size_t ampnet_sa_msg_forward_workspace_bytes(int K);
+int ampnet_sa_msg_forward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s,
+                              const int32_t *const *group_idx_host, const int *nsample_host, const float *feats, int D,
+                              const float *const *params_host, const int *cout_host, const float *eps_host, const int *L_host, int K,
+                              float *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- 3 nearest coarse points of every fine point (BUILD-DEFINED like ampnet_knn_f32) ---------------------------------------------------
  * The neighbour search of a PointNet++ feature-propagation layer (the reference imports the layer from a package it does not ship,

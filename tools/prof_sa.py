@@ -22,7 +22,14 @@ sa_all_compact_kernel, the kernels of ampnet_sa_backward_f32 on the compacted wi
 torch's composition conv2d 1x1 + eval batch_norm + relu on [B, C, N, 1], then max (forward under no_grad, the backward of a retained graph),
 in alternating rounds, every round reported.  The backward works on the winners alone: its time should not grow with N.
 python3 tools/prof_sa.py [steps] [warmup] group_all        -- the group_all leg alone; prints one JSON line.
-python3 tools/prof_sa.py [steps] [warmup] group_all-trace  -- nothing but the fused group_all forward and backward, for a kernel trace."""
+python3 tools/prof_sa.py [steps] [warmup] group_all-trace  -- nothing but the fused group_all forward and backward, for a kernel trace.
+The msg leg: multi-scale grouping with two scales at B = 16, an sa1-like shape (this file's N = 8192 cloud, 1024 centres, radii (0.1, 0.2),
+nsample (16, 32), D = 9, [32, 32, 64] twice) and an sa3-like one (a 256-point cloud, 64 centres, radii (0.4, 0.8), nsample (16, 32), D = 128,
+[128, 128, 256] twice): (a) one utils.ball_query_msg (ball_query_msg_kernel) against two utils.ball_query calls, and the same pair again as
+bare kernels on preallocated outputs, without the helpers' validation of the centres; (b) one sa_msg_forward_f32 (two sa_fold_kernel launches,
+sa_msg_forward_kernel) against two sa_forward_f32 calls plus torch.cat.  Five alternating rounds, every round reported, medians quoted.
+python3 tools/prof_sa.py [steps] [warmup] msg        -- the msg leg alone; prints one JSON line.
+python3 tools/prof_sa.py [steps] [warmup] msg-trace  -- nothing but ball_query_msg and sa_msg_forward_f32, for a kernel trace."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -295,6 +302,65 @@ def group_all_leg(trace):
                          "max_rel_diff_vs_torch": diff}
     return res
 
+
+def msg_leg(trace):
+    """-> {"sa1_like": figures, "sa3_like": figures}: two scales around the same centres at B = 16, (a) one ball_query_msg against two
+    ball_query calls, (b) one sa_msg_forward_f32 against two sa_forward_f32 calls plus torch.cat -- the baselines are the single-scale
+    building blocks, never the new code."""
+    res = {}
+    pts3 = U.gather_rows(xyz, cent)                                           # sa2's cloud: sa1's 1024 centres
+    pts3 = U.gather_rows(pts3, U.fps_indices(pts3, 256))                      # sa3's cloud: sa2's 256 centres
+    for name, (pts, s_, radii, ks, d_, mlps) in {"sa1_like": (xyz, 1024, (0.1, 0.2), (16, 32), 9, [[32, 32, 64], [32, 32, 64]]),
+                                                 "sa3_like": (pts3, 64, (0.4, 0.8), (16, 32), 128, [[128, 128, 256], [128, 128, 256]])}.items():
+        n_, nb = pts.shape[1], len(radii)
+        f = torch.from_numpy(synth.uniform(250 + d_, (B, n_, d_), -1.0, 1.0)).to(dev)
+        c = cent if pts is xyz else U.fps_indices(pts, s_)
+        lays = [make_layers(3 + d_, mlp, 260 + i) for i, mlp in enumerate(mlps)]
+        eps = [[1e-5] * len(mlp) for mlp in mlps]
+        gis, cnts = U.ball_query_msg(pts, c, radii, ks, return_counts=True)
+        mws = torch.empty(L.sa_msg_forward_workspace_bytes(nb), dtype=torch.uint8, device=dev)
+        wss = [torch.empty(L.SA_WORKSPACE_BYTES, dtype=torch.uint8, device=dev) for _ in range(nb)]
+        o = torch.empty((B, s_, sum(mlp[-1] for mlp in mlps)), device=dev)
+        parts = [torch.empty((B, s_, mlp[-1]), device=dev) for mlp in mlps]
+        bq_msg = lambda: U.ball_query_msg(pts, c, radii, ks)
+        bq_each = lambda: [U.ball_query(pts, c, r, k_) for r, k_ in zip(radii, ks)]
+        sa_msg = lambda: L.sa_msg_forward_f32(pts, c, gis, f, lays, eps, o, mws)
+        # the two queries again without the helpers' validation (its read-back): the kernels alone, on preallocated outputs
+        raw_msg = lambda: L.ball_query_msg_f32(pts, c, radii, ks, gis)
+        raw_each = lambda: [L.ball_query_f32(pts, c, r, k_, gi) for r, k_, gi in zip(radii, ks, gis)]
+
+        def sa_each():
+            for gi, lay, e, part, w in zip(gis, lays, eps, parts, wss):
+                L.sa_forward_f32(pts, c, gi, f, lay, e, part, w)
+            return torch.cat(parts, dim=2)
+
+        if trace:
+            for _ in range(steps):
+                bq_msg()
+                sa_msg()
+            torch.cuda.synchronize()
+            continue
+        with torch.no_grad():
+            rounds = [(timed(bq_msg), timed(bq_each), timed(sa_msg), timed(sa_each), timed(raw_msg), timed(raw_each)) for _ in range(5)]
+            sa_msg()
+            same = bool(torch.equal(o, sa_each())) and all(bool(torch.equal(a, b_)) for a, b_ in zip(bq_msg(), bq_each()))
+        med = lambda q: sorted(r[q] for r in rounds)[len(rounds) // 2]
+        res[name] = {"shape": {"B": B, "N": n_, "npoint": s_, "radii": radii, "nsample": ks, "D": d_, "mlps": mlps},
+                     "mean_members": [round(float(t.float().mean()), 2) for t in cnts],
+                     "ball_query_msg_ms": round(med(0), 4), "ball_query_each_ms": round(med(1), 4),
+                     "sa_msg_forward_ms": round(med(2), 4), "sa_forward_each_plus_cat_ms": round(med(3), 4),
+                     "ball_query_msg_kernel_ms": round(med(4), 4), "ball_query_each_kernels_ms": round(med(5), 4),
+                     "each_over_msg_ball_query": round(med(1) / med(0), 2), "each_over_msg_forward": round(med(3) / med(2), 2),
+                     "each_over_msg_ball_query_kernels": round(med(5) / med(4), 2),
+                     "rounds_ms_bq_msg_bq_each_sa_msg_sa_each_kernel_msg_kernel_each": [[round(v, 4) for v in r] for r in rounds],
+                     "bitwise_equal_to_the_single_scale_calls": same}
+    return res
+
+
+if mode in ("msg", "msg-trace"):
+    r = msg_leg(mode == "msg-trace")
+    print(json.dumps({"trace_only": True, "msg_calls_per_shape": steps} if mode == "msg-trace" else {"msg": r}))
+    sys.exit(0)
 
 if mode in ("group_all", "group_all-trace"):
     r = group_all_leg(mode == "group_all-trace")

@@ -47,13 +47,13 @@ __device__ __forceinline__ void bnt_tile_stats(const float *x, int ldx, int m0, 
         float sum = 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-            if ((i & 3) + 8 * (i >> 2) + 4 * h < rows) sum += acc[t][i];
+            if (mlp_acc_row(i, h) < rows) sum += acc[t][i];
         sum += __shfl_xor(sum, 32);
         const float mean = sum / (float)rows;
         float q = 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-            if ((i & 3) + 8 * (i >> 2) + 4 * h < rows) {
+            if (mlp_acc_row(i, h) < rows) {
                 const float d = acc[t][i] - mean;
                 q = fmaf(d, d, q);
             }
@@ -89,7 +89,7 @@ __device__ __forceinline__ void bnt_form_dz(const float *x, int ldx, const float
         const float dsel = arg_g ? dout_g[col] : 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int row = mlp_acc_row(i, h);
             float dzv = 0.0f;
             if (row < rows) {
                 const float a = acc[t][i];
@@ -123,7 +123,7 @@ __device__ __forceinline__ void bnt_form_dy(const float *x, int ldx, const float
         float sb = 0.0f, sg = 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int row = mlp_acc_row(i, h);
             const float a = acc[t][i];
             float dy = 0.0f;
             if (row < rows) {

@@ -37,6 +37,12 @@ int allow_dynamic_lds(size_t lds, const char *who)
     do {                                                            \
         if (!(cond)) return ::ampnet::fail(AMPNET_E_ARG, __VA_ARGS__); \
     } while (0)
+// a step that returns AMPNET_OK or a failure's code (ampnet_last_error already set): the failure is the caller's result
+#define AMPNET_TRY(...)                                             \
+    do {                                                            \
+        const int try_rc_ = (__VA_ARGS__);                          \
+        if (try_rc_ != AMPNET_OK) return try_rc_;                   \
+    } while (0)
 
 // Optional per-kernel timing with HIP events on the launch stream (bench.py's roofline leg): off by default,
 // when on every instrumented launch is bracketed by two events; ampnet_profile_read() synchronises and sums.

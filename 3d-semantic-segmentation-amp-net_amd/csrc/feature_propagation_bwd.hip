@@ -64,7 +64,7 @@ __device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const flo
         float sb = 0.0f, sg = 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int row = mlp_acc_row(i, h);
             const float a = acc[t][i];
             float din;
             if (dout) din = row < rows ? dout[(size_t)row * cout + col] : 0.0f;
@@ -244,8 +244,7 @@ extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float 
     MlpPlan p;
     MlpFold f;
     if (!mlp_plan_build(what, D1 + D2, 32, params_host, cout_host, eps_host, L, p, f)) return AMPNET_E_ARG;
-    p.nw = 1;
-    for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // this kernel stages no weights: every layer is read through L2
+    mlp_plan_unstaged(p);
     // the tiles X_0 .. X_L
     FpBwdPlan b = {};
     int floats = 0;

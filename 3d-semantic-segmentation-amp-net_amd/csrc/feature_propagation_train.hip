@@ -304,8 +304,7 @@ extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const 
     MlpPlan p;
     MlpFold f;
     if (!mlp_plan_build(what, D1 + D2, 32, params_host, cout_host, eps_host, L, p, f)) return AMPNET_E_ARG;
-    p.nw = 1;
-    for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // these kernels stage no weights: every layer is read through L2
+    mlp_plan_unstaged(p);
     float *ws = static_cast<float *>(workspace);
     BntBwd b;
     const size_t lds = bnt_bwd_plan(p, f, sh, ws, off_coef, b);

@@ -3,7 +3,7 @@
 //
 //   * A wave owns R = 32 or 64 rows; 32 of them are the M tile of v_mfma_f32_32x32x2_f32 (exact fp32: the matrix-precision scope is not
 //     consulted).  Lane (r = l & 31, h = l >> 5) supplies row r of A and row n0 + r of W, the accumulator holds column n0 + r of rows
-//     (i & 3) + 8 (i >> 2) + 4 h, i < 16.  The ORDER of the contraction inside a block of 8 is the caller's (KORDER): it fixes the
+//     mlp_acc_row(i, h), i < 16.  The ORDER of the contraction inside a block of 8 is the caller's (KORDER): it fixes the
 //     summation order and so the bits.  K_PAIRS: k-step i < 4 takes k = k0 + 2 i + h.  K_QUADS: k = k0 + 4 h + i, a lane's four weights are
 //     16 contiguous bytes, and unstaged weights with cin a multiple of 8 (plan.w_vec) are read with one global_load_dwordx4 per lane and
 //     block, a quarter of the cache lines per MFMA that four strided dwords touch.
@@ -29,6 +29,9 @@ constexpr int MLP_LDS_BYTES = 160 * 1024;
 static_assert(AMPNET_FP_MAX_LAYERS == MLP_MAX_LAYERS && AMPNET_FP_MAX_COUT == MLP_MAX_COUT, "one plan and one fold serve both forwards");
 
 enum { K_PAIRS, K_QUADS };
+
+// the lane map of the header, once: the row (of the 32-row tile) that accumulator register i < 16 of lane half h holds
+__device__ __forceinline__ constexpr int mlp_acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 struct MlpPlan {
     int L, nw, R;                         // layers, waves per workgroup, rows of a wave's tile (32 / 64)
@@ -57,6 +60,12 @@ int mlp_allow_full_lds(const char *what, const void *kernel, bool &done);
 // Every workgroup stages the weights once: at most 4 workgroups per CU's worth of them, each wave walking several items (groups, row
 // tiles).  This is min(cdiv(items, nw), 1024), written so that items near 2^31 do not overflow.
 inline int mlp_grid(int items, int nw) { return items / nw >= 1024 ? 1024 : cdiv(items, nw); }
+// the plan of a kernel that is one wave per workgroup and stages no weights: every layer is read through L2
+inline void mlp_plan_unstaged(MlpPlan &p)
+{
+    p.nw = 1;
+    for (int l = 0; l < p.L; ++l) p.w_off[l] = -1;
+}
 
 // orders a wave's own LDS writes before its later LDS reads (every tile is private to one wave)
 __device__ __forceinline__ void wave_lds_sync()
@@ -117,7 +126,7 @@ __device__ __forceinline__ const float *mlp_operand(const float *x, int ldx, int
 // max, its statistics) runs this one loop; it is mlp_tiles' loop below, statement for statement, and the two must stay so.  (mlp_tiles does
 // not call it: hipcc lays the forward kernels' blocks out differently when the loop arrives through a call, and the forward stays as it
 // was tuned.)  w: weights [cout][ldw], k_valid = columns of w that exist (the rest of kp counts as zero); VEC: 16-byte aligned rows,
-// k_valid == kp.  Lane (r, h) ends with column n0 + 32 t + r of rows (i & 3) + 8 (i >> 2) + 4 h in acc[t][i].
+// k_valid == kp.  Lane (r, h) ends with column n0 + 32 t + r of row mlp_acc_row(i, h) in acc[t][i].
 template <int NT, int KORDER, bool VEC>
 __device__ __forceinline__ void mlp_accumulate(f32x16 (&acc)[NT], const float *xr, const float *__restrict__ w, int ldw, int k_valid, int kp, int n0,
                                                int r, int h)
@@ -204,7 +213,7 @@ __device__ __forceinline__ void mlp_tiles(const float *x, int ldx, const float *
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-                ep.put(st[t], dst, m0 + (i & 3) + 8 * (i >> 2) + 4 * h, n0 + 32 * t + r, fmaxf(fmaf(acc[t][i], sc[t], sh[t]), 0.0f));
+                ep.put(st[t], dst, m0 + mlp_acc_row(i, h), n0 + 32 * t + r, fmaxf(fmaf(acc[t][i], sc[t], sh[t]), 0.0f));
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) ep.done(st[t], dst, n0 + 32 * t + r, h);

@@ -108,7 +108,7 @@ __device__ __forceinline__ void mlp_dgrad(const float *d, int ldd, const float *
         const int c = c0 + 32 * t + r;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int row = mlp_acc_row(i, h);
             if (xo) {
                 if (c < cin) xo[row * ldxo + c] = acc[t][i];
             } else if (DROP_D1) {

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(64) void fp_wgrad_kernel(const float *__restrict__ 
     for (int t = 0; t < 4; ++t)
         if (c0 + 32 * t < ldxs)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) dst[(size_t)(o0 + (i & 3) + 8 * (i >> 2) + 4 * h) * ldxs + c0 + 32 * t + r] = acc[t][i];
+            for (int i = 0; i < 16; ++i) dst[(size_t)(o0 + mlp_acc_row(i, h)) * ldxs + c0 + 32 * t + r] = acc[t][i];
 }
 
 __global__ void fp_wgrad_reduce_kernel(const float *__restrict__ part, int chunks, int cout, int cin, int ldxs, float *__restrict__ dW)

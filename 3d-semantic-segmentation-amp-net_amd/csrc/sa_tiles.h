@@ -44,6 +44,39 @@ struct SaMax {
     }
 };
 
+// The last layer's max WITH ITS ROW, one column of one lane: what the backwards and the whole-cloud forward keep where SaMax keeps a float.
+// THE TIE RULE, stated here and nowhere else: of the rows that attain the largest y = relu(fma(a, scale, shift)) the LOWEST wins.  A lane
+// offers its rows in ascending order (row tiles ascending, mlp_acc_row(i, h) ascending in i) and put() takes a row only on a strict >, so
+// an equal later row never replaces an earlier one; merge_halves() joins the two lane halves of a column with one __shfl_xor(., 32) per
+// member and hands a tie to the lower row, after which both halves hold the same winner.  Rows that are bit-identical copies of an earlier
+// row (tile padding, the slots ball query filled by repeating its first member) therefore never win.  The forward's `arg`, the backward's
+// routing of dout and the Python references' check_argmax all rest on this rule.  `a` is the winner's raw accumulator; a caller that never
+// reads it (the whole-cloud forward) pays nothing for it.
+struct SaArgMax {
+    float best;
+    int row;                              // (between the floats: the order in which hipcc emits sa_backward_kernel's selects, as before)
+    float a;
+    __device__ __forceinline__ void init() { best = -INFINITY; row = 0; a = 0.0f; }
+    __device__ __forceinline__ void put(float a_, float y, int row_)
+    {
+        if (y > best) {
+            best = y;
+            row = row_;
+            a = a_;
+        }
+    }
+    __device__ __forceinline__ void merge_halves()
+    {
+        const float ob = __shfl_xor(best, 32), oa = __shfl_xor(a, 32);
+        const int orow = __shfl_xor(row, 32);
+        if (ob > best || (ob == best && orow < row)) {
+            best = ob;
+            row = orow;
+            a = oa;
+        }
+    }
+};
+
 // The 32-row-tile variant: rows m0 .. m0 + 31 of a group (group_g: its nsample indices; cx, cy, cz: its centre) into `tile` [32][ld].
 // Unlike sa_gather_group it ZEROES the rows past `rows` instead of repeating row 0: its callers sum over the rows they store.
 __device__ __forceinline__ void sat_gather_rows(float *tile, int ld, int kp0, int cin0, const float *__restrict__ cloud, int ldc,
@@ -69,6 +102,21 @@ struct SaBwdShape : MlpBwdLayout {
     int R, n_groups, grid, chunk_rows, chunks, lds_floats;
     int off_x[MLP_MAX_LAYERS + 1], ld_x[MLP_MAX_LAYERS + 1];
 };
+
+// The host rules that several entry points state, each ONCE (set_abstraction.hip).  `what`, the entry point's name, opens the message; the
+// result is AMPNET_OK or the failure's code with ampnet_last_error set.
+// The limits: n_clouds * count below 2^31 (count = s, the groups; group_all: n, the rows), nsample (not with group_all), L, 3 + D.
+// `who` names the branch whose nsample and L these are where that is not the entry point (multi-scale grouping).
+int sa_check_limits(const char *what, int D, int n_clouds, int count, int nsample, int L, bool group_all, const char *who = nullptr);
+// the features: feats NULL exactly when D = 0, dfeats (a forward passes nullptr) NULL when D = 0
+int sa_check_feats(const char *what, const float *feats, int D, const float *dfeats);
+// the cloud of the grouped backwards and the train forward, n >= 1 and ld >= 3, then sa_check_feats.  (The eval forwards refuse n and ld
+// in one message with n_clouds and s, group_all words its own: those lines stay where they are, ahead of sa_check_feats.)
+int sa_check_cloud(const char *what, int n, int ld, const float *feats, int D, const float *dfeats);
+// the host tables of a backward: no null among the 6 L parameters (params_host = nullptr: mlp_plan_build will say so under the same
+// name) nor among the 4 L gradient pointers
+int sa_check_tables(const char *what, const float *const *params_host, float *const *grads_host, int L);
+int sa_check_workspace(const char *what, const void *workspace, size_t workspace_bytes, size_t need);
 
 // checks the shape against the forward's limits and the LDS limit of sa_backward_kernel (`what` opens every message) and fills sh
 int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SaBwdShape &sh);

@@ -39,12 +39,52 @@ int sa_forward_launch(const char *what, const MlpPlan &p, int lds, const float *
                       const int32_t *group_idx, int nsample, const float *feats, int D, const float *fold, float *out, hipStream_t st)
 {
     static bool attr_set = false;
-    int rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_forward_kernel), attr_set);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_forward_kernel), attr_set));
     const int n_groups = n_clouds * s;
     hipLaunchKernelGGL(sa_forward_kernel, dim3(mlp_grid(n_groups, p.nw)), dim3(64 * p.nw), lds, st, p, xyz, n, ld, centres, s, group_idx, nsample,
                        feats, D, fold, n_groups, out);
     return check_launch("sa_forward_kernel");
+}
+
+// ---- the host rules of the set-abstraction entry points, each stated once (sa_tiles.h says who calls what) ----------------------------
+
+int sa_check_limits(const char *what, int D, int n_clouds, int count, int nsample, int L, bool group_all, const char *who)
+{
+    if (!who) who = what;
+    const long long total = (long long)n_clouds * count;
+    AMPNET_REQUIRE(total <= 0x7fffffffLL, "%s: n_clouds * %s = %lld %s exceed 2^31 - 1", what, group_all ? "n" : "s", total, group_all ? "rows" : "groups");
+    if (!group_all)
+        AMPNET_REQUIRE(nsample >= 1 && nsample <= AMPNET_SA_MAX_NSAMPLE, "%s: nsample=%d must be in [1, %d]", who, nsample, AMPNET_SA_MAX_NSAMPLE);
+    AMPNET_REQUIRE(L >= 1 && L <= AMPNET_SA_MAX_LAYERS, "%s: L=%d layers, the kernel is built for 1 .. %d", who, L, AMPNET_SA_MAX_LAYERS);
+    AMPNET_REQUIRE(D >= 0 && 3 + D <= AMPNET_SA_MAX_CIN, "%s: cin_0 = 3 + D = %d exceeds %d", what, 3 + D, AMPNET_SA_MAX_CIN);
+    return AMPNET_OK;
+}
+
+int sa_check_feats(const char *what, const float *feats, int D, const float *dfeats)
+{
+    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
+    AMPNET_REQUIRE(D > 0 || dfeats == nullptr, "%s: dfeats must be NULL when D = 0", what);
+    return AMPNET_OK;
+}
+
+int sa_check_cloud(const char *what, int n, int ld, const float *feats, int D, const float *dfeats)
+{
+    AMPNET_REQUIRE(n >= 1 && ld >= 3, "%s: bad shape n=%d ld=%d", what, n, ld);
+    return sa_check_feats(what, feats, D, dfeats);
+}
+
+int sa_check_tables(const char *what, const float *const *params_host, float *const *grads_host, int L)
+{
+    if (params_host)
+        for (int q = 0; q < 6 * L; ++q) AMPNET_REQUIRE(params_host[q], "%s: null parameter %d of layer %d", what, q % 6, q / 6);
+    for (int q = 0; q < 4 * L; ++q) AMPNET_REQUIRE(grads_host[q], "%s: null gradient pointer %d of layer %d", what, q % 4, q / 4);
+    return AMPNET_OK;
+}
+
+int sa_check_workspace(const char *what, const void *workspace, size_t workspace_bytes, size_t need)
+{
+    AMPNET_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, need %zu", what, workspace_bytes, need);
+    return AMPNET_OK;
 }
 
 }  // namespace ampnet
@@ -54,22 +94,17 @@ extern "C" int ampnet_sa_forward_f32(const float *xyz, int n_clouds, int n, int 
                                      const float *eps_host, int L, float *out, void *workspace, size_t workspace_bytes, void *stream)
 {
     using namespace ampnet;
-    AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && out, "ampnet_sa_forward_f32: null pointer");
-    AMPNET_REQUIRE(n_clouds >= 1 && n >= 1 && ld >= 3 && s >= 1, "ampnet_sa_forward_f32: bad shape n_clouds=%d n=%d ld=%d s=%d", n_clouds, n, ld, s);
-    AMPNET_REQUIRE((long long)n_clouds * s <= 0x7fffffffLL, "ampnet_sa_forward_f32: n_clouds * s = %lld groups exceed 2^31 - 1", (long long)n_clouds * s);
-    AMPNET_REQUIRE(nsample >= 1 && nsample <= AMPNET_SA_MAX_NSAMPLE, "ampnet_sa_forward_f32: nsample=%d must be in [1, %d]", nsample, AMPNET_SA_MAX_NSAMPLE);
-    AMPNET_REQUIRE(L >= 1 && L <= AMPNET_SA_MAX_LAYERS, "ampnet_sa_forward_f32: L=%d layers, the kernel is built for 1 .. %d", L, AMPNET_SA_MAX_LAYERS);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "ampnet_sa_forward_f32: feats must be NULL exactly when D = 0 (D=%d)", D);
-    AMPNET_REQUIRE(3 + D <= AMPNET_SA_MAX_CIN, "ampnet_sa_forward_f32: cin_0 = 3 + D = %d exceeds %d", 3 + D, AMPNET_SA_MAX_CIN);
-    AMPNET_REQUIRE(workspace && workspace_bytes >= AMPNET_SA_WORKSPACE_BYTES, "ampnet_sa_forward_f32: workspace of %zu bytes, need %d",
-                   workspace_bytes, AMPNET_SA_WORKSPACE_BYTES);
+    const char *what = "ampnet_sa_forward_f32";
+    AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && out, "%s: null pointer", what);
+    AMPNET_REQUIRE(n_clouds >= 1 && n >= 1 && ld >= 3 && s >= 1, "%s: bad shape n_clouds=%d n=%d ld=%d s=%d", what, n_clouds, n, ld, s);
+    AMPNET_TRY(sa_check_feats(what, feats, D, nullptr));
+    AMPNET_TRY(sa_check_limits(what, D, n_clouds, s, nsample, L, false));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, AMPNET_SA_WORKSPACE_BYTES));
     MlpPlan p;
     MlpFold f;
-    const int lds = mlp_plan_build("ampnet_sa_forward_f32", 3 + D, nsample <= 32 ? 32 : 64, params_host, cout_host, eps_host, L, p, f);
+    const int lds = mlp_plan_build(what, 3 + D, nsample <= 32 ? 32 : 64, params_host, cout_host, eps_host, L, p, f);
     if (!lds) return AMPNET_E_ARG;
     float *fold = static_cast<float *>(workspace);
-    int rc = mlp_fold_launch(p, f, fold, (hipStream_t)stream);
-    if (rc != AMPNET_OK) return rc;
-    return sa_forward_launch("ampnet_sa_forward_f32", p, lds, xyz, n_clouds, n, ld, centres, s, group_idx, nsample, feats, D, fold, out,
-                             (hipStream_t)stream);
+    AMPNET_TRY(mlp_fold_launch(p, f, fold, (hipStream_t)stream));
+    return sa_forward_launch(what, p, lds, xyz, n_clouds, n, ld, centres, s, group_idx, nsample, feats, D, fold, out, (hipStream_t)stream);
 }

@@ -8,8 +8,8 @@
 //   sa_all_forward_kernel      A wave owns a TILE of 32 consecutive rows of one cloud: it loads them straight into its LDS tile (rows past n
 //       repeat the tile's first row, which can neither change a max nor win an argmax), runs layers 0 .. L-2 with the forward's own code
 //       (mlp_dispatch<K_PAIRS>) and the last layer's raw accumulator with mlp_accumulate, the loop every backward uses to find the
-//       forward's bits again: the epilogue of mlp_run carries ONE float per column, and this one needs the maximum and its row.  A lane
-//       walks its 16 rows in ascending order with a strict >, the two lane halves are combined with the lower row winning a tie.
+//       forward's bits again: the epilogue of mlp_run carries ONE float per column, and this one needs the maximum and its row, a
+//       SaArgMax per column (sa_tiles.h: the walk within a tile, and the rule that the LOWEST row wins a tie).
 //       A cloud's cdiv(n, 32) tiles are dealt to at most SAA_MAX_RUNS RUNS of consecutive tiles; a wave walks the tiles of a run in
 //       ascending order and keeps the run's (max, row) per column in ITS row of the workspace, every word read and written by one lane only,
 //       again with a strict >.
@@ -49,9 +49,7 @@ static int saa_check(const char *what, int D, int n_clouds, int n, const int *co
 {
     AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
     AMPNET_REQUIRE(n_clouds >= 1 && n >= 1, "%s: bad shape n_clouds=%d n=%d (both must be >= 1)", what, n_clouds, n);
-    AMPNET_REQUIRE((long long)n_clouds * n <= 0x7fffffffLL, "%s: n_clouds * n = %lld rows exceed 2^31 - 1", what, (long long)n_clouds * n);
-    AMPNET_REQUIRE(L >= 1 && L <= AMPNET_SA_MAX_LAYERS, "%s: L=%d layers, the kernel is built for 1 .. %d", what, L, AMPNET_SA_MAX_LAYERS);
-    AMPNET_REQUIRE(D >= 0 && 3 + D <= AMPNET_SA_MAX_CIN, "%s: cin_0 = 3 + D = %d exceeds %d", what, 3 + D, AMPNET_SA_MAX_CIN);
+    AMPNET_TRY(sa_check_limits(what, D, n_clouds, n, 0, L, true));
     for (int l = 0; l < L; ++l)
         AMPNET_REQUIRE(cout_host[l] >= 32 && cout_host[l] <= AMPNET_SA_MAX_COUT && cout_host[l] % 32 == 0,
                        "%s: layer %d has cout=%d, must be a multiple of 32 in [32, %d]", what, l, cout_host[l], AMPNET_SA_MAX_COUT);
@@ -60,8 +58,7 @@ static int saa_check(const char *what, int D, int n_clouds, int n, const int *co
 
 static int saa_shape(const char *what, int D, int n_clouds, int n, const int *cout_host, int L, SaAllShape &sh)
 {
-    const int rc = saa_check(what, D, n_clouds, n, cout_host, L);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(saa_check(what, D, n_clouds, n, cout_host, L));
     sh = {};
     sh.tiles = cdiv(n, 32);
     sh.runs = sh.tiles < SAA_MAX_RUNS ? sh.tiles : SAA_MAX_RUNS;
@@ -102,27 +99,16 @@ __device__ __forceinline__ void saa_last(const float *x, int ldx, const float *w
     for (int t = 0; t < NT; ++t) {
         const int col = n0 + 32 * t + r;
         const float sc = scale[col], sh = shift[col];
-        float best = -INFINITY;
-        int brow = 0;
+        SaArgMax am;
+        am.init();
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;                       // ascending in i: `>` keeps the lowest row
-            const float y = fmaxf(fmaf(acc[t][i], sc, sh), 0.0f);
-            if (y > best) {
-                best = y;
-                brow = row;
-            }
-        }
-        const float ob = __shfl_xor(best, 32);
-        const int orow = __shfl_xor(brow, 32);
-        if (ob > best || (ob == best && orow < brow)) {
-            best = ob;
-            brow = orow;
-        }
+        for (int i = 0; i < 16; ++i)                                           // (the rows ascend with i, as SaArgMax asks)
+            am.put(acc[t][i], fmaxf(fmaf(acc[t][i], sc, sh), 0.0f), mlp_acc_row(i, h));
+        am.merge_halves();
         // rows past n repeat tile row 0 and lose the tie to it; an earlier tile of the run keeps a tie too
-        if (h == 0 && (first || best > pm[col])) {
-            pm[col] = best;
-            pa[col] = j0 + brow;
+        if (h == 0 && (first || am.best > pm[col])) {
+            pm[col] = am.best;
+            pa[col] = j0 + am.row;
         }
     }
 }
@@ -215,8 +201,7 @@ struct SaAllBwdShape {
 
 static int saa_bwd_shape(const char *what, int D, int n_clouds, int n, const int *cout_host, int L, SaAllBwdShape &sh)
 {
-    const int rc = saa_check(what, D, n_clouds, n, cout_host, L);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(saa_check(what, D, n_clouds, n, cout_host, L));
     sh = {};
     sh.C = cout_host[L - 1];
     sh.K = sh.C / SAA_CHUNK;
@@ -324,12 +309,10 @@ extern "C" int ampnet_sa_all_forward_f32(const float *xyz, int n_clouds, int n, 
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && params_host && cout_host && eps_host && out, "%s: null pointer", what);
     AMPNET_REQUIRE(ld >= 3, "%s: bad shape ld=%d (must be >= 3)", what, ld);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
     SaAllShape sh;
-    int rc = saa_shape(what, D, n_clouds, n, cout_host, L, sh);
-    if (rc != AMPNET_OK) return rc;
-    AMPNET_REQUIRE(workspace && workspace_bytes >= sh.floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
-                   sh.floats * sizeof(float));
+    AMPNET_TRY(sa_check_feats(what, feats, D, nullptr));
+    AMPNET_TRY(saa_shape(what, D, n_clouds, n, cout_host, L, sh));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, sh.floats * sizeof(float)));
     MlpPlan p;
     MlpFold f;
     const int lds = mlp_plan_build(what, 3 + D, 32, params_host, cout_host, eps_host, L, p, f);
@@ -338,14 +321,11 @@ extern "C" int ampnet_sa_all_forward_f32(const float *xyz, int n_clouds, int n, 
     float *pmax = ws + sh.off_pmax;
     int32_t *parg = reinterpret_cast<int32_t *>(ws + sh.off_parg);
     static bool attr_set = false;
-    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_all_forward_kernel), attr_set);
-    if (rc != AMPNET_OK) return rc;
-    rc = mlp_fold_launch(p, f, ws, st);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_all_forward_kernel), attr_set));
+    AMPNET_TRY(mlp_fold_launch(p, f, ws, st));
     hipLaunchKernelGGL(sa_all_forward_kernel, dim3(mlp_grid(sh.items, p.nw)), dim3(64 * p.nw), lds, st, p, xyz, n, ld, feats, D, ws, sh.tiles,
                        sh.runs, sh.items, pmax, parg);
-    rc = check_launch("sa_all_forward_kernel");
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(check_launch("sa_all_forward_kernel"));
     const int total = n_clouds * p.cout[L - 1];
     hipLaunchKernelGGL(sa_all_reduce_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, pmax, parg, sh.runs, p.cout[L - 1], total, out, arg_out);
     return check_launch("sa_all_reduce_kernel");
@@ -369,15 +349,11 @@ extern "C" int ampnet_sa_all_backward_f32(const float *xyz, int n_clouds, int n,
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && params_host && cout_host && eps_host && arg && dout && grads_host, "%s: null pointer", what);
     AMPNET_REQUIRE(ld >= 3, "%s: bad shape ld=%d (must be >= 3)", what, ld);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
-    AMPNET_REQUIRE(D > 0 || dfeats == nullptr, "%s: dfeats must be NULL when D = 0", what);
     SaAllBwdShape sh;
-    int rc = saa_bwd_shape(what, D, n_clouds, n, cout_host, L, sh);
-    if (rc != AMPNET_OK) return rc;
-    for (int q = 0; q < 6 * L; ++q) AMPNET_REQUIRE(params_host[q], "%s: null parameter %d of layer %d", what, q % 6, q / 6);
-    for (int q = 0; q < 4 * L; ++q) AMPNET_REQUIRE(grads_host[q], "%s: null gradient pointer %d of layer %d", what, q % 4, q / 4);
-    AMPNET_REQUIRE(workspace && workspace_bytes >= sh.floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
-                   sh.floats * sizeof(float));
+    AMPNET_TRY(sa_check_feats(what, feats, D, dfeats));
+    AMPNET_TRY(saa_bwd_shape(what, D, n_clouds, n, cout_host, L, sh));
+    AMPNET_TRY(sa_check_tables(what, params_host, grads_host, L));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, sh.floats * sizeof(float)));
     float *ws = static_cast<float *>(workspace);
     int32_t *wrow = reinterpret_cast<int32_t *>(ws + sh.off_wrow), *centres = reinterpret_cast<int32_t *>(ws + sh.off_centres);
     int32_t *gidx = reinterpret_cast<int32_t *>(ws + sh.off_gidx);
@@ -385,10 +361,9 @@ extern "C" int ampnet_sa_all_backward_f32(const float *xyz, int n_clouds, int n,
     float *dfeats_mini = dfeats ? ws + sh.off_dfeats : nullptr;
     hipLaunchKernelGGL(sa_all_compact_kernel, dim3(n_clouds), dim3(256), 0, st, xyz, n, ld, feats, D, arg, dout, sh.C, wrow, mxyz, mfeats, centres,
                        gidx, dout_k);
-    rc = check_launch("sa_all_compact_kernel");
-    if (rc != AMPNET_OK) return rc;
-    rc = ampnet_sa_backward_f32(mxyz, n_clouds, sh.n_mini, 3, centres, sh.K, gidx, SAA_CHUNK, mfeats, D, params_host, cout_host, eps_host, L, dout_k,
-                                dfeats_mini, grads_host, nullptr, ws + sh.off_inner, sh.inner_bytes, stream);
+    AMPNET_TRY(check_launch("sa_all_compact_kernel"));
+    const int rc = ampnet_sa_backward_f32(mxyz, n_clouds, sh.n_mini, 3, centres, sh.K, gidx, SAA_CHUNK, mfeats, D, params_host, cout_host, eps_host, L, dout_k,
+                                          dfeats_mini, grads_host, nullptr, ws + sh.off_inner, sh.inner_bytes, stream);
     if (rc != AMPNET_OK || !dfeats) return rc;
     if (hipMemsetAsync(dfeats, 0, (size_t)n_clouds * n * D * sizeof(float), st) != hipSuccess)
         return fail(AMPNET_E_LAUNCH, "%s: memset of dfeats failed", what);

@@ -12,10 +12,10 @@
 //       dz in place in X_{l+1}, and dx_l = dz W overwrites X_l.  L + 1 tiles of R rows: at R = 32 every shape of the forward fits the 160 KB
 //       (cin_0 = 320 with three layers of 256: 140 KB); at R = 64 the shapes whose tiles do not fit are refused.
 //       The max.  In the last layer a lane holds, per row tile, column c of 16 rows in its accumulator; it keeps the largest relu(y), the
-//       LOWEST row that attains it and that row's a while it walks the rows in ascending order (strict >), over both row tiles; the two
-//       lane halves are combined with one __shfl_xor(., 32) each, the lower row winning a tie.  Rows past nsample and the slots ball query
-//       filled by repeating its first member are bit-identical to an earlier row and never win.  dz of the last layer is zero except at
-//       (winner, c), where it is dout[g, c] scale if the winner's y > 0: the lane that owns that element writes it.
+//       row that attains it and that row's a over both row tiles in a SaArgMax (sa_tiles.h: the walk, and the rule that the LOWEST row
+//       wins a tie).  Rows past nsample and the slots ball query filled by repeating its first member are bit-identical to an earlier row
+//       and never win.  dz of the last layer is zero except at (winner, c), where it is dout[g, c] scale if the winner's y > 0: the walk
+//       stores the zeros as it goes, and the lane that stored the winner's zero writes the value over it.
 //       The wave stores x_l and dz_l of its nsample real rows to the workspace (dW below) and adds its per-channel sums of dy and dy a
 //       (rows in the accumulator's order, row tiles ascending, lane half 0 before half 1, groups ascending) into ITS OWN row of a partials
 //       array: every element is read and written by the same lane only.  dx_0's columns [3, cin_0) go to the workspace for the gather
@@ -59,7 +59,7 @@ __device__ __forceinline__ void sab_hidden(const float *x, int ldx, const float 
             const int col = n0 + 32 * t + r;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;   // mlp_acc_row(i, h), spelled out with m0 first: see sab_last
                 const float a = acc[t][i];
                 const float dy = fmaf(a, sc[t], sh[t]) > 0.0f ? d[row * ldd + col] : 0.0f;
                 sb[t] += dy;
@@ -81,8 +81,8 @@ __device__ __forceinline__ void sab_hidden(const float *x, int ldx, const float 
     }
 }
 
-// The last layer: the max over the group's rows, its row, and dz = dout scale at that row alone.  dout_g, arg_g: the group's row of
-// dout / arg_out (arg_g may be null).
+// The last layer: the max over the group's rows and its row (SaArgMax), and dz = dout scale at that row alone.  dout_g, arg_g: the group's
+// row of dout / arg_out (arg_g may be null).
 template <int NT>
 __device__ __forceinline__ void sab_last(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
                                          const float *__restrict__ scale, const float *__restrict__ shift, float *d, int ldd, int R,
@@ -90,15 +90,13 @@ __device__ __forceinline__ void sab_last(const float *x, int ldx, const float *_
                                          float *part_g, int32_t *__restrict__ arg_g, int lane)
 {
     const int r = lane & 31, h = lane >> 5;
-    float sc[NT], sh[NT], best[NT], ba[NT];
-    int brow[NT];
+    float sc[NT], sh[NT];
+    SaArgMax am[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         sc[t] = scale[n0 + 32 * t + r];
         sh[t] = shift[n0 + 32 * t + r];
-        best[t] = -INFINITY;
-        ba[t] = 0.0f;
-        brow[t] = 0;
+        am[t].init();
     }
     for (int m0 = 0; m0 < R; m0 += 32) {
         f32x16 acc[NT];
@@ -108,13 +106,12 @@ __device__ __forceinline__ void sab_last(const float *x, int ldx, const float *_
             const int col = n0 + 32 * t + r;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;              // ascending in (m0, i): `>` keeps the lowest row
+                // m0 + mlp_acc_row(i, h), ascending in (m0, i) as SaArgMax asks.  Spelled out here, in sab_hidden and in sat_last: hipcc
+                // folds the row into the stores' address arithmetic in the order the sum is written, and m0 + (the helper's sum) costs this
+                // kernel other instructions than (m0 + ..) + 4 h does.
+                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;
                 const float a = acc[t][i], y = fmaxf(fmaf(a, sc[t], sh[t]), 0.0f);
-                if (y > best[t]) {
-                    best[t] = y;
-                    brow[t] = row;
-                    ba[t] = a;
-                }
+                am[t].put(a, y, row);
                 d[row * ldd + col] = 0.0f;
                 if (row < nsample) dz_ws[(size_t)row * cout + col] = 0.0f;
             }
@@ -123,23 +120,17 @@ __device__ __forceinline__ void sab_last(const float *x, int ldx, const float *_
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int col = n0 + 32 * t + r;
-        const float ob = __shfl_xor(best[t], 32), oa = __shfl_xor(ba[t], 32);
-        const int orow = __shfl_xor(brow[t], 32);
-        if (ob > best[t] || (ob == best[t] && orow < brow[t])) {
-            best[t] = ob;
-            brow[t] = orow;
-            ba[t] = oa;
-        }
-        // both halves agree now; rows past nsample repeat row 0 and lose the tie to it
-        const float dy = best[t] > 0.0f ? dout_g[col] : 0.0f, dzv = dy * sc[t];
-        if ((((brow[t] & 31) >> 2) & 1) == h) {   // the lane that wrote this element's zero above
-            d[brow[t] * ldd + col] = dzv;
-            if (brow[t] < nsample) dz_ws[(size_t)brow[t] * cout + col] = dzv;
+        am[t].merge_halves();                     // both halves agree now; rows past nsample repeat row 0 and lose the tie to it
+        const int brow = am[t].row;
+        const float dy = am[t].best > 0.0f ? dout_g[col] : 0.0f, dzv = dy * sc[t];
+        if ((((brow & 31) >> 2) & 1) == h) {      // the lane that wrote this element's zero above
+            d[brow * ldd + col] = dzv;
+            if (brow < nsample) dz_ws[(size_t)brow * cout + col] = dzv;
         }
         if (h == 0) {
             part_b[col] += dy;
-            part_g[col] += dy * ba[t];
-            if (arg_g) arg_g[col] = brow[t];
+            part_g[col] += dy * am[t].a;
+            if (arg_g) arg_g[col] = brow;
         }
     }
 }
@@ -239,19 +230,15 @@ int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const i
 {
     AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
     AMPNET_REQUIRE(n_clouds >= 1 && s >= 1, "%s: bad shape n_clouds=%d s=%d", what, n_clouds, s);
-    AMPNET_REQUIRE((long long)n_clouds * s <= 0x7fffffffLL, "%s: n_clouds * s = %lld groups exceed 2^31 - 1", what, (long long)n_clouds * s);
-    AMPNET_REQUIRE(nsample >= 1 && nsample <= AMPNET_SA_MAX_NSAMPLE, "%s: nsample=%d must be in [1, %d]", what, nsample, AMPNET_SA_MAX_NSAMPLE);
-    AMPNET_REQUIRE(L >= 1 && L <= AMPNET_SA_MAX_LAYERS, "%s: L=%d layers, the kernel is built for 1 .. %d", what, L, AMPNET_SA_MAX_LAYERS);
-    AMPNET_REQUIRE(D >= 0 && 3 + D <= AMPNET_SA_MAX_CIN, "%s: cin_0 = 3 + D = %d exceeds %d", what, 3 + D, AMPNET_SA_MAX_CIN);
+    AMPNET_TRY(sa_check_limits(what, D, n_clouds, s, nsample, L, false));
     sh = {};
     sh.R = nsample <= 32 ? 32 : 64;
     sh.n_groups = n_clouds * s;
     sh.M = (long long)sh.n_groups * nsample;
     sh.grid = sh.n_groups < SAB_MAX_GRID ? sh.n_groups : SAB_MAX_GRID;
     fpb_chunk_rule(sh.M, sh.chunk_rows, sh.chunks);
-    const int rc = mlp_bwd_layout(what, align_up((size_t)AMPNET_SA_WORKSPACE_BYTES / sizeof(float), 64), 3 + D, D, sh.M, sh.grid, sh.chunks, cout_host,
-                                  L, sh);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_bwd_layout(what, align_up((size_t)AMPNET_SA_WORKSPACE_BYTES / sizeof(float), 64), 3 + D, D, sh.M, sh.grid, sh.chunks, cout_host,
+                                        L, sh));
     // the tiles X_0 .. X_L of R rows
     for (int l = 0; l <= L; ++l) {
         sh.ld_x[l] = (l ? cout_host[l - 1] : (3 + D + 7) / 8 * 8) + 1;
@@ -289,21 +276,16 @@ extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int
     const char *what = "ampnet_sa_backward_f32";
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && dout && grads_host, "%s: null pointer", what);
-    AMPNET_REQUIRE(n >= 1 && ld >= 3, "%s: bad shape n=%d ld=%d", what, n, ld);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
-    AMPNET_REQUIRE(D > 0 || dfeats == nullptr, "%s: dfeats must be NULL when D = 0", what);
     SaBwdShape sh;
-    int rc = sab_shape(what, D, n_clouds, s, nsample, cout_host, L, sh);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(sa_check_cloud(what, n, ld, feats, D, dfeats));
+    AMPNET_TRY(sab_shape(what, D, n_clouds, s, nsample, cout_host, L, sh));
     AMPNET_REQUIRE((long long)n_clouds * n <= 0x7fffffffLL, "%s: n_clouds * n = %lld points exceed 2^31 - 1", what, (long long)n_clouds * n);
-    for (int q = 0; q < 4 * L; ++q) AMPNET_REQUIRE(grads_host[q], "%s: null gradient pointer %d of layer %d", what, q % 4, q / 4);
-    AMPNET_REQUIRE(workspace && workspace_bytes >= sh.floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
-                   sh.floats * sizeof(float));
+    AMPNET_TRY(sa_check_tables(what, nullptr, grads_host, L));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, sh.floats * sizeof(float)));
     MlpPlan p;
     MlpFold f;
     if (!mlp_plan_build(what, 3 + D, sh.R, params_host, cout_host, eps_host, L, p, f)) return AMPNET_E_ARG;
-    p.nw = 1;
-    for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // this kernel stages no weights: every layer is read through L2
+    mlp_plan_unstaged(p);
     float *ws = static_cast<float *>(workspace);
     SaBwdPlan b = {};
     b.sum_c = sh.sum_c;
@@ -323,22 +305,17 @@ extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int
         g.dbeta[l] = grads_host[4 * l + 3];
     }
     static bool attr_set = false;
-    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_backward_kernel), attr_set);
-    if (rc != AMPNET_OK) return rc;
-    rc = mlp_fold_launch(p, f, ws, st);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_backward_kernel), attr_set));
+    AMPNET_TRY(mlp_fold_launch(p, f, ws, st));
     hipLaunchKernelGGL(sa_backward_kernel, dim3(sh.grid), dim3(64), sh.lds_floats * sizeof(float), st, p, b, xyz, n, ld, centres, s, group_idx,
                        nsample, feats, D, ws, dout, sh.n_groups, dfeats ? 1 : 0, arg_out);
-    rc = check_launch("sa_backward_kernel");
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(check_launch("sa_backward_kernel"));
     for (int l = 0; l < L; ++l) {
-        rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, ws + sh.off_wpart,
-                              grads_host[4 * l], st);
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, ws + sh.off_wpart,
+                                    grads_host[4 * l], st));
     }
     if (dfeats) {
-        rc = sa_dfeats_launch(b.dx0, D, n_clouds, n, s, nsample, group_idx, dfeats, st);
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(sa_dfeats_launch(b.dx0, D, n_clouds, n, s, nsample, group_idx, dfeats, st));
     }
     return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);
 }

@@ -78,11 +78,8 @@ extern "C" int ampnet_sa_msg_forward_f32(const float *xyz, int n_clouds, int n, 
     AMPNET_REQUIRE(xyz && centres && group_idx_host && nsample_host && params_host && cout_host && eps_host && L_host && out, "%s: null pointer", what);
     AMPNET_REQUIRE(K >= 1 && K <= AMPNET_SA_MSG_MAX_SCALES, "%s: K=%d branches, the kernel is built for 1 .. %d", what, K, AMPNET_SA_MSG_MAX_SCALES);
     AMPNET_REQUIRE(n_clouds >= 1 && n >= 1 && ld >= 3 && s >= 1, "%s: bad shape n_clouds=%d n=%d ld=%d s=%d", what, n_clouds, n, ld, s);
-    AMPNET_REQUIRE((long long)n_clouds * s <= 0x7fffffffLL, "%s: n_clouds * s = %lld groups exceed 2^31 - 1", what, (long long)n_clouds * s);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
-    AMPNET_REQUIRE(3 + D <= AMPNET_SA_MAX_CIN, "%s: cin_0 = 3 + D = %d exceeds %d", what, 3 + D, AMPNET_SA_MAX_CIN);
-    AMPNET_REQUIRE(workspace && workspace_bytes >= (size_t)K * AMPNET_SA_WORKSPACE_BYTES, "%s: workspace of %zu bytes, need %zu", what,
-                   workspace_bytes, (size_t)K * AMPNET_SA_WORKSPACE_BYTES);
+    AMPNET_TRY(sa_check_feats(what, feats, D, nullptr));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, (size_t)K * AMPNET_SA_WORKSPACE_BYTES));
     const int n_groups = n_clouds * s;
     SaMsgArgs a = {};
     MlpFold f[AMPNET_SA_MSG_MAX_SCALES];
@@ -93,8 +90,7 @@ extern "C" int ampnet_sa_msg_forward_f32(const float *xyz, int n_clouds, int n, 
         snprintf(who, sizeof who, "%s: branch %d", what, k);
         const int nsample = nsample_host[k], L = L_host[k];
         AMPNET_REQUIRE(group_idx_host[k], "%s: null group_idx", who);
-        AMPNET_REQUIRE(nsample >= 1 && nsample <= AMPNET_SA_MAX_NSAMPLE, "%s: nsample=%d must be in [1, %d]", who, nsample, AMPNET_SA_MAX_NSAMPLE);
-        AMPNET_REQUIRE(L >= 1 && L <= AMPNET_SA_MAX_LAYERS, "%s: L=%d layers, the kernel is built for 1 .. %d", who, L, AMPNET_SA_MAX_LAYERS);
+        AMPNET_TRY(sa_check_limits(what, D, n_clouds, s, nsample, L, false, who));
         SaMsgBranch &b = a.b[k];
         const int need = mlp_plan_build(who, 3 + D, nsample <= 32 ? 32 : 64, params_host + 6 * layer0, cout_host + layer0, eps_host + layer0, L,
                                         b.p, f[k]);
@@ -113,12 +109,10 @@ extern "C" int ampnet_sa_msg_forward_f32(const float *xyz, int n_clouds, int n, 
     }
     float *fold_all = static_cast<float *>(workspace);
     for (int k = 0; k < K; ++k) {
-        int rc = mlp_fold_launch(a.b[k].p, f[k], fold_all + a.b[k].fold_off, (hipStream_t)stream);
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(mlp_fold_launch(a.b[k].p, f[k], fold_all + a.b[k].fold_off, (hipStream_t)stream));
     }
     static bool attr_set = false;
-    int rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_msg_forward_kernel), attr_set);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sa_msg_forward_kernel), attr_set));
     hipLaunchKernelGGL(sa_msg_forward_kernel, dim3(grid), dim3(64 * nw_max), lds, (hipStream_t)stream, a, xyz, n, ld, centres, s, feats, D,
                        fold_all, n_groups, C, out);
     return check_launch("sa_msg_forward_kernel");

@@ -24,8 +24,9 @@
 //   sat_bwd_last_kernel (phase L-1), one wave per workgroup, a group at a time, two LDS tiles T0 and T1 of 32 rows:
 //       per 32-row tile of the group it gathers the rows, runs layers < L-1 forward and stores every layer input x_j of the rows
 //       t < nsample to the workspace (dW reads them, and so do the later phases: the rows are never built again).  Then x_{L-1} of the
-//       group's one or two tiles comes back into T0 and T1, a_{L-1} is formed, and per column the largest relu(y), the LOWEST row
-//       t < nsample that attains it and that row's a are kept (sab_last's walk).  dy of the last layer has one nonzero per (group, column):
+//       group's one or two tiles comes back into T0 and T1, a_{L-1} is formed, and per column the largest relu(y), the row that attains
+//       it and that row's a are kept (SaArgMax, sa_tiles.h; only the rows t < nsample are offered: the padding rows are zeros here, not
+//       copies of row 0, and must not compete).  dy of the last layer has one nonzero per (group, column):
 //       it stays as arg (workspace, and arg_out) plus dout, never as a dense array; the one term per group enters sum dy and sum dy a.
 //   sat_bwd_phase_kernel (phase l = L-2 .. -1), one wave per workgroup, a 32-row tile (g, m) at a time:
 //       part A for layer j = l+1: x_j from the workspace into T0, a_j recomputed, dy_j from the workspace (j = L-1: dout at the row arg
@@ -93,8 +94,8 @@ __global__ __launch_bounds__(256) void sat_stats_kernel(MlpPlan p, int l, const 
     }
 }
 
-// The last layer of one group: x_{L-1} of its row tiles in T0 (rows 0 .. 31) and T1 (32 .. 63).  Per column the largest relu(y), the lowest
-// row t < nsample that attains it and its a; the group's one term of sum dy and sum dy a; arg to the workspace and to arg_out.
+// The last layer of one group: x_{L-1} of its row tiles in T0 (rows 0 .. 31) and T1 (32 .. 63).  Per column the SaArgMax over the rows
+// t < nsample; the group's one term of sum dy and sum dy a; arg to the workspace and to arg_out.
 template <int NT>
 __device__ __forceinline__ void sat_last(const float *t0, const float *t1, int ldx, const float *__restrict__ w, int cin, int kp, int n0,
                                          const float *__restrict__ scale, const float *__restrict__ shift, int R, int nsample,
@@ -102,15 +103,13 @@ __device__ __forceinline__ void sat_last(const float *t0, const float *t1, int l
                                          int32_t *__restrict__ arg_g, int lane)
 {
     const int r = lane & 31, h = lane >> 5;
-    float sc[NT], sh[NT], best[NT], ba[NT];
-    int brow[NT];
+    float sc[NT], sh[NT];
+    SaArgMax am[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         sc[t] = scale[n0 + 32 * t + r];
         sh[t] = shift[n0 + 32 * t + r];
-        best[t] = -INFINITY;
-        ba[t] = 0.0f;
-        brow[t] = 0;
+        am[t].init();
     }
     for (int m0 = 0; m0 < R; m0 += 32) {
         const float *x = m0 ? t1 : t0;
@@ -120,31 +119,21 @@ __device__ __forceinline__ void sat_last(const float *t0, const float *t1, int l
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;                  // ascending in (m0, i): `>` keeps the lowest row
+                const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * h;   // ascending in (m0, i), as SaArgMax asks; spelled out: see sab_last
                 const float a = acc[t][i], y = fmaxf(fmaf(a, sc[t], sh[t]), 0.0f);
-                if (row < nsample && y > best[t]) {
-                    best[t] = y;
-                    brow[t] = row;
-                    ba[t] = a;
-                }
+                if (row < nsample) am[t].put(a, y, row);   // (only the rows t < nsample compete)
             }
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int col = n0 + 32 * t + r;
-        const float ob = __shfl_xor(best[t], 32), oa = __shfl_xor(ba[t], 32);
-        const int orow = __shfl_xor(brow[t], 32);
-        if (ob > best[t] || (ob == best[t] && orow < brow[t])) {
-            best[t] = ob;
-            brow[t] = orow;
-            ba[t] = oa;
-        }
+        am[t].merge_halves();
         if (h == 0) {                             // (this lane alone ever touches these words of the workgroup's partials)
-            const float dy = best[t] > 0.0f ? dout_g[col] : 0.0f;
+            const float dy = am[t].best > 0.0f ? dout_g[col] : 0.0f;
             part_b[col] += dy;
-            part_g[col] += dy * ba[t];
-            arg_ws[col] = brow[t];
-            if (arg_g) arg_g[col] = brow[t];
+            part_g[col] += dy * am[t].a;
+            arg_ws[col] = am[t].row;
+            if (arg_g) arg_g[col] = am[t].row;
         }
     }
 }
@@ -266,10 +255,8 @@ struct SatFwdShape {
 static int sat_fwd_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SatFwdShape &sh)
 {
     SaBwdShape b;
-    int rc = sab_shape(what, D, n_clouds, s, nsample, cout_host, L, b);
-    if (rc != AMPNET_OK) return rc;
-    rc = bnt_rows_ok(what, b.M, SAT_MAX_ROWS, "n_clouds * s * nsample");
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(sab_shape(what, D, n_clouds, s, nsample, cout_host, L, b));
+    AMPNET_TRY(bnt_rows_ok(what, b.M, SAT_MAX_ROWS, "n_clouds * s * nsample"));
     sh = {};
     sh.M = b.M;
     sh.R = b.R;
@@ -286,10 +273,8 @@ static int sat_fwd_shape(const char *what, int D, int n_clouds, int s, int nsamp
 static int sat_bwd_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SaBwdShape &sh, size_t &off_coef,
                          size_t &off_arg, size_t &floats)
 {
-    int rc = sab_shape(what, D, n_clouds, s, nsample, cout_host, L, sh);
-    if (rc != AMPNET_OK) return rc;
-    rc = bnt_rows_ok(what, sh.M, SAT_MAX_ROWS, "n_clouds * s * nsample");
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(sab_shape(what, D, n_clouds, s, nsample, cout_host, L, sh));
+    AMPNET_TRY(bnt_rows_ok(what, sh.M, SAT_MAX_ROWS, "n_clouds * s * nsample"));
     off_coef = sh.floats;
     off_arg = off_coef + align_up((size_t)2 * sh.sum_c, 64);
     floats = off_arg + align_up((size_t)sh.n_groups * cout_host[L - 1], 64);
@@ -316,21 +301,17 @@ extern "C" int ampnet_sa_train_forward_f32(const float *xyz, int n_clouds, int n
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && out, "%s: null pointer", what);
     AMPNET_REQUIRE(save_mean && save_invstd, "%s: null save_mean or save_invstd", what);
-    AMPNET_REQUIRE(n >= 1 && ld >= 3, "%s: bad shape n=%d ld=%d", what, n, ld);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
+    AMPNET_TRY(sa_check_cloud(what, n, ld, feats, D, nullptr));
     AMPNET_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "%s: momentum=%g must be in [0, 1]", what, (double)momentum);
     SatFwdShape sh;
-    int rc = sat_fwd_shape(what, D, n_clouds, s, nsample, cout_host, L, sh);
-    if (rc != AMPNET_OK) return rc;
-    AMPNET_REQUIRE(workspace && workspace_bytes >= sh.floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
-                   sh.floats * sizeof(float));
+    AMPNET_TRY(sat_fwd_shape(what, D, n_clouds, s, nsample, cout_host, L, sh));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, sh.floats * sizeof(float)));
     MlpPlan p;
     MlpFold f;
     const int lds = mlp_plan_build(what, 3 + D, sh.R, params_host, cout_host, eps_host, L, p, f);
     if (!lds) return AMPNET_E_ARG;
     static bool attr_set = false;
-    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_stats_kernel), attr_set);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_stats_kernel), attr_set));
     float *ws = static_cast<float *>(workspace), *parts = ws + sh.off_parts;
     int ch = 0;
     for (int l = 0; l < L; ++l) {
@@ -338,12 +319,10 @@ extern "C" int ampnet_sa_train_forward_f32(const float *xyz, int n_clouds, int n
         for (int j = l; j < L; ++j) pl.w_off[j] = -1;
         hipLaunchKernelGGL(sat_stats_kernel, dim3(cdiv(sh.n_parts, p.nw)), dim3(64 * p.nw), lds, st, pl, l, xyz, n, ld, centres, s, group_idx,
                            nsample, feats, D, ws, sh.n_groups, sh.n_parts, parts);
-        rc = check_launch("sat_stats_kernel");
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(check_launch("sat_stats_kernel"));
         FptStats q = {f.bias[l], f.gamma[l], f.beta[l], params_host[6 * l + 4], params_host[6 * l + 5], save_mean + ch, save_invstd + ch,
                       f.eps[l],  momentum,   p.cout[l], p.fold_off[l]};
-        rc = fpt_stats_finalize_launch(q, parts, sh.n_parts, sh.M, ws, st);
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(fpt_stats_finalize_launch(q, parts, sh.n_parts, sh.M, ws, st));
         ch += p.cout[l];
     }
     return sa_forward_launch(what, p, lds, xyz, n_clouds, n, ld, centres, s, group_idx, nsample, feats, D, ws, out, st);
@@ -367,8 +346,7 @@ extern "C" int ampnet_sa_train_backward_tape(int D, int n_clouds, int s, int nsa
     AMPNET_REQUIRE(x_offset_bytes && x_stride && dz_offset_bytes && dz_stride, "%s: null pointer", what);
     SaBwdShape sh;
     size_t off_coef, off_arg, floats;
-    int rc = sat_bwd_shape(what, D, n_clouds, s, nsample, cout_host, L, sh, off_coef, off_arg, floats);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(sat_bwd_shape(what, D, n_clouds, s, nsample, cout_host, L, sh, off_coef, off_arg, floats));
     AMPNET_REQUIRE(l >= 0 && l < L, "%s: layer %d of %d", what, l, L);
     *x_offset_bytes = sh.off_xs[l] * sizeof(float);
     *x_stride = sh.ldxs[l];
@@ -386,53 +364,42 @@ extern "C" int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int 
     const char *what = "ampnet_sa_train_backward_f32";
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && dout && grads_host, "%s: null pointer", what);
-    AMPNET_REQUIRE(n >= 1 && ld >= 3, "%s: bad shape n=%d ld=%d", what, n, ld);
-    AMPNET_REQUIRE(D >= 0 && (D == 0) == (feats == nullptr), "%s: feats must be NULL exactly when D = 0 (D=%d)", what, D);
-    AMPNET_REQUIRE(D > 0 || dfeats == nullptr, "%s: dfeats must be NULL when D = 0", what);
     SaBwdShape sh;
     size_t off_coef, off_arg, floats;
-    int rc = sat_bwd_shape(what, D, n_clouds, s, nsample, cout_host, L, sh, off_coef, off_arg, floats);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(sa_check_cloud(what, n, ld, feats, D, dfeats));
+    AMPNET_TRY(sat_bwd_shape(what, D, n_clouds, s, nsample, cout_host, L, sh, off_coef, off_arg, floats));
     AMPNET_REQUIRE((long long)n_clouds * n <= 0x7fffffffLL, "%s: n_clouds * n = %lld points exceed 2^31 - 1", what, (long long)n_clouds * n);
-    for (int q = 0; q < 4 * L; ++q) AMPNET_REQUIRE(grads_host[q], "%s: null gradient pointer %d of layer %d", what, q % 4, q / 4);
-    AMPNET_REQUIRE(workspace && workspace_bytes >= floats * sizeof(float), "%s: workspace of %zu bytes, need %zu", what, workspace_bytes,
-                   floats * sizeof(float));
+    AMPNET_TRY(sa_check_tables(what, nullptr, grads_host, L));
+    AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, floats * sizeof(float)));
     MlpPlan p;
     MlpFold f;
     if (!mlp_plan_build(what, 3 + D, sh.R, params_host, cout_host, eps_host, L, p, f)) return AMPNET_E_ARG;
-    p.nw = 1;
-    for (int l = 0; l < L; ++l) p.w_off[l] = -1;               // these kernels stage no weights: every layer is read through L2
+    mlp_plan_unstaged(p);
     float *ws = static_cast<float *>(workspace);
     BntBwd b;
     const size_t lds = bnt_bwd_plan(p, f, sh, ws, off_coef, b);
     b.arg = reinterpret_cast<int32_t *>(ws + off_arg);
     static bool attr_last = false, attr_phase = false;
-    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_bwd_last_kernel), attr_last);
-    if (rc != AMPNET_OK) return rc;
-    rc = mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_bwd_phase_kernel), attr_phase);
-    if (rc != AMPNET_OK) return rc;
-    rc = fpt_fold_launch(p, f, ws, st);
-    if (rc != AMPNET_OK) return rc;
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_bwd_last_kernel), attr_last));
+    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(sat_bwd_phase_kernel), attr_phase));
+    AMPNET_TRY(fpt_fold_launch(p, f, ws, st));
     const int n_tiles = sh.n_groups * (sh.R / 32);             // (n_groups <= 2^24: M is)
     for (int l = L - 1; l >= -1; --l) {
         if (l == L - 1) {
             hipLaunchKernelGGL(sat_bwd_last_kernel, dim3(sh.grid), dim3(64), lds, st, p, b, xyz, n, ld, centres, s, group_idx, nsample, feats, D, ws,
                                dout, sh.n_groups, arg_out);
-            rc = check_launch("sat_bwd_last_kernel");
+            AMPNET_TRY(check_launch("sat_bwd_last_kernel"));
         } else {
             hipLaunchKernelGGL(sat_bwd_phase_kernel, dim3(sh.grid), dim3(64), lds, st, p, b, l, nsample, D, ws, dout, n_tiles, dfeats ? 1 : 0);
-            rc = check_launch("sat_bwd_phase_kernel");
+            AMPNET_TRY(check_launch("sat_bwd_phase_kernel"));
         }
-        if (rc != AMPNET_OK) return rc;
         if (l < 0) break;
-        rc = fpt_bwd_finalize_launch(p.cout[l], b.parts, sh.grid, sh.M, f.mean[l], f.var[l], grads_host[4 * l + 1], grads_host[4 * l + 2],
-                                     grads_host[4 * l + 3], b.coef + p.fold_off[l], st);
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(fpt_bwd_finalize_launch(p.cout[l], b.parts, sh.grid, sh.M, f.mean[l], f.var[l], grads_host[4 * l + 1], grads_host[4 * l + 2],
+                                           grads_host[4 * l + 3], b.coef + p.fold_off[l], st));
     }
     for (int l = 0; l < L; ++l) {
-        rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, ws + sh.off_wpart,
-                              grads_host[4 * l], st);
-        if (rc != AMPNET_OK) return rc;
+        AMPNET_TRY(fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, ws + sh.off_wpart,
+                                    grads_host[4 * l], st));
     }
     if (dfeats) return sa_dfeats_launch(b.dx0, D, n_clouds, n, s, nsample, group_idx, dfeats, st);
     return AMPNET_OK;

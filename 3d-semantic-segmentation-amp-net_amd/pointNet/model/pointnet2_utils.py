@@ -128,7 +128,54 @@ def _count_batch(mod):
 _SA_EVAL_ONLY = "the HIP set abstraction is built for eval mode (BatchNorm running statistics, no backward): call .eval() first"
 
 
-class PointNetSetAbstraction(nn.Module):
+class _SetAbstraction(nn.Module):
+    """What PointNetSetAbstraction and PointNetSetAbstractionMsg share: the channel-major interface around _forward_rows and the centres
+    of a block.  The class name opens the messages; D, the width of `points`, is the caller's (in_channel counts the coordinates in one
+    class and not in the other)."""
+
+    def _forward_channel_major(self, xyz, points, centres, D):
+        """forward() of both classes: the shape checks, the transposes to point-major rows and back, with or without a graph."""
+        if self.training and not self.batch_stats:
+            raise NotImplementedError(_SA_EVAL_ONLY)
+        name = type(self).__name__
+        _lib.require_gpu(xyz, "xyz")
+        if xyz.dim() != 3 or xyz.shape[1] != 3:
+            raise _lib.AmpnetError(f"{name}: expected xyz [B, 3, N], got {tuple(xyz.shape)}")
+        B, _, N = xyz.shape
+        if (points is None) != (D == 0) or (points is not None and (points.dim() != 3 or tuple(points.shape) != (B, D, N))):
+            raise _lib.AmpnetError(f"{name}: in_channel={self.in_channel} needs points "
+                                   f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
+        if points is not None:
+            _lib.require_gpu(points, "points")
+        rows = lambda t: None if t is None else t.float().transpose(1, 2).contiguous()       # [B, N, 3], [B, N, D]
+        if self._wants_grad(points):                                 # a differentiable transpose; the coordinates get no gradient
+            new_xyz, out = self._forward_rows(rows(xyz.detach()), rows(points), centres)
+        else:
+            with torch.no_grad():
+                new_xyz, out = self._forward_rows(rows(xyz), rows(points), centres)
+        return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
+
+    def _wants_grad(self, feats):
+        return self.grad and torch.is_grad_enabled() and ((feats is not None and feats.requires_grad)
+                                                          or any(p.requires_grad for p in self.parameters()))
+
+    def _sample_and_group(self, x, centres, query):
+        """The centres of x [B, N, 3] (`centres`, or farthest-point sampling from point 0) and what query(x, centres), the class's ball
+        query, finds around them -> (x detached, centres, the query's result, new_xyz [B, npoint, 3]).  The query validates the centres,
+        so it runs before the gather."""
+        with torch.no_grad():
+            x = x.detach()
+            if centres is None:
+                centres = U.fps_indices(x, self.npoint)
+            elif centres.dim() != 2 or tuple(centres.shape) != (x.shape[0], self.npoint):
+                raise _lib.AmpnetError(f"{type(self).__name__}: centres must be [B, npoint] = {[x.shape[0], self.npoint]}, "
+                                       f"got {tuple(centres.shape)}")
+            groups = query(x, centres)
+            centres = centres.contiguous()
+            return x, centres, groups, U.gather_rows(x, centres)
+
+
+class PointNetSetAbstraction(_SetAbstraction):
     """One set-abstraction layer: `npoint` centres by farthest-point sampling, per centre the first `nsample` points within `radius`
     (utils.ball_query), the shared MLP `mlp` (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on [relative xyz, point features], max over the
     group.  `in_channel` counts the 3 coordinates, as in the usual implementation.
@@ -166,29 +213,7 @@ class PointNetSetAbstraction(nn.Module):
         """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]);
         npoint counts as 1 in a group_all block.  centres: int32 [B, npoint] point indices to use instead of farthest-point sampling
         from point 0."""
-        if self.training and not self.batch_stats:
-            raise NotImplementedError(_SA_EVAL_ONLY)
-        _lib.require_gpu(xyz, "xyz")
-        if xyz.dim() != 3 or xyz.shape[1] != 3:
-            raise _lib.AmpnetError(f"PointNetSetAbstraction: expected xyz [B, 3, N], got {tuple(xyz.shape)}")
-        B, _, N = xyz.shape
-        D = self.in_channel - 3
-        if (points is None) != (D == 0) or (points is not None and (points.dim() != 3 or tuple(points.shape) != (B, D, N))):
-            raise _lib.AmpnetError(f"PointNetSetAbstraction: in_channel={self.in_channel} needs points "
-                                   f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
-        if points is not None:
-            _lib.require_gpu(points, "points")
-        rows = lambda t: None if t is None else t.float().transpose(1, 2).contiguous()       # [B, N, 3], [B, N, D]
-        if self._wants_grad(points):                                 # a differentiable transpose; the coordinates get no gradient
-            new_xyz, out = self._forward_rows(rows(xyz.detach()), rows(points), centres)
-        else:
-            with torch.no_grad():
-                new_xyz, out = self._forward_rows(rows(xyz), rows(points), centres)
-        return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
-
-    def _wants_grad(self, feats):
-        return self.grad and torch.is_grad_enabled() and ((feats is not None and feats.requires_grad)
-                                                          or any(p.requires_grad for p in self.parameters()))
+        return self._forward_channel_major(xyz, points, centres, self.in_channel - 3)
 
     def _forward_rows(self, x, feats, centres=None):
         """The layer on point-major tensors (what the kernels take): x [B, N, 3], feats [B, N, D] or None, float32 contiguous GPU
@@ -197,15 +222,7 @@ class PointNetSetAbstraction(nn.Module):
         if self.group_all:
             return self._all_rows(x, feats, centres)
         B = x.shape[0]
-        with torch.no_grad():
-            x = x.detach()
-            if centres is None:
-                centres = U.fps_indices(x, self.npoint)
-            elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
-                raise _lib.AmpnetError(f"PointNetSetAbstraction: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
-            group_idx = U.ball_query(x, centres, self.radius, self.nsample)       # validates the centres
-            centres = centres.contiguous()
-            new_xyz = U.gather_rows(x, centres)
+        x, centres, group_idx, new_xyz = self._sample_and_group(x, centres, lambda x, c: U.ball_query(x, c, self.radius, self.nsample))
         if self.training:
             return new_xyz, self._train_rows(x, centres, group_idx, feats)
         if self._wants_grad(feats):
@@ -267,7 +284,7 @@ class _Bns:
         self.mlp_bns = [bn for b in branches for bn in b.mlp_bns]
 
 
-class PointNetSetAbstractionMsg(nn.Module):
+class PointNetSetAbstractionMsg(_SetAbstraction):
     """One multi-scale-grouping set-abstraction layer: `npoint` centres by farthest-point sampling, and for every (radius, nsample, mlp) of
     radius_list, nsample_list and mlp_list a branch that groups the first `nsample` points within `radius` of each centre
     (utils.ball_query_msg: all radii in one pass), runs its shared MLP (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on the group and takes
@@ -320,27 +337,7 @@ class PointNetSetAbstractionMsg(nn.Module):
     def forward(self, xyz, points, centres=None):
         """xyz [B, 3, N], points [B, D, N] or None (D = in_channel) -> (new_xyz [B, 3, npoint], new_points [B, sum of the branches' last
         widths, npoint]).  centres: int32 [B, npoint] point indices to use instead of farthest-point sampling from point 0."""
-        if self.training and not self.batch_stats:
-            raise NotImplementedError(_SA_EVAL_ONLY)
-        _lib.require_gpu(xyz, "xyz")
-        if xyz.dim() != 3 or xyz.shape[1] != 3:
-            raise _lib.AmpnetError(f"PointNetSetAbstractionMsg: expected xyz [B, 3, N], got {tuple(xyz.shape)}")
-        B, _, N = xyz.shape
-        D = self.in_channel
-        if (points is None) != (D == 0) or (points is not None and (points.dim() != 3 or tuple(points.shape) != (B, D, N))):
-            raise _lib.AmpnetError(f"PointNetSetAbstractionMsg: in_channel={self.in_channel} needs points "
-                                   f"{'None' if D == 0 else [B, D, N]}, got {None if points is None else tuple(points.shape)}")
-        if points is not None:
-            _lib.require_gpu(points, "points")
-        rows = lambda t: None if t is None else t.float().transpose(1, 2).contiguous()       # [B, N, 3], [B, N, D]
-        if self._wants_grad(points):                                 # a differentiable transpose; the coordinates get no gradient
-            new_xyz, out = self._forward_rows(rows(xyz.detach()), rows(points), centres)
-        else:
-            with torch.no_grad():
-                new_xyz, out = self._forward_rows(rows(xyz), rows(points), centres)
-        return new_xyz.transpose(1, 2).contiguous(), out.transpose(1, 2).contiguous()
-
-    _wants_grad = PointNetSetAbstraction._wants_grad
+        return self._forward_channel_major(xyz, points, centres, self.in_channel)
 
     def _w0(self, b):
         """Layer 0's weight of branch b as the kernels take it: the checkpoint's columns [features (D), xyz (3)] rotated to [xyz, features]."""
@@ -352,15 +349,8 @@ class PointNetSetAbstractionMsg(nn.Module):
         -> (new_xyz [B, npoint, 3], new_points [B, npoint, sum of the branches' last widths]).  Farthest-point sampling and the ball
         query at all radii run once."""
         B, K = x.shape[0], len(self._branches)
-        with torch.no_grad():
-            x = x.detach()
-            if centres is None:
-                centres = U.fps_indices(x, self.npoint)
-            elif centres.dim() != 2 or tuple(centres.shape) != (B, self.npoint):
-                raise _lib.AmpnetError(f"PointNetSetAbstractionMsg: centres must be [B, npoint] = {[B, self.npoint]}, got {tuple(centres.shape)}")
-            group_idxs = U.ball_query_msg(x, centres, self.radius_list, self.nsample_list)       # validates the centres
-            centres = centres.contiguous()
-            new_xyz = U.gather_rows(x, centres)
+        x, centres, group_idxs, new_xyz = self._sample_and_group(
+            x, centres, lambda x, c: U.ball_query_msg(x, c, self.radius_list, self.nsample_list))
         wants_grad = self._wants_grad(feats)
         if self.training:
             return new_xyz, self._train_rows(x, centres, group_idxs, feats, wants_grad)

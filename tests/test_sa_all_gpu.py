@@ -1,6 +1,7 @@
 """The group_all set-abstraction forward (include/ampnet_hip.h: ampnet_sa_all_forward_f32) against the float64 restatement
 tests/sa_all_ref.py (the bar is sa_ref.sa_forward's, derived there), and bit for bit against ampnet_sa_forward_f32 on the same rows around
-a centre at the origin.  The worst error / bar ratio of every case is printed."""
+a centre at the origin.  The worst error / bar ratio of every case is printed.  The row the max selects (`arg`) is also compared with the
+one ampnet_sa_backward_f32 reports for the same rows as one group: the arg-max walks of the entry points must agree."""
 import os
 import sys
 
@@ -129,3 +130,37 @@ def test_sa_all_forward_refusals():
         run_forward(L, i, layers=R.sa_ref.make_layers(1, 321, [32]), feats=np.zeros((2, 32, 318), np.float32))
     with pytest.raises(L.AmpnetError, match="GPU"):
         L.sa_all_forward_f32(torch.zeros(2, 32, 3), None, [], [], torch.zeros(2, 32), torch.zeros(8, dtype=torch.uint8))
+
+
+@pytest.mark.parametrize("n, repeat_from", [(8, 4), (40, 32), (1, None)])
+def test_sa_all_arg_equals_the_grouped_backward_arg(n, repeat_from):
+    """The same rows through both arg-max walks: as ONE group (group_idx = arange(n), the centre a point at the exact origin) through
+    ampnet_sa_backward_f32(..., arg_out), and as a whole cloud through ampnet_sa_all_forward_f32(..., arg_out).  The rows from
+    `repeat_from` on repeat the first rows bit for bit, so every column's maximum is attained twice: n = 8 ties rows r and r + 4, which
+    sit in the two lane halves of one accumulator; n = 40 ties rows r and r + 32, which sit in two row tiles (two tiles of one group
+    there, two runs of one cloud here).  The lowest row must win in both, and `out` must be ampnet_sa_forward_f32's on that group."""
+    L = sub("_lib")
+    B, D, widths = 2, 6, [32, 64]
+    rng = np.random.default_rng(9100 + n)
+    xyz = rng.uniform(-1.0, 1.0, (B, n, 3)).astype(np.float32)
+    feats = rng.uniform(-1.0, 1.0, (B, n, D)).astype(np.float32)
+    xyz[:, 0] = 0.0                                                # the centre: x - 0 is exact
+    if repeat_from is not None:
+        xyz[:, repeat_from:] = xyz[:, :n - repeat_from]
+        feats[:, repeat_from:] = feats[:, :n - repeat_from]
+    layers = R.sa_ref.make_layers(9200 + n, 3 + D, widths)
+    i = {"xyz": xyz, "feats": feats, "layers": layers}
+    out_all, arg_all = run_forward(L, i)
+    centres = np.zeros((B, 1), np.int32)
+    group_idx = np.tile(np.arange(n, dtype=np.int32), (B, 1, 1))
+    out_ball = _ball_forward(L, xyz, feats, layers, centres, group_idx)
+    glayers = [tuple(_t(a) for a in layer) for layer in layers]
+    grads = [tuple(torch.empty_like(t) for t in layer[:4]) for layer in glayers]
+    arg_bwd = torch.full((B, 1, widths[-1]), -1, dtype=torch.int32, device="cuda")
+    ws = torch.empty(L.sa_backward_workspace_bytes(D, B, 1, n, widths), dtype=torch.uint8, device="cuda")
+    L.sa_backward_f32(_t(xyz), _t(centres), _t(group_idx), _t(feats), glayers, [R.BN_EPS] * len(layers),
+                      torch.ones((B, 1, widths[-1]), device="cuda"), None, grads, ws, arg_out=arg_bwd)
+    torch.cuda.synchronize()
+    assert torch.equal(arg_bwd[:, 0].cpu(), torch.from_numpy(arg_all)), (n, arg_bwd[:, 0].cpu(), arg_all)
+    assert np.array_equal(out_all, out_ball[:, 0]), n
+    assert (arg_all >= 0).all() and (arg_all < (n if repeat_from is None else repeat_from)).all(), n   # a repeated row never wins

@@ -66,20 +66,13 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(BnBwdFinalize a)
         }
         const double n = (double)rows_s;
         const size_t o = (size_t)slot * a.C + c;
-        const double invstd = a.invstd[o], mean = a.mean[o];
-        const double s = (double)a.gamma[c] * invstd;
-        const double p2 = n > 0.0 ? -s * invstd * Bs / n : 0.0;     // a slot with no row: P2 = P3 = 0 (as bn_finalize guards N > 0)
-        a.P1[o] = (float)s;
-        a.P2[o] = (float)p2;
-        a.P3[o] = (float)(n > 0.0 ? -s * A / n - p2 * mean : 0.0);
-        a.slot_ab[o * 2 + 0] = (float)A;
-        a.slot_ab[o * 2 + 1] = (float)Bs;
+        bn_bwd_constants<true>(A, Bs, n, a.gamma[c], a.invstd[o], a.mean[o], a.out, o, true);      // a slot may have no row
     }
 }
 
 int bn_bwd_finalize(const BnBwdFinalize &a, hipStream_t st)
 {
-    AMPNET_REQUIRE(a.part_a && a.part_b && (a.win_off || a.uniform_rows > 0) && a.gamma && a.mean && a.invstd && a.P1 && a.P2 && a.P3 && a.slot_ab, "bn_bwd_finalize: null pointer");
+    AMPNET_REQUIRE(a.part_a && a.part_b && (a.win_off || a.uniform_rows > 0) && a.gamma && a.mean && a.invstd && a.out.P1 && a.out.P2 && a.out.P3 && a.out.slot_ab, "bn_bwd_finalize: null pointer");
     const long parts = (long)(a.part_Q > 0 ? cdiv(a.part_Q, a.n_slots) : cdiv(a.Q, a.n_slots)) * a.chunks;
     if (a.n_slots * cdiv(a.C, 64) < 8 && parts >= 512)
         hipLaunchKernelGGL(bn_bwd_finalize_kernel<16>, dim3(a.n_slots, cdiv(a.C, 16)), dim3(1024), 0, st, a);
@@ -87,7 +80,7 @@ int bn_bwd_finalize(const BnBwdFinalize &a, hipStream_t st)
         hipLaunchKernelGGL(bn_bwd_finalize_kernel<64>, dim3(a.n_slots, cdiv(a.C, 64)), dim3(1024), 0, st, a);
     int rc = check_launch("bn_bwd_finalize_kernel");
     if (rc == AMPNET_OK && sync_bn_on())       // global batch: the constants again, from the all-reduced sums (slot_ab stays the rank's own)
-        rc = sync_bn_bwd_constants(a.slot_ab, a.win_off, a.Q, a.n_slots, a.uniform_rows, a.C, a.gamma, nullptr, a.mean, a.invstd, a.P1, a.P2, a.P3, st);
+        rc = sync_bn_bwd_constants(a.out.slot_ab, a.win_off, a.Q, a.n_slots, a.uniform_rows, a.C, a.gamma, nullptr, a.mean, a.invstd, a.out.P1, a.out.P2, a.out.P3, st);
     return rc;
 }
 
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(64 * PB_G) void pool_bwd_kernel(PoolBwd a)
     const int slot = blockIdx.x, cl = threadIdx.x & 63, g = threadIdx.x >> 6, c = blockIdx.y * 64 + cl;
     const bool ok = c < a.C;
     const size_t so = (size_t)slot * a.C + (ok ? c : 0);
-    const float sc = a.scale[so], sh = a.shift[so], mean = a.mean[so], invstd = a.invstd[so];
+    const float sc = a.fwd.scale[so], sh = a.fwd.shift[so], mean = a.fwd.mean[so], invstd = a.fwd.invstd[so];
     const int per_slot = (a.Q - slot + a.n_slots - 1) / a.n_slots;
     double A = 0.0, Bs = 0.0;
     int rows = 0;
@@ -183,20 +176,20 @@ __global__ __launch_bounds__(64 * PB_G) void pool_bwd_kernel(PoolBwd a)
     const double n = (double)rows;
     const double gamma_invstd = (double)sc;      // scale = gamma * invstd
     const double p2 = -gamma_invstd * (double)invstd * Bs / n;
-    a.P1[so] = sc;
-    a.P2[so] = (float)p2;
-    a.P3[so] = (float)(-gamma_invstd * A / n - p2 * (double)mean);
-    a.slot_ab[so * 2 + 0] = (float)A;
-    a.slot_ab[so * 2 + 1] = (float)Bs;
+    a.out.P1[so] = sc;
+    a.out.P2[so] = (float)p2;
+    a.out.P3[so] = (float)(-gamma_invstd * A / n - p2 * (double)mean);
+    a.out.slot_ab[so * 2 + 0] = (float)A;
+    a.out.slot_ab[so * 2 + 1] = (float)Bs;
 }
 
 int pool_bwd(const PoolBwd &a, hipStream_t st)
 {
-    AMPNET_REQUIRE(a.d_pooled && a.arg && a.zext && a.scale && a.shift && a.mean && a.invstd && a.win_off && a.dpm && a.P1 && a.P2 && a.P3 && a.slot_ab, "pool_bwd: null pointer");
+    AMPNET_REQUIRE(a.d_pooled && a.arg && a.zext && a.fwd.scale && a.fwd.shift && a.fwd.mean && a.fwd.invstd && a.win_off && a.dpm && a.out.P1 && a.out.P2 && a.out.P3 && a.out.slot_ab, "pool_bwd: null pointer");
     hipLaunchKernelGGL(pool_bwd_kernel, dim3(a.n_slots, cdiv(a.C, 64)), dim3(64 * PB_G), 0, st, a);
     int rc = check_launch("pool_bwd_kernel");
     if (rc == AMPNET_OK && sync_bn_on())
-        rc = sync_bn_bwd_constants(a.slot_ab, a.win_off, a.Q, a.n_slots, 0, a.C, nullptr, a.scale, a.mean, a.invstd, a.P1, a.P2, a.P3, st);
+        rc = sync_bn_bwd_constants(a.out.slot_ab, a.win_off, a.Q, a.n_slots, 0, a.C, nullptr, a.fwd.scale, a.fwd.mean, a.fwd.invstd, a.out.P1, a.out.P2, a.out.P3, st);
     return rc;
 }
 
@@ -680,20 +673,20 @@ __global__ __launch_bounds__(64 * IW_WAVES) void pw_input_wgrad_kernel(PwInputWg
     const int row_begin = a.win_off[q], row_end = a.win_off[q + 1];
     const int slot = a.n_slots > 1 ? q % a.n_slots : 0;
     float p1, p2, p3;
-    if (a.fin_part_a) {
-        // the same arithmetic as the fin_* prologue of the fused backward (pw_bwd_fused.hip), on this kernel's own layout -- lane = channel, one
+    if (a.fin.part_a) {
+        // the same sums as the fin prologue of the fused backward (pw_bwd_fused.hip), on this kernel's own layout -- lane = channel, one
         // scalar per thread instead of a channel quad: wave w sums the slot's partials w, w + IW_WAVES, ... (all loads of a trip in flight),
         // the waves merge through LDS in wave order
         double sa = 0.0, sb = 0.0;
-        const int per_slot_parts = (a.fin_parts - slot + a.n_slots - 1) / a.n_slots;
+        const int per_slot_parts = (a.fin.parts - slot + a.n_slots - 1) / a.n_slots;
         for (int k0 = wave; k0 < per_slot_parts; k0 += IW_WAVES * 8) {
             float va[8], vb[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = k0 + IW_WAVES * u;
                 const size_t o = (size_t)(slot + (k < per_slot_parts ? k : 0) * a.n_slots) * 64 + lane;
-                va[u] = a.fin_part_a[o];
-                vb[u] = a.fin_part_b[o];
+                va[u] = a.fin.part_a[o];
+                vb[u] = a.fin.part_b[o];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -715,23 +708,15 @@ __global__ __launch_bounds__(64 * IW_WAVES) void pw_input_wgrad_kernel(PwInputWg
         }
         __syncthreads();                                               // red[] is reused below
         const size_t o = (size_t)slot * 64 + lane;
-        const double n = (double)a.fin_rows, invstd = a.fin_invstd[o], mean = a.fin_mean[o];
-        const double s = (double)a.fin_gamma[lane] * invstd;
-        const double q2 = -s * invstd * Bs / n;
-        p1 = (float)s;
-        p2 = (float)q2;
-        p3 = (float)(-s * A / n - q2 * mean);
-        if (q < a.n_slots && wave == 0) {                              // the first window of each slot: the arrays other kernels read
-            a.fin_slot_ab[o * 2 + 0] = (float)A;
-            a.fin_slot_ab[o * 2 + 1] = (float)Bs;
-            a.fin_P1[o] = p1;
-            a.fin_P2[o] = p2;
-            a.fin_P3[o] = p3;
-        }
+        // written by the first window of each slot: the arrays other kernels read
+        const BnBwdVal v = bn_bwd_constants(A, Bs, (double)a.fin.rows, a.fin.gamma[lane], a.fin.invstd[o], a.fin.mean[o], a.fin.out, o, q < a.n_slots && wave == 0);
+        p1 = v.p1;
+        p2 = v.p2;
+        p3 = v.p3;
     } else {
-        p1 = a.P1[(size_t)slot * 64 + lane];
-        p2 = a.P2[(size_t)slot * 64 + lane];
-        p3 = a.P3[(size_t)slot * 64 + lane];
+        p1 = a.bn.P1[(size_t)slot * 64 + lane];
+        p2 = a.bn.P2[(size_t)slot * 64 + lane];
+        p3 = a.bn.P3[(size_t)slot * 64 + lane];
     }
     // effective weights of this lane's channel, exactly as pw_input forms them (pw_misc.hip)
     float w[9];
@@ -804,9 +789,10 @@ __global__ __launch_bounds__(64 * IW_WAVES) void pw_input_wgrad_kernel(PwInputWg
 
 int pw_input_wgrad(const PwInputWgrad &a, hipStream_t st)
 {
-    AMPNET_REQUIRE(a.x && a.dy && a.W && a.dWeff && a.win_off && (a.fin_part_a || (a.P1 && a.P2 && a.P3)), "pw_input_wgrad: null pointer");
-    AMPNET_REQUIRE(!a.fin_part_a || (a.fin_part_b && a.fin_parts >= a.n_slots && a.fin_rows >= 1 && a.fin_gamma && a.fin_mean && a.fin_invstd && a.fin_P1 && a.fin_P2 && a.fin_P3 &&
-                                     a.fin_slot_ab && a.Q >= a.n_slots),
+    AMPNET_REQUIRE(a.x && a.dy && a.W && a.dWeff && a.win_off && (a.fin.part_a || (a.bn.P1 && a.bn.P2 && a.bn.P3)), "pw_input_wgrad: null pointer");
+    AMPNET_REQUIRE(!a.fin.part_a || bn_bwd_in_kernel(), "pw_input_wgrad: in-kernel BatchNorm-backward constants need fp32 operands and no global-batch BatchNorm");
+    AMPNET_REQUIRE(!a.fin.part_a || (a.fin.part_b && a.fin.parts >= a.n_slots && a.fin.rows >= 1 && a.fin.gamma && a.fin.mean && a.fin.invstd && a.fin.out.P1 && a.fin.out.P2 && a.fin.out.P3 &&
+                                     a.fin.out.slot_ab && a.Q >= a.n_slots),
                    "pw_input_wgrad: in-kernel BatchNorm-backward constants need the producer's partials, the layer's statistics and the output arrays");
     AMPNET_REQUIRE(a.mode == 0 || a.T, "pw_input_wgrad: mode 1 needs T");
     hipLaunchKernelGGL(pw_input_wgrad_kernel, dim3(a.Q), dim3(64 * IW_WAVES), 0, st, a);

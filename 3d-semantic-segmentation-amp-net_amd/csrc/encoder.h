@@ -1,6 +1,6 @@
 // encoder.h -- parameter tables and workspace layout shared by the encoder forward and backward.
 #pragma once
-#include "kernels.h"
+#include "bn_wiring.h"
 
 namespace ampnet {
 
@@ -18,11 +18,6 @@ enum { EB_IT = 0, EB_FT = 10, EB_MAIN = 20, EB_COUNT = 32 };
 // BatchNorm layers of the encoder in execution order
 enum EncBn { BN_T1 = 0, BN_T2, BN_T3, BN_T4, BN_T5, BN_C1, BN_C2, BN_F1, BN_F2, BN_F3, BN_F4, BN_F5,
              BN_C3, BN_C4, BN_C5, BN_C6, BN_ENC_COUNT };
-
-struct BnSlot {              // per-layer derived arrays, each [n_slots, C]
-    float *scale, *shift, *mean, *invstd, *smean, *suvar;
-    int C;
-};
 
 struct EncShape {
     int Q, n_slots, R, max_rows, train;

@@ -104,23 +104,14 @@ void enc_carve(const EncShape &s, void *base, EncWs &ws)
     ws.part_sq = c.take<float>(np_bwd);
     ws.part_max = c.take<float>(np);
     ws.part_amax = c.take<int>(np);
-    for (int i = 0; i < BN_ENC_COUNT; ++i) {
-        const size_t n = (size_t)s.n_slots * kBnC[i];
-        ws.bn[i].C = kBnC[i];
-        ws.bn[i].scale = c.take<float>(n);
-        ws.bn[i].shift = c.take<float>(n);
-        ws.bn[i].mean = c.take<float>(n);
-        ws.bn[i].invstd = c.take<float>(n);
-        ws.bn[i].smean = c.take<float>(n);
-        ws.bn[i].suvar = c.take<float>(n);
-    }
+    for (int i = 0; i < BN_ENC_COUNT; ++i) carve_bn(c, ws.bn[i], s.n_slots, kBnC[i]);
     ws.bytes = align_up(c.off, 256);
 }
 
 namespace {
 
 struct BnParamRef {
-    const float *gamma, *beta;
+    BnLayer layer;
     float *rmean, *rvar;
 };
 
@@ -134,7 +125,7 @@ struct EncRun {
     BnParamRef bnp[BN_ENC_COUNT];
     bool zb = false;           // precision mode 3: the z tensors of the workspace are bf16
     // BatchNorm statistics in flight: the producer of layer `bn` left `parts` per-workgroup partials in region `region` of part_sum / part_sq /
-    // part_rows; the next point layer merges them itself (PwGemm.pfin_*) or settle() launches bn_finalize.  Producers alternate regions.
+    // part_rows; the next point layer or the pool merges them itself (pfin) or settle() launches bn_finalize.  Producers alternate regions.
     struct Pending {
         int bn = -1, parts = 0, region = 0;
     };
@@ -144,11 +135,10 @@ struct EncRun {
     float *psq(int r) const { return ws.part_sq + (size_t)r * enc_fwd_part_region_floats(s); }
     int *prows(int r) const { return ws.part_rows + (size_t)r * enc_fwd_part_region_rows(s); }
     static bool split_layer(int cin, int cout) { return pw_gemm_stat_lane_cap(cin, cout) != 512; }     // this layer runs on the split kernels
-    bool consumer_fin() const
-    {
-        static const bool off = [] { const char *v = getenv("AMPNET_FWD_FIN_IN_KERNEL"); return v && v[0] == '0'; }();
-        return s.train && !off && !sync_bn_on();
-    }
+    BnPartials pending() const { return BnPartials{psum(pend.region), psq(pend.region), prows(pend.region), pend.parts}; }
+    // the pending statistics of layer `bn` handed to the consumer that finishes them in its own kernel (kernels.h: BnPfin)
+    bool consumer_fin(int bn) const { return pend.bn == bn && bn_fwd_in_kernel(s.train); }
+    BnPfin owed_pfin() const { return BnPfin{pending(), bnp[pend.bn].layer, ws.bn[pend.bn]}; }
     void note_stats(int bn, int lanes) const
     {
         pend.bn = bn;
@@ -161,14 +151,14 @@ struct EncRun {
     {
         auto tn = [&](int base_p, int base_b, int first) {
             for (int i = 0; i < 5; ++i) {
-                bnp[first + i] = {P[base_p + TP_BN1_W + 2 * i], P[base_p + TP_BN1_B + 2 * i], Bf[base_b + 2 * i], Bf[base_b + 2 * i + 1]};
+                bnp[first + i] = {{P[base_p + TP_BN1_W + 2 * i], P[base_p + TP_BN1_B + 2 * i]}, Bf[base_b + 2 * i], Bf[base_b + 2 * i + 1]};
             }
         };
         tn(EP_IT, EB_IT, BN_T1);
         tn(EP_FT, EB_FT, BN_F1);
         const int main_ids[6] = {BN_C1, BN_C2, BN_C3, BN_C4, BN_C5, BN_C6};
         for (int i = 0; i < 6; ++i)
-            bnp[main_ids[i]] = {P[EP_BN1_W + 2 * i], P[EP_BN1_B + 2 * i], Bf[EB_MAIN + 2 * i], Bf[EB_MAIN + 2 * i + 1]};
+            bnp[main_ids[i]] = {{P[EP_BN1_W + 2 * i], P[EP_BN1_B + 2 * i]}, Bf[EB_MAIN + 2 * i], Bf[EB_MAIN + 2 * i + 1]};
     }
 
     // point layer on the real windows
@@ -187,26 +177,20 @@ struct EncRun {
         if (stats) { g.part_sum = psum(region); g.part_sq = psq(region); }
         // eval forward in fp32: only the extremes are tracked (no argmax rows: nothing reads them without a backward)
         const bool rows_too = s.train || !precision_is_f32();
-        if (pool) { g.part_max = ws.part_max; g.part_amax = rows_too ? ws.part_amax : nullptr; g.pool_gamma = bnp[pool_bn].gamma; }
+        if (pool) { g.part_max = ws.part_max; g.part_amax = rows_too ? ws.part_amax : nullptr; g.pool_gamma = bnp[pool_bn].layer.gamma; }
         g.win_off = win_off; g.Q = s.Q; g.chunk_rows = s.chunk_rows; g.chunks = s.chunks; g.rows_hint = s.R;
         if (split_layer(cin, cout)) { g.chunk_rows = s.x_chunk_rows; g.chunks = s.x_chunks; }     // one wave per block of rows (pw_gemm.hip)
         if (stats) {                                             // one partial per workgroup: bn_finalize in one stage (kernels.h)
             g.part_rows = prows(region);
             g.stat_lanes = pw_gemm_stat_plan(s.Q, g.chunks, g.n_slots, pw_gemm_stat_lane_cap(cin, cout)).lanes;
         }
-        if (stats && pro_bn >= 0 && pend.bn == pro_bn && consumer_fin() && (cin == 64 || cin == 128)) {
-            // this launch finishes its input's BatchNorm itself (kernels.h: pfin_*)
-            const BnSlot &b = ws.bn[pro_bn];
-            g.pfin_sum = psum(pend.region); g.pfin_sq = psq(pend.region); g.pfin_rows = prows(pend.region); g.pfin_parts = pend.parts;
-            g.pfin_gamma = bnp[pro_bn].gamma; g.pfin_beta = bnp[pro_bn].beta;
-            g.pfin_scale = b.scale; g.pfin_shift = b.shift; g.pfin_mean = b.mean; g.pfin_invstd = b.invstd; g.pfin_smean = b.smean; g.pfin_suvar = b.suvar;
-        }
+        if (stats && pro_bn >= 0 && consumer_fin(pro_bn) && (cin == 64 || cin == 128)) g.pfin = owed_pfin();     // this launch finishes its input's BatchNorm
         return g;
     }
     // launch a point layer: what is pending and not consumed by it is finalized first; its own statistics become the pending ones
     int run_point(const PwGemm &g, int stats_bn) const
     {
-        if (g.pfin_sum) pend.bn = -1;
+        if (g.pfin.part.sum) pend.bn = -1;
         else if (int rc = settle(); rc != AMPNET_OK) return rc;
         if (int rc = pw_gemm(g, st); rc != AMPNET_OK) return rc;
         if (stats_bn >= 0 && s.train) note_stats(stats_bn, g.stat_lanes);
@@ -218,21 +202,12 @@ struct EncRun {
         if (pend.bn < 0 || !s.train) return AMPNET_OK;
         const int bn = pend.bn;
         pend.bn = -1;
-        BnFinalize f;
-        f.part_sum = psum(pend.region); f.part_sq = psq(pend.region); f.part_rows = prows(pend.region);
-        f.win_off = win_off;
-        f.Q = pend.parts; f.chunks = 1; f.chunk_rows = s.chunk_rows; f.uniform_rows = 0;
-        f.n_slots = s.n_slots; f.C = ws.bn[bn].C;
-        f.gamma = bnp[bn].gamma; f.beta = bnp[bn].beta;
-        f.scale = ws.bn[bn].scale; f.shift = ws.bn[bn].shift; f.mean = ws.bn[bn].mean; f.invstd = ws.bn[bn].invstd;
-        f.stat_mean = ws.bn[bn].smean; f.stat_uvar = ws.bn[bn].suvar;
-        f.merge_ws = ws.merge;
-        return bn_finalize(f, st);
+        return bn_finalize(bn_finalize_args(pending(), bnp[bn].layer, ws.bn[bn], s.n_slots, ws.bn[bn].C, ws.merge), st);
     }
     // FC layer on the pooled rows: n_slots windows of Q / n_slots rows (one window of Q rows in eval mode)
     // stats_bn >= 0: this layer's BatchNorm.  A slot's rows are one block of rows when fc_chunks == 1 (B <= 128): the workgroup then writes
     // the BatchNorm constants itself and finalize_fc() launches nothing.  Not under global-batch BatchNorm (the ranks' partials are merged).
-    bool fc_direct() const { return s.train && s.fc_chunks == 1 && !sync_bn_on(); }
+    bool fc_direct() const { return bn_fwd_in_kernel(s.train) && s.fc_chunks == 1; }
     PwGemm fc_layer(const float *A, int cin, const float *W, int cout, const float *bias, int pro_bn, float *Z, int ldz, int stats_bn) const
     {
         PwGemm g;
@@ -245,11 +220,7 @@ struct EncRun {
         if (stats_bn >= 0 && s.train) {
             g.part_sum = ws.part_sum; g.part_sq = ws.part_sq; g.part_rows = ws.part_rows;
             g.stat_lanes = pw_gemm_stat_plan(g.Q, g.chunks, g.n_slots).lanes;
-            if (fc_direct()) {
-                const BnSlot &b = ws.bn[stats_bn];
-                g.fin_gamma = bnp[stats_bn].gamma; g.fin_beta = bnp[stats_bn].beta;
-                g.fin_scale = b.scale; g.fin_shift = b.shift; g.fin_mean = b.mean; g.fin_invstd = b.invstd; g.fin_smean = b.smean; g.fin_suvar = b.suvar;
-            }
+            if (fc_direct()) g.fin = BnFin{bnp[stats_bn].layer, ws.bn[stats_bn]};
         }
         return g;
     }
@@ -257,26 +228,14 @@ struct EncRun {
     int finalize_fc(int bn) const
     {
         if (!s.train || fc_direct()) return AMPNET_OK;
-        BnFinalize f;
-        f.part_sum = ws.part_sum; f.part_sq = ws.part_sq; f.part_rows = ws.part_rows;
-        f.win_off = win_off;
-        f.Q = cdiv(pw_gemm_stat_plan(s.n_slots, s.fc_chunks, s.n_slots).lanes, s.n_slots) * s.n_slots;    // partial slots (kernels.h: PwStatPlan.parts)
-        f.chunks = 1; f.chunk_rows = s.fc_chunk_rows; f.uniform_rows = 0;
-        f.n_slots = s.n_slots; f.C = ws.bn[bn].C;
-        f.gamma = bnp[bn].gamma; f.beta = bnp[bn].beta;
-        f.scale = ws.bn[bn].scale; f.shift = ws.bn[bn].shift; f.mean = ws.bn[bn].mean; f.invstd = ws.bn[bn].invstd;
-        f.stat_mean = ws.bn[bn].smean; f.stat_uvar = ws.bn[bn].suvar;
-        f.merge_ws = ws.merge;
-        return bn_finalize(f, st);
+        const BnPartials part{ws.part_sum, ws.part_sq, ws.part_rows, pw_gemm_stat_plan(s.n_slots, s.fc_chunks, s.n_slots).parts};
+        return bn_finalize(bn_finalize_args(part, bnp[bn].layer, ws.bn[bn], s.n_slots, ws.bn[bn].C, ws.merge), st);
     }
     int pool(int bn, float *pooled, int *arg, float *zext, bool slot_major) const
     {
         PoolFinalize p;
-        if (pend.bn == bn && consumer_fin() && ws.bn[bn].C == 256) {             // the pooled layer's own BatchNorm, finished by this launch
-            const BnSlot &bs = ws.bn[bn];
-            p.pfin_sum = psum(pend.region); p.pfin_sq = psq(pend.region); p.pfin_rows = prows(pend.region); p.pfin_parts = pend.parts;
-            p.pfin_gamma = bnp[bn].gamma; p.pfin_beta = bnp[bn].beta;
-            p.pfin_scale = bs.scale; p.pfin_shift = bs.shift; p.pfin_mean = bs.mean; p.pfin_invstd = bs.invstd; p.pfin_smean = bs.smean; p.pfin_suvar = bs.suvar;
+        if (consumer_fin(bn) && ws.bn[bn].C == 256) {             // the pooled layer's own BatchNorm, finished by this launch
+            p.pfin = owed_pfin();
             pend.bn = -1;
         } else if (int rc = settle(); rc != AMPNET_OK) return rc;
         const bool rows_too = s.train || !precision_is_f32();
@@ -365,7 +324,7 @@ extern "C" int ampnet_encoder_fwd_f32(const float *const *params_host, float *co
     if (!tr) {
         BnFoldItem items[BN_ENC_COUNT];
         for (int i = 0; i < BN_ENC_COUNT; ++i)
-            items[i] = {e.bnp[i].gamma, e.bnp[i].beta, e.bnp[i].rmean, e.bnp[i].rvar, e.ws.bn[i].scale, e.ws.bn[i].shift, e.ws.bn[i].C};
+            items[i] = {e.bnp[i].layer.gamma, e.bnp[i].layer.beta, e.bnp[i].rmean, e.bnp[i].rvar, e.ws.bn[i].scale, e.ws.bn[i].shift, e.ws.bn[i].C};
         TRY(bn_fold(items, BN_ENC_COUNT, 1e-5f, e.st));
     }
 

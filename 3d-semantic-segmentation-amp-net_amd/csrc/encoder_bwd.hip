@@ -3,7 +3,8 @@
 //
 // Walks the forward launch sequence of encoder.hip in reverse.  Per BatchNorm'ed layer l (reverse order):
 //     [pool_bwd | bn_bwd_finalize]  ->  pw_bwd_fused(l): weight gradient partials + dy_{l-1} in one pass  ->  reduce_windows
-//     -> next layer's finalize            (AMPNET_FUSED_BWD=0: the separate pw_wgrad / pw_dgrad launches of pw_bwd.hip)
+//     -> next layer's finalize            (the per-window transform falls back to pw_wgrad / pw_dgrad of pw_bwd.hip when no split of its
+//        windows over workgroups fits)
 // using only what the train-mode forward left in its workspace (pre-BatchNorm z, batch mean / invstd / affine,
 // argmax rows) plus two ping-pong dy buffers.  Train mode only (batch statistics).
 #include <cstdlib>
@@ -37,10 +38,6 @@ static int identity_constants(int n_slots, const float **ones, const float **zer
 
 namespace {
 
-struct BnBwdSlot {
-    float *P1, *P2, *P3, *slot_ab;   // [n_slots, C] x3, [n_slots, C, 2]
-};
-
 struct EncBwdWs {
     float *dyA, *dyB;          // [R, 128] ping-pong
     float *d_local, *d_h;      // [R, 64]
@@ -50,9 +47,8 @@ struct EncBwdWs {
     float *fc_split;                                 // [8, Q, 128] K-split partials of the 4096-output fc_3 data gradient
     float *dT64, *dT64t;       // [Q, 4096]
     float *dWeff, *dT3;        // [Q, 576], [Q, 12]
-    float *srows, *Gm, *c0, *gram, *asum, *wgram;   // [Q*256,128] [S,128,128] [S,128] [S,128,128] [S,128] [S,256,128]: pooled-layer algebra
-    int *srow_row, *srow_cnt;  // [Q*256], [Q]
-    BnBwdSlot bn[BN_ENC_COUNT];
+    float *Gm, *c0, *gram, *asum, *wgram;   // [S,128,128] [S,128] [S,128,128] [S,128] [S,256,128]: pooled-layer algebra
+    BnBwd bn[BN_ENC_COUNT];
     size_t bytes;
 };
 
@@ -69,7 +65,7 @@ struct Carver {
     }
 };
 
-constexpr int WG_CHUNK_ROWS = 1024;     // rows per pw_wgrad workgroup
+constexpr int WG_CHUNK_ROWS = 1024;     // wpart / dbpart hold one partial per window and this many rows (+ one per fused workgroup)
 static int wg_chunks(const EncShape &s) { return cdiv(s.max_rows, WG_CHUNK_ROWS); }
 
 static const int kBnC2[BN_ENC_COUNT] = {64, 128, 256, 256, 128, 64, 64, 64, 128, 256, 256, 128, 64, 128, 128, 256};
@@ -98,21 +94,12 @@ void enc_bwd_carve(const EncShape &s, void *base, EncBwdWs &w)
     w.dT64t = c.take<float>(Q * (size_t)s.chunks * 4096);     // per (window, chunk) partials of the per-window transform gradient
     w.dWeff = c.take<float>(Q * 576);
     w.dT3 = c.take<float>(Q * 12);
-    w.srows = c.take<float>(Q * 256 * 128);
     w.Gm = c.take<float>((size_t)s.n_slots * 128 * 128);
     w.c0 = c.take<float>((size_t)s.n_slots * 128);
     w.gram = c.take<float>((size_t)s.n_slots * 128 * 128);
     w.wgram = c.take<float>((size_t)s.n_slots * 256 * 128);
     w.asum = c.take<float>((size_t)s.n_slots * 128);
-    w.srow_row = c.take<int>(Q * 256);
-    w.srow_cnt = c.take<int>(Q);
-    for (int i = 0; i < BN_ENC_COUNT; ++i) {
-        const size_t n = (size_t)s.n_slots * kBnC2[i];
-        w.bn[i].P1 = c.take<float>(n);
-        w.bn[i].P2 = c.take<float>(n);
-        w.bn[i].P3 = c.take<float>(n);
-        w.bn[i].slot_ab = c.take<float>(2 * n);
-    }
+    for (int i = 0; i < BN_ENC_COUNT; ++i) carve_bn_bwd(c, w.bn[i], s.n_slots, kBnC2[i]);
     w.bytes = align_up(c.off, 256);
 }
 
@@ -131,7 +118,6 @@ struct EncBwd {
     float *const *G;
     const int *win_off;
     const float *gamma[BN_ENC_COUNT];
-    bool fused = true;         // AMPNET_FUSED_BWD=0 falls back to the separate pw_wgrad / pw_dgrad launches
     bool zb = false;           // precision mode 3: the forward workspace holds its z tensors as bf16
     // weight-gradient partials of the fused layers stay in wpart (one region per layer) and are reduced by ONE launch at the end
     mutable size_t wpart_used = 0;
@@ -140,16 +126,17 @@ struct EncBwd {
     mutable int n_deferred = 0;
     // BatchNorm-backward sums: every producer writes its partials (sum dy, sum dy zhat) into one of TWO regions of the forward
     // workspace's partial arrays, alternating, and the constants of that layer are owed: the next fused layer forms them itself from the
-    // region the producer wrote (PwBwd.fin_*: no bn_bwd_finalize launch) while it writes its own partials into the other region;
-    // consumers that are not the fp32 fused kernel get the launch (settle()).
+    // region the producer wrote (PwBwd.fin: no bn_bwd_finalize launch) while it writes its own partials into the other region;
+    // consumers that cannot (bn_bwd_in_kernel(), ragged windows) get the launch (settle()).
     struct Owed {
         bool open = false;
-        int bn = -1, C = 0, parts = 0, chunks = 1;
+        int bn = -1, C = 0, parts = 0;     // one partial per workgroup (+ one per window behind them: the pooled layers' scattered rows)
         const float *pa = nullptr, *pb = nullptr;
     };
     mutable Owed owed;
     mutable int part_region = 0;
-    bool in_kernel_fin = false;      // fp32 fused kernel, uniform windows, no global-batch BatchNorm
+    bool in_kernel_fin = false;      // bn_bwd_in_kernel() and uniform windows (BnBwdFin.rows is ONE count for every slot)
+    BnWindows windows() const { return BnWindows{win_off, s.Q, s.n_slots, s.max_rows, s.R}; }
     size_t region_floats() const { return enc_bwd_part_region_floats(s); }
     float *part_a_out() const { return f.part_sum + (size_t)part_region * region_floats(); }
     float *part_b_out() const { return f.part_sq + (size_t)part_region * region_floats(); }
@@ -157,27 +144,17 @@ struct EncBwd {
     {
         if (!owed.open) return AMPNET_OK;
         owed.open = false;
-        BnBwdFinalize fz;
-        fz.part_a = owed.pa; fz.part_b = owed.pb; fz.win_off = win_off;
-        fz.Q = s.Q; fz.chunks = owed.chunks; fz.part_Q = owed.parts; fz.n_slots = s.n_slots; fz.C = owed.C;
-        fz.uniform_rows = (long)s.max_rows * s.Q == (long)s.R ? s.max_rows : 0;
         const int bn = owed.bn;
-        fz.gamma = gamma[bn]; fz.mean = f.bn[bn].mean; fz.invstd = f.bn[bn].invstd;
-        fz.P1 = b.bn[bn].P1; fz.P2 = b.bn[bn].P2; fz.P3 = b.bn[bn].P3; fz.slot_ab = b.bn[bn].slot_ab;
-        return bn_bwd_finalize(fz, st);
+        return bn_bwd_finalize(bn_bwd_finalize_args(owed.pa, owed.pb, owed.parts, 1, windows(), owed.C, gamma[bn], f.bn[bn], b.bn[bn]), st);
     }
-    // the input layers' weight-gradient kernel as consumer of an owed finalize (bwd_misc.h: PwInputWgrad.fin_*)
-    int input_fin(PwInputWgrad &w, int bn) const
+    // the owed constants of layer `bn` handed to the consumer that forms them in its own kernel (PwBwd.fin, PwInputWgrad.fin); false: the
+    // consumer reads them from memory (launch settle() first)
+    bool hand_over(int bn, BnBwdFin &fin) const
     {
-        if (owed.open && in_kernel_fin && owed.bn == bn && owed.chunks == 1 && owed.C == 64) {
-            w.fin_part_a = owed.pa; w.fin_part_b = owed.pb; w.fin_parts = owed.parts;
-            w.fin_rows = (s.Q / s.n_slots) * s.max_rows;
-            w.fin_gamma = gamma[bn]; w.fin_mean = f.bn[bn].mean; w.fin_invstd = f.bn[bn].invstd;
-            w.fin_P1 = b.bn[bn].P1; w.fin_P2 = b.bn[bn].P2; w.fin_P3 = b.bn[bn].P3; w.fin_slot_ab = b.bn[bn].slot_ab;
-            owed.open = false;
-            return AMPNET_OK;
-        }
-        return settle();
+        if (!(owed.open && in_kernel_fin && owed.bn == bn)) return false;
+        fin = bn_bwd_fin(owed.pa, owed.pb, owed.parts, (s.Q / s.n_slots) * s.max_rows, gamma[bn], f.bn[bn], b.bn[bn]);
+        owed.open = false;
+        return true;
     }
     int flush_deferred() const
     {
@@ -188,21 +165,8 @@ struct EncBwd {
         return reduce_windows_multi(deferred, n, st);
     }
 
-    GradSrc dense(const float *dy, const float *z, int bn, int C) const
-    {
-        GradSrc g;
-        g.dy = dy; g.z = z; g.C = C;
-        g.z_bf16 = (zb && bn >= 0) ? 1 : 0;            // every BatchNorm'ed z of the workspace (the bmm path passes bn < 0 and fp32 tensors)
-        if (bn >= 0) { g.P1 = b.bn[bn].P1; g.P2 = b.bn[bn].P2; g.P3 = b.bn[bn].P3; }
-        return g;
-    }
-    GradSrc sparse(const int *arg, const float *dpm, int slot_major, const float *z, int bn) const
-    {
-        GradSrc g;
-        g.arg = arg; g.dpool = dpm; g.dpool_slot_major = slot_major; g.z = z; g.C = 256;
-        g.P1 = b.bn[bn].P1; g.P2 = b.bn[bn].P2; g.P3 = b.bn[bn].P3;
-        return g;
-    }
+    // dense gradient of layer `bn` (a BatchNorm'ed z of the workspace, bf16 in precision mode 3)
+    GradSrc dense(const float *dy, const float *z, int bn, int C) const { return grad_src(dy, z, C, zb ? 1 : 0, b.bn[bn]); }
     ActSrc act(const float *z, int bn, int C) const
     {
         ActSrc a;
@@ -211,65 +175,15 @@ struct EncBwd {
         if (bn >= 0) { a.s = f.bn[bn].scale; a.t = f.bn[bn].shift; }
         return a;
     }
-    // dW[cx][cy] of a shared weight: per-window partials then ordered reduction
-    int wgrad(const GradSrc &x, const ActSrc &y, float *dW) const
-    {
-        PwWgrad w;
-        w.x = x; w.y = y; w.dWpart = b.wpart; w.ldp = y.C;
-        w.win_off = win_off; w.Q = s.Q; w.n_slots = s.n_slots; w.rows_hint = s.R;
-        w.chunk_rows = WG_CHUNK_ROWS; w.chunks = wg_chunks(s);
-        TRY(pw_wgrad(w, st));
-        return reduce_windows(b.wpart, s.Q * w.chunks, (long)x.C * y.C, x.C, y.C, y.C, dW, y.C, 0, st);
-    }
-    // dy of layer `prev_bn` (masked) + its BatchNorm-backward partial sums, then that layer's constants
-    int dgrad(const GradSrc &g, const float *W, int ldw, const float *prev_z, int prev_bn, int cp, const float *add, float *out) const
-    {
-        PwDgrad d;
-        d.g = g; d.W = W; d.ldw = ldw; d.add = add; d.out = out; d.cp = cp;
-        if (prev_z) {
-            d.prev = act(prev_z, prev_bn, cp);
-            d.prev_mean = f.bn[prev_bn].mean; d.prev_invstd = f.bn[prev_bn].invstd;
-            d.part_a = f.part_sum; d.part_b = f.part_sq;
-        }
-        d.win_off = win_off; d.Q = s.Q; d.n_slots = s.n_slots; d.chunk_rows = s.chunk_rows; d.chunks = s.chunks; d.rows_hint = s.R;
-        TRY(pw_dgrad(d, st));
-        if (prev_z) {
-            BnBwdFinalize fz;
-            fz.part_a = f.part_sum; fz.part_b = f.part_sq; fz.win_off = win_off;
-            fz.Q = s.Q; fz.chunks = s.chunks; fz.n_slots = s.n_slots; fz.C = cp;
-            fz.uniform_rows = (long)s.max_rows * s.Q == (long)s.R ? s.max_rows : 0;
-            fz.gamma = gamma[prev_bn]; fz.mean = f.bn[prev_bn].mean; fz.invstd = f.bn[prev_bn].invstd;
-            fz.P1 = b.bn[prev_bn].P1; fz.P2 = b.bn[prev_bn].P2; fz.P3 = b.bn[prev_bn].P3; fz.slot_ab = b.bn[prev_bn].slot_ab;
-            TRY(bn_bwd_finalize(fz, st));
-        }
-        return AMPNET_OK;
-    }
     // weight gradient + data gradient of one shared layer in one pass over (dy, z, z_prev) (pw_bwd_fused.hip); prev_bn < 0:
     // the layer's input is prev_z itself (no activation, no mask, no sums)
     int layer_bwd(const GradSrc &g, const float *W, float *dW, const float *prev_z, int prev_bn, int cy, const float *add, float *out) const
     {
-        if (!fused || !pw_bwd_supported(g.C, cy)) {
-            TRY(settle());                    // the separate kernels read the constants from memory
-            ActSrc y;
-            if (prev_bn >= 0) y = act(prev_z, prev_bn, cy);
-            else { y.z = prev_z; y.C = cy; }
-            TRY(flush_deferred());            // wgrad() reuses wpart from its start
-            TRY(wgrad(g, y, dW));
-            return dgrad(g, W, cy, prev_bn >= 0 ? prev_z : nullptr, prev_bn, cy, add, out);
-        }
         PwBwd p;
         p.g = g;
         // the constants of the layer g belongs to: formed inside this launch when they are still owed (and g is that layer), else launched now
-        if (owed.open && in_kernel_fin && g.P1 == b.bn[owed.bn].P1 && owed.chunks == 1) {
-            p.fin_part_a = owed.pa; p.fin_part_b = owed.pb; p.fin_parts = owed.parts;
-            p.fin_rows = (s.Q / s.n_slots) * s.max_rows;
-            p.fin_gamma = gamma[owed.bn]; p.fin_mean = f.bn[owed.bn].mean; p.fin_invstd = f.bn[owed.bn].invstd;
-            p.fin_P1 = b.bn[owed.bn].P1; p.fin_P2 = b.bn[owed.bn].P2; p.fin_P3 = b.bn[owed.bn].P3; p.fin_slot_ab = b.bn[owed.bn].slot_ab;
-            owed.open = false;
-            part_region ^= 1;                 // this launch writes the other region
-        } else {
-            TRY(settle());
-        }
+        if (owed.open && g.P1 == b.bn[owed.bn].P1 && hand_over(owed.bn, p.fin)) part_region ^= 1;      // this launch writes the other region
+        else TRY(settle());
         if (prev_bn >= 0) {
             p.prev = act(prev_z, prev_bn, cy);
             p.prev_mean = f.bn[prev_bn].mean; p.prev_invstd = f.bn[prev_bn].invstd;
@@ -293,16 +207,15 @@ struct EncBwd {
         } else {
             TRY(reduce_windows(part, nblk, (long)g.C * cy, g.C, cy, cy, dW, cy, 0, st));
         }
-        if (prev_bn >= 0) TRY(finalize_prev(prev_bn, cy, nblk, 1, p.part_a, p.part_b));
+        if (prev_bn >= 0) TRY(finalize_prev(prev_bn, cy, nblk, p.part_a, p.part_b));
         return AMPNET_OK;
     }
-    // the partials (pa, pb) of layer prev_bn are complete: its constants are owed to the next consumer
-    int finalize_prev(int prev_bn, int cp, int part_Q, int chunks, const float *pa, const float *pb) const
+    // the `parts` partials (pa, pb) of layer prev_bn are complete: its constants are owed to the next consumer
+    int finalize_prev(int prev_bn, int cp, int parts, const float *pa, const float *pb) const
     {
         TRY(settle());
-        owed.open = true; owed.bn = prev_bn; owed.C = cp; owed.parts = part_Q > 0 ? part_Q : s.Q * chunks; owed.chunks = part_Q > 0 ? chunks : chunks;
+        owed.open = true; owed.bn = prev_bn; owed.C = cp; owed.parts = parts;
         owed.pa = pa; owed.pb = pb;
-        if (part_Q <= 0 || chunks != 1) return settle();      // per-(window, chunk) partials of the unfused path: finalize now
         return AMPNET_OK;
     }
     // Backward of a 128 -> 256 layer followed by BatchNorm + ReLU + MaxPool, WITHOUT its [rows, 256] output.
@@ -312,18 +225,12 @@ struct EncBwd {
     int pooled_layer(const float *d_pooled, int slot_major, const int *arg, const float *zext, int bn, const float *W, float *dW,
                      const float *z_prev, int prev_bn, float *dy_out) const
     {
-        PoolBwd p;
-        p.d_pooled = d_pooled; p.slot_major = slot_major; p.arg = arg; p.zext = zext;
-        p.scale = f.bn[bn].scale; p.shift = f.bn[bn].shift; p.mean = f.bn[bn].mean; p.invstd = f.bn[bn].invstd;
-        p.win_off = win_off; p.Q = s.Q; p.n_slots = s.n_slots; p.C = 256;
-        p.dpm = b.dpm; p.P1 = b.bn[bn].P1; p.P2 = b.bn[bn].P2; p.P3 = b.bn[bn].P3; p.slot_ab = b.bn[bn].slot_ab;
-        TRY(pool_bwd(p, st));
-        if (!fused) {
-            SparseRows sr;
-            sr.arg = arg; sr.dpm = b.dpm; sr.slot_major = slot_major; sr.P1 = b.bn[bn].P1; sr.W = W;
-            sr.Q = s.Q; sr.n_slots = s.n_slots; sr.srows = b.srows; sr.srow_row = b.srow_row; sr.srow_cnt = b.srow_cnt;
-            TRY(sparse_rows(sr, st));
-        }
+        PoolBwd pb;
+        pb.d_pooled = d_pooled; pb.slot_major = slot_major; pb.arg = arg; pb.zext = zext;
+        pb.fwd = f.bn[bn];
+        pb.win_off = win_off; pb.Q = s.Q; pb.n_slots = s.n_slots; pb.C = 256;
+        pb.dpm = b.dpm; pb.out = b.bn[bn];
+        TRY(pool_bwd(pb, st));
         TRY(slot_mats(W, b.bn[bn].P2, b.bn[bn].P3, s.n_slots, 256, 128, b.Gm, b.c0, st));
         PooledWgrad pw;
         pw.W = W; pw.P1 = b.bn[bn].P1; pw.P2 = b.bn[bn].P2; pw.P3 = b.bn[bn].P3; pw.gram = b.gram; pw.asum = b.asum;
@@ -331,67 +238,33 @@ struct EncBwd {
         pw.z_prev = z_prev; pw.s_prev = f.bn[prev_bn].scale; pw.t_prev = f.bn[prev_bn].shift; pw.z_bf16 = zb ? 1 : 0;
         pw.Q = s.Q; pw.n_slots = s.n_slots; pw.dW = dW;
         if (s.n_slots <= 10) pw.wgram = b.wgram;
-        SparseFix sf;
-        sf.srows = b.srows; sf.srow_row = b.srow_row; sf.srow_cnt = b.srow_cnt; sf.z_prev = z_prev;
-        sf.s_prev = f.bn[prev_bn].scale; sf.t_prev = f.bn[prev_bn].shift; sf.mean_prev = f.bn[prev_bn].mean; sf.invstd_prev = f.bn[prev_bn].invstd;
-        sf.Q = s.Q; sf.n_slots = s.n_slots; sf.out = dy_out;
-        if (fused) {
-            // one pass over z_prev: per-slot Gram matrix + column sums of a = relu(bn_prev(z_prev)) AND
-            // dy_prev = (a G[slot] + c0[slot]) masked by the previous layer's ReLU, with its BatchNorm-backward sums
-            PwBwd p;
-            p.g.z = z_prev; p.g.C = 128; p.g.act = 1; p.g.P2 = f.bn[prev_bn].scale; p.g.P3 = f.bn[prev_bn].shift; p.g.z_bf16 = zb ? 1 : 0;
-            p.prev = act(z_prev, prev_bn, 128);
-            p.prev_mean = f.bn[prev_bn].mean; p.prev_invstd = f.bn[prev_bn].invstd;
-            p.W = b.Gm; p.ldw = 128; p.w_slot_stride = 128 * 128; p.bias_slot = b.c0;
-            p.blocks_per_slot = pw_bwd_blocks(s.Q, s.n_slots, s.max_rows);
-            const int nblk = p.blocks_per_slot * s.n_slots;
-            if (wpart_used + (size_t)nblk * 128 * 128 > wpart_cap) TRY(flush_deferred());       // the Gram partials go behind the deferred regions
-            float *gpart = b.wpart + wpart_used;
-            TRY(settle());                    // (nothing is owed at the points this is called from; cheap insurance)
-            p.out = dy_out; p.dWpart = gpart; p.dbpart = b.dbpart; p.part_a = part_a_out(); p.part_b = part_b_out();
-            p.win_off = win_off; p.Q = s.Q; p.n_slots = s.n_slots; p.max_rows = s.max_rows; p.rows_hint = s.R;
-            TRY(pw_bwd_fused(p, st));
-            TRY(reduce_slots2(gpart, 128 * 128, b.gram, b.dbpart, 128, b.asum, nblk, 1, s.n_slots, st));
-            TRY(pooled_wgrad(pw, st));
-            // the scattered rows: added after the dense part, their share of the sums goes behind the workgroup partials
-            SparseScatter ss;
-            ss.arg = arg; ss.dpm = b.dpm; ss.slot_major = slot_major; ss.P1 = b.bn[bn].P1; ss.W = W;
-            ss.z_prev = z_prev; ss.s_prev = f.bn[prev_bn].scale; ss.t_prev = f.bn[prev_bn].shift; ss.z_bf16 = zb ? 1 : 0;
-            ss.mean_prev = f.bn[prev_bn].mean; ss.invstd_prev = f.bn[prev_bn].invstd;
-            ss.Q = s.Q; ss.n_slots = s.n_slots; ss.out = dy_out;
-            ss.part_a = p.part_a + (size_t)nblk * 128; ss.part_b = p.part_b + (size_t)nblk * 128;
-            ss.part_chunks = 1; ss.slot_idx = 0;
-            TRY(sparse_scatter(ss, st));
-            return finalize_prev(prev_bn, 128, nblk + s.Q, 1, p.part_a, p.part_b);
-        }
-        // Gram and column sums of a = relu(bn_prev(z_prev)) per slot, then dW
-        {
-            PwWgrad w;
-            w.x.z = z_prev; w.x.C = 128; w.x.act = 1; w.x.P2 = f.bn[prev_bn].scale; w.x.P3 = f.bn[prev_bn].shift;
-            w.y = act(z_prev, prev_bn, 128);
-            w.dWpart = b.wpart; w.ldp = 128; w.dbpart = b.dbpart;
-            w.win_off = win_off; w.Q = s.Q; w.n_slots = s.n_slots; w.rows_hint = s.R;
-            w.chunk_rows = WG_CHUNK_ROWS; w.chunks = wg_chunks(s);
-            TRY(pw_wgrad(w, st));
-            TRY(reduce_slots(b.wpart, s.Q, w.chunks, s.n_slots, 128 * 128, b.gram, st));
-            TRY(reduce_slots(b.dbpart, s.Q, w.chunks, s.n_slots, 128, b.asum, st));
-            TRY(pooled_wgrad(pw, st));
-        }
-        // data gradient: dy_prev = (a G[slot] + c0[slot] + scattered rows) masked by the previous layer's ReLU
-        PwDgrad d;
-        d.g.z = z_prev; d.g.C = 128; d.g.act = 1; d.g.P2 = f.bn[prev_bn].scale; d.g.P3 = f.bn[prev_bn].shift;
-        d.W = b.Gm; d.ldw = 128; d.w_slot_stride = 128 * 128; d.bias_slot = b.c0;
-        d.prev = act(z_prev, prev_bn, 128);
-        d.prev_mean = f.bn[prev_bn].mean; d.prev_invstd = f.bn[prev_bn].invstd;
-        d.part_a = f.part_sum; d.part_b = f.part_sq; d.part_chunks = s.chunks + 1;
-        d.out = dy_out; d.cp = 128;
-        d.win_off = win_off; d.Q = s.Q; d.n_slots = s.n_slots; d.chunk_rows = s.chunk_rows; d.chunks = s.chunks; d.rows_hint = s.R;
-        TRY(pw_dgrad(d, st));
-        // the scattered rows: added after the dense part, with their share of the BatchNorm-backward sums in an extra slot
-        sf.part_a = f.part_sum; sf.part_b = f.part_sq;
-        sf.part_chunks = s.chunks + 1; sf.slot_idx = s.chunks;
-        TRY(sparse_fix(sf, st));
-        return finalize_prev(prev_bn, 128, 0, s.chunks + 1, f.part_sum, f.part_sq);
+        // one pass over z_prev: per-slot Gram matrix + column sums of a = relu(bn_prev(z_prev)) AND
+        // dy_prev = (a G[slot] + c0[slot]) masked by the previous layer's ReLU, with its BatchNorm-backward sums
+        PwBwd p;
+        p.g.z = z_prev; p.g.C = 128; p.g.act = 1; p.g.P2 = f.bn[prev_bn].scale; p.g.P3 = f.bn[prev_bn].shift; p.g.z_bf16 = zb ? 1 : 0;
+        p.prev = act(z_prev, prev_bn, 128);
+        p.prev_mean = f.bn[prev_bn].mean; p.prev_invstd = f.bn[prev_bn].invstd;
+        p.W = b.Gm; p.ldw = 128; p.w_slot_stride = 128 * 128; p.bias_slot = b.c0;
+        p.blocks_per_slot = pw_bwd_blocks(s.Q, s.n_slots, s.max_rows);
+        const int nblk = p.blocks_per_slot * s.n_slots;
+        if (wpart_used + (size_t)nblk * 128 * 128 > wpart_cap) TRY(flush_deferred());       // the Gram partials go behind the deferred regions
+        float *gpart = b.wpart + wpart_used;
+        TRY(settle());                    // (nothing is owed at the points this is called from; cheap insurance)
+        p.out = dy_out; p.dWpart = gpart; p.dbpart = b.dbpart; p.part_a = part_a_out(); p.part_b = part_b_out();
+        p.win_off = win_off; p.Q = s.Q; p.n_slots = s.n_slots; p.max_rows = s.max_rows; p.rows_hint = s.R;
+        TRY(pw_bwd_fused(p, st));
+        TRY(reduce_slots2(gpart, 128 * 128, b.gram, b.dbpart, 128, b.asum, nblk, 1, s.n_slots, st));
+        TRY(pooled_wgrad(pw, st));
+        // the scattered rows: added after the dense part, their share of the sums goes behind the workgroup partials
+        SparseScatter ss;
+        ss.arg = arg; ss.dpm = b.dpm; ss.slot_major = slot_major; ss.P1 = b.bn[bn].P1; ss.W = W;
+        ss.z_prev = z_prev; ss.s_prev = f.bn[prev_bn].scale; ss.t_prev = f.bn[prev_bn].shift; ss.z_bf16 = zb ? 1 : 0;
+        ss.mean_prev = f.bn[prev_bn].mean; ss.invstd_prev = f.bn[prev_bn].invstd;
+        ss.Q = s.Q; ss.n_slots = s.n_slots; ss.out = dy_out;
+        ss.part_a = p.part_a + (size_t)nblk * 128; ss.part_b = p.part_b + (size_t)nblk * 128;
+        ss.part_chunks = 1; ss.slot_idx = 0;
+        TRY(sparse_scatter(ss, st));
+        return finalize_prev(prev_bn, 128, nblk + s.Q, p.part_a, p.part_b);
     }
 
     // T-Net FC head backward: g3 [Q, kk] (slot-major rows) -> parameter grads, d_pool [Q, 256]
@@ -453,17 +326,9 @@ extern "C" int ampnet_encoder_bwd_f32(const float *const *params_host, float *co
     e.P = params_host;
     e.G = grads_host;
     e.win_off = win_off;
-    {
-        const char *env = getenv("AMPNET_FUSED_BWD");
-        e.fused = !(env && env[0] == '0');
-    }
     e.zb = z_storage_bf16();
-    AMPNET_REQUIRE(!e.zb || e.fused, "ampnet_encoder_bwd_f32: bf16 activation storage needs the fused backward");
-    {
-        const char *env = getenv("AMPNET_BWD_FIN_IN_KERNEL");
-        e.in_kernel_fin = e.fused && !bwd_operands_bf16() && !sync_bn_on() && (long)max_rows * Q == (long)total_rows && !(env && env[0] == '0');
-    }
-    e.wpart_cap = e.fused ? ((size_t)Q * (size_t)wg_chunks(e.s) + 320 + n_slots) * 256 * 128 : 0;      // floats in b.wpart (enc_bwd_carve)
+    e.in_kernel_fin = bn_bwd_in_kernel() && (long)max_rows * Q == (long)total_rows;
+    e.wpart_cap = ((size_t)Q * (size_t)wg_chunks(e.s) + 320 + n_slots) * 256 * 128;      // floats in b.wpart (enc_bwd_carve)
     const float *const *P = params_host;
     float *const *G = grads_host;
     for (int i = 0; i < 5; ++i) {
@@ -510,7 +375,7 @@ extern "C" int ampnet_encoder_bwd_f32(const float *const *params_host, float *co
             }
         }
         const int bpw = ipb ? cpw / ipb : 0;                        // workgroups per window
-        if (e.fused && ipb > 0) {
+        if (ipb > 0) {
             // one pass over (d_local, z_c2): dT^T[j][k] = sum_rows d_local[row][j] h[row][k] per window AND
             // d_h[row][k] = sum_j d_local[row][j] T[k][j] (masked by conv_2's ReLU here already: the mask is idempotent and the
             // feature T-Net's conv_1 backward applies it again after adding its own term).  g = dy via identity constants.
@@ -527,8 +392,10 @@ extern "C" int ampnet_encoder_bwd_f32(const float *const *params_host, float *co
             TRY(pw_bwd_fused(p, st));
             TRY(transpose64_slot_major(b.dT64t, b.dT64, Q, n_slots, bpw, 1, d_feat_T, st));
         } else {
+            AMPNET_REQUIRE(!e.zb, "ampnet_encoder_bwd_f32: bf16 activation storage needs the fused backward of the per-window transform");
+            TRY(e.settle());
             PwWgrad w;                                   // dT^T[j][k] = sum_rows d_local[row][j] * h[row][k]
-            w.x = e.dense(b.d_local, nullptr, -1, 64);
+            w.x.dy = b.d_local; w.x.C = 64;
             w.y = e.act(f.z_c2, BN_C2, 64);
             w.dWpart = b.dT64t; w.ldp = 64;
             w.win_off = win_off; w.Q = Q; w.n_slots = n_slots; w.rows_hint = total_rows;
@@ -537,7 +404,7 @@ extern "C" int ampnet_encoder_bwd_f32(const float *const *params_host, float *co
             // window q's matrix (sum of its chunk partials) belongs at the slot-major row the forward used for feat_T
             TRY(transpose64_slot_major(b.dT64t, b.dT64, Q, n_slots, e.s.chunks, 0, d_feat_T, st));
             PwDgrad d;                                   // d_h[row][k] = sum_j d_local[row][j] * T[k][j]
-            d.g = e.dense(b.d_local, nullptr, -1, 64);
+            d.g = w.x;
             d.W = feat_T; d.w_win_stride = 4096; d.perwin_slot_major = 1;
             d.out = b.d_h; d.cp = 64;
             d.win_off = win_off; d.Q = Q; d.n_slots = n_slots; d.chunk_rows = e.s.chunk_rows; d.chunks = e.s.chunks; d.rows_hint = total_rows;
@@ -563,8 +430,8 @@ extern "C" int ampnet_encoder_bwd_f32(const float *const *params_host, float *co
     {
         PwInputWgrad w;
         w.x = x; w.dy = b.dyB; w.W = P[EP_CONV1]; w.T = f.T3; w.mode = 1; w.perwin_slot_major = 1;
-        w.P1 = b.bn[BN_C1].P1; w.P2 = b.bn[BN_C1].P2; w.P3 = b.bn[BN_C1].P3;
-        TRY(e.input_fin(w, BN_C1));            // bn_1's constants: in the kernel when they are still owed, else from memory
+        w.bn = b.bn[BN_C1];
+        if (!e.hand_over(BN_C1, w.fin)) TRY(e.settle());            // bn_1's constants: in the kernel when they are still owed, else from memory
         w.dWeff = b.dWeff; w.win_off = win_off; w.Q = Q; w.n_slots = n_slots;
         TRY(pw_input_wgrad(w, st));
         TRY(input_param_grads(b.dWeff, P[EP_CONV1], f.T3, Q, n_slots, 1, 1, G[EP_CONV1], b.dT3, st));
@@ -579,8 +446,8 @@ extern "C" int ampnet_encoder_bwd_f32(const float *const *params_host, float *co
     {
         PwInputWgrad w;
         w.x = x; w.dy = b.dyB; w.W = P[EP_IT + TP_CONV1]; w.mode = 0;
-        w.P1 = b.bn[BN_T1].P1; w.P2 = b.bn[BN_T1].P2; w.P3 = b.bn[BN_T1].P3;
-        TRY(e.input_fin(w, BN_T1));
+        w.bn = b.bn[BN_T1];
+        if (!e.hand_over(BN_T1, w.fin)) TRY(e.settle());
         w.dWeff = b.dWeff; w.win_off = win_off; w.Q = Q; w.n_slots = n_slots;
         TRY(pw_input_wgrad(w, st));
         TRY(input_param_grads(b.dWeff, P[EP_IT + TP_CONV1], nullptr, Q, n_slots, 0, 0, G[EP_IT + TP_CONV1], nullptr, st));

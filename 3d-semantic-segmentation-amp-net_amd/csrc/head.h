@@ -1,6 +1,6 @@
 // head.h -- parameter tables and workspace layout shared by the head forward and backward.
 #pragma once
-#include "kernels.h"
+#include "bn_wiring.h"
 
 namespace ampnet {
 
@@ -23,11 +23,6 @@ struct HeadShape {
     int logit_B;                   // the logits are [logit_B, C, R / logit_B]: B, or 1 for ampnet_head_fwd_files_f32
 };
 
-struct BnSlot1 {
-    float *scale, *shift, *mean, *invstd, *smean, *suvar;
-    int C;
-};
-
 struct HeadWs {
     // attention: tok [Q,256] qkv [Q,768] probs [B,8,W,W] ctx [Q,256] g2 [Q,256] (out_proj output = the token)
     // GRU:       qkv = gi [Q,192] (W_ih x + b_ih), ctx = gates [Q,4,64] (r, z, n, W_hn h + b_hn), g2 = h [Q,64]; tok / probs unused
@@ -39,7 +34,7 @@ struct HeadWs {
     float *merge;                                  // two-stage bn_finalize scratch
     float *loss_part;                              // [blocks, 2]
     float *z4;                                     // [R, 8] conv_4 output (row-major, padded)
-    BnSlot1 bn2, bn3;
+    BnSlot bn2, bn3;
     size_t bytes;
 };
 
@@ -77,7 +72,7 @@ struct HeadBwdWs {
     float *wpart, *dbpart, *dgb;   // [Q * wchunks, 128*128], [Q * wchunks, 128], [Q, 128] gradient of the per-window token bias
     float *w4part;                 // [blocks, C*64 + C]
     float *part_a, *part_b;        // [max(Q*chunks, blocks), 128]
-    float *P1[2], *P2[2], *P3[2], *slot_ab[2];   // bn2 (128), bn3 (64)
+    BnBwd bn2, bn3;                // (128), (64)
     // attention: d_g2 [Q,256] d_ctx [Q,256] d_qkv [Q,768] hid / slope / d_hid [Q,16]
     // GRU:       d_g2 = dL/dh from conv_2 [Q,64], d_qkv = d(gi) [Q,192], d_ctx = d(gh) [Q,192], hid = h_{t-1} [Q,64]
     float *d_g2, *d_ctx, *d_qkv, *hid, *slope, *d_hid;
@@ -127,7 +122,7 @@ struct HeadOutBwd {
     const float *dlogits;      // [B, C, P]
     const float *z3;           // [R, 64]
     int z_bf16;                // z3 is a bf16 tensor (precision mode 3)
-    const float *scale, *shift, *mean, *invstd;   // bn_3 [64]
+    BnFwd bn;                  // bn_3 [64]: scale / shift / mean / invstd are read
     const float *W;            // [C, 64]
     float drop_p;
     uint32_t drop_seed;

@@ -46,16 +46,6 @@ struct Carver {
         return p;
     }
 };
-void carve_bn(Carver &c, BnSlot1 &b, int C)
-{
-    b.C = C;
-    b.scale = c.take<float>(C);
-    b.shift = c.take<float>(C);
-    b.mean = c.take<float>(C);
-    b.invstd = c.take<float>(C);
-    b.smean = c.take<float>(C);
-    b.suvar = c.take<float>(C);
-}
 }  // namespace
 
 void head_carve(const HeadShape &s, void *base, HeadWs &ws)
@@ -80,8 +70,8 @@ void head_carve(const HeadShape &s, void *base, HeadWs &ws)
     ws.merge = c.take<float>(bn_finalize_merge_floats(1, 128));
     ws.loss_part = c.take<float>((size_t)cdiv(s.R, 128) * 2);
     ws.z4 = c.take<float>(R * HEAD_MAX_CLASSES);
-    carve_bn(c, ws.bn2, 128);
-    carve_bn(c, ws.bn3, 64);
+    carve_bn(c, ws.bn2, 1, 128);
+    carve_bn(c, ws.bn3, 1, 64);
     ws.bytes = align_up(c.off, 256);
 }
 
@@ -101,22 +91,16 @@ int head_points_fwd(const HeadShape &s, HeadWs &ws, const HeadPointParams &p, co
                     uint32_t seed, const HeadLossArgs &lo_, hipStream_t st)
 {
     const bool tr = s.train != 0;
-    const int Q = s.Q, total_rows = s.R, max_rows = s.max_rows, n_classes = s.n_classes;
+    const int Q = s.Q, total_rows = s.R, n_classes = s.n_classes;
     const int zb = z_storage_bf16() ? 1 : 0;         // z2 / z3 are stored as bf16 (precision mode 3)
     if (!tr) {
         BnFoldItem items[2] = {{p.bn2_w, p.bn2_b, p.bn2_mean, p.bn2_var, ws.bn2.scale, ws.bn2.shift, 128},
                                {p.bn3_w, p.bn3_b, p.bn3_mean, p.bn3_var, ws.bn3.scale, ws.bn3.shift, 64}};
         TRY(bn_fold(items, 2, 1e-5f, st));
     }
-    auto finalize = [&](BnSlot1 &b, const float *gamma, const float *beta) {
-        BnFinalize f;
-        f.part_sum = ws.part_sum; f.part_sq = ws.part_sq; f.chunk_rows = s.chunk_rows;
-        f.win_off = win_off; f.n_slots = 1; f.C = b.C;
-        f.part_rows = ws.part_rows; f.Q = pw_gemm_stat_plan(Q, s.chunks, 1).parts; f.chunks = 1;      // one partial per workgroup
-        f.gamma = gamma; f.beta = beta;
-        f.scale = b.scale; f.shift = b.shift; f.mean = b.mean; f.invstd = b.invstd; f.stat_mean = b.smean; f.stat_uvar = b.suvar;
-        f.merge_ws = ws.merge;
-        return bn_finalize(f, st);
+    auto finalize = [&](BnSlot &b, const float *gamma, const float *beta) {
+        const BnPartials part{ws.part_sum, ws.part_sq, ws.part_rows, pw_gemm_stat_plan(Q, s.chunks, 1).parts};      // one partial per workgroup
+        return bn_finalize(bn_finalize_args(part, BnLayer{gamma, beta}, b, 1, b.C, ws.merge), st);
     };
     {   // conv_2: local half + per-window token bias
         PwGemm g;

@@ -1,11 +1,10 @@
 // head_bwd.hip -- C ABI: ampnet_head_bwd_f32 = autograd backward of SegmentationWithAttention.forward
 // (pointNet/model/pointnetAtt.py:176-209) given dL/dlogits; returns dL/d(local features), dL/d(window tokens)
 // and writes every parameter gradient.  Reverse of head.hip's launch sequence:
-//   head_out_bwd (conv_4, dropout, bn_3 ReLU mask)  -> pw_wgrad/pw_dgrad conv_3 -> pw_wgrad/pw_dgrad conv_2
+//   head_out_bwd (conv_4, dropout, bn_3 ReLU mask)  -> pw_bwd_fused conv_3 -> pw_bwd_fused conv_2 (pw_wgrad / pw_dgrad when its
+//   per-window workgroups do not fit the partial buffers)
 //   (the per-window column sums of conv_2's gradient ARE the gradient of the per-window token bias)
 //   -> small SGEMMs for the token half of conv_2, out_proj, in_proj -> attention_core_bwd -> posenc backward.
-#include <cstdlib>
-#include "bwd_misc.h"
 #include "head.h"
 
 namespace ampnet {
@@ -22,7 +21,7 @@ template <bool ZB> __global__ __launch_bounds__(64 * HB_WAVES) void head_out_bwd
 {
     __shared__ float red[HB_WAVES][HEAD_MAX_CLASSES + 3][64];
     const int tid = threadIdx.x, k = tid & 63, wave = tid >> 6;
-    const float sc = a.scale[k], sh = a.shift[k], me = a.mean[k], is = a.invstd[k];
+    const float sc = a.bn.scale[k], sh = a.bn.shift[k], me = a.bn.mean[k], is = a.bn.invstd[k];
     float w[HEAD_MAX_CLASSES], dW[HEAD_MAX_CLASSES], db[HEAD_MAX_CLASSES];
 #pragma unroll
     for (int c = 0; c < HEAD_MAX_CLASSES; ++c) {
@@ -219,13 +218,8 @@ void head_bwd_carve(const HeadShape &s, void *base, HeadBwdWs &w)
     const size_t np = ((Q * (size_t)s.chunks > blocks ? Q * (size_t)s.chunks : blocks) + 256) * 128;
     w.part_a = c.take<float>(np);
     w.part_b = c.take<float>(np);
-    const int Cs[2] = {128, 64};
-    for (int i = 0; i < 2; ++i) {
-        w.P1[i] = c.take<float>(Cs[i]);
-        w.P2[i] = c.take<float>(Cs[i]);
-        w.P3[i] = c.take<float>(Cs[i]);
-        w.slot_ab[i] = c.take<float>(2 * Cs[i]);
-    }
+    carve_bn_bwd(c, w.bn2, 1, 128);
+    carve_bn_bwd(c, w.bn3, 1, 64);
     const bool gru = s.kind == HEAD_KIND_GRU;
     w.d_g2 = c.take<float>(Q * (gru ? GRU_H : 256));
     w.d_ctx = c.take<float>(Q * 256);
@@ -264,41 +258,38 @@ int head_points_bwd(const HeadShape &s, HeadWs &f, HeadBwdWs &b, const HeadPoint
     // the end (seven reduce_windows launches before)
     ReduceItem red[REDUCE_MULTI_MAX];
     int n_red = 0;
-    // BatchNorm-backward constants inside the consuming fused kernel (PwBwd.fin_*) instead of two bn_bwd_finalize launches: fp32 fused path only
-    const char *fenv0 = getenv("AMPNET_FUSED_BWD"), *kenv = getenv("AMPNET_BWD_FIN_IN_KERNEL");
-    const bool fin_in_kernel = !(fenv0 && fenv0[0] == '0') && !(kenv && kenv[0] == '0') && !bwd_operands_bf16() && !sync_bn_on();
+    // BatchNorm-backward constants inside the consuming fused kernel (PwBwd.fin) instead of two bn_bwd_finalize launches
+    const bool fin_in_kernel = bn_bwd_in_kernel();
+    // conv_2's fused form: every workgroup stays inside one window (its column sums of g2 are then a per-window partial of the token-bias
+    // gradient), bpw of them per window -- as long as the partial buffers, sized for wch chunks per window, hold them
+    const int cpw = cdiv(max_rows, pw_bwd_item_rows());
+    int ipb = cpw < 4 ? cpw : 4;
+    while (cpw % ipb) --ipb;
+    const int bpw = cpw / ipb;                                  // workgroups per window
+    const bool conv2_fused = bpw <= wch;
+    AMPNET_REQUIRE(!zb || conv2_fused, "ampnet_head_bwd_f32: bf16 activation storage needs the fused conv_2 backward");
     float *pa3 = b.part_a + align_up((size_t)blocks * 64, 64), *pb3 = b.part_b + align_up((size_t)blocks * 64, 64);   // conv_3's partials: behind head_out_bwd's
     // ---- conv_4 + dropout + bn_3/ReLU mask ------------------------------------------------------------
     {
         HeadOutBwd o;
         o.dlogits = dlogits; o.z3 = f.z3; o.z_bf16 = zb;
-        o.scale = f.bn3.scale; o.shift = f.bn3.shift; o.mean = f.bn3.mean; o.invstd = f.bn3.invstd;
+        o.bn = f.bn3;
         o.W = p_.conv4_w; o.drop_p = drop_p; o.drop_seed = drop_base(seed, 2);
         o.R = R; o.P = R / B; o.C = C;
         o.dy3 = b.dy3; o.part_a = b.part_a; o.part_b = b.part_b; o.dWpart = b.w4part;
         TRY(head_out_bwd(o, st));
         red[n_red++] = ReduceItem{b.w4part, blocks, (long)(C * 64 + C), 1, C * 64, C * 64, g.conv4_w, C * 64};
         red[n_red++] = ReduceItem{b.w4part + C * 64, blocks, (long)(C * 64 + C), 1, C, C, g.conv4_b, C};
-        if (!fin_in_kernel) {                    // else conv_3's fused backward forms bn_3's constants from these partials itself
-            BnBwdFinalize fz;
-            fz.part_a = b.part_a; fz.part_b = b.part_b; fz.win_off = nullptr; fz.Q = 1; fz.chunks = blocks; fz.n_slots = 1; fz.C = 64;
-            fz.uniform_rows = R;
-            fz.gamma = p_.bn3_w; fz.mean = f.bn3.mean; fz.invstd = f.bn3.invstd;
-            fz.P1 = b.P1[1]; fz.P2 = b.P2[1]; fz.P3 = b.P3[1]; fz.slot_ab = b.slot_ab[1];
-            TRY(bn_bwd_finalize(fz, st));
-        }
+        if (!fin_in_kernel)                      // else conv_3's fused backward forms bn_3's constants from these partials itself
+            TRY(bn_bwd_finalize(bn_bwd_finalize_args(b.part_a, b.part_b, 0, blocks, BnWindows{nullptr, 1, 1, R, R}, 64, p_.bn3_w, f.bn3, b.bn3), st));
     }
     // ---- conv_3: z3 = dropout(relu(bn_2(z2))) W3^T + b3 --------------------------------------------------
-    GradSrc g3;
-    g3.dy = b.dy3; g3.z = f.z3; g3.C = 64; g3.P1 = b.P1[1]; g3.P2 = b.P2[1]; g3.P3 = b.P3[1]; g3.z_bf16 = zb;
+    const GradSrc g3 = grad_src(b.dy3, f.z3, 64, zb, b.bn3);
     ActSrc a2;
     a2.z = f.z2; a2.C = 128; a2.z_bf16 = zb; a2.s = f.bn2.scale; a2.t = f.bn2.shift; a2.drop_p = drop_p; a2.drop_seed = drop_base(seed, 1);
-    const char *fenv = getenv("AMPNET_FUSED_BWD");
-    const bool fused = !(fenv && fenv[0] == '0');
-    size_t conv3_w_floats = 0, conv3_b_floats = 0;             // conv_3's partial regions (fused path): conv_2's go behind them
+    size_t conv3_w_floats = 0, conv3_b_floats = 0;             // conv_3's partial regions: conv_2's go behind them
     int conv3_parts = 0;                                       // > 0: bn_2's constants are still owed (conv_2's fused kernel forms them)
-    AMPNET_REQUIRE(!zb || fused, "ampnet_head_bwd_f32: bf16 activation storage needs the fused backward");
-    if (fused) {
+    {
         // one pass over (dy3, z3, z2): weight + bias gradient partials and dy2 with bn_2's backward sums
         PwBwd p;
         p.g = g3; p.prev = a2; p.prev_mean = f.bn2.mean; p.prev_invstd = f.bn2.invstd;
@@ -307,72 +298,28 @@ int head_points_bwd(const HeadShape &s, HeadWs &f, HeadBwdWs &b, const HeadPoint
         p.win_off = win_off; p.Q = Q; p.n_slots = 1; p.max_rows = max_rows; p.rows_hint = R;
         p.blocks_per_slot = pw_bwd_blocks(Q, 1, max_rows);
         const int nblk = p.blocks_per_slot;
-        if (fin_in_kernel) {
-            p.fin_part_a = b.part_a; p.fin_part_b = b.part_b; p.fin_parts = blocks; p.fin_rows = R;
-            p.fin_gamma = p_.bn3_w; p.fin_mean = f.bn3.mean; p.fin_invstd = f.bn3.invstd;
-            p.fin_P1 = b.P1[1]; p.fin_P2 = b.P2[1]; p.fin_P3 = b.P3[1]; p.fin_slot_ab = b.slot_ab[1];
-        }
+        if (fin_in_kernel) p.fin = bn_bwd_fin(b.part_a, b.part_b, blocks, R, p_.bn3_w, f.bn3, b.bn3);
         TRY(pw_bwd_fused(p, st));
         red[n_red++] = ReduceItem{b.wpart, nblk, 64L * 128, 64, 128, 128, g.conv3_w, 128};
         red[n_red++] = ReduceItem{b.dbpart, nblk, 64L, 1, 64, 64, g.conv3_b, 64};
         conv3_w_floats = align_up((size_t)nblk * 64 * 128, 64);
         conv3_b_floats = align_up((size_t)nblk * 64, 64);
         conv3_parts = nblk;
-        const int cpw2 = cdiv(max_rows, pw_bwd_item_rows());
-        int ipb2 = cpw2 < 4 ? cpw2 : 4;
-        while (cpw2 % ipb2) --ipb2;
-        if (!(fin_in_kernel && cpw2 / ipb2 <= wch)) {          // conv_2 will not run the fused kernel (or not in-kernel): bn_2's constants by launch
-            BnBwdFinalize fz;
-            fz.part_a = p.part_a; fz.part_b = p.part_b; fz.win_off = win_off; fz.Q = Q; fz.chunks = 1; fz.part_Q = nblk; fz.n_slots = 1; fz.C = 128;
-            fz.uniform_rows = (long)max_rows * Q == (long)total_rows ? max_rows : 0;
-            fz.gamma = p_.bn2_w; fz.mean = f.bn2.mean; fz.invstd = f.bn2.invstd;
-            fz.P1 = b.P1[0]; fz.P2 = b.P2[0]; fz.P3 = b.P3[0]; fz.slot_ab = b.slot_ab[0];
-            TRY(bn_bwd_finalize(fz, st));
+        if (!(fin_in_kernel && conv2_fused)) {                 // conv_2 will not run the fused kernel (or not in-kernel): bn_2's constants by launch
+            TRY(bn_bwd_finalize(bn_bwd_finalize_args(p.part_a, p.part_b, nblk, 1, BnWindows{win_off, Q, 1, max_rows, total_rows}, 128, p_.bn2_w, f.bn2, b.bn2), st));
             conv3_parts = 0;
         }
-    } else {
-        if (n_red) TRY(reduce_windows_multi(red, n_red, st));
-        n_red = 0;
-        PwWgrad w;
-        w.x = g3; w.y = a2; w.dWpart = b.wpart; w.ldp = 128; w.dbpart = b.dbpart;
-        w.win_off = win_off; w.Q = Q; w.n_slots = 1; w.rows_hint = R; w.chunk_rows = 1024; w.chunks = wch;
-        TRY(pw_wgrad(w, st));
-        TRY(reduce_windows(b.wpart, Q * wch, 64 * 128, 64, 128, 128, g.conv3_w, 128, 0, st));
-        TRY(reduce_windows(b.dbpart, Q * wch, 64, 1, 64, 64, g.conv3_b, 64, 0, st));
-        PwDgrad d;
-        d.g = g3; d.W = p_.conv3_w; d.ldw = 128; d.prev = a2; d.prev_mean = f.bn2.mean; d.prev_invstd = f.bn2.invstd;
-        d.out = b.dy2; d.cp = 128; d.part_a = b.part_a; d.part_b = b.part_b;
-        d.win_off = win_off; d.Q = Q; d.n_slots = 1; d.chunk_rows = s.chunk_rows; d.chunks = s.chunks; d.rows_hint = R;
-        TRY(pw_dgrad(d, st));
-        BnBwdFinalize fz;
-        fz.part_a = b.part_a; fz.part_b = b.part_b; fz.win_off = win_off; fz.Q = Q; fz.chunks = s.chunks; fz.n_slots = 1; fz.C = 128;
-        fz.uniform_rows = (long)max_rows * Q == (long)total_rows ? max_rows : 0;
-        fz.gamma = p_.bn2_w; fz.mean = f.bn2.mean; fz.invstd = f.bn2.invstd;
-        fz.P1 = b.P1[0]; fz.P2 = b.P2[0]; fz.P3 = b.P3[0]; fz.slot_ab = b.slot_ab[0];
-        TRY(bn_bwd_finalize(fz, st));
     }
     // ---- conv_2: z2 = lo W2[:, :64]^T + (token W2[:, 64:]^T + b2)[window] ------------------------------------
-    GradSrc g2;
-    g2.dy = b.dy2; g2.z = f.z2; g2.C = 128; g2.P1 = b.P1[0]; g2.P2 = b.P2[0]; g2.P3 = b.P3[0]; g2.z_bf16 = zb;
-    // fused form: every workgroup stays inside one window, so its column sums of g2 are a per-window partial of the
-    // token-bias gradient
-    const int cpw = cdiv(max_rows, pw_bwd_item_rows());
-    int ipb = cpw < 4 ? cpw : 4;
-    while (cpw % ipb) --ipb;
-    const int bpw = cpw / ipb;                                  // workgroups per window
-    AMPNET_REQUIRE(!zb || bpw <= wch, "ampnet_head_bwd_f32: bf16 activation storage needs the fused conv_2 backward");
-    if (fused && bpw <= wch) {
+    const GradSrc g2 = grad_src(b.dy2, f.z2, 128, zb, b.bn2);
+    if (conv2_fused) {
         PwBwd p;
         p.g = g2; p.prev.z = lo; p.prev.C = 64;
         float *wp2 = b.wpart + conv3_w_floats, *dbp2 = b.dbpart + conv3_b_floats;
         p.W = p_.conv2_w; p.ldw = p_.conv2_ld; p.out = d_lo; p.dWpart = wp2; p.dbpart = dbp2;
         p.win_off = win_off; p.Q = Q; p.n_slots = 1; p.max_rows = max_rows; p.rows_hint = R;
         p.items_per_block = ipb; p.blocks_per_slot = Q * bpw;
-        if (conv3_parts > 0) {
-            p.fin_part_a = pa3; p.fin_part_b = pb3; p.fin_parts = conv3_parts; p.fin_rows = R;
-            p.fin_gamma = p_.bn2_w; p.fin_mean = f.bn2.mean; p.fin_invstd = f.bn2.invstd;
-            p.fin_P1 = b.P1[0]; p.fin_P2 = b.P2[0]; p.fin_P3 = b.P3[0]; p.fin_slot_ab = b.slot_ab[0];
-        }
+        if (conv3_parts > 0) p.fin = bn_bwd_fin(pa3, pb3, conv3_parts, R, p_.bn2_w, f.bn2, b.bn2);
         TRY(pw_bwd_fused(p, st));
         red[n_red++] = ReduceItem{wp2, Q * bpw, 128L * 64, 128, 64, 64, g.conv2_w, g.conv2_ld};
         red[n_red++] = ReduceItem{dbp2, bpw, 128L, Q, 128, bpw * 128, b.dgb, 128};       // per window: the gradient of its token bias
@@ -398,7 +345,7 @@ int head_points_bwd(const HeadShape &s, HeadWs &f, HeadBwdWs &b, const HeadPoint
     if (n_red) TRY(reduce_windows_multi(red, n_red, st));
     // ---- BatchNorm weight / bias gradients ---------------------------------------------------------------------------
     {
-        BnGradItem items[2] = {{b.slot_ab[0], g.bn2_w, g.bn2_b, 128, 1}, {b.slot_ab[1], g.bn3_w, g.bn3_b, 64, 1}};
+        BnGradItem items[2] = {{b.bn2.slot_ab, g.bn2_w, g.bn2_b, 128, 1}, {b.bn3.slot_ab, g.bn3_w, g.bn3_b, 64, 1}};
         TRY(bn_param_grads(items, 2, st));
     }
     return AMPNET_OK;

@@ -2,6 +2,7 @@
 // and the kernels.  Not part of the public ABI.
 #pragma once
 #include "common.h"
+#include "bn_desc.h"
 #include "mfma_types.h"
 
 namespace ampnet {
@@ -69,20 +70,16 @@ struct PwGemm {
     // partial `lane` belongs to slot lane % n_slots, part_rows[lane] = rows it covers; stat_lanes from pw_gemm_stat_plan()
     int *part_rows = nullptr;
     int stat_lanes = 0;
-    // plan.direct (one block of rows per slot): the workgroup finishes the BatchNorm constants itself, no partial, no bn_finalize launch
-    const float *fin_gamma = nullptr, *fin_beta = nullptr;
-    float *fin_scale = nullptr, *fin_shift = nullptr, *fin_mean = nullptr, *fin_invstd = nullptr, *fin_smean = nullptr, *fin_suvar = nullptr;
-    float fin_eps = 1e-5f;
+    // plan.direct (one block of rows per slot): the workgroup finishes the BatchNorm constants itself (fin.out.scale != nullptr), no partial,
+    // no bn_finalize launch
+    BnFin fin;
+    float eps = 1e-5f;             // of fin and of pfin
     // Consumer-side finalize of the INPUT's BatchNorm (train mode, per-workgroup statistics, PRO >= 1): instead of a bn_finalize launch
     // between producer and consumer (~11 us of a mostly idle chip per layer), every workgroup of the consumer merges the producer's
-    // per-workgroup partials of ITS slot (pfin_parts / n_slots <= 114 partials of cin channels, out of L2) into the prologue constants it
-    // is about to stage; lane j == 0 of each slot (column block 0) also writes the arrays the backward, later consumers and the
+    // per-workgroup partials of ITS slot (pfin.part.parts / n_slots <= 114 partials of cin channels, out of L2) into the prologue constants
+    // it is about to stage; lane j == 0 of each slot (column block 0) also writes the arrays the backward, later consumers and the
     // running-statistics update read.  The producer's partials must not be the buffers this launch writes its own partials to.
-    const float *pfin_sum = nullptr, *pfin_sq = nullptr;
-    const int *pfin_rows = nullptr;
-    int pfin_parts = 0;                       // partial slots (a multiple of n_slots; empty ones carry rows 0)
-    const float *pfin_gamma = nullptr, *pfin_beta = nullptr;
-    float *pfin_scale = nullptr, *pfin_shift = nullptr, *pfin_mean = nullptr, *pfin_invstd = nullptr, *pfin_smean = nullptr, *pfin_suvar = nullptr;
+    BnPfin pfin;                   // pfin.part.sum != nullptr: on
 };
 struct PwStatPlan {
     int lanes = 1;                 // workgroups that take part
@@ -159,17 +156,15 @@ int pw_input(const PwInput &a, hipStream_t st);
 
 // BatchNorm statistics -> affine.  One block per (slot, 64 channels).
 struct BnFinalize {
-    const float *part_sum = nullptr, *part_sq = nullptr;   // [Q * chunks, C] chunk mean, chunk M2
+    BnPartials part;               // sum / sq [Q * chunks, C] chunk mean, chunk M2; rows: explicit rows per partial [Q * chunks] or nullptr
+                                   // (then win_off / chunk_rows say them); parts is not read: Q * chunks partials
     int chunk_rows = 512;
     int uniform_rows = 0;          // > 0: every window has this many rows (no win_off look-ups in the loops)
     const int *win_off = nullptr;
     int Q = 0, chunks = 1, n_slots = 1, C = 0;
-    const float *gamma = nullptr, *beta = nullptr;
+    BnLayer layer;
     float eps = 1e-5f;
-    float *scale = nullptr, *shift = nullptr;   // [n_slots, C]   y = z * scale + shift
-    float *mean = nullptr, *invstd = nullptr;   // [n_slots, C]   (saved for backward)
-    float *stat_mean = nullptr, *stat_uvar = nullptr;   // [n_slots, C] batch mean / unbiased var for the running update
-    const int *part_rows = nullptr; // explicit rows per partial [Q * chunks] (instead of win_off / chunk_rows)
+    BnFwd out;                     // mean / invstd and the smean / suvar pair may be nullptr
     float *merge_ws = nullptr;     // optional scratch, bn_finalize_merge_floats(n_slots, C) floats: enables the two-stage form
     // global-batch form (sync_bn.hip): the partial arrays are `gather_ranks` segments of `gather_seg` floats, one per rank, each
     // {mean [n_slots, C], M2 [n_slots, C], rows [n_slots] as int}; partial (rank, slot) belongs to slot `slot`
@@ -185,6 +180,13 @@ int sync_bn_bwd_constants(const float *slot_ab, const int *win_off, int Q, int n
                           const float *scale, const float *mean, const float *invstd, float *P1, float *P2, float *P3, hipStream_t st);
 int sync_bn_fc_apply(const float *da, const float *z, const float *scale, const float *shift, const float *mean, const float *invstd,
                      const float *slot_ab, int n_slots, int per, int C, float *g, hipStream_t st);
+// ---- who finishes a BatchNorm: its consumer, inside its own kernel, or a launched finalize.  The host code asks these two, and so do the
+// AMPNET_REQUIREs in front of the kernels that have the in-kernel form ----
+// forward (PwGemm.fin / pfin, PoolFinalize.pfin): batch statistics, and not the global batch (the ranks' partials are merged by bn_finalize)
+inline bool bn_fwd_in_kernel(bool train) { return train && !sync_bn_on(); }
+// backward (PwBwd.fin, PwInputWgrad.fin): fp32 operands (the bf16 kernels have no such prologue) and not the global batch (the sums are
+// all-reduced by bn_bwd_finalize); the callers add what their shapes need (uniform windows, per-workgroup partials)
+inline bool bn_bwd_in_kernel() { return !bwd_operands_bf16() && !sync_bn_on(); }
 inline size_t bn_finalize_merge_floats(int n_slots, int C) { return (size_t)n_slots * 16 * (2 * (size_t)C + 1); }
 int bn_finalize(const BnFinalize &a, hipStream_t st);
 // the finalize launch of the global-batch form on its own: `all` holds `ranks` gathered segments of `seg` floats (see gather_ranks above);
@@ -222,13 +224,9 @@ struct PoolFinalize {
     int *arg = nullptr;           // [Q, C] or nullptr
     float *zext = nullptr;        // [Q, C] or nullptr: the pre-BatchNorm extreme itself (row q)
     // train mode, C == 256: the pooled layer's BatchNorm is finished HERE from the per-workgroup partials of the layer's GEMM (as
-    // PwGemm.pfin_*: no bn_finalize launch in between); scale / shift above are then OUTPUTS like the other arrays
-    const float *pfin_sum = nullptr, *pfin_sq = nullptr;
-    const int *pfin_rows = nullptr;
-    int pfin_parts = 0;
-    const float *pfin_gamma = nullptr, *pfin_beta = nullptr;
-    float pfin_eps = 1e-5f;
-    float *pfin_scale = nullptr, *pfin_shift = nullptr, *pfin_mean = nullptr, *pfin_invstd = nullptr, *pfin_smean = nullptr, *pfin_suvar = nullptr;
+    // PwGemm.pfin: no bn_finalize launch in between); scale / shift above are then not read
+    BnPfin pfin;
+    float eps = 1e-5f;
 };
 int pool_finalize(const PoolFinalize &a, hipStream_t st);
 
@@ -353,16 +351,12 @@ struct PwBwd {
     int items_per_block = 0;       // > 0: fixed share of (window, pw_bwd_item_rows()-row chunk) items per workgroup; a divisor of the
                                    // chunks per window keeps every workgroup inside one window (per-window dbpart sums)
     long rows_hint = 0;
-    // Consumer-side BatchNorm-backward constants (fp32 kernel; no bn_bwd_finalize launch between two layers): fin_part_a != nullptr ->
-    // every workgroup sums the fin_parts partials (sum dy, sum dy zhat) [fin_parts, CX] of ITS slot (partial i belongs to slot
-    // i % n_slots) that the producer of g.dy left, in a fixed order, and forms P1..P3 itself (g.P1..P3 are then outputs: the first
-    // workgroup of every slot writes them and slot_ab for the parameter gradients).  The partial arrays must not be the ones this
-    // launch writes (part_a / part_b): the callers alternate two regions.
-    const float *fin_part_a = nullptr, *fin_part_b = nullptr;
-    int fin_parts = 0;
-    int fin_rows = 0;              // rows of one slot (uniform windows)
-    const float *fin_gamma = nullptr, *fin_mean = nullptr, *fin_invstd = nullptr;   // [CX], [n_slots, CX] x2 of the layer g belongs to
-    float *fin_P1 = nullptr, *fin_P2 = nullptr, *fin_P3 = nullptr, *fin_slot_ab = nullptr;
+    // Consumer-side BatchNorm-backward constants (fp32 kernel; no bn_bwd_finalize launch between two layers): fin.part_a != nullptr ->
+    // every workgroup sums the fin.parts partials (sum dy, sum dy zhat) [fin.parts, CX] of ITS slot that the producer of g.dy left, in
+    // a fixed order, and forms P1..P3 of the layer g belongs to itself (the first workgroup of every slot writes fin.out, the arrays
+    // g.P1..P3 point to among them).  The partial arrays must not be the ones this launch writes (part_a / part_b): the callers
+    // alternate two regions.
+    BnBwdFin fin;
     int dbg_row_wrap = 0;          // TIMING EXPERIMENT ONLY (AMPNET_PWBWD_ROWWRAP=n): the staging loads read row % n -- wrong results, cache-resident inputs
 };
 int pw_bwd_blocks(int Q, int n_slots, int max_rows);     // blocks_per_slot for this shape (grid = that * n_slots)
@@ -402,8 +396,7 @@ struct BnBwdFinalize {
     int Q = 0, chunks = 1, n_slots = 1, C = 0;
     int part_Q = 0;                                     // > 0: the partial arrays hold part_Q * chunks rows (index % n_slots = slot)
     const float *gamma = nullptr, *mean = nullptr, *invstd = nullptr;   // gamma [C]; mean / invstd [n_slots, C]
-    float *P1 = nullptr, *P2 = nullptr, *P3 = nullptr;  // [n_slots, C]
-    float *slot_ab = nullptr;                           // [n_slots, C, 2]
+    BnBwd out;
 };
 int bn_bwd_finalize(const BnBwdFinalize &a, hipStream_t st);
 
@@ -420,11 +413,11 @@ struct PoolBwd {
     int slot_major = 0;
     const int *arg = nullptr;          // [Q, C]
     const float *zext = nullptr;       // [Q, C] pre-BN value of the pooled layer at its argmax row (pool_finalize)
-    const float *scale = nullptr, *shift = nullptr, *mean = nullptr, *invstd = nullptr;   // [n_slots, C]
+    BnFwd fwd;                         // the pooled layer's scale / shift / mean / invstd are read
     const int *win_off = nullptr;
     int Q = 0, n_slots = 1, C = 256;
     float *dpm = nullptr;              // [Q, C] masked pooled grads, row = prow(q)
-    float *P1 = nullptr, *P2 = nullptr, *P3 = nullptr, *slot_ab = nullptr;
+    BnBwd out;
 };
 int pool_bwd(const PoolBwd &a, hipStream_t st);
 

@@ -16,6 +16,9 @@
 namespace ampnet {
 namespace {
 
+// the BatchNorm descriptors (bn_desc.h) are the workspaces' arrays, which are not const; a probe's read-only inputs enter them through here
+float *ro(const float *p) { return const_cast<float *>(p); }
+
 // the window offsets on the host: Q + 1 ascending values from 0 up; total rows and the largest window
 int read_win_off(const int32_t *win_off, int64_t n, int Q, hipStream_t st, int64_t &rows, int &max_rows)
 {
@@ -101,13 +104,11 @@ extern "C" int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream
     g.win_off = d->uniform_rows > 0 ? nullptr : d->win_off;
     g.Q = d->Q; g.chunk_rows = d->chunk_rows; g.chunks = d->chunks; g.rows_hint = rows;
     g.uniform_rows = d->uniform_rows; g.identity_k = d->identity_k;
-    g.fin_gamma = d->fin_gamma; g.fin_beta = d->fin_beta; g.fin_eps = d->fin_eps;
-    g.fin_scale = d->fin_scale; g.fin_shift = d->fin_shift; g.fin_mean = d->fin_mean; g.fin_invstd = d->fin_invstd;
-    g.fin_smean = d->fin_smean; g.fin_suvar = d->fin_suvar;
-    g.pfin_sum = d->pfin_sum; g.pfin_sq = d->pfin_sq; g.pfin_rows = d->pfin_rows; g.pfin_parts = d->pfin_parts;
-    g.pfin_gamma = d->pfin_gamma; g.pfin_beta = d->pfin_beta;
-    g.pfin_scale = d->pfin_scale; g.pfin_shift = d->pfin_shift; g.pfin_mean = d->pfin_mean; g.pfin_invstd = d->pfin_invstd;
-    g.pfin_smean = d->pfin_smean; g.pfin_suvar = d->pfin_suvar;
+    g.eps = d->fin_eps;
+    g.fin = BnFin{{d->fin_gamma, d->fin_beta}, {d->fin_scale, d->fin_shift, d->fin_mean, d->fin_invstd, d->fin_smean, d->fin_suvar}};
+    g.pfin = BnPfin{{d->pfin_sum, d->pfin_sq, d->pfin_rows, d->pfin_parts},
+                    {d->pfin_gamma, d->pfin_beta},
+                    {d->pfin_scale, d->pfin_shift, d->pfin_mean, d->pfin_invstd, d->pfin_smean, d->pfin_suvar}};
     return pw_gemm(g, st);
 }
 
@@ -125,9 +126,8 @@ PwBwd bwd_record(const AmpnetPwBwdProbe *d)
     p.dWpart = d->dWpart; p.dbpart = d->dbpart; p.part_a = d->part_a; p.part_b = d->part_b;
     p.win_off = d->win_off; p.Q = d->Q; p.n_slots = d->n_slots; p.max_rows = d->max_rows;
     p.blocks_per_slot = d->blocks_per_slot; p.items_per_block = d->items_per_block;
-    p.fin_part_a = d->fin_part_a; p.fin_part_b = d->fin_part_b; p.fin_parts = d->fin_parts; p.fin_rows = d->fin_rows;
-    p.fin_gamma = d->fin_gamma; p.fin_mean = d->fin_mean; p.fin_invstd = d->fin_invstd;
-    p.fin_P1 = d->fin_P1; p.fin_P2 = d->fin_P2; p.fin_P3 = d->fin_P3; p.fin_slot_ab = d->fin_slot_ab;
+    p.fin = BnBwdFin{d->fin_part_a, d->fin_part_b, d->fin_parts, d->fin_rows, d->fin_gamma, d->fin_mean, d->fin_invstd,
+                     {d->fin_P1, d->fin_P2, d->fin_P3, d->fin_slot_ab}};
     p.dbg_row_wrap = 0;
     return p;
 }
@@ -355,9 +355,9 @@ extern "C" int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *
         AMPNET_REQUIRE(d->P1 && d->P2 && d->P3 && d->P_n >= S * C && d->slot_ab && d->slot_ab_n >= 2 * S * C, "probe_pooled_bwd: P1..P3 / slot_ab short");
         PoolBwd p;
         p.d_pooled = d->d_pooled; p.slot_major = d->slot_major; p.arg = d->arg; p.zext = d->zext;
-        p.scale = d->scale; p.shift = d->shift; p.mean = d->mean; p.invstd = d->invstd;
+        p.fwd.scale = ro(d->scale); p.fwd.shift = ro(d->shift); p.fwd.mean = ro(d->mean); p.fwd.invstd = ro(d->invstd);
         p.win_off = d->win_off; p.Q = d->Q; p.n_slots = d->n_slots; p.C = d->C;
-        p.dpm = d->dpm; p.P1 = d->P1; p.P2 = d->P2; p.P3 = d->P3; p.slot_ab = d->slot_ab;
+        p.dpm = d->dpm; p.out = BnBwd{d->P1, d->P2, d->P3, d->slot_ab};
         return pool_bwd(p, st);
     }
     case 2: {
@@ -445,11 +445,10 @@ extern "C" int ampnet_probe_input_wgrad_f32(const AmpnetInputWgradProbe *d, void
     }
     PwInputWgrad a;
     a.x = d->x; a.dy = d->dy; a.W = d->W; a.T = d->mode ? d->T : nullptr; a.mode = d->mode; a.perwin_slot_major = d->perwin_slot_major;
-    a.fin_part_a = d->fin_part_a; a.fin_part_b = d->fin_part_b; a.fin_parts = d->fin_parts; a.fin_rows = d->fin_rows;
-    a.fin_gamma = d->fin_gamma; a.fin_mean = d->fin_mean; a.fin_invstd = d->fin_invstd;
-    a.fin_P1 = d->fin_P1; a.fin_P2 = d->fin_P2; a.fin_P3 = d->fin_P3; a.fin_slot_ab = d->fin_slot_ab;
+    a.fin = BnBwdFin{d->fin_part_a, d->fin_part_b, d->fin_parts, d->fin_rows, d->fin_gamma, d->fin_mean, d->fin_invstd,
+                     {d->fin_P1, d->fin_P2, d->fin_P3, d->fin_slot_ab}};
     if (!d->fin_part_a) {
-        a.P1 = d->P1; a.P2 = d->P2; a.P3 = d->P3;
+        a.bn.P1 = ro(d->P1); a.bn.P2 = ro(d->P2); a.bn.P3 = ro(d->P3);
     }
     a.dWeff = d->dWeff; a.win_off = d->win_off; a.Q = d->Q; a.n_slots = d->n_slots;
     return pw_input_wgrad(a, st);
@@ -549,7 +548,7 @@ extern "C" int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream)
         AMPNET_REQUIRE(d->w4part && d->w4part_n >= blocks * (C * 64 + C), "probe_head: w4part short");
         HeadOutBwd o;
         o.dlogits = d->dlogits; o.z3 = d->z3; o.z_bf16 = d->z_bf16 ? 1 : 0;
-        o.scale = d->scale; o.shift = d->shift; o.mean = d->mean; o.invstd = d->invstd;
+        o.bn.scale = ro(d->scale); o.bn.shift = ro(d->shift); o.bn.mean = ro(d->mean); o.bn.invstd = ro(d->invstd);
         o.W = d->w4; o.drop_p = d->drop_p; o.drop_seed = d->drop_seed;
         o.R = d->R; o.P = d->P; o.C = d->C;
         o.dy3 = d->dy3; o.part_a = d->part_a; o.part_b = d->part_b; o.dWpart = d->w4part;
@@ -664,8 +663,8 @@ int probe_bn_finalize(const AmpnetBnProbe *d, hipStream_t st)
     AMPNET_REQUIRE((d->stat_mean == nullptr) == (d->stat_uvar == nullptr) && (!d->stat_mean || (d->stat_mean_n >= S * C && d->stat_uvar_n >= S * C)),
                    "probe_bn: stat_mean / stat_uvar short");
     BnFinalize a;
-    a.n_slots = d->n_slots; a.C = d->C; a.gamma = d->gamma; a.beta = d->beta; a.eps = d->eps;
-    a.scale = d->scale; a.shift = d->shift; a.mean = d->mean; a.invstd = d->invstd; a.stat_mean = d->stat_mean; a.stat_uvar = d->stat_uvar;
+    a.n_slots = d->n_slots; a.C = d->C; a.layer = BnLayer{d->gamma, d->beta}; a.eps = d->eps;
+    a.out = BnFwd{d->scale, d->shift, d->mean, d->invstd, d->stat_mean, d->stat_uvar};
     if (d->op == 2) {
         const int64_t body = S * (2 * C + 1);
         AMPNET_REQUIRE(d->gather_ranks >= 1 && d->gather_ranks <= 64 && d->gather_seg >= body, "probe_bn: gather_ranks %d, gather_seg %lld", d->gather_ranks,
@@ -689,7 +688,7 @@ int probe_bn_finalize(const AmpnetBnProbe *d, hipStream_t st)
         AMPNET_REQUIRE((int64_t)d->chunks * d->chunk_rows >= max_rows, "probe_bn: chunks do not cover a window of %d rows", max_rows);
     }
     AMPNET_REQUIRE(!d->merge_ws || d->merge_ws_n >= (int64_t)bn_finalize_merge_floats(d->n_slots, d->C), "probe_bn: merge_ws short");
-    a.part_sum = d->part_sum; a.part_sq = d->part_sq; a.part_rows = d->part_rows; a.chunk_rows = d->chunk_rows;
+    a.part = BnPartials{d->part_sum, d->part_sq, d->part_rows, d->Q * d->chunks}; a.chunk_rows = d->chunk_rows;
     a.uniform_rows = d->part_rows ? 0 : d->uniform_rows; a.win_off = (d->part_rows || d->uniform_rows > 0) ? nullptr : d->win_off;
     a.Q = d->Q; a.chunks = d->chunks; a.merge_ws = d->merge_ws;
     return bn_finalize(a, st);
@@ -768,9 +767,8 @@ int probe_pool_finalize(const AmpnetBnProbe *d, hipStream_t st)
     AMPNET_REQUIRE(d->gamma && d->gamma_n >= 256 && d->beta && d->beta_n >= 256, "probe_bn: gamma / beta short");
     AMPNET_REQUIRE(d->mean && d->mean_n >= S * C && d->invstd && d->invstd_n >= S * C && d->stat_mean && d->stat_mean_n >= S * C && d->stat_uvar && d->stat_uvar_n >= S * C,
                    "probe_bn: the BatchNorm outputs [n_slots, 256] short");
-    a.pfin_sum = d->part_sum; a.pfin_sq = d->part_sq; a.pfin_rows = d->part_rows; a.pfin_parts = d->pfin_parts;
-    a.pfin_gamma = d->gamma; a.pfin_beta = d->beta; a.pfin_eps = d->eps;
-    a.pfin_scale = d->scale; a.pfin_shift = d->shift; a.pfin_mean = d->mean; a.pfin_invstd = d->invstd; a.pfin_smean = d->stat_mean; a.pfin_suvar = d->stat_uvar;
+    a.pfin = BnPfin{{d->part_sum, d->part_sq, d->part_rows, d->pfin_parts}, {d->gamma, d->beta}, {d->scale, d->shift, d->mean, d->invstd, d->stat_mean, d->stat_uvar}};
+    a.eps = d->eps;
     return pool_finalize(a, st);
 }
 
@@ -795,7 +793,7 @@ int probe_bn_bwd_finalize(const AmpnetBnProbe *d, hipStream_t st)
     BnBwdFinalize a;
     a.part_a = d->part_a; a.part_b = d->part_b; a.win_off = d->uniform_rows > 0 ? nullptr : d->win_off; a.uniform_rows = d->uniform_rows;
     a.Q = d->Q; a.chunks = d->chunks; a.n_slots = d->n_slots; a.C = d->C; a.part_Q = d->part_Q;
-    a.gamma = d->gamma; a.mean = d->mean; a.invstd = d->invstd; a.P1 = d->P1; a.P2 = d->P2; a.P3 = d->P3; a.slot_ab = d->slot_ab;
+    a.gamma = d->gamma; a.mean = d->mean; a.invstd = d->invstd; a.out = BnBwd{d->P1, d->P2, d->P3, d->slot_ab};
     return bn_bwd_finalize(a, st);
 }
 

@@ -6,7 +6,7 @@
 // metadata and its sequence of vector / LDS / memory instructions and waits (compared on the device assembly of both versions).  The bf16 and
 // the split kernels keep both with the helpers below.  The fp32 kernel does not -- even the work split alone as a function renumbers the
 // staging registers and moves instructions in 8 of its 13 instantiations -- so it shares the constants only and keeps its own copy of the
-// split and the walk.  The fin_* prologue, the D-role lane constants and the flush (dWpart tile stores, dbpart and part_a / part_b
+// split and the walk.  The PwBwd.fin prologue, the D-role lane constants and the flush (dWpart tile stores, dbpart and part_a / part_b
 // reductions) were tried as functions in every kernel and changed the stream (the dense split kernel sits at 256 VGPRs and spills
 // differently with each of them): they stay per kernel.  Staging, role assignment, K loops and epilogues are where the kernels really differ.
 #pragma once

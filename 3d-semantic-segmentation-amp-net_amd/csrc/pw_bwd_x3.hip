@@ -102,18 +102,18 @@ __global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
     const int cqx = tid % QX, rsx = (tid % STAGE) / QX;
     const bool stager = tid < STAGE;                 // (Gram form: waves 0 .. 3 = the W role)
     f32x4 p1 = {1.f, 1.f, 1.f, 1.f}, p2 = {0.f, 0.f, 0.f, 0.f}, p3 = {0.f, 0.f, 0.f, 0.f};
-    if (!GRAM && a.fin_part_a) {
-        // the BatchNorm-backward constants of this layer from the partial sums its producer left (pw_bwd_fused.hip: fin_*)
+    if (!GRAM && a.fin.part_a) {
+        // the BatchNorm-backward constants of this layer from the partial sums its producer left (pw_bwd_fused.hip: PwBwd.fin)
         double sa[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
-        const int per_slot_parts = (a.fin_parts - slot + a.n_slots - 1) / a.n_slots;
+        const int per_slot_parts = (a.fin.parts - slot + a.n_slots - 1) / a.n_slots;
         for (int k0 = rsx; k0 < per_slot_parts; k0 += SX * 8) {
             f32x4 va[8], vb[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = k0 + SX * u;
                 const size_t o = (size_t)(slot + (k < per_slot_parts ? k : 0) * a.n_slots) * CX + 4 * cqx;
-                va[u] = *reinterpret_cast<const f32x4 *>(a.fin_part_a + o);
-                vb[u] = *reinterpret_cast<const f32x4 *>(a.fin_part_b + o);
+                va[u] = *reinterpret_cast<const f32x4 *>(a.fin.part_a + o);
+                vb[u] = *reinterpret_cast<const f32x4 *>(a.fin.part_b + o);
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
             redd[((size_t)rsx * CX + 4 * cqx + c) * 2 + 1] = sb[c];
         }
         __syncthreads();
-        const double n = (double)a.fin_rows;
+        const double n = (double)a.fin.rows;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int ch = 4 * cqx + c;
@@ -143,21 +143,21 @@ __global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3_kernel(PwBwd a)
                 Bs += redd[((size_t)gq * CX + ch) * 2 + 1];
             }
             const size_t o = (size_t)slot * CX + ch;
-            const double invstd = a.fin_invstd[o], mean = a.fin_mean[o];
-            const double s = (double)a.fin_gamma[ch] * invstd;
+            const double invstd = a.fin.invstd[o], mean = a.fin.mean[o];          // bn_bwd_constants (bn_desc.h) is the definition of these lines
+            const double s = (double)a.fin.gamma[ch] * invstd;
             const double q2 = -s * invstd * Bs / n;
             p1[c] = (float)s;
             p2[c] = (float)q2;
             p3[c] = (float)(-s * A / n - q2 * mean);
             if (jb == 0 && rsx == 0) {                       // one writer per slot: the arrays other kernels read
-                a.fin_slot_ab[o * 2 + 0] = (float)A;
-                a.fin_slot_ab[o * 2 + 1] = (float)Bs;
+                a.fin.out.slot_ab[o * 2 + 0] = (float)A;
+                a.fin.out.slot_ab[o * 2 + 1] = (float)Bs;
             }
         }
         if (jb == 0 && rsx == 0) {
-            *reinterpret_cast<f32x4 *>(a.fin_P1 + (size_t)slot * CX + 4 * cqx) = p1;
-            *reinterpret_cast<f32x4 *>(a.fin_P2 + (size_t)slot * CX + 4 * cqx) = p2;
-            *reinterpret_cast<f32x4 *>(a.fin_P3 + (size_t)slot * CX + 4 * cqx) = p3;
+            *reinterpret_cast<f32x4 *>(a.fin.out.P1 + (size_t)slot * CX + 4 * cqx) = p1;
+            *reinterpret_cast<f32x4 *>(a.fin.out.P2 + (size_t)slot * CX + 4 * cqx) = p2;
+            *reinterpret_cast<f32x4 *>(a.fin.out.P3 + (size_t)slot * CX + 4 * cqx) = p3;
         }
         __syncthreads();                                             // the scratch becomes the first tile
     } else {
@@ -598,19 +598,19 @@ __global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
 
     // ---- BatchNorm-backward constants of the layer g belongs to (formed here from the producer's partial sums, or read) ----
     f32x4 p1 = {1.f, 1.f, 1.f, 1.f}, p2 = {0.f, 0.f, 0.f, 0.f}, p3 = {0.f, 0.f, 0.f, 0.f};
-    if (a.fin_part_a) {
-        // every thread takes part (512 = FG groups of QX channel quads), pw_bwd_fused.hip: fin_*
+    if (a.fin.part_a) {
+        // every thread takes part (512 = FG groups of QX channel quads), pw_bwd_fused.hip: PwBwd.fin
         const int fq = tid % QX, fg = tid / QX;
         double sa[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
-        const int per_slot_parts = (a.fin_parts - slot + a.n_slots - 1) / a.n_slots;
+        const int per_slot_parts = (a.fin.parts - slot + a.n_slots - 1) / a.n_slots;
         for (int k0 = fg; k0 < per_slot_parts; k0 += FG * 8) {
             f32x4 va[8], vb[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = k0 + FG * u;
                 const size_t o = (size_t)(slot + (k < per_slot_parts ? k : 0) * a.n_slots) * CX + 4 * fq;
-                va[u] = *reinterpret_cast<const f32x4 *>(a.fin_part_a + o);
-                vb[u] = *reinterpret_cast<const f32x4 *>(a.fin_part_b + o);
+                va[u] = *reinterpret_cast<const f32x4 *>(a.fin.part_a + o);
+                vb[u] = *reinterpret_cast<const f32x4 *>(a.fin.part_b + o);
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
             redd[((size_t)fg * CX + 4 * fq + c) * 2 + 1] = sb[c];
         }
         __syncthreads();
-        const double n = (double)a.fin_rows;
+        const double n = (double)a.fin.rows;
         f32x4 q1, q2, q3;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -641,22 +641,22 @@ __global__ __launch_bounds__(PW_BWD_THREADS, 1) void pw_bwd_x3n_kernel(PwBwd a)
                 Bs += redd[((size_t)gq * CX + ch) * 2 + 1];
             }
             const size_t o = (size_t)slot * CX + ch;
-            const double invstd = a.fin_invstd[o], mean = a.fin_mean[o];
-            const double sc = (double)a.fin_gamma[ch] * invstd;
+            const double invstd = a.fin.invstd[o], mean = a.fin.mean[o];
+            const double sc = (double)a.fin.gamma[ch] * invstd;                   // bn_bwd_constants (bn_desc.h) is the definition of these lines
             const double qq = -sc * invstd * Bs / n;
             q1[c] = (float)sc;
             q2[c] = (float)qq;
             q3[c] = (float)(-sc * A / n - qq * mean);
             if (jb == 0 && tid < QX) {                          // one writer per slot (threads 0 .. 31 = wave 0: cqx = tid)
-                a.fin_slot_ab[o * 2 + 0] = (float)A;
-                a.fin_slot_ab[o * 2 + 1] = (float)Bs;
+                a.fin.out.slot_ab[o * 2 + 0] = (float)A;
+                a.fin.out.slot_ab[o * 2 + 1] = (float)Bs;
             }
         }
         p1 = q1; p2 = q2; p3 = q3;
         if (jb == 0 && tid < QX) {
-            *reinterpret_cast<f32x4 *>(a.fin_P1 + (size_t)slot * CX + 4 * cqx) = p1;
-            *reinterpret_cast<f32x4 *>(a.fin_P2 + (size_t)slot * CX + 4 * cqx) = p2;
-            *reinterpret_cast<f32x4 *>(a.fin_P3 + (size_t)slot * CX + 4 * cqx) = p3;
+            *reinterpret_cast<f32x4 *>(a.fin.out.P1 + (size_t)slot * CX + 4 * cqx) = p1;
+            *reinterpret_cast<f32x4 *>(a.fin.out.P2 + (size_t)slot * CX + 4 * cqx) = p2;
+            *reinterpret_cast<f32x4 *>(a.fin.out.P3 + (size_t)slot * CX + 4 * cqx) = p3;
         }
         __syncthreads();
     } else {
@@ -998,7 +998,7 @@ bool pw_bwd_x3_supported(const PwBwd &a)
     const bool gram = a.g.act != 0;
     if (a.g.z_bf16 || a.prev.z_bf16) return false;
     if (a.w_win_stride && !(a.g.C == 64 && a.prev.C == 64 && a.items_per_block > 0)) return false;      // per-window weights: the bmm backward only
-    const bool dense_g = !gram && a.g.dy != nullptr && a.g.z != nullptr && (a.g.P1 != nullptr || a.fin_part_a != nullptr);
+    const bool dense_g = !gram && a.g.dy != nullptr && a.g.z != nullptr && (a.g.P1 != nullptr || a.fin.part_a != nullptr);
     // 64 -> 64 (conv_2 / conv_3 of the encoder and the feature T-Net's conv_1; some with the addend of a joining branch): the built variants
     if (a.g.C == 64 && a.prev.C == 64) return dense_g && !(a.prev.drop_p > 0.f) && (a.prev.s != nullptr || a.add != nullptr);
     if (a.add) return false;

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
     // lane_id / n_slots) walks the blocks of rows j, j + L_slot, ... of ITS slot only (L_slot = the lanes that slot has: stat_lanes / n_slots,
     // one more for the first stat_lanes % n_slots slots), merges their (rows, mean, M2) as it goes and leaves ONE partial per column: ~57
     // partials per slot for bn_finalize (one stage) instead of one per block of rows (two stages) -- or none at all when a slot is a single
-    // block of rows (the T-Net FC layers): then the BatchNorm constants are finished right here (fin_*).  With stat_lanes = the resident
+    // block of rows (the T-Net FC layers): then the BatchNorm constants are finished right here (PwGemm.fin).  With stat_lanes = the resident
     // grid the blocks of rows are dealt exactly as evenly as by the slot-blind walk (2304 blocks over 512 lanes: 256 lanes take five, 256 four,
     // and the five-block lanes are the low lane ids, so a CU's two workgroups -- ids c and c + 256 -- get nine between them).
     const bool wg_stats = a.part_rows != nullptr;
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
         }
     };
 
-    // Consumer-side finalize of the INPUT's BatchNorm (kernels.h: pfin_*): the input BatchNorm's constants of this workgroup's slot from the
+    // Consumer-side finalize of the INPUT's BatchNorm (kernels.h: PwGemm.pfin): the input BatchNorm's constants of this workgroup's slot from the
     // producer's per-workgroup partials in ONE memory round trip -- thread (gq, cq) takes the partials gq, gq + G, ... of the slot for the four
     // channels 4 cq .. 4 cq + 3 (16-byte loads, a batch of eight in flight).  The FIRST batch (all of them for <= 64 partials per slot) is
     // requested BEFORE the weight tile is staged, so that its round trip runs under the staging instead of after it (round 3 had it behind:
@@ -194,9 +194,9 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
     constexpr int G = GW * PW_NW > 8 ? 8 : GW * PW_NW;             // groups in all
     constexpr int WV = G / GW;                                     // waves that take part
     static_assert(CQ <= 64 && G % GW == 0, "a wave holds whole groups");
-    const bool pfin = PRO && a.pfin_sum != nullptr;
+    const bool pfin = PRO && a.pfin.part.sum != nullptr;
     const int cq = lane % CQ, gq = wave * GW + lane / CQ;
-    const int per_slot_parts = pfin ? a.pfin_parts / a.n_slots : 0;
+    const int per_slot_parts = pfin ? a.pfin.part.parts / a.n_slots : 0;
     f32x4 fv[8], fw[8];
     int frw[8];
     auto pfin_load = [&](int k0) {
@@ -204,9 +204,9 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
         for (int u = 0; u < 8; ++u) {
             const int kk = k0 + G * u;
             const int idx = my_slot + (kk < per_slot_parts ? kk : 0) * a.n_slots;
-            frw[u] = kk < per_slot_parts ? a.pfin_rows[idx] : 0;
-            fv[u] = *reinterpret_cast<const f32x4 *>(a.pfin_sum + (size_t)idx * CIN + 4 * cq);
-            fw[u] = *reinterpret_cast<const f32x4 *>(a.pfin_sq + (size_t)idx * CIN + 4 * cq);
+            frw[u] = kk < per_slot_parts ? a.pfin.part.rows[idx] : 0;
+            fv[u] = *reinterpret_cast<const f32x4 *>(a.pfin.part.sum + (size_t)idx * CIN + 4 * cq);
+            fw[u] = *reinterpret_cast<const f32x4 *>(a.pfin.part.sq + (size_t)idx * CIN + 4 * cq);
         }
     };
     if (PRO) {
@@ -271,20 +271,20 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
             const double mean = N > 0.0 ? S / N : 0.0;
             double m2 = Q2 - N * mean * mean;
             if (m2 < 0.0) m2 = 0.0;
-            const double var = N > 0.0 ? m2 / N : 0.0;
-            const float invstd = (float)(1.0 / sqrt(var + (double)a.fin_eps));
-            const float sc = a.pfin_gamma[c] * invstd;
-            const float sh = a.pfin_beta[c] - (float)mean * sc;
+            const double var = N > 0.0 ? m2 / N : 0.0;              // bn_fwd_constants (bn_desc.h) is the definition of these lines
+            const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
+            const float sc = a.pfin.layer.gamma[c] * invstd;
+            const float sh = a.pfin.layer.beta[c] - (float)mean * sc;
             sPro[c] = sc;
             sPro[CIN + c] = sh;
             if (sl.j == 0 && cb0 == 0) {                        // one writer per slot
                 const size_t o = (size_t)my_slot * CIN + c;
-                a.pfin_scale[o] = sc;
-                a.pfin_shift[o] = sh;
-                a.pfin_mean[o] = (float)mean;
-                a.pfin_invstd[o] = invstd;
-                a.pfin_smean[o] = (float)mean;
-                a.pfin_suvar[o] = (float)(N > 1.0 ? m2 / (N - 1.0) : m2);
+                a.pfin.out.scale[o] = sc;
+                a.pfin.out.shift[o] = sh;
+                a.pfin.out.mean[o] = (float)mean;
+                a.pfin.out.invstd[o] = invstd;
+                a.pfin.out.smean[o] = (float)mean;
+                a.pfin.out.suvar[o] = (float)(N > 1.0 ? m2 / (N - 1.0) : m2);
             }
         }
         staged_slot = my_slot;
@@ -958,19 +958,19 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
         const int col = cb0 + c;
         if (col >= a.cout) continue;
         const double mean = run_n > 0 ? sRun[2 * c] : 0.0, m2 = run_n > 0 ? sRun[2 * c + 1] : 0.0;
-        if (a.fin_scale) {                          // one lane per slot: this workgroup saw every row of its slot
+        if (a.fin.out.scale) {                          // one lane per slot: this workgroup saw every row of its slot
             const double N = (double)run_n;
-            const double var = N > 0.0 ? m2 / N : 0.0;
-            const float invstd = (float)(1.0 / sqrt(var + (double)a.fin_eps));
+            const double var = N > 0.0 ? m2 / N : 0.0;          // bn_fwd_constants / bn_fwd_store (bn_desc.h) are the definition of these lines
+            const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
             const size_t o = (size_t)my_slot * a.cout + col;
-            const float sc = a.fin_gamma[col] * invstd;
-            a.fin_scale[o] = sc;
-            a.fin_shift[o] = a.fin_beta[col] - (float)mean * sc;
-            if (a.fin_mean) a.fin_mean[o] = (float)mean;
-            if (a.fin_invstd) a.fin_invstd[o] = invstd;
-            if (a.fin_smean) {
-                a.fin_smean[o] = (float)mean;
-                a.fin_suvar[o] = (float)(N > 1.0 ? m2 / (N - 1.0) : m2);
+            const float sc = a.fin.layer.gamma[col] * invstd;
+            a.fin.out.scale[o] = sc;
+            a.fin.out.shift[o] = a.fin.layer.beta[col] - (float)mean * sc;
+            if (a.fin.out.mean) a.fin.out.mean[o] = (float)mean;
+            if (a.fin.out.invstd) a.fin.out.invstd[o] = invstd;
+            if (a.fin.out.smean) {
+                a.fin.out.smean[o] = (float)mean;
+                a.fin.out.suvar[o] = (float)(N > 1.0 ? m2 / (N - 1.0) : m2);
             }
         } else {
             // pooled layers: the statistics were taken of z' = sgn(gamma) z -- the mean changes sign back, M2 does not care
@@ -979,7 +979,7 @@ __global__ __launch_bounds__(NW * 64, X3 ? 1 : 2) void pw_gemm_kernel(PwGemm a)
             a.part_sq[(size_t)part_idx * a.cout + col] = (float)m2;
         }
     }
-    if (tid == 0 && cb0 == 0 && !a.fin_scale) {
+    if (tid == 0 && cb0 == 0 && !a.fin.out.scale) {
         a.part_rows[part_idx] = run_n;
         // slots with one lane fewer than the widest leave their last partial slot empty: mark it (rows 0) for bn_finalize
         if (sl.j == sl.L - 1 && sl.L < (stat_lanes + a.n_slots - 1) / a.n_slots) a.part_rows[part_idx + a.n_slots] = 0;
@@ -1104,11 +1104,12 @@ int pw_gemm(const PwGemm &a, hipStream_t st)
 {
     AMPNET_REQUIRE(a.A && a.W && (a.win_off || a.uniform_rows > 0), "pw_gemm: null pointer");
     AMPNET_REQUIRE(!a.part_rows || (a.part_sum && a.stat_lanes >= a.n_slots && a.stat_lanes <= 2048), "pw_gemm: per-workgroup statistics need part_sum and a lane plan");
-    AMPNET_REQUIRE(!a.pfin_sum || (a.part_rows && a.pro_scale && a.pfin_sq && a.pfin_rows && a.pfin_parts >= a.n_slots && a.pfin_parts % a.n_slots == 0 && a.pfin_gamma &&
-                                   a.pfin_beta && a.pfin_scale && a.pfin_shift && a.pfin_mean && a.pfin_invstd && a.pfin_smean && a.pfin_suvar && a.pfin_sum != a.part_sum &&
-                                   a.pfin_rows != a.part_rows && (a.cin == 64 || a.cin == 128) && !a.w_win_stride && a.pfin_parts / a.n_slots <= 1024),
+    AMPNET_REQUIRE(!a.pfin.part.sum || (a.part_rows && a.pro_scale && a.pfin.part.sq && a.pfin.part.rows && a.pfin.part.parts >= a.n_slots && a.pfin.part.parts % a.n_slots == 0 && a.pfin.layer.gamma &&
+                                   a.pfin.layer.beta && a.pfin.out.scale && a.pfin.out.shift && a.pfin.out.mean && a.pfin.out.invstd && a.pfin.out.smean && a.pfin.out.suvar && a.pfin.part.sum != a.part_sum &&
+                                   a.pfin.part.rows != a.part_rows && (a.cin == 64 || a.cin == 128) && !a.w_win_stride && a.pfin.part.parts / a.n_slots <= 1024),
                    "pw_gemm: consumer-side BatchNorm finalize needs per-workgroup statistics, the producer's partials in buffers of their own and every output array");
-    AMPNET_REQUIRE(!a.fin_scale || (a.part_rows && a.stat_lanes == a.n_slots && a.fin_gamma && a.fin_beta && a.fin_shift && cdiv(a.Q, a.n_slots) * a.chunks == 1),
+    AMPNET_REQUIRE((!a.pfin.part.sum && !a.fin.out.scale) || bn_fwd_in_kernel(a.part_rows != nullptr), "pw_gemm: a BatchNorm is finished in the kernel from batch statistics, and not the global batch's");
+    AMPNET_REQUIRE(!a.fin.out.scale || (a.part_rows && a.stat_lanes == a.n_slots && a.fin.layer.gamma && a.fin.layer.beta && a.fin.out.shift && cdiv(a.Q, a.n_slots) * a.chunks == 1),
                    "pw_gemm: in-kernel BatchNorm constants need one block of rows per slot");
     AMPNET_REQUIRE(a.Q >= 1 && a.chunks >= 1 && a.cout >= 1, "pw_gemm: bad sizes Q=%d chunks=%d cout=%d", a.Q, a.chunks, a.cout);
     AMPNET_REQUIRE(a.lda % 4 == 0 && (a.w_win_stride != 0 || a.ldw % 4 == 0), "pw_gemm: lda/ldw must be multiples of 4");

@@ -181,13 +181,13 @@ __global__ __launch_bounds__(64 * FIN_G) void bn_finalize_kernel(BnFinalize a, f
         const int q = slot + qi * a.n_slots;
         const int p = q * a.chunks + ch;
         if (a.gather_ranks > 0) {        // partial qi = rank qi's merged slot: segment {mean, M2, rows}
-            const float *seg = a.part_sum + (size_t)qi * a.gather_seg;
+            const float *seg = a.part.sum + (size_t)qi * a.gather_seg;
             rows = reinterpret_cast<const int *>(seg + (size_t)2 * a.n_slots * a.C)[slot];
             off = (size_t)qi * a.gather_seg + (size_t)slot * a.C + c;
             return;
         }
-        if (a.part_rows) {
-            rows = a.part_rows[p];
+        if (a.part.rows) {
+            rows = a.part.rows[p];
         } else {
             const int wrows = a.uniform_rows > 0 ? a.uniform_rows : a.win_off[q + 1] - a.win_off[q];
             rows = max(min(wrows - ch * a.chunk_rows, a.chunk_rows), 0);
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64 * FIN_G) void bn_finalize_kernel(BnFinalize a, f
             size_t off = 0;
             rw[u] = 0;
             if (e < total && ok) decode(e, rw[u], off);
-            v[u] = rw[u] > 0 ? a.part_sum[off] : 0.f;
+            v[u] = rw[u] > 0 ? a.part.sum[off] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -235,8 +235,8 @@ __global__ __launch_bounds__(64 * FIN_G) void bn_finalize_kernel(BnFinalize a, f
             size_t off = 0;
             rw[u] = 0;
             if (e < total && ok) decode(e, rw[u], off);
-            v[u] = rw[u] > 0 ? a.part_sum[off] : 0.f;
-            w[u] = rw[u] > 0 ? a.part_sq[off] : 0.f;
+            v[u] = rw[u] > 0 ? a.part.sum[off] : 0.f;
+            w[u] = rw[u] > 0 ? a.part.sq[off] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -257,17 +257,7 @@ __global__ __launch_bounds__(64 * FIN_G) void bn_finalize_kernel(BnFinalize a, f
             if (c == 0) out_rows[slot] = (int)N;
             return;
         }
-        const double var = N > 0.0 ? m2 / N : 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
-        const float sc = a.gamma[c] * invstd;
-        a.scale[o] = sc;
-        a.shift[o] = a.beta[c] - (float)mean * sc;
-        if (a.mean) a.mean[o] = (float)mean;
-        if (a.invstd) a.invstd[o] = invstd;
-        if (a.stat_mean) {
-            a.stat_mean[o] = (float)mean;
-            a.stat_uvar[o] = (float)(N > 1.0 ? m2 / (N - 1.0) : m2);
-        }
+        bn_fwd_store(a.out, o, bn_fwd_constants(N, mean, m2, a.layer.gamma[c], a.layer.beta[c], a.eps));
     }
 }
 
@@ -275,16 +265,16 @@ __global__ __launch_bounds__(64 * FIN_G) void bn_finalize_kernel(BnFinalize a, f
 int bn_finalize_gathered(const BnFinalize &a, const float *all, int ranks, size_t seg, hipStream_t st)
 {
     BnFinalize s2 = a;
-    s2.part_sum = all; s2.part_sq = all + (size_t)a.n_slots * a.C;
+    s2.part.sum = all; s2.part.sq = all + (size_t)a.n_slots * a.C;
     s2.gather_ranks = ranks; s2.gather_seg = (long)seg;
-    s2.Q = ranks * a.n_slots; s2.chunks = 1; s2.uniform_rows = 0; s2.part_rows = nullptr;
+    s2.Q = ranks * a.n_slots; s2.chunks = 1; s2.uniform_rows = 0; s2.part.rows = nullptr;
     hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3(a.n_slots, cdiv(a.C, 64)), dim3(64 * FIN_G), 0, st, s2, nullptr, nullptr, nullptr);
     return check_launch("bn_finalize_kernel (global batch)");
 }
 
 int bn_finalize(const BnFinalize &a, hipStream_t st)
 {
-    AMPNET_REQUIRE(a.part_sum && a.part_sq && (a.win_off || a.part_rows || a.uniform_rows > 0) && a.gamma && a.beta && a.scale && a.shift, "bn_finalize: null pointer");
+    AMPNET_REQUIRE(a.part.sum && a.part.sq && (a.win_off || a.part.rows || a.uniform_rows > 0) && a.layer.gamma && a.layer.beta && a.out.scale && a.out.shift, "bn_finalize: null pointer");
     if (sync_bn_on()) {
         // global batch: merge the rank's partials per slot, all-gather the (rows, mean, M2) of every rank, finalize from those
         const size_t seg = (size_t)a.n_slots * (2 * (size_t)a.C + 1);
@@ -311,7 +301,7 @@ int bn_finalize(const BnFinalize &a, hipStream_t st)
         s1.n_slots = V;
         hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3(V, cdiv(a.C, 64)), dim3(64 * FIN_G), 0, st, s1, m_sum, m_sq, m_rows);
         BnFinalize s2 = a;
-        s2.part_sum = m_sum; s2.part_sq = m_sq; s2.part_rows = m_rows;
+        s2.part.sum = m_sum; s2.part.sq = m_sq; s2.part.rows = m_rows;
         s2.Q = V; s2.chunks = 1; s2.uniform_rows = 0;
         hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3(a.n_slots, cdiv(a.C, 64)), dim3(64 * FIN_G), 0, st, s2, nullptr, nullptr, nullptr);
         return check_launch("bn_finalize_kernel (two stages)");
@@ -412,7 +402,7 @@ __global__ __launch_bounds__(256) void pool_finalize_kernel(PoolFinalize a)
     }
 }
 
-// The same with the layer's BatchNorm finished in the kernel (PoolFinalize.pfin_*): workgroup = (slot, four windows of it), 1024 threads =
+// The same with the layer's BatchNorm finished in the kernel (PoolFinalize.pfin): workgroup = (slot, four windows of it), 1024 threads =
 // 4 groups x 256 channels.  Group g first sums the slot's partials g, g + 4, ... (n, n mean, M2 + n mean^2 in double, sixteen partials in
 // flight per thread: one memory round trip for the ~57 a slot has), the groups merge through LDS in group order, every thread forms its
 // channel's scale / shift, and group g then pools window 4 wg + g.  Workgroup 0 of a slot writes the BatchNorm arrays.
@@ -422,7 +412,7 @@ __global__ __launch_bounds__(1024) void pool_finalize_bn_kernel(PoolFinalize a)
     __shared__ double rn[4];
     const int slot = blockIdx.x % a.n_slots, wg = blockIdx.x / a.n_slots;
     const int c = threadIdx.x & 255, g = threadIdx.x >> 8;
-    const int per_slot_parts = a.pfin_parts / a.n_slots;
+    const int per_slot_parts = a.pfin.part.parts / a.n_slots;
     double sn = 0.0, sm = 0.0, sq = 0.0;
     for (int k0 = g; k0 < per_slot_parts; k0 += 4 * 16) {
         float v[16], w[16];
@@ -431,9 +421,9 @@ __global__ __launch_bounds__(1024) void pool_finalize_bn_kernel(PoolFinalize a)
         for (int u = 0; u < 16; ++u) {
             const int kk = k0 + 4 * u;
             const int idx = slot + (kk < per_slot_parts ? kk : 0) * a.n_slots;
-            rw[u] = kk < per_slot_parts ? a.pfin_rows[idx] : 0;
-            v[u] = a.pfin_sum[(size_t)idx * 256 + c];
-            w[u] = a.pfin_sq[(size_t)idx * 256 + c];
+            rw[u] = kk < per_slot_parts ? a.pfin.part.rows[idx] : 0;
+            v[u] = a.pfin.part.sum[(size_t)idx * 256 + c];
+            w[u] = a.pfin.part.sq[(size_t)idx * 256 + c];
         }
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -455,19 +445,9 @@ __global__ __launch_bounds__(1024) void pool_finalize_bn_kernel(PoolFinalize a)
     const double mean = N > 0.0 ? S / N : 0.0;
     double m2 = Q2 - N * mean * mean;
     if (m2 < 0.0) m2 = 0.0;
-    const double var = N > 0.0 ? m2 / N : 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)a.pfin_eps));
-    const float sc = a.pfin_gamma[c] * invstd;
-    const float sh = a.pfin_beta[c] - (float)mean * sc;
-    if (wg == 0 && g == 0) {
-        const size_t o = (size_t)slot * 256 + c;
-        a.pfin_scale[o] = sc;
-        a.pfin_shift[o] = sh;
-        a.pfin_mean[o] = (float)mean;
-        a.pfin_invstd[o] = invstd;
-        a.pfin_smean[o] = (float)mean;
-        a.pfin_suvar[o] = (float)(N > 1.0 ? m2 / (N - 1.0) : m2);
-    }
+    const BnFwdVal bv = bn_fwd_constants(N, mean, m2, a.pfin.layer.gamma[c], a.pfin.layer.beta[c], a.eps);
+    const float sc = bv.scale, sh = bv.shift;
+    if (wg == 0 && g == 0) bn_fwd_store(a.pfin.out, (size_t)slot * 256 + c, bv);
     const int q = slot + (wg * 4 + g) * a.n_slots;
     if (q >= a.Q) return;
     const int orow = a.out_slot_major ? (q % a.n_slots) * (a.Q / a.n_slots) + q / a.n_slots : q;
@@ -491,12 +471,13 @@ __global__ __launch_bounds__(1024) void pool_finalize_bn_kernel(PoolFinalize a)
 
 int pool_finalize(const PoolFinalize &a, hipStream_t st)
 {
-    AMPNET_REQUIRE(a.part_max && a.pooled && (a.pfin_sum ? a.part_amax != nullptr : (a.scale && a.shift)), "pool_finalize: null pointer");
+    AMPNET_REQUIRE(a.part_max && a.pooled && (a.pfin.part.sum ? a.part_amax != nullptr : (a.scale && a.shift)), "pool_finalize: null pointer");
+    AMPNET_REQUIRE(!a.pfin.part.sum || bn_fwd_in_kernel(true), "pool_finalize: the global-batch BatchNorm is finished by bn_finalize");
     AMPNET_REQUIRE(a.part_amax || (!a.arg), "pool_finalize: argmax rows requested but not tracked by the producer");
     AMPNET_REQUIRE(!a.out_slot_major || a.Q % a.n_slots == 0, "pool_finalize: Q %% n_slots != 0");
-    if (a.pfin_sum) {
-        AMPNET_REQUIRE(a.C == 256 && a.pfin_sq && a.pfin_rows && a.pfin_parts >= a.n_slots && a.pfin_parts % a.n_slots == 0 && a.pfin_gamma && a.pfin_beta && a.pfin_scale &&
-                           a.pfin_shift && a.pfin_mean && a.pfin_invstd && a.pfin_smean && a.pfin_suvar,
+    if (a.pfin.part.sum) {
+        AMPNET_REQUIRE(a.C == 256 && a.pfin.part.sq && a.pfin.part.rows && a.pfin.part.parts >= a.n_slots && a.pfin.part.parts % a.n_slots == 0 && a.pfin.layer.gamma && a.pfin.layer.beta && a.pfin.out.scale &&
+                           a.pfin.out.shift && a.pfin.out.mean && a.pfin.out.invstd && a.pfin.out.smean && a.pfin.out.suvar,
                        "pool_finalize: in-kernel BatchNorm finalize needs 256 channels, the producer's partials and every output array");
         const int per_slot = cdiv(a.Q, a.n_slots);
         hipLaunchKernelGGL(pool_finalize_bn_kernel, dim3(a.n_slots * cdiv(per_slot, 4)), dim3(1024), 0, st, a);

@@ -397,18 +397,35 @@ def sa_train_backward_tape(D, B, S, nsample, couts, l):
 
 
 # ---- set abstraction: eval forward and frozen-statistics backward ------------------------------------------------------------------------
+def _sa_forward(prefix, symbol, xyz, centres, group_idx, feats, layers, eps, out, workspace):
+    """The eval forward under its two arithmetics: one argument list, one set of checks (`prefix` opens their messages)."""
+    B, N, ld, S, nsample, D = _sa_geometry(prefix, xyz, centres, group_idx, feats, [("out", out, _F32, 3, True)])
+    table, couts, epss = _mlp_tables(prefix, layers, 3 + D, eps)
+    _check_cout_last(prefix, layers, (B, S), "B, S", out=out)
+    ws, ws_bytes = _workspace_args(prefix, workspace)
+    with torch.cuda.device(xyz.device):
+        rc = getattr(lib(), symbol)(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
+                                    len(layers), ptr(out), ws, ws_bytes, stream_ptr(xyz.device))
+    check(rc, symbol)
+
+
 def sa_forward_f32(xyz, centres, group_idx, feats, layers, eps, out, workspace):
     """One fused set-abstraction layer.  layers: per layer the six contiguous float32 GPU tensors (weight [cout, cin], conv bias, BatchNorm
     weight, bias, running_mean, running_var); eps: per layer the BatchNorm eps; feats [B, N, D] or None; out [B, S, cout_last]; workspace:
     SA_WORKSPACE_BYTES GPU bytes."""
-    B, N, ld, S, nsample, D = _sa_geometry("sa_forward", xyz, centres, group_idx, feats, [("out", out, _F32, 3, True)])
-    table, couts, epss = _mlp_tables("sa_forward", layers, 3 + D, eps)
-    _check_cout_last("sa_forward", layers, (B, S), "B, S", out=out)
-    ws, ws_bytes = _workspace_args("sa_forward", workspace)
-    with torch.cuda.device(xyz.device):
-        rc = lib().ampnet_sa_forward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
-                                         len(layers), ptr(out), ws, ws_bytes, stream_ptr(xyz.device))
-    check(rc, "ampnet_sa_forward_f32")
+    _sa_forward("sa_forward", "ampnet_sa_forward_f32", xyz, centres, group_idx, feats, layers, eps, out, workspace)
+
+
+def sa_forward_bf16_workspace_bytes(D, B, S, nsample, couts):
+    """Device bytes sa_forward_bf16 needs (the BatchNorm fold and every layer's weights as bf16); a shape outside the kernel's limits is an
+    AmpnetError that names the limit."""
+    return _workspace_bytes("ampnet_sa_forward_bf16_workspace_bytes", (D, B, S, nsample), couts)
+
+
+def sa_forward_bf16(xyz, centres, group_idx, feats, layers, eps, out, workspace):
+    """sa_forward_f32 with the matrix products in bf16 (include/ampnet_hip.h, "the rounding model"): the same float32 arguments and
+    output; workspace: sa_forward_bf16_workspace_bytes(D, B, S, nsample, couts) GPU bytes, 16-byte aligned."""
+    _sa_forward("sa_forward_bf16", "ampnet_sa_forward_bf16", xyz, centres, group_idx, feats, layers, eps, out, workspace)
 
 
 # ---- multi-scale grouping: K radii, K branches around the same centres ------------------------------------------------------------------
@@ -570,18 +587,35 @@ def sa_train_backward_f32(xyz, centres, group_idx, feats, layers, eps, save_mean
 
 
 # ---- feature propagation: eval forward and frozen-statistics backward --------------------------------------------------------------------
+def _fp_forward(prefix, symbol, points1, points2, idx, dist2, layers, eps, out, workspace):
+    """The eval forward under its two arithmetics: one argument list, one set of checks (`prefix` opens their messages)."""
+    B, N, k, S, D1, D2 = _fp_geometry(prefix, points1, points2, idx, dist2, [("out", out, _F32, 3, True)])
+    table, couts, epss = _mlp_tables(prefix, layers, D1 + D2, eps)
+    _check_cout_last(prefix, layers, (B, N), "B, N", out=out)
+    ws, ws_bytes = _workspace_args(prefix, workspace)
+    with torch.cuda.device(points2.device):
+        rc = getattr(lib(), symbol)(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, len(layers),
+                                    ptr(out), ws, ws_bytes, stream_ptr(points2.device))
+    check(rc, symbol)
+
+
 def fp_forward_f32(points1, points2, idx, dist2, layers, eps, out, workspace):
     """One fused feature-propagation layer.  points1 [B, N, D1] or None, points2 [B, S, D2], idx int32 / dist2 float32 [B, N, k] (the output
     of three_nn_f32), layers and eps as in sa_forward_f32 with cin_0 = D1 + D2, out [B, N, cout_last]; workspace: FP_WORKSPACE_BYTES GPU
     bytes."""
-    B, N, k, S, D1, D2 = _fp_geometry("fp_forward", points1, points2, idx, dist2, [("out", out, _F32, 3, True)])
-    table, couts, epss = _mlp_tables("fp_forward", layers, D1 + D2, eps)
-    _check_cout_last("fp_forward", layers, (B, N), "B, N", out=out)
-    ws, ws_bytes = _workspace_args("fp_forward", workspace)
-    with torch.cuda.device(points2.device):
-        rc = lib().ampnet_fp_forward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, len(layers),
-                                         ptr(out), ws, ws_bytes, stream_ptr(points2.device))
-    check(rc, "ampnet_fp_forward_f32")
+    _fp_forward("fp_forward", "ampnet_fp_forward_f32", points1, points2, idx, dist2, layers, eps, out, workspace)
+
+
+def fp_forward_bf16_workspace_bytes(D1, D2, B, N, couts):
+    """Device bytes fp_forward_bf16 needs (the BatchNorm fold and every layer's weights as bf16); a shape outside the kernel's limits is an
+    AmpnetError that names the limit."""
+    return _workspace_bytes("ampnet_fp_forward_bf16_workspace_bytes", (D1, D2, B, N), couts)
+
+
+def fp_forward_bf16(points1, points2, idx, dist2, layers, eps, out, workspace):
+    """fp_forward_f32 with the matrix products in bf16 (include/ampnet_hip.h, "the rounding model"): the same float32 arguments and
+    output; workspace: fp_forward_bf16_workspace_bytes(D1, D2, B, N, couts) GPU bytes, 16-byte aligned."""
+    _fp_forward("fp_forward_bf16", "ampnet_fp_forward_bf16", points1, points2, idx, dist2, layers, eps, out, workspace)
 
 
 def _fp_backward_rows(dout, dpoints1, dpoints2):

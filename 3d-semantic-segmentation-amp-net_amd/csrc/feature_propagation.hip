@@ -22,17 +22,6 @@
 
 namespace ampnet {
 
-// the last layer's epilogue: rows < rows of the tile go to `dst` (global, row stride ldo)
-struct FpStore {
-    int ldo, rows;
-    __device__ static float init() { return 0.0f; }
-    __device__ void put(float &, float *dst, int row, int col, float v) const
-    {
-        if (row < rows) dst[(size_t)row * ldo + col] = v;
-    }
-    __device__ static void done(float, float *, int, int) {}
-};
-
 __global__ __launch_bounds__(256) void fp_forward_kernel(MlpPlan p, const float *__restrict__ points1, int D1, const float *__restrict__ points2,
                                                         int D2, int n, int s, const int32_t *__restrict__ idx, const float *__restrict__ dist2,
                                                         int k, const float *__restrict__ fold, int tiles_per_cloud, int n_tiles,

@@ -21,8 +21,10 @@ __device__ __forceinline__ void fp_interp_weights(const float *__restrict__ d, i
 
 // Rows row0 .. row0 + 31 of cloud `cloud_i` into `tile` [32][ld], kp0 columns each (zeros past cin0 = D1 + D2): the rows past `rows` are
 // zero-filled and nothing is read for them.  Lane t (and t + 32) holds the neighbours and weights of row t; indices are clamped into the
-// coarse cloud.  The caller orders the stores before its reads (wave_lds_sync).
-__device__ __forceinline__ void fp_build_rows(float *tile, int ld, int kp0, const float *__restrict__ points1, int D1,
+// coarse cloud.  The caller orders the stores before its reads (wave_lds_sync).  T: the tile's element type, float or (the bf16 forward,
+// feature_propagation_bf16.hip) __bf16: the value is formed in fp32 either way and rounded once by the store.
+template <class T>
+__device__ __forceinline__ void fp_build_rows(T *tile, int ld, int kp0, const float *__restrict__ points1, int D1,
                                               const float *__restrict__ points2, int D2, int n, int s, const int32_t *__restrict__ idx,
                                               const float *__restrict__ dist2, int k, int cloud_i, int row0, int rows, int lane)
 {
@@ -53,10 +55,22 @@ __device__ __forceinline__ void fp_build_rows(float *tile, int ld, int kp0, cons
                     if (k > 2) v = fmaf(w2, f2[c - D1], v);
                 }
             }
-            tile[t * ld + c] = v;
+            tile[t * ld + c] = (T)v;
         }
     }
 }
+
+// the forwards' last-layer epilogue (feature_propagation.hip, feature_propagation_bf16.hip): rows < rows of the tile go to `dst` (global,
+// row stride ldo)
+struct FpStore {
+    int ldo, rows;
+    __device__ static float init() { return 0.0f; }
+    __device__ void put(float &, float *dst, int row, int col, float v) const
+    {
+        if (row < rows) dst[(size_t)row * ldo + col] = v;
+    }
+    __device__ static void done(float, float *, int, int) {}
+};
 
 // fp_forward_kernel (feature_propagation.hip) on `st`, reading scale and shift of every layer from `fold` (plan.fold_off)
 int fp_forward_launch(const char *what, const MlpPlan &p, int lds, const float *points1, int D1, const float *points2, int D2, int n_clouds, int n,

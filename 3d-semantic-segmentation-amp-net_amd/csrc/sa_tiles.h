@@ -11,8 +11,10 @@ constexpr int SAB_MAX_GRID = 2048;        // workgroups (= rows of the partials 
 
 // The forward's gather of a WHOLE group g: the R rows [xyz[idx_t] - xyz[centre] (3), feats[idx_t] (D)] of group_idx[g][:] into `tile`
 // [R][ldt], kp0 columns each (zeros past cin0).  Lane t holds the point of row t; the rows past nsample REPEAT row 0, which changes no max.
-// Element e = (row, column) with the columns fastest, so a row's features load contiguously.
-__device__ __forceinline__ void sa_gather_group(float *tile, int ldt, int R, int kp0, int cin0, const float *__restrict__ xyz, int n, int ld,
+// Element e = (row, column) with the columns fastest, so a row's features load contiguously.  T: the tile's element type, float or (the
+// bf16 forward, set_abstraction_bf16.hip) __bf16: the value is formed in fp32 either way and rounded once by the store.
+template <class T>
+__device__ __forceinline__ void sa_gather_group(T *tile, int ldt, int R, int kp0, int cin0, const float *__restrict__ xyz, int n, int ld,
                                                 const int32_t *__restrict__ centres, int s, const int32_t *__restrict__ group_idx, int nsample,
                                                 const float *__restrict__ feats, int D, int g, int lane)
 {
@@ -28,7 +30,7 @@ __device__ __forceinline__ void sa_gather_group(float *tile, int ldt, int R, int
         float v = 0.0f;
         if (c < 3) v = cloud[(size_t)j * ld + c] - (c == 0 ? cx : c == 1 ? cy : cz);
         else if (c < cin0) v = fcloud[(size_t)j * D + (c - 3)];
-        tile[t * ldt + c] = v;
+        tile[t * ldt + c] = (T)v;
     }
 }
 

@@ -8,7 +8,18 @@ used at :285-292).  This module provides both with the constructors and the stat
     gather + shared MLP + max (ampnet_sa_forward_f32);
   * PointNetFeaturePropagation: the 3 nearest coarse points of every fine point (ampnet_three_nn_f32) and ONE fused kernel for
     inverse-distance interpolation + concatenation + shared MLP (ampnet_fp_forward_f32).
-Both fused kernels are exact fp32 whatever the matrix precision is.
+Both fused kernels are exact fp32 whatever the matrix precision is: the process-wide mode, a precision scope and AMPNET_PRECISION do
+not reach these blocks.  The blocks' exact-bits contracts -- the multi-scale block equals its branches, a train-mode forward equals the
+eval kernel on the batch's statistics, a backward finds the forward's ReLU masks and max again -- rest on that, so here precision=None
+MEANS fp32 (for the other models it follows the library's default: a deliberate difference).
+
+bf16 is opt-in and an inference mode: PointNetSetAbstraction(..., precision='bf16') and PointNetFeaturePropagation(..., precision='bf16')
+(keyword-only; also set_precision(mode)) run the eval forward without a graph through ampnet_sa_forward_bf16 / ampnet_fp_forward_bf16:
+the input rows, the weights and the hidden activations rounded to bf16, fp32 accumulation, BatchNorm and max (include/ampnet_hip.h, "the
+rounding model").  Sampling, ball query, 3-NN and the interpolation weights are untouched, so the groups and neighbours are those of the
+fp32 block.  A block built with grad=True, batch_stats=True or group_all=True refuses the mode (NotImplementedError) at construction and
+in set_precision: a forward value never depends on whether a graph is wanted.  The other precision names of the package ('f32x3',
+'bf16_train', 'bf16_store') are not built here and raise NotImplementedError.
 
 Gradients are opt-in.  PointNetFeaturePropagation(..., grad=True) in EVAL mode is differentiable (ampnet_fp_backward_f32 through
 autograd._FpFn) with respect to points1, points2, its conv weights and biases and its BatchNorm weight and bias;
@@ -35,7 +46,8 @@ PointNetSetAbstractionMsg is the multi-scale-grouping layer of the usual impleme
 mlp) branches around the same centres, concatenated.  Farthest-point sampling runs once, one ball query fills all index lists
 (ampnet_ball_query_msg_f32) and in eval mode one launch runs all branches (ampnet_sa_msg_forward_f32); grad=True and batch_stats=True go
 branch by branch through the kernels above.  It serves models defined inside the set-abstraction limits (its docstring).
-Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block.
+Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block, a `precision`
+keyword for PointNetSetAbstractionMsg (its one-launch forward is fp32 only), bf16 in a backward, a train-mode or a group_all forward.
 
 Differences from the usual implementation: its farthest-point sampling starts from a RANDOM point of each cloud; here the centres come
 from the project's `fps_indices`, whose seed is point 0 (the rule of the reference's utils.fps).  Pass `centres=` to use other ones.
@@ -48,6 +60,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...utils import utils as U
+from ._precision import _EvalForwardPrecision, is_bf16
 
 
 class _Conv(nn.Module):
@@ -94,8 +107,9 @@ def _build_mlp(mod, in_channel, mlp, tail, ok, limits, device):
 
 
 def _workspace(mod, nbytes, device):
-    """The module's fold workspace, allocated on first use and again when the input moves to another device."""
-    if mod._ws is None or mod._ws.device != device:
+    """The module's workspace (the BatchNorm fold; in bf16 mode also the converted weights), allocated on first use and again when the
+    input moves to another device or a call needs more than the buffer holds."""
+    if mod._ws is None or mod._ws.device != device or mod._ws.numel() < nbytes:
         mod._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     return mod._ws
 
@@ -175,7 +189,7 @@ class _SetAbstraction(nn.Module):
             return x, centres, groups, U.gather_rows(x, centres)
 
 
-class PointNetSetAbstraction(_SetAbstraction):
+class PointNetSetAbstraction(_EvalForwardPrecision, _SetAbstraction):
     """One set-abstraction layer: `npoint` centres by farthest-point sampling, per centre the first `nsample` points within `radius`
     (utils.ball_query), the shared MLP `mlp` (Conv2d 1x1 + BatchNorm2d + ReLU per entry) on [relative xyz, point features], max over the
     group.  `in_channel` counts the 3 coordinates, as in the usual implementation.
@@ -189,12 +203,17 @@ class PointNetSetAbstraction(_SetAbstraction):
     group_all=True: ONE group of all N points per cloud, the coordinates as they are (the usual sample_and_group_all): npoint, radius and
     nsample are ignored and may be None, new_xyz is zeros [B, 3, 1] and new_points [B, mlp[-1], 1] (ampnet_sa_all_forward_f32); grad=True
     works as above (ampnet_sa_all_backward_f32 through autograd._SaAllFn: only the rows that won a channel carry a gradient);
-    `centres=` raises and batch_stats=True is refused at construction."""
+    `centres=` raises and batch_stats=True is refused at construction.
+    precision (keyword-only; set_precision(mode)): None or 'fp32' -- the exact-fp32 kernel, whatever the library's mode is; 'bf16' -- the
+    eval forward without a graph through ampnet_sa_forward_bf16 (the module docstring), refused together with grad=True, batch_stats=True
+    or group_all=True."""
 
-    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda', grad=False, batch_stats=False):
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all, device='cuda', grad=False, batch_stats=False, *, precision=None):
         super().__init__()
         self.grad = bool(grad)
         self.batch_stats = bool(batch_stats)
+        self.group_all = bool(group_all)
+        self.set_precision(precision)
         if group_all:
             if self.batch_stats:
                 raise NotImplementedError("group_all=True is built for eval mode (with grad=True: the running statistics frozen); train mode "
@@ -209,6 +228,10 @@ class PointNetSetAbstraction(_SetAbstraction):
                    f"of 32 up to {_lib.SA_MAX_COUT}, 3 <= in_channel <= {_lib.SA_MAX_CIN}, nsample <= {_lib.SA_MAX_NSAMPLE}", device)
         self.npoint, self.radius, self.nsample, self.group_all = int(npoint), float(radius), int(nsample), False
 
+    def _bf16_refusal(self):
+        flags = [f for f in ("grad", "batch_stats", "group_all") if getattr(self, f)]
+        return f"this block was built with {', '.join(f + '=True' for f in flags)}" if flags else None
+
     def forward(self, xyz, points, centres=None):
         """xyz [B, 3, N], points [B, D, N] or None (D = in_channel - 3) -> (new_xyz [B, 3, npoint], new_points [B, mlp[-1], npoint]);
         npoint counts as 1 in a group_all block.  centres: int32 [B, npoint] point indices to use instead of farthest-point sampling
@@ -219,6 +242,7 @@ class PointNetSetAbstraction(_SetAbstraction):
         """The layer on point-major tensors (what the kernels take): x [B, N, 3], feats [B, N, D] or None, float32 contiguous GPU
         -> (new_xyz [B, npoint, 3], new_points [B, npoint, mlp[-1]]).  pointnet_2 chains its blocks through this, without the transpose
         pair per block that forward() owes to the channel-major interface."""
+        self._check_bf16()
         if self.group_all:
             return self._all_rows(x, feats, centres)
         B = x.shape[0]
@@ -231,8 +255,12 @@ class PointNetSetAbstraction(_SetAbstraction):
         feats = None if feats is None else feats.detach()
         layers = _mlp_tensors(self)
         out = torch.empty((B, self.npoint, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
-        _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out,
-                            _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
+        if is_bf16(self.precision):
+            need = _lib.sa_forward_bf16_workspace_bytes(self.in_channel - 3, B, self.npoint, self.nsample, [w.shape[0] for w, *_ in layers])
+            _lib.sa_forward_bf16(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out, _workspace(self, need, x.device))
+        else:
+            _lib.sa_forward_f32(x, centres, group_idx, feats, layers, [bn.eps for bn in self.mlp_bns], out,
+                                _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
         return new_xyz, out
 
     def _all_rows(self, x, feats, centres):
@@ -391,7 +419,7 @@ _FP_EVAL_ONLY = ("the HIP feature propagation is built for eval mode (BatchNorm 
                  "or build the block with batch_stats=True")
 
 
-class PointNetFeaturePropagation(nn.Module):
+class PointNetFeaturePropagation(_EvalForwardPrecision, nn.Module):
     """One feature-propagation layer: every fine point takes the inverse-squared-distance weighted mean of the features of its 3 nearest
     coarse points (utils.three_nn; all of them when there are fewer than 3), concatenated behind its own features, through the shared MLP
     `mlp` (Conv1d 1x1 + BatchNorm1d + ReLU per entry).  `in_channel` = D1 + D2, as in the usual implementation.
@@ -399,12 +427,16 @@ class PointNetFeaturePropagation(nn.Module):
     conv / BatchNorm affine parameters.  grad=False (default): no graph, ever.
     batch_stats=False (default): eval mode only, the running statistics frozen; train mode raises.  batch_stats=True: train mode is
     accepted and runs BatchNorm on the batch's statistics, updating running_mean / running_var (momentum: the `momentum` attribute of the
-    block's mlp_bns, one value for the block) and num_batches_tracked once per forward, graph or not; eval mode is unchanged."""
+    block's mlp_bns, one value for the block) and num_batches_tracked once per forward, graph or not; eval mode is unchanged.
+    precision (keyword-only; set_precision(mode)): None or 'fp32' -- the exact-fp32 kernel, whatever the library's mode is; 'bf16' -- the
+    eval forward without a graph through ampnet_fp_forward_bf16 (the module docstring), refused together with grad=True or
+    batch_stats=True."""
 
-    def __init__(self, in_channel, mlp, device='cuda', grad=False, batch_stats=False):
+    def __init__(self, in_channel, mlp, device='cuda', grad=False, batch_stats=False, *, precision=None):
         super().__init__()
         self.grad = bool(grad)
         self.batch_stats = bool(batch_stats)
+        self.set_precision(precision)
         _build_mlp(self, in_channel, mlp, (1,), 1 <= in_channel <= _lib.FP_MAX_CIN,
                    f"the HIP feature propagation is built for 1..{_lib.FP_MAX_LAYERS} MLP layers of widths that are "
                    f"multiples of 32 up to {_lib.FP_MAX_COUT} and 1 <= in_channel <= {_lib.FP_MAX_CIN}", device)
@@ -438,6 +470,10 @@ class PointNetFeaturePropagation(nn.Module):
             out = self._forward_rows(rows(xyz1), rows(xyz2), rows(points1), rows(points2))
         return out.transpose(1, 2).contiguous()
 
+    def _bf16_refusal(self):
+        flags = [f for f in ("grad", "batch_stats") if getattr(self, f)]
+        return f"this block was built with {', '.join(f + '=True' for f in flags)}" if flags else None
+
     def _wants_grad(self, p1, p2):
         return self.grad and torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in (p1, p2))
                                                           or any(p.requires_grad for p in self.parameters()))
@@ -445,6 +481,7 @@ class PointNetFeaturePropagation(nn.Module):
     def _forward_rows(self, x1, x2, p1, p2):
         """The layer on point-major tensors: x1 [B, N, 3], x2 [B, S, 3], p1 [B, N, D1] or None, p2 [B, S, D2], float32 contiguous GPU
         -> [B, N, mlp[-1]]."""
+        self._check_bf16()
         idx, dist2 = U.three_nn(x1.detach(), x2.detach())
         if self.training:
             return self._train_rows(p1, p2, idx, dist2)
@@ -453,8 +490,13 @@ class PointNetFeaturePropagation(nn.Module):
             return autograd.fp_apply(self, p1, p2, idx, dist2, _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
         layers = _mlp_tensors(self)
         out = torch.empty((x1.shape[0], x1.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
-        _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out,
-                            _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
+        if is_bf16(self.precision):
+            need = _lib.fp_forward_bf16_workspace_bytes(0 if p1 is None else p1.shape[2], p2.shape[2], x1.shape[0], x1.shape[1],
+                                                        [w.shape[0] for w, *_ in layers])
+            _lib.fp_forward_bf16(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out, _workspace(self, need, x1.device))
+        else:
+            _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out,
+                                _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
         return out
 
     def _train_rows(self, p1, p2, idx, dist2):

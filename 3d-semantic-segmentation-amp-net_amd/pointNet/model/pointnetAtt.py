@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from ... import _lib, ops
 from ... import params as P
+from ._precision import _EvalForwardPrecision, _HasPrecision, is_bf16     # noqa: F401  (_HasPrecision: _baseline.py takes it from here)
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction
 
 
@@ -75,17 +76,6 @@ def _named_tensors(module):
     d = {k: v for k, v in module.named_parameters()}
     d.update({k: v for k, v in module.named_buffers() if not k.endswith("num_batches_tracked")})
     return d
-
-
-class _HasPrecision:
-    """Mix-in of the modules that launch kernels: `precision` is the matrix precision every C-ABI call made on the module's behalf runs
-    in (_lib.precision_scope), None = follow the library's process-wide default.  A forward in grad mode records the mode it ran in and
-    its backward runs in that mode (autograd.py), so changing the attribute between the two does not touch a step under way."""
-    precision = None
-
-    def set_precision(self, mode):
-        self.precision = None if mode is None else _lib.checked_precision(mode)
-        return self
 
 
 class _TableCache:
@@ -420,7 +410,7 @@ class ClassificationWithAttention(_HasPrecision, nn.Module):
         return out
 
 
-class pointnet_2(nn.Module):
+class pointnet_2(_EvalForwardPrecision, nn.Module):
     """The PointNet++ backbone of pointnetAtt.py:282-322 in eval mode: three set-abstraction layers (`sa1`..`sa3`), three
     feature-propagation layers (`fp3`..`fp1`) and `conv1`, with the reference's constructor argument, attribute names, layer sizes and
     state_dict keys.  forward(xyz [B, 9, N]) -> (global_feature [B, 128], l0_points [B, 128, N]); the nine input channels are the point
@@ -444,10 +434,14 @@ class pointnet_2(nn.Module):
     encoder_batch_stats=True (needs encoder_grad=True and decoder_batch_stats=True, else ValueError) trains the model from scratch as
     torch trains it: `sa1`..`sa3` are built with batch_stats=True and .train(mode) puts the WHOLE model in `mode`.  In train mode every
     block normalises with the statistics of its batch (the set abstraction over all B * npoint * nsample rows), updates its running
-    statistics and num_batches_tracked, and back-propagates through the statistics."""
+    statistics and num_batches_tracked, and back-propagates through the statistics.
+
+    precision (keyword-only; also set_precision(mode)) is handed to the six blocks (pointnet2_utils.py): None and 'fp32' are the exact-fp32
+    kernels whatever the library's mode is, 'bf16' runs every block's matrix products in bf16 -- an inference mode, refused
+    (NotImplementedError) together with any of the four flags above.  `conv1` and the max stay torch fp32."""
 
     def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False,
-                 encoder_batch_stats=False):
+                 encoder_batch_stats=False, *, precision=None):
         super().__init__()
         self.decoder_grad = bool(decoder_grad)
         self.encoder_grad = bool(encoder_grad)
@@ -470,6 +464,17 @@ class pointnet_2(nn.Module):
         self.fp2 = PointNetFeaturePropagation(320, [256, 128], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
         self.fp1 = PointNetFeaturePropagation(128, [128, 128, 128], device=device, grad=self.decoder_grad, batch_stats=self.decoder_batch_stats)
         self.conv1 = nn.Conv1d(128, 128, 1, device=device)
+        self.set_precision(precision)
+
+    def _bf16_refusal(self):
+        flags = [f for f in ("decoder_grad", "encoder_grad", "decoder_batch_stats", "encoder_batch_stats") if getattr(self, f)]
+        return f"this model was built with {', '.join(f + '=True' for f in flags)}" if flags else None
+
+    def set_precision(self, mode):
+        super().set_precision(mode)                                  # (the model's own refusals first: nothing is half set)
+        for m in (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1):
+            m.set_precision(self.precision)
+        return self
 
     def train(self, mode=True):
         super().train(mode)
@@ -482,6 +487,7 @@ class pointnet_2(nn.Module):
         if self.training and not self.decoder_batch_stats:
             raise NotImplementedError("pointnet_2 on the HIP path is built for eval mode (BatchNorm running statistics, no backward): "
                                       "call .eval() first")
+        self._check_bf16()
         _lib.require_gpu(xyz, "xyz")
         if xyz.dim() != 3 or xyz.shape[1] != 9:
             raise _lib.AmpnetError(f"pointnet_2: expected xyz [B, 9, N], got {tuple(xyz.shape)}")

@@ -416,6 +416,35 @@ int ampnet_fp_forward_f32(const float *points1, int D1, const float *points2, in
                           const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
                           float *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the two eval forwards with their matrix products in bf16 (inference; added within ABI 17: new symbols, nothing else moved) --------
+ * ampnet_sa_forward_bf16 takes the arguments of ampnet_sa_forward_f32 and ampnet_fp_forward_bf16 those of ampnet_fp_forward_f32; inputs
+ * and outputs stay float32, and the groups, the neighbours and the interpolation weights are the caller's, as there.  They are entry
+ * points of their own: neither ampnet_set_matrix_precision nor a precision scope selects them, and the *_f32 entry points stay exact
+ * fp32 whatever the mode is.
+ * THE ROUNDING MODEL.  For a row x_0 -- set abstraction: [relative xyz, feats]; feature propagation: [points1, interpolated points2] --
+ * formed in fp32 exactly as the *_f32 entry point forms it:
+ *   xb_0 = bf16(x_0) and Wb_l = bf16(W_l), round to nearest even, once;
+ *   a_l  = sum_k Wb_l[., k] xb_l[k], every product exact and the sum accumulated in fp32 by v_mfma_f32_32x32x16_bf16, k ascending in
+ *          blocks of 16 (the contraction padded to a multiple of 16 with zeros).  The order is a function of the shape alone: no atomics,
+ *          the same bits run to run;
+ *   y_l  = relu(fma(a_l, scale_l, shift_l)) in fp32, scale and shift the folded BatchNorm constants of ampnet_sa_forward_f32;
+ *   xb_{l+1} = bf16(y_l); the LAST layer's y stays fp32 and goes to the *_f32 entry point's epilogue: the max over the group's rows (set
+ *          abstraction: filler slots and the rows that pad a tile repeat a row of the group and cannot change it), or the store.
+ * tests/pn2_bf16_ref.py restates this in float64 with the roundings switchable.
+ *   workspace   ampnet_*_forward_bf16_workspace_bytes(..) device bytes, 16-byte aligned: the fold of the *_f32 entry point and behind it
+ *               every layer's weights as bf16 rows [cout_l][cin_l padded to 16], written once per call.  The size functions answer on the
+ *               host from the shape (D, n_clouds, s, nsample | D1, D2, n_clouds, n) and the widths; 0 = the shape is outside the limits
+ *               (ampnet_last_error says which).
+ * Limits are those of the *_f32 entry points (AMPNET_E_ARG otherwise, there is no other path).                                        */
+size_t ampnet_sa_forward_bf16_workspace_bytes(int D, int n_clouds, int s, int nsample, const int *cout_host, int L);
+int ampnet_sa_forward_bf16(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                           int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                           const float *eps_host, int L, float *out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ampnet_fp_forward_bf16_workspace_bytes(int D1, int D2, int n_clouds, int n, const int *cout_host, int L);
+int ampnet_fp_forward_bf16(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                           const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                           float *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the backward of ampnet_fp_forward_f32 with BatchNorm's running statistics frozen (decoder fine-tuning) --------------------------
  *   points1 .. eps_host, L   the forward's arguments, unchanged (the forward keeps nothing: the backward recomputes it)
  *   dout                  [n_clouds, n, cout_{L-1}] float32, the gradient of the forward's `out`

@@ -13,7 +13,10 @@ fpt_fold_kernel, L + 1 fpt_bwd_phase_kernel with fpt_bwd_finalize_kernel between
 fp_scatter_kernel) against torch's train-mode composition -- conv1d + batch_norm(training=True) + relu per layer -- on the SAME interpolated
 rows, which torch is handed ready-made (the fused side interpolates in its forward and gathers dpoints2 in its backward).  Same protocol:
 HIP events, `steps` calls after `warmup`, three alternating rounds, the median round reported.  Per-kernel times: a kernel-trace run of
-this tool, on its own, never together with counters."""
+this tool, on its own, never together with counters.
+The bf16 leg ("bf16" in the JSON line): ampnet_fp_forward_bf16 (sa_fold_kernel, mlp_bf16_weights_kernel, fp_forward_bf16_kernel) on the same
+inputs in the same process, timed against ampnet_fp_forward_f32 in three alternating rounds, every round reported.  A third argument
+`forward` ends the run after the forward legs."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -76,6 +79,20 @@ with torch.no_grad():
     err_own = float((out - torch_layer()).abs().max())
     t_idx = torch.cdist(fine, coarse).topk(3, dim=-1, largest=False)[1]
     other = float((t_idx.sort(-1)[0] != idx.long().sort(-1)[0]).any(-1).float().mean())
+    # ---- the bf16 leg: the two arithmetics in alternating rounds ----
+    ws16 = torch.empty(L.fp_forward_bf16_workspace_bytes(D1, D2, B, N, MLP), dtype=torch.uint8, device=dev)
+    out16 = torch.empty_like(out)
+    fwd32 = lambda: L.fp_forward_f32(None, feats, idx, dist2, layers, [1e-5] * len(MLP), out, ws)
+    fwd16 = lambda: L.fp_forward_bf16(None, feats, idx, dist2, layers, [1e-5] * len(MLP), out16, ws16)
+    f_rounds = [(timed(fwd32), timed(fwd16)) for _ in range(3)]
+    bf16 = {"fp_forward_f32_ms": round(sorted(r[0] for r in f_rounds)[1], 4), "fp_forward_bf16_ms": round(sorted(r[1] for r in f_rounds)[1], 4),
+            "rounds_ms_f32_bf16": [[round(a, 4), round(b, 4)] for a, b in f_rounds],
+            "f32_over_bf16": round(sorted(r[0] for r in f_rounds)[1] / sorted(r[1] for r in f_rounds)[1], 2),
+            "max_abs_diff_bf16_vs_f32": float((out16 - out).abs().max()), "max_abs_out": float(out.abs().max())}
+if len(sys.argv) > 3 and sys.argv[3] == "forward":
+    print(json.dumps({"shape": {"B": B, "N": N, "S": S, "D1": D1, "D2": D2, "mlp": MLP}, "three_nn_ms": round(nn_ms, 4),
+                      "fp_forward_ms": round(fp_ms, 4), "bf16": bf16}))
+    sys.exit(0)
 
 # ---- the backward leg -----------------------------------------------------------------------------------------------------------------
 dout = torch.from_numpy(synth.uniform(212, (B, N, MLP[-1]), -1.0, 1.0)).to(dev)
@@ -172,4 +189,4 @@ print(json.dumps({"shape": {"B": B, "N": N, "S": S, "D1": D1, "D2": D2, "mlp": M
                   "fp_backward_ms": round(fb_ms, 4), "torch_backward_ms": round(tb_ms, 4), "torch_backward_over_fused": round(tb_ms / fb_ms, 2),
                   "backward_rounds_ms_fused_torch": [[round(a, 4), round(b, 4)] for a, b in rounds],
                   "fp_backward_useful_TFLOPs": round(bwd_flops / (fb_ms * 1e-3) / 1e12, 2), "fp_backward_workspace_MB": round(bws.numel() / 1e6, 1),
-                  "backward_max_rel_diff_vs_torch": bwd_diff, "backward_hbm_counters": "not measured", "train": train}))
+                  "backward_max_rel_diff_vs_torch": bwd_diff, "backward_hbm_counters": "not measured", "train": train, "bf16": bf16}))

@@ -29,7 +29,10 @@ nsample (16, 32), D = 9, [32, 32, 64] twice) and an sa3-like one (a 256-point cl
 bare kernels on preallocated outputs, without the helpers' validation of the centres; (b) one sa_msg_forward_f32 (two sa_fold_kernel launches,
 sa_msg_forward_kernel) against two sa_forward_f32 calls plus torch.cat.  Five alternating rounds, every round reported, medians quoted.
 python3 tools/prof_sa.py [steps] [warmup] msg        -- the msg leg alone; prints one JSON line.
-python3 tools/prof_sa.py [steps] [warmup] msg-trace  -- nothing but ball_query_msg and sa_msg_forward_f32, for a kernel trace."""
+python3 tools/prof_sa.py [steps] [warmup] msg-trace  -- nothing but ball_query_msg and sa_msg_forward_f32, for a kernel trace.
+The bf16 leg, at the sa1 shape above: ampnet_sa_forward_bf16 (sa_fold_kernel, mlp_bf16_weights_kernel, sa_forward_bf16_kernel) against
+ampnet_sa_forward_f32 on the same groups in the same process, three alternating rounds, every round reported ("bf16" in the JSON line).
+python3 tools/prof_sa.py [steps] [warmup] bf16       -- the bf16 leg alone; prints one JSON line."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -357,6 +360,24 @@ def msg_leg(trace):
     return res
 
 
+def bf16_leg():
+    """The eval forward under its two arithmetics at the sa1 shape, in alternating rounds."""
+    with torch.no_grad():
+        ws16 = torch.empty(L.sa_forward_bf16_workspace_bytes(D, B, S, K, MLP), dtype=torch.uint8, device=dev)
+        out16 = torch.empty_like(out)
+        fwd32 = lambda: L.sa_forward_f32(xyz, cent, grp, feats, layers, [1e-5] * len(MLP), out, ws)
+        fwd16 = lambda: L.sa_forward_bf16(xyz, cent, grp, feats, layers, [1e-5] * len(MLP), out16, ws16)
+        rounds = [(timed(fwd32), timed(fwd16)) for _ in range(3)]
+        m32, m16 = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
+        return {"sa_forward_f32_ms": round(m32, 4), "sa_forward_bf16_ms": round(m16, 4), "f32_over_bf16": round(m32 / m16, 2),
+                "rounds_ms_f32_bf16": [[round(a, 4), round(b, 4)] for a, b in rounds],
+                "max_abs_diff_bf16_vs_f32": float((out16 - out).abs().max()), "max_abs_out": float(out.abs().max())}
+
+
+if mode == "bf16":
+    print(json.dumps({"shape": {"B": B, "N": N, "npoint": S, "nsample": K, "D": D, "mlp": MLP, "radius": RADIUS}, "bf16": bf16_leg()}))
+    sys.exit(0)
+
 if mode in ("msg", "msg-trace"):
     r = msg_leg(mode == "msg-trace")
     print(json.dumps({"trace_only": True, "msg_calls_per_shape": steps} if mode == "msg-trace" else {"msg": r}))
@@ -391,4 +412,5 @@ print(json.dumps({"shape": {"B": B, "N": N, "npoint": S, "nsample": K, "D": D, "
                   "mean_members": round(float(cnt.float().mean()), 2), "ball_query_ms": round(bq_ms, 4), "sa_forward_ms": round(sa_ms, 4),
                   "torch_gather_conv2d_max_ms": round(torch_ms, 4), "torch_over_fused": round(torch_ms / sa_ms, 2),
                   "sa_algorithmic_bytes": algo, "sa_GBps_at_algorithmic_bytes": round(algo / (sa_ms * 1e-3) / 1e9, 1),
-                  "sa_useful_TFLOPs": round(flops / (sa_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch": err, "backward": backward_leg(), "train": train_leg(False)}))
+                  "sa_useful_TFLOPs": round(flops / (sa_ms * 1e-3) / 1e12, 2), "max_abs_diff_vs_torch": err, "backward": backward_leg(), "train": train_leg(False),
+                  "bf16": bf16_leg()}))

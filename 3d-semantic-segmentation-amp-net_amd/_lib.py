@@ -675,3 +675,88 @@ def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, 
                                                 len(layers), ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws, ws_bytes,
                                                 stream_ptr(points2.device))
     check(rc, "ampnet_fp_train_backward_f32")
+
+
+# ---- the segmentation head: per-point classifier, eval forward and frozen-statistics backward ------------------------------------------
+SEG_HEAD_MAX_CIN, SEG_HEAD_MAX_HIDDEN, SEG_HEAD_MAX_CLASSES = 256, 256, 32
+
+
+def _seg_head_bytes(symbol, cin, hidden, n_classes, M):
+    fn = getattr(lib(), symbol)
+    fn.restype = ctypes.c_size_t
+    need = fn(int(cin), int(hidden), int(n_classes), ctypes.c_longlong(int(M)))
+    if not need:
+        check(-1, symbol)
+    return int(need)
+
+
+def seg_head_forward_workspace_bytes(cin, hidden, n_classes, M):
+    """Device bytes seg_head_forward_f32 needs (the BatchNorm fold); a shape outside the kernel's limits is an AmpnetError that names the
+    limit."""
+    return _seg_head_bytes("ampnet_seg_head_forward_workspace_bytes", cin, hidden, n_classes, M)
+
+
+def seg_head_backward_workspace_bytes(cin, hidden, n_classes, M):
+    """Device bytes seg_head_backward_f32 needs for M rows (include/ampnet_hip.h: ampnet_seg_head_backward_workspace_bytes)."""
+    return _seg_head_bytes("ampnet_seg_head_backward_workspace_bytes", cin, hidden, n_classes, M)
+
+
+def _seg_head_args(prefix, x, params, eps, extra):
+    """x [M, ld] and the 8 parameters W1 [hidden, cin], b1, gamma, beta, running_mean, running_var, W2 [n_classes, hidden], b2 ->
+    (M, ld, cin, hidden, n_classes, the pointer table of the C ABI).  conv1 is a layer of _mlp_tables; extra as in _sa_geometry."""
+    _check_tensors(prefix, [("x", x, _F32, 2, True)] + extra)
+    if len(params) != 8 or not torch.is_tensor(params[0]) or params[0].dim() != 2:
+        raise AmpnetError(f"{prefix}: params must be the 8 tensors W1 [hidden, cin], b1, gamma, beta, running_mean, running_var, "
+                          f"W2 [n_classes, hidden], b2")
+    hidden, cin = (int(v) for v in params[0].shape)
+    _mlp_tables(prefix, [tuple(params[:6])], cin, [eps])
+    w2, b2 = params[6], params[7]
+    n_classes = int(w2.shape[0]) if torch.is_tensor(w2) and w2.dim() == 2 else -1
+    want = [(n_classes, hidden), (n_classes,)]
+    if any(not torch.is_tensor(t) or tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+           for t, w in zip((w2, b2), want)):
+        raise AmpnetError(f"{prefix}: W2 and b2 must be contiguous float32 GPU tensors of shapes [n_classes, {hidden}] and [n_classes], got "
+                          f"{[tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in (w2, b2)]}")
+    M, ld = x.shape
+    if ld < cin:
+        raise AmpnetError(f"{prefix}: x {tuple(x.shape)} must be [M, ld >= cin] with cin = {cin}")
+    return M, ld, cin, hidden, n_classes, (ctypes.c_void_p * 8)(*[t.data_ptr() for t in params])
+
+
+def seg_head_forward_f32(x, params, eps, logp, preds, workspace):
+    """The fused per-point classifier in eval mode (include/ampnet_hip.h: ampnet_seg_head_forward_f32).  x [M, ld >= cin] float32 rows,
+    params the 8 tensors W1 [hidden, cin], b1, gamma, beta, running_mean, running_var, W2 [n_classes, hidden], b2, eps BatchNorm's;
+    logp [M, n_classes] float32 and preds [M] int64 (or None): written; workspace: seg_head_forward_workspace_bytes(...) GPU bytes."""
+    M, ld, cin, hidden, C, table = _seg_head_args("seg_head_forward", x, params, eps, [("logp", logp, _F32, 2, True),
+                                                                                         ("preds", preds, torch.int64, 1, False)])
+    if tuple(logp.shape) != (M, C) or (preds is not None and tuple(preds.shape) != (M,)):
+        raise AmpnetError(f"seg_head_forward: logp {tuple(logp.shape)} must be [M, n_classes] = {[M, C]} and preds "
+                          f"{None if preds is None else tuple(preds.shape)} [M] or None")
+    ws, ws_bytes = _workspace_args("seg_head_forward", workspace)
+    with torch.cuda.device(x.device):
+        rc = lib().ampnet_seg_head_forward_f32(ptr(x), ld, ctypes.c_longlong(M), cin, hidden, C, table, ctypes.c_float(float(eps)), ptr(logp),
+                                               ptr(preds), ws, ws_bytes, stream_ptr(x.device))
+    check(rc, "ampnet_seg_head_forward_f32")
+
+
+def seg_head_backward_f32(x, params, eps, dlogp, dx, grads, workspace):
+    """The backward of seg_head_forward_f32 with the running statistics frozen.  x, params, eps: the forward's; dlogp [M, n_classes] any
+    upstream gradient; dx [M, cin] or None (not wanted) and grads = (dW1, db1, dgamma, dbeta, dW2, db2): written; workspace:
+    seg_head_backward_workspace_bytes(...) GPU bytes."""
+    M, ld, cin, hidden, C, table = _seg_head_args("seg_head_backward", x, params, eps, [("dlogp", dlogp, _F32, 2, True),
+                                                                                          ("dx", dx, _F32, 2, False)])
+    if tuple(dlogp.shape) != (M, C):
+        raise AmpnetError(f"seg_head_backward: dlogp {tuple(dlogp.shape)} must be [M, n_classes] = {[M, C]}")
+    if dx is not None and tuple(dx.shape) != (M, cin):
+        raise AmpnetError(f"seg_head_backward: dx {tuple(dx.shape)} must be [M, cin] = {[M, cin]} or None")
+    want = [tuple(params[q].shape) for q in (0, 1, 1, 1, 6, 7)]
+    if len(grads) != 6 or any(not torch.is_tensor(t) or tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                              for t, w in zip(grads, want)):
+        raise AmpnetError(f"seg_head_backward: grads must be six contiguous float32 GPU tensors (dW1, db1, dgamma, dbeta, dW2, db2) of "
+                          f"shapes {want}, got {[tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in grads]}")
+    gtable = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in grads])
+    ws, ws_bytes = _workspace_args("seg_head_backward", workspace)
+    with torch.cuda.device(x.device):
+        rc = lib().ampnet_seg_head_backward_f32(ptr(x), ld, ctypes.c_longlong(M), cin, hidden, C, table, ctypes.c_float(float(eps)), ptr(dlogp),
+                                                ptr(dx), gtable, ws, ws_bytes, stream_ptr(x.device))
+    check(rc, "ampnet_seg_head_backward_f32")

@@ -417,3 +417,53 @@ def sa_train_apply(module, x, centres, group_idx, feats, momentum, w0=None):
     stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
     return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats,
                             *_block_tensors(module, stats=False, w0=w0))
+
+
+def seg_head_tensors(module):
+    """The eight tensors of a PointNetSegHead, the module's own: conv1 weight [hidden, in, 1] and bias, bn1 weight, bias, running_mean,
+    running_var, conv2 weight [classes, hidden, 1] and bias."""
+    return [module.conv1.weight, module.conv1.bias, module.bn1.weight, module.bn1.bias, module.bn1.running_mean, module.bn1.running_var,
+            module.conv2.weight, module.conv2.bias]
+
+
+def seg_head_params(tensors):
+    """The eight contiguous float32 tensors the C ABI takes, from seg_head_tensors' (the conv weights as [out, in])."""
+    return [t.detach().reshape(t.shape[0], -1).float().contiguous() if q in (0, 6) else t.detach().float().contiguous()
+            for q, t in enumerate(tensors)]
+
+
+class _SegHeadFn(torch.autograd.Function):
+    """The fused per-point classifier with bn1's running statistics frozen (pointnet2_utils.PointNetSegHead with grad=True).  rows [M, cin];
+    tensors: seg_head_tensors.  The forward is the eval forward, unchanged, and keeps no activation: the backward kernel recomputes them
+    (csrc/seg_head_bwd.hip).  Exact fp32 whatever the matrix precision is, so there is no precision scope to carry over."""
+
+    @staticmethod
+    def forward(ctx, eps, fold_ws, rows, *tensors):
+        params = seg_head_params(tensors)
+        logp = torch.empty((rows.shape[0], params[6].shape[0]), dtype=torch.float32, device=rows.device)
+        _lib.seg_head_forward_f32(rows, params, eps, logp, None, fold_ws)
+        ctx.save_for_backward(rows, *tensors)                      # (inputs only: see the note in _EncoderFn.forward)
+        ctx.eps = eps
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        rows, *tensors = ctx.saved_tensors
+        params = seg_head_params(tensors)
+        need_grad = ctx.needs_input_grad
+        dx = torch.empty((rows.shape[0], params[0].shape[1]), dtype=torch.float32, device=rows.device) if need_grad[2] else None
+        slots = (0, 1, 2, 3, 6, 7)                                 # the tensors that have a gradient, in the C ABI's order
+        grads = [torch.empty_like(params[q]) for q in slots]
+        need = _lib.seg_head_backward_workspace_bytes(params[0].shape[1], params[0].shape[0], params[6].shape[0], rows.shape[0])
+        _lib.seg_head_backward_f32(rows, params, ctx.eps, dlogp.contiguous().float(), dx, grads, _ws(need, rows.device))
+        ret = [None] * 8
+        for g, q in zip(grads, slots):
+            if need_grad[3 + q]:
+                ret[q] = g.reshape(tensors[q].shape)
+        return (None, None, dx) + tuple(ret)
+
+
+def seg_head_apply(module, rows, fold_ws):
+    """Grad-mode forward of a PointNetSegHead on rows [M, in_channel] -> log-probabilities [M, num_classes] with a graph to the rows and to
+    the head's conv1, bn1 (weight and bias) and conv2."""
+    return _SegHeadFn.apply(module.bn1.eps, fold_ws, rows, *seg_head_tensors(module))

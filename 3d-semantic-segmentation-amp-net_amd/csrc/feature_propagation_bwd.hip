@@ -46,44 +46,6 @@ struct FpBwdPlan {
     float *xs[MLP_MAX_LAYERS], *dz[MLP_MAX_LAYERS], *dx0, *parts;
 };
 
-// The accumulators of layer l on the wave's tile x, NT column tiles from n0, in the forward's order (mlp_accumulate<NT, K_QUADS, VEC>), and the
-// backward's epilogue: d [32][ldd] holds dx_l on entry (dout != nullptr: the rows come from global memory, row stride cout) and dz on exit.
-template <int NT, bool VEC>
-__device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
-                                              const float *__restrict__ scale, const float *__restrict__ shift, float *d, int ldd,
-                                              const float *__restrict__ dout, int rows, float *__restrict__ dz_ws, float *part_b,
-                                              float *part_g, int lane)
-{
-    const int r = lane & 31, h = lane >> 5;
-    f32x16 acc[NT];
-    mlp_accumulate<NT, K_QUADS, VEC>(acc, mlp_operand<K_QUADS>(x, ldx, r, h), w, cin, cin, kp, n0, r, h);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int col = n0 + 32 * t + r;
-        const float sc = scale[col], sh = shift[col];
-        float sb = 0.0f, sg = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = mlp_acc_row(i, h);
-            const float a = acc[t][i];
-            float din;
-            if (dout) din = row < rows ? dout[(size_t)row * cout + col] : 0.0f;
-            else din = d[row * ldd + col];
-            const float dy = fmaf(a, sc, sh) > 0.0f ? din : 0.0f;
-            sb += dy;
-            sg = fmaf(dy, a, sg);
-            const float dzv = dy * sc;
-            d[row * ldd + col] = dzv;
-            if (row < rows) dz_ws[(size_t)row * cout + col] = dzv;
-        }
-        const float ob = __shfl_down(sb, 32), og = __shfl_down(sg, 32);
-        if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
-            part_b[col] += sb + ob;
-            part_g[col] += sg + og;
-        }
-    }
-}
-
 __global__ __launch_bounds__(64) void fp_backward_kernel(MlpPlan p, FpBwdPlan b, const float *__restrict__ points1, int D1,
                                                         const float *__restrict__ points2, int D2, int n, int s,
                                                         const int32_t *__restrict__ idx, const float *__restrict__ dist2, int k,

@@ -2,7 +2,8 @@
 // kernels and their launchers: mlp_bwd.hip): the split-K GEMM dW_l = dz_l^T x_l over rows kept in the workspace, its ordered reduce,
 // the finalize kernel that turns the workgroups' per-channel partial sums into dbeta, dgamma and dbias, the chunk rule, the common part of
 // the workspace layout, and the device code all four backwards (eval and train-mode) run on a wave's 32-row tile: the row stores and loads
-// between LDS and the workspace and dx = dz W (mlp_dgrad).  The raw accumulator they recompute is the forward's, fused_mlp.h's
+// between LDS and the workspace and dx = dz W (mlp_dgrad); and the recompute-and-mask step of the frozen-statistics backwards that have no
+// max to undo (fpb_recompute: feature propagation, and conv1 of the segmentation head, seg_head_bwd.hip).  The raw accumulator they recompute is the forward's, fused_mlp.h's
 // mlp_accumulate, where the lane map and the two contraction orders are defined.
 #pragma once
 #include "fused_mlp.h"
@@ -69,6 +70,45 @@ __device__ __forceinline__ void fpb_load_rows_flat(float *tile, int ld, int widt
     for (int e = lane; e < 32 * width; e += 64) {
         const int t = e / width, c = e - t * width;
         tile[t * ld + c] = t < rows ? g[(size_t)t * ldg + c] : 0.0f;
+    }
+}
+
+// The accumulators of layer l on the wave's tile x, NT column tiles from n0, in the forward's order (mlp_accumulate<NT, K_QUADS, VEC>), and the
+// frozen-statistics backward's epilogue (feature_propagation_bwd.hip, seg_head_bwd.hip): d [32][ldd] holds dx_l on entry (dout != nullptr: the
+// rows come from global memory, row stride cout) and dz on exit.
+template <int NT, bool VEC>
+__device__ __forceinline__ void fpb_recompute(const float *x, int ldx, const float *__restrict__ w, int cin, int kp, int cout, int n0,
+                                              const float *__restrict__ scale, const float *__restrict__ shift, float *d, int ldd,
+                                              const float *__restrict__ dout, int rows, float *__restrict__ dz_ws, float *part_b,
+                                              float *part_g, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc[NT];
+    mlp_accumulate<NT, K_QUADS, VEC>(acc, mlp_operand<K_QUADS>(x, ldx, r, h), w, cin, cin, kp, n0, r, h);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = n0 + 32 * t + r;
+        const float sc = scale[col], sh = shift[col];
+        float sb = 0.0f, sg = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = mlp_acc_row(i, h);
+            const float a = acc[t][i];
+            float din;
+            if (dout) din = row < rows ? dout[(size_t)row * cout + col] : 0.0f;
+            else din = d[row * ldd + col];
+            const float dy = fmaf(a, sc, sh) > 0.0f ? din : 0.0f;
+            sb += dy;
+            sg = fmaf(dy, a, sg);
+            const float dzv = dy * sc;
+            d[row * ldd + col] = dzv;
+            if (row < rows) dz_ws[(size_t)row * cout + col] = dzv;
+        }
+        const float ob = __shfl_down(sb, 32), og = __shfl_down(sg, 32);
+        if (h == 0) {                             // (this lane alone ever touches these two words of the workgroup's partials)
+            part_b[col] += sb + ob;
+            part_g[col] += sg + og;
+        }
     }
 }
 

@@ -46,6 +46,10 @@ PointNetSetAbstractionMsg is the multi-scale-grouping layer of the usual impleme
 mlp) branches around the same centres, concatenated.  Farthest-point sampling runs once, one ball query fills all index lists
 (ampnet_ball_query_msg_f32) and in eval mode one launch runs all branches (ampnet_sa_msg_forward_f32); grad=True and batch_stats=True go
 branch by branch through the kernels above.  It serves models defined inside the set-abstraction limits (its docstring).
+
+PointNetSegHead is the per-point classifier behind the backbone (conv1, bn1, ReLU, drop1, conv2, log_softmax): one fused kernel in eval
+mode (ampnet_seg_head_forward_f32), with grad=True differentiable through ampnet_seg_head_backward_f32 (its docstring;
+pointnetAtt.pointnet_2_seg puts it behind pointnet_2's six blocks).  Its train-mode bn1, dropout, bf16 and a fused loss are not built.
 Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block, a `precision`
 keyword for PointNetSetAbstractionMsg (its one-launch forward is fp32 only), bf16 in a backward, a train-mode or a group_all forward.
 
@@ -513,3 +517,82 @@ class PointNetFeaturePropagation(_EvalForwardPrecision, nn.Module):
                                                       _mlp_tensors(self, live_stats=True), [bn.eps for bn in self.mlp_bns], momentum)
         _count_batch(self)
         return out
+
+
+_SEG_EVAL_ONLY = ("the HIP segmentation head is built for eval mode (bn1 on its running statistics, dropout the identity): call .eval() "
+                  "first")
+
+
+class PointNetSegHead(nn.Module):
+    """The per-point classifier of the usual PointNet++ semantic-segmentation model -- conv1 (Conv1d 1x1), bn1, ReLU, drop1, conv2 (Conv1d
+    1x1), log_softmax over the classes, permute -- the lines the reference's pointnet_2 carries commented out (pointnetAtt.py:294-296,
+    :318-321), as ONE fused kernel (ampnet_seg_head_forward_f32): the hidden activations and the logits never reach memory.
+    `conv1`, `bn1` and `conv2` are holders with the names and shapes of nn.Conv1d(in_channel, hidden, 1), nn.BatchNorm1d(hidden) and
+    nn.Conv1d(hidden, num_classes, 1), `drop1` has no state: a strict state_dict exchange with a torch head built that way works in both
+    directions.  forward(points [B, in_channel, N]) -> log-probabilities [B, N, num_classes]; predict(points) -> the classes, int64 [B, N]
+    (the lowest class among equal logits).
+    Eval mode only: bn1 normalises with its running statistics and dropout is the identity; .train() followed by a call raises.
+    grad=True: with grad mode on and an input or a parameter that requires grad, the result carries a graph to the points and to conv1,
+    bn1's weight and bias and conv2 (ampnet_seg_head_backward_f32 through autograd._SegHeadFn; running_mean and running_var are constants).
+    grad=False (default): no graph, ever.
+    Limits: 1 <= in_channel <= 256, hidden a multiple of 32 in [32, 256], 2 <= num_classes <= 32.  The head is exact fp32 and has no
+    `precision` keyword.  Not built: train-mode bn1 (batch statistics), dropout, bf16, a fused loss (F.nll_loss on the [B * N,
+    num_classes] log-probabilities is a small operation)."""
+
+    def __init__(self, in_channel, hidden, num_classes, dropout=0.5, device='cuda', grad=False):
+        super().__init__()
+        in_channel, hidden, num_classes = int(in_channel), int(hidden), int(num_classes)
+        if not (1 <= in_channel <= _lib.SEG_HEAD_MAX_CIN and 32 <= hidden <= _lib.SEG_HEAD_MAX_HIDDEN and hidden % 32 == 0
+                and 2 <= num_classes <= _lib.SEG_HEAD_MAX_CLASSES):
+            raise NotImplementedError(f"the HIP segmentation head is built for 1 <= in_channel <= {_lib.SEG_HEAD_MAX_CIN}, hidden a multiple "
+                                      f"of 32 in [32, {_lib.SEG_HEAD_MAX_HIDDEN}] and 2 <= num_classes <= {_lib.SEG_HEAD_MAX_CLASSES}, got "
+                                      f"in_channel={in_channel} hidden={hidden} num_classes={num_classes}")
+        self.grad = bool(grad)
+        self.in_channel, self.hidden, self.num_classes = in_channel, hidden, num_classes
+        self.conv1 = _Conv(in_channel, hidden, (1,), device)
+        self.bn1 = _BN2d(hidden, device)
+        self.drop1 = nn.Dropout(dropout)                            # (a holder as well: eval mode, the identity)
+        self.conv2 = _Conv(hidden, num_classes, (1,), device)
+        self._ws = None
+
+    def _wants_grad(self, points):
+        return self.grad and torch.is_grad_enabled() and (points.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    def _check_input(self, points):
+        if self.training:
+            raise NotImplementedError(_SEG_EVAL_ONLY)
+        _lib.require_gpu(points, "points")
+        if points.dim() != 3 or points.shape[1] != self.in_channel:
+            raise _lib.AmpnetError(f"PointNetSegHead: expected points [B, {self.in_channel}, N], got {tuple(points.shape)}")
+
+    def forward(self, points):
+        """points [B, in_channel, N] -> log-probabilities [B, N, num_classes]."""
+        self._check_input(points)
+        if self._wants_grad(points):                                 # a differentiable transpose
+            return self._forward_rows(points.float().transpose(1, 2).contiguous())
+        with torch.no_grad():
+            return self._forward_rows(points.detach().float().transpose(1, 2).contiguous())
+
+    def predict(self, points):
+        """points [B, in_channel, N] -> the class of every point, int64 [B, N]: the kernel's own arg-max of the logits, the lowest class
+        among equal ones (what utils.get_metrics.confusion_device takes).  Never a graph."""
+        self._check_input(points)
+        with torch.no_grad():
+            return self._forward_rows(points.detach().float().transpose(1, 2).contiguous(), want_preds=True)[1]
+
+    def _forward_rows(self, rows, want_preds=False):
+        """The head on point-major rows [B, N, in_channel], float32 contiguous GPU -> [B, N, num_classes]; want_preds: (that, int64
+        [B, N]) without a graph."""
+        if self.training:
+            raise NotImplementedError(_SEG_EVAL_ONLY)
+        from ... import autograd
+        B, N, _ = rows.shape
+        flat = rows.reshape(B * N, self.in_channel)
+        ws = _workspace(self, _lib.seg_head_forward_workspace_bytes(self.in_channel, self.hidden, self.num_classes, B * N), rows.device)
+        if not want_preds and self._wants_grad(rows):
+            return autograd.seg_head_apply(self, flat, ws).reshape(B, N, self.num_classes)
+        logp = torch.empty((B * N, self.num_classes), dtype=torch.float32, device=rows.device)
+        preds = torch.empty((B * N,), dtype=torch.int64, device=rows.device) if want_preds else None
+        _lib.seg_head_forward_f32(flat.detach(), autograd.seg_head_params(autograd.seg_head_tensors(self)), self.bn1.eps, logp, preds, ws)
+        logp = logp.reshape(B, N, self.num_classes)
+        return (logp, preds.reshape(B, N)) if want_preds else logp

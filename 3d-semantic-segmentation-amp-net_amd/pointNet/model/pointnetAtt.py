@@ -26,7 +26,7 @@ import torch.nn as nn
 from ... import _lib, ops
 from ... import params as P
 from ._precision import _EvalForwardPrecision, _HasPrecision, is_bf16     # noqa: F401  (_HasPrecision: _baseline.py takes it from here)
-from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction
+from .pointnet2_utils import PointNetFeaturePropagation, PointNetSegHead, PointNetSetAbstraction
 
 
 class _Conv(nn.Module):
@@ -484,6 +484,13 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
         return self
 
     def forward(self, xyz):
+        _, l0_points = self._backbone(xyz)
+        global_feature = self.conv1(l0_points).amax(2)                                # MaxPool1d(N) + view(-1, 128)
+        return global_feature, l0_points
+
+    def _backbone(self, xyz):
+        """The six blocks -> (fp1's point-major result [B, N, 128] as it left the kernel, l0_points [B, 128, N]): what pointnet_2 puts
+        conv1 and the max behind, and pointnet_2_seg its head."""
         if self.training and not self.decoder_batch_stats:
             raise NotImplementedError("pointnet_2 on the HIP path is built for eval mode (BatchNorm running statistics, no backward): "
                                       "call .eval() first")
@@ -509,7 +516,50 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
         with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
             l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)  # [B, 256, 256]
             l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)  # [B, 1024, 128]
-            l0_points = self.fp1._forward_rows(l0_xyz, l1_xyz, None, l1_points)       # [B, N, 128]
-            l0_points = l0_points.transpose(1, 2).contiguous()                        # [B, 128, N], the reference's layout
-        global_feature = self.conv1(l0_points).amax(2)                                # MaxPool1d(N) + view(-1, 128)
-        return global_feature, l0_points
+            l0_rows = self.fp1._forward_rows(l0_xyz, l1_xyz, None, l1_points)         # [B, N, 128]
+            l0_points = l0_rows.transpose(1, 2).contiguous()                          # [B, 128, N], the reference's layout
+        return l0_rows, l0_points
+
+
+class pointnet_2_seg(pointnet_2):
+    """pointnet_2 with the classifier the reference carries commented out (pointnetAtt.py:294-296, :318-321) restored: the six blocks,
+    then conv1, bn1, ReLU, drop1, conv2 and log_softmax per point as ONE fused kernel (pointnet2_utils.PointNetSegHead).
+    forward(xyz [B, 9, N]) -> (log_probs [B, N, num_classes], l0_points [B, 128, N]); predict(xyz) -> the classes, int64 [B, N].
+    The state_dict keys are sa1..fp1, conv1.*, bn1.*, conv2.* -- what the reference's class would have with those lines restored -- so a
+    pointnet_2 checkpoint loads with strict=False, only bn1.* and conv2.* missing.  `conv1` is the head's first layer here; the global
+    feature of pointnet_2 (conv1 and a max over the points) is not computed.
+
+    The four flags are pointnet_2's, with the same rules; the head runs with grad = decoder_grad, so with decoder_grad=True
+    F.nll_loss(log_probs.reshape(-1, num_classes), target.reshape(-1)).backward() reaches conv2, bn1's weight and bias, conv1 and the
+    decoder (with encoder_grad=True: the whole backbone).  .train(mode) with the batch-statistics flags moves the backbone as in
+    pointnet_2 and KEEPS THE HEAD IN EVAL MODE: bn1 always normalises with its running statistics, which are never updated, and drop1 is
+    always the identity.  Not built: train-mode bn1, dropout, bf16 (the model has no `precision` keyword and refuses set_precision('bf16'))
+    and a fused loss."""
+
+    def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False,
+                 encoder_batch_stats=False):
+        super().__init__(num_classes, device, decoder_grad, encoder_grad, decoder_batch_stats, encoder_batch_stats)
+        head = PointNetSegHead(128, 128, num_classes, device=device, grad=self.decoder_grad)
+        # the reference's flat names; the head itself is not a registered child (its keys would carry a prefix)
+        self.conv1, self.bn1, self.drop1, self.conv2 = head.conv1, head.bn1, head.drop1, head.conv2
+        self.__dict__["_head"] = head.eval()
+
+    def _bf16_refusal(self):
+        return "the segmentation head is exact fp32"
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._head.train(False)                                      # (bn1 and drop1 with it: they are the head's own children)
+        return self
+
+    def forward(self, xyz):
+        l0_rows, l0_points = self._backbone(xyz)
+        with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
+            log_probs = self._head._forward_rows(l0_rows)
+        return log_probs, l0_points
+
+    def predict(self, xyz):
+        """xyz [B, 9, N] -> the class of every point, int64 [B, N] (the lowest class among equal logits).  Never a graph."""
+        with torch.no_grad():
+            l0_rows, _ = self._backbone(xyz)
+            return self._head._forward_rows(l0_rows, want_preds=True)[1]

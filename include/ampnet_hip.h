@@ -650,6 +650,60 @@ int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int n, int ld, 
                                  const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
                                  void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the per-point classifier of the PointNet++ segmentation model, eval mode, fused, and its backward (added within ABI 17: new
+ * symbols, nothing else moved).  Stands in for the lines the reference's pointnet_2 carries commented out (pointnetAtt.py:294-296,
+ * :318-321): bn1, drop1 (the identity in eval mode), conv2, log_softmax, permute.
+ *   x            [M][ld] float32 rows, the first cin columns used, ld >= cin.  The rows are a flat list: the head has no per-cloud structure
+ *   params_host  HOST array of 8 DEVICE pointers: W1 [hidden][cin], b1, gamma, beta, running_mean, running_var (each [hidden]),
+ *                W2 [n_classes][hidden], b2 [n_classes]
+ *   eps          BatchNorm's
+ *   logp         [M][n_classes] float32 out, dense
+ *   preds        [M] int64 out (what ampnet_confusion_i64 takes), or NULL
+ * Arithmetic, per row x:
+ *     a      = W1 x                                       cin ascending in blocks of 8 (padded with zeros), k-step i < 4 of lane half h takes k = k0 + 4 h + i,
+ *                                                         one fmaf chain per element (the order of ampnet_fp_forward_f32)
+ *     h      = relu(fma(a, scale, shift))                 scale = gamma / sqrt(var + eps), shift = (b1 - mean) * scale + beta: the fold of
+ *                                                         ampnet_sa_forward_f32
+ *     z      = W2 h + b2                                  the same contraction order over hidden, then one addition; no BatchNorm, no ReLU
+ *     logp_c = (z_c - m) - logf(S)                        m = max_c z_c,  S = sum over c ascending of expf(z_c - m)
+ *     pred   = the LOWEST c with z_c == m
+ * expf and logf are the accurate library functions (tests/head_probe.py measures them).  Neither h nor z is written to memory.  The
+ * summation orders are functions of the shape alone: the same bits run to run.
+ * Backward, running_mean and running_var frozen, the forward keeps nothing.  dlogp [M][n_classes] is ANY upstream gradient g:
+ *     dz_c = fma(-expf(logp_c), sum over j ascending of g_j, g_c)        logp recomputed by the forward's own code: the forward's bits
+ *     db2  = sum_rows dz          dW2 = dz^T h          dh = dz W2
+ *     dy = dh [y > 0],  dbeta = sum_rows dy,  G = sum_rows dy a,  dgamma = (G + (b1 - mean) dbeta) / sqrt(var + eps),  db1 = scale dbeta,
+ *     dz1 = dy scale,  dW1 = dz1^T x,  dx = dz1 W1          one layer of ampnet_fp_backward_f32, with its summation orders
+ *   dx           [M][cin] float32 out, dense, or NULL: not wanted
+ *   grads_host   HOST array of 6 DEVICE pointers, all out: dW1 [hidden][cin], db1, dgamma, dbeta (each [hidden]), dW2 [n_classes][hidden],
+ *                db2 [n_classes]
+ *   db2          per 32-row tile the rows ascending; a workgroup adds its tiles (tile = workgroup + t * min(tiles, 1024)) ascending; lane t
+ *                of a wave adds workgroups t, t + 64, .. ascending and the 64 lane sums go through a halving tree
+ *   dW2, dh      as dW_l and dx_l of ampnet_fp_backward_f32 with the class dimension padded to 32 by zeros
+ * No float atomics anywhere: two calls on the same inputs return the same bits.
+ * Workspaces (contents undefined before and after; the size functions answer on the host, 0 = the shape is refused and ampnet_last_error
+ * says why).  Forward: the fold, scale [hidden] then shift [hidden].  Backward: the fold; the layout of ampnet_fp_backward_f32 for ONE layer
+ * cin -> hidden (the workgroups' partial sums, the rows x padded to a multiple of 32 columns, dz1 [M][hidden], the split-K partials of
+ * dW); then h [M][hidden], dz [M][32], the workgroups' partial sums of dz [min(tiles, 1024)][32] and dW2 as [32][hidden], of which the
+ * first n_classes rows are copied to the caller's.
+ * Limits (anything else is refused with AMPNET_E_ARG on the host before any launch, there is no other path): 1 <= cin <=
+ * AMPNET_SEG_HEAD_MAX_CIN, hidden a multiple of 32 in [32, AMPNET_SEG_HEAD_MAX_HIDDEN], 2 <= n_classes <= AMPNET_SEG_HEAD_MAX_CLASSES (one
+ * MFMA column tile), 1 <= M <= AMPNET_SEG_HEAD_MAX_ROWS (a wave's tile counter stays inside an int).  Exact fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32) whatever the matrix precision is.
+ * NOT BUILT: train-mode bn1 (batch statistics), dropout (drop1 is the identity of eval mode), bf16, a fused loss (nll_loss on [M][C] is a
+ * small operation of the caller's).                                                                                                  */
+#define AMPNET_SEG_HEAD_MAX_CIN 256
+#define AMPNET_SEG_HEAD_MAX_HIDDEN 256
+#define AMPNET_SEG_HEAD_MAX_CLASSES 32
+#define AMPNET_SEG_HEAD_MAX_ROWS (0x7fff0000LL * 32)
+size_t ampnet_seg_head_forward_workspace_bytes(int cin, int hidden, int n_classes, long long M);
+int ampnet_seg_head_forward_f32(const float *x, int ld, long long M, int cin, int hidden, int n_classes, const float *const *params_host,
+                                float eps, float *logp, long long *preds, void *workspace, size_t workspace_bytes, void *stream);
+size_t ampnet_seg_head_backward_workspace_bytes(int cin, int hidden, int n_classes, long long M);
+int ampnet_seg_head_backward_f32(const float *x, int ld, long long M, int cin, int hidden, int n_classes, const float *const *params_host,
+                                 float eps, const float *dlogp, float *dx, float *const *grads_host, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =
  * n_points, n_init 5, max_iter 10, tol 1e-2, features x, y, NDVI) and utils/utils.py:500-505 (size_min only).  That package is not part

@@ -4,14 +4,12 @@
 // conv/fc bias, T-Net on x[:, :, :2]).  Config 1 of BASELINE.json is the reference's CPU plumbing case ([4, 512, 9]):
 // this path is built for parity, not speed -- every layer is sgemm_small + one affine pass.  BatchNorm uses the
 // running statistics (module.eval()); training this model is not part of the HIP path.
-#include "kernels.h"
+#include "baseline.h"
 
 namespace ampnet {
 namespace {
 
-struct Layer {                 // six device pointers per layer, any of b / BatchNorm may be null
-    const float *W, *b, *g, *be, *rm, *rv;
-};
+using Layer = BlLayer;
 
 struct Dims {
     int k, G, F1, F2, H1, H2, H3;
@@ -92,6 +90,37 @@ __global__ void bl_logits_kernel(const float *__restrict__ z, int B, int N, int 
     logits[i] = z[((size_t)b * N + p) * C + c];
 }
 
+}  // namespace
+
+// ---- launch wrappers (baseline.h) -------------------------------------------------------------------------------------------------------
+void bl_fold(const BlLayer &l, int C, float eps, float *scale, float *shift, hipStream_t st)
+{
+    hipLaunchKernelGGL(bl_fold_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, l, C, eps, scale, shift);
+}
+
+void bl_affine(float *z, size_t n, int C, const float *scale, const float *shift, const float *add, int per, int relu, hipStream_t st)
+{
+    hipLaunchKernelGGL(bl_affine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, n, C, scale, shift, add, per > 0 ? per : 1, relu);
+}
+
+void bl_rowmax(const float *a, int B, int N, int C, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bl_rowmax_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, st, a, N, C, out);
+}
+
+void bl_mix(const float *x, const float *T, int R, int N, int k, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bl_mix_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, x, T, R, N, k, out);
+}
+
+void bl_logits(const float *z, int B, int N, int C, float *logits, hipStream_t st)
+{
+    const size_t n = (size_t)B * N * C;
+    hipLaunchKernelGGL(bl_logits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, B, N, C, logits);
+}
+
+namespace {
+
 struct Ctx {
     hipStream_t st;
     float *scale, *shift;
@@ -110,10 +139,8 @@ int layer(const Ctx &c, const float *A, int lda, int M, int K, const Layer &l, i
 {
     AMPNET_REQUIRE(l.W, "baseline PointNet: a layer has no weight pointer");
     BL_TRY(sgemm_small(0, 1, M, cout, K, A, lda, l.W + w0, ldw, out, cout, 0, c.st));
-    hipLaunchKernelGGL(bl_fold_kernel, dim3(cdiv(cout, 256)), dim3(256), 0, c.st, l, cout, c.eps, c.scale, c.shift);
-    const size_t n = (size_t)M * cout;
-    hipLaunchKernelGGL(bl_affine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, out, n, cout, c.scale, c.shift, add,
-                       per > 0 ? per : 1, relu);
+    bl_fold(l, cout, c.eps, c.scale, c.shift, c.st);
+    bl_affine(out, (size_t)M * cout, cout, c.scale, c.shift, add, per, relu, c.st);
     return check_launch("baseline layer");
 }
 
@@ -159,7 +186,7 @@ int tnet(const Ctx &c, const Dims &d, const Layer *L, const float *A, int lda, i
     BL_TRY(layer(c, A, lda, R, k, L[0], k, 0, 64, w.a64a, nullptr, 0, 1));
     BL_TRY(layer(c, w.a64a, 64, R, 64, L[1], 64, 0, 128, w.a128, nullptr, 0, 1));
     BL_TRY(layer(c, w.a128, 128, R, 128, L[2], 128, 0, d.G, w.big, nullptr, 0, 1));
-    hipLaunchKernelGGL(bl_rowmax_kernel, dim3(cdiv(d.G, 64), B), dim3(256), 0, c.st, w.big, N, d.G, w.pool);
+    bl_rowmax(w.big, B, N, d.G, w.pool, c.st);
     BL_TRY(layer(c, w.pool, d.G, B, d.G, L[3], d.G, 0, d.F1, w.f1, nullptr, 0, 1));
     BL_TRY(layer(c, w.f1, d.F1, B, d.F1, L[4], d.F1, 0, d.F2, w.f2, nullptr, 0, 1));
     BL_TRY(layer(c, w.f2, d.F2, B, d.F2, L[5], d.F2, 0, k * k, T, nullptr, 0, 0));
@@ -203,7 +230,7 @@ extern "C" int ampnet_pointnet_seg_fwd_f32(const float *const *layers_host, int 
     const int R = B * N, k = d.k;
     // input transform on x[:, :, :k], folded back into the 9 input channels
     BL_TRY(tnet(c, d, L + 0, x, 9, k, B, N, w, w.T3));
-    hipLaunchKernelGGL(bl_mix_kernel, dim3(cdiv(R, 256)), dim3(256), 0, c.st, x, w.T3, R, N, k, w.xin);
+    bl_mix(x, w.T3, R, N, k, w.xin, c.st);
     BL_TRY(layer(c, w.xin, 9, R, 9, L[12], 9, 0, 64, w.a64a, nullptr, 0, 1));
     BL_TRY(layer(c, w.a64a, 64, R, 64, L[13], 64, 0, 64, w.a64b, nullptr, 0, 1));
     // feature transform, local features = bmm(x, T64)
@@ -213,7 +240,7 @@ extern "C" int ampnet_pointnet_seg_fwd_f32(const float *const *layers_host, int 
     BL_TRY(layer(c, w.local, 64, R, 64, L[14], 64, 0, 64, w.a64a, nullptr, 0, 1));
     BL_TRY(layer(c, w.a64a, 64, R, 64, L[15], 64, 0, 128, w.a128, nullptr, 0, 1));
     BL_TRY(layer(c, w.a128, 128, R, 128, L[16], 128, 0, d.G, w.big, nullptr, 0, 1));
-    hipLaunchKernelGGL(bl_rowmax_kernel, dim3(cdiv(d.G, 64), B), dim3(256), 0, c.st, w.big, N, d.G, w.pool);
+    bl_rowmax(w.big, B, N, d.G, w.pool, c.st);
     // segmentation head on cat([global, local]) (pointnet.py:95): the global part is one row per window
     const int ldw = d.G + 64;
     BL_TRY(sgemm_small(0, 1, B, d.H1, d.G, w.pool, d.G, L[17].W, ldw, w.gb, d.H1, 0, c.st));
@@ -221,8 +248,7 @@ extern "C" int ampnet_pointnet_seg_fwd_f32(const float *const *layers_host, int 
     BL_TRY(layer(c, w.big, d.H1, R, d.H1, L[18], d.H1, 0, d.H2, w.h2, nullptr, 0, 1));
     BL_TRY(layer(c, w.h2, d.H2, R, d.H2, L[19], d.H2, 0, d.H3, w.h3, nullptr, 0, 1));
     BL_TRY(layer(c, w.h3, d.H3, R, d.H3, L[20], d.H3, 0, n_classes, w.zc, nullptr, 0, 0));
-    const size_t n = (size_t)R * n_classes;
-    hipLaunchKernelGGL(bl_logits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, w.zc, B, N, n_classes, logits);
+    bl_logits(w.zc, B, N, n_classes, logits, c.st);
     if (feat_T && hipMemcpyAsync(feat_T, w.T64, (size_t)B * 4096 * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
         return fail(AMPNET_E_LAUNCH, "ampnet_pointnet_seg_fwd_f32: copy of the feature transform failed");
     return check_launch("ampnet_pointnet_seg_fwd_f32");

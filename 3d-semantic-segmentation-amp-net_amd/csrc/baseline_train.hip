@@ -8,19 +8,11 @@
 //     z = A W^T + b (+ per-window addend)   ->   batch statistics (double, fixed order) + running update   ->   a = relu(bn(z))
 // and the backward walks the tape: BatchNorm/ReLU backward (two column sums + one elementwise pass), dW = dz^T A, db = sum dz,
 // dA = dz W, MaxPool1d backward as a scatter to the argmax rows, the two torch.bmm, the T-Net identity.
-#include "kernels.h"
+#include "baseline.h"
 #include "bwd_misc.h"
 
 namespace ampnet {
 namespace {
-
-struct TLayer {                // device pointers of one layer: weight, bias, BatchNorm weight / bias / running mean / running var
-    const float *W, *b, *g, *be;
-    float *rm, *rv;
-};
-struct TGrad {                 // gradients of the same (nullptr where the layer has no such parameter)
-    float *dW, *db, *dg, *dbe;
-};
 
 struct Dims {
     int k, G, F1, F2, H1, H2, H3;
@@ -217,14 +209,15 @@ __global__ __launch_bounds__(256) void bt_segsum_kernel(const float *__restrict_
     if (g == 0 && c < C) out[(size_t)b * C + c] = (float)((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]));
 }
 
-// z [B * N, C] <-> logits [B, C, N]
-__global__ void bt_logits_kernel(const float *__restrict__ z, int B, int N, int C, float *__restrict__ logits, int to_rows)
+// z [B * N, C] <-> logits [B, C, N]: TO_ROWS = 0 reads rows and writes logits, 1 the other way round
+template <int TO_ROWS> __global__ void bt_logits_kernel(const float *__restrict__ src, int B, int N, int C, float *__restrict__ dst)
 {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= (size_t)B * N * C) return;
     const int p = (int)(i % N), c = (int)((i / N) % C), b = (int)(i / N / C);
-    if (to_rows) const_cast<float *>(z)[((size_t)b * N + p) * C + c] = logits[i];
-    else logits[i] = z[((size_t)b * N + p) * C + c];
+    const size_t row = ((size_t)b * N + p) * C + c;
+    if (TO_ROWS) dst[row] = src[i];
+    else dst[i] = src[row];
 }
 
 __global__ void bt_fill_kernel(float *__restrict__ p, size_t n, float v)
@@ -251,8 +244,8 @@ __global__ void bt_running_stats_kernel(const float *__restrict__ rm, const floa
 }
 
 // nn.Dropout(p) on a [n] tensor: out = keep(i) ? a * 1 / (1 - p) : 0 with the package's counter hash (kernels.h: mix32; the oracle's keep_mask);
-// the backward is the same map on the gradient
-__global__ void bt_dropout_kernel(const float *__restrict__ a, size_t n, uint32_t base, uint32_t thr, float scale, float *__restrict__ out)
+// the backward is the same map on the gradient, in place (out == a: no __restrict__ here)
+__global__ void bt_dropout_kernel(const float *a, size_t n, uint32_t base, uint32_t thr, float scale, float *out)
 {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n) out[i] = (mix32((uint32_t)i ^ base) >= thr) ? a[i] * scale : 0.f;
@@ -294,13 +287,126 @@ __global__ void bt_log_softmax_bwd_kernel(const float *__restrict__ z, const flo
 
 inline unsigned nb(size_t n) { return (unsigned)((n + 255) / 256); }
 
-// ---- the tape ----------------------------------------------------------------------------------------------------------------------
-struct Rec {                   // one linear (+ BatchNorm + ReLU) layer on the tape
-    float *z, *a;              // [M, cout] pre-BatchNorm (with bias / addend) and activation; a == z for layers without BatchNorm
-    float *mean, *invstd;      // [cout]
-    int M, K, cout;
-};
+}  // namespace
 
+// ---- launch wrappers (baseline.h) -------------------------------------------------------------------------------------------------------
+void bt_bias(float *z, size_t n, int C, const float *bias, const float *add, int per, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_bias_kernel, dim3(nb(n)), dim3(256), 0, st, z, n, C, bias, add, per > 0 ? per : 1);
+}
+
+void bt_stats(const float *z, int M, int C, float eps, float momentum, float *mean, float *invstd, float *rm, float *rv, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_stats_kernel, dim3(cdiv(C, 64)), dim3(256), 0, st, z, M, C, eps, momentum, mean, invstd, rm, rv);
+}
+
+void bt_running_stats(const float *rm, const float *rv, int C, float eps, float *mean, float *invstd, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_running_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, rm, rv, C, eps, mean, invstd);
+}
+
+void bt_bn_act(const float *z, size_t n, int C, const float *mean, const float *invstd, const float *g, const float *be, float *a, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_bn_act_kernel, dim3(nb(n)), dim3(256), 0, st, z, n, C, mean, invstd, g, be, a);
+}
+
+void bt_bn_bwd_sums(const float *da, const float *a, const float *z, int M, int C, const float *mean, const float *invstd, float *dg, float *dbe,
+                    hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_bn_bwd_sums_kernel, dim3(cdiv(C, 64)), dim3(256), 0, st, da, a, z, M, C, mean, invstd, dg, dbe);
+}
+
+void bt_bn_bwd_apply(float *da, const float *a, const float *z, size_t n, int M, int C, const float *mean, const float *invstd, const float *gamma,
+                     const float *dg, const float *dbe, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_bn_bwd_apply_kernel, dim3(nb(n)), dim3(256), 0, st, da, a, z, n, M, C, mean, invstd, gamma, dg, dbe);
+}
+
+void bt_rowmax(const float *a, int B, int N, int C, float *out, int *arg, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_rowmax_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, st, a, N, C, out, arg);
+}
+
+void bt_pool_scatter(const float *d_pool, const int *arg, int B, int N, int C, float *d_a, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_pool_scatter_kernel, dim3(nb((size_t)B * C)), dim3(256), 0, st, d_pool, arg, B, N, C, d_a);
+}
+
+void bt_mix(const float *x, const float *T, int R, int N, int k, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_mix_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, x, T, R, N, k, out);
+}
+
+void bt_mix_bwd(const float *x, const float *d_xin, int B, int N, int k, float *dT, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_mix_bwd_kernel, dim3(B), dim3(256), 0, st, x, d_xin, N, k, dT);
+}
+
+void bt_segsum(const float *dz, int B, int N, int C, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_segsum_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, st, dz, N, C, out);
+}
+
+void bt_logits(const float *z, int B, int N, int C, float *logits, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_logits_kernel<0>, dim3(nb((size_t)B * N * C)), dim3(256), 0, st, z, B, N, C, logits);
+}
+
+void bt_logits_to_rows(const float *logits, int B, int N, int C, float *z, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_logits_kernel<1>, dim3(nb((size_t)B * N * C)), dim3(256), 0, st, logits, B, N, C, z);
+}
+
+void bt_fill(float *p, size_t n, float v, hipStream_t st) { hipLaunchKernelGGL(bt_fill_kernel, dim3(nb(n)), dim3(256), 0, st, p, n, v); }
+
+void bt_add(float *y, const float *x, size_t n, hipStream_t st) { hipLaunchKernelGGL(bt_add_kernel, dim3(nb(n)), dim3(256), 0, st, y, x, n); }
+
+void bt_dropout(const float *a, size_t n, uint32_t seed, float p, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_dropout_kernel, dim3(nb(n)), dim3(256), 0, st, a, n, drop_base(seed, 0), drop_threshold(p), 1.0f / (1.0f - p), out);
+}
+
+void bt_log_softmax(const float *z, int B, int C, float *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_log_softmax_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, z, B, C, out);
+}
+
+void bt_log_softmax_bwd(const float *z, const float *d_out, int B, int C, float *dz, hipStream_t st)
+{
+    hipLaunchKernelGGL(bt_log_softmax_bwd_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, z, d_out, B, C, dz);
+}
+
+int fwd_layer(const TLayer &l, Rec &r, bool running, const float *A, int lda, int ldw, int w0, const float *add, int per, hipStream_t st)
+{
+    BT_TRY(sgemm_small(0, 1, r.M, r.cout, r.K, A, lda, l.W + w0, ldw, r.z, r.cout, 0, st));
+    const size_t n = (size_t)r.M * r.cout;
+    if (l.b || add) bt_bias(r.z, n, r.cout, l.b, add, per, st);
+    if (l.g) {
+        if (running) bt_running_stats(l.rm, l.rv, r.cout, 1e-5f, r.mean, r.invstd, st);
+        else bt_stats(r.z, r.M, r.cout, 1e-5f, 0.1f, r.mean, r.invstd, l.rm, l.rv, st);
+        bt_bn_act(r.z, n, r.cout, r.mean, r.invstd, l.g, l.be, r.a, st);
+    }
+    return check_launch("baseline train layer forward");
+}
+
+int bwd_layer(const TLayer &l, const TGrad &g, const Rec &r, float *dgs, float *dbs, float *da, const float *A, int lda, int ldw, int w0, float *dA,
+              int ld_dA, int accumulate, hipStream_t st)
+{
+    const size_t n = (size_t)r.M * r.cout;
+    if (l.g) {
+        float *dg = g.dg ? g.dg : dgs, *dbe = g.dbe ? g.dbe : dbs;
+        bt_bn_bwd_sums(da, r.a, r.z, r.M, r.cout, r.mean, r.invstd, dg, dbe, st);
+        bt_bn_bwd_apply(da, r.a, r.z, n, r.M, r.cout, r.mean, r.invstd, l.g, dg, dbe, st);
+    }
+    if (g.dW) BT_TRY(sgemm_small(1, 0, r.cout, r.K, r.M, da, r.cout, A, lda, g.dW + w0, ldw, 0, st));
+    if (g.db) BT_TRY(colsum(da, r.M, r.cout, g.db, st));
+    if (dA) BT_TRY(sgemm_small(0, 0, r.M, r.K, r.cout, da, r.cout, l.W + w0, ldw, dA, ld_dA, accumulate, st));
+    return check_launch("baseline train layer backward");
+}
+
+namespace {
+
+// ---- the tape ----------------------------------------------------------------------------------------------------------------------
 struct Ws {
     Rec L[AMPNET_POINTNET_LAYERS];
     float *xin, *pool_i, *pool_f, *pool_c, *T3, *T64, *local, *gb;
@@ -376,35 +482,13 @@ struct Ctx {
 // forward of layer i: z = A[:, :K] W[:, w0 : w0 + K]^T + b (+ add[row / per]); statistics; activation
 int fwd_layer(const Ctx &c, int i, const float *A, int lda, int ldw, int w0, const float *add, int per)
 {
-    const TLayer &l = c.L[i];
-    Rec &r = c.w->L[i];
-    BT_TRY(sgemm_small(0, 1, r.M, r.cout, r.K, A, lda, l.W + w0, ldw, r.z, r.cout, 0, c.st));
-    const size_t n = (size_t)r.M * r.cout;
-    if (l.b || add) hipLaunchKernelGGL(bt_bias_kernel, dim3(nb(n)), dim3(256), 0, c.st, r.z, n, r.cout, l.b, add, per > 0 ? per : 1);
-    if (l.g) {
-        if (c.running) hipLaunchKernelGGL(bt_running_stats_kernel, dim3(cdiv(r.cout, 256)), dim3(256), 0, c.st, l.rm, l.rv, r.cout, 1e-5f, r.mean, r.invstd);
-        else hipLaunchKernelGGL(bt_stats_kernel, dim3(cdiv(r.cout, 64)), dim3(256), 0, c.st, r.z, r.M, r.cout, 1e-5f, 0.1f, r.mean, r.invstd, l.rm, l.rv);
-        hipLaunchKernelGGL(bt_bn_act_kernel, dim3(nb(n)), dim3(256), 0, c.st, r.z, n, r.cout, r.mean, r.invstd, l.g, l.be, r.a);
-    }
-    return check_launch("baseline train layer forward");
+    return ampnet::fwd_layer(c.L[i], c.w->L[i], c.running, A, lda, ldw, w0, add, per, c.st);
 }
 
 // backward of layer i: `da` [M, cout] (overwritten with dz) -> parameter gradients; dA [M, K] (=, or += when accumulate) unless nullptr
 int bwd_layer(const Ctx &c, int i, float *da, const float *A, int lda, int ldw, int w0, float *dA, int ld_dA, int accumulate)
 {
-    const TLayer &l = c.L[i];
-    const TGrad &g = c.G[i];
-    const Rec &r = c.w->L[i];
-    const size_t n = (size_t)r.M * r.cout;
-    if (l.g) {
-        float *dg = g.dg ? g.dg : c.w->dgs, *dbe = g.dbe ? g.dbe : c.w->dbs;
-        hipLaunchKernelGGL(bt_bn_bwd_sums_kernel, dim3(cdiv(r.cout, 64)), dim3(256), 0, c.st, da, r.a, r.z, r.M, r.cout, r.mean, r.invstd, dg, dbe);
-        hipLaunchKernelGGL(bt_bn_bwd_apply_kernel, dim3(nb(n)), dim3(256), 0, c.st, da, r.a, r.z, n, r.M, r.cout, r.mean, r.invstd, l.g, dg, dbe);
-    }
-    if (g.dW) BT_TRY(sgemm_small(1, 0, r.cout, r.K, r.M, da, r.cout, A, lda, g.dW + w0, ldw, 0, c.st));
-    if (g.db) BT_TRY(colsum(da, r.M, r.cout, g.db, c.st));
-    if (dA) BT_TRY(sgemm_small(0, 0, r.M, r.K, r.cout, da, r.cout, l.W + w0, ldw, dA, ld_dA, accumulate, c.st));
-    return check_launch("baseline train layer backward");
+    return ampnet::bwd_layer(c.L[i], c.G[i], c.w->L[i], c.w->dgs, c.w->dbs, da, A, lda, ldw, w0, dA, ld_dA, accumulate, c.st);
 }
 
 int tnet_fwd(const Ctx &c, const Dims &d, int base, const float *A, int lda, int k, int B, int N, float *pool, int *arg, float *T)
@@ -413,7 +497,7 @@ int tnet_fwd(const Ctx &c, const Dims &d, int base, const float *A, int lda, int
     BT_TRY(fwd_layer(c, base + 0, A, lda, k, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, base + 1, w.L[base + 0].a, 64, 64, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, base + 2, w.L[base + 1].a, 128, 128, 0, nullptr, 0));
-    hipLaunchKernelGGL(bt_rowmax_kernel, dim3(cdiv(d.G, 64), B), dim3(256), 0, c.st, w.L[base + 2].a, N, d.G, pool, arg);
+    bt_rowmax(w.L[base + 2].a, B, N, d.G, pool, arg, c.st);
     BT_TRY(fwd_layer(c, base + 3, pool, d.G, d.G, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, base + 4, w.L[base + 3].a, d.F1, d.F1, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, base + 5, w.L[base + 4].a, d.F2, d.F2, 0, nullptr, 0));
@@ -431,8 +515,8 @@ int tnet_bwd(const Ctx &c, const Dims &d, int base, float *dT, const float *A, i
     BT_TRY(bwd_layer(c, base + 5, dT, w.L[base + 4].a, d.F2, d.F2, 0, w.dA, d.F2, 0));                 // fc_3 (no BatchNorm): dT is dz
     BT_TRY(bwd_layer(c, base + 4, w.dA, w.L[base + 3].a, d.F1, d.F1, 0, w.dB, d.F1, 0));
     BT_TRY(bwd_layer(c, base + 3, w.dB, pool, d.G, d.G, 0, w.d_pool, d.G, 0));
-    hipLaunchKernelGGL(bt_fill_kernel, dim3(nb(R * d.G)), dim3(256), 0, c.st, w.dA, R * d.G, 0.f);
-    hipLaunchKernelGGL(bt_pool_scatter_kernel, dim3(nb((size_t)B * d.G)), dim3(256), 0, c.st, w.d_pool, arg, B, N, d.G, w.dA);
+    bt_fill(w.dA, R * d.G, 0.f, c.st);
+    bt_pool_scatter(w.d_pool, arg, B, N, d.G, w.dA, c.st);
     BT_TRY(bwd_layer(c, base + 2, w.dA, w.L[base + 1].a, 128, 128, 0, w.dB, 128, 0));
     BT_TRY(bwd_layer(c, base + 1, w.dB, w.L[base + 0].a, 64, 64, 0, w.dA, 64, 0));
     return bwd_layer(c, base + 0, w.dA, A, lda, k, 0, d_in, ld_in, 1);
@@ -460,7 +544,7 @@ int base_fwd(const Ctx &c, const Dims &d, const float *x, int B, int N)
     Ws &w = *c.w;
     const int R = B * N, k = d.k;
     BT_TRY(tnet_fwd(c, d, 0, x, 9, k, B, N, w.pool_i, w.arg_i, w.T3));
-    hipLaunchKernelGGL(bt_mix_kernel, dim3(cdiv(R, 256)), dim3(256), 0, c.st, x, w.T3, R, N, k, w.xin);
+    bt_mix(x, w.T3, R, N, k, w.xin, c.st);
     BT_TRY(fwd_layer(c, 12, w.xin, 9, 9, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, 13, w.L[12].a, 64, 64, 0, nullptr, 0));
     BT_TRY(tnet_fwd(c, d, 6, w.L[13].a, 64, 64, B, N, w.pool_f, w.arg_f, w.T64));
@@ -469,7 +553,7 @@ int base_fwd(const Ctx &c, const Dims &d, const float *x, int B, int N)
     BT_TRY(fwd_layer(c, 14, w.local, 64, 64, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, 15, w.L[14].a, 64, 64, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, 16, w.L[15].a, 128, 128, 0, nullptr, 0));
-    hipLaunchKernelGGL(bt_rowmax_kernel, dim3(cdiv(d.G, 64), B), dim3(256), 0, c.st, w.L[16].a, N, d.G, w.pool_c, w.arg_c);
+    bt_rowmax(w.L[16].a, B, N, d.G, w.pool_c, w.arg_c, c.st);
     return check_launch("baseline PointNet base forward");
 }
 
@@ -481,8 +565,8 @@ int base_bwd(const Ctx &c, const Dims &d, const float *x, int B, int N, const fl
     const int k = d.k;
     const size_t R = (size_t)B * N;
     // ---- conv_5 .. conv_3 ----
-    hipLaunchKernelGGL(bt_fill_kernel, dim3(nb(R * d.G)), dim3(256), 0, c.st, w.dA, R * d.G, 0.f);
-    hipLaunchKernelGGL(bt_pool_scatter_kernel, dim3(nb((size_t)B * d.G)), dim3(256), 0, c.st, w.d_pool, w.arg_c, B, N, d.G, w.dA);
+    bt_fill(w.dA, R * d.G, 0.f, c.st);
+    bt_pool_scatter(w.d_pool, w.arg_c, B, N, d.G, w.dA, c.st);
     BT_TRY(bwd_layer(c, 16, w.dA, w.L[15].a, 128, 128, 0, w.dB, 128, 0));
     BT_TRY(bwd_layer(c, 15, w.dB, w.L[14].a, 64, 64, 0, w.dA, 64, 0));
     BT_TRY(bwd_layer(c, 14, w.dA, w.local, 64, 64, 0, w.d_local, 64, local_accumulate));                   // (+= the head's d_local)
@@ -491,12 +575,12 @@ int base_bwd(const Ctx &c, const Dims &d, const float *x, int B, int N, const fl
         BT_TRY(sgemm_small(1, 0, 64, 64, N, w.L[13].a + (size_t)b * N * 64, 64, w.d_local + (size_t)b * N * 64, 64, w.dT64 + (size_t)b * 4096, 64, 0, c.st));
         BT_TRY(sgemm_small(0, 1, N, 64, 64, w.d_local + (size_t)b * N * 64, 64, w.T64 + (size_t)b * 4096, 64, w.d_c2 + (size_t)b * N * 64, 64, 0, c.st));
     }
-    if (d_feat_T) hipLaunchKernelGGL(bt_add_kernel, dim3(nb((size_t)B * 4096)), dim3(256), 0, c.st, w.dT64, d_feat_T, (size_t)B * 4096);
+    if (d_feat_T) bt_add(w.dT64, d_feat_T, (size_t)B * 4096, c.st);
     BT_TRY(tnet_bwd(c, d, 6, w.dT64, w.L[13].a, 64, 64, B, N, w.pool_f, w.arg_f, w.d_c2, 64));             // += into d_a_c2
     // ---- conv_2, conv_1 ----
     BT_TRY(bwd_layer(c, 13, w.d_c2, w.L[12].a, 64, 64, 0, w.dA, 64, 0));
     BT_TRY(bwd_layer(c, 12, w.dA, w.xin, 9, 9, 0, w.d_xin, 9, 0));
-    hipLaunchKernelGGL(bt_mix_bwd_kernel, dim3(B), dim3(256), 0, c.st, x, w.d_xin, N, k, w.dT3);
+    bt_mix_bwd(x, w.d_xin, B, N, k, w.dT3, c.st);
     // ---- input T-Net (its input is x: no gradient needed) ----
     return tnet_bwd(c, d, 0, w.dT3, x, 9, k, B, N, w.pool_i, w.arg_i, nullptr, 0);
 }
@@ -529,7 +613,6 @@ extern "C" int ampnet_pointnet_seg_train_fwd_f32(const float *const *layers_host
     TLayer L[AMPNET_POINTNET_LAYERS];
     BT_TRY(read_tables(layers_host, nullptr, L, nullptr));
     Ctx c{static_cast<hipStream_t>(stream), L, nullptr, &w};
-    const int R = B * N;
     BT_TRY(base_fwd(c, d, x, B, N));
     const int ldw = d.G + 64;
     BT_TRY(sgemm_small(0, 1, B, d.H1, d.G, w.pool_c, d.G, L[17].W, ldw, w.gb, d.H1, 0, c.st));
@@ -537,8 +620,7 @@ extern "C" int ampnet_pointnet_seg_train_fwd_f32(const float *const *layers_host
     BT_TRY(fwd_layer(c, 18, w.L[17].a, d.H1, d.H1, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, 19, w.L[18].a, d.H2, d.H2, 0, nullptr, 0));
     BT_TRY(fwd_layer(c, 20, w.L[19].a, d.H3, d.H3, 0, nullptr, 0));
-    const size_t n = (size_t)R * n_classes;
-    hipLaunchKernelGGL(bt_logits_kernel, dim3(nb(n)), dim3(256), 0, c.st, w.L[20].z, B, N, n_classes, logits, 0);
+    bt_logits(w.L[20].z, B, N, n_classes, logits, c.st);
     if (hipMemcpyAsync(feat_T, w.T64, (size_t)B * 4096 * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
         return fail(AMPNET_E_LAUNCH, "ampnet_pointnet_seg_train_fwd_f32: copy of the feature transform failed");
     return check_launch("ampnet_pointnet_seg_train_fwd_f32");
@@ -551,6 +633,8 @@ extern "C" int ampnet_pointnet_seg_bwd_f32(const float *const *layers_host, floa
     Dims d;
     AMPNET_REQUIRE(dims_for(variant, &d), "ampnet_pointnet_seg_bwd_f32: variant %d", variant);
     AMPNET_REQUIRE(layers_host && grads_host && x && dlogits && workspace, "ampnet_pointnet_seg_bwd_f32: null pointer");
+    AMPNET_REQUIRE(B >= 2 && N >= 1 && n_classes >= 1 && n_classes <= 64 && (long long)B * N < (1LL << 24),
+                   "ampnet_pointnet_seg_bwd_f32: bad shape B=%d N=%d classes=%d (the train forward's limits)", B, N, n_classes);
     Ws w;
     carve(d, B, N, n_classes, workspace, w);
     AMPNET_REQUIRE(workspace_bytes >= w.bytes, "ampnet_pointnet_seg_bwd_f32: workspace %zu bytes, need %zu", workspace_bytes, w.bytes);
@@ -559,15 +643,14 @@ extern "C" int ampnet_pointnet_seg_bwd_f32(const float *const *layers_host, floa
     BT_TRY(read_tables(layers_host, grads_host, L, G));
     Ctx c{static_cast<hipStream_t>(stream), L, G, &w};
     const int ldw = d.G + 64;
-    const size_t R = (size_t)B * N;
     // ---- segmentation head ----
-    hipLaunchKernelGGL(bt_logits_kernel, dim3(nb(R * n_classes)), dim3(256), 0, c.st, w.dA, B, N, n_classes, const_cast<float *>(dlogits), 1);
+    bt_logits_to_rows(dlogits, B, N, n_classes, w.dA, c.st);
     BT_TRY(bwd_layer(c, 20, w.dA, w.L[19].a, d.H3, d.H3, 0, w.dB, d.H3, 0));
     BT_TRY(bwd_layer(c, 19, w.dB, w.L[18].a, d.H2, d.H2, 0, w.dA, d.H2, 0));
     BT_TRY(bwd_layer(c, 18, w.dA, w.L[17].a, d.H1, d.H1, 0, w.dB, d.H1, 0));
     // conv_1 on cat([global, local]): local half through the generic layer, global half = one row per window
     BT_TRY(bwd_layer(c, 17, w.dB, w.local, 64, ldw, d.G, w.d_local, 64, 0));                              // dW[:, G:], db, BatchNorm; d_local
-    hipLaunchKernelGGL(bt_segsum_kernel, dim3(cdiv(d.H1, 64), B), dim3(256), 0, c.st, w.dB, N, d.H1, w.d_gb);
+    bt_segsum(w.dB, B, N, d.H1, w.d_gb, c.st);
     BT_TRY(sgemm_small(1, 0, d.H1, d.G, B, w.d_gb, d.H1, w.pool_c, d.G, G[17].dW, ldw, 0, c.st));          // dW[:, :G]
     BT_TRY(sgemm_small(0, 0, B, d.G, d.H1, w.d_gb, d.H1, L[17].W, ldw, w.d_pool, d.G, 0, c.st));           // d global feature
     BT_TRY(base_bwd(c, d, x, B, N, d_feat_T, 1));
@@ -607,11 +690,11 @@ extern "C" int ampnet_pointnet_cls_fwd_f32(const float *const *layers_host, int 
     const float *a2 = w.L[18].a;
     if (train && drop_p > 0.f) {
         const size_t n = (size_t)B * d.C2;
-        hipLaunchKernelGGL(bt_dropout_kernel, dim3(nb(n)), dim3(256), 0, c.st, a2, n, drop_base(seed, 0), drop_threshold(drop_p), 1.0f / (1.0f - drop_p), w.a_drop);
+        bt_dropout(a2, n, seed, drop_p, w.a_drop, c.st);
         a2 = w.a_drop;
     }
     BT_TRY(fwd_layer(c, 19, a2, d.C2, d.C2, 0, nullptr, 0));
-    hipLaunchKernelGGL(bt_log_softmax_kernel, dim3(cdiv(B, 64)), dim3(64), 0, c.st, w.L[19].z, B, n_classes, log_probs);
+    bt_log_softmax(w.L[19].z, B, n_classes, log_probs, c.st);
     if (hipMemcpyAsync(feat_T, w.T64, (size_t)B * 4096 * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
         return fail(AMPNET_E_LAUNCH, "ampnet_pointnet_cls_fwd_f32: copy of the feature transform failed");
     return check_launch("ampnet_pointnet_cls_fwd_f32");
@@ -624,6 +707,8 @@ extern "C" int ampnet_pointnet_cls_bwd_f32(const float *const *layers_host, floa
     Dims d;
     AMPNET_REQUIRE(dims_for(variant, &d), "ampnet_pointnet_cls_bwd_f32: variant %d", variant);
     AMPNET_REQUIRE(layers_host && grads_host && x && d_log_probs && workspace, "ampnet_pointnet_cls_bwd_f32: null pointer");
+    AMPNET_REQUIRE(B >= 2 && N >= 1 && n_classes >= 1 && n_classes <= 64 && (long long)B * N < (1LL << 24),
+                   "ampnet_pointnet_cls_bwd_f32: bad shape B=%d N=%d classes=%d (the train forward's limits)", B, N, n_classes);
     AMPNET_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "ampnet_pointnet_cls_bwd_f32: dropout p=%f", drop_p);
     Ws w;
     carve(d, B, N, n_classes, workspace, w, true);
@@ -633,12 +718,12 @@ extern "C" int ampnet_pointnet_cls_bwd_f32(const float *const *layers_host, floa
     BT_TRY(read_tables(layers_host, grads_host, L, G, AMPNET_POINTNET_CLS_LAYERS));
     Ctx c{static_cast<hipStream_t>(stream), L, G, &w};
     // log_softmax, fc_3 (its input is the dropped activation), dropout, fc_2, fc_1
-    hipLaunchKernelGGL(bt_log_softmax_bwd_kernel, dim3(cdiv(B, 64)), dim3(64), 0, c.st, w.L[19].z, d_log_probs, B, n_classes, w.dA);
+    bt_log_softmax_bwd(w.L[19].z, d_log_probs, B, n_classes, w.dA, c.st);
     const bool drop = drop_p > 0.f;
     BT_TRY(bwd_layer(c, 19, w.dA, drop ? w.a_drop : w.L[18].a, d.C2, d.C2, 0, w.dB, d.C2, 0));
     if (drop) {
         const size_t n = (size_t)B * d.C2;
-        hipLaunchKernelGGL(bt_dropout_kernel, dim3(nb(n)), dim3(256), 0, c.st, w.dB, n, drop_base(seed, 0), drop_threshold(drop_p), 1.0f / (1.0f - drop_p), w.dB);
+        bt_dropout(w.dB, n, seed, drop_p, w.dB, c.st);
     }
     BT_TRY(bwd_layer(c, 18, w.dB, w.L[17].a, d.C1, d.C1, 0, w.dA, d.C1, 0));
     BT_TRY(bwd_layer(c, 17, w.dA, w.pool_c, d.G, d.G, 0, w.d_pool, d.G, 0));

@@ -12,6 +12,7 @@
 #include "bwd_misc.h"
 #include "encoder.h"
 #include "head.h"
+#include "baseline.h"
 
 namespace ampnet {
 namespace {
@@ -977,4 +978,172 @@ extern "C" int ampnet_probe_seq_f32(const AmpnetSeqProbe *d, void *stream)
         return cls_out(d->act, d->W3, d->b3, d->B, d->C, d->out, st);
     }
     }
+}
+
+// ---- the baseline single-window PointNet's kernels (tests/test_baseline_layers_gpu.py) -----------------------------------------------------
+// One launch through the wrappers of baseline.h that ampnet_pointnet_seg_* / ampnet_pointnet_cls_* call themselves; ops 23 and 24 are the
+// composed layer steps fwd_layer / bwd_layer.
+namespace ampnet {
+namespace {
+const char *const BASELINE_KERNEL[] = {"bt_bias_kernel", "bt_stats_kernel", "bt_running_stats_kernel", "bt_bn_act_kernel", "bt_bn_bwd_sums_kernel",
+                                       "bt_bn_bwd_apply_kernel", "bt_rowmax_kernel", "bl_rowmax_kernel", "bt_pool_scatter_kernel", "bt_mix_kernel",
+                                       "bl_mix_kernel", "bt_mix_bwd_kernel", "bt_segsum_kernel", "bt_logits_kernel", "bt_logits_kernel", "bl_logits_kernel",
+                                       "bt_fill_kernel", "bt_add_kernel", "bt_dropout_kernel", "bt_log_softmax_kernel", "bt_log_softmax_bwd_kernel",
+                                       "bl_fold_kernel", "bl_affine_kernel", "bt_fwd_layer", "bt_bwd_layer"};
+constexpr int64_t BASELINE_LIM = 1 << 24;
+inline bool bp_has(const void *p, int64_t have, int64_t want) { return p && have >= want; }
+inline bool bp_opt(const void *p, int64_t have, int64_t want) { return !p || have >= want; }
+inline bool bp_dim(int64_t a) { return a >= 1 && a < BASELINE_LIM; }
+}  // namespace
+}  // namespace ampnet
+
+extern "C" int ampnet_probe_baseline_f32(const AmpnetBaselineProbe *d, void *stream)
+{
+    using namespace ampnet;
+    AMPNET_REQUIRE(d, "probe_baseline: null descriptor");
+    AMPNET_REQUIRE(d->op >= 0 && d->op <= 24, "probe_baseline: op %d not built", d->op);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int op = d->op;
+    const int64_t B = d->B, N = d->N, M = d->M, C = d->C, K = d->K, k = d->k, per = d->per;
+    const bool rows_op = (op <= 5 && op != 2) || op >= 22;                               // [M, C]
+    const bool win_op = op == 6 || op == 7 || op == 8 || (op >= 11 && op <= 15);         // [B, N, C] (11: [B, N, 9])
+    // ---- every shape and extent first: nothing is launched, copied or recorded before all of them hold ----
+    if (rows_op) AMPNET_REQUIRE(bp_dim(M) && bp_dim(C) && M * C < BASELINE_LIM, "probe_baseline: M %d C %d", d->M, d->C);
+    if (op == 2 || op == 21) AMPNET_REQUIRE(bp_dim(C), "probe_baseline: C %d", d->C);
+    if (win_op) AMPNET_REQUIRE(B >= 1 && B <= 65535 && bp_dim(N) && B * N * 9 < BASELINE_LIM, "probe_baseline: B %d N %d", d->B, d->N);
+    if (win_op && op != 11) AMPNET_REQUIRE(bp_dim(C) && B * N * C < BASELINE_LIM, "probe_baseline: B %d N %d C %d", d->B, d->N, d->C);
+    if (op == 19 || op == 20) AMPNET_REQUIRE(bp_dim(B) && C >= 1 && C <= 64, "probe_baseline: log_softmax B %d C %d (1 <= C <= 64)", d->B, d->C);
+    if (op == 9 || op == 10) AMPNET_REQUIRE(bp_dim(M) && bp_dim(N) && M * 9 < BASELINE_LIM, "probe_baseline: mix M %d N %d", d->M, d->N);
+    if (op >= 9 && op <= 11) AMPNET_REQUIRE(k == 2 || k == 3, "probe_baseline: k %d (2 or 3)", d->k);
+    if (op >= 16 && op <= 18) AMPNET_REQUIRE(bp_dim(d->n), "probe_baseline: n %lld", (long long)d->n);
+    if (op == 0 || op == 22 || op == 23) AMPNET_REQUIRE(!d->add || per >= 1, "probe_baseline: per %d with an addend", d->per);
+    const int64_t MC = M * C, BC = B * C, BNC = B * N * C;
+    const int64_t add_n = d->add && per >= 1 ? ((M - 1) / per + 1) * C : 0;
+    const bool bn = d->gamma != nullptr;
+    switch (op) {
+    case 0:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, MC) && bp_opt(d->bias, d->bias_n, C) && bp_opt(d->add, d->add_n, add_n), "probe_baseline: z / bias / add short");
+        break;
+    case 1:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, MC) && bp_has(d->mean, d->mean_n, C) && bp_has(d->invstd, d->invstd_n, C) && bp_has(d->rm, d->rm_n, C) &&
+                           bp_has(d->rv, d->rv_n, C),
+                       "probe_baseline: z / mean / invstd / rm / rv short");
+        break;
+    case 2:
+        AMPNET_REQUIRE(bp_has(d->rm, d->rm_n, C) && bp_has(d->rv, d->rv_n, C) && bp_has(d->mean, d->mean_n, C) && bp_has(d->invstd, d->invstd_n, C),
+                       "probe_baseline: rm / rv / mean / invstd short");
+        break;
+    case 3:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, MC) && bp_has(d->a, d->a_n, MC) && bp_has(d->mean, d->mean_n, C) && bp_has(d->invstd, d->invstd_n, C) &&
+                           bp_has(d->gamma, d->gamma_n, C) && bp_has(d->beta, d->beta_n, C),
+                       "probe_baseline: z / a / mean / invstd / gamma / beta short");
+        break;
+    case 4:
+    case 5:
+        AMPNET_REQUIRE(bp_has(d->da, d->da_n, MC) && bp_has(d->a, d->a_n, MC) && bp_has(d->z, d->z_n, MC) && bp_has(d->mean, d->mean_n, C) &&
+                           bp_has(d->invstd, d->invstd_n, C) && bp_has(d->dg, d->dg_n, C) && bp_has(d->dbe, d->dbe_n, C),
+                       "probe_baseline: da / a / z / mean / invstd / dg / dbe short");
+        AMPNET_REQUIRE(op == 4 || bp_has(d->gamma, d->gamma_n, C), "probe_baseline: gamma short");
+        break;
+    case 6:
+    case 7:
+        AMPNET_REQUIRE(bp_has(d->a, d->a_n, BNC) && bp_has(d->out, d->out_n, BC) && (op == 7 || bp_has(d->arg, d->arg_n, BC)), "probe_baseline: a / out / arg short");
+        break;
+    case 8: {
+        AMPNET_REQUIRE(bp_has(d->x, d->x_n, BC) && bp_has(d->arg, d->arg_n, BC) && bp_has(d->a, d->a_n, BNC), "probe_baseline: x / arg / a short");
+        std::vector<int32_t> h((size_t)BC);
+        if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(h.data(), d->arg, (size_t)BC * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(AMPNET_E_LAUNCH, "probe_baseline: copy of arg failed");
+        for (int64_t i = 0; i < BC; ++i) AMPNET_REQUIRE(h[i] >= 0 && h[i] < N, "probe_baseline: arg[%lld] = %d outside [0, %d)", (long long)i, h[i], d->N);
+        break;
+    }
+    case 9:
+    case 10:
+        AMPNET_REQUIRE(bp_has(d->x, d->x_n, M * 9) && bp_has(d->T, d->T_n, ((M - 1) / N + 1) * k * k) && bp_has(d->out, d->out_n, M * 9), "probe_baseline: x / T / out short");
+        break;
+    case 11:
+        AMPNET_REQUIRE(bp_has(d->x, d->x_n, B * N * 9) && bp_has(d->da, d->da_n, B * N * 9) && bp_has(d->out, d->out_n, B * k * k), "probe_baseline: x / da / out short");
+        break;
+    case 12:
+        AMPNET_REQUIRE(bp_has(d->da, d->da_n, BNC) && bp_has(d->out, d->out_n, BC), "probe_baseline: da / out short");
+        break;
+    case 13:
+    case 14:
+    case 15:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, BNC) && bp_has(d->out, d->out_n, BNC), "probe_baseline: z / out short");
+        break;
+    case 16:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, d->n), "probe_baseline: z short");
+        break;
+    case 17:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, d->n) && bp_has(d->x, d->x_n, d->n), "probe_baseline: z / x short");
+        break;
+    case 18:
+        AMPNET_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "probe_baseline: drop_p %f", (double)d->drop_p);
+        AMPNET_REQUIRE(bp_has(d->a, d->a_n, d->n) && bp_has(d->out, d->out_n, d->n), "probe_baseline: a / out short");
+        break;
+    case 19:
+    case 20:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, BC) && bp_has(d->out, d->out_n, BC) && (op == 19 || bp_has(d->da, d->da_n, BC)), "probe_baseline: z / out / da short");
+        break;
+    case 21:
+        AMPNET_REQUIRE(bp_opt(d->bias, d->bias_n, C) && bp_has(d->scale, d->scale_n, C) && bp_has(d->shift, d->shift_n, C), "probe_baseline: bias / scale / shift short");
+        AMPNET_REQUIRE(!bn || (d->gamma_n >= C && bp_has(d->beta, d->beta_n, C) && bp_has(d->rm, d->rm_n, C) && bp_has(d->rv, d->rv_n, C)),
+                       "probe_baseline: gamma / beta / rm / rv short");
+        break;
+    case 22:
+        AMPNET_REQUIRE(bp_has(d->z, d->z_n, MC) && bp_has(d->scale, d->scale_n, C) && bp_has(d->shift, d->shift_n, C) && bp_opt(d->add, d->add_n, add_n),
+                       "probe_baseline: z / scale / shift / add short");
+        break;
+    default: {   // 23, 24
+        AMPNET_REQUIRE(K >= 1 && K <= 4096 && d->w0 >= 0 && d->lda >= K && d->ldw >= d->w0 + K && M * d->lda < BASELINE_LIM && C * d->ldw < BASELINE_LIM,
+                       "probe_baseline: K %d lda %d ldw %d w0 %d", d->K, d->lda, d->ldw, d->w0);
+        const int64_t A_n = (M - 1) * d->lda + K, W_n = (C - 1) * d->ldw + d->w0 + K;
+        AMPNET_REQUIRE(bp_has(d->A, d->A_n, A_n) && bp_has(d->W, d->W_n, W_n) && bp_has(d->z, d->z_n, MC), "probe_baseline: A / W / z short");
+        AMPNET_REQUIRE(!bn || (d->gamma_n >= C && bp_has(d->a, d->a_n, MC) && bp_has(d->mean, d->mean_n, C) && bp_has(d->invstd, d->invstd_n, C)),
+                       "probe_baseline: gamma / a / mean / invstd short");
+        if (op == 23) {
+            AMPNET_REQUIRE(bp_opt(d->bias, d->bias_n, C) && bp_opt(d->add, d->add_n, add_n), "probe_baseline: bias / add short");
+            AMPNET_REQUIRE(!bn || (bp_has(d->beta, d->beta_n, C) && bp_has(d->rm, d->rm_n, C) && bp_has(d->rv, d->rv_n, C)), "probe_baseline: beta / rm / rv short");
+            break;
+        }
+        AMPNET_REQUIRE(bp_has(d->da, d->da_n, MC) && bp_has(d->dW, d->dW_n, W_n) && bp_opt(d->db, d->db_n, C), "probe_baseline: da / dW / db short");
+        AMPNET_REQUIRE(!bn || (bp_has(d->dg, d->dg_n, C) && bp_has(d->dbe, d->dbe_n, C)), "probe_baseline: dg / dbe short");
+        AMPNET_REQUIRE(!d->dA || (d->ld_dA >= K && M * d->ld_dA < BASELINE_LIM && d->dA_n >= (M - 1) * d->ld_dA + K), "probe_baseline: dA short (ld_dA %d)", d->ld_dA);
+    }
+    }
+    // ---- the launch ----
+    if (op >= 23) {
+        Rec r{d->z, bn ? d->a : d->z, d->mean, d->invstd, d->M, d->K, d->C};
+        if (op == 23) return fwd_layer(TLayer{d->W, d->bias, d->gamma, d->beta, d->rm, d->rv}, r, d->train == 0, d->A, d->lda, d->ldw, d->w0, d->add, d->per, st);
+        return bwd_layer(TLayer{d->W, nullptr, d->gamma, nullptr, nullptr, nullptr}, TGrad{d->dW, d->db, bn ? d->dg : nullptr, bn ? d->dbe : nullptr}, r, nullptr,
+                         nullptr, d->da, d->A, d->lda, d->ldw, d->w0, d->dA, d->ld_dA, d->accumulate, st);
+    }
+    ProfScope prof(BASELINE_KERNEL[op], 0.0, 0.0, st);
+    switch (op) {
+    case 0: bt_bias(d->z, (size_t)MC, d->C, d->bias, d->add, d->per, st); break;
+    case 1: bt_stats(d->z, d->M, d->C, d->eps, d->momentum, d->mean, d->invstd, d->rm, d->rv, st); break;
+    case 2: bt_running_stats(d->rm, d->rv, d->C, d->eps, d->mean, d->invstd, st); break;
+    case 3: bt_bn_act(d->z, (size_t)MC, d->C, d->mean, d->invstd, d->gamma, d->beta, d->a, st); break;
+    case 4: bt_bn_bwd_sums(d->da, d->a, d->z, d->M, d->C, d->mean, d->invstd, d->dg, d->dbe, st); break;
+    case 5: bt_bn_bwd_apply(d->da, d->a, d->z, (size_t)MC, d->M, d->C, d->mean, d->invstd, d->gamma, d->dg, d->dbe, st); break;
+    case 6: bt_rowmax(d->a, d->B, d->N, d->C, d->out, d->arg, st); break;
+    case 7: bl_rowmax(d->a, d->B, d->N, d->C, d->out, st); break;
+    case 8: bt_pool_scatter(d->x, d->arg, d->B, d->N, d->C, d->a, st); break;
+    case 9: bt_mix(d->x, d->T, d->M, d->N, d->k, d->out, st); break;
+    case 10: bl_mix(d->x, d->T, d->M, d->N, d->k, d->out, st); break;
+    case 11: bt_mix_bwd(d->x, d->da, d->B, d->N, d->k, d->out, st); break;
+    case 12: bt_segsum(d->da, d->B, d->N, d->C, d->out, st); break;
+    case 13: bt_logits(d->z, d->B, d->N, d->C, d->out, st); break;
+    case 14: bt_logits_to_rows(d->out, d->B, d->N, d->C, d->z, st); break;
+    case 15: bl_logits(d->z, d->B, d->N, d->C, d->out, st); break;
+    case 16: bt_fill(d->z, (size_t)d->n, d->value, st); break;
+    case 17: bt_add(d->z, d->x, (size_t)d->n, st); break;
+    case 18: bt_dropout(d->a, (size_t)d->n, d->drop_seed, d->drop_p, d->out, st); break;
+    case 19: bt_log_softmax(d->z, d->B, d->C, d->out, st); break;
+    case 20: bt_log_softmax_bwd(d->z, d->da, d->B, d->C, d->out, st); break;
+    case 21: bl_fold(BlLayer{nullptr, d->bias, d->gamma, d->beta, d->rm, d->rv}, d->C, d->eps, d->scale, d->shift, st); break;
+    default: bl_affine(d->z, (size_t)MC, d->C, d->scale, d->shift, d->add, d->per, d->relu, st); break;
+    }
+    return check_launch(BASELINE_KERNEL[op]);
 }

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AMPNET_ABI_VERSION 17
+#define AMPNET_ABI_VERSION 18
 
 enum {
     AMPNET_OK = 0,
@@ -1168,6 +1168,63 @@ typedef struct AmpnetSeqProbe {
     float *Y; int64_t Y_n;
 } AmpnetSeqProbe;
 
+/* One launch of a kernel of the baseline single-window PointNet (csrc/baseline.hip: bl_*, the eval forward; csrc/baseline_train.hip: bt_*,
+ * the train forward and backward) through the launch wrappers the product entry points call (csrc/baseline.h), by `op` (ABI 18;
+ * csrc/layer_probe.hip, tests/test_baseline_layers_gpu.py).  Rows are [M, C]; windowed tensors are [B, N, C]:
+ *    0 bt_bias            (z [M, C] in place, bias [C] or NULL, add [ceil(M / per), C] or NULL, per)
+ *    1 bt_stats           (z [M, C], eps, momentum -> mean, invstd [C]; rm, rv [C] in place)
+ *    2 bt_running_stats   (rm, rv [C], eps -> mean, invstd [C])
+ *    3 bt_bn_act          (z [M, C], mean, invstd, gamma, beta [C] -> a [M, C])
+ *    4 bt_bn_bwd_sums     (da, a, z [M, C], mean, invstd [C] -> dg, dbe [C])
+ *    5 bt_bn_bwd_apply    (da [M, C] in place, a, z, mean, invstd, gamma, dg, dbe)
+ *    6 bt_rowmax          (a [B, N, C] -> out [B, C], arg [B, C])            7 bl_rowmax (a -> out)
+ *    8 bt_pool_scatter    (x = d_pool [B, C], arg [B, C] (each in [0, N), checked) -> a = d_a [B, N, C], which the caller zeroed)
+ *    9 bt_mix, 10 bl_mix  (x [M, 9], T [ceil(M / N), k, k] -> out [M, 9]; M rows in windows of N; k in {2, 3})
+ *   11 bt_mix_bwd         (x, da = d_xin [B * N, 9] -> out = dT [B, k, k])
+ *   12 bt_segsum          (da = dz [B, N, C] -> out [B, C])
+ *   13 bt_logits          (z [B * N, C] -> out [B, C, N])      14 bt_logits_to_rows (out -> z)      15 bl_logits (as 13)
+ *   16 bt_fill            (z [n] = value)                       17 bt_add (z [n] += x [n])
+ *   18 bt_dropout         (a [n], drop_p, drop_seed -> out [n]; out == a allowed)
+ *   19 bt_log_softmax     (z [B, C] -> out [B, C]; C <= 64)     20 bt_log_softmax_bwd (z, da = d_out [B, C] -> out = dz)
+ *   21 bl_fold            (bias, gamma (with beta, rm, rv) [C], either NULL, eps -> scale, shift [C])
+ *   22 bl_affine          (z [M, C] in place, scale, shift [C], add [ceil(M / per), C] or NULL, per, relu)
+ *   23 fwd_layer          (A [M, lda], W [C, ldw] read at column w0, K; bias / gamma, beta, rm, rv / add, per as above; train = 0 takes
+ *                          the running statistics -> z [M, C], a [M, C] (gamma given, else z alone is written), mean, invstd [C])
+ *   24 bwd_layer          (da [M, C] in place, a, z, mean, invstd, gamma or NULL, W, A as above -> dW [C, ldw] at column w0, db or NULL,
+ *                          dg, dbe (required with gamma), dA [M, ld_dA] or NULL, = or += by `accumulate`)
+ * Every dimension an op reads is >= 1 and every product of them < 2^24; B <= 65535.  Every extent is checked on the host before the launch
+ * (AMPNET_E_ARG, nothing written); single-kernel ops are recorded under the kernel's name for ampnet_profile_read.                        */
+typedef struct AmpnetBaselineProbe {
+    int32_t op, B, N, M, C, K, k, per, relu, train, accumulate, lda, ldw, w0, ld_dA, pad0;
+    float eps, momentum, value, drop_p; uint32_t drop_seed, pad1;
+    int64_t n;
+    float *z; int64_t z_n;
+    float *a; int64_t a_n;
+    float *da; int64_t da_n;
+    float *mean; int64_t mean_n;
+    float *invstd; int64_t invstd_n;
+    const float *gamma; int64_t gamma_n;
+    const float *beta; int64_t beta_n;
+    float *rm; int64_t rm_n;
+    float *rv; int64_t rv_n;
+    const float *bias; int64_t bias_n;
+    const float *add; int64_t add_n;
+    float *dg; int64_t dg_n;
+    float *dbe; int64_t dbe_n;
+    float *out; int64_t out_n;
+    int32_t *arg; int64_t arg_n;
+    const float *x; int64_t x_n;
+    const float *T; int64_t T_n;
+    const float *W; int64_t W_n;
+    float *dW; int64_t dW_n;
+    float *db; int64_t db_n;
+    float *dA; int64_t dA_n;
+    const float *A; int64_t A_n;
+    float *scale; int64_t scale_n;
+    float *shift; int64_t shift_n;
+} AmpnetBaselineProbe;
+
+int ampnet_probe_baseline_f32(const AmpnetBaselineProbe *d, void *stream);
 int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream);
 int ampnet_probe_pw_bwd_f32(const AmpnetPwBwdProbe *d, void *stream);
 int ampnet_probe_pooled_bwd_f32(const AmpnetPooledBwdProbe *d, void *stream);

@@ -28,6 +28,16 @@ SHAPES = [
     (False, False, 1, 1, 1),
     (True, False, 40, 9, 5),
     (False, True, 100, 65, 1030),     # more than one pass of 16 x 8 chunks
+    # the shapes only the baseline single-window PointNet uses (csrc/baseline.hip, csrc/baseline_train.hip)
+    (False, True, 70, 64, 2),         # the input T-Net's conv_1, K below one 4-wide chunk, A rows wider than K when padded / unaligned
+    (False, True, 70, 64, 3),
+    (True, False, 64, 2, 70),         # its dW: ldc of 2 or 3
+    (True, False, 64, 3, 70),
+    (False, True, 2, 4096, 128),      # the T-Nets' fc_3 on B rows
+    (False, True, 3, 4, 128),
+    (False, True, 3, 9, 256),
+    (False, False, 70, 9, 64),        # dA of conv_1 on the 9 mixed channels
+    (True, False, 64, 9, 70),         # and its dW
 ]
 
 

@@ -723,6 +723,16 @@ def _seg_head_args(prefix, x, params, eps, extra):
     return M, ld, cin, hidden, n_classes, (ctypes.c_void_p * 8)(*[t.data_ptr() for t in params])
 
 
+def _seg_head_grads(prefix, params, grads):
+    """The six gradient tensors (dW1, db1, dgamma, dbeta, dW2, db2) checked against the parameters -> the pointer table of the C ABI."""
+    want = [tuple(params[q].shape) for q in (0, 1, 1, 1, 6, 7)]
+    if len(grads) != 6 or any(not torch.is_tensor(t) or tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                              for t, w in zip(grads, want)):
+        raise AmpnetError(f"{prefix}: grads must be six contiguous float32 GPU tensors (dW1, db1, dgamma, dbeta, dW2, db2) of "
+                          f"shapes {want}, got {[tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in grads]}")
+    return (ctypes.c_void_p * 6)(*[t.data_ptr() for t in grads])
+
+
 def seg_head_forward_f32(x, params, eps, logp, preds, workspace):
     """The fused per-point classifier in eval mode (include/ampnet_hip.h: ampnet_seg_head_forward_f32).  x [M, ld >= cin] float32 rows,
     params the 8 tensors W1 [hidden, cin], b1, gamma, beta, running_mean, running_var, W2 [n_classes, hidden], b2, eps BatchNorm's;
@@ -749,14 +759,67 @@ def seg_head_backward_f32(x, params, eps, dlogp, dx, grads, workspace):
         raise AmpnetError(f"seg_head_backward: dlogp {tuple(dlogp.shape)} must be [M, n_classes] = {[M, C]}")
     if dx is not None and tuple(dx.shape) != (M, cin):
         raise AmpnetError(f"seg_head_backward: dx {tuple(dx.shape)} must be [M, cin] = {[M, cin]} or None")
-    want = [tuple(params[q].shape) for q in (0, 1, 1, 1, 6, 7)]
-    if len(grads) != 6 or any(not torch.is_tensor(t) or tuple(t.shape) != w or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
-                              for t, w in zip(grads, want)):
-        raise AmpnetError(f"seg_head_backward: grads must be six contiguous float32 GPU tensors (dW1, db1, dgamma, dbeta, dW2, db2) of "
-                          f"shapes {want}, got {[tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in grads]}")
-    gtable = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in grads])
+    gtable = _seg_head_grads("seg_head_backward", params, grads)
     ws, ws_bytes = _workspace_args("seg_head_backward", workspace)
     with torch.cuda.device(x.device):
         rc = lib().ampnet_seg_head_backward_f32(ptr(x), ld, ctypes.c_longlong(M), cin, hidden, C, table, ctypes.c_float(float(eps)), ptr(dlogp),
                                                 ptr(dx), gtable, ws, ws_bytes, stream_ptr(x.device))
     check(rc, "ampnet_seg_head_backward_f32")
+
+
+# ---- the segmentation head in train mode: batch-statistics bn1 and dropout ------------------------------------------------------------
+def seg_head_train_forward_workspace_bytes(cin, hidden, n_classes, M):
+    """Device bytes seg_head_train_forward_f32 needs (the fold and the statistics' partial rows); fewer than 2 or more than 2^24 rows are
+    AmpnetErrors, as is a shape outside the eval head's limits."""
+    return _seg_head_bytes("ampnet_seg_head_train_forward_workspace_bytes", cin, hidden, n_classes, M)
+
+
+def seg_head_train_backward_workspace_bytes(cin, hidden, n_classes, M):
+    """Device bytes seg_head_train_backward_f32 needs for M rows (include/ampnet_hip.h)."""
+    return _seg_head_bytes("ampnet_seg_head_train_backward_workspace_bytes", cin, hidden, n_classes, M)
+
+
+def _seg_head_saved(prefix, hidden, save_mean, save_invstd):
+    if any(tuple(t.shape) != (hidden,) for t in (save_mean, save_invstd)):
+        raise AmpnetError(f"{prefix}: save_mean {tuple(save_mean.shape)} and save_invstd {tuple(save_invstd.shape)} must be [hidden] = "
+                          f"{[hidden]}")
+
+
+def seg_head_train_forward_f32(x, params, eps, momentum, drop_p, seed, logp, save_mean, save_invstd, workspace):
+    """The fused per-point classifier in train mode (include/ampnet_hip.h: ampnet_seg_head_train_forward_f32): bn1 on the statistics of
+    the M rows, dropout with probability drop_p in [0, 1) and the mask `seed` selects.  x, params, eps as in seg_head_forward_f32;
+    running_mean and running_var (params[4], params[5]) are UPDATED IN PLACE with `momentum` (a float in [0, 1]); logp [M, n_classes],
+    save_mean / save_invstd [hidden]: written; workspace: seg_head_train_forward_workspace_bytes(...) GPU bytes."""
+    M, ld, cin, hidden, C, table = _seg_head_args("seg_head_train_forward", x, params, eps,
+                                                  [("logp", logp, _F32, 2, True)] + _saved_rows(save_mean, save_invstd))
+    mom = _momentum("seg_head_train_forward", momentum)
+    if tuple(logp.shape) != (M, C):
+        raise AmpnetError(f"seg_head_train_forward: logp {tuple(logp.shape)} must be [M, n_classes] = {[M, C]}")
+    _seg_head_saved("seg_head_train_forward", hidden, save_mean, save_invstd)
+    ws, ws_bytes = _workspace_args("seg_head_train_forward", workspace)
+    with torch.cuda.device(x.device):
+        rc = lib().ampnet_seg_head_train_forward_f32(ptr(x), ld, ctypes.c_longlong(M), cin, hidden, C, table, ctypes.c_float(float(eps)), mom,
+                                                     ctypes.c_float(float(drop_p)), ctypes.c_uint32(int(seed) & 0xFFFFFFFF), ptr(logp),
+                                                     ptr(save_mean), ptr(save_invstd), ws, ws_bytes, stream_ptr(x.device))
+    check(rc, "ampnet_seg_head_train_forward_f32")
+
+
+def seg_head_train_backward_f32(x, params, eps, drop_p, seed, save_mean, save_invstd, dlogp, dx, grads, workspace):
+    """The backward of seg_head_train_forward_f32 through the batch statistics and the dropout mask.  x, params, eps, drop_p, seed: the
+    forward's (running_mean, running_var and b1 are not read); save_mean / save_invstd: what the forward wrote; dlogp, dx, grads as in
+    seg_head_backward_f32 (db1 is written as zeros); workspace: seg_head_train_backward_workspace_bytes(...) GPU bytes."""
+    M, ld, cin, hidden, C, table = _seg_head_args("seg_head_train_backward", x, params, eps,
+                                                  _saved_rows(save_mean, save_invstd) + [("dlogp", dlogp, _F32, 2, True),
+                                                                                         ("dx", dx, _F32, 2, False)])
+    if tuple(dlogp.shape) != (M, C):
+        raise AmpnetError(f"seg_head_train_backward: dlogp {tuple(dlogp.shape)} must be [M, n_classes] = {[M, C]}")
+    if dx is not None and tuple(dx.shape) != (M, cin):
+        raise AmpnetError(f"seg_head_train_backward: dx {tuple(dx.shape)} must be [M, cin] = {[M, cin]} or None")
+    _seg_head_saved("seg_head_train_backward", hidden, save_mean, save_invstd)
+    gtable = _seg_head_grads("seg_head_train_backward", params, grads)
+    ws, ws_bytes = _workspace_args("seg_head_train_backward", workspace)
+    with torch.cuda.device(x.device):
+        rc = lib().ampnet_seg_head_train_backward_f32(ptr(x), ld, ctypes.c_longlong(M), cin, hidden, C, table, ctypes.c_float(float(eps)),
+                                                      ctypes.c_float(float(drop_p)), ctypes.c_uint32(int(seed) & 0xFFFFFFFF), ptr(save_mean),
+                                                      ptr(save_invstd), ptr(dlogp), ptr(dx), gtable, ws, ws_bytes, stream_ptr(x.device))
+    check(rc, "ampnet_seg_head_train_backward_f32")

@@ -432,6 +432,9 @@ def seg_head_params(tensors):
             for q, t in enumerate(tensors)]
 
 
+_SEG_GRAD_SLOTS = (0, 1, 2, 3, 6, 7)                                # of seg_head_tensors: the tensors that have a gradient, in the C ABI's order
+
+
 class _SegHeadFn(torch.autograd.Function):
     """The fused per-point classifier with bn1's running statistics frozen (pointnet2_utils.PointNetSegHead with grad=True).  rows [M, cin];
     tensors: seg_head_tensors.  The forward is the eval forward, unchanged, and keeps no activation: the backward kernel recomputes them
@@ -452,15 +455,63 @@ class _SegHeadFn(torch.autograd.Function):
         params = seg_head_params(tensors)
         need_grad = ctx.needs_input_grad
         dx = torch.empty((rows.shape[0], params[0].shape[1]), dtype=torch.float32, device=rows.device) if need_grad[2] else None
-        slots = (0, 1, 2, 3, 6, 7)                                 # the tensors that have a gradient, in the C ABI's order
-        grads = [torch.empty_like(params[q]) for q in slots]
+        grads = [torch.empty_like(params[q]) for q in _SEG_GRAD_SLOTS]
         need = _lib.seg_head_backward_workspace_bytes(params[0].shape[1], params[0].shape[0], params[6].shape[0], rows.shape[0])
         _lib.seg_head_backward_f32(rows, params, ctx.eps, dlogp.contiguous().float(), dx, grads, _ws(need, rows.device))
         ret = [None] * 8
-        for g, q in zip(grads, slots):
+        for g, q in zip(grads, _SEG_GRAD_SLOTS):
             if need_grad[3 + q]:
                 ret[q] = g.reshape(tensors[q].shape)
         return (None, None, dx) + tuple(ret)
+
+
+def seg_head_train_forward(rows, params, eps, momentum, p, seed):
+    """ampnet_seg_head_train_forward_f32 on the eight tensors of seg_head_params, running_mean and running_var (entries 4 and 5) being the
+    buffers themselves: updated in place -> (logp [M, classes], save_mean, save_invstd)."""
+    hidden, cin = params[0].shape
+    logp = torch.empty((rows.shape[0], params[6].shape[0]), dtype=torch.float32, device=rows.device)
+    save_mean, save_invstd = (torch.empty(hidden, dtype=torch.float32, device=rows.device) for _ in range(2))
+    need = _lib.seg_head_train_forward_workspace_bytes(cin, hidden, params[6].shape[0], rows.shape[0])
+    _lib.seg_head_train_forward_f32(rows, params, eps, momentum, p, seed, logp, save_mean, save_invstd, _ws(need, rows.device))
+    return logp, save_mean, save_invstd
+
+
+class _SegHeadTrainFn(torch.autograd.Function):
+    """The fused per-point classifier in TRAIN mode (pointnet2_utils.PointNetSegHead with grad=True and batch_stats=True, in train mode):
+    bn1 on the batch's statistics, dropout with probability p and the mask `seed` selects.  stats: the module's (running_mean, running_var)
+    buffers, updated in place by the forward and NOT saved; tensors: conv1 weight and bias, bn1 weight and bias, conv2 weight and bias.
+    Saved for the backward: the rows, save_mean, save_invstd and the six tensors, with p and the seed -- no activation and no mask: the
+    backward kernels recompute both (csrc/seg_head_train_bwd.hip).  Exact fp32 whatever the matrix precision is."""
+
+    @staticmethod
+    def forward(ctx, eps, momentum, p, seed, stats, rows, *tensors):
+        params = seg_head_params(list(tensors[:4]) + list(stats) + list(tensors[4:]))
+        params[4], params[5] = stats                               # (the buffers themselves: float32 and contiguous by construction)
+        logp, save_mean, save_invstd = seg_head_train_forward(rows, params, eps, momentum, p, seed)
+        ctx.save_for_backward(rows, save_mean, save_invstd, *tensors)
+        ctx.eps, ctx.p, ctx.seed = eps, p, seed
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        rows, save_mean, save_invstd, *tensors = ctx.saved_tensors
+        params = seg_head_params(list(tensors[:4]) + [save_mean, save_invstd] + list(tensors[4:]))      # (slots 4 and 5 are not read)
+        need_grad = ctx.needs_input_grad
+        dx = torch.empty((rows.shape[0], params[0].shape[1]), dtype=torch.float32, device=rows.device) if need_grad[5] else None
+        grads = [torch.empty_like(params[q]) for q in _SEG_GRAD_SLOTS]
+        need = _lib.seg_head_train_backward_workspace_bytes(params[0].shape[1], params[0].shape[0], params[6].shape[0], rows.shape[0])
+        _lib.seg_head_train_backward_f32(rows, params, ctx.eps, ctx.p, ctx.seed, save_mean, save_invstd, dlogp.contiguous().float(), dx, grads,
+                                         _ws(need, rows.device))
+        ret = [g.reshape(t.shape) if need_grad[6 + q] else None for q, (g, t) in enumerate(zip(grads, tensors))]      # (db1 is zeros)
+        return (None, None, None, None, None, dx) + tuple(ret)
+
+
+def seg_head_train_apply(module, rows, momentum, p, seed):
+    """Grad-mode, train-mode forward of a PointNetSegHead on rows [M, in_channel] -> log-probabilities [M, num_classes]: batch statistics,
+    bn1's running statistics updated in place, dropout, a graph to the rows and to conv1, bn1 (weight and bias) and conv2 (conv1's bias
+    gets zeros: it has no effect on a batch-normalised output)."""
+    t = seg_head_tensors(module)
+    return _SegHeadTrainFn.apply(module.bn1.eps, momentum, p, seed, (t[4], t[5]), rows, *(t[q] for q in _SEG_GRAD_SLOTS))
 
 
 def seg_head_apply(module, rows, fold_ws):

@@ -13,13 +13,18 @@
 //     The rows past M are never stored.
 //   * The plan is mlp_plan_build's with the tiles and the staging laid out here: the waves per workgroup are halved (4, 2, 1) until the
 //     tiles fit beside W2, and W1 is staged behind W2 when it still fits (else read through L2 by dwordx4, as fp1 of pointnet_2 reads its).
+//   * Train mode (seg_head_train.hip) launches the same kernel as its last step, on a fold formed from the batch statistics and with
+//     DROP = true: eval and train share the hot kernel, as fp_forward_kernel serves both feature-propagation forwards.
 #include "seg_head.h"
 
 namespace ampnet {
 
-__global__ __launch_bounds__(256) void seg_head_forward_kernel(MlpPlan p, SegPlan s, const float *__restrict__ x, int ld, long long M,
-                                                              const float *__restrict__ fold, int n_tiles, float *__restrict__ logp,
-                                                              long long *__restrict__ preds)
+// DROP = false is eval mode and does nothing with `drop`; DROP = true (train mode, seg_head_train.hip) drops and rescales conv1's
+// activations in tile B before conv2 reads them.
+template <bool DROP>
+__global__ __launch_bounds__(256) void seg_head_forward_kernel(MlpPlan p, SegPlan s, SegDrop drop, const float *__restrict__ x, int ld,
+                                                              long long M, const float *__restrict__ fold, int n_tiles,
+                                                              float *__restrict__ logp, long long *__restrict__ preds)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -36,6 +41,10 @@ __global__ __launch_bounds__(256) void seg_head_forward_kernel(MlpPlan p, SegPla
         wave_lds_sync();
         mlp_dispatch<K_QUADS>(p, 0, 32, m.s_w, m.tile_a, p.ld_a, fold, MlpToTile{m.tile_b, p.ld_b}, nullptr, lane);
         wave_lds_sync();
+        if (DROP) {
+            seg_dropout(m.tile_b, p.ld_b, s.hidden, row0, rows, drop, lane);
+            wave_lds_sync();
+        }
         seg_logits(m.tile_b, p.ld_b, s_w2, s.hidden, s.b2, C, m.tile_a, p.ld_a, lane);       // (conv1's reads of tile A are done)
         wave_lds_sync();
         if (lane < 32) {
@@ -81,6 +90,10 @@ int seg_shape(const char *what, int cin, int hidden, int n_classes, long long M,
     sh.off_dw2 = off;
     off += (size_t)32 * hidden;
     sh.floats = off;
+    sh.off_coef = align_up(off, 64);
+    sh.train_floats = sh.off_coef + align_up((size_t)2 * hidden, 64);
+    sh.off_stats = sh.fold_floats;
+    sh.train_fwd_floats = sh.off_stats + align_up((size_t)sh.grid * 3 * hidden, 64);
     return AMPNET_OK;
 }
 
@@ -92,6 +105,38 @@ int seg_check_entry(const char *what, const float *x, int ld, int cin, int hidde
     AMPNET_TRY(seg_shape(what, cin, hidden, n_classes, M, sh));
     AMPNET_REQUIRE(ld >= cin, "%s: ld=%d is less than cin=%d", what, ld, cin);
     return AMPNET_OK;
+}
+
+int seg_forward_plan(const char *what, int cin, int hidden, const float *const *params_host, float eps, MlpPlan &p, MlpFold &f, size_t &lds)
+{
+    if (!mlp_plan_build(what, cin, 32, params_host, &hidden, &eps, 1, p, f)) return AMPNET_E_ARG;
+    // the tiles and the staging of this kernel: tile A also carries z (32 columns), tile B conv1's activations; W2, then W1 if it fits
+    p.ld_a = (p.kp[0] > 32 ? p.kp[0] : 32) + 1;
+    p.ld_b = hidden + 1;
+    const size_t tile_bytes = (size_t)32 * (p.ld_a + p.ld_b) * sizeof(float), w2_floats = (size_t)32 * (hidden + 1),
+                 w1_floats = (size_t)hidden * (p.kp[0] + 1);
+    p.nw = 4;
+    while (p.nw > 1 && p.nw * tile_bytes + w2_floats * sizeof(float) > (size_t)MLP_LDS_BYTES) p.nw /= 2;
+    lds = p.nw * tile_bytes + w2_floats * sizeof(float);
+    AMPNET_REQUIRE(lds <= (size_t)MLP_LDS_BYTES, "%s: a wave's tiles and W2 (%zu bytes) exceed the LDS", what, lds);
+    p.w_off[0] = lds + w1_floats * sizeof(float) <= (size_t)MLP_LDS_BYTES ? (int)w2_floats : -1;
+    if (p.w_off[0] >= 0) lds += w1_floats * sizeof(float);
+    return AMPNET_OK;
+}
+
+int seg_forward_launch(const char *what, const MlpPlan &p, size_t lds, const SegPlan &s, const SegDrop *drop, const float *x, int ld, long long M,
+                       const float *fold, int n_tiles, float *logp, long long *preds, hipStream_t st)
+{
+    static bool attr_set[2] = {false, false};
+    const dim3 grid(mlp_grid(n_tiles, p.nw)), block(64 * p.nw);
+    if (drop) {
+        AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(seg_head_forward_kernel<true>), attr_set[1]));
+        hipLaunchKernelGGL(seg_head_forward_kernel<true>, grid, block, lds, st, p, s, *drop, x, ld, M, fold, n_tiles, logp, preds);
+    } else {
+        AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(seg_head_forward_kernel<false>), attr_set[0]));
+        hipLaunchKernelGGL(seg_head_forward_kernel<false>, grid, block, lds, st, p, s, SegDrop{}, x, ld, M, fold, n_tiles, logp, preds);
+    }
+    return check_launch("seg_head_forward_kernel");
 }
 
 }  // namespace ampnet
@@ -116,24 +161,10 @@ extern "C" int ampnet_seg_head_forward_f32(const float *x, int ld, long long M, 
     AMPNET_TRY(sa_check_workspace(what, workspace, workspace_bytes, sh.fold_floats * sizeof(float)));
     MlpPlan p;
     MlpFold f;
-    if (!mlp_plan_build(what, cin, 32, params_host, &hidden, &eps, 1, p, f)) return AMPNET_E_ARG;
-    // the tiles and the staging of this kernel: tile A also carries z (32 columns), tile B conv1's activations; W2, then W1 if it fits
-    p.ld_a = (p.kp[0] > 32 ? p.kp[0] : 32) + 1;
-    p.ld_b = hidden + 1;
-    const size_t tile_bytes = (size_t)32 * (p.ld_a + p.ld_b) * sizeof(float), w2_floats = (size_t)32 * (hidden + 1),
-                 w1_floats = (size_t)hidden * (p.kp[0] + 1);
-    p.nw = 4;
-    while (p.nw > 1 && p.nw * tile_bytes + w2_floats * sizeof(float) > (size_t)MLP_LDS_BYTES) p.nw /= 2;
-    size_t lds = p.nw * tile_bytes + w2_floats * sizeof(float);
-    AMPNET_REQUIRE(lds <= (size_t)MLP_LDS_BYTES, "%s: a wave's tiles and W2 (%zu bytes) exceed the LDS", what, lds);
-    p.w_off[0] = lds + w1_floats * sizeof(float) <= (size_t)MLP_LDS_BYTES ? (int)w2_floats : -1;
-    if (p.w_off[0] >= 0) lds += w1_floats * sizeof(float);
+    size_t lds;
+    AMPNET_TRY(seg_forward_plan(what, cin, hidden, params_host, eps, p, f, lds));
     const SegPlan s = {n_classes, hidden, 0, params_host[6], params_host[7]};
-    static bool attr_set = false;
-    AMPNET_TRY(mlp_allow_full_lds(what, reinterpret_cast<const void *>(seg_head_forward_kernel), attr_set));
     float *fold = static_cast<float *>(workspace);
     AMPNET_TRY(mlp_fold_launch(p, f, fold, st));
-    hipLaunchKernelGGL(seg_head_forward_kernel, dim3(mlp_grid(sh.n_tiles, p.nw)), dim3(64 * p.nw), lds, st, p, s, x, ld, M, fold, sh.n_tiles, logp,
-                       preds);
-    return check_launch("seg_head_forward_kernel");
+    return seg_forward_launch(what, p, lds, s, nullptr, x, ld, M, fold, sh.n_tiles, logp, preds, st);
 }

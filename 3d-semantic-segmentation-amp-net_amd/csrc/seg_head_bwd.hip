@@ -26,14 +26,6 @@
 
 namespace ampnet {
 
-struct SegBwdPlan {
-    int off_h, off_d, off_g, off_w2;      // float offsets of the tiles in LDS (X is at 0); D and G have the row stride 33
-    int ld_x, ld_h, ldxs0;
-    float *xs0, *dz1, *hs, *dz2, *parts, *parts2;
-};
-
-constexpr int SEG_LD_D = 33;
-
 __global__ __launch_bounds__(64) void seg_head_backward_kernel(MlpPlan p, SegPlan s, SegBwdPlan b, const float *__restrict__ x, int ld, long long M,
                                                               const float *__restrict__ fold, const float *__restrict__ dlogp, int n_tiles,
                                                               float *__restrict__ dx)
@@ -119,6 +111,19 @@ __global__ __launch_bounds__(256) void seg_db2_kernel(const float *__restrict__ 
     if (!lane) db2[c] = v;
 }
 
+int seg_weight_grads_launch(const char *what, const SegShape &sh, float *ws, int cin, int hidden, int n_classes, long long M,
+                            float *const *grads_host, hipStream_t st)
+{
+    float *wpart = ws + sh.lay.off_wpart, *dw2 = ws + sh.off_dw2;
+    AMPNET_TRY(fpb_wgrad_launch(ws + sh.lay.off_dz[0], hidden, ws + sh.lay.off_xs[0], cin, sh.ldxs0, M, sh.chunk_rows, sh.chunks, wpart,
+                                grads_host[0], st));
+    AMPNET_TRY(fpb_wgrad_launch(ws + sh.off_dz2, 32, ws + sh.off_hs, hidden, hidden, M, sh.chunk_rows, sh.chunks, wpart, dw2, st));
+    hipError_t e = hipMemcpyAsync(grads_host[4], dw2, (size_t)n_classes * hidden * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "%s: hipMemcpyAsync(dW2): %s", what, hipGetErrorString(e));
+    hipLaunchKernelGGL(seg_db2_kernel, dim3(cdiv(n_classes, 4)), dim3(256), 0, st, ws + sh.off_parts2, sh.grid, n_classes, grads_host[5]);
+    return check_launch("seg_db2_kernel");
+}
+
 }  // namespace ampnet
 
 extern "C" size_t ampnet_seg_head_backward_workspace_bytes(int cin, int hidden, int n_classes, long long M)
@@ -147,23 +152,9 @@ extern "C" int ampnet_seg_head_backward_f32(const float *x, int ld, long long M,
     if (!mlp_plan_build(what, cin, 32, params_host, &hidden, &eps, 1, p, f)) return AMPNET_E_ARG;
     mlp_plan_unstaged(p);
     float *ws = static_cast<float *>(workspace);
-    SegBwdPlan b = {};
-    b.ld_x = p.kp[0] + 1;
-    b.ld_h = hidden + 1;
-    b.off_h = 32 * b.ld_x;
-    b.off_d = b.off_h + 32 * b.ld_h;
-    b.off_g = b.off_d + 32 * SEG_LD_D;
-    b.off_w2 = b.off_g + 32 * SEG_LD_D;
-    const size_t lds = (size_t)(b.off_w2 + 32 * (hidden + 1)) * sizeof(float);
+    SegBwdPlan b;
+    const size_t lds = seg_bwd_plan(p, sh, ws, b);
     AMPNET_REQUIRE(lds <= (size_t)MLP_LDS_BYTES, "%s: a wave's tiles (%zu bytes) exceed the LDS", what, lds);
-    b.ldxs0 = sh.ldxs0;
-    b.parts = ws + sh.lay.off_parts;
-    b.xs0 = ws + sh.lay.off_xs[0];
-    b.dz1 = ws + sh.lay.off_dz[0];
-    b.hs = ws + sh.off_hs;
-    b.dz2 = ws + sh.off_dz2;
-    b.parts2 = ws + sh.off_parts2;
-    float *wpart = ws + sh.lay.off_wpart, *dw2 = ws + sh.off_dw2;
     const SegPlan s = {n_classes, hidden, 0, params_host[6], params_host[7]};
     FpBwdFin g = {};
     g.dbias[0] = grads_host[1];
@@ -174,11 +165,6 @@ extern "C" int ampnet_seg_head_backward_f32(const float *x, int ld, long long M,
     AMPNET_TRY(mlp_fold_launch(p, f, ws, st));
     hipLaunchKernelGGL(seg_head_backward_kernel, dim3(sh.grid), dim3(64), lds, st, p, s, b, x, ld, M, ws, dlogp, sh.n_tiles, dx);
     AMPNET_TRY(check_launch("seg_head_backward_kernel"));
-    AMPNET_TRY(fpb_wgrad_launch(b.dz1, hidden, b.xs0, cin, sh.ldxs0, M, sh.chunk_rows, sh.chunks, wpart, grads_host[0], st));
-    AMPNET_TRY(fpb_wgrad_launch(b.dz2, 32, b.hs, hidden, hidden, M, sh.chunk_rows, sh.chunks, wpart, dw2, st));
-    hipError_t e = hipMemcpyAsync(grads_host[4], dw2, (size_t)n_classes * hidden * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "%s: hipMemcpyAsync(dW2): %s", what, hipGetErrorString(e));
-    hipLaunchKernelGGL(seg_db2_kernel, dim3(cdiv(n_classes, 4)), dim3(256), 0, st, b.parts2, sh.grid, n_classes, grads_host[5]);
-    AMPNET_TRY(check_launch("seg_db2_kernel"));
+    AMPNET_TRY(seg_weight_grads_launch(what, sh, ws, cin, hidden, n_classes, M, grads_host, st));
     return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, hidden, st);
 }

@@ -49,7 +49,8 @@ branch by branch through the kernels above.  It serves models defined inside the
 
 PointNetSegHead is the per-point classifier behind the backbone (conv1, bn1, ReLU, drop1, conv2, log_softmax): one fused kernel in eval
 mode (ampnet_seg_head_forward_f32), with grad=True differentiable through ampnet_seg_head_backward_f32 (its docstring;
-pointnetAtt.pointnet_2_seg puts it behind pointnet_2's six blocks).  Its train-mode bn1, dropout, bf16 and a fused loss are not built.
+pointnetAtt.pointnet_2_seg puts it behind pointnet_2's six blocks); batch_stats=True adds train mode -- bn1 on batch statistics and a real
+dropout (ampnet_seg_head_train_forward_f32, ampnet_seg_head_train_backward_f32).  Its bf16 and a fused loss are not built.
 Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block, a `precision`
 keyword for PointNetSetAbstractionMsg (its one-launch forward is fp32 only), bf16 in a backward, a train-mode or a group_all forward.
 
@@ -520,7 +521,7 @@ class PointNetFeaturePropagation(_EvalForwardPrecision, nn.Module):
 
 
 _SEG_EVAL_ONLY = ("the HIP segmentation head is built for eval mode (bn1 on its running statistics, dropout the identity): call .eval() "
-                  "first")
+                  "first, or build the head with batch_stats=True")
 
 
 class PointNetSegHead(nn.Module):
@@ -531,15 +532,22 @@ class PointNetSegHead(nn.Module):
     nn.Conv1d(hidden, num_classes, 1), `drop1` has no state: a strict state_dict exchange with a torch head built that way works in both
     directions.  forward(points [B, in_channel, N]) -> log-probabilities [B, N, num_classes]; predict(points) -> the classes, int64 [B, N]
     (the lowest class among equal logits).
-    Eval mode only: bn1 normalises with its running statistics and dropout is the identity; .train() followed by a call raises.
+    batch_stats=False (default): eval mode only -- bn1 normalises with its running statistics and dropout is the identity; .train()
+    followed by a call raises.  batch_stats=True: train mode is accepted and is the layer torch trains (ampnet_seg_head_train_forward_f32):
+    bn1 normalises with the statistics of the call's B * N rows and updates running_mean / running_var (with bn1.momentum, a float) and
+    num_batches_tracked once per forward, graph or not; drop1 drops with p = drop1.p (p >= 1 raises) and the package's counter hash.  The
+    mask of a call comes from `seed` and `_step` (next_seed(): seed + 0x632BE5AB * _step, _step advancing by one per train-mode call): two
+    heads with equal seed and _step draw equal masks, consecutive calls different ones, and setting `seed` reproduces a run.  predict() is
+    an eval operation and raises in train mode; eval mode is the same whatever batch_stats is.
     grad=True: with grad mode on and an input or a parameter that requires grad, the result carries a graph to the points and to conv1,
-    bn1's weight and bias and conv2 (ampnet_seg_head_backward_f32 through autograd._SegHeadFn; running_mean and running_var are constants).
+    bn1's weight and bias and conv2 (ampnet_seg_head_backward_f32 through autograd._SegHeadFn; running_mean and running_var are constants;
+    in train mode ampnet_seg_head_train_backward_f32 through autograd._SegHeadTrainFn, back through the batch statistics and the mask).
     grad=False (default): no graph, ever.
     Limits: 1 <= in_channel <= 256, hidden a multiple of 32 in [32, 256], 2 <= num_classes <= 32.  The head is exact fp32 and has no
-    `precision` keyword.  Not built: train-mode bn1 (batch statistics), dropout, bf16, a fused loss (F.nll_loss on the [B * N,
-    num_classes] log-probabilities is a small operation)."""
+    `precision` keyword.  Not built: bf16, a fused loss (F.nll_loss on the [B * N, num_classes] log-probabilities is a small operation),
+    momentum=None (the cumulative average), dropout in eval mode."""
 
-    def __init__(self, in_channel, hidden, num_classes, dropout=0.5, device='cuda', grad=False):
+    def __init__(self, in_channel, hidden, num_classes, dropout=0.5, device='cuda', grad=False, batch_stats=False):
         super().__init__()
         in_channel, hidden, num_classes = int(in_channel), int(hidden), int(num_classes)
         if not (1 <= in_channel <= _lib.SEG_HEAD_MAX_CIN and 32 <= hidden <= _lib.SEG_HEAD_MAX_HIDDEN and hidden % 32 == 0
@@ -548,18 +556,28 @@ class PointNetSegHead(nn.Module):
                                       f"of 32 in [32, {_lib.SEG_HEAD_MAX_HIDDEN}] and 2 <= num_classes <= {_lib.SEG_HEAD_MAX_CLASSES}, got "
                                       f"in_channel={in_channel} hidden={hidden} num_classes={num_classes}")
         self.grad = bool(grad)
+        self.batch_stats = bool(batch_stats)
         self.in_channel, self.hidden, self.num_classes = in_channel, hidden, num_classes
         self.conv1 = _Conv(in_channel, hidden, (1,), device)
         self.bn1 = _BN2d(hidden, device)
-        self.drop1 = nn.Dropout(dropout)                            # (a holder as well: eval mode, the identity)
+        self.drop1 = nn.Dropout(dropout)                            # (a holder as well: its p is read in train mode, nothing else)
         self.conv2 = _Conv(hidden, num_classes, (1,), device)
         self._ws = None
+        self._step = 0
+        self.seed = 0x6A09E667
+
+    def next_seed(self):
+        """The dropout seed of this call; train mode advances the step (the convention of pointnetAtt.SegmentationWithGRU)."""
+        seed = (self.seed + 0x632BE5AB * self._step) & 0xFFFFFFFF
+        if self.training:
+            self._step += 1
+        return seed
 
     def _wants_grad(self, points):
         return self.grad and torch.is_grad_enabled() and (points.requires_grad or any(p.requires_grad for p in self.parameters()))
 
     def _check_input(self, points):
-        if self.training:
+        if self.training and not self.batch_stats:
             raise NotImplementedError(_SEG_EVAL_ONLY)
         _lib.require_gpu(points, "points")
         if points.dim() != 3 or points.shape[1] != self.in_channel:
@@ -576,6 +594,8 @@ class PointNetSegHead(nn.Module):
     def predict(self, points):
         """points [B, in_channel, N] -> the class of every point, int64 [B, N]: the kernel's own arg-max of the logits, the lowest class
         among equal ones (what utils.get_metrics.confusion_device takes).  Never a graph."""
+        if self.training and self.batch_stats:                       # (without batch_stats: _check_input's refusal, as before)
+            raise NotImplementedError("PointNetSegHead.predict is an eval operation: call .eval() first")
         self._check_input(points)
         with torch.no_grad():
             return self._forward_rows(points.detach().float().transpose(1, 2).contiguous(), want_preds=True)[1]
@@ -583,11 +603,13 @@ class PointNetSegHead(nn.Module):
     def _forward_rows(self, rows, want_preds=False):
         """The head on point-major rows [B, N, in_channel], float32 contiguous GPU -> [B, N, num_classes]; want_preds: (that, int64
         [B, N]) without a graph."""
-        if self.training:
-            raise NotImplementedError(_SEG_EVAL_ONLY)
         from ... import autograd
         B, N, _ = rows.shape
         flat = rows.reshape(B * N, self.in_channel)
+        if self.training:
+            if want_preds:
+                raise NotImplementedError("PointNetSegHead.predict is an eval operation: call .eval() first")
+            return self._train_rows(flat).reshape(B, N, self.num_classes)
         ws = _workspace(self, _lib.seg_head_forward_workspace_bytes(self.in_channel, self.hidden, self.num_classes, B * N), rows.device)
         if not want_preds and self._wants_grad(rows):
             return autograd.seg_head_apply(self, flat, ws).reshape(B, N, self.num_classes)
@@ -596,3 +618,29 @@ class PointNetSegHead(nn.Module):
         _lib.seg_head_forward_f32(flat.detach(), autograd.seg_head_params(autograd.seg_head_tensors(self)), self.bn1.eps, logp, preds, ws)
         logp = logp.reshape(B, N, self.num_classes)
         return (logp, preds.reshape(B, N)) if want_preds else logp
+
+    def _train_rows(self, flat):
+        """_forward_rows in train mode (batch_stats=True) on the flat rows [B * N, in_channel]: batch statistics, bn1's buffers updated in
+        place, dropout from next_seed(), a graph when one is wanted."""
+        if not self.batch_stats:
+            raise NotImplementedError(_SEG_EVAL_ONLY)
+        p = float(self.drop1.p)
+        if not 0.0 <= p < 1.0:
+            raise NotImplementedError(f"the HIP segmentation head drops with 0 <= p < 1, got drop1.p={self.drop1.p}")
+        if self.bn1.momentum is None:
+            raise NotImplementedError("train-mode segmentation head takes one float momentum for bn1, got None (momentum=None, the cumulative "
+                                      "average, is not built)")
+        momentum = float(self.bn1.momentum)
+        from ... import autograd
+        seed = self.next_seed()
+        if self._wants_grad(flat):
+            logp = autograd.seg_head_train_apply(self, flat, momentum, p, seed)
+        else:
+            with torch.no_grad():
+                t = autograd.seg_head_tensors(self)
+                params = autograd.seg_head_params(t)
+                params[4], params[5] = t[4], t[5]                   # the buffers themselves: the forward updates them in place
+                logp, _, _ = autograd.seg_head_train_forward(flat.detach(), params, self.bn1.eps, momentum, p, seed)
+        with torch.no_grad():
+            self.bn1.num_batches_tracked += 1
+        return logp

@@ -532,14 +532,23 @@ class pointnet_2_seg(pointnet_2):
     The four flags are pointnet_2's, with the same rules; the head runs with grad = decoder_grad, so with decoder_grad=True
     F.nll_loss(log_probs.reshape(-1, num_classes), target.reshape(-1)).backward() reaches conv2, bn1's weight and bias, conv1 and the
     decoder (with encoder_grad=True: the whole backbone).  .train(mode) with the batch-statistics flags moves the backbone as in
-    pointnet_2 and KEEPS THE HEAD IN EVAL MODE: bn1 always normalises with its running statistics, which are never updated, and drop1 is
-    always the identity.  Not built: train-mode bn1, dropout, bf16 (the model has no `precision` keyword and refuses set_precision('bf16'))
-    and a fused loss."""
+    pointnet_2 and, without head_batch_stats, KEEPS THE HEAD IN EVAL MODE: bn1 then always normalises with its running statistics, which are
+    never updated, and drop1 is always the identity.
+
+    head_batch_stats=True (needs decoder_batch_stats=True, else ValueError) trains the head as torch trains it: the head is built with
+    batch_stats=True and .train(mode) moves it with the decoder, so in train mode bn1 normalises with the statistics of the batch, updates
+    its running statistics and drop1 drops (PointNetSegHead; the mask follows the head's `seed`).  With all five flags the model trains
+    from scratch; .eval() afterwards is the eval forward on the trained state, bit for bit what a default pointnet_2_seg loaded with that
+    state_dict gives.  Not built: bf16 (the model has no `precision` keyword and refuses set_precision('bf16')), a fused loss,
+    momentum=None, dropout in eval mode, train mode for group_all set abstraction."""
 
     def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False,
-                 encoder_batch_stats=False):
+                 encoder_batch_stats=False, head_batch_stats=False):
         super().__init__(num_classes, device, decoder_grad, encoder_grad, decoder_batch_stats, encoder_batch_stats)
-        head = PointNetSegHead(128, 128, num_classes, device=device, grad=self.decoder_grad)
+        self.head_batch_stats = bool(head_batch_stats)
+        if self.head_batch_stats and not self.decoder_batch_stats:
+            raise ValueError("pointnet_2_seg: head_batch_stats=True needs decoder_batch_stats=True (the head trains with the decoder)")
+        head = PointNetSegHead(128, 128, num_classes, device=device, grad=self.decoder_grad, batch_stats=self.head_batch_stats)
         # the reference's flat names; the head itself is not a registered child (its keys would carry a prefix)
         self.conv1, self.bn1, self.drop1, self.conv2 = head.conv1, head.bn1, head.drop1, head.conv2
         self.__dict__["_head"] = head.eval()
@@ -549,7 +558,7 @@ class pointnet_2_seg(pointnet_2):
 
     def train(self, mode=True):
         super().train(mode)
-        self._head.train(False)                                      # (bn1 and drop1 with it: they are the head's own children)
+        self._head.train(bool(mode) and self.head_batch_stats)       # (bn1 and drop1 with it: they are the head's own children)
         return self
 
     def forward(self, xyz):

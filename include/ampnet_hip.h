@@ -690,8 +690,8 @@ int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int n, int ld, 
  * AMPNET_SEG_HEAD_MAX_CIN, hidden a multiple of 32 in [32, AMPNET_SEG_HEAD_MAX_HIDDEN], 2 <= n_classes <= AMPNET_SEG_HEAD_MAX_CLASSES (one
  * MFMA column tile), 1 <= M <= AMPNET_SEG_HEAD_MAX_ROWS (a wave's tile counter stays inside an int).  Exact fp32 MFMA
  * (v_mfma_f32_32x32x2_f32) whatever the matrix precision is.
- * NOT BUILT: train-mode bn1 (batch statistics), dropout (drop1 is the identity of eval mode), bf16, a fused loss (nll_loss on [M][C] is a
- * small operation of the caller's).                                                                                                  */
+ * NOT BUILT: bf16, a fused loss (nll_loss on [M][C] is a small operation of the caller's).  Train-mode bn1 and dropout are the
+ * _train_ entry points below; these two stay eval mode (drop1 the identity).                                                        */
 #define AMPNET_SEG_HEAD_MAX_CIN 256
 #define AMPNET_SEG_HEAD_MAX_HIDDEN 256
 #define AMPNET_SEG_HEAD_MAX_CLASSES 32
@@ -703,6 +703,51 @@ size_t ampnet_seg_head_backward_workspace_bytes(int cin, int hidden, int n_class
 int ampnet_seg_head_backward_f32(const float *x, int ld, long long M, int cin, int hidden, int n_classes, const float *const *params_host,
                                  float eps, const float *dlogp, float *dx, float *const *grads_host, void *workspace, size_t workspace_bytes,
                                  void *stream);
+
+/* ---- the segmentation head in TRAIN mode: bn1 on batch statistics, drop1 a real dropout (new within ABI 18) ---------------------------
+ * Forward.  The arguments of ampnet_seg_head_forward_f32 without preds (predict is an eval operation), and:
+ *   params_host           the 8 pointers as before; running_mean and running_var (slots 4, 5) are READ AND WRITTEN
+ *   momentum              a float in [0, 1] (anything else, NaN included, is refused)
+ *   drop_p, seed          dropout of conv1's activations: 0 <= drop_p < 1 (anything else, NaN included, is refused); seed selects the mask
+ *   save_mean, save_invstd   [hidden] float32 out each: the batch mean of the raw accumulator (WITHOUT b1) and 1 / sqrt(var + eps).  The
+ *                         backward takes them; it never recomputes statistics.
+ *   workspace             ampnet_seg_head_train_forward_workspace_bytes(cin, hidden, n_classes, M) device bytes (0 = the shape is refused):
+ *                         the fold, then min(tiles, 1024) partial rows of 3 hidden floats
+ * Over the M rows, with a = W1 x the raw accumulator in the eval forward's contraction order, the formulas of ampnet_fp_train_forward_f32:
+ *     mu = mean_rows a      var = mean_rows (a - mu)^2 (biased)      invstd = 1 / sqrt(var + eps)      scale = gamma invstd
+ *     shift = fma(-mu, scale, beta)   (b1 cancels)      y = fma(a, scale, shift)      h = relu(y)
+ *     running_mean <- fma(m, mu + b1, (1 - m) running_mean)      running_var <- fma(m, var M / (M - 1), (1 - m) running_var)
+ *     hd[r, c] = keep(r hidden + c) ? h dscale : 0      keep(i) = mix32(i ^ drop_base(seed, 0)) >= drop_threshold(drop_p)
+ *     dscale = 1.0f / (1.0f - drop_p)      (the package's counter hash, restated in oracle/ampnet_oracle.py::keep_mask; drop_p == 0 hashes
+ *     nothing and is the identity)
+ *     z = W2 hd + b2      logp = log_softmax(z)      as in ampnet_seg_head_forward_f32
+ * The statistics are centred and merged exactly as ampnet_fp_train_forward_f32 states: per column and 32-row tile the count, mean and
+ * sum (a - tile mean)^2 of the valid rows, Chan's merge first into P = min(tiles, 1024) partial rows (row r: the tiles r, r + P, ..
+ * ascending), then over the rows (lane t of a wave the rows t, t + 64, .. ascending, then a halving tree).  The last launch is the eval
+ * forward's own kernel on the fold so formed, with the dropout applied to h in LDS between conv1 and conv2.
+ * Backward.  The arguments of ampnet_seg_head_backward_f32 with drop_p, seed, save_mean and save_invstd as the forward had them;
+ * running_mean, running_var and b1 are not read.  From g = dlogp:
+ *     dz, db2 = sum_rows dz, dW2 = dz^T hd, dh = dz W2      as in ampnet_seg_head_backward_f32 (logp and hd recomputed: the forward's bits)
+ *     dh' = keep ? dh dscale : 0      dy = dh' [y > 0]      dbeta = sum_rows dy      G = sum_rows dy a
+ *     dgamma = invstd fma(-mu, dbeta, G)      db1 = 0 (exact zeros, written)
+ *     dz1 = scale fma(-(a - mu), dgamma invstd / M, dy - dbeta / M)      dW1 = dz1^T x      dx = dz1 W1
+ * with the summation orders of ampnet_fp_train_backward_f32 and ampnet_seg_head_backward_f32.  Workspace:
+ * ampnet_seg_head_train_backward_workspace_bytes(...) device bytes: the eval backward's layout, then the two coefficients per channel.
+ * Limits and refusals (AMPNET_E_ARG on the host before any launch): those of the eval entry points, plus M < 2,
+ * M > AMPNET_SEG_HEAD_TRAIN_MAX_ROWS (the statistics carry row counts as floats, exact up to there; M hidden then fits the 32-bit dropout
+ * counter), drop_p outside [0, 1), momentum outside [0, 1], null pointers and a short workspace.  No float atomics: two calls return the
+ * same bits.  Exact fp32 MFMA whatever the matrix precision is.  Caller's stream, no host synchronisation.
+ * NOT BUILT: bf16, a fused loss, momentum = None (the cumulative average), dropout in eval mode.                                     */
+#define AMPNET_SEG_HEAD_TRAIN_MAX_ROWS (1 << 24)
+size_t ampnet_seg_head_train_forward_workspace_bytes(int cin, int hidden, int n_classes, long long M);
+int ampnet_seg_head_train_forward_f32(const float *x, int ld, long long M, int cin, int hidden, int n_classes, float *const *params_host,
+                                      float eps, float momentum, float drop_p, uint32_t seed, float *logp, float *save_mean,
+                                      float *save_invstd, void *workspace, size_t workspace_bytes, void *stream);
+size_t ampnet_seg_head_train_backward_workspace_bytes(int cin, int hidden, int n_classes, long long M);
+int ampnet_seg_head_train_backward_f32(const float *x, int ld, long long M, int cin, int hidden, int n_classes,
+                                       const float *const *params_host, float eps, float drop_p, uint32_t seed, const float *save_mean,
+                                       const float *save_invstd, const float *dlogp, float *dx, float *const *grads_host, void *workspace,
+                                       size_t workspace_bytes, void *stream);
 
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =

@@ -823,3 +823,62 @@ def seg_head_train_backward_f32(x, params, eps, drop_p, seed, save_mean, save_in
                                                       ctypes.c_float(float(drop_p)), ctypes.c_uint32(int(seed) & 0xFFFFFFFF), ptr(save_mean),
                                                       ptr(save_invstd), ptr(dlogp), ptr(dx), gtable, ws, ws_bytes, stream_ptr(x.device))
     check(rc, "ampnet_seg_head_train_backward_f32")
+
+
+# ---- the loss behind the segmentation head: masked, weighted NLL with predictions and confusion counts (csrc/seg_loss.hip) ---------------
+_F64, _I64 = torch.float64, torch.int64
+
+
+def seg_nll_forward_workspace_bytes(M):
+    """Device bytes seg_nll_forward_f32 needs for M rows (the workgroups' float64 partial rows); M outside [1, AMPNET_SEG_HEAD_MAX_ROWS] is
+    an AmpnetError."""
+    fn = lib().ampnet_seg_nll_forward_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    need = fn(ctypes.c_longlong(int(M)))
+    if not need:
+        check(-1, "ampnet_seg_nll_forward_workspace_bytes")
+    return int(need)
+
+
+def _seg_nll_args(prefix, target, class_w, C, extra):
+    """target [M] int64, class_w [C] float32 or None and the wrapper's other tensors (`extra`: _check_tensors rows) -> M."""
+    _check_tensors(prefix, [("target", target, _I64, 1, True), ("class_w", class_w, _F32, 1, False)] + extra)
+    if class_w is not None and tuple(class_w.shape) != (C,):
+        raise AmpnetError(f"{prefix}: class_w {tuple(class_w.shape)} must be [C] = {[C]} or None")
+    return int(target.shape[0])
+
+
+def seg_nll_forward_f32(logp, target, class_w, sums, loss, preds, counts, workspace):
+    """The masked, weighted NLL of logp [M, C] float32 against target [M] int64 (a target outside [0, C) -- the drivers' -1 -- is ignored) with
+    class_w [C] float32 or None (include/ampnet_hip.h: ampnet_seg_nll_forward_f32).  Written: sums [2] float64, loss [1] float32, preds [M]
+    int64 or None (the lowest arg-max), counts [C * C + 1] int64 or None (confusion_device's layout); workspace:
+    seg_nll_forward_workspace_bytes(M) GPU bytes."""
+    _check_tensors("seg_nll_forward", [("logp", logp, _F32, 2, True)])
+    M, C = (int(v) for v in logp.shape)
+    m = _seg_nll_args("seg_nll_forward", target, class_w, C, [("sums", sums, _F64, 1, True), ("loss", loss, _F32, 1, True),
+                                                              ("preds", preds, _I64, 1, False), ("counts", counts, _I64, 1, False)])
+    if m != M or tuple(sums.shape) != (2,) or tuple(loss.shape) != (1,) or (preds is not None and tuple(preds.shape) != (M,)) \
+            or (counts is not None and tuple(counts.shape) != (C * C + 1,)):
+        raise AmpnetError(f"seg_nll_forward: logp {tuple(logp.shape)} needs target [M] = {[M]}, sums [2], loss [1], preds {[M]} or None and "
+                          f"counts {[C * C + 1]} or None, got {tuple(target.shape)} {tuple(sums.shape)} {tuple(loss.shape)} "
+                          f"{None if preds is None else tuple(preds.shape)} {None if counts is None else tuple(counts.shape)}")
+    ws, ws_bytes = _workspace_args("seg_nll_forward", workspace)
+    with torch.cuda.device(logp.device):
+        rc = lib().ampnet_seg_nll_forward_f32(ptr(logp), ctypes.c_longlong(M), C, ptr(target), ptr(class_w), ptr(sums), ptr(loss), ptr(preds),
+                                              ptr(counts), ws, ws_bytes, stream_ptr(logp.device))
+    check(rc, "ampnet_seg_nll_forward_f32")
+
+
+def seg_nll_backward_f32(target, class_w, sums, grad_loss, dlogp):
+    """The backward of seg_nll_forward_f32: target, class_w, sums as the forward had / wrote them, grad_loss [1] float32 on the GPU (read
+    there: no synchronisation); dlogp [M, C] float32: every element written, it may be uninitialised."""
+    _check_tensors("seg_nll_backward", [("dlogp", dlogp, _F32, 2, True)])
+    M, C = (int(v) for v in dlogp.shape)
+    m = _seg_nll_args("seg_nll_backward", target, class_w, C, [("sums", sums, _F64, 1, True), ("grad_loss", grad_loss, _F32, 1, True)])
+    if m != M or tuple(sums.shape) != (2,) or tuple(grad_loss.shape) != (1,):
+        raise AmpnetError(f"seg_nll_backward: dlogp {tuple(dlogp.shape)} needs target [M] = {[M]}, sums [2] and grad_loss [1], got "
+                          f"{tuple(target.shape)} {tuple(sums.shape)} {tuple(grad_loss.shape)}")
+    with torch.cuda.device(dlogp.device):
+        rc = lib().ampnet_seg_nll_backward_f32(ptr(target), ptr(class_w), ptr(sums), ptr(grad_loss), ctypes.c_longlong(M), C, ptr(dlogp),
+                                               stream_ptr(dlogp.device))
+    check(rc, "ampnet_seg_nll_backward_f32")

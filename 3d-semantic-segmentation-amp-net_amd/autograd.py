@@ -518,3 +518,36 @@ def seg_head_apply(module, rows, fold_ws):
     """Grad-mode forward of a PointNetSegHead on rows [M, in_channel] -> log-probabilities [M, num_classes] with a graph to the rows and to
     the head's conv1, bn1 (weight and bias) and conv2."""
     return _SegHeadFn.apply(module.bn1.eps, fold_ws, rows, *seg_head_tensors(module))
+
+
+def seg_nll_forward(logp, target, class_w, want_preds, want_counts):
+    """ampnet_seg_nll_forward_f32 on logp [M, C], target [M] -> (loss 0-d, sums [2] float64, preds [M] or None, counts [C * C + 1] or None)."""
+    M, C = logp.shape
+    dev = logp.device
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    preds = torch.empty(M, dtype=torch.int64, device=dev) if want_preds else None
+    counts = torch.empty(C * C + 1, dtype=torch.int64, device=dev) if want_counts else None
+    _lib.seg_nll_forward_f32(logp, target, class_w, sums, loss, preds, counts, _ws(_lib.seg_nll_forward_workspace_bytes(M), dev))
+    return loss.reshape(()), sums, preds, counts
+
+
+class _SegNllFn(torch.autograd.Function):
+    """The masked, weighted NLL behind the segmentation head (pointnet2_utils.seg_nll_loss): logp [M, C] -> (loss 0-d, preds, counts), the
+    last two None when not wanted.  Saved for the backward: target, class_w and the forward's float64 sums -- not logp, the gradient does
+    not depend on it.  preds and counts are integers: marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, logp, target, class_w, want_preds, want_counts):
+        loss, sums, preds, counts = seg_nll_forward(logp, target, class_w, want_preds, want_counts)
+        ctx.save_for_backward(target, sums, *(() if class_w is None else (class_w,)))
+        ctx.shape = tuple(logp.shape)
+        ctx.mark_non_differentiable(*(t for t in (preds, counts) if t is not None))
+        return loss, preds, counts
+
+    @staticmethod
+    def backward(ctx, gloss, _gpreds, _gcounts):
+        target, sums, *w = ctx.saved_tensors
+        dlogp = torch.empty(ctx.shape, dtype=torch.float32, device=target.device)
+        _lib.seg_nll_backward_f32(target, w[0] if w else None, sums, gloss.detach().float().reshape(1).contiguous(), dlogp)
+        return dlogp, None, None, None, None

@@ -43,12 +43,14 @@ def augment_batch(pc_clusters, targets, train):
     return x, t
 
 
-def augment_batch_device(pc_clusters, targets, train, device):
+def augment_batch_device(pc_clusters, targets, train, device, return_perm=False):
     """augment_batch on the GPU (include/ampnet_hip.h: ampnet_augment_f32): the collated batch goes up in one copy and one
     kernel applies cluster permutation, z-rotation (float64, as numpy computes it), the per-window point permutations and the
     re-layout.  The draws come from numpy's global RNG in the reference's order -- cluster permutation, angle, then (train
     only) one point permutation per window -- so a seeded run sees the same batch as augment_batch / the reference.
-    pc_clusters [B, N, 9, W], targets [B, N, W] (host or device tensors) -> device x [B, W, N, 9] f32, t [B, W, N] i64."""
+    pc_clusters [B, N, 9, W], targets [B, N, W] (host or device tensors) -> device x [B, W, N, 9] f32, t [B, W, N] i64.
+    return_perm=True: also the cluster permutation that was drawn (numpy int array [W]: output window w is input cluster cperm[w]); the
+    draws and the outputs are the same either way."""
     import ctypes
     pc = torch.as_tensor(pc_clusters)
     tg = torch.as_tensor(targets)
@@ -77,14 +79,14 @@ def augment_batch_device(pc_clusters, targets, train, device):
                                            ctypes.c_double(float(np.cos(r_angle))), ctypes.c_double(float(np.sin(r_angle))),
                                            1 if train else 0, B, N, W, _lib.ptr(x), _lib.ptr(t), _lib.stream_ptr(dev))
     _lib.check(rc, "ampnet_augment_f32")
-    return x, t
+    return (x, t, cperm) if return_perm else (x, t)
 
 
-def augment_ragged_device(rb, train, device):
+def augment_ragged_device(rb, train, device, return_perm=False):
     """augment_batch_device for a collate_fns.RaggedBatch: the same draws from numpy's RNG in the same order, ONE upload of the ragged
     samples (less than half the bytes of the padded batch) and one kernel that resamples, pads, permutes, rotates and re-lays-out
     (include/ampnet_hip.h: ampnet_collate_augment_f32) -> device x [B, W, N, 9] f32, t [B, W, N] i64, bit-identical to
-    augment_batch_device(*rb.to_padded()) (tests/test_augment_gpu.py)."""
+    augment_batch_device(*rb.to_padded()) (tests/test_augment_gpu.py).  return_perm: as in augment_batch_device."""
     import ctypes
     B, N, W = len(rb), rb.n_points, rb.n_windows
     cperm = np.arange(W)
@@ -108,7 +110,7 @@ def augment_ragged_device(rb, train, device):
                                                    ctypes.c_double(float(np.cos(r_angle))), ctypes.c_double(float(np.sin(r_angle))),
                                                    1 if train else 0, B, N, W, _lib.ptr(x), _lib.ptr(t), _lib.stream_ptr(dev))
     _lib.check(rc, "ampnet_collate_augment_f32")
-    return x, t
+    return (x, t, cperm) if return_perm else (x, t)
 
 
 def forward_batch(pointnet, att_net, x, t, centroids, class_w=None, want_loss=True, want_preds=True):

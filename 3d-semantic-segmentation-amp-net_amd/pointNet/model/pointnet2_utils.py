@@ -50,7 +50,9 @@ branch by branch through the kernels above.  It serves models defined inside the
 PointNetSegHead is the per-point classifier behind the backbone (conv1, bn1, ReLU, drop1, conv2, log_softmax): one fused kernel in eval
 mode (ampnet_seg_head_forward_f32), with grad=True differentiable through ampnet_seg_head_backward_f32 (its docstring;
 pointnetAtt.pointnet_2_seg puts it behind pointnet_2's six blocks); batch_stats=True adds train mode -- bn1 on batch statistics and a real
-dropout (ampnet_seg_head_train_forward_f32, ampnet_seg_head_train_backward_f32).  Its bf16 and a fused loss are not built.
+dropout (ampnet_seg_head_train_forward_f32, ampnet_seg_head_train_backward_f32).  Its bf16 and a loss fused into its kernel are not built;
+seg_nll_loss is the loss BEHIND it: masked, weighted NLL, predictions and confusion counts in one pass over the log-probabilities
+(ampnet_seg_nll_forward_f32, ampnet_seg_nll_backward_f32 through autograd._SegNllFn).
 Not built: momentum=None, gradients to coordinates, train-mode BatchNorm (batch_stats=True) in a `group_all=True` block, a `precision`
 keyword for PointNetSetAbstractionMsg (its one-launch forward is fp32 only), bf16 in a backward, a train-mode or a group_all forward.
 
@@ -544,7 +546,8 @@ class PointNetSegHead(nn.Module):
     in train mode ampnet_seg_head_train_backward_f32 through autograd._SegHeadTrainFn, back through the batch statistics and the mask).
     grad=False (default): no graph, ever.
     Limits: 1 <= in_channel <= 256, hidden a multiple of 32 in [32, 256], 2 <= num_classes <= 32.  The head is exact fp32 and has no
-    `precision` keyword.  Not built: bf16, a fused loss (F.nll_loss on the [B * N, num_classes] log-probabilities is a small operation),
+    `precision` keyword.  Not built: bf16, a fused loss (F.nll_loss on the [B * N, num_classes] log-probabilities is a small operation;
+    seg_nll_loss below is that operation with the predictions and the confusion counts in one pass, behind the head, not inside its kernel),
     momentum=None (the cumulative average), dropout in eval mode."""
 
     def __init__(self, in_channel, hidden, num_classes, dropout=0.5, device='cuda', grad=False, batch_stats=False):
@@ -644,3 +647,33 @@ class PointNetSegHead(nn.Module):
         with torch.no_grad():
             self.bn1.num_batches_tracked += 1
         return logp
+
+
+def seg_nll_loss(log_probs, target, weight=None, want_preds=False, want_counts=False):
+    """The loss behind PointNetSegHead / pointnet_2_seg in one pass over the log-probabilities (ampnet_seg_nll_forward_f32):
+    log_probs [..., C] float32, target [...] int64 (a target outside [0, C) is ignored; -1 is the padding label), weight [C] float32 or None
+    -> (loss 0-d, preds int64 [...] or None, counts int64 [C * C + 1] or None).
+    loss is F.nll_loss(log_probs.reshape(-1, C), target.reshape(-1), weight, ignore_index=-1) with the two sums taken in float64 (NaN when
+    every row is ignored, as torch); preds the lowest class among the equal largest entries of a row (the head's own rule), ignored rows
+    included; counts what utils.get_metrics.confusion_device(preds, target, C) returns, so metrics_from_confusion applies unchanged.
+    GPU tensors only, nothing synchronises.  With grad mode on and log_probs requiring grad, loss carries a graph to log_probs
+    (ampnet_seg_nll_backward_f32 through autograd._SegNllFn, the upstream gradient read on the device); preds and counts never do.
+    Limits: 2 <= C <= 32 (the head's)."""
+    from ... import autograd
+    _lib.require_gpu(log_probs, "log_probs")
+    _lib.require_gpu(target, "target")
+    if log_probs.dim() < 1 or tuple(target.shape) != tuple(log_probs.shape[:-1]) or target.dtype != torch.int64:
+        raise _lib.AmpnetError(f"seg_nll_loss: expected log_probs [..., C] and an int64 target of shape [...], got {tuple(log_probs.shape)} "
+                               f"{log_probs.dtype} / {tuple(target.shape)} {target.dtype}")
+    C = log_probs.shape[-1]
+    flat = log_probs.float().reshape(-1, C).contiguous()            # (views of the head's output: no copy)
+    t = target.reshape(-1).contiguous()
+    if weight is not None:
+        _lib.require_gpu(weight, "weight")
+        weight = weight.detach().float().contiguous()
+    if torch.is_grad_enabled() and log_probs.requires_grad:
+        loss, preds, counts = autograd._SegNllFn.apply(flat, t, weight, bool(want_preds), bool(want_counts))
+    else:
+        with torch.no_grad():
+            loss, _, preds, counts = autograd.seg_nll_forward(flat.detach(), t, weight, bool(want_preds), bool(want_counts))
+    return loss, (None if preds is None else preds.reshape(target.shape)), counts

@@ -488,15 +488,20 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
         global_feature = self.conv1(l0_points).amax(2)                                # MaxPool1d(N) + view(-1, 128)
         return global_feature, l0_points
 
-    def _backbone(self, xyz):
+    def _backbone(self, xyz, rows=False):
         """The six blocks -> (fp1's point-major result [B, N, 128] as it left the kernel, l0_points [B, 128, N]): what pointnet_2 puts
-        conv1 and the max behind, and pointnet_2_seg its head."""
+        conv1 and the max behind, and pointnet_2_seg its head.  rows=True: `xyz` is the point-major [B, N, 9] float32 contiguous tensor the
+        blocks consume, taken as it is, and l0_points is None -- neither the transpose in nor the [B, 128, N] copy out."""
         if self.training and not self.decoder_batch_stats:
             raise NotImplementedError("pointnet_2 on the HIP path is built for eval mode (BatchNorm running statistics, no backward): "
                                       "call .eval() first")
         self._check_bf16()
         _lib.require_gpu(xyz, "xyz")
-        if xyz.dim() != 3 or xyz.shape[1] != 9:
+        if rows:
+            if xyz.dim() != 3 or xyz.shape[2] != 9 or xyz.dtype != torch.float32 or not xyz.is_contiguous():
+                raise _lib.AmpnetError(f"pointnet_2: expected point-major rows [Q, N, 9], float32 and contiguous, got {tuple(xyz.shape)} "
+                                       f"{xyz.dtype}, strides {xyz.stride()}")
+        elif xyz.dim() != 3 or xyz.shape[1] != 9:
             raise _lib.AmpnetError(f"pointnet_2: expected xyz [B, 9, N], got {tuple(xyz.shape)}")
         for m in (self.sa1, self.sa2, self.sa3):
             if m.training != (self.training and self.encoder_batch_stats):
@@ -507,7 +512,7 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
                 raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
                                           "pointnet_2: fp1..fp3 follow the model's mode; call .train() on the model, not on its blocks")
         with torch.no_grad():
-            l0_points = xyz.detach().float().transpose(1, 2).contiguous()             # [B, N, 9]
+            l0_points = xyz.detach() if rows else xyz.detach().float().transpose(1, 2).contiguous()      # [B, N, 9]
             l0_xyz = l0_points[:, :, :3].contiguous()                                 # [B, N, 3]
         with contextlib.nullcontext() if self.encoder_grad else torch.no_grad():    # (the caller's grad mode, or none)
             l1_xyz, l1_points = self.sa1._forward_rows(l0_xyz, l0_points)             # [B, 1024, 3], [B, 1024, 64]
@@ -517,7 +522,7 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
             l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)  # [B, 256, 256]
             l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)  # [B, 1024, 128]
             l0_rows = self.fp1._forward_rows(l0_xyz, l1_xyz, None, l1_points)         # [B, N, 128]
-            l0_points = l0_rows.transpose(1, 2).contiguous()                          # [B, 128, N], the reference's layout
+            l0_points = None if rows else l0_rows.transpose(1, 2).contiguous()        # [B, 128, N], the reference's layout
         return l0_rows, l0_points
 
 
@@ -539,8 +544,10 @@ class pointnet_2_seg(pointnet_2):
     batch_stats=True and .train(mode) moves it with the decoder, so in train mode bn1 normalises with the statistics of the batch, updates
     its running statistics and drop1 drops (PointNetSegHead; the mask follows the head's `seed`).  With all five flags the model trains
     from scratch; .eval() afterwards is the eval forward on the trained state, bit for bit what a default pointnet_2_seg loaded with that
-    state_dict gives.  Not built: bf16 (the model has no `precision` keyword and refuses set_precision('bf16')), a fused loss,
-    momentum=None, dropout in eval mode, train mode for group_all set abstraction."""
+    state_dict gives.  forward_rows / predict_rows are forward / predict on point-major [Q, N, 9] rows, without the transposes
+    (pointNet/pn2_step.py trains through them, with pointnet2_utils.seg_nll_loss as the loss).  Not built: bf16 (the model has no
+    `precision` keyword and refuses set_precision('bf16')), a loss fused into the head's kernel, momentum=None, dropout in eval mode, train
+    mode for group_all set abstraction."""
 
     def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False,
                  encoder_batch_stats=False, head_batch_stats=False):
@@ -571,4 +578,20 @@ class pointnet_2_seg(pointnet_2):
         """xyz [B, 9, N] -> the class of every point, int64 [B, N] (the lowest class among equal logits).  Never a graph."""
         with torch.no_grad():
             l0_rows, _ = self._backbone(xyz)
+            return self._head._forward_rows(l0_rows, want_preds=True)[1]
+
+    def forward_rows(self, points):
+        """forward() on point-major rows: points [Q, N, 9] float32 contiguous GPU (what the device input pipeline writes per window,
+        amp_step.augment_ragged_device) -> log_probs [Q, N, num_classes], the bits of forward(points.transpose(1, 2))[0].  The six blocks
+        and the head consume and produce rows, so nothing is transposed on the way in and the [Q, 128, N] copy of l0_points -- 604 MB at
+        576 windows of 2048 points, with a backward mirror, read by nobody in a train step -- is not made.  Mode checks, graph rules and
+        flags are forward()'s."""
+        l0_rows, _ = self._backbone(points, rows=True)
+        with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
+            return self._head._forward_rows(l0_rows)
+
+    def predict_rows(self, points):
+        """predict() on point-major rows [Q, N, 9] -> int64 [Q, N].  An eval operation, never a graph."""
+        with torch.no_grad():
+            l0_rows, _ = self._backbone(points, rows=True)
             return self._head._forward_rows(l0_rows, want_preds=True)[1]

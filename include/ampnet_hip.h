@@ -749,6 +749,40 @@ int ampnet_seg_head_train_backward_f32(const float *x, int ld, long long M, int 
                                        const float *save_invstd, const float *dlogp, float *dx, float *const *grads_host, void *workspace,
                                        size_t workspace_bytes, void *stream);
 
+/* ---- the loss behind the segmentation head: masked, weighted NLL with predictions and confusion counts (new symbols within ABI 18:
+ * nothing else moved, AMPNET_ABI_VERSION stays 18) ---------------------------------------------------------------------------------------
+ * One pass over the log-probabilities the head wrote, where the composition nll_loss + argmax + ampnet_confusion_i64 takes about eight
+ * launches over the same array.  The loss is NOT fused into the head's kernel: logp is read from memory.
+ *   logp      [M][C] float32, dense                      target   [M] int64
+ *   class_w   [C] float32 device, or NULL = ones
+ *   sums      [2] float64 device out: sum over the live rows of w[t] * -logp[m][t], and of w[t]
+ *   loss      [1] float32 device out: (float)(sums[0] / sums[1])
+ *   preds     [M] int64 out, or NULL                      counts   [C * C + 1] int64 out, or NULL
+ * Ignored rows.  A row whose target lies outside [0, C) is ignored; -1 is the padding label and the ONLY such value the package's drivers
+ * produce.  An ignored row adds nothing to sums and gets a zero row of dlogp; it still gets a prediction and is counted in counts[C * C].
+ * This is torch's nll_loss(weight, ignore_index=-1, reduction='mean') on the drivers' targets; with every row ignored the loss is 0 / 0 = NaN
+ * and dlogp is all zeros, as in torch.
+ *   preds[m]  the LOWEST class among the equal largest logp[m][:] (the head's own rule, what ampnet_confusion_i64 takes)
+ *   counts    the layout of ampnet_confusion_i64: counts[t * C + p] over the live rows, counts[C * C] the ignored rows.  The entry point
+ *             zero-fills it on the stream; a workgroup counts in an int32 LDS table and adds its non-zero cells with integer atomics.
+ * Summation: float64 throughout.  256-thread workgroups, grid = min(cdiv(M, 256), 1024), thread `i` of workgroup `g` takes the rows
+ * 256 g + i + 256 grid k, k ascending; a wave adds its 64 lanes by a butterfly of shuffles (xor 32, 16, .. 1), thread 0 adds the four waves
+ * ascending, the workgroup writes one double[2] row of the workspace, and a one-workgroup kernel adds the rows ascending.  w[t] * -logp is
+ * exact in float64 (two float32 factors).  Every order is a function of (M, C) alone: two calls return the same bits.  No float atomics.
+ *   workspace ampnet_seg_nll_forward_workspace_bytes(M) device bytes (0 = M is refused), aligned to 8: the workgroups' partial rows
+ * Backward, for the upstream gradient g = grad_loss[0] (DEVICE memory: no host synchronisation):
+ *     dlogp[m][t] = (float)(-(w[t] * g) / sums[1])      the float64 quotient rounded once, within half a float32 ulp;      0 elsewhere
+ * (the float32 statement -(w[t] * g) / (float)sums[1] rounds sums[1], the product and the quotient and can land 2.5 ulp away; the C
+ * values a row can take are formed once per workgroup, so the float64 divisions cost nothing that shows).
+ * One thread per row writes all C values of its row: dlogp may be uninitialised memory.
+ * Limits (AMPNET_E_ARG on the host before any launch): 2 <= C <= AMPNET_SEG_HEAD_MAX_CLASSES, 1 <= M <= AMPNET_SEG_HEAD_MAX_ROWS, null
+ * pointers, a short or misaligned workspace.  The pass moves 4 M C bytes and is bound by its launches.  Caller's stream.               */
+size_t ampnet_seg_nll_forward_workspace_bytes(long long M);
+int ampnet_seg_nll_forward_f32(const float *logp, long long M, int C, const long long *target, const float *class_w, double *sums, float *loss,
+                               long long *preds, long long *counts, void *workspace, size_t workspace_bytes, void *stream);
+int ampnet_seg_nll_backward_f32(const long long *target, const float *class_w, const double *sums, const float *grad_loss, long long M, int C,
+                                float *dlogp, void *stream);
+
 /* ---- size-constrained k-means: the window grouping step in front of the path --------------------------
  * replaces the calls of the third-party k_means_constrained.KMeansConstrained at data_proc/3_kmeans.py:78-82 (size_min = size_max =
  * n_points, n_init 5, max_iter 10, tol 1e-2, features x, y, NDVI) and utils/utils.py:500-505 (size_min only).  That package is not part

@@ -188,6 +188,38 @@ def three_nn_f32(fine, coarse, idx, dist2):
     check(rc, "ampnet_three_nn_f32")
 
 
+BALL_QUERY_MAX_N = 12288
+
+
+def ball_query_ragged_f32(rows, cloud_off, max_n, centres, radius, nsample, global_index, out, count=None):
+    """rows [total, ld] float32, cloud_off [Q + 1] int32 (device), centres [Q, S] int32 relative to their cloud, out [Q, S, nsample] int32,
+    count [Q, S] int32 or None: contiguous GPU tensors; max_n the largest cloud (host int)."""
+    total, ld = rows.shape
+    Q, S = centres.shape
+    with torch.cuda.device(rows.device):
+        rc = lib().ampnet_ball_query_ragged_f32(ptr(rows), ld, ptr(cloud_off), Q, total, int(max_n), ptr(centres), S, ctypes.c_float(radius),
+                                                int(nsample), int(bool(global_index)), ptr(out), ptr(count), stream_ptr(rows.device))
+    check(rc, "ampnet_ball_query_ragged_f32")
+
+
+def three_nn_ragged_f32(fine, cloud_off, max_n, coarse, global_index, idx, dist2):
+    """fine [total, ld1] float32, cloud_off [Q + 1] int32 (device), coarse [Q, S, ld2] float32, idx int32 / dist2 float32 [total, k],
+    k = min(3, S): contiguous GPU tensors; max_n the largest fine cloud (host int)."""
+    total, ld1 = fine.shape
+    Q, S, ld2 = coarse.shape
+    k = min(3, S)
+    for name, t, dt in (("fine", fine, _F32), ("cloud_off", cloud_off, _I32), ("coarse", coarse, _F32), ("idx", idx, _I32), ("dist2", dist2, _F32)):
+        if not t.is_cuda or t.dtype != dt:
+            raise AmpnetError(f"three_nn_ragged: {name} must be a {dt} GPU tensor")
+    if cloud_off.numel() != Q + 1 or tuple(idx.shape) != (total, k) or tuple(dist2.shape) != (total, k):
+        raise AmpnetError(f"three_nn_ragged: cloud_off [Q + 1], idx and dist2 [total, min(3, S)] do not agree with fine {tuple(fine.shape)} "
+                          f"and coarse {tuple(coarse.shape)}")
+    with torch.cuda.device(fine.device):
+        rc = lib().ampnet_three_nn_ragged_f32(ptr(fine), ld1, ptr(cloud_off), Q, total, int(max_n), ptr(coarse), S, ld2,
+                                              int(bool(global_index)), ptr(idx), ptr(dist2), stream_ptr(fine.device))
+    check(rc, "ampnet_three_nn_ragged_f32")
+
+
 # The rules the fused set-abstraction (sa_*) and feature-propagation (fp_*) wrappers share, each written once.  The kernels take bare
 # pointers and no strides: what a wrapper lets through is read wrongly without any error.  `prefix` is the wrapper's name, the start of
 # every message.

@@ -270,6 +270,34 @@ class PointNetSetAbstraction(_EvalForwardPrecision, _SetAbstraction):
                                 _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
         return new_xyz, out
 
+    def _forward_ragged(self, x, feats, layout):
+        """The eval layer on clouds of UNEQUAL size packed back to back: x [total, 3], feats [total, D] or None, float32 contiguous GPU,
+        layout = utils.RaggedLayout of the clouds, every one of >= npoint points -> (new_xyz [Q, npoint, 3], new_points [Q, npoint, mlp[-1]]),
+        cloud by cloud the bits of _forward_rows on that cloud alone.  Ragged FPS, then the ragged ball query with GLOBAL indices, then the
+        fused kernel of _forward_rows on the packed array as ONE cloud of `total` points and Q * npoint centres: a centre's row of the
+        output depends on its own group and the weights alone (csrc/set_abstraction.hip: a wave owns a centre, a fixed contraction order,
+        no atomics), so which launch it shares is immaterial.  No graph, no host read-back (the centres are FPS's own)."""
+        self._check_bf16()
+        if self.group_all or self.training or is_bf16(self.precision):
+            raise NotImplementedError("PointNetSetAbstraction._forward_ragged is built for the exact-fp32 eval forward of a grouping block "
+                                      "(group_all=False, .eval(), precision fp32)")
+        Q, S = len(layout.sizes), self.npoint
+        if min(layout.sizes) < S:
+            raise _lib.AmpnetError(f"PointNetSetAbstraction: every cloud needs at least npoint={S} points for farthest-point sampling, "
+                                   f"got sizes {layout.sizes}")
+        with torch.no_grad():
+            x = x.detach()
+            centres = torch.stack(U.fps_indices_ragged(x, layout.sizes, S))                       # [Q, npoint], relative to their cloud
+            group_idx = U.ball_query_ragged(x, layout, centres, self.radius, self.nsample, global_index=True, _trusted_centres=True)
+            centres = (centres + layout.off[:-1].unsqueeze(1)).reshape(1, Q * S)                  # rows of the packed array
+            packed = x.unsqueeze(0)
+            new_xyz = U.gather_rows(packed, centres)
+            layers = _mlp_tensors(self)
+            out = torch.empty((1, Q * S, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
+            _lib.sa_forward_f32(packed, centres, group_idx.reshape(1, Q * S, self.nsample), None if feats is None else feats.detach().unsqueeze(0),
+                                layers, [bn.eps for bn in self.mlp_bns], out, _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
+        return new_xyz.reshape(Q, S, 3), out.reshape(Q, S, -1)
+
     def _all_rows(self, x, feats, centres):
         """_forward_rows of a group_all block: ONE group of all N points per cloud, the coordinates as they are (no centre)
         -> (zeros [B, 1, 3], [B, 1, mlp[-1]])."""
@@ -505,6 +533,27 @@ class PointNetFeaturePropagation(_EvalForwardPrecision, nn.Module):
             _lib.fp_forward_f32(p1, p2, idx, dist2, layers, [bn.eps for bn in self.mlp_bns], out,
                                 _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
         return out
+
+    def _forward_ragged(self, x1, layout, x2, p1, p2):
+        """The eval layer from fine clouds of UNEQUAL size packed back to back to S coarse points per cloud: x1 [total, 3], p1 [total, D1] or
+        None, layout = utils.RaggedLayout of the fine clouds, x2 [Q, S, 3], p2 [Q, S, D2], float32 contiguous GPU -> [total, mlp[-1]], cloud
+        by cloud the bits of _forward_rows on that cloud alone.  The ragged 3-NN with GLOBAL indices, then the fused kernel of _forward_rows
+        on the packed arrays as ONE cloud (total fine, Q * S coarse points): a fine point's output row depends on its own input row and the
+        weights alone (csrc/feature_propagation.hip: the rows of a tile do not mix, a fixed contraction order, no atomics), so where the
+        tile boundaries fall is immaterial.  No graph."""
+        self._check_bf16()
+        if self.training or is_bf16(self.precision):
+            raise NotImplementedError("PointNetFeaturePropagation._forward_ragged is built for the exact-fp32 eval forward (.eval(), "
+                                      "precision fp32)")
+        Q, S = x2.shape[0], x2.shape[1]
+        with torch.no_grad():
+            idx, dist2 = U.three_nn_ragged(x1.detach(), layout, x2.detach(), global_index=True)
+            layers = _mlp_tensors(self)
+            out = torch.empty((1, layout.total, layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
+            _lib.fp_forward_f32(None if p1 is None else p1.detach().unsqueeze(0), p2.detach().reshape(1, Q * S, p2.shape[2]), idx.unsqueeze(0),
+                                dist2.unsqueeze(0), layers, [bn.eps for bn in self.mlp_bns], out,
+                                _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
+        return out[0]
 
     def _train_rows(self, p1, p2, idx, dist2):
         """_forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when one is wanted."""

@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from ... import _lib, ops
 from ... import params as P
+from ...utils import utils as U
 from ._precision import _EvalForwardPrecision, _HasPrecision, is_bf16     # noqa: F401  (_HasPrecision: _baseline.py takes it from here)
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSegHead, PointNetSetAbstraction
 
@@ -545,7 +546,9 @@ class pointnet_2_seg(pointnet_2):
     its running statistics and drop1 drops (PointNetSegHead; the mask follows the head's `seed`).  With all five flags the model trains
     from scratch; .eval() afterwards is the eval forward on the trained state, bit for bit what a default pointnet_2_seg loaded with that
     state_dict gives.  forward_rows / predict_rows are forward / predict on point-major [Q, N, 9] rows, without the transposes
-    (pointNet/pn2_step.py trains through them, with pointnet2_utils.seg_nll_loss as the loss).  Not built: bf16 (the model has no
+    (pointNet/pn2_step.py trains through them, with pointnet2_utils.seg_nll_loss as the loss).  forward_ragged / predict_ragged /
+    predict_clouds label clouds of UNEQUAL size in one launch sequence, cloud by cloud the bits of forward_rows / predict_rows on that cloud
+    alone (eval, no graph; pointNet/pn2_infer.py drives them).  Not built: bf16 (the model has no
     `precision` keyword and refuses set_precision('bf16')), a loss fused into the head's kernel, momentum=None, dropout in eval mode, train
     mode for group_all set abstraction."""
 
@@ -595,3 +598,64 @@ class pointnet_2_seg(pointnet_2):
         with torch.no_grad():
             l0_rows, _ = self._backbone(points, rows=True)
             return self._head._forward_rows(l0_rows, want_preds=True)[1]
+
+    # ---- clouds of UNEQUAL size in one launch sequence (eval, no graph) ------------------------------------------------------------------
+    # Only level 0 is ragged: sa1 emits npoint centres for every cloud, so sa2, sa3, fp3 and fp2 see uniform [Q, npoint, .] tensors and
+    # run as they are; sa1 samples and groups ragged clouds, fp1 searches from ragged fine points, and the head takes any number of rows.
+
+    def _ragged(self, rows, sizes, want_preds):
+        """The six blocks and the head on `rows` [total, 9] = clouds of `sizes` points back to back -> the head's result on [1, total, 128]."""
+        if self.training or self._head.training or any(m.training for m in (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1)):
+            raise NotImplementedError("pointnet_2_seg: forward_ragged / predict_ragged / predict_clouds are eval operations: call .eval() "
+                                      "first")
+        _lib.require_gpu(rows, "rows")
+        if rows.dim() != 2 or rows.shape[1] != 9 or rows.dtype != torch.float32 or not rows.is_contiguous():
+            raise _lib.AmpnetError(f"pointnet_2_seg: expected packed rows [total, 9], float32 and contiguous, got {tuple(rows.shape)} "
+                                   f"{rows.dtype}, strides {rows.stride()}")
+        layout = U.ragged_layout("pointnet_2_seg", rows, sizes)
+        if min(layout.sizes) < self.sa1.npoint:
+            raise _lib.AmpnetError(f"pointnet_2_seg: every cloud needs at least sa1.npoint={self.sa1.npoint} points, cloud "
+                                   f"{layout.sizes.index(min(layout.sizes))} has {min(layout.sizes)} (predict_clouds pads such clouds)")
+        with torch.no_grad():
+            l0_points = rows.detach()
+            l0_xyz = l0_points[:, :3].contiguous()                                             # [total, 3]
+            l1_xyz, l1_points = self.sa1._forward_ragged(l0_xyz, l0_points, layout)            # [Q, 1024, 3], [Q, 1024, 64]
+            l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)
+            l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)
+            l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)
+            l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)
+            l0_rows = self.fp1._forward_ragged(l0_xyz, layout, l1_xyz, None, l1_points)        # [total, 128]
+            return self._head._forward_rows(l0_rows.unsqueeze(0), want_preds=want_preds)
+
+    def forward_ragged(self, rows, sizes):
+        """rows [total, 9] float32 contiguous GPU = clouds of `sizes` points back to back, every one of >= sa1.npoint points
+        -> log_probs [total, num_classes]; the rows of cloud b are the bits of forward_rows on that cloud alone.  One launch sequence for
+        all clouds, no host read-back.  An eval operation, never a graph; train mode raises NotImplementedError."""
+        return self._ragged(rows, sizes, False)[0]
+
+    def predict_ragged(self, rows, sizes):
+        """forward_ragged's classes, int64 [total]: cloud by cloud the bits of predict_rows."""
+        return self._ragged(rows, sizes, True)[1].reshape(-1)
+
+    def _predict_padded(self, rows, sizes):
+        """predict_ragged for clouds of ANY size >= 1: a cloud below sa1.npoint points is padded on the device by repeating its rows
+        cyclically (utils.pad_cloud_sizes) and the padding's predictions are dropped -> int64 [total]."""
+        sizes = [int(n) for n in sizes]
+        if not sizes or min(sizes) >= self.sa1.npoint:
+            return self.predict_ragged(rows, sizes)
+        if sum(sizes) != rows.shape[0]:
+            raise _lib.AmpnetError(f"pointnet_2_seg: sizes (sum {sum(sizes)}) do not tile the {rows.shape[0]} rows")
+        padded, _, gather, keep = U.pad_cloud_sizes(sizes, self.sa1.npoint)
+        preds = self.predict_ragged(rows[torch.from_numpy(gather).to(rows.device, non_blocking=True)], padded)
+        return preds[torch.from_numpy(keep).to(rows.device, non_blocking=True)]
+
+    def predict_clouds(self, clouds):
+        """clouds: a list of [n_i, >= 9] tensors (the first nine columns are the features; CPU or GPU) -> a list of int64 [n_i] GPU tensors,
+        each the bits of predict_rows on that cloud alone.  A cloud with fewer than sa1.npoint points is padded by repeating its rows
+        cyclically and the padding's predictions are dropped."""
+        if not clouds:
+            return []
+        dev = self.conv1.weight.device
+        sizes = [int(c.shape[0]) for c in clouds]
+        rows = torch.cat([torch.as_tensor(c)[:, :9].float().to(dev, non_blocking=True) for c in clouds], dim=0).contiguous()
+        return list(self._predict_padded(rows, sizes).split(sizes))

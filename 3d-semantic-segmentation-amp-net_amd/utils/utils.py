@@ -203,6 +203,119 @@ def three_nn(fine_xyz, coarse_xyz):
     return idx, dist2
 
 
+class CentreRangeError(_lib.AmpnetError, IndexError):
+    """A centre outside its cloud in a ragged call: an IndexError, as ball_query raises for it, and an AmpnetError, as every refusal of a
+    ragged layout is."""
+
+
+class RaggedLayout:
+    """Clouds of unequal size packed back to back: `sizes` (host ints), `off` (their prefix sums as the DEVICE int32 [Q + 1] table the
+    ragged entry points read), `total` and `max_n`.  Built once per call sequence (ragged_layout) and shared by its launches: one upload."""
+
+    def __init__(self, sizes, off):
+        self.sizes, self.off = sizes, off
+        self.total, self.max_n = sum(sizes), max(sizes)
+
+
+def ragged_layout(what, rows, sizes):
+    """`sizes` must tile the rows of `rows` [total, D] (a GPU tensor) with clouds of >= 1 point -> RaggedLayout; a RaggedLayout is checked
+    against `rows` and returned as it is."""
+    if isinstance(sizes, RaggedLayout):
+        if sizes.total != rows.shape[0] or sizes.off.device != rows.device:
+            raise _lib.AmpnetError(f"{what}: the layout ({sizes.total} rows on {sizes.off.device}) does not tile the {rows.shape[0]} rows on "
+                                   f"{rows.device}")
+        return sizes
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 1 or sum(sizes) != rows.shape[0]:
+        raise _lib.AmpnetError(f"{what}: sizes (sum {sum(sizes)}) do not tile the {rows.shape[0]} rows")
+    if rows.shape[0] > 0x7fffffff:
+        raise _lib.AmpnetError(f"{what}: {rows.shape[0]} rows exceed 2^31 - 1")
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(rows.device, non_blocking=True)
+    return RaggedLayout(sizes, off)
+
+
+def pad_cloud_sizes(sizes, npoint):
+    """The packing behind pointnet_2_seg.predict_clouds, a pure host function: clouds of `sizes` points of which every one below `npoint` is
+    padded to `npoint` by repeating its rows cyclically (row j of the padded cloud is row j % n of the cloud)
+    -> (padded sizes [Q] list, offsets int64 [Q + 1] of the padded clouds, gather int64 [sum padded]: the row of the UNPADDED concatenation
+    every padded row is a copy of, keep int64 [sum sizes]: the padded rows that are the clouds' own, in order)."""
+    sizes, npoint = [int(n) for n in sizes], int(npoint)
+    if not sizes or min(sizes) < 1 or npoint < 1:
+        raise ValueError(f"pad_cloud_sizes: sizes {sizes} must be >= 1 each, npoint={npoint} >= 1")
+    padded = [max(n, npoint) for n in sizes]
+    off = np.concatenate([[0], np.cumsum(padded)]).astype(np.int64)
+    src = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    gather = np.concatenate([src[i] + np.arange(p, dtype=np.int64) % n for i, (n, p) in enumerate(zip(sizes, padded))])
+    keep = np.concatenate([off[i] + np.arange(n, dtype=np.int64) for i, n in enumerate(sizes)])
+    return padded, off, gather, keep
+
+
+def ball_query_ragged(rows, sizes, centres, radius, nsample, return_counts=False, global_index=False, _trusted_centres=False):
+    """ball_query on MANY clouds of unequal size in ONE launch (include/ampnet_hip.h: ampnet_ball_query_ragged_f32): `rows` [total, D>=3]
+    float32 GPU = the clouds back to back, `sizes` their point counts (or a RaggedLayout), centres [Q, S] int32 RELATIVE to their cloud, the
+    same S for every cloud -> int32 [Q, S, nsample]; [b] is bit for bit ball_query(rows of cloud b, centres[b:b+1], radius, nsample).
+    global_index=True adds the cloud's first row to every index: the lists then address `rows` as one cloud.  return_counts=True also
+    returns int32 [Q, S].  Every cloud holds at most 12288 points.  Argument rules and error types are ball_query's; a layout that does not
+    tile the rows, a cloud that is too large and a centre outside its cloud are AmpnetError (the last an IndexError as well).
+    _trusted_centres (internal): the centres come straight from this package's FPS on these clouds, so their range is not read back -- the
+    call then never waits for the device."""
+    _lib.require_gpu(rows, "rows")
+    _lib.require_gpu(centres, "centres")
+    if rows.dim() != 2 or rows.shape[1] < 3:
+        raise _lib.AmpnetError(f"ball_query_ragged: expected rows [total, D>=3], got {tuple(rows.shape)}")
+    lay = ragged_layout("ball_query_ragged", rows, sizes)
+    Q = len(lay.sizes)
+    if centres.dim() != 2 or centres.shape[0] != Q or centres.shape[1] < 1:
+        raise _lib.AmpnetError(f"ball_query_ragged: expected centres [Q, S] = [{Q}, S >= 1], got {tuple(centres.shape)}")
+    if centres.dtype != torch.int32:
+        raise _lib.AmpnetError("ball_query_ragged: centres must be int32")
+    for b, n in enumerate(lay.sizes):
+        if n > _lib.BALL_QUERY_MAX_N:
+            raise _lib.AmpnetError(f"ball_query_ragged: cloud {b} has {n} points, more than {_lib.BALL_QUERY_MAX_N} (coordinates must fit LDS)")
+    radius, nsample = float(radius), int(nsample)
+    if not (1 <= nsample <= _lib.SA_MAX_NSAMPLE):
+        raise IndexError(f"ball_query_ragged: nsample={nsample} out of range [1, {_lib.SA_MAX_NSAMPLE}]")
+    if not radius >= 0.0:
+        raise _lib.AmpnetError(f"ball_query_ragged: radius={radius} must be >= 0")
+    x = (rows if rows.dtype == torch.float32 else rows.float()).contiguous()
+    c = centres.contiguous()
+    if not _trusted_centres:
+        n_b = (lay.off[1:] - lay.off[:-1]).unsqueeze(1)
+        if bool(((c < 0) | (c >= n_b)).any()):
+            raise CentreRangeError("ball_query_ragged: centre index out of its cloud's range")
+    S = c.shape[1]
+    out = torch.empty((Q, S, nsample), dtype=torch.int32, device=x.device)
+    count = torch.empty((Q, S), dtype=torch.int32, device=x.device) if return_counts else None
+    _lib.ball_query_ragged_f32(x, lay.off, lay.max_n, c, radius, nsample, global_index, out, count)
+    return (out, count) if return_counts else out
+
+
+def three_nn_ragged(fine_rows, sizes, coarse_xyz, global_index=False):
+    """three_nn from MANY fine clouds of unequal size, each to its own S coarse points, in ONE launch (include/ampnet_hip.h:
+    ampnet_three_nn_ragged_f32): fine_rows [total, D>=3] float32 GPU = the fine clouds back to back, `sizes` their point counts (or a
+    RaggedLayout), coarse_xyz [Q, S, D>=3] -> (idx int32 [total, k], dist2 float32 [total, k]), k = min(3, S); the rows of cloud b are bit for
+    bit three_nn(fine rows of cloud b, coarse_xyz[b:b+1]).  global_index=True stores b * S + j: idx then addresses coarse_xyz as one cloud
+    of Q * S points.  Argument rules and error types are three_nn's; a layout that does not tile the rows is an AmpnetError."""
+    _lib.require_gpu(fine_rows, "fine_rows")
+    _lib.require_gpu(coarse_xyz, "coarse_xyz")
+    if fine_rows.dim() != 2 or fine_rows.shape[1] < 3 or coarse_xyz.dim() != 3 or coarse_xyz.shape[2] < 3:
+        raise _lib.AmpnetError(f"three_nn_ragged: expected fine_rows [total, D>=3] and coarse_xyz [Q, S, D>=3], got {tuple(fine_rows.shape)} "
+                               f"{tuple(coarse_xyz.shape)}")
+    lay = ragged_layout("three_nn_ragged", fine_rows, sizes)
+    Q, S = len(lay.sizes), coarse_xyz.shape[1]
+    if coarse_xyz.shape[0] != Q:
+        raise _lib.AmpnetError(f"three_nn_ragged: {Q} fine clouds, coarse_xyz {tuple(coarse_xyz.shape)} holds {coarse_xyz.shape[0]}")
+    if not (1 <= S <= _lib.THREE_NN_MAX_S):
+        raise IndexError(f"three_nn_ragged: S={S} coarse points out of range [1, {_lib.THREE_NN_MAX_S}]")
+    x1 = (fine_rows if fine_rows.dtype == torch.float32 else fine_rows.float()).contiguous()
+    x2 = (coarse_xyz if coarse_xyz.dtype == torch.float32 else coarse_xyz.float()).contiguous()
+    k = min(3, S)
+    idx = torch.empty((lay.total, k), dtype=torch.int32, device=x1.device)
+    dist2 = torch.empty((lay.total, k), dtype=torch.float32, device=x1.device)
+    _lib.three_nn_ragged_f32(x1, lay.off, lay.max_n, x2, global_index, idx, dist2)
+    return idx, dist2
+
+
 def gather_rows(pc, idx):
     """pc [B, N, D] f32 GPU, idx [B, S] int32 -> [B, S, D] (the `pc[sample_inds]` of utils.py:933)."""
     _lib.require_gpu(pc, "pc")

@@ -333,6 +333,27 @@ int ampnet_ball_query_f32(const float *xyz, int n_clouds, int n, int ld, const i
 int ampnet_ball_query_msg_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const float *radii_host,
                               const int *nsample_host, int K, int32_t *const *out_host, int32_t *const *count_host, void *stream);
 
+/* ---- ball query of clouds of UNEQUAL size in one launch (new symbol within ABI 18: nothing else moved, AMPNET_ABI_VERSION stays 18) ----
+ *   rows        [total, ld] float32 (first 3 columns used): the clouds back to back
+ *   cloud_off   DEVICE int32 [n_clouds + 1], ascending, cloud_off[0] = 0, cloud_off[n_clouds] = total (the table of ampnet_fps_ragged_f32):
+ *               cloud b is the rows cloud_off[b] .. cloud_off[b + 1], n_b of them
+ *   total, max_n  HOST ints: the rows of `rows` and the largest n_b; 1 <= n_b <= max_n <= 12288 (max_n * 12 bytes <= 144 KB)
+ *   centres     [n_clouds, s] int32, RELATIVE to their cloud (in [0, n_b)): the same s for every cloud
+ *   radius, nsample   as in ampnet_ball_query_f32
+ *   out         [n_clouds, s, nsample] int32;  count [n_clouds, s] int32 or NULL
+ *   global_index   0: out[b] and count[b] are bit for bit what ampnet_ball_query_f32 writes for cloud b alone (n_clouds = 1, n = n_b) -- the
+ *               same d(j), r2 formed once on the host, the boundary included, ascending index order, the padding repeating the list's
+ *               first member.  1: the same lists with cloud_off[b] added to every stored index, padding included: they address `rows` as ONE
+ *               cloud of `total` points (ampnet_sa_forward_f32 with n_clouds = 1, n = total, s = n_clouds * s).  count is the same.
+ * One launch, cloud = blockIdx.y, the plan of ampnet_ball_query_f32 (one wave per centre, the cloud's coordinate planes in LDS); the
+ * dynamic LDS is sized by max_n, so the LARGEST cloud sets the workgroups per CU of the whole call.  The kernel clamps a cloud's length
+ * to max_n and a centre into its cloud and skips a cloud whose rows leave [0, total): a wrong table or centre gives wrong lists, never an
+ * access outside `rows`.  Limits (AMPNET_E_ARG): max_n <= 12288, 1 <= nsample <= AMPNET_SA_MAX_NSAMPLE, n_clouds <= 65535; the host
+ * cannot see cloud_off -- the Python binding checks the sizes and names the offending cloud.                                          */
+int ampnet_ball_query_ragged_f32(const float *rows, int ld, const int32_t *cloud_off, int n_clouds, int total, int max_n,
+                                 const int32_t *centres, int s, float radius, int nsample, int global_index, int32_t *out, int32_t *count,
+                                 void *stream);
+
 /* ---- one set-abstraction layer, eval mode, fused (stands in for PointNetSetAbstraction.forward of pointnetAtt.py:4,285-287) ---------
  *   xyz, centres          as in ampnet_ball_query_f32 (no limit on n here)
  *   group_idx             [n_clouds, s, nsample] int32 point indices (the output of ampnet_ball_query_f32), 1 <= nsample <= 64
@@ -394,6 +415,20 @@ int ampnet_sa_msg_forward_f32(const float *xyz, int n_clouds, int n, int ld, con
 #define AMPNET_THREE_NN_MAX_S 12288
 int ampnet_three_nn_f32(const float *fine, int n_clouds, int n, int ld1, const float *coarse, int s, int ld2, int32_t *idx, float *dist2,
                         void *stream);
+
+/* ---- the same search from fine clouds of UNEQUAL size (new symbol within ABI 18: nothing else moved) ------------------------------------
+ *   fine        [total, ld1] float32 (first 3 columns used): the fine clouds back to back, cloud b = rows cloud_off[b] .. cloud_off[b + 1]
+ *   cloud_off, total, max_n   as in ampnet_ball_query_ragged_f32 (no limit on max_n here)
+ *   coarse      [n_clouds, s, ld2] float32: s coarse points for EVERY cloud, 1 <= s <= AMPNET_THREE_NN_MAX_S
+ *   idx, dist2  [total, k] int32 / float32, k = min(3, s)
+ *   global_index   0: the rows of cloud b are bit for bit the idx and dist2 of ampnet_three_nn_f32 on that cloud alone -- the same distance
+ *               form, one lane per fine point, strict `<` insertion, equal distances to the lower index.  1: idx holds b * s + j instead of
+ *               j: it addresses coarse as ONE cloud of n_clouds * s points (ampnet_fp_forward_f32 with n_clouds = 1, n = total,
+ *               s = n_clouds * s).  dist2 is the same.
+ * One launch, grid (ceil(max_n / 256), n_clouds): a workgroup wholly past its cloud's end returns before it stages anything.  The kernel
+ * clamps a cloud's length to max_n and skips a cloud whose rows leave [0, total).  Limits (AMPNET_E_ARG): n_clouds <= 65535, s as above. */
+int ampnet_three_nn_ragged_f32(const float *fine, int ld1, const int32_t *cloud_off, int n_clouds, int total, int max_n, const float *coarse,
+                               int s, int ld2, int global_index, int32_t *idx, float *dist2, void *stream);
 
 /* ---- one feature-propagation layer, eval mode, fused (stands in for PointNetFeaturePropagation.forward of pointnetAtt.py:4,290-292) --
  *   points1               [n_clouds, n, D1] float32 features of the fine points, or NULL with D1 = 0

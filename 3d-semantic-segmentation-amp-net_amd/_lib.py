@@ -373,6 +373,17 @@ def _workspace_args(prefix, workspace):
     return ptr(workspace), ctypes.c_size_t(workspace.numel() * workspace.element_size())
 
 
+def _ragged_clouds(prefix, cloud_off, B, S, label):
+    """The ragged form of a backward (cloud_off given): the tensors hold the packed array as ONE cloud (B = 1) and cloud_off, int32
+    [Q + 1] on the device, says where its Q clouds lie; the S `label` of the call are Q equal shares -> (Q, S // Q)."""
+    _check_tensors(prefix, [("cloud_off", cloud_off, _I32, 1, True)])
+    Q = cloud_off.numel() - 1
+    if B != 1 or Q < 1 or S % Q:
+        raise AmpnetError(f"{prefix}: with cloud_off the tensors hold the packed clouds as one (leading dimension 1, got {B}) and the "
+                          f"{S} {label} are the equal shares of the {Q} clouds of cloud_off {tuple(cloud_off.shape)}")
+    return Q, S // Q
+
+
 def fp_backward_workspace_bytes(D1, D2, B, N, couts):
     """Device bytes fp_backward_f32 needs for points1 [B, N, D1], points2 [B, S, D2] and layers of widths `couts` (include/ampnet_hip.h:
     ampnet_fp_backward_workspace_bytes); a shape outside the kernel's limits is an AmpnetError that names the limit."""
@@ -530,10 +541,12 @@ def sa_msg_forward_f32(xyz, centres, group_idxs, feats, branches, eps, out, work
     check(rc, "ampnet_sa_msg_forward_f32")
 
 
-def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, grads, workspace, arg_out=None):
+def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, grads, workspace, arg_out=None, cloud_off=None):
     """The backward of sa_forward_f32 with the running statistics frozen.  xyz .. eps: the forward's arguments; dout [B, S, cout_last];
     dfeats [B, N, D] written, or None when it is not wanted (always None when feats is None); grads: per layer (dW [cout, cin],
-    dbias [cout], dgamma [cout], dbeta [cout]), written (_grad_table); workspace: sa_backward_workspace_bytes(...) GPU bytes; arg_out: int32 [B, S, cout_last] or None, the row of each group that the max selected."""
+    dbias [cout], dgamma [cout], dbeta [cout]), written (_grad_table); workspace: sa_backward_workspace_bytes(...) GPU bytes; arg_out: int32 [B, S, cout_last] or None, the row of each group that the max selected.
+    cloud_off: int32 [Q + 1] on the device, or None.  Given, the tensors are Q clouds of unequal size packed as one (B = 1, N = total,
+    S = Q centres-per-cloud, global indices) and the call is ampnet_sa_backward_ragged_f32: the same phases, the dfeats gather cloud by cloud."""
     B, N, ld, S, nsample, D = _sa_geometry("sa_backward", xyz, centres, group_idx, feats,
                                            [("dout", dout, _F32, 3, True), ("dfeats", dfeats, _F32, 3, False), ("arg_out", arg_out, _I32, 3, False)])
     _check_grad_of("sa_backward", "dfeats", dfeats, "feats", feats, optional=True)
@@ -541,6 +554,13 @@ def sa_backward_f32(xyz, centres, group_idx, feats, layers, eps, dout, dfeats, g
     _check_cout_last("sa_backward", layers, (B, S), "B, S", dout=dout, arg_out=arg_out)
     gtable = _grad_table("sa_backward", layers, grads)
     ws, ws_bytes = _workspace_args("sa_backward", workspace)
+    if cloud_off is not None:
+        Q, S1 = _ragged_clouds("sa_backward", cloud_off, B, S, "centres")
+        with torch.cuda.device(xyz.device):
+            rc = lib().ampnet_sa_backward_ragged_f32(ptr(xyz), ptr(cloud_off), Q, N, ld, ptr(centres), S1, ptr(group_idx), nsample, ptr(feats), D,
+                                                     table, couts, epss, len(layers), ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ws, ws_bytes,
+                                                     stream_ptr(xyz.device))
+        return check(rc, "ampnet_sa_backward_ragged_f32")
     with torch.cuda.device(xyz.device):
         rc = lib().ampnet_sa_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
                                           len(layers), ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ws, ws_bytes, stream_ptr(xyz.device))
@@ -600,10 +620,12 @@ def sa_train_forward_f32(xyz, centres, group_idx, feats, layers, eps, momentum, 
     check(rc, "ampnet_sa_train_forward_f32")
 
 
-def sa_train_backward_f32(xyz, centres, group_idx, feats, layers, eps, save_mean, save_invstd, dout, dfeats, grads, workspace, arg_out=None):
+def sa_train_backward_f32(xyz, centres, group_idx, feats, layers, eps, save_mean, save_invstd, dout, dfeats, grads, workspace, arg_out=None,
+                          cloud_off=None):
     """The backward of sa_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
     further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dfeats, grads, arg_out as in
-    sa_backward_f32 (dbias is written as zeros); workspace: sa_train_backward_workspace_bytes(...) GPU bytes."""
+    sa_backward_f32 (dbias is written as zeros); workspace: sa_train_backward_workspace_bytes(...) GPU bytes; cloud_off as in
+    sa_backward_f32 (ampnet_sa_train_backward_ragged_f32)."""
     B, N, ld, S, nsample, D = _sa_geometry("sa_train_backward", xyz, centres, group_idx, feats,
                                            _saved_rows(save_mean, save_invstd) + [("dout", dout, _F32, 3, True), ("dfeats", dfeats, _F32, 3, False),
                                                                                   ("arg_out", arg_out, _I32, 3, False)])
@@ -612,6 +634,13 @@ def sa_train_backward_f32(xyz, centres, group_idx, feats, layers, eps, save_mean
     _check_cout_last("sa_train_backward", layers, (B, S), "B, S", dout=dout, arg_out=arg_out)
     gtable = _grad_table("sa_train_backward", layers, grads)
     ws, ws_bytes = _workspace_args("sa_train_backward", workspace)
+    if cloud_off is not None:
+        Q, S1 = _ragged_clouds("sa_train_backward", cloud_off, B, S, "centres")
+        with torch.cuda.device(xyz.device):
+            rc = lib().ampnet_sa_train_backward_ragged_f32(ptr(xyz), ptr(cloud_off), Q, N, ld, ptr(centres), S1, ptr(group_idx), nsample, ptr(feats),
+                                                           D, table, couts, epss, len(layers), ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ws,
+                                                           ws_bytes, stream_ptr(xyz.device))
+        return check(rc, "ampnet_sa_train_backward_ragged_f32")
     with torch.cuda.device(xyz.device):
         rc = lib().ampnet_sa_train_backward_f32(ptr(xyz), B, N, ld, ptr(centres), S, ptr(group_idx), nsample, ptr(feats), D, table, couts, epss,
                                                 len(layers), ptr(dout), ptr(dfeats), gtable, ptr(arg_out), ws, ws_bytes, stream_ptr(xyz.device))
@@ -654,10 +683,13 @@ def _fp_backward_rows(dout, dpoints1, dpoints2):
     return [("dout", dout, _F32, 3, True), ("dpoints1", dpoints1, _F32, 3, False), ("dpoints2", dpoints2, _F32, 3, True)]
 
 
-def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, dpoints2, grads, workspace):
+def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, dpoints2, grads, workspace, cloud_off=None):
     """The backward of fp_forward_f32 with the running statistics frozen.  points1 .. eps: the forward's arguments; dout [B, N, cout_last];
     dpoints1 [B, N, D1] (None exactly when points1 is None) and dpoints2 [B, S, D2]: written; grads as in sa_backward_f32; workspace:
-    fp_backward_workspace_bytes(...) GPU bytes."""
+    fp_backward_workspace_bytes(...) GPU bytes.
+    cloud_off: int32 [Q + 1] on the device, or None.  Given, the tensors are Q fine clouds of unequal size packed as one (B = 1, N = total,
+    S = Q coarse-points-per-cloud, global indices) and the call is ampnet_fp_backward_ragged_f32: the same phases, the dpoints2 gather
+    cloud by cloud."""
     B, N, k, S, D1, D2 = _fp_geometry("fp_backward", points1, points2, idx, dist2, _fp_backward_rows(dout, dpoints1, dpoints2))
     _check_grad_of("fp_backward", "dpoints1", dpoints1, "points1", points1)
     _check_grad_of("fp_backward", "dpoints2", dpoints2, "points2", points2)
@@ -665,6 +697,13 @@ def fp_backward_f32(points1, points2, idx, dist2, layers, eps, dout, dpoints1, d
     _check_cout_last("fp_backward", layers, (B, N), "B, N", dout=dout)
     gtable = _grad_table("fp_backward", layers, grads)
     ws, ws_bytes = _workspace_args("fp_backward", workspace)
+    if cloud_off is not None:
+        Q, S1 = _ragged_clouds("fp_backward", cloud_off, B, S, "coarse points")
+        with torch.cuda.device(points2.device):
+            rc = lib().ampnet_fp_backward_ragged_f32(ptr(points1), D1, ptr(points2), D2, ptr(cloud_off), Q, N, S1, ptr(idx), ptr(dist2), k, table,
+                                                     couts, epss, len(layers), ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws, ws_bytes,
+                                                     stream_ptr(points2.device))
+        return check(rc, "ampnet_fp_backward_ragged_f32")
     with torch.cuda.device(points2.device):
         rc = lib().ampnet_fp_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss, len(layers),
                                           ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws, ws_bytes, stream_ptr(points2.device))
@@ -690,10 +729,12 @@ def fp_train_forward_f32(points1, points2, idx, dist2, layers, eps, momentum, ou
     check(rc, "ampnet_fp_train_forward_f32")
 
 
-def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, save_invstd, dout, dpoints1, dpoints2, grads, workspace):
+def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, save_invstd, dout, dpoints1, dpoints2, grads, workspace,
+                          cloud_off=None):
     """The backward of fp_train_forward_f32 through the batch statistics.  layers: per layer (weight, conv bias, BatchNorm weight, bias) --
     further entries are ignored; save_mean / save_invstd: what the forward wrote (never recomputed); dout, dpoints1, dpoints2, grads as in
-    fp_backward_f32 (dbias is written as zeros); workspace: fp_train_backward_workspace_bytes(...) GPU bytes."""
+    fp_backward_f32 (dbias is written as zeros); workspace: fp_train_backward_workspace_bytes(...) GPU bytes; cloud_off as in
+    fp_backward_f32 (ampnet_fp_train_backward_ragged_f32)."""
     B, N, k, S, D1, D2 = _fp_geometry("fp_train_backward", points1, points2, idx, dist2,
                                       _saved_rows(save_mean, save_invstd) + _fp_backward_rows(dout, dpoints1, dpoints2))
     _check_grad_of("fp_train_backward", "dpoints1", dpoints1, "points1", points1)
@@ -702,6 +743,13 @@ def fp_train_backward_f32(points1, points2, idx, dist2, layers, eps, save_mean, 
     _check_cout_last("fp_train_backward", layers, (B, N), "B, N", dout=dout)
     gtable = _grad_table("fp_train_backward", layers, grads)
     ws, ws_bytes = _workspace_args("fp_train_backward", workspace)
+    if cloud_off is not None:
+        Q, S1 = _ragged_clouds("fp_train_backward", cloud_off, B, S, "coarse points")
+        with torch.cuda.device(points2.device):
+            rc = lib().ampnet_fp_train_backward_ragged_f32(ptr(points1), D1, ptr(points2), D2, ptr(cloud_off), Q, N, S1, ptr(idx), ptr(dist2), k,
+                                                           table, couts, epss, len(layers), ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws,
+                                                           ws_bytes, stream_ptr(points2.device))
+        return check(rc, "ampnet_fp_train_backward_ragged_f32")
     with torch.cuda.device(points2.device):
         rc = lib().ampnet_fp_train_backward_f32(ptr(points1), D1, ptr(points2), D2, B, N, S, ptr(idx), ptr(dist2), k, table, couts, epss,
                                                 len(layers), ptr(dout), ptr(dpoints1), ptr(dpoints2), gtable, ws, ws_bytes,

@@ -213,19 +213,29 @@ def _param_grads(tensors, grads, per, need_grad, first):
     return tuple(ret)
 
 
+_ragged_note = """cloud_off of fp_apply, fp_train_apply, sa_apply and sa_train_apply (pointnet2_utils' _forward_ragged).  None: B clouds of one size.
+An int32 [Q + 1] device table (utils.RaggedLayout.off): the tensors hold Q clouds of UNEQUAL size packed back to back as ONE cloud
+(leading dimension 1, N = total) with the Q * S centres or coarse points behind one another and GLOBAL indices, as the ragged searches
+write them.  The forwards need nothing else -- no row of theirs mixes with another, and batch statistics over all rows of the call are
+the right statistics -- and run unchanged; the backward goes through the ampnet_*_backward_ragged_f32 entry points, whose last gather
+scans a point's own cloud and not the whole array (include/ampnet_hip.h)."""
+
+
 class _FpFn(torch.autograd.Function):
     """One fused feature-propagation layer with BatchNorm's running statistics frozen (pointnet2_utils.PointNetFeaturePropagation with
     grad=True).  tensors: per layer conv weight [out, in, 1], conv bias, BatchNorm weight, bias, running_mean, running_var.  The forward
     is the eval forward, unchanged, and keeps no activation: the backward kernel recomputes them (csrc/feature_propagation_bwd.hip).
-    Exact fp32 whatever the matrix precision is, so there is no precision scope to carry over."""
+    Exact fp32 whatever the matrix precision is, so there is no precision scope to carry over.
+    cloud_off: None, or the int32 [Q + 1] device table of Q fine clouds of unequal size that p1 .. dist2 hold packed as ONE cloud with global
+    indices (_ragged_note): the forward is unchanged and the backward gathers dp2 cloud by cloud."""
 
     @staticmethod
-    def forward(ctx, eps, fold_ws, p1, p2, idx, dist2, *tensors):
+    def forward(ctx, eps, cloud_off, fold_ws, p1, p2, idx, dist2, *tensors):
         layers = _mlp_layers(tensors, 6)
         out = torch.empty((p2.shape[0], idx.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=p2.device)
         _lib.fp_forward_f32(p1, p2, idx, dist2, layers, eps, out, fold_ws)
         ctx.save_for_backward(p1, p2, idx, dist2, *tensors)        # (inputs only: see the note in _EncoderFn.forward)
-        ctx.eps = eps
+        ctx.eps, ctx.cloud_off = eps, cloud_off
         return out
 
     @staticmethod
@@ -236,16 +246,18 @@ class _FpFn(torch.autograd.Function):
         dp2 = torch.empty_like(p2)
         grads = _alloc_grads(layers)
         need = _lib.fp_backward_workspace_bytes(_width(p1), p2.shape[2], p2.shape[0], idx.shape[1], _couts(layers))
-        _lib.fp_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, dout.contiguous().float(), dp1, dp2, grads, _ws(need, p2.device))
+        _lib.fp_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, dout.contiguous().float(), dp1, dp2, grads, _ws(need, p2.device),
+                             cloud_off=ctx.cloud_off)
         need_grad = ctx.needs_input_grad
-        return (None, None, dp1 if need_grad[2] else None, dp2 if need_grad[3] else None, None, None) \
-            + _param_grads(tensors, grads, 6, need_grad, 6)
+        return (None, None, None, dp1 if need_grad[3] else None, dp2 if need_grad[4] else None, None, None) \
+            + _param_grads(tensors, grads, 6, need_grad, 7)
 
 
-def fp_apply(module, p1, p2, idx, dist2, fold_ws):
+def fp_apply(module, p1, p2, idx, dist2, fold_ws, cloud_off=None):
     """Grad-mode forward of a PointNetFeaturePropagation block on point-major rows: p1 [B, N, D1] or None, p2 [B, S, D2], idx / dist2
-    [B, N, k] from utils.three_nn -> [B, N, mlp[-1]] with a graph to p1, p2 and the block's conv and BatchNorm affine parameters."""
-    return _FpFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, p1, p2, idx, dist2, *_block_tensors(module))
+    [B, N, k] from utils.three_nn -> [B, N, mlp[-1]] with a graph to p1, p2 and the block's conv and BatchNorm affine parameters.
+    cloud_off: _ragged_note."""
+    return _FpFn.apply([bn.eps for bn in module.mlp_bns], cloud_off, fold_ws, p1, p2, idx, dist2, *_block_tensors(module))
 
 
 class _FpTrainFn(torch.autograd.Function):
@@ -256,11 +268,11 @@ class _FpTrainFn(torch.autograd.Function):
     precision is (csrc/feature_propagation_train.hip)."""
 
     @staticmethod
-    def forward(ctx, eps, momentum, stats, p1, p2, idx, dist2, *tensors):
+    def forward(ctx, eps, cloud_off, momentum, stats, p1, p2, idx, dist2, *tensors):
         layers = [layer + tuple(st) for layer, st in zip(_mlp_layers(tensors, 4), stats)]
         out, save_mean, save_invstd = fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum)
         ctx.save_for_backward(p1, p2, idx, dist2, save_mean, save_invstd, *tensors)
-        ctx.eps = eps
+        ctx.eps, ctx.cloud_off = eps, cloud_off
         return out
 
     @staticmethod
@@ -272,10 +284,10 @@ class _FpTrainFn(torch.autograd.Function):
         grads = _alloc_grads(layers)
         need = _lib.fp_train_backward_workspace_bytes(_width(p1), p2.shape[2], p2.shape[0], idx.shape[1], _couts(layers))
         _lib.fp_train_backward_f32(p1, p2, idx, dist2, layers, ctx.eps, save_mean, save_invstd, dout.contiguous().float(), dp1, dp2, grads,
-                                   _ws(need, p2.device))
+                                   _ws(need, p2.device), cloud_off=ctx.cloud_off)
         need_grad = ctx.needs_input_grad
-        return (None, None, None, dp1 if need_grad[3] else None, dp2 if need_grad[4] else None, None, None) \
-            + _param_grads(tensors, grads, 4, need_grad, 7)                         # (dbias is zeros)
+        return (None, None, None, None, dp1 if need_grad[4] else None, dp2 if need_grad[5] else None, None, None) \
+            + _param_grads(tensors, grads, 4, need_grad, 8)                         # (dbias is zeros)
 
 
 def fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum):
@@ -288,12 +300,13 @@ def fp_train_forward(p1, p2, idx, dist2, layers, eps, momentum):
     return out, save_mean, save_invstd
 
 
-def fp_train_apply(module, p1, p2, idx, dist2, momentum):
+def fp_train_apply(module, p1, p2, idx, dist2, momentum, cloud_off=None):
     """Grad-mode, train-mode forward of a PointNetFeaturePropagation block on point-major rows (as fp_apply): batch statistics, the
     module's running statistics updated in place, a graph to p1, p2 and the block's conv and BatchNorm affine parameters (the conv bias
-    gets zeros: it has no effect on a batch-normalised output)."""
+    gets zeros: it has no effect on a batch-normalised output).  cloud_off: _ragged_note."""
     stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
-    return _FpTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, p1, p2, idx, dist2, *_block_tensors(module, stats=False))
+    return _FpTrainFn.apply([bn.eps for bn in module.mlp_bns], cloud_off, momentum, stats, p1, p2, idx, dist2,
+                            *_block_tensors(module, stats=False))
 
 
 class _SaFn(torch.autograd.Function):
@@ -303,12 +316,12 @@ class _SaFn(torch.autograd.Function):
     (csrc/set_abstraction_bwd.hip).  Exact fp32 whatever the matrix precision is, so there is no precision scope to carry over."""
 
     @staticmethod
-    def forward(ctx, eps, fold_ws, x, centres, group_idx, feats, *tensors):
+    def forward(ctx, eps, cloud_off, fold_ws, x, centres, group_idx, feats, *tensors):
         layers = _mlp_layers(tensors, 6)
         out = torch.empty((x.shape[0], centres.shape[1], layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
         _lib.sa_forward_f32(x, centres, group_idx, feats, layers, eps, out, fold_ws)
         ctx.save_for_backward(x, centres, group_idx, feats, *tensors)        # (inputs only: see the note in _EncoderFn.forward)
-        ctx.eps = eps
+        ctx.eps, ctx.cloud_off = eps, cloud_off
         return out
 
     @staticmethod
@@ -316,19 +329,19 @@ class _SaFn(torch.autograd.Function):
         x, centres, group_idx, feats, *tensors = ctx.saved_tensors
         layers = _mlp_layers(tensors, 6)
         need_grad = ctx.needs_input_grad
-        dfeats = torch.empty_like(feats) if feats is not None and need_grad[5] else None
+        dfeats = torch.empty_like(feats) if feats is not None and need_grad[6] else None
         grads = _alloc_grads(layers)
         need = _lib.sa_backward_workspace_bytes(_width(feats), x.shape[0], centres.shape[1], group_idx.shape[2], _couts(layers))
         _lib.sa_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, dout.contiguous().float(), dfeats, grads, _ws(need, x.device),
-                             arg_out=None)
-        return (None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 6, need_grad, 6)
+                             arg_out=None, cloud_off=ctx.cloud_off)
+        return (None, None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 6, need_grad, 7)
 
 
-def sa_apply(module, x, centres, group_idx, feats, fold_ws, w0=None):
+def sa_apply(module, x, centres, group_idx, feats, fold_ws, w0=None, cloud_off=None):
     """Grad-mode forward of a PointNetSetAbstraction block on point-major rows: x [B, N, 3], centres [B, S] and group_idx [B, S, nsample]
     int32, feats [B, N, D] or None -> [B, S, mlp[-1]] with a graph to feats and the block's conv and BatchNorm affine parameters.
-    w0: as in _block_tensors."""
-    return _SaFn.apply([bn.eps for bn in module.mlp_bns], fold_ws, x, centres, group_idx, feats, *_block_tensors(module, w0=w0))
+    w0: as in _block_tensors.  cloud_off: _ragged_note."""
+    return _SaFn.apply([bn.eps for bn in module.mlp_bns], cloud_off, fold_ws, x, centres, group_idx, feats, *_block_tensors(module, w0=w0))
 
 
 class _SaAllFn(torch.autograd.Function):
@@ -380,11 +393,11 @@ class _SaTrainFn(torch.autograd.Function):
     the matrix precision is (csrc/set_abstraction_train.hip)."""
 
     @staticmethod
-    def forward(ctx, eps, momentum, stats, x, centres, group_idx, feats, *tensors):
+    def forward(ctx, eps, cloud_off, momentum, stats, x, centres, group_idx, feats, *tensors):
         layers = [layer + tuple(st) for layer, st in zip(_mlp_layers(tensors, 4), stats)]
         out, save_mean, save_invstd = sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum)
         ctx.save_for_backward(x, centres, group_idx, feats, save_mean, save_invstd, *tensors)
-        ctx.eps = eps
+        ctx.eps, ctx.cloud_off = eps, cloud_off
         return out
 
     @staticmethod
@@ -392,12 +405,12 @@ class _SaTrainFn(torch.autograd.Function):
         x, centres, group_idx, feats, save_mean, save_invstd, *tensors = ctx.saved_tensors
         layers = _mlp_layers(tensors, 4)
         need_grad = ctx.needs_input_grad
-        dfeats = torch.empty_like(feats) if feats is not None and need_grad[6] else None
+        dfeats = torch.empty_like(feats) if feats is not None and need_grad[7] else None
         grads = _alloc_grads(layers)
         need = _lib.sa_train_backward_workspace_bytes(_width(feats), x.shape[0], centres.shape[1], group_idx.shape[2], _couts(layers))
         _lib.sa_train_backward_f32(x, centres, group_idx, feats, layers, ctx.eps, save_mean, save_invstd, dout.contiguous().float(), dfeats,
-                                   grads, _ws(need, x.device), arg_out=None)
-        return (None, None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 4, need_grad, 7)      # (dbias is zeros)
+                                   grads, _ws(need, x.device), arg_out=None, cloud_off=ctx.cloud_off)
+        return (None, None, None, None, None, None, None, dfeats) + _param_grads(tensors, grads, 4, need_grad, 8)      # (dbias is zeros)
 
 
 def sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum):
@@ -410,12 +423,13 @@ def sa_train_forward(x, centres, group_idx, feats, layers, eps, momentum):
     return out, save_mean, save_invstd
 
 
-def sa_train_apply(module, x, centres, group_idx, feats, momentum, w0=None):
+def sa_train_apply(module, x, centres, group_idx, feats, momentum, w0=None, cloud_off=None):
     """Grad-mode, train-mode forward of a PointNetSetAbstraction block on point-major rows (as sa_apply): batch statistics over all
     B * npoint * nsample rows, the module's running statistics updated in place, a graph to feats and the block's conv and BatchNorm affine
-    parameters (the conv bias gets zeros: it has no effect on a batch-normalised output).  w0: as in _block_tensors."""
+    parameters (the conv bias gets zeros: it has no effect on a batch-normalised output).  w0: as in _block_tensors.  cloud_off:
+    _ragged_note."""
     stats = [(bn.running_mean, bn.running_var) for bn in module.mlp_bns]
-    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], momentum, stats, x, centres, group_idx, feats,
+    return _SaTrainFn.apply([bn.eps for bn in module.mlp_bns], cloud_off, momentum, stats, x, centres, group_idx, feats,
                             *_block_tensors(module, stats=False, w0=w0))
 
 

@@ -154,6 +154,62 @@ int fp_scatter_launch(const float *dx0, int D2, int n_clouds, int n, int s, cons
     return check_launch("fp_scatter_kernel");
 }
 
+// fp_scatter_kernel for fine clouds of UNEQUAL size packed back to back (ampnet_fp_backward_ragged_f32): one wave per coarse point; global
+// coarse point j = blockIdx.x belongs to cloud b = j / s and scans the neighbour entries of that cloud's fine rows
+// [cloud_off[b], cloud_off[b + 1]) alone, not those of the whole array.  idx holds GLOBAL coarse indices and is clamped into the cloud's own
+// range [b s, (b + 1) s - 1]; dx0's rows and dist2 are addressed by the global fine row.  The hits are walked in ascending (i, k) order with
+// fp_scatter_kernel's own statements, so cloud by cloud the result is what that kernel writes for the cloud alone, bit for bit (where a
+// 64-entry step begins does not enter the order).  The table's rows are clamped into [0, total]: a wrong table cannot read past the arrays.
+__global__ __launch_bounds__(64) void fp_scatter_ragged_kernel(const float *__restrict__ dx0, int D2, const int32_t *__restrict__ cloud_off,
+                                                              int total, int s, const int32_t *__restrict__ idx,
+                                                              const float *__restrict__ dist2, int k, float *__restrict__ dpoints2)
+{
+    const int lane = threadIdx.x;
+    const int cloud_i = blockIdx.x / s, j = blockIdx.x;
+    const int lo = cloud_i * s, hi = lo + s - 1;
+    const int row0 = min(max(cloud_off[cloud_i], 0), total), row1 = min(max(cloud_off[cloud_i + 1], row0), total);
+    const long long e_end = (long long)row1 * k;
+    float acc[AMPNET_FP_MAX_CIN / 64];
+#pragma unroll
+    for (int u = 0; u < AMPNET_FP_MAX_CIN / 64; ++u) acc[u] = 0.0f;
+    for (long long e0 = (long long)row0 * k; e0 < e_end; e0 += 64) {
+        const long long e = e0 + lane;
+        const bool hit = e < e_end && min(max(idx[e], lo), hi) == j;
+        int i = 0;
+        float w = 0.0f;
+        if (hit) {
+            i = (int)(e / k);
+            const int q = (int)(e - (long long)i * k);
+            float wk[3];
+            fp_interp_weights(dist2 + (size_t)i * k, k, wk);
+            w = q == 0 ? wk[0] : q == 1 ? wk[1] : wk[2];
+        }
+        unsigned long long mask = __ballot(hit);
+        while (mask) {                            // wave-uniform: every lane walks the hits in ascending entry order
+            const int src = __ffsll(mask) - 1;
+            mask &= mask - 1;
+            const int ib = __shfl(i, src);
+            const float wb = __shfl(w, src);
+            const float *row = dx0 + (size_t)ib * D2;
+#pragma unroll
+            for (int u = 0; u < AMPNET_FP_MAX_CIN / 64; ++u)
+                if (lane + 64 * u < D2) acc[u] = fmaf(wb, row[lane + 64 * u], acc[u]);
+        }
+    }
+    float *dst = dpoints2 + (size_t)blockIdx.x * D2;
+#pragma unroll
+    for (int u = 0; u < AMPNET_FP_MAX_CIN / 64; ++u)
+        if (lane + 64 * u < D2) dst[lane + 64 * u] = acc[u];
+}
+
+int fp_gather_launch(const float *dx0, int D2, const BwdClouds &c, const int32_t *idx, const float *dist2, int k, float *dpoints2, hipStream_t st)
+{
+    if (!c.cloud_off) return fp_scatter_launch(dx0, D2, c.n_clouds, c.n, c.s, idx, dist2, k, dpoints2, st);
+    hipLaunchKernelGGL(fp_scatter_ragged_kernel, dim3(c.q * c.s_cloud), dim3(64), 0, st, dx0, D2, c.cloud_off, c.n, c.s_cloud, idx, dist2, k,
+                       dpoints2);
+    return check_launch("fp_scatter_ragged_kernel");
+}
+
 int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, const int *cout_host, int L, FpBwdShape &sh)
 {
     AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
@@ -183,13 +239,16 @@ extern "C" size_t ampnet_fp_backward_workspace_bytes(int D1, int D2, int n_cloud
     return sh.floats * sizeof(float);
 }
 
-extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
-                                      const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host,
-                                      int L, const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
-                                      size_t workspace_bytes, void *stream)
+namespace ampnet {
+
+// The body of ampnet_fp_backward_f32 and ampnet_fp_backward_ragged_f32: every phase runs on c's (n_clouds, n, s) -- the packed array as ONE
+// cloud for the ragged entry point -- and the dpoints2 gather alone looks at c.cloud_off (fp_gather_launch).
+static int fp_backward_run(const char *what, const float *points1, int D1, const float *points2, int D2, const BwdClouds &c, const int32_t *idx,
+                           const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                           const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
+                           size_t workspace_bytes, void *stream)
 {
-    using namespace ampnet;
-    const char *what = "ampnet_fp_backward_f32";
+    const int n_clouds = c.n_clouds, n = c.n, s = c.s;
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(points2 && idx && dist2 && params_host && cout_host && eps_host && dout && dpoints2 && grads_host, "%s: null pointer", what);
     AMPNET_REQUIRE(s >= 1, "%s: bad shape s=%d", what, s);
@@ -250,7 +309,33 @@ extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float 
         rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, wpart, grads_host[4 * l], st);
         if (rc != AMPNET_OK) return rc;
     }
-    rc = fp_scatter_launch(b.dx0, D2, n_clouds, n, s, idx, dist2, k, dpoints2, st);
+    rc = fp_gather_launch(b.dx0, D2, c, idx, dist2, k, dpoints2, st);
     if (rc != AMPNET_OK) return rc;
     return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);
+}
+
+}  // namespace ampnet
+
+extern "C" int ampnet_fp_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s, const int32_t *idx,
+                                      const float *dist2, int k, const float *const *params_host, const int *cout_host, const float *eps_host,
+                                      int L, const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    const ampnet::BwdClouds c = {n_clouds, n, s, nullptr, 0, 0};
+    return ampnet::fp_backward_run("ampnet_fp_backward_f32", points1, D1, points2, D2, c, idx, dist2, k, params_host, cout_host, eps_host, L, dout,
+                                   dpoints1, dpoints2, grads_host, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ampnet_fp_backward_ragged_f32(const float *points1, int D1, const float *points2, int D2, const int32_t *cloud_off, int n_clouds,
+                                             int total, int s, const int32_t *idx, const float *dist2, int k, const float *const *params_host,
+                                             const int *cout_host, const float *eps_host, int L, const float *dout, float *dpoints1,
+                                             float *dpoints2, float *const *grads_host, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *what = "ampnet_fp_backward_ragged_f32";
+    ampnet::BwdClouds c;
+    int rc = ampnet::bwd_clouds_ragged(what, cloud_off, n_clouds, total, s, c);
+    if (rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE(k <= s, "%s: k=%d must be <= s=%d, the coarse points of ONE cloud", what, k, s);
+    return ampnet::fp_backward_run(what, points1, D1, points2, D2, c, idx, dist2, k, params_host, cout_host, eps_host, L, dout, dpoints1, dpoints2,
+                                   grads_host, workspace, workspace_bytes, stream);
 }

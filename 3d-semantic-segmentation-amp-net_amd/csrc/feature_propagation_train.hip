@@ -32,7 +32,7 @@
 //                 half 1, tiles ascending).
 //   fpt_bwd_finalize_kernel     (bn_train.hip) a wave per channel adds the partial rows and writes dbeta, dgamma = invstd (G - mu dbeta),
 //       dbias = 0 and the two coefficients dbeta / M and dgamma invstd / M of the next phase.
-//   fpb_wgrad_launch, fp_scatter_launch   dW_l = dz_l^T x_l and dpoints2, exactly the eval backward's.
+//   fpb_wgrad_launch, fp_gather_launch    dW_l = dz_l^T x_l and dpoints2, exactly the eval backward's (the gather ragged when the clouds are).
 //   A phase holds two tiles of the widest layer input (at most 131 KB), so the eval backward's shared-space special case is not needed.
 //   The statistics, part A and part B of a tile are bn_train.h's (bnt_tile_stats, bnt_form_dz, bnt_form_dy), shared with the set
 //   abstraction; this file keeps what is feature propagation's own: the row builder, the tiling and the entry points.
@@ -280,13 +280,16 @@ extern "C" size_t ampnet_fp_train_backward_workspace_bytes(int D1, int D2, int n
     return floats * sizeof(float);
 }
 
-extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s,
-                                            const int32_t *idx, const float *dist2, int k, const float *const *params_host,
-                                            const int *cout_host, const float *eps_host, int L, const float *dout, float *dpoints1,
-                                            float *dpoints2, float *const *grads_host, void *workspace, size_t workspace_bytes, void *stream)
+namespace ampnet {
+
+// The body of ampnet_fp_train_backward_f32 and ampnet_fp_train_backward_ragged_f32 (fp_bwd_tiles.h, BwdClouds): the phases and the statistics
+// over c's rows as one batch, the dpoints2 gather alone ragged.
+static int fp_train_backward_run(const char *what, const float *points1, int D1, const float *points2, int D2, const BwdClouds &c,
+                                 const int32_t *idx, const float *dist2, int k, const float *const *params_host, const int *cout_host,
+                                 const float *eps_host, int L, const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host,
+                                 void *workspace, size_t workspace_bytes, void *stream)
 {
-    using namespace ampnet;
-    const char *what = "ampnet_fp_train_backward_f32";
+    const int n_clouds = c.n_clouds, n = c.n, s = c.s;
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(points2 && idx && dist2 && params_host && cout_host && eps_host && dout && dpoints2 && grads_host, "%s: null pointer", what);
     AMPNET_REQUIRE(s >= 1, "%s: bad shape s=%d", what, s);
@@ -328,5 +331,32 @@ extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const 
         rc = fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, wpart, grads_host[4 * l], st);
         if (rc != AMPNET_OK) return rc;
     }
-    return fp_scatter_launch(b.dx0, D2, n_clouds, n, s, idx, dist2, k, dpoints2, st);
+    return fp_gather_launch(b.dx0, D2, c, idx, dist2, k, dpoints2, st);
+}
+
+}  // namespace ampnet
+
+extern "C" int ampnet_fp_train_backward_f32(const float *points1, int D1, const float *points2, int D2, int n_clouds, int n, int s,
+                                            const int32_t *idx, const float *dist2, int k, const float *const *params_host,
+                                            const int *cout_host, const float *eps_host, int L, const float *dout, float *dpoints1,
+                                            float *dpoints2, float *const *grads_host, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const ampnet::BwdClouds c = {n_clouds, n, s, nullptr, 0, 0};
+    return ampnet::fp_train_backward_run("ampnet_fp_train_backward_f32", points1, D1, points2, D2, c, idx, dist2, k, params_host, cout_host,
+                                         eps_host, L, dout, dpoints1, dpoints2, grads_host, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ampnet_fp_train_backward_ragged_f32(const float *points1, int D1, const float *points2, int D2, const int32_t *cloud_off,
+                                                   int n_clouds, int total, int s, const int32_t *idx, const float *dist2, int k,
+                                                   const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                                                   const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host,
+                                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    const char *what = "ampnet_fp_train_backward_ragged_f32";
+    ampnet::BwdClouds c;
+    int rc = ampnet::bwd_clouds_ragged(what, cloud_off, n_clouds, total, s, c);
+    if (rc != AMPNET_OK) return rc;
+    AMPNET_REQUIRE(k <= s, "%s: k=%d must be <= s=%d, the coarse points of ONE cloud", what, k, s);
+    return ampnet::fp_train_backward_run(what, points1, D1, points2, D2, c, idx, dist2, k, params_host, cout_host, eps_host, L, dout, dpoints1,
+                                         dpoints2, grads_host, workspace, workspace_bytes, stream);
 }

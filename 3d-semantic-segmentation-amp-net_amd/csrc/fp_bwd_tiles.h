@@ -21,4 +21,8 @@ int fpb_shape(const char *what, int D1, int D2, int n_clouds, int n, const int *
 int fp_scatter_launch(const float *dx0, int D2, int n_clouds, int n, int s, const int32_t *idx, const float *dist2, int k, float *dpoints2,
                       hipStream_t st);
 
+// the dpoints2 gather of c (mlp_bwd.h; s: coarse points) on `st`: fp_scatter_launch, or fp_scatter_ragged_kernel, which scans a coarse
+// point's own cloud alone
+int fp_gather_launch(const float *dx0, int D2, const BwdClouds &c, const int32_t *idx, const float *dist2, int k, float *dpoints2, hipStream_t st);
+
 }  // namespace ampnet

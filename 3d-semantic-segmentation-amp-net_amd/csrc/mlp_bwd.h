@@ -35,6 +35,18 @@ int fpb_wgrad_launch(const float *dz, int cout, const float *xs, int cin, int ld
 int fpb_finalize_launch(const MlpPlan &p, const MlpFold &f, const FpBwdFin &g, const float *fold, const float *parts, int n_parts, int sum_c,
                         hipStream_t st);
 
+// The clouds of a backward.  Uniform: n_clouds clouds of n points and s centres (set abstraction) or coarse points (feature propagation),
+// cloud_off null.  Ragged (bwd_clouds_ragged): q clouds of unequal size packed back to back, cloud b being the rows cloud_off[b] ..
+// cloud_off[b + 1] (a device table), each with s_cloud centres or coarse points; every phase but the last gather takes the packed array as
+// ONE cloud: n_clouds = 1, n = total, s = q s_cloud.
+struct BwdClouds {
+    int n_clouds, n, s;
+    const int32_t *cloud_off;
+    int q, s_cloud;
+};
+// checks the ragged shape (`what` opens every message) and fills c
+int bwd_clouds_ragged(const char *what, const int32_t *cloud_off, int n_clouds, int total, int s, BwdClouds &c);
+
 // The part of the workspace every backward lays out the same way (float offsets, each a multiple of 64): the workgroups' partial rows, per
 // layer its input rows x_l [M][ldxs_l] and dz_l [M][cout_l], the dx_0 rows the gather reads, and the split-K partials of dW.
 struct MlpBwdLayout {

@@ -125,4 +125,13 @@ int fpb_finalize_launch(const MlpPlan &p, const MlpFold &f, const FpBwdFin &g, c
     return check_launch("fp_bwd_finalize_kernel");
 }
 
+int bwd_clouds_ragged(const char *what, const int32_t *cloud_off, int n_clouds, int total, int s, BwdClouds &c)
+{
+    AMPNET_REQUIRE(cloud_off, "%s: null cloud_off", what);
+    AMPNET_REQUIRE(n_clouds >= 1 && total >= 1 && s >= 1, "%s: bad shape n_clouds=%d total=%d s=%d", what, n_clouds, total, s);
+    AMPNET_REQUIRE((long long)n_clouds * s <= 0x7fffffffLL, "%s: n_clouds * s = %lld exceed 2^31 - 1", what, (long long)n_clouds * s);
+    c = {1, total, n_clouds * s, cloud_off, n_clouds, s};
+    return AMPNET_OK;
+}
+
 }  // namespace ampnet

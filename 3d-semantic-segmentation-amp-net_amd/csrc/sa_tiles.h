@@ -128,4 +128,8 @@ int sa_forward_launch(const char *what, const MlpPlan &p, int lds, const float *
 // sa_dfeats_kernel (set_abstraction_bwd.hip) on `st`: dfeats [n_clouds, n, D] from the dx_0 rows [n_clouds s nsample][D] as an ordered gather
 int sa_dfeats_launch(const float *dx0, int D, int n_clouds, int n, int s, int nsample, const int32_t *group_idx, float *dfeats, hipStream_t st);
 
+// the dfeats gather of c (mlp_bwd.h; s: centres) on `st`: sa_dfeats_launch, or sa_dfeats_ragged_kernel, which scans the groups of a point's
+// own cloud alone
+int sa_gather_launch(const float *dx0, int D, const BwdClouds &c, int nsample, const int32_t *group_idx, float *dfeats, hipStream_t st);
+
 }  // namespace ampnet

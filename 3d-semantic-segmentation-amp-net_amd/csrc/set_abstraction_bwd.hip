@@ -226,6 +226,51 @@ __global__ __launch_bounds__(64) void sa_dfeats_kernel(const float *__restrict__
         if (lane + 64 * u < D) dst[lane + 64 * u] = acc[u];
 }
 
+// sa_dfeats_kernel for clouds of UNEQUAL size packed back to back (ampnet_sa_backward_ragged_f32): one wave per point j = blockIdx.x of the
+// packed array.  Its cloud b -- cloud_off[b] <= j < cloud_off[b + 1], a binary search over the table, wave-uniform -- has the centres
+// [b s, (b + 1) s), and the wave scans the s nsample group entries of those centres alone, not those of the whole array.  The entries are
+// GLOBAL point indices and are clamped into the cloud's own rows; the hits are added in ascending entry order with sa_dfeats_kernel's own
+// statements, so cloud by cloud the result is what that kernel writes for the cloud alone, bit for bit.  b stays in [0, n_clouds - 1]
+// whatever the table holds, so nothing is read past group_idx or dx0.
+__global__ __launch_bounds__(64) void sa_dfeats_ragged_kernel(const float *__restrict__ dx0, int D, const int32_t *__restrict__ cloud_off,
+                                                             int n_clouds, int s, int nsample, const int32_t *__restrict__ group_idx,
+                                                             float *__restrict__ dfeats)
+{
+    const int lane = threadIdx.x;
+    const int j = blockIdx.x;
+    int cloud_i = 0, above = n_clouds;
+    while (above - cloud_i > 1) {                 // the last cloud whose first row is <= j
+        const int mid = (cloud_i + above) >> 1;
+        if (cloud_off[mid] <= j) cloud_i = mid;
+        else above = mid;
+    }
+    const int lo = cloud_off[cloud_i], hi = cloud_off[cloud_i + 1] - 1;
+    const long long total = (long long)s * nsample;
+    const int32_t *ic = group_idx + (size_t)cloud_i * total;
+    const float *gx = dx0 + (size_t)cloud_i * total * D;
+    constexpr int U = (AMPNET_SA_MAX_CIN + 63) / 64;
+    float acc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] = 0.0f;
+    for (long long e0 = 0; e0 < total; e0 += 64) {
+        const long long e = e0 + lane;
+        const bool hit = e < total && min(max(ic[e], lo), hi) == j;
+        unsigned long long mask = __ballot(hit);
+        while (mask) {                            // wave-uniform: every lane walks the hits in ascending entry order
+            const int src = __ffsll(mask) - 1;
+            mask &= mask - 1;
+            const float *row = gx + (size_t)(e0 + src) * D;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (lane + 64 * u < D) acc[u] += row[lane + 64 * u];
+        }
+    }
+    float *dst = dfeats + (size_t)blockIdx.x * D;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (lane + 64 * u < D) dst[lane + 64 * u] = acc[u];
+}
+
 int sab_shape(const char *what, int D, int n_clouds, int s, int nsample, const int *cout_host, int L, SaBwdShape &sh)
 {
     AMPNET_REQUIRE(cout_host, "%s: null pointer", what);
@@ -257,6 +302,13 @@ int sa_dfeats_launch(const float *dx0, int D, int n_clouds, int n, int s, int ns
     return check_launch("sa_dfeats_kernel");
 }
 
+int sa_gather_launch(const float *dx0, int D, const BwdClouds &c, int nsample, const int32_t *group_idx, float *dfeats, hipStream_t st)
+{
+    if (!c.cloud_off) return sa_dfeats_launch(dx0, D, c.n_clouds, c.n, c.s, nsample, group_idx, dfeats, st);
+    hipLaunchKernelGGL(sa_dfeats_ragged_kernel, dim3(c.n), dim3(64), 0, st, dx0, D, c.cloud_off, c.q, c.s_cloud, nsample, group_idx, dfeats);
+    return check_launch("sa_dfeats_ragged_kernel");
+}
+
 }  // namespace ampnet
 
 extern "C" size_t ampnet_sa_backward_workspace_bytes(int D, int n_clouds, int s, int nsample, const int *cout_host, int L)
@@ -267,13 +319,16 @@ extern "C" size_t ampnet_sa_backward_workspace_bytes(int D, int n_clouds, int s,
     return sh.floats * sizeof(float);
 }
 
-extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
-                                      int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
-                                      const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host,
-                                      int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream)
+namespace ampnet {
+
+// The body of ampnet_sa_backward_f32 and ampnet_sa_backward_ragged_f32: every phase runs on c's (n_clouds, n, s) -- the packed array as ONE
+// cloud for the ragged entry point -- and the dfeats gather alone looks at c.cloud_off (sa_gather_launch).
+static int sa_backward_run(const char *what, const float *xyz, const BwdClouds &c, int ld, const int32_t *centres, const int32_t *group_idx,
+                           int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                           const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
+                           void *workspace, size_t workspace_bytes, void *stream)
 {
-    using namespace ampnet;
-    const char *what = "ampnet_sa_backward_f32";
+    const int n_clouds = c.n_clouds, n = c.n, s = c.s;
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && dout && grads_host, "%s: null pointer", what);
     SaBwdShape sh;
@@ -315,7 +370,32 @@ extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int
                                     grads_host[4 * l], st));
     }
     if (dfeats) {
-        AMPNET_TRY(sa_dfeats_launch(b.dx0, D, n_clouds, n, s, nsample, group_idx, dfeats, st));
+        AMPNET_TRY(sa_gather_launch(b.dx0, D, c, nsample, group_idx, dfeats, st));
     }
     return fpb_finalize_launch(p, f, g, ws, b.parts, sh.grid, sh.sum_c, st);
+}
+
+}  // namespace ampnet
+
+extern "C" int ampnet_sa_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s, const int32_t *group_idx,
+                                      int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                                      const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host,
+                                      int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const ampnet::BwdClouds c = {n_clouds, n, s, nullptr, 0, 0};
+    return ampnet::sa_backward_run("ampnet_sa_backward_f32", xyz, c, ld, centres, group_idx, nsample, feats, D, params_host, cout_host, eps_host, L,
+                                   dout, dfeats, grads_host, arg_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ampnet_sa_backward_ragged_f32(const float *xyz, const int32_t *cloud_off, int n_clouds, int total, int ld, const int32_t *centres,
+                                             int s, const int32_t *group_idx, int nsample, const float *feats, int D,
+                                             const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                                             const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out, void *workspace,
+                                             size_t workspace_bytes, void *stream)
+{
+    ampnet::BwdClouds c;
+    const int rc = ampnet::bwd_clouds_ragged("ampnet_sa_backward_ragged_f32", cloud_off, n_clouds, total, s, c);
+    if (rc != AMPNET_OK) return rc;
+    return ampnet::sa_backward_run("ampnet_sa_backward_ragged_f32", xyz, c, ld, centres, group_idx, nsample, feats, D, params_host, cout_host,
+                                   eps_host, L, dout, dfeats, grads_host, arg_out, workspace, workspace_bytes, stream);
 }

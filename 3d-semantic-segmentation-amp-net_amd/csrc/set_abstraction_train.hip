@@ -36,7 +36,8 @@
 //       part B for layer l:  x_l from the workspace into T1, a_l recomputed, dy_l = dx_l [fma(a, scale, shift) > 0] stored to the workspace,
 //       sum dy and sum dy a added into the workgroup's own partial row.
 //   fpt_bwd_finalize_kernel     (bn_train.hip) after every phase l >= 0.
-//   fpb_wgrad_launch, sa_dfeats_launch   dW_l = dz_l^T x_l and dfeats, exactly the eval backward's, on the eval backward's workspace layout.
+//   fpb_wgrad_launch, sa_gather_launch   dW_l = dz_l^T x_l and dfeats, exactly the eval backward's (the gather ragged when the clouds are), on
+//       the eval backward's workspace layout.
 //   A phase holds two 32-row tiles of the widest layer input (at most 82 KB) whatever nsample is.
 //   The statistics, part A and part B of a tile are bn_train.h's (bnt_tile_stats, bnt_form_dz, bnt_form_dy), shared with feature propagation;
 //   this file keeps what is set abstraction's own: the gathers, the tiling, the max of the last layer (sat_last).
@@ -355,13 +356,16 @@ extern "C" int ampnet_sa_train_backward_tape(int D, int n_clouds, int s, int nsa
     return AMPNET_OK;
 }
 
-extern "C" int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s,
-                                            const int32_t *group_idx, int nsample, const float *feats, int D, const float *const *params_host,
-                                            const int *cout_host, const float *eps_host, int L, const float *dout, float *dfeats,
-                                            float *const *grads_host, int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream)
+namespace ampnet {
+
+// The body of ampnet_sa_train_backward_f32 and ampnet_sa_train_backward_ragged_f32 (sa_tiles.h, BwdClouds): the phases and the statistics
+// over c's groups as one batch, the dfeats gather alone ragged.
+static int sa_train_backward_run(const char *what, const float *xyz, const BwdClouds &c, int ld, const int32_t *centres, const int32_t *group_idx,
+                                 int nsample, const float *feats, int D, const float *const *params_host, const int *cout_host,
+                                 const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
+                                 void *workspace, size_t workspace_bytes, void *stream)
 {
-    using namespace ampnet;
-    const char *what = "ampnet_sa_train_backward_f32";
+    const int n_clouds = c.n_clouds, n = c.n, s = c.s;
     hipStream_t st = (hipStream_t)stream;
     AMPNET_REQUIRE(xyz && centres && group_idx && params_host && cout_host && eps_host && dout && grads_host, "%s: null pointer", what);
     SaBwdShape sh;
@@ -401,6 +405,31 @@ extern "C" int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int 
         AMPNET_TRY(fpb_wgrad_launch(b.dz[l], p.cout[l], b.xs[l], p.cin[l], sh.ldxs[l], sh.M, sh.chunk_rows, sh.chunks, ws + sh.off_wpart,
                                     grads_host[4 * l], st));
     }
-    if (dfeats) return sa_dfeats_launch(b.dx0, D, n_clouds, n, s, nsample, group_idx, dfeats, st);
+    if (dfeats) return sa_gather_launch(b.dx0, D, c, nsample, group_idx, dfeats, st);
     return AMPNET_OK;
+}
+
+}  // namespace ampnet
+
+extern "C" int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int n, int ld, const int32_t *centres, int s,
+                                            const int32_t *group_idx, int nsample, const float *feats, int D, const float *const *params_host,
+                                            const int *cout_host, const float *eps_host, int L, const float *dout, float *dfeats,
+                                            float *const *grads_host, int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const ampnet::BwdClouds c = {n_clouds, n, s, nullptr, 0, 0};
+    return ampnet::sa_train_backward_run("ampnet_sa_train_backward_f32", xyz, c, ld, centres, group_idx, nsample, feats, D, params_host, cout_host,
+                                         eps_host, L, dout, dfeats, grads_host, arg_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ampnet_sa_train_backward_ragged_f32(const float *xyz, const int32_t *cloud_off, int n_clouds, int total, int ld,
+                                                   const int32_t *centres, int s, const int32_t *group_idx, int nsample, const float *feats,
+                                                   int D, const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                                                   const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
+                                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    ampnet::BwdClouds c;
+    const int rc = ampnet::bwd_clouds_ragged("ampnet_sa_train_backward_ragged_f32", cloud_off, n_clouds, total, s, c);
+    if (rc != AMPNET_OK) return rc;
+    return ampnet::sa_train_backward_run("ampnet_sa_train_backward_ragged_f32", xyz, c, ld, centres, group_idx, nsample, feats, D, params_host,
+                                         cout_host, eps_host, L, dout, dfeats, grads_host, arg_out, workspace, workspace_bytes, stream);
 }

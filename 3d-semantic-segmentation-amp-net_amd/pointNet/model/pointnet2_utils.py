@@ -37,6 +37,11 @@ over all B * npoint * nsample rows of its groups -- the slots that ball query fi
 other, as they are for BatchNorm2d over [B, C, nsample, npoint] (ampnet_sa_train_forward_f32, ampnet_sa_train_backward_f32 through
 autograd._SaTrainFn).  In eval mode the flag changes nothing, and without it .train() still raises.
 
+Clouds of UNEQUAL size packed back to back go through the blocks' _forward_ragged (pointnetAtt.pointnet_2_seg.forward_ragged): the ragged
+searches write GLOBAL indices and the fused kernels above take the packed array as ONE cloud.  grad=True and batch_stats=True work there
+as in _forward_rows -- the statistics over all rows of the call -- and the backward gathers the gradient of the features (set abstraction)
+or of the coarse points (feature propagation) cloud by cloud (autograd._ragged_note; ampnet_*_backward_ragged_f32).
+
 PointNetSetAbstraction(..., group_all=True) forms ONE group of all N points of a cloud, runs the shared MLP on [xyz, features] (the
 coordinates as they are) and takes the max over the points: the global descriptor of a cloud (ampnet_sa_all_forward_f32).  Eval mode,
 with grad=True the frozen-statistics backward (ampnet_sa_all_backward_f32 through autograd._SaAllFn), which runs on the rows that won a
@@ -271,16 +276,20 @@ class PointNetSetAbstraction(_EvalForwardPrecision, _SetAbstraction):
         return new_xyz, out
 
     def _forward_ragged(self, x, feats, layout):
-        """The eval layer on clouds of UNEQUAL size packed back to back: x [total, 3], feats [total, D] or None, float32 contiguous GPU,
+        """The layer on clouds of UNEQUAL size packed back to back: x [total, 3], feats [total, D] or None, float32 contiguous GPU,
         layout = utils.RaggedLayout of the clouds, every one of >= npoint points -> (new_xyz [Q, npoint, 3], new_points [Q, npoint, mlp[-1]]),
-        cloud by cloud the bits of _forward_rows on that cloud alone.  Ragged FPS, then the ragged ball query with GLOBAL indices, then the
-        fused kernel of _forward_rows on the packed array as ONE cloud of `total` points and Q * npoint centres: a centre's row of the
-        output depends on its own group and the weights alone (csrc/set_abstraction.hip: a wave owns a centre, a fixed contraction order,
-        no atomics), so which launch it shares is immaterial.  No graph, no host read-back (the centres are FPS's own)."""
+        in eval mode cloud by cloud the bits of _forward_rows on that cloud alone.  Ragged FPS, then the ragged ball query with GLOBAL
+        indices, then the fused kernel of _forward_rows on the packed array as ONE cloud of `total` points and Q * npoint centres: a
+        centre's row of the output depends on its own group and the weights alone (csrc/set_abstraction.hip: a wave owns a centre, a fixed
+        contraction order, no atomics), so which launch it shares is immaterial.  No host read-back (the centres are FPS's own).
+        A default block: eval mode, no graph.  grad=True: a graph when _wants_grad says so, to `feats` and the parameters; its backward
+        gathers dfeats cloud by cloud (autograd._ragged_note).  batch_stats=True in train mode: the train-mode layer of _train_rows on the
+        packed array -- the statistics over all Q * npoint * nsample rows, what _forward_rows takes over B = Q equal clouds -- the buffers
+        updated and num_batches_tracked counted once.  group_all and bf16 are refused."""
         self._check_bf16()
-        if self.group_all or self.training or is_bf16(self.precision):
+        if self.group_all or (self.training and not self.batch_stats) or is_bf16(self.precision):
             raise NotImplementedError("PointNetSetAbstraction._forward_ragged is built for the exact-fp32 eval forward of a grouping block "
-                                      "(group_all=False, .eval(), precision fp32)")
+                                      "(group_all=False, .eval(), precision fp32); train mode needs a block built with batch_stats=True")
         Q, S = len(layout.sizes), self.npoint
         if min(layout.sizes) < S:
             raise _lib.AmpnetError(f"PointNetSetAbstraction: every cloud needs at least npoint={S} points for farthest-point sampling, "
@@ -290,13 +299,23 @@ class PointNetSetAbstraction(_EvalForwardPrecision, _SetAbstraction):
             centres = torch.stack(U.fps_indices_ragged(x, layout.sizes, S))                       # [Q, npoint], relative to their cloud
             group_idx = U.ball_query_ragged(x, layout, centres, self.radius, self.nsample, global_index=True, _trusted_centres=True)
             centres = (centres + layout.off[:-1].unsqueeze(1)).reshape(1, Q * S)                  # rows of the packed array
+            group_idx = group_idx.reshape(1, Q * S, self.nsample)
             packed = x.unsqueeze(0)
-            new_xyz = U.gather_rows(packed, centres)
-            layers = _mlp_tensors(self)
-            out = torch.empty((1, Q * S, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
-            _lib.sa_forward_f32(packed, centres, group_idx.reshape(1, Q * S, self.nsample), None if feats is None else feats.detach().unsqueeze(0),
-                                layers, [bn.eps for bn in self.mlp_bns], out, _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
-        return new_xyz.reshape(Q, S, 3), out.reshape(Q, S, -1)
+            new_xyz = U.gather_rows(packed, centres).reshape(Q, S, 3)
+        packed_feats = None if feats is None else feats.unsqueeze(0)                              # (a view: the graph goes through it)
+        if self.training:
+            out = self._train_rows(packed, centres, group_idx, packed_feats, cloud_off=layout.off)
+        elif self._wants_grad(feats):
+            from ... import autograd
+            out = autograd.sa_apply(self, packed, centres, group_idx, packed_feats, _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device),
+                                    cloud_off=layout.off)
+        else:
+            with torch.no_grad():
+                layers = _mlp_tensors(self)
+                out = torch.empty((1, Q * S, layers[-1][0].shape[0]), dtype=torch.float32, device=x.device)
+                _lib.sa_forward_f32(packed, centres, group_idx, None if feats is None else packed_feats.detach(), layers,
+                                    [bn.eps for bn in self.mlp_bns], out, _workspace(self, _lib.SA_WORKSPACE_BYTES, x.device))
+        return new_xyz, out.reshape(Q, S, -1)
 
     def _all_rows(self, x, feats, centres):
         """_forward_rows of a group_all block: ONE group of all N points per cloud, the coordinates as they are (no centre)
@@ -314,15 +333,15 @@ class PointNetSetAbstraction(_EvalForwardPrecision, _SetAbstraction):
             out, _ = autograd.sa_all_forward(x, None if feats is None else feats.detach(), _mlp_tensors(self), [bn.eps for bn in self.mlp_bns])
         return new_xyz, out.unsqueeze(1)
 
-    def _train_rows(self, x, centres, group_idx, feats):
+    def _train_rows(self, x, centres, group_idx, feats, cloud_off=None):
         """The fused layer of _forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when
-        one is wanted."""
+        one is wanted.  cloud_off: autograd._ragged_note (_forward_ragged)."""
         if not self.batch_stats:
             raise NotImplementedError(_SA_EVAL_ONLY)
         momentum = _momentum(self, "set abstraction")
         from ... import autograd
         if self._wants_grad(feats):
-            out = autograd.sa_train_apply(self, x, centres, group_idx, feats, momentum)
+            out = autograd.sa_train_apply(self, x, centres, group_idx, feats, momentum, cloud_off=cloud_off)
         else:
             with torch.no_grad():
                 out, _, _ = autograd.sa_train_forward(x, centres, group_idx, None if feats is None else feats.detach(),
@@ -535,34 +554,47 @@ class PointNetFeaturePropagation(_EvalForwardPrecision, nn.Module):
         return out
 
     def _forward_ragged(self, x1, layout, x2, p1, p2):
-        """The eval layer from fine clouds of UNEQUAL size packed back to back to S coarse points per cloud: x1 [total, 3], p1 [total, D1] or
-        None, layout = utils.RaggedLayout of the fine clouds, x2 [Q, S, 3], p2 [Q, S, D2], float32 contiguous GPU -> [total, mlp[-1]], cloud
-        by cloud the bits of _forward_rows on that cloud alone.  The ragged 3-NN with GLOBAL indices, then the fused kernel of _forward_rows
-        on the packed arrays as ONE cloud (total fine, Q * S coarse points): a fine point's output row depends on its own input row and the
-        weights alone (csrc/feature_propagation.hip: the rows of a tile do not mix, a fixed contraction order, no atomics), so where the
-        tile boundaries fall is immaterial.  No graph."""
+        """The layer from fine clouds of UNEQUAL size packed back to back to S coarse points per cloud: x1 [total, 3], p1 [total, D1] or
+        None, layout = utils.RaggedLayout of the fine clouds, x2 [Q, S, 3], p2 [Q, S, D2], float32 contiguous GPU -> [total, mlp[-1]], in
+        eval mode cloud by cloud the bits of _forward_rows on that cloud alone.  The ragged 3-NN with GLOBAL indices, then the fused kernel
+        of _forward_rows on the packed arrays as ONE cloud (total fine, Q * S coarse points): a fine point's output row depends on its own
+        input row and the weights alone (csrc/feature_propagation.hip: the rows of a tile do not mix, a fixed contraction order, no
+        atomics), so where the tile boundaries fall is immaterial.
+        A default block: eval mode, no graph.  grad=True: a graph when _wants_grad says so, to p1, p2 and the parameters; its backward
+        gathers dp2 cloud by cloud (autograd._ragged_note).  batch_stats=True in train mode: the train-mode layer of _train_rows on the
+        packed arrays, the statistics over all `total` rows, the buffers updated and num_batches_tracked counted once.  bf16 is refused."""
         self._check_bf16()
-        if self.training or is_bf16(self.precision):
+        if (self.training and not self.batch_stats) or is_bf16(self.precision):
             raise NotImplementedError("PointNetFeaturePropagation._forward_ragged is built for the exact-fp32 eval forward (.eval(), "
-                                      "precision fp32)")
+                                      "precision fp32); train mode needs a block built with batch_stats=True")
         Q, S = x2.shape[0], x2.shape[1]
         with torch.no_grad():
             idx, dist2 = U.three_nn_ragged(x1.detach(), layout, x2.detach(), global_index=True)
+            idx, dist2 = idx.unsqueeze(0), dist2.unsqueeze(0)
+        packed1 = None if p1 is None else p1.unsqueeze(0)                                          # (views: the graph goes through them)
+        packed2 = p2.reshape(1, Q * S, p2.shape[2])
+        if self.training:
+            return self._train_rows(packed1, packed2, idx, dist2, cloud_off=layout.off)[0]
+        if self._wants_grad(p1, p2):
+            from ... import autograd
+            return autograd.fp_apply(self, packed1, packed2, idx, dist2, _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device),
+                                     cloud_off=layout.off)[0]
+        with torch.no_grad():
             layers = _mlp_tensors(self)
             out = torch.empty((1, layout.total, layers[-1][0].shape[0]), dtype=torch.float32, device=x1.device)
-            _lib.fp_forward_f32(None if p1 is None else p1.detach().unsqueeze(0), p2.detach().reshape(1, Q * S, p2.shape[2]), idx.unsqueeze(0),
-                                dist2.unsqueeze(0), layers, [bn.eps for bn in self.mlp_bns], out,
-                                _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
+            _lib.fp_forward_f32(None if p1 is None else packed1.detach(), packed2.detach(), idx, dist2, layers, [bn.eps for bn in self.mlp_bns],
+                                out, _workspace(self, _lib.FP_WORKSPACE_BYTES, x1.device))
         return out[0]
 
-    def _train_rows(self, p1, p2, idx, dist2):
-        """_forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when one is wanted."""
+    def _train_rows(self, p1, p2, idx, dist2, cloud_off=None):
+        """_forward_rows in train mode (batch_stats=True): batch statistics, the buffers updated in place, a graph when one is wanted.
+        cloud_off: autograd._ragged_note (_forward_ragged)."""
         if not self.batch_stats:
             raise NotImplementedError(_FP_EVAL_ONLY)
         momentum = _momentum(self, "feature propagation")
         from ... import autograd
         if self._wants_grad(p1, p2):
-            out = autograd.fp_train_apply(self, p1, p2, idx, dist2, momentum)
+            out = autograd.fp_train_apply(self, p1, p2, idx, dist2, momentum, cloud_off=cloud_off)
         else:
             with torch.no_grad():
                 out, _, _ = autograd.fp_train_forward(None if p1 is None else p1.detach(), p2.detach(), idx, dist2,

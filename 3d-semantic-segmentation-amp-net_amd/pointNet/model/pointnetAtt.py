@@ -489,6 +489,17 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
         global_feature = self.conv1(l0_points).amax(2)                                # MaxPool1d(N) + view(-1, 128)
         return global_feature, l0_points
 
+    def _check_block_modes(self):
+        """The blocks follow the model's mode (train()): sa1..sa3 train only with encoder_batch_stats, fp1..fp3 with the model."""
+        for m in (self.sa1, self.sa2, self.sa3):
+            if m.training != (self.training and self.encoder_batch_stats):
+                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
+                                          "pointnet_2: sa1..sa3 follow the model's mode; call .train() on the model, not on its blocks")
+        for m in (self.fp3, self.fp2, self.fp1):
+            if m.training != self.training:
+                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
+                                          "pointnet_2: fp1..fp3 follow the model's mode; call .train() on the model, not on its blocks")
+
     def _backbone(self, xyz, rows=False):
         """The six blocks -> (fp1's point-major result [B, N, 128] as it left the kernel, l0_points [B, 128, N]): what pointnet_2 puts
         conv1 and the max behind, and pointnet_2_seg its head.  rows=True: `xyz` is the point-major [B, N, 9] float32 contiguous tensor the
@@ -504,14 +515,7 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
                                        f"{xyz.dtype}, strides {xyz.stride()}")
         elif xyz.dim() != 3 or xyz.shape[1] != 9:
             raise _lib.AmpnetError(f"pointnet_2: expected xyz [B, 9, N], got {tuple(xyz.shape)}")
-        for m in (self.sa1, self.sa2, self.sa3):
-            if m.training != (self.training and self.encoder_batch_stats):
-                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
-                                          "pointnet_2: sa1..sa3 follow the model's mode; call .train() on the model, not on its blocks")
-        for m in (self.fp3, self.fp2, self.fp1):
-            if m.training != self.training:
-                raise NotImplementedError("pointnet_2: a block of the model is in train mode; call .eval() on the model" if m.training else
-                                          "pointnet_2: fp1..fp3 follow the model's mode; call .train() on the model, not on its blocks")
+        self._check_block_modes()
         with torch.no_grad():
             l0_points = xyz.detach() if rows else xyz.detach().float().transpose(1, 2).contiguous()      # [B, N, 9]
             l0_xyz = l0_points[:, :, :3].contiguous()                                 # [B, N, 3]
@@ -548,7 +552,8 @@ class pointnet_2_seg(pointnet_2):
     state_dict gives.  forward_rows / predict_rows are forward / predict on point-major [Q, N, 9] rows, without the transposes
     (pointNet/pn2_step.py trains through them, with pointnet2_utils.seg_nll_loss as the loss).  forward_ragged / predict_ragged /
     predict_clouds label clouds of UNEQUAL size in one launch sequence, cloud by cloud the bits of forward_rows / predict_rows on that cloud
-    alone (eval, no graph; pointNet/pn2_infer.py drives them).  Not built: bf16 (the model has no
+    alone (pointNet/pn2_infer.py drives them); forward_ragged also carries a graph and trains under forward_rows' rules, so the model learns
+    from clouds of native size (pn2_step.train_loop_clouds), the two predict calls stay eval operations without a graph.  Not built: bf16 (the model has no
     `precision` keyword and refuses set_precision('bf16')), a loss fused into the head's kernel, momentum=None, dropout in eval mode, train
     mode for group_all set abstraction."""
 
@@ -599,15 +604,23 @@ class pointnet_2_seg(pointnet_2):
             l0_rows, _ = self._backbone(points, rows=True)
             return self._head._forward_rows(l0_rows, want_preds=True)[1]
 
-    # ---- clouds of UNEQUAL size in one launch sequence (eval, no graph) ------------------------------------------------------------------
+    # ---- clouds of UNEQUAL size in one launch sequence -----------------------------------------------------------------------------------
     # Only level 0 is ragged: sa1 emits npoint centres for every cloud, so sa2, sa3, fp3 and fp2 see uniform [Q, npoint, .] tensors and
     # run as they are; sa1 samples and groups ragged clouds, fp1 searches from ragged fine points, and the head takes any number of rows.
+    # forward_ragged follows forward_rows' mode and graph rules (the backwards of sa1 and fp1 gather cloud by cloud: autograd._ragged_note);
+    # the two predict calls are eval operations.
 
     def _ragged(self, rows, sizes, want_preds):
-        """The six blocks and the head on `rows` [total, 9] = clouds of `sizes` points back to back -> the head's result on [1, total, 128]."""
-        if self.training or self._head.training or any(m.training for m in (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1)):
+        """The six blocks and the head on `rows` [total, 9] = clouds of `sizes` points back to back -> the head's result on [1, total, 128].
+        want_preds: an eval operation, the caller holds no_grad; else the mode checks and the graph rules of _backbone."""
+        if want_preds:
+            every = (self, self._head, self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1)
+        else:
+            every = (self,) if not self.decoder_batch_stats else ()
+        if any(m.training for m in every):
             raise NotImplementedError("pointnet_2_seg: forward_ragged / predict_ragged / predict_clouds are eval operations: call .eval() "
-                                      "first")
+                                      "first (forward_ragged trains in a model built with the batch-statistics flags)")
+        self._check_block_modes()
         _lib.require_gpu(rows, "rows")
         if rows.dim() != 2 or rows.shape[1] != 9 or rows.dtype != torch.float32 or not rows.is_contiguous():
             raise _lib.AmpnetError(f"pointnet_2_seg: expected packed rows [total, 9], float32 and contiguous, got {tuple(rows.shape)} "
@@ -619,9 +632,11 @@ class pointnet_2_seg(pointnet_2):
         with torch.no_grad():
             l0_points = rows.detach()
             l0_xyz = l0_points[:, :3].contiguous()                                             # [total, 3]
+        with contextlib.nullcontext() if self.encoder_grad else torch.no_grad():             # (the caller's grad mode, or none)
             l1_xyz, l1_points = self.sa1._forward_ragged(l0_xyz, l0_points, layout)            # [Q, 1024, 3], [Q, 1024, 64]
             l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)
             l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)
+        with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
             l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)
             l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)
             l0_rows = self.fp1._forward_ragged(l0_xyz, layout, l1_xyz, None, l1_points)        # [total, 128]
@@ -629,13 +644,17 @@ class pointnet_2_seg(pointnet_2):
 
     def forward_ragged(self, rows, sizes):
         """rows [total, 9] float32 contiguous GPU = clouds of `sizes` points back to back, every one of >= sa1.npoint points
-        -> log_probs [total, num_classes]; the rows of cloud b are the bits of forward_rows on that cloud alone.  One launch sequence for
-        all clouds, no host read-back.  An eval operation, never a graph; train mode raises NotImplementedError."""
+        -> log_probs [total, num_classes].  One launch sequence for all clouds, no host read-back.  Mode checks, graph rules and flags are
+        forward_rows': in eval mode the rows of cloud b are the bits of forward_rows on that cloud alone, with decoder_grad=True and grad
+        mode on they carry a graph, and in train mode (the batch-statistics flags) the model trains on the clouds as ONE batch -- every
+        BatchNorm over all rows of the call, the dropout mask over `total` rows -- which is forward_rows' train mode when the clouds are of
+        one size.  A model built without the flags never builds a graph, and its train mode raises NotImplementedError."""
         return self._ragged(rows, sizes, False)[0]
 
     def predict_ragged(self, rows, sizes):
-        """forward_ragged's classes, int64 [total]: cloud by cloud the bits of predict_rows."""
-        return self._ragged(rows, sizes, True)[1].reshape(-1)
+        """forward_ragged's classes, int64 [total]: cloud by cloud the bits of predict_rows.  An eval operation, never a graph."""
+        with torch.no_grad():
+            return self._ragged(rows, sizes, True)[1].reshape(-1)
 
     def _predict_padded(self, rows, sizes):
         """predict_ragged for clouds of ANY size >= 1: a cloud below sa1.npoint points is padded on the device by repeating its rows

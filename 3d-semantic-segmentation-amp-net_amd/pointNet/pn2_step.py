@@ -13,6 +13,8 @@ so every REAL window is one cloud of the batch:
   * pointnet_2_seg.forward_rows runs the six blocks and the head on the rows (no transpose in, no [Q, 128, N] copy out);
   * pointnet2_utils.seg_nll_loss gives the weighted loss, the predictions and the confusion counts in one pass;
   * backward() and optimizer.step() (trainer.FusedAdam).
+train_loop_clouds is the same step on clouds of UNEQUAL size taken as they are (the clusters of a `<name>_clusters_list.pkl`), through
+pointnet_2_seg.forward_ragged: no windows, no resampling, no augmentation.
 The model is exact fp32: there is no `precision` argument.  With device_outputs=True (the default) nothing in the step waits for the GPU:
 no .item(), no download, no data-dependent shape."""
 import numpy as np
@@ -74,6 +76,56 @@ def train_loop(data, optimizer, class_w, model, train=True, device_outputs=True)
     else:
         with torch.no_grad():
             loss, preds, counts = seg_nll_loss(model.forward_rows(rows), tg, class_w, want_preds=True, want_counts=True)
+    metrics = {'loss': loss.detach()}
+    if device_outputs:
+        return metrics, tg, preds, counts
+    return metrics, tg.to('cpu'), preds.to('cpu'), counts.to('cpu')           # (the one place that waits for the GPU, on request)
+
+
+def train_loop_clouds(clouds, optimizer, class_w, model, train=True, device_outputs=True):
+    """One step on clouds of UNEQUAL size, as the cluster files (`<name>_clusters_list.pkl`) hold them
+    -> (metrics {'loss'}, targets [sum n_i], preds [sum n_i], counts [C * C + 1]).
+    clouds: a list of [n_i, >= 10] tensors, columns 0 .. 8 the features and column 9 the ASPRS class code; one concatenation into
+    page-locked memory, one upload, and the labels from the class-code column by one table look-up on the device
+    (amp_test._upload_clusters).  The clouds go through pointnet_2_seg.forward_ragged as ONE batch at their native sizes: no resampling to
+    windows, one launch sequence, every BatchNorm over all rows of the call.  A cloud below sa1.npoint points is padded by repeating its
+    rows cyclically (utils.pad_cloud_sizes) with target -1 for the padding rows: the padding rows ENTER the BatchNorm statistics (they are
+    rows of the call like any other, and farthest-point sampling needs them) but NOT the loss, the predictions returned or the counts'
+    confusion cells (counts[-1], the ignored rows, counts them).  targets and preds come back without the padding, in the clouds' order.
+    The loss is pointnet2_utils.seg_nll_loss with class_w (float32 [C] GPU tensor or None).  train=True: model.train(), forward, loss,
+    backward(), optimizer.step() -- the model needs the flags forward_rows' train mode needs; else model.eval() under no_grad.
+    device_outputs=True: everything stays on the GPU and nothing in the step waits for it; False: targets, preds and counts are
+    downloaded.  Not built: augmentation of ragged clouds (the device pipeline is window-shaped), an epoch driver, data parallelism."""
+    from .amp_test import _upload_clusters
+    from ..utils import utils as U
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.AmpnetError("the pointnet_2_seg HIP path needs the model on the GPU")
+    if not clouds or any(c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 10 for c in clouds):
+        raise _lib.AmpnetError(f"train_loop_clouds: expected a list of [n_i >= 1, >= 10] tensors, got {[tuple(c.shape) for c in clouds]}")
+    model.train(train)
+    rows, tg, _ = _upload_clusters(clouds, dev)
+    sizes = [int(c.shape[0]) for c in clouds]
+    keep = None
+    if min(sizes) < model.sa1.npoint:
+        sizes, _, gather, keep = U.pad_cloud_sizes(sizes, model.sa1.npoint)
+        own = np.zeros(len(gather), dtype=bool)
+        own[keep] = True
+        gather = torch.from_numpy(gather).to(dev, non_blocking=True)
+        keep = torch.from_numpy(keep).to(dev, non_blocking=True)
+        rows = rows[gather]
+        tg = torch.where(torch.from_numpy(own).to(dev, non_blocking=True), tg[gather], -1)
+    if train:
+        optimizer.zero_grad()
+        log_probs = model.forward_ragged(rows, sizes)
+        loss, preds, counts = seg_nll_loss(log_probs, tg, class_w, want_preds=True, want_counts=True)
+        loss.backward()
+        optimizer.step()
+    else:
+        with torch.no_grad():
+            loss, preds, counts = seg_nll_loss(model.forward_ragged(rows, sizes), tg, class_w, want_preds=True, want_counts=True)
+    if keep is not None:
+        tg, preds = tg[keep], preds[keep]
     metrics = {'loss': loss.detach()}
     if device_outputs:
         return metrics, tg, preds, counts

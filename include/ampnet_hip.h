@@ -685,6 +685,54 @@ int ampnet_sa_train_backward_f32(const float *xyz, int n_clouds, int n, int ld, 
                                  const float *eps_host, int L, const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out,
                                  void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the four backwards above on clouds of UNEQUAL size packed back to back (new symbols within ABI 18: nothing else moved,
+ * AMPNET_ABI_VERSION stays 18).  Training and fine-tuning on clouds of native size: the ragged searches (ampnet_fps_ragged_f32,
+ * ampnet_ball_query_ragged_f32 and ampnet_three_nn_ragged_f32 with global_index = 1) give centres, groups and neighbours as rows of the
+ * packed array, and the forwards -- ampnet_sa_forward_f32, ampnet_fp_forward_f32 and their _train_ namesakes -- take that array as ONE
+ * cloud (n_clouds = 1, n = total, n_clouds * s centres or coarse points): no row of theirs mixes with another, and batch statistics over
+ * all rows of the call are the right statistics.  These are their backwards.  Each takes the argument list of its uniform namesake with
+ * (n_clouds, n) replaced by
+ *   cloud_off             DEVICE int32 [n_clouds + 1], ascending, cloud_off[0] = 0, cloud_off[n_clouds] = total (the table of
+ *                         ampnet_fps_ragged_f32): cloud b is the rows cloud_off[b] .. cloud_off[b + 1] - 1 of the packed arrays
+ *   n_clouds, total       the clouds and the rows of all of them
+ * and s PER CLOUD: points2 / dpoints2 are [n_clouds * s, D2] with the coarse points of cloud b at [b s, (b + 1) s); centres, group_idx,
+ * dout and arg_out of the set abstraction are [n_clouds * s, ..] in the same order.  idx (feature propagation), centres and group_idx
+ * (set abstraction) hold GLOBAL rows: of the n_clouds * s coarse points, of the `total` points.
+ * Each runs exactly the phases of its namesake on the packed array as one cloud -- so dpoints1, dW, dbias, dgamma, dbeta and arg_out are
+ * that call's, bit for bit -- and only the last gather is segmented by cloud_off:
+ *   dpoints2   one wave per coarse point j of cloud b = j / s scans the entries (i, q) of the fine rows i of cloud b alone, ascending,
+ *              idx clamped into [b s, (b + 1) s - 1], fmaf(w, dx_0, sum)
+ *   dfeats     one wave per point j; its cloud b (a binary search over cloud_off) has the centres [b s, (b + 1) s), and the wave scans
+ *              their s nsample entries alone, ascending, clamped into the cloud's rows, plain sums
+ * instead of the entries of the whole array, whose number grows with n_clouds for every one of the n_clouds * s (or total) waves.
+ * Cloud by cloud, dpoints2 and dfeats are the bits the uniform entry point writes for that cloud alone (n_clouds = 1, local indices).
+ * PRECONDITION: every index refers to a point, centre or coarse point of ITS OWN cloud, as the indices of the ragged searches do.  The
+ * phases before the gather clamp an index into the whole packed array, the gather into the cloud: the two disagree only for an index that
+ * violates the precondition (nothing is read or written out of bounds either way; the table's rows are clamped into [0, total]).
+ * Workspace: the existing *_workspace_bytes functions called with the packed shape -- ampnet_fp_backward_workspace_bytes(D1, D2, 1,
+ * total, ..) / ampnet_fp_train_backward_workspace_bytes likewise; ampnet_sa_backward_workspace_bytes(D, 1, n_clouds * s, nsample, ..) /
+ * ampnet_sa_train_backward_workspace_bytes likewise -- and the layout is theirs.  Limits: those of the namesakes on the packed shape, so
+ * total <= AMPNET_FP_TRAIN_MAX_ROWS and n_clouds * s * nsample <= AMPNET_SA_TRAIN_MAX_ROWS for the train-mode pair, k <= s, and
+ * n_clouds * s <= 2^31 - 1.  No float atomics, every order a function of the shape and the table alone: two calls return the same bits.
+ * Caller's stream, no host synchronisation.                                                                                         */
+int ampnet_fp_backward_ragged_f32(const float *points1, int D1, const float *points2, int D2, const int32_t *cloud_off, int n_clouds, int total,
+                                  int s, const int32_t *idx, const float *dist2, int k, const float *const *params_host, const int *cout_host,
+                                  const float *eps_host, int L, const float *dout, float *dpoints1, float *dpoints2, float *const *grads_host,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int ampnet_fp_train_backward_ragged_f32(const float *points1, int D1, const float *points2, int D2, const int32_t *cloud_off, int n_clouds,
+                                        int total, int s, const int32_t *idx, const float *dist2, int k, const float *const *params_host,
+                                        const int *cout_host, const float *eps_host, int L, const float *dout, float *dpoints1,
+                                        float *dpoints2, float *const *grads_host, void *workspace, size_t workspace_bytes, void *stream);
+int ampnet_sa_backward_ragged_f32(const float *xyz, const int32_t *cloud_off, int n_clouds, int total, int ld, const int32_t *centres, int s,
+                                  const int32_t *group_idx, int nsample, const float *feats, int D, const float *const *params_host,
+                                  const int *cout_host, const float *eps_host, int L, const float *dout, float *dfeats,
+                                  float *const *grads_host, int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream);
+int ampnet_sa_train_backward_ragged_f32(const float *xyz, const int32_t *cloud_off, int n_clouds, int total, int ld, const int32_t *centres,
+                                        int s, const int32_t *group_idx, int nsample, const float *feats, int D,
+                                        const float *const *params_host, const int *cout_host, const float *eps_host, int L,
+                                        const float *dout, float *dfeats, float *const *grads_host, int32_t *arg_out, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+
 /* ---- the per-point classifier of the PointNet++ segmentation model, eval mode, fused, and its backward (added within ABI 17: new
  * symbols, nothing else moved).  Stands in for the lines the reference's pointnet_2 carries commented out (pointnetAtt.py:294-296,
  * :318-321): bn1, drop1 (the identity in eval mode), conv2, log_softmax, permute.

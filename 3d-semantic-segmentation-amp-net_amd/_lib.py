@@ -962,3 +962,27 @@ def seg_nll_backward_f32(target, class_w, sums, grad_loss, dlogp):
         rc = lib().ampnet_seg_nll_backward_f32(ptr(target), ptr(class_w), ptr(sums), ptr(grad_loss), ctypes.c_longlong(M), C, ptr(dlogp),
                                                stream_ptr(dlogp.device))
     check(rc, "ampnet_seg_nll_backward_f32")
+
+
+# ---- the input pipeline of clouds of unequal size (csrc/augment_clouds.hip) ---------------------------------------------------------------
+def cloud_input_f32(raw, in_off, out_off, seed, step, permute, rotate, cos_a, sin_a, rows, targets, src=None):
+    """One launch from the uploaded clusters to what forward_ragged and the loss consume (include/ampnet_hip.h: ampnet_cloud_input_f32).
+    raw [total_in, 10] float32, in_off / out_off int32 [Q + 1] (the clouds in raw and in the padded output; TRUSTED: they are built on the
+    host by the caller and not read back), seed / step: the keys of the point shuffle (u32), permute / rotate: flags, cos_a / sin_a: the
+    step's angle.  Written, every element: rows [total_out, 9] float32, targets [total_out] int64 (-1 on padding rows), src [total_out]
+    int32 or None (the row of raw behind every output row).  Contiguous GPU tensors."""
+    _check_tensors("cloud_input", [("raw", raw, _F32, 2, True), ("in_off", in_off, _I32, 1, True), ("out_off", out_off, _I32, 1, True),
+                                   ("rows", rows, _F32, 2, True), ("targets", targets, _I64, 1, True), ("src", src, _I32, 1, False)])
+    Q = int(in_off.numel()) - 1
+    total_in, total_out = int(raw.shape[0]), int(rows.shape[0])
+    if raw.shape[1] != 10 or rows.shape[1] != 9 or Q < 1 or out_off.numel() != Q + 1 or targets.numel() != total_out \
+            or (src is not None and src.numel() != total_out):
+        raise AmpnetError(f"cloud_input: expected raw [total_in, 10], in_off and out_off [Q + 1 >= 2], rows [total_out, 9], targets and src "
+                          f"[total_out], got {tuple(raw.shape)} {tuple(in_off.shape)} {tuple(out_off.shape)} {tuple(rows.shape)} "
+                          f"{tuple(targets.shape)} {None if src is None else tuple(src.shape)}")
+    with torch.cuda.device(raw.device):
+        rc = lib().ampnet_cloud_input_f32(ptr(raw), ptr(in_off), ptr(out_off), Q, ctypes.c_longlong(total_in), ctypes.c_longlong(total_out),
+                                          ctypes.c_uint32(int(seed) & 0xFFFFFFFF), ctypes.c_uint32(int(step) & 0xFFFFFFFF),
+                                          int(bool(permute)), int(bool(rotate)), ctypes.c_double(float(cos_a)), ctypes.c_double(float(sin_a)),
+                                          ptr(rows), ptr(targets), ptr(src), stream_ptr(raw.device))
+    check(rc, "ampnet_cloud_input_f32")

@@ -245,6 +245,30 @@ __host__ __device__ inline uint32_t mix32(uint32_t x)
     return x;
 }
 __host__ __device__ inline uint32_t drop_base(uint32_t seed, uint32_t stream) { return mix32(seed + stream * 0x9E3779B9U); }
+// The stateless point shuffle of the ragged input pipeline (augment_clouds.hip; spec: include/ampnet_hip.h, ampnet_cloud_input_f32):
+// cloud_perm(ck, n, .) is a bijection of [0, n) -- a four-round Feistel network on 2 * half bits (a domain of at most 4 n values) keyed by
+// ck, walked until it lands inside [0, n).  Never stored: every reader recomputes it from (seed, step, cloud).
+__host__ __device__ inline uint32_t cloud_perm_key(uint32_t seed, uint32_t step, uint32_t cloud)
+{
+    return mix32(drop_base(seed, step) + cloud * 0x85EBCA6BU);
+}
+__host__ __device__ inline uint32_t cloud_perm(uint32_t ck, uint32_t n, uint32_t x)
+{
+    int bits = 1;                                 // max(bit_length(n - 1), 1)
+    while ((1U << bits) < n) ++bits;
+    const int half = (bits + 1) / 2;
+    const uint32_t mask = (1U << half) - 1U;
+    do {
+        uint32_t L = x >> half, R = x & mask;
+        for (uint32_t r = 0; r < 4; ++r) {
+            const uint32_t t = L ^ (mix32(ck ^ ((R << 2) | r)) & mask);
+            L = R;
+            R = t;
+        }
+        x = (L << half) | R;
+    } while (x >= n);
+    return x;
+}
 __host__ __device__ inline uint32_t drop_threshold(float p)
 {
     double t = (double)p * 4294967296.0;

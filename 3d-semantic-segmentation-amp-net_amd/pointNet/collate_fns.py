@@ -215,3 +215,53 @@ def collate_seq_ragged(batch):
         _fill_padded(cents, i, torch.as_tensor(cent).float().unsqueeze(1), MAX_WINDOWS, "replicate")
         names.append(name)
     return RaggedBatch(pts[:po], lab[:lo], idx, meta), None, names, cents.view(-1, MAX_WINDOWS, 2)
+
+
+class CloudBatch:
+    """What collate_clouds hands to pn2_step.train_loop_clouds: the clusters of the batch's files at their native sizes, back to back in
+    ONE [total, 10] float32 buffer (columns 0 .. 8 the features, column 9 the ASPRS class code) that travels to the device as it is --
+    page-locked once DataLoader(pin_memory=True) or pin_memory() has seen it -- plus what stays on the host: `sizes`, the points of every
+    cluster in order, and `names`, the files.  Padding, shuffling, rotation and the labels happen on
+    the GPU (include/ampnet_hip.h: ampnet_cloud_input_f32)."""
+    __slots__ = ("raw", "sizes", "names")
+
+    def __init__(self, raw, sizes, names):
+        self.raw, self.sizes, self.names = raw, [int(n) for n in sizes], list(names)
+
+    def __len__(self):
+        return len(self.names)
+
+    def pin_memory(self):                    # DataLoader(pin_memory=True) calls this on custom batch types
+        return CloudBatch(self.raw.pin_memory(), self.sizes, self.names)
+
+    def to(self, device, non_blocking=False):
+        return CloudBatch(self.raw.to(device, non_blocking=non_blocking), self.sizes, self.names)
+
+    def record_stream(self, stream):
+        if self.raw.is_cuda:
+            self.raw.record_stream(stream)
+
+    @property
+    def is_cuda(self):
+        return self.raw.is_cuda
+
+
+def collate_clouds(batch):
+    """batch: one entry per file, each the list of its clusters ([n_k, >= 10] float tensors, what datasets.LidarClusterDataset returns; the
+    file's name is the list's `name` attribute when it has one) -> CloudBatch.  One pass: every cluster is written once into its rows of
+    the batch's buffer (shared memory inside a DataLoader worker).  No resampling, no random draws."""
+    sizes, names = [], []
+    for item in batch:
+        if not len(item) or any(c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 10 for c in map(torch.as_tensor, item)):
+            raise ValueError(f"{getattr(item, 'name', '?')}: expected a non-empty list of [n_k >= 1, >= 10] tensors, got "
+                             f"{[tuple(torch.as_tensor(c).shape) for c in item]}")
+        sizes += [int(c.shape[0]) for c in item]
+        names.append(getattr(item, "name", ""))
+    raw = _batch_buffer(sum(sizes) * 10, torch.float32).view(-1, 10)
+    r = 0
+    for item in batch:
+        for c in item:
+            n = int(c.shape[0])
+            raw[r:r + n] = torch.as_tensor(c)[:, :10]
+            r += n
+    return CloudBatch(raw, sizes, names)

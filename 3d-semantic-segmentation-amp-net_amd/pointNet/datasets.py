@@ -283,3 +283,45 @@ class LidarInferenceDataset(data.Dataset):
         if constrained_sample:
             pc = pc[pc[:, 10] == 1]
         return torch.from_numpy(pc)
+
+
+CLUSTER_MAX_POINTS = 12288      # the ragged entry points' limit (include/ampnet_hip.h: ampnet_ball_query_ragged_f32)
+
+
+class ClusterList(list):
+    """The clusters of one file, a plain list of [n_k, >= 10] tensors that also remembers the file's `name`."""
+    name = ""
+
+
+class LidarClusterDataset(data.Dataset):
+    """The files of a list as their precomputed clusters at NATIVE size -- what pn2_infer.test evaluates on, as a training set
+    (pn2_train.train_pn2_clouds).  Item i is the list of [n_k, >= 10] float tensors of `<cluster_dir>/<name>_clusters_list.pkl` (columns
+    0 .. 8 the features, column 9 the ASPRS class code; written by the reference's kmeans_clustering, utils/utils.py:526-533, or
+    synthetic.write_cluster_dataset), <name> being files[i] without directory and extension.  The reference has no such dataset: it trains
+    on windows resampled to 2048 points.  Read through _safe_load.load_tensor_list (torch.save files load restricted; files written
+    with pickle.dump need allow_pickle=True / AMPNET_ALLOW_PICKLE=1).  A cluster above CLUSTER_MAX_POINTS points cannot enter the ragged
+    launch sequence and is an AmpnetError naming the file and the cluster (splitting it is not built)."""
+
+    def __init__(self, cluster_dir, files, allow_pickle=None):
+        self.cluster_dir, self.files, self.allow_pickle = cluster_dir, list(files), allow_pickle
+
+    def __len__(self):
+        return len(self.files)
+
+    def path(self, index):
+        return os.path.join(self.cluster_dir, self.files[index].split('/')[-1].split('.')[0] + '_clusters_list.pkl')
+
+    def __getitem__(self, index):
+        from .._lib import AmpnetError
+        from .._safe_load import load_tensor_list
+        path = self.path(index)
+        out = ClusterList(torch.as_tensor(c) for c in load_tensor_list(path, self.allow_pickle))
+        out.name = self.files[index]
+        for k, c in enumerate(out):
+            if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 10:
+                raise AmpnetError(f"{path}: cluster {k} is {tuple(c.shape)}, expected [n >= 1, >= 10]")
+            if c.shape[0] > CLUSTER_MAX_POINTS:
+                raise AmpnetError(f"{path}: cluster {k} holds {c.shape[0]} points, above the ragged limit of {CLUSTER_MAX_POINTS}")
+        if not out:
+            raise AmpnetError(f"{path}: no clusters")
+        return out

@@ -14,15 +14,18 @@ so every REAL window is one cloud of the batch:
   * pointnet2_utils.seg_nll_loss gives the weighted loss, the predictions and the confusion counts in one pass;
   * backward() and optimizer.step() (trainer.FusedAdam).
 train_loop_clouds is the same step on clouds of UNEQUAL size taken as they are (the clusters of a `<name>_clusters_list.pkl`), through
-pointnet_2_seg.forward_ragged: no windows, no resampling, no augmentation.
+pointnet_2_seg.forward_ragged: no windows, no resampling; its input side is ONE kernel (cloud_input), which in train_loop_clouds_aug with
+a CloudAugment also shuffles the points of every cloud and rotates the step's clouds about z.
 The model is exact fp32: there is no `precision` argument.  With device_outputs=True (the default) nothing in the step waits for the GPU:
 no .item(), no download, no data-dependent shape."""
+import math
+
 import numpy as np
 import torch
 
 from .. import _lib
 from .amp_step import augment_batch_device, augment_ragged_device
-from .collate_fns import RaggedBatch
+from .collate_fns import CloudBatch, RaggedBatch
 from .model.pointnet2_utils import seg_nll_loss
 
 NUM_CLASSES = 5
@@ -82,39 +85,144 @@ def train_loop(data, optimizer, class_w, model, train=True, device_outputs=True)
     return metrics, tg.to('cpu'), preds.to('cpu'), counts.to('cpu')           # (the one place that waits for the GPU, on request)
 
 
+def _mix32(x):
+    """kernels.h: mix32 (the dropout hash) on a Python int."""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def step_angle(seed, step):
+    """The z-rotation angle of step `step` under `seed`: 2 pi * mix32(base ^ 0x3C6EF372) / 2^32, base = mix32(seed + step * 0x9E3779B9)
+    (include/ampnet_hip.h: ampnet_cloud_input_f32).  A function of the two ints alone: nothing is drawn from numpy's or torch's RNG."""
+    base = _mix32((int(seed) + int(step) * 0x9E3779B9) & 0xFFFFFFFF)
+    return 2.0 * math.pi * _mix32(base ^ 0x3C6EF372) / 4294967296.0
+
+
+class CloudAugment:
+    """The augmentation state of train_loop_clouds_aug: two ints.  `seed` is fixed, `_step` advances by one per train-mode step (the convention
+    of PointNetSegHead.seed / _step); step k shuffles the points of every cloud with the keyed bijection of ampnet_cloud_input_f32 and
+    rotates all clouds about z by step_angle(seed, k) -- the reference's shuffle_data and rotate_point_cloud_z (one angle per step).  A run
+    is reproducible from state_dict().  The shuffle is an augmentation shuffle, not a uniform sampler of permutations."""
+
+    def __init__(self, seed=0x6A09E667):
+        self.seed, self._step = int(seed) & 0xFFFFFFFF, 0
+
+    def state_dict(self):
+        return {'seed': self.seed, 'step': self._step}
+
+    def load_state_dict(self, state):
+        self.seed, self._step = int(state['seed']) & 0xFFFFFFFF, int(state['step'])
+
+
+def _cloud_input(raw, sizes, npoint, train, seed, step, want_src):
+    """cloud_input -> (rows, targets, the padded clouds as a utils.RaggedLayout -- its device table is the one the kernel read, so
+    forward_ragged uploads none of its own --, src or None)."""
+    from ..utils.utils import RaggedLayout
+    _lib.require_gpu(raw, "raw")
+    npoint = int(npoint)
+    if raw.dim() != 2 or raw.shape[1] != 10 or raw.dtype != torch.float32 or not raw.is_contiguous():
+        raise _lib.AmpnetError(f"cloud_input: expected raw contiguous [total, 10] float32, got {tuple(raw.shape)} {raw.dtype}")
+    n = np.asarray(sizes, dtype=np.int64).reshape(-1)                # (numpy from here on: the call is bound by its host side)
+    if n.size == 0 or n.min() < 1 or n.sum() != raw.shape[0] or npoint < 1:
+        raise _lib.AmpnetError(f"cloud_input: sizes (sum {int(n.sum())}, each >= 1) must tile the {raw.shape[0]} rows of raw, npoint={npoint} >= 1")
+    p = np.maximum(n, npoint)
+    total_out = int(p.sum())
+    if total_out > 0x7fffffff:
+        raise _lib.AmpnetError(f"cloud_input: {total_out} padded rows exceed 2^31 - 1")
+    padded = p.tolist()
+    off = np.zeros((2, n.size + 1), dtype=np.int32)
+    np.cumsum(n, dtype=np.int32, out=off[0, 1:])
+    np.cumsum(p, dtype=np.int32, out=off[1, 1:])
+    off = torch.from_numpy(off).to(raw.device, non_blocking=True)
+    rows = torch.empty((total_out, 9), dtype=torch.float32, device=raw.device)
+    targets = torch.empty((total_out,), dtype=torch.int64, device=raw.device)
+    src = torch.empty((total_out,), dtype=torch.int32, device=raw.device) if want_src else None
+    angle = step_angle(seed, step) if train else 0.0
+    _lib.cloud_input_f32(raw, off[0], off[1], seed, step, train, train, math.cos(angle), math.sin(angle), rows, targets, src)
+    return rows, targets, RaggedLayout(padded, off[1]), src
+
+
+def cloud_input(raw, sizes, npoint, *, train, seed, step, want_src=False):
+    """The input side of train_loop_clouds in ONE launch (include/ampnet_hip.h: ampnet_cloud_input_f32)
+    -> (rows [sum p_i, 9] f32, targets [sum p_i] int64, padded sizes [p_i][, src int32 [sum p_i]]).
+    raw: [sum n_i, 10] float32 ON THE DEVICE, the clouds back to back (columns 0 .. 8 the features, column 9 the ASPRS class code); sizes:
+    the n_i (host ints); npoint: every cloud below it is padded to p_i = max(n_i, npoint) by repeating its rows cyclically, targets -1 on
+    the padding rows (utils.pad_cloud_sizes' rule).  The labels are amp_test._label_lut's.  train=True: the points of every cloud are
+    shuffled by the bijection keyed with (seed, step, cloud) and x, y, z are rotated about z by step_angle(seed, step), bit for bit
+    utils.rotate_point_cloud_z; train=False: neither, and rows / targets are what _upload_clusters + the pad_cloud_sizes gather give.
+    want_src: also the row of `raw` behind every output row.  Both offset tables are built on the host and go up in one non-blocking
+    copy: the call never waits for the GPU."""
+    rows, targets, layout, src = _cloud_input(raw, sizes, npoint, train, seed, step, want_src)
+    return (rows, targets, layout.sizes, src) if want_src else (rows, targets, layout.sizes)
+
+
+def _upload_raw(clouds, device):
+    """list of [n_i, >= 10] float tensors -> raw [sum n_i, 10] f32 on the device: one concatenation into amp_test's page-locked staging
+    buffer, one asynchronous upload (the host half of amp_test._upload_clusters)."""
+    from .amp_test import _STAGE, _Staging
+    st = _STAGE.setdefault(str(device), _Staging())
+    k, buf = st.take(sum(int(c.shape[0]) for c in clouds), 10)
+    torch.cat([torch.as_tensor(c)[:, :10].float() for c in clouds], dim=0, out=buf)
+    raw = buf.to(device, non_blocking=True)
+    st.uploaded(k, device)
+    return raw
+
+
 def train_loop_clouds(clouds, optimizer, class_w, model, train=True, device_outputs=True):
     """One step on clouds of UNEQUAL size, as the cluster files (`<name>_clusters_list.pkl`) hold them
     -> (metrics {'loss'}, targets [sum n_i], preds [sum n_i], counts [C * C + 1]).
-    clouds: a list of [n_i, >= 10] tensors, columns 0 .. 8 the features and column 9 the ASPRS class code; one concatenation into
-    page-locked memory, one upload, and the labels from the class-code column by one table look-up on the device
-    (amp_test._upload_clusters).  The clouds go through pointnet_2_seg.forward_ragged as ONE batch at their native sizes: no resampling to
+    clouds: a list of [n_i, >= 10] tensors, columns 0 .. 8 the features and column 9 the ASPRS class code -- one concatenation into
+    page-locked memory, one upload -- or a collate_fns.CloudBatch; one that is on the device already (the DevicePrefetcher moved it) is
+    taken as it is and the step uploads nothing but the clouds' offsets (one [2, Q + 1] table, which forward_ragged reads too) and, with a
+    short cloud, the indices of the clouds' own rows.  ONE kernel (cloud_input) then writes the rows, the labels from the class-code
+    column and the padding.  The clouds go through pointnet_2_seg.forward_ragged as ONE batch at their native sizes: no resampling to
     windows, one launch sequence, every BatchNorm over all rows of the call.  A cloud below sa1.npoint points is padded by repeating its
-    rows cyclically (utils.pad_cloud_sizes) with target -1 for the padding rows: the padding rows ENTER the BatchNorm statistics (they are
-    rows of the call like any other, and farthest-point sampling needs them) but NOT the loss, the predictions returned or the counts'
-    confusion cells (counts[-1], the ignored rows, counts them).  targets and preds come back without the padding, in the clouds' order.
+    rows cyclically (utils.pad_cloud_sizes' rule) with target -1 for the padding rows: the padding rows ENTER the BatchNorm statistics
+    (they are rows of the call like any other, and farthest-point sampling needs them) but NOT the loss, the predictions returned or the
+    counts' confusion cells (counts[-1], the ignored rows, counts them).  targets and preds come back without the padding, in the clouds'
+    order.  No augmentation: the results are bit for bit those of the step before the kernel existed; train_loop_clouds_aug is this step
+    with the keyword `augment`.
     The loss is pointnet2_utils.seg_nll_loss with class_w (float32 [C] GPU tensor or None).  train=True: model.train(), forward, loss,
     backward(), optimizer.step() -- the model needs the flags forward_rows' train mode needs; else model.eval() under no_grad.
     device_outputs=True: everything stays on the GPU and nothing in the step waits for it; False: targets, preds and counts are
-    downloaded.  Not built: augmentation of ragged clouds (the device pipeline is window-shaped), an epoch driver, data parallelism."""
-    from .amp_test import _upload_clusters
-    from ..utils import utils as U
+    downloaded.  Not built: data parallelism."""
+    return train_loop_clouds_aug(clouds, optimizer, class_w, model, train, device_outputs, augment=None)
+
+
+def train_loop_clouds_aug(clouds, optimizer, class_w, model, train=True, device_outputs=True, *, augment=None):
+    """train_loop_clouds with the device augmentation: the same arguments, results and rules, plus the keyword-only `augment` (the
+    keyword lives here, not on train_loop_clouds, whose argument list is pinned).
+    augment: None or a CloudAugment.  None: train_loop_clouds.  A CloudAugment with train=True: the points of every cloud are shuffled
+    and all clouds rotated about z by the step's angle (cloud_input), then augment._step advances by one; with train=False nothing is
+    augmented and _step stays.  targets and preds come back without the padding, cloud after cloud, and are consistent with each other;
+    WITH augmentation they are in the AUGMENTED order of every cloud (row j of cloud b is the cloud's point perm_b(j);
+    cloud_input(want_src=True) names it), not the file's."""
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise _lib.AmpnetError("the pointnet_2_seg HIP path needs the model on the GPU")
-    if not clouds or any(c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 10 for c in clouds):
-        raise _lib.AmpnetError(f"train_loop_clouds: expected a list of [n_i >= 1, >= 10] tensors, got {[tuple(c.shape) for c in clouds]}")
+    if isinstance(clouds, CloudBatch):
+        raw, sizes = clouds.raw.to(dev, non_blocking=True), clouds.sizes
+    else:
+        if not clouds or any(c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 10 for c in clouds):
+            raise _lib.AmpnetError(f"train_loop_clouds: expected a list of [n_i >= 1, >= 10] tensors, got {[tuple(c.shape) for c in clouds]}")
+        raw = _upload_raw(clouds, dev)
+        sizes = [int(c.shape[0]) for c in clouds]
+    if augment is not None and not isinstance(augment, CloudAugment):
+        raise _lib.AmpnetError(f"train_loop_clouds_aug: augment must be None or a CloudAugment, got {type(augment).__name__}")
     model.train(train)
-    rows, tg, _ = _upload_clusters(clouds, dev)
-    sizes = [int(c.shape[0]) for c in clouds]
+    aug = train and augment is not None
+    rows, tg, layout, _ = _cloud_input(raw, sizes, model.sa1.npoint, aug, augment.seed if aug else 0, augment._step if aug else 0, False)
+    if aug:
+        augment._step += 1
     keep = None
-    if min(sizes) < model.sa1.npoint:
-        sizes, _, gather, keep = U.pad_cloud_sizes(sizes, model.sa1.npoint)
-        own = np.zeros(len(gather), dtype=bool)
-        own[keep] = True
-        gather = torch.from_numpy(gather).to(dev, non_blocking=True)
-        keep = torch.from_numpy(keep).to(dev, non_blocking=True)
-        rows = rows[gather]
-        tg = torch.where(torch.from_numpy(own).to(dev, non_blocking=True), tg[gather], -1)
+    if layout.sizes != sizes:
+        off = np.concatenate([[0], np.cumsum(layout.sizes)[:-1]]).astype(np.int64)
+        keep = torch.from_numpy(np.concatenate([o + np.arange(n, dtype=np.int64) for o, n in zip(off, sizes)])).to(dev, non_blocking=True)
+    sizes = layout                                                   # forward_ragged reads the table the kernel read: no second upload
     if train:
         optimizer.zero_grad()
         log_probs = model.forward_ragged(rows, sizes)

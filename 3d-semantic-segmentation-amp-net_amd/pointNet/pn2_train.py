@@ -7,6 +7,9 @@ has no driver for it; files read and written are those of the other two families
              windows of every batch (pn2_step.train_loop), weighted NLL with class weights [1, 2, 2, 1, 1], ONE FusedAdam(lr), MultiStepLR
              milestones [150, 250, 350] gamma 0.5 stepped per epoch; writes pointNet/checkpoints/checkpoint_<name>.pth
              (utils.save_checkpoint: keys 'model', 'optimizer', ...) whenever the mean validation loss improves
+  train_pn2_clouds  train_pn2's twin on the clusters of `<cluster_dir>/<name>_clusters_list.pkl` at their NATIVE sizes -- the clouds
+             pn2_infer.test evaluates on: `files_per_step` files are one ragged batch (pn2_step.train_loop_clouds_aug), shuffled and rotated
+             on the device (pn2_step.CloudAugment), validation without augmentation
   test       one file per step, clustered in situ with kmeans_clustering(pc, n_points, True, MAX_CLUSTERS = 18) as gru_train.test does;
              every cluster is one cloud of its own size (segment_file).
 
@@ -23,10 +26,10 @@ from ..trainer import FusedAdam
 from ..utils.get_metrics import get_accuracy, get_iou_obj, metrics_from_confusion
 from ..utils.utils import get_labels, kmeans_clustering, limit_host_threads, save_checkpoint
 from .amp_train import IOU_NAMES, reduce_epoch_metrics, start_workers
-from .collate_fns import collate_seq_ragged
-from .datasets import LidarDataset4Test, LidarKmeansDataset
+from .collate_fns import collate_clouds, collate_seq_ragged
+from .datasets import LidarClusterDataset, LidarDataset4Test, LidarKmeansDataset
 from .model.pointnetAtt import pointnet_2_seg
-from .pn2_step import NUM_CLASSES, train_loop, window_counts
+from .pn2_step import NUM_CLASSES, CloudAugment, train_loop, train_loop_clouds_aug, window_counts
 from .prefetch import DevicePrefetcher
 
 MAX_CLUSTERS = 18
@@ -49,15 +52,14 @@ class _WithWindowCounts:
             yield tuple(batch) + (window_counts(batch[0], batch[1]),)
 
 
-def _epoch(loader, train, model, optimizer, class_w):
-    """One pass over the loader: prefetched uploads, the loss and the confusion counts of every step stay queued on the device, ONE
-    download per epoch."""
+def _run_steps(batches, step, dev):
+    """One pass: `step(batch)` -> (metrics, targets, preds, counts) for every prefetched batch; the loss and the confusion counts of every
+    step stay queued on the device, ONE download per epoch."""
     sums = dict(loss=[], acc=[])
     ious = {k: [] for k in IOU_NAMES}
-    dev = next(model.parameters()).device
     counts, losses = [], []
-    for data in DevicePrefetcher(_WithWindowCounts(loader), dev):
-        metrics, _, _, c = train_loop(data, optimizer, class_w, model, train=train, device_outputs=True)
+    for data in DevicePrefetcher(batches, dev):
+        metrics, _, _, c = step(data)
         counts.append(c)
         losses.append(metrics['loss'].reshape(()))
     if counts:
@@ -69,6 +71,32 @@ def _epoch(loader, train, model, optimizer, class_w):
                 ious[name].append(v)
             sums['loss'].append(float(l))
     return reduce_epoch_metrics(sums, ious, device=dev)
+
+
+def _epoch(loader, train, model, optimizer, class_w):
+    """One pass over the window loader (pn2_step.train_loop on every batch)."""
+    return _run_steps(_WithWindowCounts(loader), lambda data: train_loop(data, optimizer, class_w, model, train=train, device_outputs=True),
+                      next(model.parameters()).device)
+
+
+class _AsTuple:
+    """A loader of CloudBatch objects as the 1-tuples the prefetcher moves entry by entry."""
+
+    def __init__(self, loader):
+        self.loader = loader
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            yield (batch,)
+
+
+def _epoch_clouds(loader, train, model, optimizer, class_w, augment):
+    """One pass over the cluster loader (pn2_step.train_loop_clouds_aug on every batch; the CloudBatch arrives on the device)."""
+    return _run_steps(_AsTuple(loader), lambda data: train_loop_clouds_aug(data[0], optimizer, class_w, model, train=train,
+                                                                           device_outputs=True, augment=augment), next(model.parameters()).device)
 
 
 def train_pn2(dataset_folder, path_list_files, output_folder, n_points, batch_size, epochs, learning_rate, number_of_workers=4,
@@ -117,6 +145,68 @@ def train_pn2(dataset_folder, path_list_files, output_folder, n_points, batch_si
             best_vloss, since = va['loss'], 0
             stamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
             save_checkpoint(stamp + name, epoch, since, model, optimizer, va['acc'], batch_size, learning_rate, n_points)
+        else:
+            since += 1
+    print("--- TOTAL TIME: %s h ---" % (round((time.time() - start) / 3600, 3)))
+    return history
+
+
+def train_pn2_clouds(cluster_dir, path_list_files, output_folder, files_per_step, epochs, learning_rate, number_of_workers=4,
+                     model_checkpoint=None, device='cuda', allow_pickle=None, seed=0x6A09E667):
+    """train_pn2 on clusters of NATIVE size: reads <path_list_files>/train_seg_files.txt, val_seg_files.txt and
+    `<cluster_dir>/<name>_clusters_list.pkl` (datasets.LidarClusterDataset), trains pointnet_2_seg(5) with all five flags; the clusters
+    of `files_per_step` files are ONE ragged batch (pn2_step.train_loop_clouds_aug, every BatchNorm over all its rows).  The same class
+    weights, FusedAdam, MultiStepLR and checkpoint keys as train_pn2 (utils.save_checkpoint; 'batch_size' holds files_per_step,
+    'number_of_points' None -- the clouds keep their sizes -- and 'weighing_method', the free slot, {'cloud_augment': the two ints of
+    the augmentation}, so a run continued from `model_checkpoint` draws the steps the uninterrupted run would have drawn).  Train steps
+    shuffle the points of every cloud and rotate the batch about z on the device (pn2_step.CloudAugment(seed): a function of
+    (seed, step), nothing is drawn from numpy's or torch's RNG); validation is not augmented.  Returns the per-epoch history
+    [(train metrics, validation metrics)].  The checkpoint loads into a default pointnet_2_seg(5) and into pn2_infer.test.  Exact fp32:
+    no `precision` argument.  Single process: data parallelism is not built for this model."""
+    start = time.time()
+    limit_host_threads(reserve=number_of_workers)
+    device = torch.device(device)
+    with open(os.path.join(path_list_files, 'train_seg_files.txt')) as f:
+        train_files = f.read().splitlines()
+    with open(os.path.join(path_list_files, 'val_seg_files.txt')) as f:
+        val_files = f.read().splitlines()
+    train_ds = LidarClusterDataset(cluster_dir, train_files, allow_pickle=allow_pickle)
+    val_ds = LidarClusterDataset(cluster_dir, val_files, allow_pickle=allow_pickle)
+    # persistent workers, forked before the first pinned batch exists (amp_train.start_workers: a later fork stalls the GPU queues)
+    mk = lambda ds, train: torch.utils.data.DataLoader(ds, batch_size=files_per_step, shuffle=train, num_workers=number_of_workers,  # noqa: E731
+                                                       drop_last=train, collate_fn=collate_clouds, pin_memory=True,
+                                                       persistent_workers=number_of_workers > 0)
+    train_loader, val_loader = mk(train_ds, True), mk(val_ds, False)
+    start_workers(val_loader, train_loader)
+    print(f'Cluster folder: {cluster_dir}\nFiles for training: {len(train_ds)}\nFiles for validation: {len(val_ds)}')
+    model = pointnet_2_seg(NUM_CLASSES, device=device, **TRAIN_FLAGS)
+    class_w = torch.tensor([1.0, 2.0, 2.0, 1.0, 1.0], device=device)
+    optimizer = FusedAdam(model.parameters(), lr=learning_rate)
+    scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[150, 250, 350], gamma=0.5)
+    augment = CloudAugment(seed)
+    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters())}")
+    best_vloss, epoch_ini, since = 1_000_000., 0, 0
+    if model_checkpoint:
+        ck = torch.load(model_checkpoint, map_location=device, weights_only=True)
+        model.load_state_dict(ck['model'])
+        optimizer.load_state_dict(ck['optimizer'])
+        epoch_ini = ck['epoch']
+        if isinstance(ck.get('weighing_method'), dict) and 'cloud_augment' in ck['weighing_method']:
+            augment.load_state_dict(ck['weighing_method']['cloud_augment'])
+    history = []
+    for epoch in range(epoch_ini, epochs):
+        t0 = time.time()
+        tr = _epoch_clouds(train_loader, True, model, optimizer, class_w, augment)
+        va = _epoch_clouds(val_loader, False, model, optimizer, class_w, None)
+        scheduler.step()
+        history.append((tr, va))
+        print(f"epoch {epoch}: train loss {tr['loss']:.4f} acc {tr['acc']:.3f} | val loss {va['loss']:.4f} acc {va['acc']:.3f} "
+              f"iou tower {va['iou_tower']:.3f} | {time.time() - t0:.1f} s", flush=True)
+        if va['loss'] < best_vloss:
+            best_vloss, since = va['loss'], 0
+            stamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
+            save_checkpoint(stamp + 'PN2segClouds', epoch, since, model, optimizer, va['acc'], files_per_step, learning_rate, None,
+                            weighing_method={'cloud_augment': augment.state_dict()})
         else:
             since += 1
     print("--- TOTAL TIME: %s h ---" % (round((time.time() - start) / 3600, 3)))

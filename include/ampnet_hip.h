@@ -293,6 +293,41 @@ int ampnet_collate_augment_f32(const float *pts, const signed char *labels, cons
                                const int32_t *cluster_perm, const int32_t *point_perm, double cos_a, double sin_a, int rotate,
                                int B, int N, int W, float *x_out, long long *t_out, void *stream);
 
+/* ---- the input pipeline of pn2_step.train_loop_clouds in one kernel: clouds of unequal size (BUILD-DEFINED, within ABI 18) ----------
+ * What ampnet_augment_f32 is for the window batch, for the clusters of `<name>_clusters_list.pkl` files at their native sizes.  The
+ * reference augments a batch with rotate_point_cloud_z (utils/utils.py:582-604, one angle per step) and shuffle_data (:607-617); it
+ * has no ragged batch, so the layout and the shuffle below are this project's.
+ *   raw      [total_in, 10] float32: the Q clouds back to back as they were uploaded, columns 0 .. 8 the features, column 9 the ASPRS
+ *            class code; 8-byte aligned
+ *   in_off   int32 [Q + 1]: cloud b is rows in_off[b] .. in_off[b + 1] of raw, n_b = in_off[b + 1] - in_off[b] >= 1, in_off[Q] = total_in
+ *   out_off  int32 [Q + 1]: the same for the output, p_b = out_off[b + 1] - out_off[b] >= n_b (the package pads to
+ *            p_b = max(n_b, npoint), utils.pad_cloud_sizes), out_off[Q] = total_out.  Both arrays on the device; they are TRUSTED (built
+ *            by the caller on the host), as the meta of ampnet_collate_augment_f32 is
+ *   rows     [total_out, 9] float32, 16-byte aligned; targets int64 [total_out]; src int32 [total_out] or NULL
+ * Output row j of cloud b copies row s = in_off[b] + perm_b(j % n_b) of raw: rows[out_off[b] + j] = raw[s, 0:9], src[..] = s,
+ *   targets[..] = j < n_b ? lut(raw[s, 9]) : -1     (the padding rows are ignored by the loss)
+ *   lut(code): k = (long)code (truncated towards zero) clamped to [0, 255]; 15 -> 1, 14 -> 2, 3 and 4 -> 3, 5 -> 4, everything else 0
+ *              (amp_test._label_lut; computed in the kernel, no table is read)
+ *   rotate != 0: (x, y, z) <- (x c - y s, x s + y c, z) exactly as ampnet_augment_f32 does it -- the float64 product of the float32
+ *              coordinates with [[c, s, 0], [-s, c, 0], [0, 0, 1]] column by column, no fused multiply-add, rounded to float32 once --
+ *              bit for bit utils.rotate_point_cloud_z with the angle whose cosine and sine are cos_a, sin_a
+ *   permute == 0: perm_b is the identity.  Otherwise perm_b is a STATELESS bijection of [0, n_b), never stored, a function of
+ *              (seed, step, b, n_b) alone -- the convention of the dropout masks (a counter hash), with u32 wrapping arithmetic:
+ *       mix32(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16           (the dropout hash)
+ *       base = mix32(seed + step * 0x9E3779B9);   ck = mix32(base + b * 0x85EBCA6B)
+ *       bits = max(bit_length(n - 1), 1);   half = (bits + 1) / 2;   mask = (1 << half) - 1            (a domain of 2^(2 half) <= 4 n)
+ *       F(x):  L = x >> half, R = x & mask;  four rounds r = 0 .. 3: (L, R) <- (R, L ^ (mix32(ck ^ ((R << 2) | r)) & mask));
+ *              F(x) = (L << half) | R                                          (a Feistel network: a bijection of the domain)
+ *       perm_b(j) = the first of F(j), F(F(j)), ... that is < n                 (cycle walking: it ends because F is a bijection)
+ *     An augmentation shuffle, not a uniform sampler: at n = 8 the least likely (position, source) pair came up 444 times in 4096 steps
+ *     against 512 for a uniform draw.  The angle of a step is chosen by the caller; the package takes
+ *     2 pi * mix32(base ^ 0x3C6EF372) / 2^32, so a step is reproducible from (seed, step) and draws from no global generator.
+ * Every element of rows, targets and src is written (no memset needed), no atomics, deterministic.  Q >= 1, Q <= total_in <= total_out
+ * < 2^31.                                                                                                                        */
+int ampnet_cloud_input_f32(const float *raw, const int32_t *in_off, const int32_t *out_off, int Q, long long total_in,
+                           long long total_out, uint32_t seed, uint32_t step, int permute, int rotate, double cos_a, double sin_a,
+                           float *rows, long long *targets, int32_t *src, void *stream);
+
 /* ---- k-NN grouping of FPS centres (BUILD-DEFINED; BASELINE.json north_star / config 5) ------------------------------
  * The reference has no k-NN or ball query: nothing is replaced, parity against it is "unpinned"; the spec
  * below is pinned by oracle/fps_oracle.py:knn_indices.

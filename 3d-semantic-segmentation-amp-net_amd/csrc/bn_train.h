@@ -159,7 +159,9 @@ struct BntBwd {
 // returns the dynamic LDS bytes of a phase kernel: two tiles of 32 rows of the widest layer input or output, plus one float
 size_t bnt_bwd_plan(const MlpPlan &p, const MlpFold &f, const MlpBwdLayout &lay, float *ws, size_t off_coef, BntBwd &b);
 
-// the two limits of the batch statistics on top of the eval entry points' (`what` opens the message; rows_text says what M is the product of)
+// the two limits of the batch statistics on top of the eval entry points' (`what` opens the message; rows_text says what M is the product of).
+// With a registered collective the statistics are the GLOBAL batch's and its merged row count must be an exact float too: the call then
+// also refuses M * world_size > max_rows -- a host-side rule, conservative because the ranks' row counts differ and no rank knows the others'.
 int bnt_rows_ok(const char *what, long long M, long long max_rows, const char *rows_text);
 
 struct FptStats {                         // what the finalize of pass l reads and writes
@@ -169,6 +171,12 @@ struct FptStats {                         // what the finalize of pass l reads a
     int cout, fold_off;
 };
 
+// The two finalize launchers follow a registered collective (kernels.h: sync_bn_on()): each call then issues exactly ONE exchange through
+// sync_bn_exchange, whatever the data, so every rank must make the same sequence of calls; a failing callback comes back as the launcher's
+// status.  Forward: the rank's partial rows packed into one row (n, mean, M2)[cout], all-gathered, finalized over the ranks' rows in rank order
+// with the MERGED row count (M is not used) -- every rank writes the same fold, saved and running statistics, bit for bit.  Backward: dbeta,
+// dgamma, dbias stay the rank's own sums (the gradient all-reduce adds them); (sum dy, sum dy a)[cout] and M are all-reduced and coef comes
+// from the global sums.  With one rank both reproduce the plain path's bits.
 // fpt_stats_finalize_kernel on `st`: parts [n_parts][3 q.cout] (count, mean, sum of squared deviations per partial row) -> scale and shift of
 // the layer in `fold`, save_mean, save_invstd and the running-statistics update over M rows
 int fpt_stats_finalize_launch(const FptStats &q, const float *parts, int n_parts, long long M, float *fold, hipStream_t st);

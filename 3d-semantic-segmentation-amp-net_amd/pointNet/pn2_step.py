@@ -17,13 +17,22 @@ train_loop_clouds is the same step on clouds of UNEQUAL size taken as they are (
 pointnet_2_seg.forward_ragged: no windows, no resampling; its input side is ONE kernel (cloud_input), which in train_loop_clouds_aug with
 a CloudAugment also shuffles the points of every cloud and rotates the step's clouds about z.
 The model is exact fp32: there is no `precision` argument.  With device_outputs=True (the default) nothing in the step waits for the GPU:
-no .item(), no download, no data-dependent shape."""
+no .item(), no download, no data-dependent shape.
+
+Data parallelism.  Under torch.distributed (trainer._collectives_on(): more than one rank, or one rank with AMPNET_FORCE_COLLECTIVES=1) a
+train-mode step of both loops keeps its gradients in ONE flat float32 buffer (p.grad are views of it), all-reduces that buffer once after
+backward() (trainer.reduce_gradients: SUM, 1 / world folded into FusedAdam.grad_scale) and then steps the optimiser, so every rank applies
+the same update.  By default every rank's BatchNorm statistics and loss are its own batch's.  After trainer.enable_sync_batchnorm() the 17
+train-mode BatchNorms take the statistics of the GLOBAL batch (one exchange per layer and direction inside the C library, csrc/bn_train.hip)
+and the loss is the global batch's weighted mean (global_loss), which metrics['loss'] then reports on every rank: the step of N ranks is
+the single-process step on the concatenated batch, except that every rank draws the dropout mask of its own rows from its own head.seed.
+Without a process group nothing changes, bits included."""
 import math
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, trainer
 from .amp_step import augment_batch_device, augment_ragged_device
 from .collate_fns import CloudBatch, RaggedBatch
 from .model.pointnet2_utils import seg_nll_loss
@@ -47,13 +56,102 @@ def real_window_index(cperm, n_windows):
     return torch.from_numpy(np.arange(keep.size, dtype=np.int64)[keep.reshape(-1)])
 
 
+class FlatGrads:
+    """The data-parallel step's gradients: ONE flat float32 buffer with a 256-byte aligned view per trainable parameter, in the manner of
+    trainer.GradStore, for a module whose backward runs through autograd (which adds into a p.grad that exists, in place)."""
+
+    def __init__(self, module):
+        self.params = [p for p in module.parameters() if p.requires_grad]
+        offs, total = [], 0
+        for p in self.params:
+            offs.append(total)
+            total += (p.numel() + 63) // 64 * 64
+        self.flat = torch.zeros(total, dtype=torch.float32, device=self.params[0].device)
+        self.views = [self.flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
+
+    def matches(self, module):
+        ps = [p for p in module.parameters() if p.requires_grad]
+        return len(ps) == len(self.params) and all(a is b for a, b in zip(ps, self.params)) and ps[0].device == self.flat.device
+
+    def zero_attach(self):
+        """What optimizer.zero_grad() is for the plain step: zeroes the buffer and makes every p.grad its view again (set-to-None would
+        drop the views)."""
+        self.flat.zero_()
+        for p, v in zip(self.params, self.views):
+            p.grad = v
+
+
+def _flat_grads(model):
+    st = model.__dict__.get("_dp_grads")
+    if st is None or not st.matches(model):
+        st = FlatGrads(model)
+        model.__dict__["_dp_grads"] = st
+    return st
+
+
+def loss_weight_sum(target, class_w, num_classes):
+    """W of seg_nll_loss's weighted mean S / W: the sum of the class weights (1 without class_w) over the rows whose target is in
+    [0, num_classes), float64 0-d on target's device.  Nothing synchronises."""
+    live = (target >= 0) & (target < num_classes)
+    if class_w is None:
+        return live.sum().double()
+    return (class_w.double()[target.clamp(0, num_classes - 1)] * live).sum()
+
+
+def global_loss(loss, weight_sum):
+    """The weighted-mean loss of the GLOBAL batch from every rank's own weighted mean `loss` = S_r / W_r and `weight_sum` = W_r (0-d
+    tensors on one device, CPU tensors under gloo included) -> (sum_r S_r / sum_r W_r, world * W_r / sum_r W_r), both in loss's dtype.
+    The second is the seed of this rank's backward(): d(global loss) / d(loss_r) is W_r / sum W, and the gradient all-reduce is followed
+    by 1 / world.  One all-reduce of two float64 values; a rank without a live row (its loss is NaN, its W_r 0) contributes nothing.
+    With one rank the pair is (loss, 1), bit for bit."""
+    dist, world = trainer._dist_world()
+    w = weight_sum.detach().double()
+    pack = torch.stack([torch.where(w > 0, loss.detach().double() * w, torch.zeros_like(w)), w])
+    dist.all_reduce(pack, op=dist.ReduceOp.SUM)
+    return (pack[0] / pack[1]).to(loss.dtype), (world * w / pack[1]).to(loss.dtype)
+
+
+def _train_pass(model, optimizer, class_w, forward, tg):
+    """forward() -> log_probs, the loss against tg, backward(), optimizer.step() -> (the loss to report, preds, counts).  Plain without a
+    process group; data parallel as the module's docstring says."""
+    _, _, on = trainer._collectives_on()
+    if not on:
+        optimizer.zero_grad()
+        loss, preds, counts = seg_nll_loss(forward(), tg, class_w, want_preds=True, want_counts=True)
+        loss.backward()
+        optimizer.step()
+        return loss.detach(), preds, counts
+    grads = _flat_grads(model)
+    grads.zero_attach()
+    sync = trainer._SYNC["on"]
+    try:
+        log_probs = forward()
+        loss, preds, counts = seg_nll_loss(log_probs, tg, class_w, want_preds=True, want_counts=True)
+        if sync:
+            reported, seed = global_loss(loss, loss_weight_sum(tg, class_w, log_probs.shape[-1]))
+            loss.backward(seed)
+        else:
+            reported = loss.detach()
+            loss.backward()
+    except Exception as e:
+        # a collective that failed inside the C library's callback: the exception it kept says why, the library's status only that
+        err = trainer._SYNC["state"]["error"] if sync else None
+        if err is not None and err is not e:
+            trainer._SYNC["state"]["error"] = None
+            raise err from e
+        raise
+    trainer.reduce_gradients([grads.flat], (optimizer,))
+    optimizer.step()
+    return reported, preds, counts
+
+
 def train_loop(data, optimizer, class_w, model, train=True, device_outputs=True):
     """One step on one batch -> (metrics {'loss'}, targets [Q, N], preds [Q, N], counts [C * C + 1]), Q = sum(w_b) the real windows.
     data: what collate_seq_ragged / collate_seq_padd return (pc_clusters, targets, filenames, centroids), optionally followed by the Python
     list n_windows (w_b per sample); without it the step counts on the host (window_counts).  class_w: float32 [C] GPU tensor or None.
     train=True: model.train(), forward, loss, backward(), optimizer.step(); else model.eval() under no_grad.  counts is
     utils.get_metrics.confusion_device's layout.  device_outputs=True: everything stays on the GPU and nothing synchronises;
-    False: targets, preds and counts are downloaded."""
+    False: targets, preds and counts are downloaded.  Under torch.distributed a train-mode step is data parallel (the module's docstring)."""
     pc_clusters, targets = data[0], data[1]
     n_windows = data[4] if len(data) > 4 else window_counts(pc_clusters, targets)
     dev = next(model.parameters()).device
@@ -71,11 +169,7 @@ def train_loop(data, optimizer, class_w, model, train=True, device_outputs=True)
     rows = x.view(B * W, N, 9).index_select(0, idx)                  # [Q, N, 9]
     tg = t.view(B * W, N).index_select(0, idx)                       # [Q, N]
     if train:
-        optimizer.zero_grad()
-        log_probs = model.forward_rows(rows)
-        loss, preds, counts = seg_nll_loss(log_probs, tg, class_w, want_preds=True, want_counts=True)
-        loss.backward()
-        optimizer.step()
+        loss, preds, counts = _train_pass(model, optimizer, class_w, lambda: model.forward_rows(rows), tg)
     else:
         with torch.no_grad():
             loss, preds, counts = seg_nll_loss(model.forward_rows(rows), tg, class_w, want_preds=True, want_counts=True)
@@ -189,7 +283,9 @@ def train_loop_clouds(clouds, optimizer, class_w, model, train=True, device_outp
     The loss is pointnet2_utils.seg_nll_loss with class_w (float32 [C] GPU tensor or None).  train=True: model.train(), forward, loss,
     backward(), optimizer.step() -- the model needs the flags forward_rows' train mode needs; else model.eval() under no_grad.
     device_outputs=True: everything stays on the GPU and nothing in the step waits for it; False: targets, preds and counts are
-    downloaded.  Not built: data parallelism."""
+    downloaded.  Under torch.distributed a train-mode step is data parallel (the module's docstring): one gradient all-reduce per step, and
+    after trainer.enable_sync_batchnorm() the BatchNorm statistics and the loss of the global batch; with the nccl backend the step still
+    never waits for the GPU."""
     return train_loop_clouds_aug(clouds, optimizer, class_w, model, train, device_outputs, augment=None)
 
 
@@ -224,11 +320,7 @@ def train_loop_clouds_aug(clouds, optimizer, class_w, model, train=True, device_
         keep = torch.from_numpy(np.concatenate([o + np.arange(n, dtype=np.int64) for o, n in zip(off, sizes)])).to(dev, non_blocking=True)
     sizes = layout                                                   # forward_ragged reads the table the kernel read: no second upload
     if train:
-        optimizer.zero_grad()
-        log_probs = model.forward_ragged(rows, sizes)
-        loss, preds, counts = seg_nll_loss(log_probs, tg, class_w, want_preds=True, want_counts=True)
-        loss.backward()
-        optimizer.step()
+        loss, preds, counts = _train_pass(model, optimizer, class_w, lambda: model.forward_ragged(rows, sizes), tg)
     else:
         with torch.no_grad():
             loss, preds, counts = seg_nll_loss(model.forward_ragged(rows, sizes), tg, class_w, want_preds=True, want_counts=True)

@@ -13,8 +13,15 @@ has no driver for it; files read and written are those of the other two families
   test       one file per step, clustered in situ with kmeans_clustering(pc, n_points, True, MAX_CLUSTERS = 18) as gru_train.test does;
              every cluster is one cloud of its own size (segment_file).
 
-The model is exact fp32 (pointnet2_utils.py), so neither driver takes a `precision` argument.  Single process: data-parallel training of
-pointnet_2_seg is not built (its train-mode BatchNorm kernels take the statistics of the local batch only)."""
+The model is exact fp32 (pointnet2_utils.py), so neither driver takes a `precision` argument.
+
+Data parallelism: both training drivers read the launch from the environment, as amp_train.train_att does --
+    python -m torch.distributed.run --nproc-per-node <GPUs> pointNet/<the CLI file> ...
+starts one process per GPU (device cuda:LOCAL_RANK whatever `device` says, nccl).  The train and validation files are sharded by rank
+(trainer.shard_indices: equal step counts), every step all-reduces the gradients once (pn2_step), rank 0 alone prints and writes
+checkpoints, and every rank takes the same checkpoint decision because reduce_epoch_metrics gives all of them the same validation loss.
+Default: every rank's BatchNorm statistics and loss are its own batch's; AMPNET_SYNC_BN=1 (trainer.enable_sync_batchnorm) makes both the
+global batch's.  Each rank draws its own dropout masks (head seed + rank) and its own augmentation (CloudAugment(seed + rank))."""
 import datetime
 import os
 import time
@@ -22,10 +29,10 @@ import time
 import numpy as np
 import torch
 
-from ..trainer import FusedAdam
+from ..trainer import FusedAdam, enable_sync_batchnorm, shard_indices
 from ..utils.get_metrics import get_accuracy, get_iou_obj, metrics_from_confusion
 from ..utils.utils import get_labels, kmeans_clustering, limit_host_threads, save_checkpoint
-from .amp_train import IOU_NAMES, reduce_epoch_metrics, start_workers
+from .amp_train import IOU_NAMES, _dist_setup, reduce_epoch_metrics, start_workers
 from .collate_fns import collate_clouds, collate_seq_ragged
 from .datasets import LidarClusterDataset, LidarDataset4Test, LidarKmeansDataset
 from .model.pointnetAtt import pointnet_2_seg
@@ -99,18 +106,42 @@ def _epoch_clouds(loader, train, model, optimizer, class_w, augment):
                                                                            device_outputs=True, augment=augment), next(model.parameters()).device)
 
 
+def _launch(device):
+    """The launch from the environment -> (rank, world, device): one process, `device` as given; under torch.distributed.run the process
+    group (amp_train._dist_setup), cuda:LOCAL_RANK and, with AMPNET_SYNC_BN=1, global-batch BatchNorm."""
+    rank, world, local = _dist_setup()
+    if world > 1:
+        device = torch.device('cuda', local)
+        if os.environ.get("AMPNET_SYNC_BN") == "1":
+            enable_sync_batchnorm()
+    return rank, world, torch.device(device)
+
+
+def _shard(files, rank, world):
+    return [files[i] for i in shard_indices(len(files), rank, world)] if world > 1 else files
+
+
+def _same_start(model, rank, world):
+    """Every rank its own dropout masks (head seed + rank) and, from rank 0, the same parameters and buffers."""
+    model._head.seed = (model._head.seed + rank) & 0xFFFFFFFF
+    if world > 1:
+        import torch.distributed as dist
+        for t in list(model.parameters()) + list(model.buffers()):
+            dist.broadcast(t.data, src=0)
+
+
 def train_pn2(dataset_folder, path_list_files, output_folder, n_points, batch_size, epochs, learning_rate, number_of_workers=4,
               model_checkpoint=None, device='cuda'):
     """Trains pointnet_2_seg(5) from scratch (or from `model_checkpoint`, a file this function wrote) on the k-means window dataset and
-    returns the per-epoch history [(train metrics, validation metrics)].  Exact fp32: no `precision` argument.  Single process: data
-    parallelism is not built for this model."""
+    returns the per-epoch history [(train metrics, validation metrics)].  Exact fp32: no `precision` argument.  Data parallel under
+    `python -m torch.distributed.run` (the module's docstring): files sharded by rank, `batch_size` per rank."""
     start = time.time()
+    rank, world, device = _launch(device)
     limit_host_threads(reserve=number_of_workers)
-    device = torch.device(device)
     with open(os.path.join(path_list_files, 'train_seg_files.txt')) as f:
-        train_files = f.read().splitlines()
+        train_files = _shard(f.read().splitlines(), rank, world)
     with open(os.path.join(path_list_files, 'val_seg_files.txt')) as f:
-        val_files = f.read().splitlines()
+        val_files = _shard(f.read().splitlines(), rank, world)
     name = 'PN2seg' + str(n_points)
     train_ds = LidarKmeansDataset(dataset_folder, task='segmentation', number_of_points=n_points, files=train_files, lazy=True)
     val_ds = LidarKmeansDataset(dataset_folder, task='segmentation', number_of_points=n_points, files=val_files, lazy=True)
@@ -120,18 +151,22 @@ def train_pn2(dataset_folder, path_list_files, output_folder, n_points, batch_si
                                                 persistent_workers=number_of_workers > 0)
     train_loader, val_loader = mk(train_ds), mk(val_ds)
     start_workers(val_loader, train_loader)
-    print(f'Dataset folder: {dataset_folder}\nSamples for training: {len(train_ds)}\nSamples for validation: {len(val_ds)}')
+    if rank == 0:
+        print(f'Dataset folder: {dataset_folder}\nSamples for training: {len(train_ds)}\nSamples for validation: {len(val_ds)}'
+              + (f' (per rank, {world} ranks)' if world > 1 else ''))
     model = pointnet_2_seg(NUM_CLASSES, device=device, **TRAIN_FLAGS)
     class_w = torch.tensor([1.0, 2.0, 2.0, 1.0, 1.0], device=device)
     optimizer = FusedAdam(model.parameters(), lr=learning_rate)
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[150, 250, 350], gamma=0.5)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters())}")
+    if rank == 0:
+        print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters())}")
     best_vloss, epoch_ini, since = 1_000_000., 0, 0
     if model_checkpoint:
         ck = torch.load(model_checkpoint, map_location=device, weights_only=True)
         model.load_state_dict(ck['model'])
         optimizer.load_state_dict(ck['optimizer'])
         epoch_ini = ck['epoch']
+    _same_start(model, rank, world)
     history = []
     for epoch in range(epoch_ini, epochs):
         t0 = time.time()
@@ -139,15 +174,18 @@ def train_pn2(dataset_folder, path_list_files, output_folder, n_points, batch_si
         va = _epoch(val_loader, False, model, optimizer, class_w)
         scheduler.step()
         history.append((tr, va))
-        print(f"epoch {epoch}: train loss {tr['loss']:.4f} acc {tr['acc']:.3f} | val loss {va['loss']:.4f} acc {va['acc']:.3f} "
-              f"iou tower {va['iou_tower']:.3f} | {time.time() - t0:.1f} s", flush=True)
+        if rank == 0:
+            print(f"epoch {epoch}: train loss {tr['loss']:.4f} acc {tr['acc']:.3f} | val loss {va['loss']:.4f} acc {va['acc']:.3f} "
+                  f"iou tower {va['iou_tower']:.3f} | {time.time() - t0:.1f} s", flush=True)
         if va['loss'] < best_vloss:
             best_vloss, since = va['loss'], 0
-            stamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
-            save_checkpoint(stamp + name, epoch, since, model, optimizer, va['acc'], batch_size, learning_rate, n_points)
+            if rank == 0:
+                stamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
+                save_checkpoint(stamp + name, epoch, since, model, optimizer, va['acc'], batch_size, learning_rate, n_points)
         else:
             since += 1
-    print("--- TOTAL TIME: %s h ---" % (round((time.time() - start) / 3600, 3)))
+    if rank == 0:
+        print("--- TOTAL TIME: %s h ---" % (round((time.time() - start) / 3600, 3)))
     return history
 
 
@@ -162,14 +200,15 @@ def train_pn2_clouds(cluster_dir, path_list_files, output_folder, files_per_step
     shuffle the points of every cloud and rotate the batch about z on the device (pn2_step.CloudAugment(seed): a function of
     (seed, step), nothing is drawn from numpy's or torch's RNG); validation is not augmented.  Returns the per-epoch history
     [(train metrics, validation metrics)].  The checkpoint loads into a default pointnet_2_seg(5) and into pn2_infer.test.  Exact fp32:
-    no `precision` argument.  Single process: data parallelism is not built for this model."""
+    no `precision` argument.  Data parallel under `python -m torch.distributed.run` (the module's docstring): files sharded by rank,
+    `files_per_step` files per rank and step, rank r augmenting with CloudAugment(seed + r)."""
     start = time.time()
+    rank, world, device = _launch(device)
     limit_host_threads(reserve=number_of_workers)
-    device = torch.device(device)
     with open(os.path.join(path_list_files, 'train_seg_files.txt')) as f:
-        train_files = f.read().splitlines()
+        train_files = _shard(f.read().splitlines(), rank, world)
     with open(os.path.join(path_list_files, 'val_seg_files.txt')) as f:
-        val_files = f.read().splitlines()
+        val_files = _shard(f.read().splitlines(), rank, world)
     train_ds = LidarClusterDataset(cluster_dir, train_files, allow_pickle=allow_pickle)
     val_ds = LidarClusterDataset(cluster_dir, val_files, allow_pickle=allow_pickle)
     # persistent workers, forked before the first pinned batch exists (amp_train.start_workers: a later fork stalls the GPU queues)
@@ -178,13 +217,16 @@ def train_pn2_clouds(cluster_dir, path_list_files, output_folder, files_per_step
                                                        persistent_workers=number_of_workers > 0)
     train_loader, val_loader = mk(train_ds, True), mk(val_ds, False)
     start_workers(val_loader, train_loader)
-    print(f'Cluster folder: {cluster_dir}\nFiles for training: {len(train_ds)}\nFiles for validation: {len(val_ds)}')
+    if rank == 0:
+        print(f'Cluster folder: {cluster_dir}\nFiles for training: {len(train_ds)}\nFiles for validation: {len(val_ds)}'
+              + (f' (per rank, {world} ranks)' if world > 1 else ''))
     model = pointnet_2_seg(NUM_CLASSES, device=device, **TRAIN_FLAGS)
     class_w = torch.tensor([1.0, 2.0, 2.0, 1.0, 1.0], device=device)
     optimizer = FusedAdam(model.parameters(), lr=learning_rate)
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[150, 250, 350], gamma=0.5)
     augment = CloudAugment(seed)
-    print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters())}")
+    if rank == 0:
+        print(f"Total Trainable Params: {sum(p.numel() for p in model.parameters())}")
     best_vloss, epoch_ini, since = 1_000_000., 0, 0
     if model_checkpoint:
         ck = torch.load(model_checkpoint, map_location=device, weights_only=True)
@@ -193,6 +235,8 @@ def train_pn2_clouds(cluster_dir, path_list_files, output_folder, files_per_step
         epoch_ini = ck['epoch']
         if isinstance(ck.get('weighing_method'), dict) and 'cloud_augment' in ck['weighing_method']:
             augment.load_state_dict(ck['weighing_method']['cloud_augment'])
+    augment.seed = (augment.seed + rank) & 0xFFFFFFFF             # data parallel: every rank its own shuffles and angles
+    _same_start(model, rank, world)
     history = []
     for epoch in range(epoch_ini, epochs):
         t0 = time.time()
@@ -200,16 +244,19 @@ def train_pn2_clouds(cluster_dir, path_list_files, output_folder, files_per_step
         va = _epoch_clouds(val_loader, False, model, optimizer, class_w, None)
         scheduler.step()
         history.append((tr, va))
-        print(f"epoch {epoch}: train loss {tr['loss']:.4f} acc {tr['acc']:.3f} | val loss {va['loss']:.4f} acc {va['acc']:.3f} "
-              f"iou tower {va['iou_tower']:.3f} | {time.time() - t0:.1f} s", flush=True)
+        if rank == 0:
+            print(f"epoch {epoch}: train loss {tr['loss']:.4f} acc {tr['acc']:.3f} | val loss {va['loss']:.4f} acc {va['acc']:.3f} "
+                  f"iou tower {va['iou_tower']:.3f} | {time.time() - t0:.1f} s", flush=True)
         if va['loss'] < best_vloss:
             best_vloss, since = va['loss'], 0
-            stamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
-            save_checkpoint(stamp + 'PN2segClouds', epoch, since, model, optimizer, va['acc'], files_per_step, learning_rate, None,
-                            weighing_method={'cloud_augment': augment.state_dict()})
+            if rank == 0:
+                stamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
+                save_checkpoint(stamp + 'PN2segClouds', epoch, since, model, optimizer, va['acc'], files_per_step, learning_rate, None,
+                                weighing_method={'cloud_augment': augment.state_dict()})   # (rank 0's: the seed as given)
         else:
             since += 1
-    print("--- TOTAL TIME: %s h ---" % (round((time.time() - start) / 3600, 3)))
+    if rank == 0:
+        print("--- TOTAL TIME: %s h ---" % (round((time.time() - start) / 3600, 3)))
     return history
 
 

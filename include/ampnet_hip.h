@@ -925,7 +925,25 @@ int ampnet_kmeans_balanced_f32(const float *feat, int n, int k, int size_min, in
  * send / recv point into `scratch` (device memory of ampnet_collective_scratch_bytes(world_size) bytes the caller owns and keeps
  * alive); the exchange must be ordered after the work already enqueued on `stream` and before what is enqueued after fn returns
  * (torch.distributed on the current stream does that).  fn returns 0 on success.  fn = NULL switches back to per-rank statistics.
- * 18 + 18 latency-bound collectives per AMP-Net step: off by default (per-rank BatchNorm is the documented deviation). */
+ * 18 + 18 latency-bound collectives per AMP-Net step: off by default (per-rank BatchNorm is the documented deviation).
+ *
+ * The six PointNet++ train entry points -- ampnet_fp_train_forward_f32 / ampnet_fp_train_backward_f32, ampnet_sa_train_forward_f32 /
+ * ampnet_sa_train_backward_f32, ampnet_seg_head_train_forward_f32 / ampnet_seg_head_train_backward_f32 -- and their ragged namesakes
+ * (ampnet_fp_train_backward_ragged_f32, ampnet_sa_train_backward_ragged_f32) follow a registered collective too, whatever world_size
+ * is.  Per BatchNorm layer:
+ *   forward   the rank's rows give ONE row (n_r, mean_r, M2_r)[cout]; one AMPNET_COLLECTIVE_ALLGATHER of 3 cout floats; every rank merges the
+ *             world_size rows in rank order (Chan) into (n, mean, M2) and uses var = M2 / n, running_var's M2 / (n - 1) with the MERGED
+ *             row count n = sum_r n_r -- the ranks may hold different numbers of rows.  scale, shift, save_mean, save_invstd and the running
+ *             statistics come out the same on every rank, bit for bit.
+ *   backward  dbeta = sum dy, dgamma = invstd (sum dy a - mean sum dy) and dbias = 0 are written from the RANK's sums (the caller's gradient
+ *             all-reduce adds them up like every other parameter gradient); one AMPNET_COLLECTIVE_ALLREDUCE_SUM of (sum dy, sum dy a)[cout]
+ *             and the rank's row count, 2 cout + 1 floats; the input gradient then uses the coefficients sum dy / n and
+ *             dgamma_global invstd / n with dgamma_global = invstd (G - mean sum dy) on the global sums.
+ * One exchange per BatchNorm layer and direction whatever the data (17 + 17 per step of pointnet_2_seg): every rank must make the same
+ * sequence of calls.  A callback that fails ends the call with AMPNET_E_LAUNCH; nothing waits or retries.  With world_size 1 every exchange
+ * is the identity and the results are those without a collective, bit for bit.  Row counts are carried as floats: with a collective
+ * registered these entry points also refuse M * world_size above their AMPNET_*_TRAIN_MAX_ROWS -- a host-side rule, conservative because the
+ * ranks' row counts differ and no rank knows the others'.  No new symbol: AMPNET_ABI_VERSION stays 18.                               */
 #define AMPNET_COLLECTIVE_ALLGATHER 0
 #define AMPNET_COLLECTIVE_ALLREDUCE_SUM 1
 #define AMPNET_SYNC_MAX_SLOTS 32

@@ -578,9 +578,11 @@ extern "C" int ampnet_probe_head_f32(const AmpnetHeadProbe *d, void *stream)
     }
 }
 
-// ---- the BatchNorm / pooling glue kernels (tests/test_bn_glue_gpu.py) ---------------------------------------------------------------------
+// ---- the BatchNorm / pooling glue kernels (tests/test_bn_glue_gpu.py, tests/test_syncbn_layers_gpu.py) -------------------------------------
 // One launch of a kernel of pw_misc.hip, of a small kernel of bwd_misc.hip or of reduce_windows (pw_bwd.hip), or of its host entry point.  The
-// host entry points branch on an installed collective (sync_bn_on()); the probe is about the single-process forms and refuses to run then.
+// host entry points branch on an installed collective (sync_bn_on()).  Ops 1 (bn_finalize), 6 (bn_bwd_finalize) and 10 (fc_bn_bwd) run with one
+// installed, through the same entry points: they then take the global-batch branch (one exchange each, so every rank must make the same calls).
+// Every other op is about the single-process form and refuses to run then.
 namespace ampnet {
 namespace {
 
@@ -859,7 +861,7 @@ extern "C" int ampnet_probe_bn_f32(const AmpnetBnProbe *d, void *stream)
     using namespace ampnet;
     AMPNET_REQUIRE(d, "probe_bn: null descriptor");
     AMPNET_REQUIRE(d->op >= 0 && d->op <= 16, "probe_bn: op %d not built", d->op);
-    AMPNET_REQUIRE(!sync_bn_on(), "probe_bn: a collective is installed; the probe launches the single-process forms only");
+    AMPNET_REQUIRE(!sync_bn_on() || d->op == 1 || d->op == 6 || d->op == 10, "probe_bn: a collective is installed; the probe launches the single-process forms only");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     switch (d->op) {
     case 0: return probe_pw_input(d, st);

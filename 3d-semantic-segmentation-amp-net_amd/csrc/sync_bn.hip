@@ -37,7 +37,9 @@ __global__ void sync_pack_kernel(const float *__restrict__ slot_ab, const int *_
     }
 }
 
-// P1 = s, P2 = -s invstd B / n, P3 = -s A / n - P2 mean with s = gamma invstd (bn_bwd_finalize_kernel / pool_bwd_kernel), global A, B, n
+// P1 = s, P2 = -s invstd B / n, P3 = -s A / n - P2 mean with s = gamma invstd (bn_bwd_finalize_kernel / pool_bwd_kernel), global A, B, n.
+// A slot with no row on ANY rank (n = 0, and with it A = B = 0) gets P2 = P3 = 0, the guard of bn_bwd_constants<true> (bn_desc.h): the plain
+// launch before this one wrote those zeros, and 0 / 0 here would replace them with NaN.
 __global__ void sync_constants_kernel(const float *__restrict__ comm, const float *__restrict__ gamma, const float *__restrict__ scale,
                                       const float *__restrict__ mean, const float *__restrict__ invstd, int n_slots, int C, float *__restrict__ P1,
                                       float *__restrict__ P2, float *__restrict__ P3)
@@ -49,10 +51,10 @@ __global__ void sync_constants_kernel(const float *__restrict__ comm, const floa
         const double A = comm[o * 2 + 0], B = comm[o * 2 + 1];
         const double is = invstd[o];
         const double sc = scale ? (double)scale[o] : (double)gamma[c] * is;
-        const double p2 = -sc * is * B / n;
+        const double p2 = n > 0.0 ? -sc * is * B / n : 0.0;
         P1[o] = (float)sc;
         P2[o] = (float)p2;
-        P3[o] = (float)(-sc * A / n - p2 * (double)mean[o]);
+        P3[o] = (float)(n > 0.0 ? -sc * A / n - p2 * (double)mean[o] : 0.0);
     }
 }
 

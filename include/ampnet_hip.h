@@ -918,8 +918,9 @@ int ampnet_kmeans_balanced_f32(const float *feat, int n, int k, int size_min, in
  * The reference is single-device: its BatchNorm layers see the whole batch.  With a collective registered and world_size > 1,
  * every TRAIN-mode BatchNorm inside ampnet_encoder_fwd_f32 / _bwd_f32, ampnet_head_* and ampnet_gru_head_* uses the statistics of the
  * global batch: the forward all-gathers the per-slot (rows, mean, M2) of every rank and merges them (Chan), the backward all-reduces
- * the per-slot (sum dy, sum dy zhat, rows).  Running statistics are then identical on every rank.  The library calls `fn` on the host,
- * between two launches:
+ * the per-slot (sum dy, sum dy zhat, rows).  Running statistics are then identical on every rank.  A slot that holds no row on any rank
+ * gets mean 0, variance 0 in the forward and P2 = P3 = 0 (dz = P1 dy) in the backward, as without a collective.  The library calls `fn`
+ * on the host, between two launches:
  *   op AMPNET_COLLECTIVE_ALLGATHER      recv[k * n_floats .. ] = rank k's send[0 .. n_floats)      (recv holds world_size * n_floats)
  *   op AMPNET_COLLECTIVE_ALLREDUCE_SUM  send == recv: element-wise float32 sum over the ranks, in place
  * send / recv point into `scratch` (device memory of ampnet_collective_scratch_bytes(world_size) bytes the caller owns and keeps
@@ -1264,8 +1265,10 @@ typedef struct AmpnetHeadProbe {
  *   14 transpose64_slot_major (src [Q * chunks, 64, 64], add [Q, 64, 64] or NULL -> dst [Q, 64, 64])
  *   15 add_identity        (dst [Q, k, k] += I)
  *   16 fill_i32_ramp       (idst [rows] = i * step)
- * Every extent is checked on the host first (win_off, part_amax and, for op 5 mode 1, part_rows are copied to the host for that); the
- * probe refuses to run while a collective is installed (the host entry points then take their global-batch branches).                  */
+ * Every extent is checked on the host first (win_off, part_amax and, for op 5 mode 1, part_rows are copied to the host for that).
+ * While a collective is installed the host entry points take their global-batch branches: ops 1, 6 and 10 run them (one exchange per
+ * call, after the checks: every rank must make the same calls; shapes beyond the scratch segment come back as AMPNET_E_ARG before any
+ * exchange), every other op refuses to run.                                                                                         */
 #define AMPNET_BN_PROBE_ITEMS 25       /* one more than bn_fold / bn_running_update / bn_param_grads take: the refusal can be reached */
 #define AMPNET_BN_PROBE_REDUCE 13      /* one more than reduce_windows_multi takes */
 typedef struct AmpnetBnProbe {

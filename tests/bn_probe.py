@@ -12,6 +12,12 @@ Bars: the project's one rule, pw_probe.bar = 8 eps sqrt(K) mag + 2 eps |x64| wit
 (1 where it sums in double: only the roundings of the outputs remain), mag = the float64 sum of the absolute terms.  Where an output is formed
 from outputs that carry a bar of their own (shift from scale, pooled from scale and shift, g from the slot sums) those bars are carried through.
 Every restatement returns {output name: (float64 value, bar)}.
+
+The global-batch forms (ampnet_set_collective: the sync_bn_on() branches of bn_finalize, bn_bwd_finalize, fc_bn_bwd; csrc/sync_bn.hip) are restated
+on the WHOLE batch from the ranks' inputs: finalize_global_ref, bn_bwd_finalize_global_ref, fc_bn_bwd_global_ref (pool_bwd's is beside pool_bwd_ref in
+tests/test_pooled_bwd_gpu.py).  Their bars add what the exchange carries in fp32 -- one rounding per rank and packed quantity, an all-reduce of
+`world` fp32 terms (`allreduced`) -- carried through to the outputs; outputs that stay per-rank keep the single-process bars.  With one rank each
+collapses to its single-process restatement.  The GPU tests are tests/test_syncbn_layers_gpu.py (two gloo ranks).
 """
 import ctypes
 
@@ -179,6 +185,47 @@ def finalize_ref(means, m2s, rows, slots, n_slots, gamma, beta, eps=BN_EPS):
             "stat_mean": (out["mean"], b_mean), "stat_uvar": (out["uvar"], bar(out["uvar"], out["uvar"], 1)), "N": out["N"]}
 
 
+def concat_ranks(ranks):
+    """(means, m2s, rows, slots) of the whole batch from the ranks' (means [P_r, C], m2s [P_r, C], rows [P_r], slots [P_r]): the partials one
+    after the other, each with its slot."""
+    return tuple(np.concatenate([np.asarray(r[i]) for r in ranks]) for i in range(4))
+
+
+def finalize_global_ref(ranks, n_slots, gamma, beta, eps=BN_EPS):
+    """bn_finalize under a collective (pw_misc.hip: rank merge -> all-gather -> gathered finalize): finalize_ref of the concatenated partials.
+    Bars: finalize_ref's own (the output roundings of the double merge) plus, with more than one rank, what the all-gather carries in fp32:
+    rank r's merged mean_r and M2_r are ONE rounding of a double sum each, d mean_r = bar(mag_r, mean_r, 1), d M2_r = bar(M2_r, M2_r, 1)
+    (M2_r is a sum of non-negative terms: its own magnitude); the rows are integers, exact.  Carried through the merge
+    mean = sum N_r mean_r / N, M2 = sum M2_r + N_r (mean_r - mean)^2:
+      d mean = sum N_r d mean_r / N;  d M2 = sum d M2_r + 2 N_r |mean_r - mean| d mean_r + N_r d mean_r^2;  d var = d M2 / N;
+      d invstd = invstd^3 d var / 2;  d uvar = d M2 / (N - 1) (N <= 1: d M2);  d scale = |gamma| d invstd;  d shift = |mean| d scale + |scale| d mean."""
+    res = finalize_ref(*concat_ranks(ranks), n_slots, gamma, beta, eps)
+    if len(ranks) == 1:
+        return res
+    gamma = f64(gamma)
+    C = gamma.shape[0]
+    mean, N = res["mean"][0], res["N"]
+    d_mean, d_m2 = np.zeros((n_slots, C)), np.zeros((n_slots, C))
+    for means, m2s, rows, slots in ranks:
+        means, m2s = f64(means), f64(m2s)
+        for s in range(n_slots):
+            sel = np.nonzero((np.asarray(slots) == s) & (np.asarray(rows) > 0))[0]
+            if not len(sel):
+                continue
+            Nr, mr, m2r = chan_merge([means[p] for p in sel], [m2s[p] for p in sel], [rows[p] for p in sel])
+            mag = sum(rows[p] * np.abs(means[p]) for p in sel) / Nr
+            dm = bar(mag, mr, 1)
+            d_mean[s] += Nr * dm / N[s]
+            d_m2[s] += bar(m2r, m2r, 1) + 2.0 * Nr * np.abs(mr - mean[s]) * dm + Nr * dm * dm
+    Ns = np.where(N > 0, N, 1.0)
+    invstd, scale = res["invstd"][0], res["scale"][0]
+    d_inv = 0.5 * invstd ** 3 * d_m2 / Ns
+    d_scale = np.abs(gamma)[None, :] * d_inv
+    add = {"mean": d_mean, "stat_mean": d_mean, "invstd": d_inv, "scale": d_scale, "shift": np.abs(mean) * d_scale + np.abs(scale) * d_mean,
+           "stat_uvar": d_m2 / np.where(N > 1, N - 1.0, 1.0)}
+    return {k: ((v[0], v[1] + add[k]) if k in add else v) for k, v in res.items()}
+
+
 def fold_ref(gamma, beta, rmean, rvar, eps=BN_EPS):
     """eval mode: scale = gamma / sqrt(rvar + eps), shift = beta - rmean scale (fp32 arithmetic in the kernel: one term each, K = 1)."""
     gamma, beta, rmean, rvar = f64(gamma), f64(beta), f64(rmean), f64(rvar)
@@ -275,6 +322,52 @@ def bn_bwd_finalize_ref(part_a, part_b, slots, slot_rows, gamma, mean, invstd, n
             "slot_ab": (ab, bar(np.stack([Am, Bm], -1), ab, 1))}
 
 
+def allreduced(sums, mags):
+    """What the all-reduce of sync_bn.hip leaves of one packed quantity: (float64 sum over the ranks, its magnitude, its bar).  Rank r packs
+    x_r as ONE fp32 rounding of a double sum: bar(mag_r, x_r, 1) each; the all-reduce then adds world fp32 terms: K = world, mag = the sum of
+    the ranks' magnitudes.  One rank: the exchange is the identity and only the rank's own rounding remains."""
+    tot, mag = sum(f64(x) for x in sums), sum(f64(m) for m in mags)
+    b = sum(bar(f64(m), f64(x), 1) for x, m in zip(sums, mags))
+    if len(sums) > 1:
+        b = b + bar(mag, tot, len(sums))
+    return tot, mag, b
+
+
+def global_bwd_constants(A, Bs, n, sv, invstd, mean):
+    """sync_constants_kernel: P1 = s, P2 = -s invstd Bs / n, P3 = -s A / n - P2 mean in double from the all-reduced A, Bs = `allreduced`
+    triples [n_slots, C] and the global rows n [n_slots] (exact: integers below 2^24 carried as floats); a slot with no row on any rank:
+    P2 = P3 = 0.  Bars: the output roundings (K = 1) plus the bars of A and Bs carried through."""
+    (A, Am, bA), (Bs, Bm, bB) = A, Bs
+    sv, invstd, mean = f64(sv), f64(invstd), f64(mean)
+    n = f64(n)[:, None]
+    live = n > 0
+    nn = np.where(live, n, 1.0)
+    P2 = np.where(live, -sv * invstd * Bs / nn, 0.0)
+    P2m = np.where(live, np.abs(sv * invstd) * Bm / nn, 0.0)
+    bP2 = np.where(live, np.abs(sv * invstd) * bB / nn, 0.0)
+    P3 = np.where(live, -sv * A / nn - P2 * mean, 0.0)
+    P3m = np.where(live, np.abs(sv) * Am / nn + P2m * np.abs(mean), 0.0)
+    bP3 = np.where(live, np.abs(sv) * bA / nn + bP2 * np.abs(mean), 0.0)
+    return {"P1": (sv, bar(np.abs(sv), sv, 1)), "P2": (P2, bar(P2m, P2, 1) + bP2), "P3": (P3, bar(P3m, P3, 1) + bP3)}
+
+
+def bn_bwd_finalize_global_ref(ranks, gamma, mean, invstd, n_slots):
+    """bn_bwd_finalize under a collective (bwd_misc.hip + sync_bn.hip: sync_pack_kernel, all-reduce, sync_constants_kernel).  ranks = one
+    (part_a, part_b, slots, slot_rows) per rank, as bn_bwd_finalize_ref takes them.  A, Bs and n are summed over the ranks and P1, P2, P3
+    come from the global sums (equal on every rank); slot_ab stays each rank's own: "slot_ab" is the LIST of the ranks' (value, bar)."""
+    own = [bn_bwd_finalize_ref(pa, pb, slots, rows, gamma, mean, invstd, n_slots) for pa, pb, slots, rows in ranks]
+    mags = []
+    for pa, pb, slots, rows in ranks:
+        pa, pb = np.abs(f64(pa)), np.abs(f64(pb))
+        mags.append(np.stack([np.stack([pa[np.asarray(slots) == s].sum(0), pb[np.asarray(slots) == s].sum(0)], -1) for s in range(n_slots)]))
+    A = allreduced([o["slot_ab"][0][..., 0] for o in own], [m[..., 0] for m in mags])
+    Bs = allreduced([o["slot_ab"][0][..., 1] for o in own], [m[..., 1] for m in mags])
+    n = sum(f64(rows) for _, _, _, rows in ranks)
+    res = global_bwd_constants(A, Bs, n, f64(gamma)[None, :] * f64(invstd), invstd, mean)
+    res["slot_ab"] = [o["slot_ab"] for o in own]
+    return res
+
+
 def param_grads_ref(slot_ab):
     """dbeta = sum_slots A, dgamma = sum_slots Bs of slot_ab [S, C, 2]; fp32 sums of S terms."""
     ab = f64(slot_ab)
@@ -316,6 +409,37 @@ def fc_bn_bwd_ref(da, z, scale, shift, mean, invstd, n_slots, per):
     bg = bar(gm, g, 3) + np.abs(sc) * (bA[slot] + zhm * bB[slot]) / per
     ab = np.stack([A, Bs], -1)
     return {"g": (g, bg), "slot_ab": (ab, np.stack([bA, bB], -1)), "sure": sure}
+
+
+def fc_bn_bwd_global_ref(das, zs, scale, shift, mean, invstd, n_slots, pers):
+    """fc_bn_bwd under a collective (bwd_misc.hip + sync_bn.hip: sync_fc_apply_kernel): rank r holds per_r = pers[r] rows of every slot
+    (da_r, z_r [n_slots * per_r, C]); the constants are the same on every rank.  The means of dy and dy zhat are taken over the ranks' rows
+    together: g_r = scale (dy_r - A / n - zhat_r Bs / n) with A, Bs the `allreduced` sums of the ranks' own (A_r, Bs_r) and n = sum pers.
+    Returns the LISTS "g", "slot_ab", "sure" of the ranks' results; slot_ab and sure are fc_bn_bwd_ref's of the rank's rows."""
+    own = [fc_bn_bwd_ref(da, z, scale, shift, mean, invstd, n_slots, per) for da, z, per in zip(das, zs, pers)]
+    mags = []
+    for da, z, per, o in zip(das, zs, pers, own):          # the magnitudes of (A_r, Bs_r), as fc_bn_bwd_ref forms them
+        da, z = f64(da), f64(z)
+        slot = np.arange(z.shape[0]) // per
+        sc, sh, mu, iv = (f64(v)[slot] for v in (scale, shift, mean, invstd))
+        dy = np.where(z * sc + sh > 0, np.abs(da), 0.0).reshape(n_slots, per, -1)
+        zhm = ((np.abs(z) + np.abs(mu)) * iv).reshape(n_slots, per, -1)
+        mags.append((dy.sum(1), (dy * zhm).sum(1)))
+    A, Am, bA = allreduced([o["slot_ab"][0][..., 0] for o in own], [m[0] for m in mags])
+    Bs, Bm, bB = allreduced([o["slot_ab"][0][..., 1] for o in own], [m[1] for m in mags])
+    n = float(sum(pers))
+    gs = []
+    for da, z, per in zip(das, zs, pers):
+        da, z = f64(da), f64(z)
+        slot = np.arange(z.shape[0]) // per
+        sc, sh, mu, iv = (f64(v)[slot] for v in (scale, shift, mean, invstd))
+        dy = np.where(z * sc + sh > 0, da, 0.0)
+        zh, zhm = (z - mu) * iv, (np.abs(z) + np.abs(mu)) * iv
+        an, bn = A[slot] / n, Bs[slot] / n
+        g = sc * (dy - an - zh * bn)
+        gm = np.abs(sc) * (np.abs(dy) + np.abs(an) + zhm * np.abs(bn))
+        gs.append((g, bar(gm, g, 3) + np.abs(sc) * (bA[slot] + zhm * bB[slot]) / n))
+    return {"g": gs, "slot_ab": [o["slot_ab"] for o in own], "sure": [o["sure"] for o in own]}
 
 
 def colsum_ref(x):
@@ -370,3 +494,20 @@ def make_fc_bn_bwd(per, C, n_slots=3, seed=0):
     shift = beta[None, :] - mean * scale
     return {"z": z, "da": da, "scale": scale.astype(np.float32), "shift": shift.astype(np.float32), "mean": mean.astype(np.float32),
             "invstd": invstd.astype(np.float32), "gamma": gamma, "beta": beta, "per": per, "C": C, "n_slots": n_slots}
+
+
+FC_PERS = ((5, 3), (70, 57))          # rows of every slot on rank 0 | rank 1 (production shards are equal; the kernel takes n from the exchange)
+FC_SLOTS = (1, 3)
+
+
+def make_fc_bn_bwd_ranks(pers, C, n_slots, seed=1):
+    """make_fc_bn_bwd at sum(pers) rows per slot -- the constants are the statistics of the WHOLE batch, the same on every rank -- dealt to
+    the ranks: rank r gets rows sum(pers[:r]) .. + pers[r] of every slot.  One dict per rank.  (Seed 1: with seed 0 one element of the
+    127-row, 512-channel case has its ReLU decision inside the fp32 bar; tests/test_bn_refs_cpu.py checks that every case is decided.)"""
+    c = make_fc_bn_bwd(sum(pers), C, n_slots, seed)
+    res, o = [], 0
+    for per in pers:
+        cut = lambda x: np.ascontiguousarray(x.reshape(n_slots, sum(pers), C)[:, o:o + per].reshape(n_slots * per, C))
+        res.append(dict(c, z=cut(c["z"]), da=cut(c["da"]), per=per))
+        o += per
+    return res

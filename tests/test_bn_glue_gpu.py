@@ -35,8 +35,8 @@ Cases and the branch each is for
                 Q 12, 3 slots, chunks {1, 3, 8, 9}, by_workgroup 0 / 1, add NULL / present.  add_identity (k 3, 64), fill_i32_ramp: exact.
   test_probe_refuses_short_buffers: every buffer of every op one element short -> AMPNET_E_ARG, nothing written.
 
-Left out: sync_bn_bwd_constants and sync_bn_fc_apply read buffers that only a collective exchange fills; the probe refuses to run with a
-collective installed, and the two-rank test covers them.
+Left out: sync_bn_bwd_constants and sync_bn_fc_apply read buffers that only a collective exchange fills; the two-rank layer tests of
+tests/test_syncbn_layers_gpu.py cover them (ops 1, 6 and 10 of the probe run with a collective installed, the others refuse).
 
 Observed worst error/bar on the MI355X: pw_input Z 0.16 (bf16 Z 0.50: half an ulp of bf16 against the 2 EPS16 |z| term), slot mean 0.02, variance 0.01
 (offset case included); bn_finalize scale 0.18, shift 0.13, mean / invstd / stat_mean / stat_uvar 0.10; its two-stage form invstd 0.39, stat_uvar 0.62

@@ -2,7 +2,9 @@
 against F.batch_norm(training=True) on the concatenated rows of a slot, the running update against a double nn.BatchNorm1d fed the slots in order,
 the pool against max_pool1d(relu(bn(z))) (channels with negative gamma included), bn_bwd_finalize / fc_bn_bwd / bn_param_grads against autograd
 through relu(batch_norm(z)), the input layers against conv_1 of cat(xyz T, x), and the committed fc_bn_bwd inputs for ReLU decisions outside
-the fp32 bar.  No GPU."""
+the fp32 bar.  The global-batch restatements (two ranks with uneven shares, a slot one rank holds no row of, a slot no rank holds a row of)
+against the same torch operations on the ranks' rows TOGETHER, within 1e-12, and each against its single-process restatement for one rank.
+No GPU."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -240,3 +242,160 @@ def test_small_refs():
         close(got[p], (src[2 * q] + src[2 * q + 1]).T + add[p], "window-major partials")
         j = q // S
         close(wg[p], (src[(j * chunks) * S + q % S] + src[(j * chunks + 1) * S + q % S]).T, "workgroup-major partials")
+
+
+# ---- the global-batch forms (two ranks with uneven shares) ---------------------------------------------------------------------------------
+GTOL = 1e-12
+
+
+def _two_rank_layer(seed, wins, C, S, chunks, cr):
+    """make_layer on the ranks' windows one after the other (rank 0 holds a multiple of S windows, so every window keeps its slot) and the
+    row ranges of the ranks."""
+    assert len(wins[0]) % S == 0
+    z, win_off, gamma, beta, slot = make_layer(seed, wins[0] + wins[1], C, S, chunks, cr)
+    cut = int(win_off[len(wins[0])])
+    offs = [win_off[:len(wins[0]) + 1], win_off[len(wins[0]):] - cut]
+    return z, gamma, beta, slot, [slice(0, cut), slice(cut, None)], offs
+
+
+def _rank_partials(z, offs, S, chunks, cr):
+    mean, m2, rows = B.chunk_partials(z, offs, chunks, cr)
+    return mean, m2, rows, B.slot_of_partial(len(rows), chunks, S)
+
+
+# rank 1: not a multiple of S windows, no row of slot 2 (3 slots) -- and, last, no row of slot 1 on either rank
+GLOBAL_LAYERS = ((20, ([5, 0, 9, 17, 4, 30], [7, 12, 0, 3]), 7, 3, 2, 16), (21, ([40, 3], [11, 64, 2]), 5, 2, 3, 24), (22, ([6, 1], [9]), 4, 1, 1, 16),
+                 (23, ([5, 0, 9, 17, 0, 30], [7, 0, 3, 2]), 6, 3, 2, 16))
+
+
+def test_finalize_global_ref_matches_batch_norm_on_the_concatenated_rows():
+    for seed, wins, C, S, chunks, cr in GLOBAL_LAYERS:
+        z, gamma, beta, slot, rows_of, offs = _two_rank_layer(seed, wins, C, S, chunks, cr)
+        ranks = [_rank_partials(z[rows_of[r]], offs[r], S, chunks, cr) for r in range(2)]
+        g = B.finalize_global_ref(ranks, S, gamma, beta, EPS)
+        if seed == 20:
+            assert not any(n > 0 and s == 2 for n, s in zip(ranks[1][2], ranks[1][3])) and g["N"][2, 0] > 0      # slot 2: rank 0's rows only
+        for s in range(S):
+            zs = t64(z[slot == s])
+            if zs.shape[0] == 0:
+                assert seed == 23 and s == 1
+                close(g["mean"][0][s], np.zeros(C), "no row anywhere: mean")
+                close(g["invstd"][0][s], np.full(C, 1.0 / np.sqrt(EPS)), "no row anywhere: invstd")
+                close(g["stat_uvar"][0][s], np.zeros(C), "no row anywhere: variance")
+                continue
+            rm, rv = torch.zeros(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)
+            y = F.batch_norm(zs, rm, rv, t64(gamma), t64(beta), training=True, momentum=1.0, eps=EPS)
+            close(z[slot == s] * g["scale"][0][s] + g["shift"][0][s], y.numpy(), f"y slot {s}", GTOL)
+            close(g["mean"][0][s], rm.numpy(), "mean", GTOL)
+            close(g["stat_mean"][0][s], rm.numpy(), "stat_mean", GTOL)
+            close(g["stat_uvar"][0][s], rv.numpy(), "unbiased variance", GTOL)
+            close(g["invstd"][0][s], 1.0 / np.sqrt(zs.numpy().var(0) + EPS), "invstd", GTOL)
+            assert g["N"][s, 0] == (slot == s).sum()
+        # per-rank statistics are NOT the global ones, and the bars of the exchange only add to finalize_ref's
+        own = B.finalize_ref(*ranks[0], S, gamma, beta, EPS)
+        assert np.abs(own["mean"][0] - g["mean"][0]).max() > 1e-3
+        whole = B.finalize_ref(*B.concat_ranks(ranks), S, gamma, beta, EPS)
+        for k in ("scale", "shift", "mean", "invstd", "stat_mean", "stat_uvar"):
+            assert np.array_equal(g[k][0], whole[k][0]) and np.all(g[k][1] >= whole[k][1]) and np.all(np.isfinite(g[k][1])), k
+        one = B.finalize_global_ref(ranks[:1], S, gamma, beta, EPS)                       # one rank: the single-process restatement
+        for k in ("scale", "shift", "mean", "invstd", "stat_mean", "stat_uvar"):
+            assert np.array_equal(one[k][0], own[k][0]) and np.array_equal(one[k][1], own[k][1]), k
+
+
+def _rank_bwd_partials(dy, zh, offs, S, chunks, cr):
+    n = B.chunk_rows_of(offs, chunks, cr)
+    Q = len(offs) - 1
+    pa, pb = np.zeros((Q * chunks, dy.shape[1])), np.zeros((Q * chunks, dy.shape[1]))
+    for q in range(Q):
+        for ch in range(chunks):
+            rr = slice(offs[q] + ch * cr, offs[q] + ch * cr + n[q, ch])
+            pa[q * chunks + ch], pb[q * chunks + ch] = dy[rr].sum(0), (dy[rr] * zh[rr]).sum(0)
+    rows = np.array([n[s::S].sum() for s in range(S)])
+    return pa, pb, B.slot_of_partial(Q * chunks, chunks, S), rows
+
+
+def test_bn_bwd_finalize_global_ref_matches_autograd_on_the_concatenated_rows():
+    for seed, wins, C, S, chunks, cr in GLOBAL_LAYERS:
+        z, gamma, beta, slot, rows_of, offs = _two_rank_layer(seed, wins, C, S, chunks, cr)
+        da = np.random.default_rng(seed + 100).standard_normal(z.shape)
+        fw = B.finalize_global_ref([_rank_partials(z[rows_of[r]], offs[r], S, chunks, cr) for r in range(2)], S, gamma, beta, EPS)
+        scale, shift, mean, invstd = (fw[k][0] for k in ("scale", "shift", "mean", "invstd"))
+        dy = np.where(z * scale[slot] + shift[slot] > 0, da, 0.0)
+        zh = (z - mean[slot]) * invstd[slot]
+        ranks = [_rank_bwd_partials(dy[rows_of[r]], zh[rows_of[r]], offs[r], S, chunks, cr) for r in range(2)]
+        f = B.bn_bwd_finalize_global_ref(ranks, gamma, mean, invstd, S)
+        dz, dgamma, dbeta = _autograd(z, da, gamma, beta, slot, S)
+        close(f["P1"][0][slot] * dy + f["P2"][0][slot] * z + f["P3"][0][slot], dz, "dz = P1 dy + P2 z + P3", GTOL)
+        pg = [B.param_grads_ref(ab[0]) for ab in f["slot_ab"]]                         # the gradient all-reduce adds the ranks' own
+        close(pg[0]["dgamma"][0] + pg[1]["dgamma"][0], dgamma, "dgamma", GTOL)
+        close(pg[0]["dbeta"][0] + pg[1]["dbeta"][0], dbeta, "dbeta", GTOL)
+        own = B.bn_bwd_finalize_ref(*ranks[0], gamma, mean, invstd, S)
+        assert np.abs(own["P3"][0] - f["P3"][0]).max() > 1e-4                          # per-rank constants are not the global ones
+        one = B.bn_bwd_finalize_global_ref(ranks[:1], gamma, mean, invstd, S)
+        for k in ("P1", "P2", "P3"):
+            assert np.array_equal(one[k][0], own[k][0]) and np.all(one[k][1] >= own[k][1]), k
+        assert np.array_equal(one["slot_ab"][0][0], own["slot_ab"][0]) and np.array_equal(one["slot_ab"][0][1], own["slot_ab"][1])
+        if seed == 23:                                                               # a slot with no row on any rank
+            assert np.all(f["P2"][0][1] == 0) and np.all(f["P3"][0][1] == 0) and np.all(f["P2"][1][1] == 0) and np.all(f["P3"][1][1] == 0)
+            assert np.all(np.isfinite(f["P1"][0])) and all(np.all(np.isfinite(f[k][i])) for k in ("P1", "P2", "P3") for i in (0, 1))
+
+
+def test_fc_bn_bwd_global_ref_matches_autograd_and_cases_are_decided():
+    for pers in B.FC_PERS:
+        for C in B.FC_C:
+            for S in B.FC_SLOTS:
+                rk = B.make_fc_bn_bwd_ranks(pers, C, S)
+                r = B.fc_bn_bwd_global_ref([c["da"] for c in rk], [c["z"] for c in rk], rk[0]["scale"], rk[0]["shift"], rk[0]["mean"], rk[0]["invstd"], S, pers)
+                assert all(s.all() for s in r["sure"]), f"per {pers}, C {C}, {S} slots: a ReLU decision inside the fp32 bar"
+    pers, C, S = (5, 3), 6, 3
+    rk = B.make_fc_bn_bwd_ranks(pers, C, S)
+    whole = B.make_fc_bn_bwd(sum(pers), C, S, 1)                                      # (the seed make_fc_bn_bwd_ranks uses)
+    z, da = B.f64(whole["z"]), B.f64(whole["da"])
+    zz = z.reshape(S, sum(pers), C)
+    mean, invstd = zz.mean(1), 1.0 / np.sqrt(zz.var(1) + EPS)
+    scale = whole["gamma"][None, :] * invstd
+    shift = whole["beta"][None, :] - mean * scale
+    r = B.fc_bn_bwd_global_ref([c["da"] for c in rk], [c["z"] for c in rk], scale, shift, mean, invstd, S, pers)
+    slot = np.arange(S * sum(pers)) // sum(pers)
+    dz, dgamma, dbeta = _autograd(z, da, whole["gamma"], whole["beta"], slot, S)
+    dzz, o = dz.reshape(S, sum(pers), C), 0
+    for i, per in enumerate(pers):
+        close(r["g"][i][0], dzz[:, o:o + per].reshape(S * per, C), f"g of rank {i}", GTOL)
+        o += per
+    pg = [B.param_grads_ref(ab[0]) for ab in r["slot_ab"]]
+    close(pg[0]["dgamma"][0] + pg[1]["dgamma"][0], dgamma, "dgamma", GTOL)
+    close(pg[0]["dbeta"][0] + pg[1]["dbeta"][0], dbeta, "dbeta", GTOL)
+    own = B.fc_bn_bwd_ref(rk[0]["da"], rk[0]["z"], scale, shift, mean, invstd, S, pers[0])
+    assert np.abs(own["g"][0] - r["g"][0][0]).max() > 1e-3                             # the rank's own means are not the global ones
+    one = B.fc_bn_bwd_global_ref([rk[0]["da"]], [rk[0]["z"]], scale, shift, mean, invstd, S, pers[:1])
+    for k in ("g", "slot_ab"):
+        assert np.array_equal(one[k][0][0], own[k][0]) and np.array_equal(one[k][0][1], own[k][1]), k
+
+
+def test_pool_bwd_global_ref_matches_autograd_on_the_concatenated_rows():
+    import test_pooled_bwd_gpu as PB
+    C = PB.C
+    for sm in (0, 1):
+        hs = PB.pool_ranks([dict(sizes=[5, 3, 9, 4, 7, 2], S=3, sm=sm), dict(sizes=[6, 1, 8], S=3, sm=sm)], (31, 32), exact=True)
+        g = PB.pool_bwd_global_ref(hs)
+        z = np.concatenate([h["z32"] for h in hs]).astype(np.float64)
+        slot = np.concatenate([h["slot"] for h in hs])
+        zt, gm, bt = t64(z).requires_grad_(True), t64(hs[0]["gamma"]), t64(hs[0]["beta"])
+        y = torch.zeros_like(zt)
+        for s in range(3):
+            idx = torch.from_numpy(np.nonzero(slot == s)[0])
+            y = y.index_copy(0, idx, torch.relu(F.batch_norm(zt[idx], None, None, gm, bt, training=True, eps=EPS)))
+        loss, dys, row0 = 0.0, np.zeros_like(z), 0
+        for h, r in zip(hs, g["ranks"]):
+            for q in range(h["Q"]):
+                pr = PB.prow_of(q, h["Q"], 3, sm)
+                rows = torch.from_numpy(h["arg"][q].astype(np.int64) + row0)
+                loss = loss + (y[rows, torch.arange(C)] * t64(h["d_pooled"][pr])).sum()
+                dys[h["arg"][q] + row0, np.arange(C)] += r["dpm"][pr]
+            row0 += h["rows"]
+        loss.backward()
+        close(g["P1"][0][slot] * dys + g["P2"][0][slot] * z + g["P3"][0][slot], zt.grad.numpy(), f"dz, slot_major {sm}", GTOL)
+        assert np.abs(g["ranks"][1]["P3"] - g["P3"][0]).max() > 1e-5                       # the rank's own constants are not the global ones
+        one = PB.pool_bwd_global_ref(hs[:1])
+        for k in ("P1", "P2", "P3"):
+            assert np.array_equal(one[k][0], one["ranks"][0][k]), k

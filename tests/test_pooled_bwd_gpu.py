@@ -25,7 +25,8 @@ sums, the whole layer) run their defect checks in fp32 and f32x3 only: there the
 window.
 
 Not covered (no caller): the sparse GradSrc (arg / dpool) of pw_dgrad / pw_wgrad -- EncBwd::sparse() has no call site -- and
-PwDgrad.rowmap / srows, which nothing in csrc/ sets.  Global-batch BatchNorm (sync_bn_bwd_constants inside pool_bwd) needs a process group.
+PwDgrad.rowmap / srows, which nothing in csrc/ sets.  Global-batch BatchNorm (sync_bn_bwd_constants inside pool_bwd) needs a process group:
+tests/test_syncbn_layers_gpu.py holds it to pool_bwd_global_ref below on two ranks.
 """
 import numpy as np
 import pytest
@@ -135,6 +136,26 @@ def pool_inputs(c, seed, zb=False):
                 arg=arg, zext=zext, d_pooled=d_pooled, zb=zb)
 
 
+def pool_ranks(cfgs, seeds, exact=False):
+    """pool_inputs of every rank (its own windows and seed) under ONE BatchNorm: gamma and beta of rank 0 and the statistics of the ranks' rows
+    together, per slot (every rank's window count is a multiple of S, so window q of any rank belongs to slot q % S of the whole batch).
+    The sign of a channel's scale is the sign of its gamma, the same for every seed, so each rank's arg / zext stay the extremes the forward
+    would have kept.  exact: the constants stay float64 (the CPU tests against autograd); otherwise fp32, as the kernels get them."""
+    hs = [pool_inputs(c, s) for c, s in zip(cfgs, seeds)]
+    S = hs[0]["S"]
+    assert all(h["S"] == S and h["Q"] % S == 0 for h in hs)
+    z, slot = np.concatenate([h["z32"] for h in hs]).astype(np.float64), np.concatenate([h["slot"] for h in hs])
+    gamma, beta = hs[0]["gamma"], hs[0]["beta"]
+    mean = np.stack([z[slot == s].mean(0) for s in range(S)])
+    invstd = np.stack([1.0 / np.sqrt(z[slot == s].var(0) + 1e-5) for s in range(S)])
+    scale = gamma * invstd
+    cast =(lambda x: x) if exact else f32
+    for h in hs:
+        assert np.array_equal(h["scale"] < 0, scale < 0)
+        h.update(gamma=gamma, beta=beta, scale=cast(scale), shift=cast(beta - mean * cast(scale)), mean=cast(mean), invstd=cast(invstd))
+    return hs
+
+
 # ---- float64 restatements ------------------------------------------------------------------------------------------------------
 def pool_bwd_ref(h, neighbour_p1=False, skip_window=None):
     """pool_bwd (kernels.h: PoolBwd): dpm[prow(q)] = d_pooled[prow(q)] where arg >= 0 and fmaf(zext, s, t) > 0 (exact in float64 as
@@ -167,6 +188,20 @@ def pool_bwd_ref(h, neighbour_p1=False, skip_window=None):
     P2m = np.abs(sc * inv) * Bm / nn
     P3m = np.abs(sc) * Am / nn + P2m * np.abs(mu)
     return dict(dpm=dpm, P1=P1, P2=P2, P3=P3, A=A, Bs=Bs, Am=Am, Bm=Bm, P2m=P2m, P3m=P3m, n=n)
+
+
+def pool_bwd_global_ref(hs):
+    """pool_bwd under a collective (bwd_misc.hip: pool_bwd -> sync_bn_bwd_constants): hs = the ranks' pool_inputs, with the SAME forward
+    constants (scale, shift, mean, invstd) on every rank.  dpm and slot_ab are each rank's own (`ranks` = the ranks' pool_bwd_ref); P1, P2, P3
+    come from A, Bs and the window rows summed over the ranks, with bn_probe's bars of the exchange (allreduced, global_bwd_constants)."""
+    import bn_probe as B
+    assert all(np.array_equal(h[k], hs[0][k]) for h in hs for k in ("scale", "shift", "mean", "invstd"))
+    ranks = [pool_bwd_ref(h) for h in hs]
+    A = B.allreduced([r["A"] for r in ranks], [r["Am"] for r in ranks])
+    Bs = B.allreduced([r["Bs"] for r in ranks], [r["Bm"] for r in ranks])
+    res = B.global_bwd_constants(A, Bs, sum(r["n"] for r in ranks), hs[0]["scale"], hs[0]["invstd"], hs[0]["mean"])
+    res["ranks"] = ranks
+    return res
 
 
 def act_prev(h, zp=None):

@@ -51,6 +51,7 @@ extern "C" int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AMPNET_REQUIRE(d->Q >= 1 && d->chunks >= 1 && d->chunk_rows >= 1 && d->n_slots >= 1 && d->cout >= 1 && d->cin >= 1,
                    "probe_pw_gemm: bad sizes");
+    AMPNET_REQUIRE(d->tail == 0 || d->tail == 1, "probe_pw_gemm: tail = %d is neither 0 (ends at pfin_out_n) nor 1 (a_bf16 / z_bf16 follow)", d->tail);
     int64_t rows = 0;
     int max_rows = 0;
     if (d->uniform_rows > 0) {
@@ -95,6 +96,9 @@ extern "C" int ampnet_probe_pw_gemm_f32(const AmpnetPwGemmProbe *d, void *stream
     }
     PwGemm g;
     g.A = d->A; g.lda = d->lda; g.cin = d->cin;
+    // bf16 tensors: A_n / Z_n are in elements, the checks above hold; pw_gemm's own checks gate the rest.  tail == 0: a descriptor that
+    // ends at pfin_out_n (callers from before the two flags) -- reading on would be reading past the caller's struct
+    if (d->tail == 1) { g.a_bf16 = d->a_bf16; g.z_bf16 = d->z_bf16; }
     g.W = d->W; g.ldw = d->ldw; g.w_win_stride = d->w_win_stride; g.perwin_slot_major = d->perwin_slot_major;
     g.bias = d->bias; g.bias_win_stride = d->bias_win_stride;
     g.pro_scale = d->pro_scale; g.pro_shift = d->pro_shift;

@@ -1073,7 +1073,12 @@ int ampnet_profile_read(int max_rows, char *names, double *ms, long long *calls,
  * (PwGemm, PwBwd + GradSrc / ActSrc): see the comments there for what every field means.  Every pointer comes with
  * its extent in ELEMENTS (`*_n`); before anything is launched the probe checks on the host that each extent covers
  * what the kernel will touch (win_off is copied to the host and checked for monotonicity) and returns AMPNET_E_ARG
- * otherwise.  The current matrix precision picks the kernel family, as it does for the product paths.        */
+ * otherwise.  The current matrix precision picks the kernel family, as it does for the product paths.
+ * AmpnetPwGemmProbe.a_bf16 / z_bf16 (the last two fields) declare A / Z to be bf16 tensors behind the float pointers, as
+ * precision mode 3 stores them; A_n / Z_n count ELEMENTS of whichever type, so the same extent checks hold.  They are
+ * read only where `tail` == 1: a caller built against the descriptor that ended at pfin_out_n left that word (its pad0)
+ * at 0, and nothing past its shorter struct is touched.  The probe adds no check of its own on the flags: pw_gemm's argument checks (a bf16 precision mode, lda % 8 == 0 for a bf16 A) are
+ * the gate, as in the product.                                                                                */
 typedef struct AmpnetPwGemmProbe {
     const float *A; int64_t A_n; int32_t lda, cin;
     const float *W; int64_t W_n; int64_t w_win_stride; int32_t ldw, perwin_slot_major;
@@ -1090,9 +1095,10 @@ typedef struct AmpnetPwGemmProbe {
     const float *fin_gamma, *fin_beta; int64_t fin_in_n;       /* [cout] each */
     float *fin_scale, *fin_shift, *fin_mean, *fin_invstd, *fin_smean, *fin_suvar; int64_t fin_out_n;   /* [n_slots, cout] each */
     const float *pfin_sum, *pfin_sq; int64_t pfin_n;           /* [pfin_parts, cin] each */
-    const int32_t *pfin_rows; int64_t pfin_rows_n; int32_t pfin_parts, pad0;
+    const int32_t *pfin_rows; int64_t pfin_rows_n; int32_t pfin_parts, tail;   /* tail (the former pad0, 0 there): 1 = a_bf16 / z_bf16 follow */
     const float *pfin_gamma, *pfin_beta; int64_t pfin_in_n;    /* [cin] each */
     float *pfin_scale, *pfin_shift, *pfin_mean, *pfin_invstd, *pfin_smean, *pfin_suvar; int64_t pfin_out_n;   /* [n_slots, cin] each */
+    int32_t a_bf16, z_bf16;                                     /* A / Z are bf16 tensors (PwGemm.a_bf16 / z_bf16); A_n / Z_n stay in ELEMENTS */
 } AmpnetPwGemmProbe;
 
 /* kind 0 = pw_bwd_fused (which picks the split / bf16 kernels by itself, as in the product).  dbg_row_wrap is always 0.

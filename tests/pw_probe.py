@@ -4,7 +4,9 @@ The C side is the test hook of include/ampnet_hip.h ("test hooks"): ampnet_probe
 buffers the test chose, after checking every extent on the host.  This module holds
   * the ctypes mirrors of AmpnetPwGemmProbe / AmpnetPwBwdProbe / AmpnetPwPlan,
   * a float64 restatement of each kernel's contract, written from the comments in csrc/kernels.h (PwGemm, PwBwd, GradSrc, ActSrc),
-  * the one error bar every comparison uses (`bar`).
+  * the one error bar every comparison uses (`bar`),
+  * the bf16 side of the forward: `bf16_rne`, the rounded-operand reference `gemm_ref(operands="bf16")` with its ambiguity mask and
+    widening, and `bf16_bracket` for a stored bf16 Z (held to torch and to negative controls by tests/test_pw_refs_cpu.py).
 Host side only; the GPU tests are tests/test_pw_layers_gpu.py.
 """
 import ctypes
@@ -46,10 +48,15 @@ class PwGemmProbe(ctypes.Structure):
                 ("fin_scale", _p), ("fin_shift", _p), ("fin_mean", _p), ("fin_invstd", _p), ("fin_smean", _p), ("fin_suvar", _p),
                 ("fin_out_n", _i64),
                 ("pfin_sum", _p), ("pfin_sq", _p), ("pfin_n", _i64),
-                ("pfin_rows", _p), ("pfin_rows_n", _i64), ("pfin_parts", _i32), ("pad0", _i32),
+                ("pfin_rows", _p), ("pfin_rows_n", _i64), ("pfin_parts", _i32), ("tail", _i32),    # tail = 1: a_bf16 / z_bf16 follow
                 ("pfin_gamma", _p), ("pfin_beta", _p), ("pfin_in_n", _i64),
                 ("pfin_scale", _p), ("pfin_shift", _p), ("pfin_mean", _p), ("pfin_invstd", _p), ("pfin_smean", _p), ("pfin_suvar", _p),
-                ("pfin_out_n", _i64)]
+                ("pfin_out_n", _i64),
+                ("a_bf16", _i32), ("z_bf16", _i32)]       # A / Z are bf16 tensors; A_n / Z_n stay in elements (read where tail == 1)
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.tail = 1
 
 
 class PwBwdProbe(ctypes.Structure):
@@ -295,11 +302,52 @@ def dscale32(p):
 
 
 # ---- forward: Z = pro(A) W^T + bias (+ identity) -------------------------------------------------------------------------------
+def bf16_rne(x):
+    """float64 -> the nearest value with an 8-bit significand (bf16), ties to even.  No subnormals, no overflow (not in these inputs)."""
+    m, e = np.frexp(np.asarray(x, dtype=np.float64))              # |m| in [0.5, 1): m * 256 in [128, 256), the 8-bit integer grid
+    return np.ldexp(np.round(m * 256.0) / 256.0, e)               # np.round: halves to even
+
+
+def ulp_bf16(x):
+    """spacing of the bf16 values around x (0 at 0)."""
+    x = np.asarray(x, dtype=np.float64)
+    _, e = np.frexp(x)
+    return np.where(x == 0.0, 0.0, np.ldexp(1.0, e - 8))
+
+
+def ambiguous_bf16(v):
+    """mask of the v > 0 that lie within 2^-22 |v| of a bf16 rounding midpoint: the kernel forms v in fp32 (one rounding of the fma,
+    exact before it, one of the dropout scale: 2 * 2^-24 |v| < 2^-22 |v|) where the reference forms it in float64, so only these can
+    round to different bf16 neighbours.  In units of the bf16 spacing: |frac(256 m) - 1/2| <= 2^-14 m, v = m 2^e."""
+    m, _ = np.frexp(np.asarray(v, dtype=np.float64))
+    x = m * 256.0
+    return (m > 0.0) & (np.abs(x - np.floor(x) - 0.5) <= 2.0 ** -14 * m)
+
+
+def ambiguity_widening(mask, v, Wr):
+    """sum_k [mask] ulp_bf16(v_k) |w'_jk| [rows, cout]: what the ambiguous elements of the rounded prologue output can move each output
+    by (one bf16 step of that operand each).  v [rows, cin] the unrounded prologue output, Wr [cin, cout] the rounded weights."""
+    return np.where(mask, ulp_bf16(v), 0.0) @ np.abs(Wr)
+
+
+def bf16_bracket(z64, b):
+    """(lowest, highest) bf16 value a correct round-to-nearest-even store of a value within b of z64 can give: a stored bf16 Z is right
+    if and only if it lies between them."""
+    z64 = np.asarray(z64, dtype=np.float64)
+    return bf16_rne(z64 - b), bf16_rne(z64 + b)
+
+
 def gemm_ref(A, cin, cout, W, win_off, n_slots, pro=None, drop=None, bias=None, bias_win_stride=0, w_win_stride=0, slot_major=0,
-             identity_k=0, rows_window=None):
+             identity_k=0, rows_window=None, operands="fp32"):
     """float64 Z [rows, cout] and the operand magnitudes (|u| |v|) [rows, cout].
     A [rows, >= cin] fp32; W shared [cout, >= cin] or, w_win_stride != 0, flat [.., cin, cout] k-major at pidx(q) * w_win_stride;
-    pro = (scale [S, cin], shift [S, cin]) -> relu(a s + t); drop = (p, (seed, stream)) on pro(a) at index row * cin + k."""
+    pro = (scale [S, cin], shift [S, cin]) -> relu(a s + t); drop = (p, (seed, stream)) on pro(a) at index row * cin + k.
+    operands="bf16": the contract of the bf16-operand kernels -- the prologue output (A itself without a prologue) and the weights are
+    rounded to bf16, products exact, sums in float64, bias / identity unrounded; the magnitudes are those of the ROUNDED operands, and a
+    third result {"mask" [rows, cin], "v" [rows, cin], "wid" [rows, cout], "share"} describes the ambiguous prologue outputs
+    (ambiguous_bf16 / ambiguity_widening; all zero without a prologue: fp32 -> bf16 is deterministic and a bf16 A is exact)."""
+    assert operands in ("fp32", "bf16")
+    rnd = operands == "bf16"
     A = np.asarray(A, dtype=np.float64)[:, :cin]
     rows = A.shape[0]
     q = win_of_rows(win_off) if rows_window is None else rows_window
@@ -316,6 +364,13 @@ def gemm_ref(A, cin, cout, W, win_off, n_slots, pro=None, drop=None, bias=None, 
             um = np.where(k, um * ds, 0.0)
     else:
         u, um = A, np.abs(A)
+    amb = None
+    if rnd:
+        mask = ambiguous_bf16(u) if pro is not None else np.zeros(u.shape, dtype=bool)
+        pos = int((u > 0.0).sum())
+        amb = {"mask": mask, "v": u, "wid": np.zeros((rows, cout)), "share": float(mask.sum()) / pos if pos else 0.0}
+        u = bf16_rne(u)
+        um = np.abs(u)
     Z = np.zeros((rows, cout))
     M = np.zeros((rows, cout))
     if w_win_stride:
@@ -324,10 +379,16 @@ def gemm_ref(A, cin, cout, W, win_off, n_slots, pro=None, drop=None, bias=None, 
             r = q == qq
             pidx = (qq % n_slots) * (Q // n_slots) + qq // n_slots if slot_major else qq
             Wq = Wf[pidx * w_win_stride:pidx * w_win_stride + cin * cout].reshape(cin, cout)
+            if rnd:
+                Wq = bf16_rne(Wq)
+                amb["wid"][r] = ambiguity_widening(mask[r], amb["v"][r], Wq)
             Z[r] = u[r] @ Wq
             M[r] = um[r] @ np.abs(Wq)
     else:
         Wm = np.asarray(W, dtype=np.float64)[:cout, :cin]
+        if rnd:
+            Wm = bf16_rne(Wm)
+            amb["wid"] = ambiguity_widening(mask, amb["v"], Wm.T)
         Z = u @ Wm.T
         M = um @ np.abs(Wm).T
     if bias is not None:
@@ -343,6 +404,8 @@ def gemm_ref(A, cin, cout, W, win_off, n_slots, pro=None, drop=None, bias=None, 
         cols = np.arange(cout)
         Z[:, cols % (identity_k + 1) == 0] += 1.0
         M[:, cols % (identity_k + 1) == 0] += 1.0
+    if rnd:
+        return Z, M, amb
     return Z, M
 
 

@@ -9,8 +9,26 @@ Every case also checks: outputs pre-filled with NaN are finite where the contrac
 (padding columns, partial slots past the plan); a second run is bitwise identical; the kernel that ran is the instantiation the case is
 meant for (profile names: " x3" in f32x3 for every split-eligible shape, " bf16" in the bf16 modes).
 
+The forward in the bf16 modes is held in TWO tiers (check_gemm).  Tier 1, the project bar: the reference above on the operands as given
+(a bf16 A: its rounded values), eps = 2^-8, a bf16 Z with 2 eps |z64| more.  Tier 2, the contract bar (families "pw_gemm t2 ..."): the
+reference on the bf16-ROUNDED prologue output and weights (pw_probe.gemm_ref(operands="bf16")), eps = 2^-24 -- fp32 accumulation is the
+only error left; a bf16 Z must be the round-to-nearest-even of a value within the bar (pw_probe.bf16_bracket); the statistics, fin_*
+constants and pool extremes follow the UNROUNDED accumulator.  The reference forms the prologue in float64, the kernel in fp32: a prologue
+output within 2^-22 |v| of a bf16 rounding midpoint may round either way ("ambiguous"; asserted < 2^-10 of the positive ones per case,
+observed 3.6e-5 .. 3.1e-4), and each output carries sum_k [ambiguous] ulp_bf16(v_k) |w'_jk| on top of its bar (families "... amb";
+outputs, slots and extremes that no ambiguous element reaches keep the plain bar and are reported apart).  tests/test_pw_refs_cpu.py
+shows on the c128_128 data that a truncating store, statistics of the stored z and a truncated weight image each land outside tier 2
+and inside tier 1.
+Observed on the MI355X, worst error/bar, bf16_train / bf16_store: tier 1 Z 0.007 / 0.011, statistics 0.001 / 0.001, pool 0.002 / 0.003;
+tier 2 Z 0.077 / 0.0625 (bf16 Z: the lowest rung of bracket_ratio's ladder), statistics 0.027 / 0.013, pool 0.032 / 0.023; tier 2 with an
+ambiguous element in reach: Z 0.998 / 1.0 (rung (1/2, 1]), statistics 0.51 / 0.12.  The two above 0.5 are the reference's own ambiguity,
+not accumulation error: where an ambiguous element did round the other way the output is off by exactly its widening, i.e. at
+widening / (bar + widening), just under 1 (every output beyond the plain bar had an ambiguous element: 118 of 118 on ones160, 246 of 246
+on c128_128, against 0.014 / 0.035 on the others); see tier_moment_bars for the statistics.
+
 Cases, from the dispatch of pw_gemm / launch_pw / launch_pw_x and pw_bwd_fused / launch_fused / pw_bwd_fused_x3 / pw_bwd_fused_bf16:
-  forward (fp32 and f32x3; c64_64, c128_128, pool, c64_40 and drop128 in fp32 with AMPNET_PW_PIPE=1 and =0)
+  forward (fp32, f32x3, bf16_train: every case, pool_eval there asserted as pw_gemm's refusal, chunk512 skipped; bf16_store: the
+  (a_bf16, z_bf16) pairs of FWD_STORE; c64_64, c128_128, pool, c64_40 and drop128 in fp32 with AMPNET_PW_PIPE=1 and =0)
     c64_64    cin 64 -> 64, no prologue, per-workgroup statistics, ragged windows, 3 slots
     c64_128   cin 64 -> 128, BN+ReLU prologue, statistics; Q = 576, 9 slots, 300 rows (the persistent loop wraps)
     c128_128  cin 128 -> 128 BN+ReLU, Z + statistics (split-eligible), 12 slots, windows of 1 .. 700 rows
@@ -27,6 +45,11 @@ Cases, from the dispatch of pw_gemm / launch_pw / launch_pw_x and pw_bwd_fused /
     c128_200  cin 128 -> 200 (not a multiple of 128: not split-eligible), ldz 208
     pfin      cin 128 -> 128 with the consumer-side finalize of the input's BatchNorm (pfin_*)
     chunk512  the split-eligible c128_128 shape handed chunk_rows 512 (the non-split chunking): refused or correct
+    conv2     cin 64 -> 128, no prologue, a per-window bias (bias_win_stride), 1 slot: the head's conv_2
+    ones      cin 128 -> 128 BN+ReLU, 40 windows of ONE row, 4 slots: every prefetch crosses a window (narrowed to 32 columns)
+    ones160   the same with 160 windows: the 128-column instantiations (split-eligible)
+    bf16_store only: drop128 with a bias (the head's conv_3), drop64 with a bias, cout 5, ldz 8 (the head's conv_4)
+    refusals  a bf16 A or Z in fp32 / f32x3, a bf16 A with lda 68: pw_gemm's own checks, outputs left at their sentinels
   backward (fp32, f32x3, bf16_train, bf16_store)
     b128_128 dense / b128_gram Gram / b128_64 act / b128_64lin / b64_64 act / b64_64add act+add / b64_64lin lin+add / b64_128 /
     b64_128drop dropout / bmm64 per-window weights + items_per_block / slotw Gram with w_slot_stride + bias_slot /
@@ -81,6 +104,8 @@ def is_sentinel(t):
     a = t.detach().cpu()
     if a.dtype == torch.int32:
         return bool((a == -7).all())
+    if a.dtype == torch.bfloat16:
+        return bool((a.contiguous().view(torch.int16) == NAN_BITS >> 16).all())
     return bool((a.view(torch.int32) == NAN_BITS).all())
 
 
@@ -135,7 +160,29 @@ FWD = {
     "c128_200": dict(cin=128, cout=200, ldz=208, sizes=[129, 255, 4], S=3, pro=1, stats="wg"),
     "pfin": dict(cin=128, cout=128, sizes=[127, 129, 255, 257, 31, 33] * 8, S=3, pro=1, stats="wg", pfin=True),
     "chunk512": dict(cin=128, cout=128, sizes=[700, 257, 129, 1] * 16, S=2, pro=1, stats="wg", chunk512=True),
+    "conv2": dict(cin=64, cout=128, sizes=[33, 1, 257, 127, 700, 31], S=1, pro=0, stats="wg", biaswin=True),
+    "ones": dict(cin=128, cout=128, sizes=[1] * 40, S=4, pro=1, stats="wg"),
+    "ones160": dict(cin=128, cout=128, sizes=[1] * 160, S=4, pro=1, stats="wg"),
 }
+# bf16_store: the (a_bf16, z_bf16) pairs the product launches each shape with (csrc/encoder.hip, head.hip), and what the head's layers add
+FWD_STORE = {
+    "c64_64": [(1, 1), (0, 1)], "c64_128": [(1, 1)], "c128_128": [(1, 1)], "pool": [(1, 0)], "pool_z": [(1, 1)], "drop128": [(1, 1)],
+    "drop64": [(1, 0)], "c64_40": [(1, 1)], "c128_200": [(1, 1)], "pfin": [(1, 1)], "bmm": [(1, 1)], "conv2": [(0, 1)], "ones": [(1, 1)],
+    "ones160": [(1, 1)],
+}
+FWD_STORE_EXTRA = {"drop128": dict(bias=True),                        # as the head's conv_3
+                   "drop64": dict(bias=True, cout=5, ldz=8)}          # as the head's conv_4
+FWD_MODES = ["fp32", "f32x3", "bf16_train", "bf16_store"]
+POOL_EVAL_REFUSAL = "the pool epilogue without argmax rows is the fp32 eval form"
+
+
+def fwd_case(name, mode):
+    return dict(FWD[name], **FWD_STORE_EXTRA.get(name, {})) if mode == "bf16_store" else FWD[name]
+
+
+def fwd_params():
+    ps = [pytest.param(name, mode, None, id=f"{name}-{mode}") for mode in FWD_MODES[:3] for name in FWD]
+    return ps + [pytest.param(name, "bf16_store", pair, id=f"{name}-bf16_store-a{pair[0]}z{pair[1]}") for name in FWD_STORE for pair in FWD_STORE[name]]
 
 
 def fwd_x3_expected(c, mode, n_blocks):
@@ -150,20 +197,21 @@ def fwd_x3_expected(c, mode, n_blocks):
             and not c.get("perwin") and not c.get("uniform") and (bool(c.get("pool")) != c.get("Z", True)) and c.get("stats") != "chunk")
 
 
-def fwd_name(c, n_blocks, split):
+def fwd_name(c, n_blocks, split, mode="fp32"):
     """The profile name of the instantiation pw_gemm picks (pw_gemm.hip: pw_gemm's NT choice and tiny-problem narrowing, launch_pw_y's name)."""
     cout = c["cout"]
     nt = 4 if cout > 64 else (2 if cout > 32 else 1)
     while nt > 1 and not c.get("pool") and c.get("pro") != 2 and n_blocks * -(-cout // (32 * nt)) < 128:
         nt //= 2
     return (f"pw_gemm<{c['cin']},{32 * nt}>" + ("+store" if c.get("Z", True) else "") + ("+pool" if c.get("pool") else "")
-            + (" x3" if split else ""))
+            + (" x3" if split else (" bf16" if mode.startswith("bf16") else "")))
 
 
-def make_gemm(name, c, mode, seed):
+def gemm_host(c, seed, a_bf16=0):
+    """The host side of a forward case: every input as numpy fp32 (no GPU, no library).  a_bf16: A holds bf16 values (rounded here, so
+    that the float64 references read what the kernel reads)."""
     g = rng(seed)
     cin, cout, S = c["cin"], c["cout"], c["S"]
-    ldz = c.get("ldz", cout)
     uniform = c.get("uniform", 0)
     if uniform:
         Q = c["Q"]
@@ -173,11 +221,45 @@ def make_gemm(name, c, mode, seed):
         Q = len(sizes)
     wo = offsets(sizes)
     rows = int(wo[-1])
-    max_rows = max(sizes)
     A = f32(g.standard_normal((rows, cin)))
     if c.get("dup"):
         A[wo[c["dup"]]:wo[c["dup"] + 1]] = A[wo[c["dup"]]]          # a window of identical rows
+    if a_bf16:
+        A = torch.from_numpy(A).bfloat16().float().numpy()
     W = f32(g.uniform(-1, 1, (cout, cin)) / np.sqrt(cin))
+    host = dict(A=A, W=W, win_off=wo, rows=rows, Q=Q, S=S, max_rows=max(sizes))
+    if c.get("perwin"):
+        host["W"] = f32(g.uniform(-1, 1, (Q, cin, cout)) / np.sqrt(cin))
+    if c.get("bias"):
+        host["bias"] = f32(g.uniform(-0.5, 0.5, cout))
+    if c.get("biaswin"):
+        host["bias"] = f32(g.uniform(-0.5, 0.5, (Q, cout)))        # one row per window (bias_win_stride = cout)
+    if c.get("pro"):
+        s = f32(g.uniform(0.5, 1.5, (S, cin)) * np.where(g.random((S, cin)) < 0.1, -1, 1))
+        host["pro"] = (s, f32(g.uniform(-0.5, 0.5, (S, cin))))
+    if c.get("pro") == 2:
+        host["drop"] = (0.3, (seed, 7))
+    if c.get("stats") == "fin":
+        host["fin"] = (f32(g.uniform(0.5, 1.5, cout)), f32(g.uniform(-0.3, 0.3, cout)))
+    if c.get("pool") and c.get("neg"):
+        host["gamma"] = f32(g.uniform(0.5, 1.5, cout) * np.where(np.arange(cout) % 3 == 1, -1, 1))
+    if c.get("pfin"):
+        P = 2 * S
+        pm = f32(g.uniform(-1, 1, (P, cin)))
+        prow = (g.integers(50, 400, P)).astype(np.int32)
+        prow[-1] = 0                                         # an empty partial slot
+        pq = f32(g.uniform(0.5, 2.0, (P, cin)) * prow[:, None])
+        host["pfin"] = (pm, pq, prow, f32(g.uniform(0.5, 1.5, cin)), f32(g.uniform(-0.3, 0.3, cin)))
+    return host
+
+
+def make_gemm(name, c, mode, seed, pair=None):
+    a_bf16, z_bf16 = pair or (0, 0)
+    host = gemm_host(c, seed, a_bf16)
+    cin, cout, S = c["cin"], c["cout"], c["S"]
+    ldz = c.get("ldz", cout)
+    uniform = c.get("uniform", 0)
+    A, W, wo, rows, Q, max_rows = (host[k] for k in ("A", "W", "win_off", "rows", "Q", "max_rows"))
     sh = PP.plan(Q, S, max_rows, cin, cout)
     chunk_rows, chunks = (sh.x_chunk_rows, sh.x_chunks) if (mode == "f32x3" and cin == 128 and cout > 64 and cout % 128 == 0) else (sh.chunk_rows, sh.chunks)
     if uniform:
@@ -188,29 +270,21 @@ def make_gemm(name, c, mode, seed):
     d = PP.PwGemmProbe()
     d.lda, d.cin, d.ldw, d.n_slots, d.cout, d.ldz = cin, cin, cin, S, cout, ldz
     d.Q, d.chunk_rows, d.chunks, d.uniform_rows, d.identity_k, d.fin_eps = Q, chunk_rows, chunks, uniform, c.get("identity_k", 0), 1e-5
-    t = dict(A=dev(A), win_off=dev(wo, torch.int32))
-    host = dict(A=A, W=W, win_off=wo, rows=rows, Q=Q, S=S, chunk_rows=chunk_rows, chunks=chunks, name=fwd_name(c, Q * chunks, split))
+    d.a_bf16, d.z_bf16 = a_bf16, z_bf16
+    t = dict(A=dev(A, torch.bfloat16 if a_bf16 else torch.float32), win_off=dev(wo, torch.int32), W=dev(W))
+    host.update(chunk_rows=chunk_rows, chunks=chunks, name=fwd_name(c, Q * chunks, split, mode))
     if c.get("perwin"):
-        Wp = f32(g.uniform(-1, 1, (Q, cin, cout)) / np.sqrt(cin))
-        t["W"] = dev(Wp)
         d.w_win_stride, d.perwin_slot_major = cin * cout, 1
-        host["W"] = Wp
-    else:
-        t["W"] = dev(W)
-    if c.get("bias"):
-        host["bias"] = f32(g.uniform(-0.5, 0.5, cout))
+    if "bias" in host:
         t["bias"] = dev(host["bias"])
+        d.bias_win_stride = cout if c.get("biaswin") else 0
     if c.get("pro"):
-        s = f32(g.uniform(0.5, 1.5, (S, cin)) * np.where(g.random((S, cin)) < 0.1, -1, 1))
-        tt = f32(g.uniform(-0.5, 0.5, (S, cin)))
-        host["pro"] = (s, tt)
-        t["pro_scale"], t["pro_shift"] = dev(s), dev(tt)
+        t["pro_scale"], t["pro_shift"] = dev(host["pro"][0]), dev(host["pro"][1])
     if c.get("pro") == 2:
         d.drop_p = 0.3
-        host["drop"] = (0.3, (seed, 7))
         d.drop_seed = PP.drop_base(seed, 7)
     if c.get("Z", True):
-        t["Z"] = nanbuf(rows, ldz)
+        t["Z"] = nanbuf(rows, ldz, dtype=torch.bfloat16 if z_bf16 else torch.float32)
     if c.get("stats") == "wg":
         lanes = PP.plan(Q, S, max_rows, cin, cout, chunks).stat_lanes      # the orchestration's plan (lane cap of the kernel family)
         parts = -(-lanes // S) * S
@@ -223,7 +297,6 @@ def make_gemm(name, c, mode, seed):
         d.stat_lanes = lanes
         t["part_sum"], t["part_sq"] = nanbuf(S, cout), nanbuf(S, cout)
         t["part_rows"] = nanbuf(S, dtype=torch.int32)
-        host["fin"] = (f32(g.uniform(0.5, 1.5, cout)), f32(g.uniform(-0.3, 0.3, cout)))
         t["fin_gamma"], t["fin_beta"] = dev(host["fin"][0]), dev(host["fin"][1])
         for k in ("scale", "shift", "mean", "invstd", "smean", "suvar"):
             t["fin_" + k] = nanbuf(S, cout)
@@ -233,31 +306,74 @@ def make_gemm(name, c, mode, seed):
         if c["pool"] == "arg":
             t["part_amax"] = nanbuf(n + 1, cout, dtype=torch.int32)
         if c.get("neg"):
-            gam = f32(g.uniform(0.5, 1.5, cout) * np.where(np.arange(cout) % 3 == 1, -1, 1))
-            host["gamma"] = gam
-            t["pool_gamma"] = dev(gam)
+            t["pool_gamma"] = dev(host["gamma"])
     if c.get("pfin"):
-        P = 2 * S
-        pm = f32(g.uniform(-1, 1, (P, cin)))
-        prow = (g.integers(50, 400, P)).astype(np.int32)
-        prow[-1] = 0                                         # an empty partial slot
-        pq = f32(g.uniform(0.5, 2.0, (P, cin)) * prow[:, None])
-        host["pfin"] = (pm, pq, prow, f32(g.uniform(0.5, 1.5, cin)), f32(g.uniform(-0.3, 0.3, cin)))
+        pm, pq, prow = host["pfin"][:3]
         t["pfin_sum"], t["pfin_sq"], t["pfin_rows"] = dev(pm), dev(pq), dev(prow, torch.int32)
         t["pfin_gamma"], t["pfin_beta"] = dev(host["pfin"][3]), dev(host["pfin"][4])
-        d.pfin_parts = P
+        d.pfin_parts = len(prow)
         for k in ("scale", "shift", "mean", "invstd", "smean", "suvar"):
             t["pfin_" + k] = nanbuf(S, cin)
     PP.set_tensors(d, PP.GEMM_EXTENTS, **t)
     return d, t, host, split
 
 
+def bracket_ratio(Z, Z64, b):
+    """A stored bf16 Z against PP.bf16_bracket: the smallest s of (1/16, 1/4, 1/2, 1) at which EVERY element lies in the bracket of s * b
+    (2.0: not even at the bar itself).  Elements that pass at one s pass at every larger one and are not looked at again."""
+    assert np.all(np.isfinite(Z)), "non-finite where the contract writes"
+    z, z64, b = Z.reshape(-1), Z64.reshape(-1), np.broadcast_to(b, Z64.shape).reshape(-1)
+    for s in (0.0625, 0.25, 0.5, 1.0):
+        lo, hi = PP.bf16_bracket(z64, s * b)
+        bad = (z < lo) | (z > hi)
+        if not bad.any():
+            return s
+        z, z64, b = z[bad], z64[bad], b[bad]
+    return 2.0
+
+
+def tier_moment_bars(z64, mag, cin, eps, wid):
+    """PP.moment_bars, and the family suffix.  Tier 2 (wid = the ambiguity widening of these rows): a slot none of whose rows has an
+    ambiguous element keeps exactly that bar (suffix ""); in any other the REFERENCE's moments are only known up to the flips -- each row
+    moves by at most wid, so the mean by at most mean(wid) and the variance by at most mean(2 |dz| w + w^2) + mean(w) (2 mean|dz| +
+    mean(w)) -- and that is added (suffix " amb").  Measured on ones160 / bf16_train, slot 0 (40 rows, one flipped element): the kernel's
+    mean is 8.631e-06 from the reference's, which is exactly wid / 40 of that row, its variance 1.61 x the plain bar from it, and both equal the
+    moments of the kernel's own fp32 Z to 1e-16; the plain bar alone would hold the reference's ambiguity against the kernel."""
+    mu, var, bmean, bvar = PP.moment_bars(z64, mag, cin, eps)
+    if wid is None or not wid.any():
+        return mu, var, bmean, bvar, ""
+    dz = np.abs(z64 - mu)
+    wm = wid.mean(0)
+    return mu, var, bmean + wm, bvar + (2 * dz * wid + wid * wid).mean(0) + wm * (2 * dz.mean(0) + wm), " amb"
+
+
 def check_gemm(name, c, mode, d, t, host, split, names):
-    fam = "pw_gemm"
-    eps = PP.EPS32
+    """Tier 1 (every mode): the float64 reference on the operands as given, the bar at the mode's eps.  Tier 2 (bf16 modes, families
+    "pw_gemm t2 ..."): the float64 reference on the bf16-ROUNDED operands, the bar at eps = 2^-24 plus the ambiguity widening -- fp32
+    accumulation is the only error left; a bf16 Z must lie in PP.bf16_bracket; statistics and pool extremes follow the UNROUNDED z."""
+    bf = mode.startswith("bf16")
     cin, cout = c["cin"], c["cout"]
-    S, Q, rows = host["S"], host["Q"], host["rows"]
-    assert names == [host["name"]], (names, host["name"])          # the intended instantiation, x3 or not, ran
+    S = host["S"]
+    assert names == [host["name"]], (names, host["name"])          # the intended instantiation, x3 or bf16 or neither, ran
+    pro = pfin_constants(c, mode, t, host)
+    kw = dict(pro=pro, drop=host.get("drop"), bias=host.get("bias"), bias_win_stride=d.bias_win_stride, w_win_stride=d.w_win_stride,
+              slot_major=d.perwin_slot_major, identity_k=c.get("identity_k", 0))
+    Z64, M = PP.gemm_ref(host["A"], cin, cout, host["W"], host["win_off"], S, **kw)
+    worst = check_gemm_tier("", c, mode, d, t, host, Z64, M, PP.EPS16 if bf else PP.EPS32, None)
+    if bf:
+        del Z64, M
+        Z64r, Mr, amb = PP.gemm_ref(host["A"], cin, cout, host["W"], host["win_off"], S, operands="bf16", **kw)
+        print(f"[pw layers] {name} {mode}: ambiguous share of the positive prologue outputs {amb['share']:.3e}")
+        assert amb["share"] < 2.0 ** -10, amb["share"]
+        assert pro is not None or not amb["wid"].any()
+        worst = max(worst, check_gemm_tier(" t2", c, mode, d, t, host, Z64r, Mr, PP.EPS32, amb["wid"]))
+    return worst
+
+
+def pfin_constants(c, mode, t, host):
+    """The prologue constants of the case; pfin: the kernel's own pfin_scale / pfin_shift, held to float64 here."""
+    fam = "pw_gemm"
+    S = host["S"]
     pro = host.get("pro")
     if c.get("pfin"):
         pm, pq, prow, gam, bet = host["pfin"]
@@ -274,13 +390,29 @@ def check_gemm(name, c, mode, d, t, host, split, names):
             note(fam + " pfin", mode, PP.ratio(shf[sl], bet - mean * gam * inv, np.abs(bet) + np.abs(mean * gam * inv), len(idx)))
             note(fam + " pfin", mode, PP.ratio(t["pfin_suvar"].cpu().numpy()[sl], m2 / (n - 1), m2 / (n - 1), len(idx)))
         pro = (f32(sc), f32(shf))                      # the prologue the kernel staged: its own outputs, held to float64 above
-    Z64, M = PP.gemm_ref(host["A"], cin, cout, host["W"], host["win_off"], S, pro=pro, drop=host.get("drop"), bias=host.get("bias"),
-                         w_win_stride=d.w_win_stride, slot_major=d.perwin_slot_major, identity_k=c.get("identity_k", 0))
+    return pro
+
+
+def check_gemm_tier(tier, c, mode, d, t, host, Z64, M, eps, wid):
+    """Every output against one float64 reference (Z64, magnitudes M) at `eps`; wid [rows, cout]: the ambiguity widening of tier 2."""
+    fam = "pw_gemm" + tier
+    cin, cout = c["cin"], c["cout"]
+    S, Q, rows = host["S"], host["Q"], host["rows"]
+    zbf = bool(d.z_bf16)
     worst = 0.0
     if "Z" in t:
         Zt = t["Z"].cpu()
-        Z = Zt.numpy()
-        worst = max(worst, note(fam, mode, PP.ratio(Z[:rows, :cout], Z64, M, cin, eps)))
+        Z = Zt.float().numpy().astype(np.float64)[:rows, :cout]                 # (bf16 -> float64 is exact)
+        zb = PP.bar(M, Z64, cin, eps)
+        if not tier:                                                # (a bf16 Z, tier 1: its rounding on top, the rule of test_bn_glue_gpu.py)
+            worst = max(worst, note(fam, mode, PP.err_ratio(Z, Z64, zb + (2 * PP.EPS16 * np.abs(Z64) if zbf else 0.0))))
+        else:
+            # outputs no ambiguous element feeds carry the plain bar (family "t2"); the others the bar plus the widening ("t2 amb": one that
+            # did flip sits at widening / (bar + widening), just under 1, by construction).  A bf16 Z: the RNE rounding of a value in the bar
+            for sub, sel in (("", wid == 0.0), (" amb", wid > 0.0)):
+                if sel.any():
+                    z, z64, b = Z[sel], Z64[sel], (zb + wid)[sel]
+                    worst = max(worst, note(fam + sub, mode, bracket_ratio(z, z64, b) if zbf else PP.err_ratio(z, z64, b)))
         if d.ldz > cout:
             assert is_sentinel(Zt[:, cout:]), "padding columns of Z were written"
     q = PP.win_of_rows(host["win_off"])
@@ -297,15 +429,15 @@ def check_gemm(name, c, mode, d, t, host, split, names):
             n, mean, m2 = PP.chan_merge(ps[idx][live], pq[idx][live], pr[idx][live])
             r = slot == sl
             assert n == r.sum(), (sl, n, r.sum())
-            mu, var, bmean, bvar = PP.moment_bars(Z64[r], M[r], cin, eps)
-            worst = max(worst, note(fam + " stats", mode, PP.err_ratio(mean, mu, bmean)))
-            worst = max(worst, note(fam + " stats", mode, PP.err_ratio(m2 / n, var, bvar)))
+            mu, var, bmean, bvar, sub = tier_moment_bars(Z64[r], M[r], cin, eps, None if wid is None else wid[r])
+            worst = max(worst, note(fam + " stats" + sub, mode, PP.err_ratio(mean, mu, bmean)))
+            worst = max(worst, note(fam + " stats" + sub, mode, PP.err_ratio(m2 / n, var, bvar)))
     if c.get("stats") == "fin":
         gam, bet = host["fin"]
         for sl in range(S):
             r = slot == sl if not d.uniform_rows else (np.arange(rows) // d.uniform_rows) % S == sl
             K = r.sum()
-            mu, var, bmean, bvar = PP.moment_bars(Z64[r], M[r], cin, eps)
+            mu, var, bmean, bvar, _ = tier_moment_bars(Z64[r], M[r], cin, eps, None if wid is None else wid[r])
             inv = 1.0 / np.sqrt(var + 1e-5)
             binv = 0.5 * inv ** 3 * bvar + 4 * eps * inv
             got = {k: t["fin_" + k].cpu().numpy()[sl].astype(np.float64) for k in ("scale", "shift", "mean", "invstd", "suvar")}
@@ -321,7 +453,9 @@ def check_gemm(name, c, mode, d, t, host, split, names):
         gam = host.get("gamma", np.ones(cout, np.float32))
         sg = np.where(gam < 0, -1.0, 1.0)
         cr = host["chunk_rows"]
-        Zk = t["Z"].cpu().numpy() if "Z" in t else None
+        Zk = t["Z"].float().cpu().numpy() if "Z" in t and not tier else None      # (the kernel against its own Z: once)
+        # a bf16 Z is the rounding of the fp32 value the extreme was taken from; rounding is monotone, so the extremes agree after it
+        own = (lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).bfloat16().float().numpy()) if zbf else (lambda x: x)
         for qq in range(Q):
             for ch in range(host["chunks"]):
                 i = qq * host["chunks"] + ch
@@ -334,25 +468,49 @@ def check_gemm(name, c, mode, d, t, host, split, names):
                 ext64 = z64.max(0) * sg
                 b = PP.bar(M[r0:r1].max(0), ext64, cin, eps)
                 assert np.all(np.isfinite(pmx[i]))
-                worst = max(worst, note(fam + " pool", mode, float(np.max(np.abs(pmx[i] - ext64) / b))))
+                # tier 2: every row's z' is known up to its own widening w, so the extreme lies in [max(z' - w), max(z' + w)] (the column
+                # maximum itself where no ambiguous row comes near it)
+                w = np.zeros_like(z64) if wid is None else wid[r0:r1]
+                elo, ehi = (z64 - w).max(0), (z64 + w).max(0)
+                x = pmx[i] * sg
+                worst = max(worst, note(fam + " pool", mode, float(np.max(np.maximum(np.maximum(elo - x, x - ehi), 0.0) / b))))
                 if am is not None:
                     a = am[i]
                     assert np.all((a >= r0) & (a < r1)), "argmax row outside its chunk"
-                    at = Z64[a, np.arange(cout)]
-                    worst = max(worst, note(fam + " pool", mode, float(np.max(np.abs(at - ext64) / (2 * b)))))
+                    at = z64[a - r0, np.arange(cout)] + w[a - r0, np.arange(cout)]
+                    worst = max(worst, note(fam + " pool", mode, float(np.max(np.maximum(elo - at, 0.0) / (2 * b)))))
                     if Zk is not None:
                         zk = Zk[r0:r1, :cout] * sg
-                        assert np.array_equal(pmx[i], Zk[a, np.arange(cout)]), "extreme != the kernel's own Z at its row"
-                        assert np.array_equal(pmx[i] * sg, zk.max(0)), "extreme is not the extreme of the kernel's own Z"
+                        assert np.array_equal(own(pmx[i]), Zk[a, np.arange(cout)]), "extreme != the kernel's own Z at its row"
+                        assert np.array_equal(own(pmx[i]) * sg, zk.max(0)), "extreme is not the extreme of the kernel's own Z"
                     if c.get("dup") == qq:
                         assert np.all(a == r0), "tie rule: the first row of the chunk among equal extremes"
     return worst
 
 
-@pytest.mark.parametrize("mode", ["fp32", "f32x3"])
-@pytest.mark.parametrize("name", list(FWD))
-def test_pw_gemm_layer(name, mode):
-    c = FWD[name]
+def outputs_of(t):
+    return {k: v for k, v in t.items() if k in ("Z",) or k.startswith(("part_", "fin_s", "fin_m", "fin_i", "pfin_s", "pfin_m", "pfin_i")) and k not in ("pfin_sum", "pfin_sq")}
+
+
+def assert_refused(d, t, message):
+    """AMPNET_E_ARG with `message`, nothing launched, every output still at its sentinel."""
+    rc, names = PP.run_gemm(d)
+    assert rc == PP.AMPNET_E_ARG and names == [], (rc, names)
+    assert message in PP.last_error(), PP.last_error()
+    for k, v in outputs_of(t).items():
+        assert is_sentinel(v), f"{k} was written by a refused launch"
+
+
+@pytest.mark.parametrize("name,mode,pair", fwd_params())
+def test_pw_gemm_layer(name, mode, pair):
+    c = fwd_case(name, mode)
+    if c.get("chunk512") and mode.startswith("bf16"):
+        pytest.skip("chunk512 hands the split-eligible shape the non-split chunking: there is no split kernel to refuse it outside f32x3")
+    if c.get("pool") == "noarg" and mode.startswith("bf16"):
+        with precision(mode):
+            d, t, host, split = make_gemm(name, c, mode, 1234 + len(name), pair)
+            assert_refused(d, t, POOL_EVAL_REFUSAL)
+        return
     pipes = ["1", "0"] if mode == "fp32" and name in ("c64_64", "c128_128", "pool", "c64_40", "drop128") else [None]
     old = os.environ.get("AMPNET_PW_PIPE")
     try:
@@ -360,27 +518,65 @@ def test_pw_gemm_layer(name, mode):
             if pipe is not None:
                 os.environ["AMPNET_PW_PIPE"] = pipe
             with precision(mode):
-                d, t, host, split = make_gemm(name, c, mode, 1234 + len(name))
+                d, t, host, split = make_gemm(name, c, mode, 1234 + len(name), pair)
                 rc, names = PP.run_gemm(d)
                 if c.get("chunk512") and rc == PP.AMPNET_E_ARG:
                     print(f"[pw layers] chunk512 {mode}: refused ({PP.last_error()})")
                     continue
                 assert rc == 0, PP.last_error()
                 first = snap(t)
-                for k, v in t.items():                               # second run on re-poisoned outputs
-                    if k in ("Z",) or k.startswith(("part_", "fin_s", "fin_m", "fin_i", "pfin_s", "pfin_m", "pfin_i")) and k not in ("pfin_sum", "pfin_sq"):
-                        v.copy_(nanbuf(*v.shape, dtype=v.dtype))
+                for v in outputs_of(t).values():                     # second run on re-poisoned outputs
+                    v.copy_(nanbuf(*v.shape, dtype=v.dtype))
                 rc2, _ = PP.run_gemm(d)
                 assert rc2 == 0, PP.last_error()
                 bitwise_equal(first, snap(t))
                 w = check_gemm(name, c, mode, d, t, host, split, names)
-                print(f"[pw layers] {name} {mode} pipe={pipe}: {names[0]}, worst error/bar {w:.4f}")
+                print(f"[pw layers] {name} {mode} pair={pair} pipe={pipe}: {names[0]}, worst error/bar {w:.4f}")
                 assert w <= 1.0
     finally:
         if old is None:
             os.environ.pop("AMPNET_PW_PIPE", None)
         else:
             os.environ["AMPNET_PW_PIPE"] = old
+
+
+def test_pw_gemm_bf16_tensor_refusals():
+    """pw_gemm's own argument checks are the gate of the bf16 tensors (the hook adds none): a bf16 A or Z outside the bf16 modes, and a
+    bf16 A whose rows are not 16-byte aligned (lda = 68), get AMPNET_E_ARG with pw_gemm's message and leave the outputs alone."""
+    c = FWD["c64_64"]
+    for mode in ("fp32", "f32x3"):
+        for pair in ((1, 0), (0, 1)):
+            with precision(mode):
+                d, t, host, _ = make_gemm("c64_64", c, mode, 5, pair)
+                assert_refused(d, t, "pw_gemm: bf16 tensors need a bf16 precision mode")
+    with precision("bf16_store"):
+        d, t, host, _ = make_gemm("c64_64", c, "bf16_store", 5, (1, 1))
+        A68 = torch.zeros(host["rows"], 68, dtype=torch.bfloat16, device="cuda")
+        A68[:, :64] = t["A"]
+        d.A, d.A_n, d.lda = A68.data_ptr(), A68.numel(), 68
+        assert_refused(d, t, "pw_gemm: bf16 A needs lda % 8 == 0")
+
+
+def test_pw_gemm_probe_descriptor_without_the_tail():
+    """A caller built against the descriptor that ended at pfin_out_n has tail (its pad0) == 0 and whatever memory follows its struct where
+    a_bf16 / z_bf16 now are: the hook must not read them.  tail == 0 with both words set runs the fp32 kernel and gives the bits of the
+    plain run; any other tail but 0 and 1 is refused."""
+    c = FWD["c64_64"]
+    with precision("fp32"):
+        d, t, host, _ = make_gemm("c64_64", c, "fp32", 5)
+        rc, names = PP.run_gemm(d)
+        assert rc == 0 and names == [host["name"]], (rc, names, PP.last_error())
+        first = snap(outputs_of(t))
+        for v in outputs_of(t).values():
+            v.copy_(nanbuf(*v.shape, dtype=v.dtype))
+        d.tail, d.a_bf16, d.z_bf16 = 0, 0x5A5A5A5A, -1
+        rc, names = PP.run_gemm(d)
+        assert rc == 0 and names == [host["name"]], (rc, names, PP.last_error())
+        bitwise_equal(first, snap(outputs_of(t)))
+        for v in outputs_of(t).values():
+            v.copy_(nanbuf(*v.shape, dtype=v.dtype))
+        d.tail, d.a_bf16, d.z_bf16 = 2, 0, 0
+        assert_refused(d, t, "probe_pw_gemm: tail = 2")
 
 
 # ================================================================================================================================

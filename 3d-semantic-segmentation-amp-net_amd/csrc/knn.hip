@@ -8,13 +8,13 @@
 //     distance = float32 ((dx*dx + dy*dy) + dz*dz), one rounding per operation (this file is compiled with
 //     -ffp-contract=off like fps.hip); equal distances go to the lower index; the centre itself (distance 0) comes first.
 //
-// Mapping to CDNA4: the cloud's coordinates sit in LDS as three planes (n * 12 bytes <= 144 KB), one workgroup serves a
+// Mapping to CDNA4: the cloud's coordinates sit in LDS as three planes (cloud_search.h; n * 12 bytes <= 144 KB), one workgroup serves a
 // slice of the centres of one cloud, one WAVE per centre.  Lane l scans candidates l, l + 64, ... (conflict-free LDS
 // reads) keeping its four smallest (distance, index) keys in registers; then k rounds of a 64-lane DPP minimum pop the
 // global order.  A lane that runs out of its four (rare: the k winners spread over 64 lanes) rescans for its next four.
 // HBM traffic is the cloud once per workgroup; the algorithmic figure SURVEY.md section 8(d) counts is 12 B per
 // (candidate, centre), served from LDS.
-#include "common.h"
+#include "cloud_search.h"
 
 #pragma clang fp contract(off)
 
@@ -72,13 +72,7 @@ __global__ __launch_bounds__(64 * KNN_WAVES) void knn_kernel(const float *__rest
     extern __shared__ __attribute__((aligned(16))) float s_cloud[];      // x[n], y[n], z[n]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cloud_i = blockIdx.y;
-    const float *cloud = xyz + (size_t)cloud_i * n * ld;
-    for (int j = tid; j < n; j += 64 * KNN_WAVES) {
-        s_cloud[j] = cloud[(size_t)j * ld + 0];
-        s_cloud[n + j] = cloud[(size_t)j * ld + 1];
-        s_cloud[2 * n + j] = cloud[(size_t)j * ld + 2];
-    }
-    __syncthreads();
+    stage_cloud<64 * KNN_WAVES>(s_cloud, xyz + (size_t)cloud_i * n * ld, n, ld);
     const int c_begin = blockIdx.x * centres_per_block, c_end = min(c_begin + centres_per_block, s);
     for (int ci = c_begin + wave; ci < c_end; ci += KNN_WAVES) {
         const int cidx = centres[(size_t)cloud_i * s + ci];
@@ -157,22 +151,13 @@ extern "C" int ampnet_knn_f32(const float *xyz, int n_clouds, int n, int ld, con
                               void *stream)
 {
     using namespace ampnet;
-    AMPNET_REQUIRE(xyz && centres && out, "ampnet_knn_f32: null pointer");
-    AMPNET_REQUIRE(n_clouds >= 1 && n >= 1 && ld >= 3 && s >= 1, "ampnet_knn_f32: bad shape n_clouds=%d n=%d ld=%d s=%d", n_clouds, n, ld, s);
-    AMPNET_REQUIRE(k >= 1 && k <= n, "ampnet_knn_f32: k=%d must be in [1, n=%d]", k, n);
-    const size_t lds = (size_t)n * 3 * sizeof(float);
-    AMPNET_REQUIRE(lds <= 144 * 1024, "ampnet_knn_f32: n=%d exceeds %d points per cloud (coordinates must fit LDS)", n, 144 * 1024 / 12);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-        if (e != hipSuccess) return fail(AMPNET_E_LAUNCH, "ampnet_knn_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    // enough workgroups to fill 256 CUs, each amortising its copy of the cloud over >= 32 centres
-    int per_block = cdiv(s * n_clouds, 1024);
-    if (per_block < 32) per_block = 32;
-    if (per_block > s) per_block = s;
-    hipLaunchKernelGGL(knn_kernel, dim3(cdiv(s, per_block), n_clouds), dim3(64 * KNN_WAVES), lds, (hipStream_t)stream, xyz, n, ld, centres, s, k,
-                       per_block, out);
+    const char *what = "ampnet_knn_f32";
+    AMPNET_REQUIRE(xyz && centres && out, "%s: null pointer", what);
+    AMPNET_TRY(check_dense_clouds(what, n_clouds, n, ld, s));
+    AMPNET_REQUIRE(k >= 1 && k <= n, "%s: k=%d must be in [1, n=%d]", what, k, n);
+    AMPNET_TRY(allow_dynamic_lds<knn_kernel>(CLOUD_LDS_MAX, what));
+    const int per_block = centres_per_block(s, n_clouds);
+    hipLaunchKernelGGL(knn_kernel, dim3(cdiv(s, per_block), n_clouds), dim3(64 * KNN_WAVES), (size_t)n * 12, (hipStream_t)stream, xyz, n, ld, centres,
+                       s, k, per_block, out);
     return check_launch("knn_kernel");
 }

@@ -146,15 +146,21 @@ def _ball_query_args(what, xyz, centres, radii, nsamples, tags):
     x = xyz.float().contiguous()
     c = centres.contiguous()
     N, S = x.shape[1], c.shape[1]
+    radii, nsamples = _ball_query_scales(what, radii, nsamples, tags)
+    if S and (int(c.min()) < 0 or int(c.max()) >= N):
+        raise IndexError(f"{what}: centre index out of range")
+    return x, c, radii, nsamples
+
+
+def _ball_query_scales(what, radii, nsamples, tags):
+    """The nsample / radius rule of every ball query, written once -> (radii as floats, nsamples as ints)."""
     radii, nsamples = [float(r) for r in radii], [int(ns) for ns in nsamples]
     for radius, nsample, tag in zip(radii, nsamples, tags):
         if not (1 <= nsample <= _lib.SA_MAX_NSAMPLE):
             raise IndexError(f"{what}: nsample={nsample} out of range [1, {_lib.SA_MAX_NSAMPLE}]{tag}")
         if not radius >= 0.0:
             raise _lib.AmpnetError(f"{what}: radius={radius} must be >= 0{tag}")
-    if S and (int(c.min()) < 0 or int(c.max()) >= N):
-        raise IndexError(f"{what}: centre index out of range")
-    return x, c, radii, nsamples
+    return radii, nsamples
 
 
 def ball_query_msg(xyz, centres, radii, nsamples, return_counts=False):
@@ -272,11 +278,7 @@ def ball_query_ragged(rows, sizes, centres, radius, nsample, return_counts=False
     for b, n in enumerate(lay.sizes):
         if n > _lib.BALL_QUERY_MAX_N:
             raise _lib.AmpnetError(f"ball_query_ragged: cloud {b} has {n} points, more than {_lib.BALL_QUERY_MAX_N} (coordinates must fit LDS)")
-    radius, nsample = float(radius), int(nsample)
-    if not (1 <= nsample <= _lib.SA_MAX_NSAMPLE):
-        raise IndexError(f"ball_query_ragged: nsample={nsample} out of range [1, {_lib.SA_MAX_NSAMPLE}]")
-    if not radius >= 0.0:
-        raise _lib.AmpnetError(f"ball_query_ragged: radius={radius} must be >= 0")
+    (radius,), (nsample,) = _ball_query_scales("ball_query_ragged", [radius], [nsample], [""])
     x = (rows if rows.dtype == torch.float32 else rows.float()).contiguous()
     c = centres.contiguous()
     if not _trusted_centres:

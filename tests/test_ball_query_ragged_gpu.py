@@ -55,6 +55,45 @@ def test_ragged_equals_the_uniform_kernel_and_the_restatement_cloud_by_cloud(pac
         assert count.cpu().tolist() == [[min(n, nsample)] * S for n in sizes]
 
 
+def test_one_launch_over_a_late_member_cloud_a_cloud_above_the_staging_threads_and_a_single_point():
+    """Three clouds in one launch.  (1) The 311-point line-plus-cluster cloud of test_ball_query_gpu.py::
+    test_members_past_the_first_step_are_found: members past empty steps of the walk.  (2) The 1216-point integer grid with duplicates of
+    that file's _grid_cloud(): more points than the 1024 threads that stage a cloud, so every thread stages a second row, and at radius 1.0
+    d == r2 exactly for the axis neighbours.  (3) One point.  The ragged kernel and the uniform one share their walk: cloud by cloud the
+    lists and counts are the uniform call's and the restatement's, and global_index adds the cloud's first row to EVERY entry, padding
+    included."""
+    U = sub("utils.utils")
+    line = np.stack([10.0 * np.arange(300), np.zeros(300), np.zeros(300)], 1)
+    line[130] = line[2]
+    line[299] = line[2]
+    g = np.stack(np.meshgrid(np.arange(16), np.arange(16), np.arange(4), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+    clouds = [np.concatenate([line, np.array([5000.0, 7.0, -3.0]) + 0.01 * np.arange(11)[:, None]]).astype(np.float32),
+              np.concatenate([g, g[:64], np.zeros((128, 3), np.float32)], 0),
+              np.array([[0.25, -1.5, 3.0]], np.float32)]
+    sizes = [c.shape[0] for c in clouds]
+    assert sizes == [311, 1216, 1]
+    centres = np.array([[305, 2, 300, 310, 64], [0, 5, 341, 1023, 1215], [0, 0, 0, 0, 0]], dtype=np.int32)
+    assert sa_ref.ball_query(clouds[0], centres[0], 0.5, 16)[1].tolist() == [11, 3, 11, 11, 1]
+    rows = torch.from_numpy(np.concatenate(clouds)).cuda()
+    cent = torch.from_numpy(centres).cuda()
+    for radius, nsample in ((0.5, 1), (0.5, 3), (0.5, 16), (1.0, 7)):
+        out, count = U.ball_query_ragged(rows, sizes, cent, radius, nsample, return_counts=True)
+        glob, gcount = U.ball_query_ragged(rows, sizes, cent, radius, nsample, return_counts=True, global_index=True)
+        assert tuple(out.shape) == (3, 5, nsample) and tuple(count.shape) == (3, 5)
+        off, alone = 0, []
+        for b, (pc, n) in enumerate(zip(clouds, sizes)):
+            lists, acount = U.ball_query(torch.from_numpy(pc).cuda()[None], cent[b:b + 1], radius, nsample, return_counts=True)
+            want, wcount = sa_ref.ball_query(pc, centres[b], radius, nsample)
+            assert torch.equal(out[b], lists[0]) and torch.equal(count[b], acount[0]), (radius, nsample, b)
+            assert np.array_equal(out[b].cpu().numpy(), want) and np.array_equal(count[b].cpu().numpy(), wcount), (radius, nsample, b)
+            alone.append(lists[0] + off)
+            off += n
+        assert torch.equal(gcount, count)
+        for b in range(3):
+            assert torch.equal(glob[b], alone[b]), (radius, nsample, b)
+        assert count[2].tolist() == [1] * 5 and glob[2].unique().tolist() == [311 + 1216]      # the single point: one member, then padding
+
+
 def test_a_wider_row_and_a_layout_object_give_the_same_lists(packed):
     """ld = 9 (the model's packed rows) and a RaggedLayout built once, as the model hands them over."""
     U = sub("utils.utils")

@@ -52,6 +52,27 @@ def test_ragged_equals_the_uniform_kernel_cloud_by_cloud(synth, fine, s):
     assert torch.equal(dup[:100], dup[100:200]) and torch.equal(dup[:50], dup[200:250])
 
 
+def test_more_coarse_points_than_staging_threads(synth):
+    """s = 300 coarse points per cloud: more than the 256 threads that stage them, so 44 threads stage a second row; fine clouds of 1 and
+    257 points (a workgroup with one live lane, twice).  Coarse point 2 is a copy of point 0."""
+    U = sub("utils.utils")
+    sizes, s = [1, 257], 300
+    clouds = [synth.clouds(40 + b, 1, n)[0] for b, n in enumerate(sizes)]
+    coarse = synth.clouds(45, len(sizes), s)
+    coarse[:, 2] = coarse[:, 0]
+    rows = torch.from_numpy(np.concatenate(clouds)).cuda()
+    cx = torch.from_numpy(coarse).cuda()
+    idx, d2 = U.three_nn_ragged(rows, sizes, cx)
+    gidx, gd2 = U.three_nn_ragged(rows, sizes, cx, global_index=True)
+    assert tuple(idx.shape) == tuple(d2.shape) == (sum(sizes), 3)
+    off = 0
+    for b, (pc, n) in enumerate(zip(clouds, sizes)):
+        want_idx, want_d2 = U.three_nn(torch.from_numpy(pc).cuda()[None], cx[b:b + 1])
+        assert torch.equal(idx[off:off + n], want_idx[0]) and torch.equal(d2[off:off + n], want_d2[0]), (b, n)
+        assert torch.equal(gidx[off:off + n], want_idx[0] + b * s) and torch.equal(gd2[off:off + n], want_d2[0]), (b, n)
+        off += n
+
+
 def test_wider_rows_and_a_layout_object_give_the_same_answers(synth, fine):
     U = sub("utils.utils")
     clouds, sizes = fine

@@ -25,7 +25,7 @@ python3 tools/prof_sa.py [steps] [warmup] group_all        -- the group_all leg 
 python3 tools/prof_sa.py [steps] [warmup] group_all-trace  -- nothing but the fused group_all forward and backward, for a kernel trace.
 The msg leg: multi-scale grouping with two scales at B = 16, an sa1-like shape (this file's N = 8192 cloud, 1024 centres, radii (0.1, 0.2),
 nsample (16, 32), D = 9, [32, 32, 64] twice) and an sa3-like one (a 256-point cloud, 64 centres, radii (0.4, 0.8), nsample (16, 32), D = 128,
-[128, 128, 256] twice): (a) one utils.ball_query_msg (ball_query_msg_kernel) against two utils.ball_query calls, and the same pair again as
+[128, 128, 256] twice): (a) one utils.ball_query_msg (ball_query_kernel<2>) against two utils.ball_query calls (ball_query_kernel<1>), and the same pair again as
 bare kernels on preallocated outputs, without the helpers' validation of the centres; (b) one sa_msg_forward_f32 (two sa_fold_kernel launches,
 sa_msg_forward_kernel) against two sa_forward_f32 calls plus torch.cat.  Five alternating rounds, every round reported, medians quoted.
 python3 tools/prof_sa.py [steps] [warmup] msg        -- the msg leg alone; prints one JSON line.

@@ -986,3 +986,73 @@ def cloud_input_f32(raw, in_off, out_off, seed, step, permute, rotate, cos_a, si
                                           int(bool(permute)), int(bool(rotate)), ctypes.c_double(float(cos_a)), ctypes.c_double(float(sin_a)),
                                           ptr(rows), ptr(targets), ptr(src), stream_ptr(raw.device))
     check(rc, "ampnet_cloud_input_f32")
+
+
+# ---- the window token: one linear layer and a segmented max, fused (csrc/token_pool.hip) ------------------------------------------------
+def _token_pool_workspace_bytes(symbol, cin, cout, Q, total):
+    fn = getattr(lib(), symbol)
+    fn.restype = ctypes.c_size_t
+    need = fn(int(cin), int(cout), int(Q), ctypes.c_longlong(int(total)))
+    if not need:
+        check(-1, symbol)
+    return int(need)
+
+
+def token_pool_forward_workspace_bytes(cin, cout, Q, total):
+    """Device bytes token_pool_forward_f32 needs for Q clouds of `total` rows in all, cin -> cout; a shape outside the kernel's limits is
+    an AmpnetError that names the limit."""
+    return _token_pool_workspace_bytes("ampnet_token_pool_forward_workspace_bytes", cin, cout, Q, total)
+
+
+def token_pool_backward_workspace_bytes(cin, cout, Q, total):
+    """Device bytes token_pool_backward_f32 needs (as token_pool_forward_workspace_bytes)."""
+    return _token_pool_workspace_bytes("ampnet_token_pool_backward_workspace_bytes", cin, cout, Q, total)
+
+
+def _token_pool_geometry(prefix, rows, cloud_off, weight, extra, per_cloud):
+    """rows [total, cin], cloud_off int32 [Q + 1] (the device table of a utils.RaggedLayout: TRUSTED, it is not read back), weight
+    [cout, cin] -> (Q, total, cin, cout).  extra: the _check_tensors rows of the wrapper's other tensors; per_cloud: the names among them
+    that must be [Q, cout]."""
+    _check_tensors(prefix, [("rows", rows, _F32, 2, True), ("cloud_off", cloud_off, _I32, 1, True), ("weight", weight, _F32, 2, True)] + extra)
+    total, cin = rows.shape
+    Q, cout = cloud_off.numel() - 1, weight.shape[0]
+    if Q < 1 or weight.shape[1] != cin:
+        raise AmpnetError(f"{prefix}: rows [total, cin], cloud_off [Q + 1 >= 2] and weight [cout, cin] do not agree: {tuple(rows.shape)} "
+                          f"{tuple(cloud_off.shape)} {tuple(weight.shape)}")
+    for name, t, _, _, _ in extra:
+        if name in per_cloud and t is not None and tuple(t.shape) != (Q, cout):
+            raise AmpnetError(f"{prefix}: {name} must be [Q, cout] = [{Q}, {cout}], got {tuple(t.shape)}")
+    return Q, total, cin, cout
+
+
+def token_pool_forward_f32(rows, cloud_off, weight, bias, out, workspace, arg_out=None):
+    """ampnet_token_pool_forward_f32 (include/ampnet_hip.h): rows [total, cin] float32 = the clouds back to back, cloud_off int32 [Q + 1]
+    on the device, weight [cout, cin], bias [cout]; written: out [Q, cout] float32 and arg_out [Q, cout] int32 or None (the lowest row of
+    the cloud that attains each maximum); workspace: token_pool_forward_workspace_bytes(...) GPU bytes.  Contiguous GPU tensors."""
+    Q, total, cin, cout = _token_pool_geometry("token_pool_forward", rows, cloud_off, weight,
+                                               [("bias", bias, _F32, 1, True), ("out", out, _F32, 2, True), ("arg_out", arg_out, _I32, 2, False)],
+                                               ("out", "arg_out"))
+    if bias.numel() != cout:
+        raise AmpnetError(f"token_pool_forward: bias must be [cout] = [{cout}], got {tuple(bias.shape)}")
+    ws, ws_bytes = _workspace_args("token_pool_forward", workspace)
+    with torch.cuda.device(rows.device):
+        rc = lib().ampnet_token_pool_forward_f32(ptr(rows), ptr(cloud_off), Q, ctypes.c_longlong(total), ptr(weight), ptr(bias), cin, cout,
+                                                 ptr(out), ptr(arg_out), ws, ws_bytes, stream_ptr(rows.device))
+    check(rc, "ampnet_token_pool_forward_f32")
+
+
+def token_pool_backward_f32(rows, cloud_off, weight, arg, dout, dx, dW, db, workspace):
+    """ampnet_token_pool_backward_f32: rows, cloud_off, weight as in the forward, arg int32 [Q, cout] (the forward's arg_out), dout
+    [Q, cout]; written, each or None when it is not wanted: dx [total, cin] (every element), dW [cout, cin], db [cout]; workspace:
+    token_pool_backward_workspace_bytes(...) GPU bytes."""
+    Q, total, cin, cout = _token_pool_geometry("token_pool_backward", rows, cloud_off, weight,
+                                               [("arg", arg, _I32, 2, True), ("dout", dout, _F32, 2, True), ("dx", dx, _F32, 2, False),
+                                                ("dW", dW, _F32, 2, False), ("db", db, _F32, 1, False)], ("arg", "dout"))
+    for name, t, want in (("dx", dx, (total, cin)), ("dW", dW, (cout, cin)), ("db", db, (cout,))):
+        if t is not None and tuple(t.shape) != want:
+            raise AmpnetError(f"token_pool_backward: {name} must be {list(want)}, got {tuple(t.shape)}")
+    ws, ws_bytes = _workspace_args("token_pool_backward", workspace)
+    with torch.cuda.device(rows.device):
+        rc = lib().ampnet_token_pool_backward_f32(ptr(rows), ptr(cloud_off), Q, ctypes.c_longlong(total), ptr(weight), cin, cout, ptr(arg),
+                                                  ptr(dout), ptr(dx), ptr(dW), ptr(db), ws, ws_bytes, stream_ptr(rows.device))
+    check(rc, "ampnet_token_pool_backward_f32")

@@ -565,3 +565,43 @@ class _SegNllFn(torch.autograd.Function):
         dlogp = torch.empty(ctx.shape, dtype=torch.float32, device=target.device)
         _lib.seg_nll_backward_f32(target, w[0] if w else None, sums, gloss.detach().float().reshape(1).contiguous(), dlogp)
         return dlogp, None, None, None, None
+
+
+# ---- the window token of pointnet_2: conv1 and the max over a cloud's points, fused (csrc/token_pool.hip) ---------------------------------
+def token_pool_forward(rows, cloud_off, weight, bias, want_arg=False):
+    """ampnet_token_pool_forward_f32 on rows [total, cin], the device table cloud_off int32 [Q + 1], weight [cout, cin], bias [cout]
+    -> (tokens [Q, cout], arg int32 [Q, cout] or None)."""
+    Q, cout = cloud_off.numel() - 1, weight.shape[0]
+    out = torch.empty((Q, cout), dtype=torch.float32, device=rows.device)
+    arg = torch.empty((Q, cout), dtype=torch.int32, device=rows.device) if want_arg else None
+    need = _lib.token_pool_forward_workspace_bytes(rows.shape[1], cout, Q, rows.shape[0])
+    _lib.token_pool_forward_f32(rows, cloud_off, weight, bias, out, _ws(need, rows.device), arg_out=arg)
+    return out, arg
+
+
+class _TokenPoolFn(torch.autograd.Function):
+    """tokens[q, c] = max over the rows of cloud q of (weight[c, :] . row + bias[c]) (pointnet2_utils.token_pool): rows [total, cin]
+    float32 contiguous, cloud_off the int32 [Q + 1] device table, weight [cout, cin] or nn.Conv1d's [cout, cin, 1], bias [cout]
+    -> (tokens [Q, cout], arg int32 [Q, cout]).  Saved for the backward: the inputs and arg only -- the [total, cout] products are never
+    stored, the backward runs on the winning rows alone.  The lowest row takes the whole gradient of a tie.  Exact fp32 whatever the
+    matrix precision is, so there is no precision scope to carry over.  arg is an integer: marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, cloud_off, rows, weight, bias):
+        w = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
+        out, arg = token_pool_forward(rows, cloud_off, w, bias.detach().float().contiguous(), want_arg=True)
+        ctx.save_for_backward(rows, cloud_off, arg, weight)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        rows, cloud_off, arg, weight = ctx.saved_tensors
+        w = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
+        need_grad = ctx.needs_input_grad
+        dx = torch.empty_like(rows) if need_grad[1] else None
+        dW = torch.empty_like(w) if need_grad[2] else None
+        db = torch.empty(w.shape[0], dtype=torch.float32, device=w.device) if need_grad[3] else None
+        need = _lib.token_pool_backward_workspace_bytes(w.shape[1], w.shape[0], cloud_off.numel() - 1, rows.shape[0])
+        _lib.token_pool_backward_f32(rows, cloud_off, w, arg, dout.contiguous().float(), dx, dW, db, _ws(need, rows.device))
+        return None, dx, None if dW is None else dW.reshape(weight.shape), db

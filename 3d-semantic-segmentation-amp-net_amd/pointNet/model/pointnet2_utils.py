@@ -758,3 +758,57 @@ def seg_nll_loss(log_probs, target, weight=None, want_preds=False, want_counts=F
         with torch.no_grad():
             loss, _, preds, counts = autograd.seg_nll_forward(flat.detach(), t, weight, bool(want_preds), bool(want_counts))
     return loss, (None if preds is None else preds.reshape(target.shape)), counts
+
+
+def token_pool(rows, weight, bias, sizes=None, want_arg=False):
+    """One token per cloud in ONE fused kernel (ampnet_token_pool_forward_f32): tokens[q, c] = max over the rows r of cloud q of
+    (weight[c, :] . rows[r, :] + bias[c]) -- nn.Conv1d(cin, cout, 1) and the max over the points, what pointnet_2 ends in, on point-major
+    rows: no transpose, no [Q, cout, n] tensor.  No BatchNorm, no ReLU: a maximum below zero stays below zero.
+    rows: [Q, n, cin] with sizes=None, or the clouds packed back to back [total, cin] with `sizes`, their row counts (each >= 1; or a
+    utils.RaggedLayout); float32 GPU.  weight: [cout, cin] or nn.Conv1d's [cout, cin, 1]; bias [cout].  cin and cout multiples of 32 in
+    [32, 256].  -> tokens [Q, cout] float32, or (tokens, arg) with want_arg: arg int32 [Q, cout], the index inside its cloud of the LOWEST
+    row that attains the maximum.
+    Exact fp32 whatever the matrix precision is (no precision scope is consulted), and a row's value is a function of the row and the
+    weights alone: cloud by cloud the packed call gives the bits of the call on that cloud alone, and two calls give the same bits.
+    Graph: torch's own rule -- with grad mode on and rows, weight or bias requiring grad the tokens carry a graph to those of them
+    (autograd._TokenPoolFn: ampnet_token_pool_backward_f32 on the winning rows alone; the gradient of rows is dense, zero outside the
+    winners).  Tie rule: the lowest row takes the whole gradient, where torch.amax's backward splits it evenly among equal maxima.  Equal
+    maxima arise from exact duplicate rows (cyclic padding), and there both rules give the same gradients of weight and bias.
+    A layout that does not tile the rows, a size below 1, a width outside the limits and a CPU tensor are AmpnetError."""
+    from ... import autograd
+    for name, t in (("rows", rows), ("weight", weight), ("bias", bias)):
+        if not torch.is_tensor(t):
+            raise _lib.AmpnetError(f"token_pool: {name} must be a GPU tensor, got {type(t).__name__}")
+        _lib.require_gpu(t, name)
+    if weight.dim() == 3 and weight.shape[2] == 1:
+        w2 = weight.reshape(weight.shape[0], weight.shape[1])
+    else:
+        w2 = weight
+    if w2.dim() != 2 or bias.dim() != 1 or bias.shape[0] != w2.shape[0]:
+        raise _lib.AmpnetError(f"token_pool: expected weight [cout, cin] or [cout, cin, 1] and bias [cout], got {tuple(weight.shape)} "
+                               f"{tuple(bias.shape)}")
+    cout, cin = w2.shape
+    if sizes is None:
+        if rows.dim() != 3 or rows.shape[2] != cin or rows.shape[0] < 1 or rows.shape[1] < 1:
+            raise _lib.AmpnetError(f"token_pool: without sizes, expected rows [Q >= 1, n >= 1, cin = {cin}], got {tuple(rows.shape)}")
+        Q, n = rows.shape[0], rows.shape[1]
+        if Q * n > 0x7fffffff:
+            raise _lib.AmpnetError(f"token_pool: {Q * n} rows exceed 2^31 - 1")
+        off = torch.arange(0, (Q + 1) * n, n, dtype=torch.int32 if (Q + 1) * n <= 0x7fffffff else torch.int64, device=rows.device).int()
+    else:
+        if rows.dim() != 2 or rows.shape[1] != cin:
+            raise _lib.AmpnetError(f"token_pool: with sizes, expected packed rows [total, cin = {cin}], got {tuple(rows.shape)}")
+        off = U.ragged_layout("token_pool", rows, sizes).off
+        Q = off.numel() - 1
+    for name, v in (("cin", cin), ("cout", cout)):
+        if v % 32 or not (32 <= v <= 256):
+            raise _lib.AmpnetError(f"token_pool: {name}={v}, must be a multiple of 32 in [32, 256]")
+    flat = rows.reshape(-1, cin)
+    flat = (flat if flat.dtype == torch.float32 else flat.float()).contiguous()
+    if torch.is_grad_enabled() and (rows.requires_grad or weight.requires_grad or bias.requires_grad):
+        tokens, arg = autograd._TokenPoolFn.apply(off, flat, weight, bias)
+    else:
+        with torch.no_grad():
+            tokens, arg = autograd.token_pool_forward(flat.detach(), off, w2.detach().float().contiguous(), bias.detach().float().contiguous(),
+                                                      want_arg=bool(want_arg))
+    return (tokens, arg) if want_arg else tokens

@@ -27,7 +27,7 @@ from ... import _lib, ops
 from ... import params as P
 from ...utils import utils as U
 from ._precision import _EvalForwardPrecision, _HasPrecision, is_bf16     # noqa: F401  (_HasPrecision: _baseline.py takes it from here)
-from .pointnet2_utils import PointNetFeaturePropagation, PointNetSegHead, PointNetSetAbstraction
+from .pointnet2_utils import PointNetFeaturePropagation, PointNetSegHead, PointNetSetAbstraction, token_pool
 
 
 class _Conv(nn.Module):
@@ -439,7 +439,12 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
 
     precision (keyword-only; also set_precision(mode)) is handed to the six blocks (pointnet2_utils.py): None and 'fp32' are the exact-fp32
     kernels whatever the library's mode is, 'bf16' runs every block's matrix products in bf16 -- an inference mode, refused
-    (NotImplementedError) together with any of the four flags above.  `conv1` and the max stay torch fp32."""
+    (NotImplementedError) together with any of the four flags above.  `conv1` and the max stay fp32.
+
+    forward_tokens(points [Q, N, 9]) -> (tokens [Q, 128], l0_rows [Q, N, 128]) and forward_tokens_ragged(rows [total, 9], sizes) ->
+    (tokens [Q, 128], l0_rows [total, 128]) are the model as a WINDOW ENCODER on point-major rows, for windows of one size and for clouds
+    of native size: `conv1` and the max run as one fused exact-fp32 kernel with a backward (pointnet2_utils.token_pool), nothing is
+    transposed and no [Q, 128, N] tensor is written.  forward() itself stays the torch `conv1` + amax, bit for bit."""
 
     def __init__(self, num_classes, device='cuda', decoder_grad=False, encoder_grad=False, decoder_batch_stats=False,
                  encoder_batch_stats=False, *, precision=None):
@@ -530,6 +535,63 @@ class pointnet_2(_EvalForwardPrecision, nn.Module):
             l0_points = None if rows else l0_rows.transpose(1, 2).contiguous()        # [B, 128, N], the reference's layout
         return l0_rows, l0_points
 
+    def _backbone_ragged(self, rows, sizes):
+        """The six blocks on `rows` [total, 9] = clouds of `sizes` points back to back -> (fp1's rows [total, 128], the utils.RaggedLayout).
+        Only level 0 is ragged: sa1 emits npoint centres for every cloud, so sa2, sa3, fp3 and fp2 see uniform [Q, npoint, .] tensors and
+        run as they are; sa1 samples and groups ragged clouds and fp1 searches from ragged fine points.  The graph rules are _backbone's;
+        the mode check is the caller's.  What pointnet_2.forward_tokens_ragged puts the token behind and pointnet_2_seg its head."""
+        who = type(self).__name__
+        self._check_block_modes()
+        _lib.require_gpu(rows, "rows")
+        if rows.dim() != 2 or rows.shape[1] != 9 or rows.dtype != torch.float32 or not rows.is_contiguous():
+            raise _lib.AmpnetError(f"{who}: expected packed rows [total, 9], float32 and contiguous, got {tuple(rows.shape)} "
+                                   f"{rows.dtype}, strides {rows.stride()}")
+        layout = U.ragged_layout(who, rows, sizes)
+        if min(layout.sizes) < self.sa1.npoint:
+            raise _lib.AmpnetError(f"{who}: every cloud needs at least sa1.npoint={self.sa1.npoint} points, cloud "
+                                   f"{layout.sizes.index(min(layout.sizes))} has {min(layout.sizes)} (predict_clouds pads such clouds)")
+        with torch.no_grad():
+            l0_points = rows.detach()
+            l0_xyz = l0_points[:, :3].contiguous()                                             # [total, 3]
+        with contextlib.nullcontext() if self.encoder_grad else torch.no_grad():             # (the caller's grad mode, or none)
+            l1_xyz, l1_points = self.sa1._forward_ragged(l0_xyz, l0_points, layout)            # [Q, 1024, 3], [Q, 1024, 64]
+            l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)
+            l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)
+        with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
+            l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)
+            l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)
+            l0_rows = self.fp1._forward_ragged(l0_xyz, layout, l1_xyz, None, l1_points)        # [total, 128]
+        return l0_rows, layout
+
+    # ---- the fused token path: conv1 and the max as ONE kernel on fp1's rows (pointnet2_utils.token_pool) ---------------------------------
+    def forward_tokens(self, points):
+        """The model as a window encoder on point-major rows: points [Q, N, 9] float32 contiguous GPU -> (tokens [Q, 128], l0_rows
+        [Q, N, 128]): one token per window for a sequence model, per-point local features for a head.  The six blocks as
+        _backbone(points, rows=True) runs them, then pointnet2_utils.token_pool(l0_rows, conv1.weight, conv1.bias): neither the
+        transpose in nor the [Q, 128, N] copy out, and conv1's [Q, 128, N] output is never written.  tokens is forward()'s global_feature
+        up to float32 rounding (another summation order), l0_rows its l0_points transposed, bit for bit.
+        Mode checks, flags and graph rules are _backbone's; conv1 has no BatchNorm, so the call works in every mode the backbone accepts.
+        conv1 is a torch parameter: with grad mode on, tokens carries a graph to conv1 in every model, and with decoder_grad=True both
+        results carry one to the decoder (with encoder_grad=True the whole backbone); a consumer may use either or both, autograd adds the
+        two gradients of l0_rows.  The token kernel is exact fp32, behind precision='bf16' blocks too.  Tie rule: the LOWEST row of a
+        window takes the whole gradient of a channel, where torch.amax (forward()) splits it evenly among equal maxima; equal maxima arise
+        from exact duplicate rows (cyclic padding), and there both rules give the same parameter gradients."""
+        l0_rows, _ = self._backbone(points, rows=True)
+        return token_pool(l0_rows, self.conv1.weight, self.conv1.bias), l0_rows
+
+    def forward_tokens_ragged(self, rows, sizes):
+        """forward_tokens on clouds of UNEQUAL size in one launch sequence: rows [total, 9] float32 contiguous GPU = clouds of `sizes`
+        points back to back, sa1.npoint <= n_i <= 12288 -> (tokens [Q, 128], l0_rows [total, 128]).  The ragged backbone that
+        pointnet_2_seg.forward_ragged runs, followed by the segmented max; in eval mode, cloud by cloud, the token and the rows are the
+        bits of forward_tokens on that cloud alone.  Mode checks, flags and graph rules are forward_tokens'; in train mode (the
+        batch-statistics flags) every BatchNorm runs over all rows of the call."""
+        if self.training and not self.decoder_batch_stats:
+            raise NotImplementedError("pointnet_2 on the HIP path is built for eval mode (BatchNorm running statistics, no backward): "
+                                      "call .eval() first")
+        self._check_bf16()
+        l0_rows, layout = self._backbone_ragged(rows, sizes)
+        return token_pool(l0_rows, self.conv1.weight, self.conv1.bias, sizes=layout), l0_rows
+
 
 class pointnet_2_seg(pointnet_2):
     """pointnet_2 with the classifier the reference carries commented out (pointnetAtt.py:294-296, :318-321) restored: the six blocks,
@@ -582,6 +644,14 @@ class pointnet_2_seg(pointnet_2):
             log_probs = self._head._forward_rows(l0_rows)
         return log_probs, l0_points
 
+    def forward_tokens(self, points):
+        raise NotImplementedError("pointnet_2_seg: conv1 is the first layer of the segmentation head here, not the token's; forward_tokens "
+                                  "and forward_tokens_ragged belong to pointnet_2")
+
+    def forward_tokens_ragged(self, rows, sizes):
+        raise NotImplementedError("pointnet_2_seg: conv1 is the first layer of the segmentation head here, not the token's; forward_tokens "
+                                  "and forward_tokens_ragged belong to pointnet_2")
+
     def predict(self, xyz):
         """xyz [B, 9, N] -> the class of every point, int64 [B, N] (the lowest class among equal logits).  Never a graph."""
         with torch.no_grad():
@@ -620,26 +690,8 @@ class pointnet_2_seg(pointnet_2):
         if any(m.training for m in every):
             raise NotImplementedError("pointnet_2_seg: forward_ragged / predict_ragged / predict_clouds are eval operations: call .eval() "
                                       "first (forward_ragged trains in a model built with the batch-statistics flags)")
-        self._check_block_modes()
-        _lib.require_gpu(rows, "rows")
-        if rows.dim() != 2 or rows.shape[1] != 9 or rows.dtype != torch.float32 or not rows.is_contiguous():
-            raise _lib.AmpnetError(f"pointnet_2_seg: expected packed rows [total, 9], float32 and contiguous, got {tuple(rows.shape)} "
-                                   f"{rows.dtype}, strides {rows.stride()}")
-        layout = U.ragged_layout("pointnet_2_seg", rows, sizes)
-        if min(layout.sizes) < self.sa1.npoint:
-            raise _lib.AmpnetError(f"pointnet_2_seg: every cloud needs at least sa1.npoint={self.sa1.npoint} points, cloud "
-                                   f"{layout.sizes.index(min(layout.sizes))} has {min(layout.sizes)} (predict_clouds pads such clouds)")
-        with torch.no_grad():
-            l0_points = rows.detach()
-            l0_xyz = l0_points[:, :3].contiguous()                                             # [total, 3]
-        with contextlib.nullcontext() if self.encoder_grad else torch.no_grad():             # (the caller's grad mode, or none)
-            l1_xyz, l1_points = self.sa1._forward_ragged(l0_xyz, l0_points, layout)            # [Q, 1024, 3], [Q, 1024, 64]
-            l2_xyz, l2_points = self.sa2._forward_rows(l1_xyz, l1_points)
-            l3_xyz, l3_points = self.sa3._forward_rows(l2_xyz, l2_points)
+        l0_rows = self._backbone_ragged(rows, sizes)[0]
         with torch.enable_grad() if self.decoder_grad and torch.is_grad_enabled() else torch.no_grad():
-            l2_points = self.fp3._forward_rows(l2_xyz, l3_xyz, l2_points, l3_points)
-            l1_points = self.fp2._forward_rows(l1_xyz, l2_xyz, l1_points, l2_points)
-            l0_rows = self.fp1._forward_ragged(l0_xyz, layout, l1_xyz, None, l1_points)        # [total, 128]
             return self._head._forward_rows(l0_rows.unsqueeze(0), want_preds=want_preds)
 
     def forward_ragged(self, rows, sizes):

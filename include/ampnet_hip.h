@@ -664,6 +664,57 @@ int ampnet_sa_all_backward_f32(const float *xyz, int n_clouds, int n, int ld, co
                                const int *cout_host, const float *eps_host, int L, const int32_t *arg, const float *dout, float *dfeats,
                                float *const *grads_host, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the window token of pointnet_2: one linear layer and a segmented max over clouds of unequal size, fused, with its backward (new
+ * symbols within ABI 18: nothing else moved, AMPNET_ABI_VERSION stays 18) -----------------------------------------------------------------
+ * Forward.
+ *   rows                  [total, cin] float32, point-major, 16-byte aligned: the clouds back to back
+ *   cloud_off             [Q + 1] int32 on the DEVICE: cloud q is the rows cloud_off[q] .. cloud_off[q + 1]; cloud_off[0] = 0,
+ *                         cloud_off[Q] = total < 2^31, every cloud holds at least one row (the caller's promise: the table is not read back)
+ *   W, bias               [cout, cin] (16-byte aligned) and [cout] float32 on the device: nn.Conv1d(cin, cout, 1)'s tensors, squeezed
+ *   out                   [Q, cout] float32: out[q, c] = max over the rows r of cloud q of y[r, c] = (W[c, :] . rows[r, :]) + bias[c].
+ *                         No BatchNorm, no ReLU: a maximum below zero stays below zero, the running maximum starts from a row's value
+ *   arg_out               [Q, cout] int32, or NULL: the index INSIDE cloud q of the LOWEST row whose float32 value attains out[q, c], the
+ *                         rule of ampnet_sa_all_forward_f32
+ *   workspace             ampnet_token_pool_forward_workspace_bytes(cin, cout, Q, total) device bytes, 16-byte aligned (0 = the shape is
+ *                         refused, ampnet_last_error says why); contents undefined before and after
+ * Every element of out and arg_out is written.  Non-finite inputs are out of contract.
+ * The value of a row: exact fp32 on v_mfma_f32_32x32x2_f32, whatever the matrix precision is -- neither ampnet_set_matrix_precision nor a
+ * precision scope is consulted.  The accumulator starts at 0 and takes the products rows[r, k] W[c, k] one fused multiply-add at a time, k
+ * in blocks of 8 from 0 upwards and inside a block in the order k0 + 0, + 4, + 1, + 5, + 2, + 6, + 3, + 7 (k-step i < 4 of lane half h takes
+ * k = k0 + 4 h + i, a lane's four weights are 16 contiguous bytes); the bias is added last, one float32 add.  The value is a function of
+ * the row's cin numbers and the weights alone: it does not depend on the row's place in its tile, on its cloud or on the launch.  So the
+ * same rows cut into other clouds give the same y, equal rows tie exactly, and the lowest wins.
+ * Work: a cloud of n rows owns ceil(n / 32) tiles of 32 consecutive rows (a tile never mixes two clouds; the rows past n repeat the tile's
+ * first row).  The tiles of all clouds, in order, are cut into items of G consecutive tiles, G = ceil(ceil((total + 31 Q) / 32) / 4096); a
+ * wave finds an item's first cloud by bisection of the tile prefix sums (computed on the device from cloud_off) and walks its tiles, cloud
+ * after cloud.  A cloud that lies inside one item is finished there; the runs of a cloud that spans several items go as (max, row)
+ * partials to the workspace, and an ordered reduce combines them: ascending rows with a strict > everywhere, no atomics, so two calls
+ * return the same bits.  The weights are staged in LDS once per workgroup when they fit beside the four waves' tiles
+ * (4 (cin + 1) (128 + cout) <= 160 KB: 128 x 128 does, 256 x 256 does not and is read through L2).
+ * Limits (AMPNET_E_ARG otherwise, the message names the entry point and the value): cin and cout multiples of 32 in [32, 256], Q >= 1,
+ * Q <= total <= 2^31 - 1, Q cout <= 2^31 - 1.
+ *
+ * Backward.
+ *   rows, cloud_off, Q, total, W, cin, cout   the forward's arguments
+ *   arg                   [Q, cout] int32, an INPUT: the forward's arg_out (values are clamped into their cloud)
+ *   dout                  [Q, cout] float32
+ *   dx                    [total, cin] out, or NULL: EVERY element is written, zero outside the winners;
+ *                         dx[cloud q's row r, k] = sum over the channels c with arg[q, c] = r, ascending c, of dout[q, c] W[c, k]
+ *   dW                    [cout, cin] out, or NULL: dW[c, k] = sum over q ascending of dout[q, c] rows[cloud q's row arg[q, c], k]
+ *   db                    [cout] out, or NULL: db[c] = sum over q ascending of dout[q, c]
+ *   workspace             ampnet_token_pool_backward_workspace_bytes(cin, cout, Q, total) device bytes (0 = refused)
+ * float32 accumulators: dx and dW are fmaf chains from 0 in the stated order, db plain float32 adds.  No atomics: two calls return the same
+ * bits.  Apart from the zero fill of dx the work is O(Q cout cin) whatever total is.  Tie rule: the LOWEST row takes the whole
+ * gradient, where torch.amax's backward splits it evenly among equal maxima; equal maxima arise from exact duplicate rows (cyclic
+ * padding), and there both rules give the same dW and db.                                                                           */
+size_t ampnet_token_pool_forward_workspace_bytes(int cin, int cout, int Q, long long total);
+int ampnet_token_pool_forward_f32(const float *rows, const int32_t *cloud_off, int Q, long long total, const float *W, const float *bias,
+                                  int cin, int cout, float *out, int32_t *arg_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ampnet_token_pool_backward_workspace_bytes(int cin, int cout, int Q, long long total);
+int ampnet_token_pool_backward_f32(const float *rows, const int32_t *cloud_off, int Q, long long total, const float *W, int cin, int cout,
+                                   const int32_t *arg, const float *dout, float *dx, float *dW, float *db, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
 /* ---- ampnet_sa_forward_f32 and its backward with TRAIN-mode BatchNorm: batch statistics (encoder training; new in ABI 14) -------------
  * Forward.  The arguments of ampnet_sa_forward_f32, and (as in ampnet_fp_train_forward_f32):
  *   params_host           per layer W, b, gamma, beta, running_mean, running_var as before; running_mean and running_var are READ AND WRITTEN
